@@ -16,9 +16,15 @@ the engine's own reset, actions from a ring of 16 pre-generated uniform columns.
 Besides the contract fields the line carries
   roofline     — dominant kernel (the step kernel): algorithmic bytes per launch / average launch
                  duration from HIP events on the launch stream over the timed region, vs 8 TB/s.
+With --full it also carries (each measured in runs of its own, after the timed region):
+  roofline.steady — the same kernel's per-launch time over 480 graph-replayed launches (--steps < 256).
   cpu_baseline — the CPU oracle (C restatement of the Rust reference; the reference itself cannot
                  be built here) timed on this box's host cores on a bounded sample, rank 0, N=1 only.
   extra        — the other BASELINE configs measured after the timed region (not the headline).
+
+--dump-outputs DIR writes what the timed path returned in its last step (observation, reward, done,
+truncated per family; [K][n] tables for --ll-rollout) as float32 .npy files, for output-by-output
+comparisons of two builds: the inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -55,8 +61,14 @@ def parse():
     ap.add_argument("--total-envs", type=int, default=8 << 20, help="node total for --scaling strong (default 8 388 608, BASELINE configs[4])")
     ap.add_argument("--ll-rollout", type=int, default=0, metavar="K",
                     help="LunarLander: step through mgym_rollout, K steps per persistent launch (0: mgym_step); --steps / --warmup are rounded down to multiples of K")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline.steady, cpu_baseline, extra (the other BASELINE configs, "
+                         "rollouts, the mixed batch, the all-gather); off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out extra")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<family>_<name>.npy (float32; "
+                         "a fixed sample of env columns beyond 64 MB in all; rank 0's shard)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0001)
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="rehearse the multi-process launch without a GPU: every rank joins a gloo group, rank 0 prints one JSON line "
@@ -193,11 +205,52 @@ class Stepper:
         if steps % RING:
             self.env.graph_launch(self.tail_graphs[steps % RING])
 
+    def outputs(self):
+        """What a caller of the timed path holds after its last step, on the host: the engine-owned observation
+        [obs_dim][n] and the step's reward / done / truncated [n] (--ll-rollout: the last launch's [K][n] tables)."""
+        out = {"observation": self.env.observation()}
+        last = self.roll_out if self.roll_k else (self.reward, self.done, self.trunc)
+        for name, t in zip(("reward", "done", "truncated"), last):
+            out[name] = t.cpu().numpy()
+        return out
+
     def close(self):
         for g in [self.graph] + list(self.tail_graphs.values()) + ([self.timed[1]] if self.timed else []):
             if g is not None:
                 self.env.graph_destroy(g)
         self.env.close()
+
+
+DUMP_LIMIT = 64 << 20   # bytes of .npy written by --dump-outputs, headers included
+
+
+def dump_outputs(steppers, out_dir, limit=DUMP_LIMIT):
+    """--dump-outputs: every stepper's last outputs as <out_dir>/<family>_<name>.npy in float32 (done / truncated as 0.0 / 1.0).
+    When all of them together would pass `limit`, the same fixed, seeded sample of env columns (the last axis) is written for each
+    array of a family, and <family>_env_index.npy (float64) names the columns kept."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    fams = [(s.name, {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in s.outputs().items()}) for s in steppers]
+    header = 128    # an .npy header of these shapes
+    frac = 1.0
+    if sum(a.nbytes + header for _, arrs in fams for a in arrs.values()) > limit:
+        # a sampled family costs frac x (its arrays + 8 bytes of index per env column), plus one header per file
+        sampled = sum(sum(a.nbytes for a in arrs.values()) + 8 * next(iter(arrs.values())).shape[-1] for _, arrs in fams)
+        frac = 0.99 * (limit - header * sum(len(arrs) + 1 for _, arrs in fams)) / sampled
+    written = []
+    for i, (name, arrs) in enumerate(fams):
+        n = next(iter(arrs.values())).shape[-1]
+        if frac < 1.0:
+            m = max(1, int(n * frac))
+            idx = np.sort(np.random.default_rng(0x5EED0000 + i).choice(n, m, replace=False))
+            arrs = {k: np.ascontiguousarray(v[..., idx]) for k, v in arrs.items()}
+            arrs["env_index"] = idx.astype(np.float64)
+        for k, v in arrs.items():
+            path = os.path.join(out_dir, f"{name}_{k}.npy")
+            np.save(path, v)
+            written.append(os.path.getsize(path))
+    assert sum(written) <= limit, f"--dump-outputs wrote {sum(written)} bytes (limit {limit})"
 
 
 def host_cores():
@@ -417,6 +470,8 @@ def main():
         elapsed, ev_ms = float(t[0]), float(t[1])
     for s in steppers:
         s.env.sync()                  # surfaces any sticky device-side error
+    if args.dump_outputs and rank == 0:
+        dump_outputs(steppers, args.dump_outputs)   # before anything below steps the handles again
 
     total_envs = sum(pop.values()) * world if args.scaling == "weak" else (args.total_envs if args.workload != "mixed" else sum(mg.mixed_population(args.total_envs).values()))
     value = total_envs * args.steps / elapsed
@@ -447,7 +502,7 @@ def main():
                               "avg_launch_us": dur * 1e6,
                               "note": "algorithmic bytes/env-step x envs per launch / HIP-event time per launch; at 1Mi envs the working set "
                                       "(~50 MB) is Infinity-Cache resident, see DESIGN.md for the >256 MiB run"}
-        if args.steps < 256 and lead.launch == "graph":
+        if args.full and args.steps < 256 and lead.launch == "graph":
             # A short timed region (the driver runs --steps 20) starts on an idle stream, so its event interval carries
             # the host's graph-launch latency (10-20 us) and the clock ramp.  Report, beside it and AFTER the timed
             # region, the same kernel's steady per-launch time: HIP events around 30 replays of the 16-step graph.
@@ -467,11 +522,11 @@ def main():
 
     if args.workload == "lunar_lander":
         result["roofline"] = lunar_roofline(n, ev_ms * 1e-3 / args.steps, "_rollout%d" % args.ll_rollout if args.ll_rollout else "")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and (args.workload in ALG_BYTES or args.workload == "lunar_lander"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and (args.workload in ALG_BYTES or args.workload == "lunar_lander"):
         result["cpu_baseline"] = cpu_baseline(args.workload, n, args.seed)
 
     mixed_rec = None
-    if not args.no_extra and args.workload == "cartpole" and args.envs is None:
+    if args.full and not args.no_extra and args.workload == "cartpole" and args.envs is None:
         # BASELINE configs[4] at this N (north_star: "steps/sec reported at 1/2/4/8 GPUs on the 8M-env mixed batch"):
         # 524288 CartPole + 262144 MountainCar + 262144 LunarLander per GPU, measured on EVERY rank after the
         # headline region (never part of `value`).  Every rank reaches both collectives even if its run raised.
@@ -539,7 +594,7 @@ def main():
         else:
             mixed_rec = {"error": m_err or "failed on another rank"}
 
-    if rank == 0 and world == 1 and not args.no_extra and args.workload == "cartpole" and args.envs is None:
+    if args.full and rank == 0 and world == 1 and not args.no_extra and args.workload == "cartpole" and args.envs is None:
         # the other BASELINE configs, measured AFTER the timed region (never the headline `value`)
         extra = {}
         for name, cnt, k in (("mountain_car", 1 << 20, 400), ("mountain_car_cont", 1 << 20, 400), ("lunar_lander", 1 << 18, 128),
@@ -739,7 +794,7 @@ def main():
     if mixed_rec is not None and rank == 0:
         result.setdefault("extra", {})["mixed_configs4_this_n"] = mixed_rec
 
-    if dist is not None and args.workload in ("cartpole", "mixed") and not args.no_extra:
+    if args.full and dist is not None and args.workload in ("cartpole", "mixed") and not args.no_extra:
         # the optional collective: all-gather of the CartPole observation shards into a learner tensor on every
         # rank, RCCL over xGMI; off the step path, reported on its own (rehearsable on one GPU with MGYM_FORCE_DIST=1)
         from modurl_gym_amd.shard import all_gather_observations, all_reduce_episode_count

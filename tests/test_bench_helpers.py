@@ -91,3 +91,51 @@ def test_lunar_roofline_fields():
     assert r["hbm_for_reference"]["frac"] < 0.05
     if r["achieved"] is not None:   # counters present and current
         assert 0.001 < r["frac"] < 0.2 and r["frac"] < r["frac_if_all_64_lanes_counted"]
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    # `bench.py --gpus 1 --steps N --warmup W` measures the headline only; the other figures need --full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+class _FakeStepper:
+    def __init__(self, name, obs_dim, n, rows, seed):
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        self.name = name
+        shape = (rows, n) if rows else (n,)
+        self._out = {"observation": rng.standard_normal((obs_dim, n)).astype(np.float32),
+                     "reward": rng.standard_normal(shape).astype(np.float32),
+                     "done": rng.integers(0, 2, shape).astype(np.uint8), "truncated": rng.integers(0, 2, shape).astype(np.uint8)}
+
+    def outputs(self):
+        return self._out
+
+
+def test_dump_outputs_writes_float_arrays_whole_or_as_one_fixed_sample(tmp_path):
+    import numpy as np
+    steppers = [_FakeStepper("cartpole", 4, 5000, 0, 1), _FakeStepper("lunar_lander", 8, 3000, 16, 2)]
+    bench.dump_outputs(steppers, str(tmp_path / "whole"))
+    for s in steppers:
+        for k, v in s.outputs().items():
+            got = np.load(tmp_path / "whole" / f"{s.name}_{k}.npy")
+            assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    assert not list((tmp_path / "whole").glob("*_env_index.npy"))
+    # over the limit: the same seeded columns for every array of a family, float64 indices beside them, the limit kept
+    limit = 200_000
+    for d in ("a", "b"):
+        bench.dump_outputs(steppers, str(tmp_path / d), limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+    for s in steppers:
+        idx = np.load(tmp_path / "a" / f"{s.name}_env_index.npy")
+        assert idx.dtype == np.float64 and 0 < len(idx) < 5000 and np.all(np.diff(idx) > 0)
+        cols = idx.astype(np.int64)
+        for k, v in s.outputs().items():
+            got = np.load(tmp_path / "a" / f"{s.name}_{k}.npy")
+            assert np.array_equal(got, v[..., cols].astype(np.float32))
+            assert np.array_equal(got, np.load(tmp_path / "b" / f"{s.name}_{k}.npy"))
