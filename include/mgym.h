@@ -159,7 +159,10 @@ int mgym_rollout(mgym_env *env, const void *actions, int32_t K, float *obs_out, 
  * MountainCar (Discrete(3)): same key and the first two counter words, fourth word 0x40000000 + t / 2; env g takes half (t % 2) (low half first)
  * of word (g % 4), h, and the action (3 h) >> 16 — every action within 2^-16 of probability 1/3.  MountainCarContinuous (Box(-1, 1)): fourth
  * word 0x40000000 + t, the top 24 bits u of word (g % 4) give the force u * 2^-23 - 1 (actions_out then holds f32 words).
- * LunarLander: MGYM_ERR_BAD_ARG. */
+ * LunarLander (Discrete(4)): same key and the first two counter words, fourth word 0x40000000 + t / 16; env g takes bits 2 (t % 16) and
+ * 2 (t % 16) + 1 of word (g % 4): action (word >> (2 * (t % 16))) & 3.  t counts the steps of this call (a call of more than 240 steps runs as
+ * several launches; t goes on across them).  Any n_envs; env_id_base a multiple of 4.  A handle that was never reset reports MGYM_ERR_NOT_RESET
+ * (at the next mgym_sync), as mgym_step does.  Reference loop: lunar_lander.rs:919-1167 behind `action_space().sample()`. */
 int mgym_rollout_uniform(mgym_env *env, uint64_t policy_seed, int32_t K, void *actions_out, float *obs_out,
                          float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
 
@@ -170,7 +173,16 @@ int mgym_rollout_uniform(mgym_env *env, uint64_t policy_seed, int32_t K, void *a
  * followed by the bias (5 floats, read during the call).  actions_out ([K][n_envs] uint32, may be NULL) receives the actions taken.
  * MountainCar (Discrete(3), mountain_car.rs:293-330): `policy` = three rows of (w_position, w_velocity, bias), 9 floats; the action is the index of the largest
  * score s_j = (w_j0 * position + w_j1 * velocity) + b_j, the first of equal ones.  MountainCarContinuous: one row, 3 floats; the score itself is the force
- * (actions_out then holds f32 words).  n_envs a multiple of 4.  LunarLander: MGYM_ERR_BAD_ARG (its rollout is a persistent launch of its own, ll_roll.h). */
+ * (actions_out then holds f32 words).  n_envs a multiple of 4.
+ * LunarLander (Discrete(4), lunar_lander.rs:919-1167): `policy` = four rows of (w_j0 .. w_j7, b_j), 36 floats; the score of row j is
+ * s_j = (((((((w_j0*o0 + w_j1*o1) + w_j2*o2) + w_j3*o3) + w_j4*o4) + w_j5*o5) + w_j6*o6) + w_j7*o7) + b_j in f32, in exactly that order, nothing fused;
+ * the action starts as 0 with best = s_0, and row j = 1..3 replaces it when s_j > best (strict): the first of equal scores wins, a NaN score never
+ * replaces an earlier one, and a NaN s_0 gives action 0.  o is the observation the env holds before the step: at the first step of the call the handle's
+ * current observation (mgym_observation), later the one the previous step returned (under MGYM_FLAG_AUTO_RESET, for an env that finished there, its
+ * reset observation).  Any n_envs.  A handle that was never reset reports MGYM_ERR_NOT_RESET (at the next mgym_sync), as mgym_step does.  From
+ * MGYM_LL_ROLLOUT_MIN_K steps up the call is one persistent launch (ll_roll.h) in which each environment's next action is decided where its observation
+ * is produced; below that, above the launch's population limit, or while the stream is being captured it runs as K x (a policy kernel, mgym_step) —
+ * the same words either way. */
 int mgym_rollout_linear(mgym_env *env, const float *policy, int32_t K, void *actions_out, float *obs_out,
                         float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
 

@@ -29,6 +29,7 @@
 #pragma once
 #include "ll_kernel_common.h"
 #include "ll_roll_types.h"
+#include <type_traits>
 
 namespace mgym {
 
@@ -245,6 +246,23 @@ LLD void roll_write_scalars(const LLDev& d, const LLIo& io, uint32_t t, uint32_t
     if (io.done_out) io.done_out[o] = (uint8_t)done;
     if (io.trunc_out) io.trunc_out[o] = 0;  // :1165 truncated: false
 }
+// the action of step t of environment i by the launch's action source (ll_roll_types.h RollPolicy); the next-action words are agent-scope (sc1) accesses,
+// like the records' leading lines on the free-flight path: their stores are complete before the environment's entry is published (vmcnt(0))
+#define RA_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RA_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+struct RollNoPolicy {};   // the table form's (empty) policy argument
+template <int POLICY> using RollPolicyOf = typename std::conditional<POLICY == ROLL_ACT_TABLE, RollNoPolicy, RollPolicy>::type;
+template <int POLICY, class PolT>
+LLD uint32_t roll_action(const LLDev& d, const LLIo& io, const PolT& pol, uint32_t i, uint32_t t) {
+    if constexpr (POLICY == ROLL_ACT_TABLE) return io.act[(uint64_t)t * d.n + i];
+    else if constexpr (POLICY == ROLL_ACT_LINEAR) return RA_LOAD(pol.next + i);
+    else return ll_uniform_action(pol.seed, pol.call, d.env_id_base + i, pol.t0 + t);
+}
+// the action step t has taken, for mgym_rollout_{linear,uniform}'s actions_out (one writer: the wave that finishes the step)
+template <int POLICY, class PolT>
+LLD void roll_write_action(const LLDev& d, const PolT& pol, uint32_t t, uint32_t i, uint32_t a) {
+    if constexpr (POLICY != ROLL_ACT_TABLE) { if (pol.act_out) pol.act_out[(uint64_t)t * d.n + i] = a; }
+}
 
 // where an environment goes after step t has been finished with flag word `flags` (t1 = t + 1):
 //   RESET  finished and auto-reset is on (also when t1 == K: the reset belongs to step t)
@@ -272,10 +290,11 @@ LLD void roll_dispatch(const LLDev& d, const RollQ& q, int route, uint32_t i, ui
 // through the queue — and lanes that fall vacant are refilled from that queue, up to max_lanes on board.  K consecutive touching steps
 // of one environment are the launch's longest chain: this takes the queue hand-over (a wave in free-flight mode looks at the queues once
 // per step) out of every link of it.
-template <int BLK>
+template <int BLK, int POLICY = ROLL_ACT_TABLE>
 __device__ __forceinline__ void roll_contact_batch(const LLDev& d, const LLIo& io, const RollQ& q, int m, ContactLds<BLK>& S, VConstraint* far_lane0, int far_stride,
                                                    uint32_t& overflow, uint32_t& finished, int keep_which, int max_lanes, unsigned long long& n_batches, unsigned long long& n_lanes,
-                                                   bool resume_toi /* the entries stand at a sub-step (RQ_TOI) */, int toi_budget /* sub-steps this visit takes (< 0: all) */) {
+                                                   bool resume_toi /* the entries stand at a sub-step (RQ_TOI) */, int toi_budget /* sub-steps this visit takes (< 0: all) */,
+                                                   const RollPolicyOf<POLICY>& pol) {
     static_assert(BLK <= 32, "rollout: World records in LDS");
     constexpr int kThreads = ll_contact_threads(BLK);
     const PolyTab& tab = S.tab;
@@ -306,7 +325,7 @@ __device__ __forceinline__ void roll_contact_batch(const LLDev& d, const LLIo& i
         }
         if (q.debug & 16u) { if (have && e.step == 0xfffffff0u) atomicOr(d.err, DEV_ERR_INTERNAL); rq_retire(q, have); return; }   // (diagnosis: ... and the load)
         if (have) {
-            action = io.act[(uint64_t)t * d.n + i];
+            action = roll_action<POLICY>(d, io, pol, i, t);   // (LINEAR: a step that comes back unfinished still finds its own action: the word moves on when it ends)
             if (resume_toi) {   // world.step is past its island solve and its time-of-impact evaluations: on with SolveTOI
             } else if (w.resume) {   // the free-flight path has taken this step up to the end of the island solve (ll_free.h)
                 ll_resume_after_island(w);
@@ -375,6 +394,8 @@ __device__ __forceinline__ void roll_contact_batch(const LLDev& d, const LLIo& i
             route = (q.debug & (32u | 128u)) ? ROLL_RETIRE : roll_route(d, q, flags, (q.debug & 256u) ? 0u : done, t + 1u);
             if (!(q.debug & 64u)) roll_write_scalars(d, io, t, i, reward, done);
             if (route != ROLL_TO_RESET && !(q.debug & 64u)) roll_write_obs(d, io, t, i, state, t + 1u == q.K);   // (a finished env's observation comes from its reset)
+            roll_write_action<POLICY>(d, pol, t, i, action);
+            if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route != ROLL_TO_RESET && t + 1u < q.K) RA_STORE(pol.next + i, ll_linear_action(pol.lin, state)); }   // step t + 1's, from this observation
             is_done = done != 0u;
             overflow |= w.overflow;
         }
@@ -432,8 +453,8 @@ __device__ __forceinline__ void roll_contact_batch(const LLDev& d, const LLIo& i
 
 // ---- reset batch: reset() of up to BLK finished environments — the scene (lunar_lander.rs:727-908), then the implicit step(0) on the
 // free-flight path (:911-916; a fresh scene spawns far above the highest terrain vertex) — as ll_reset_pass does for mgym_step
-template <int BLK>
-__device__ __forceinline__ void roll_reset_batch(const LLDev& d, const LLIo& io, const RollQ& q, int m, ContactLds<BLK>& S) {
+template <int BLK, int POLICY = ROLL_ACT_TABLE>
+__device__ __forceinline__ void roll_reset_batch(const LLDev& d, const LLIo& io, const RollQ& q, int m, ContactLds<BLK>& S, const RollPolicyOf<POLICY>& pol) {
     const PolyTab& tab = S.tab;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const bool have = (int)threadIdx.x < BLK && (int)threadIdx.x < m && S.late[threadIdx.x] != 0xffffffffu;
@@ -462,6 +483,7 @@ __device__ __forceinline__ void roll_reset_batch(const LLDev& d, const LLIo& io,
             ll_free_store(d, i, f, e);
             roll_write_obs(d, io, t1 - 1u, i, state, t1 == q.K);
             route = t1 >= q.K ? ROLL_RETIRE : ROLL_TO_FREE;
+            if constexpr (POLICY == ROLL_ACT_LINEAR) { if (t1 < q.K) RA_STORE(pol.next + i, ll_linear_action(pol.lin, state)); }   // step t1's, from the reset observation
         } else {
             atomicOr(d.err, DEV_ERR_INTERNAL);   // (cannot happen: see above) — the environment is dropped from the launch, loudly
             route = ROLL_RETIRE;
@@ -544,8 +566,10 @@ static_assert(ROLL_TO_CONTACT == ROLL_TO_FREE + RQ_CONTACT && ROLL_TO_RESET == R
 // the batch — outside this function, so that the slots' registers are dead by then)
 // HELPER (ll_rollout_free_kernel): the wave never takes a batch of the contact path — the function returns 0 only.  LDS: anything with `tab` and `late`.
 struct RollFreeLds { PolyTab tab; uint32_t late[64 * 4]; };
-template <int BLK, bool HELPER = false, class LDS = ContactLds<BLK>>
-__device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, const RollQ& q, const __amdgpu_buffer_rsrc_t rs, LDS& S, uint32_t& finished, RollStat& st) {
+template <int BLK, bool HELPER = false, class LDS = ContactLds<BLK>, int POLICY = ROLL_ACT_TABLE>
+__device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, const RollQ& q, const __amdgpu_buffer_rsrc_t rs, LDS& S, uint32_t& finished, RollStat& st,
+                                              const RollPolicyOf<POLICY>& pol) {
+    static_assert(!HELPER || POLICY == ROLL_ACT_TABLE, "policy rollouts run without the helper waves");
     const int lane = threadIdx.x & 63;
     const unsigned long long below = (1ull << lane) - 1ull;
     const PolyTab& tab = S.tab;
@@ -565,7 +589,8 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
         roll_unpack(d, r, X.f, X.e);
         X.seq_word = r.w[C_SEQ];
         X.have = true; X.fresh = true;
-        X.act = io.act[(uint64_t)X.t * d.n + X.i];
+        if constexpr (POLICY == ROLL_ACT_TABLE) X.act = io.act[(uint64_t)X.t * d.n + X.i];
+        else X.act = roll_action<POLICY>(d, io, pol, X.i, X.t);
     };
     // take the entries at ring positions [h, h + m) into the vacant slots (slot order: all lanes' first, then all lanes' second): slots -> records
     // (the one exposed round trip of a refill)
@@ -604,6 +629,7 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                 RollRec r;
                 roll_pack_store(r, X.f, X.e, X.f.flags, X.seq_word);
                 roll_rec_store(rs, X.i, r);
+                if constexpr (POLICY == ROLL_ACT_LINEAR) RA_STORE(pol.next + X.i, X.act);   // decided in the registers (a fresh one's word is still in memory)
             }
             Pz.route = ROLL_TO_FREE; Pz.ent = (X.t << 24) | X.i;
             X.have = false;
@@ -701,7 +727,13 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                 if (how == FREE_DONE) {
                     const uint32_t flags = roll_flags_after_step(X.f, X.e);
                     const int route = roll_route(d, q, flags, done, X.t + 1u);
-                    if (route == ROLL_TO_FREE) X.act = io.act[(uint64_t)(X.t + 1u) * d.n + X.i];   // stays on board: next step's action, ahead of this step's stores
+                    roll_write_action<POLICY>(d, pol, X.t, X.i, X.act);
+                    uint32_t lin_next = 0u;   // LINEAR: step t + 1's action, from this step's observation (straight from the registers)
+                    if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route == ROLL_TO_FREE || route == ROLL_TO_CONTACT || route == ROLL_TO_LIGHT) lin_next = ll_linear_action(pol.lin, state); }
+                    if (route == ROLL_TO_FREE) {   // stays on board: next step's action, ahead of this step's stores
+                        if constexpr (POLICY == ROLL_ACT_LINEAR) X.act = lin_next;
+                        else X.act = roll_action<POLICY>(d, io, pol, X.i, X.t + 1u);
+                    }
                     roll_write_scalars(d, io, X.t, X.i, reward, done);
                     if (route != ROLL_TO_RESET) roll_write_obs(d, io, X.t, X.i, state, X.t + 1u == q.K);
                     is_done = done != 0u;
@@ -714,6 +746,7 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                         RollRec r;
                         roll_pack_store(r, X.f, X.e, flags, X.seq_word);
                         roll_rec_store(rs, X.i, r);
+                        if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route == ROLL_TO_CONTACT || route == ROLL_TO_LIGHT) RA_STORE(pol.next + X.i, lin_next); }
                         P[z].route = route; P[z].ent = (X.t << 24) | X.i;
                         X.have = false;
                     }
@@ -732,6 +765,7 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                     for (int b = 0; b < 3; ++b)
                         __builtin_amdgcn_raw_buffer_store_b128(ll_u32x4{as_u32(X.f.b[b].sw.c0.x), as_u32(X.f.b[b].sw.c0.y), as_u32(X.f.b[b].sw.a0), as_u32(0.0f)}, rs, off + 16u * b, 0, 16);
                     __builtin_amdgcn_raw_buffer_store_b128(ll_u32x4{as_u32(0.0f), 0u, 0u, 0u}, rs, off + 48u, 0, 16);
+                    if constexpr (POLICY == ROLL_ACT_LINEAR) RA_STORE(pol.next + X.i, X.act);   // the contact path finishes step t with the same action
                     P[z].route = ROLL_TO_LIGHT; P[z].ent = (X.t << 24) | X.i;   // same step index: the step is not finished
                     X.have = false;
                 }
@@ -789,9 +823,16 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
 }
 
 // ---- the launch ----
-template <int BLK>
+// POLICY: the action source (ll_roll_types.h).  ROLL_ACT_TABLE (mgym_rollout) takes no fourth argument — its kernel is the same code as before the
+// policy forms existed; ROLL_ACT_LINEAR / ROLL_ACT_UNIFORM (mgym_rollout_linear / _uniform) take one RollPolicy by value (the weights travel in the
+// kernel arguments: wave-uniform, scalar loads).
+LLD RollNoPolicy roll_policy_arg() { return RollNoPolicy{}; }
+LLD RollPolicy roll_policy_arg(const RollPolicy& p) { return p; }
+template <int BLK, int POLICY = ROLL_ACT_TABLE, class... Pol>
 __global__ void __launch_bounds__(64) LL_CONTACT_ATTR
-ll_rollout_kernel(LLDev d, LLIo io, RollQ q) {
+ll_rollout_kernel(LLDev d, LLIo io, RollQ q, Pol... pol_arg) {
+    static_assert((POLICY == ROLL_ACT_TABLE) == (sizeof...(Pol) == 0), "a policy rollout takes one RollPolicy, the table form none");
+    const RollPolicyOf<POLICY> pol = roll_policy_arg(pol_arg...);
     __shared__ ContactLds<BLK> S;
     const int lane = threadIdx.x & 63;
     uint32_t overflow = 0u, finished = 0u;
@@ -826,12 +867,20 @@ ll_rollout_kernel(LLDev d, LLIo io, RollQ q) {
                     if (io.rew) io.rew[o] = 0.0f;
                     if (io.done_out) io.done_out[o] = 0;
                     if (io.trunc_out) io.trunc_out[o] = 0;
+                    roll_write_action<POLICY>(d, pol, t, (uint32_t)i, 0u);
                 }
                 route = ROLL_RETIRE;
             } else {
                 route = ll_free_eligible(flags) ? ROLL_TO_FREE : (flags & F_TOUCHING) ? ROLL_TO_CONTACT : ROLL_TO_LIGHT;
+                if constexpr (POLICY == ROLL_ACT_LINEAR) {   // step 0's action, from the handle's observation (mgym_observation)
+                    float o[8];
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) o[c] = d.obs[(uint64_t)c * d.n_pad + i];
+                    RA_STORE(pol.next + i, ll_linear_action(pol.lin, o));
+                }
             }
         }
+        if constexpr (POLICY == ROLL_ACT_LINEAR) rq_drain();   // the next-action words are stored before the entries are published
         roll_dispatch(d, q, route, (uint32_t)i, 0u);
     }
     st.v[RS_T_SEED] = (unsigned long long)(wall_clock64() - t_begin);
@@ -861,7 +910,7 @@ ll_rollout_kernel(LLDev d, LLIo io, RollQ q) {
         if (which == RQ_FREE && !(q.debug & 2u)) {
             const long long tf0 = wall_clock64();
             trace(RT_FREE);
-            m = roll_free_mode<BLK>(d, io, q, rs, S, finished, st);   // -> a contact batch it has taken (in S.late), or 0
+            m = roll_free_mode<BLK, false, ContactLds<BLK>, POLICY>(d, io, q, rs, S, finished, st, pol);   // -> a contact batch it has taken (in S.late), or 0
             st.v[RS_T_FREE] += (unsigned long long)(wall_clock64() - tf0);
             idle_since = -1;
             if (m == 0) { st.v[RS_N_MAIN] += 1ull; continue; }
@@ -878,14 +927,14 @@ ll_rollout_kernel(LLDev d, LLIo io, RollQ q) {
         if (which >= 0) {
             const long long tb0 = wall_clock64();
             trace(which == RQ_RESET ? RT_RESET : which == RQ_LIGHT ? RT_LIGHT : which == RQ_TOI ? RT_TOI : RT_CONTACT);
-            if (which == RQ_RESET) roll_reset_batch<BLK>(d, io, q, m, S);
+            if (which == RQ_RESET) roll_reset_batch<BLK, POLICY>(d, io, q, m, S, pol);
             else {   // ONE call site for the contact path's three kinds of batch (the body is large)
                 const int keep = which == RQ_LIGHT ? ((q.keep & 2u) ? RQ_LIGHT : -1) : (which == RQ_CONTACT && (q.keep & 1u)) ? RQ_CONTACT : -1;
                 const int lanes_max = which == RQ_CONTACT ? heavy_lanes : tail ? (int)q.tail_lanes : BLK;
                 const int budget = which == RQ_TOI ? ((q.toi_split & 4u) ? 1 : -1) : (which == RQ_LIGHT ? (q.toi_split & 1u) : which == RQ_CONTACT ? (q.toi_split & 2u) : 0u) ? 0 : -1;
                 unsigned long long& nb = which == RQ_LIGHT ? st.v[RS_N_LIGHT_BATCHES] : which == RQ_TOI ? st.v[RS_N_TOI_BATCHES] : st.v[RS_N_CONTACT_BATCHES];
                 unsigned long long& nl = which == RQ_LIGHT ? st.v[RS_N_LIGHT_LANES] : which == RQ_TOI ? st.v[RS_N_TOI_LANES] : st.v[RS_N_CONTACT_LANES];
-                roll_contact_batch<BLK>(d, io, q, m, S, far_lane0, far_stride, overflow, finished, keep, lanes_max, nb, nl, which == RQ_TOI, budget);   // (diagnosis 2: free-flight entries come here too)
+                roll_contact_batch<BLK, POLICY>(d, io, q, m, S, far_lane0, far_stride, overflow, finished, keep, lanes_max, nb, nl, which == RQ_TOI, budget, pol);   // (diagnosis 2: free-flight entries come here too)
             }
             __syncthreads();
             const unsigned long long tb = (unsigned long long)(wall_clock64() - tb0);
@@ -939,7 +988,7 @@ ll_rollout_free_kernel(LLDev d, LLIo io, RollQ q) {
         if (live == 0u || rq_aborted(q)) break;
         if (wall_clock64() - t_begin > 4 * kRollTimeoutTicks) break;   // (never the one to abort: the main waves finish the launch without it)
         if (avail >= (int)q.helper_min) {
-            roll_free_mode<BLK, true, RollFreeLds>(d, io, q, rs, S, finished, st);
+            roll_free_mode<BLK, true, RollFreeLds>(d, io, q, rs, S, finished, st, RollNoPolicy{});
             continue;
         }
         __builtin_amdgcn_s_sleep(64);

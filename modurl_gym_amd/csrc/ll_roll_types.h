@@ -2,6 +2,7 @@
 // (lunar_lander.hip) and the kernels (ll_roll.hip) share.
 #pragma once
 #include <stdint.h>
+#include "ll_policy.h"
 
 namespace mgym {
 
@@ -67,6 +68,22 @@ constexpr uint32_t kRollEnvMask = 0xffffffu;
 // round stood still for ~3 s in the middle of its register-only sweeps — whole-GPU, every phase of every wave 50-150 x longer — and the 3 s bound of the time turned that
 // stall into an abort; profiles/r04_lunarlander/rollout_stall_record.txt).
 constexpr long long kRollTimeoutTicks = 12000000000ll;
+
+// Where a launch takes the action of step t of environment i from (the action-source parameter of ll_rollout_kernel):
+//   TABLE    io.act[t][i] (mgym_rollout)
+//   LINEAR   next[i], the engine-owned "next action" word: written where the observation the action depends on is produced (the end of step t - 1 on the
+//            free-flight path, in a contact-path batch or in a reset batch; for t = 0 the seed phase, from the handle's observation), before the release
+//            that publishes the environment; a free-flight resident keeps it in a register (mgym_rollout_linear)
+//   UNIFORM  a pure function of (global id, call, t0 + t): ll_uniform_action (mgym_rollout_uniform)
+enum { ROLL_ACT_TABLE = 0, ROLL_ACT_LINEAR = 1, ROLL_ACT_UNIFORM = 2 };
+struct RollPolicy {
+    LLLinearPolicy lin;
+    uint32_t* next;      // LINEAR: [n] next action words
+    uint32_t* act_out;   // [K][n] actions taken (this launch's slice), or null
+    uint64_t seed;       // UNIFORM: policy seed and the handle's count of earlier mgym_rollout_uniform calls
+    uint32_t call;
+    uint32_t t0;         // step of the call this launch starts at (a call of more than kRollMaxK steps is split)
+};
 
 
 }  // namespace mgym

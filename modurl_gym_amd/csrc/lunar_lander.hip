@@ -725,6 +725,27 @@ void ll_rollout_ring_init(hipStream_t s, const RollQ& q);
 void ll_rollout_begin(hipStream_t s, const RollQ& q, uint32_t n);
 void ll_rollout_launch(hipStream_t s, unsigned grid, const LLDev& d, const LLIo& io, const RollQ& q);
 void ll_rollout_helper_launch(hipStream_t s, unsigned grid, const LLDev& d, const LLIo& io, const RollQ& q);
+int ll_rollout_policy_blocks_per_cu(int* per_cu);
+void ll_rollout_policy_launch(hipStream_t s, unsigned grid, const LLDev& d, const LLIo& io, const RollQ& q, const RollPolicy& pol, int policy);
+
+// The K-step form of mgym_rollout_linear / mgym_rollout_uniform (below the persistent launch's minimum K, above its population limit, with
+// MGYM_LL_ROLLOUT=0, and while the stream is being captured): before each step() this kernel writes the step's action column — from the observation
+// the environment holds (ll_linear_action on the [8][n_pad] observation columns) or from the policy stream (ll_uniform_action) — into actions_out[t]
+// or the engine's [n] next-action words.  The weights are a kernel argument, so a captured graph carries them.
+template <int POLICY>
+__global__ void __launch_bounds__(256) ll_policy_kernel(const float* __restrict__ obs, uint64_t n, uint64_t n_pad, uint64_t env_id_base, RollPolicy pol, uint32_t t,
+                                                        uint32_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (POLICY == ROLL_ACT_LINEAR) {
+        float o[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) o[c] = obs[(uint64_t)c * n_pad + i];
+        out[i] = ll_linear_action(pol.lin, o);
+    } else {
+        out[i] = ll_uniform_action(pol.seed, pol.call, env_id_base + i, t);
+    }
+}
 
 // Staged resets.  The state an env has after reset() — scene, implicit step(0), observation — is a pure function of
 // (seed, env id, episode counter), so it does not have to be computed when the episode ends, on the critical path of
@@ -1004,7 +1025,10 @@ struct LunarLanderEnv final : Env {
     void* roll_vc_far = nullptr;
     RollQ rq{};
     unsigned roll_grid = 0;
+    unsigned roll_policy_grid = 0;      // waves of the policy forms' persistent launch (no helper waves; at most roll_grid: the far workspace is sized for that)
     void* roll_trace = nullptr;
+    uint32_t* next_act = nullptr;       // [n_pad] mgym_rollout_linear: the next action of every environment (persistent launch) / the K-step form's action column
+    uint32_t policy_calls = 0;          // mgym_rollout_uniform calls so far (Philox counter word of the policy stream)
 
     ~LunarLanderEnv() override {
         if (base) (void)hipFree(base);
@@ -1016,6 +1040,7 @@ struct LunarLanderEnv final : Env {
         if (roll_ctl) (void)hipFree(roll_ctl);
         if (roll_vc_far) (void)hipFree(roll_vc_far);
         if (roll_trace) (void)hipFree(roll_trace);
+        if (next_act) (void)hipFree(next_act);
         if (aux) (void)hipStreamDestroy(aux);
         if (env_class) (void)hipFree(env_class);
         if (aux2) { (void)hipStreamSynchronize(aux2); (void)hipStreamDestroy(aux2); }
@@ -1056,6 +1081,8 @@ struct LunarLanderEnv final : Env {
         MGYM_HIP(hipMemsetAsync(obs_base, 0, (size_t)8 * n_pad * sizeof(float), stream));
         dev.st = static_cast<uint32_t*>(base);
         dev.obs = static_cast<float*>(obs_base);
+        MGYM_HIP(hipMalloc((void**)&next_act, (size_t)n_pad * sizeof(uint32_t)));
+        MGYM_HIP(hipMemsetAsync(next_act, 0, (size_t)n_pad * sizeof(uint32_t), stream));
         MGYM_HIP(hipMalloc(&work_base, (size_t)(L_LISTS * n_pad + 64) * sizeof(uint32_t)));
         MGYM_HIP(hipMemsetAsync(work_base, 0, (size_t)(L_LISTS * n_pad + 64) * sizeof(uint32_t), stream));
         dev.work_count = static_cast<uint32_t*>(work_base);
@@ -1198,6 +1225,14 @@ struct LunarLanderEnv final : Env {
             if (g > need) g = need;
             if (g < 1) g = 1;
             roll_grid = (unsigned)g;
+            {   // the policy forms: as many waves as are resident at once without helper waves, capped like the table form's
+                int pcu = 0;
+                if (ll_rollout_policy_blocks_per_cu(&pcu) != MGYM_OK) return MGYM_ERR_HIP;
+                uint64_t pg = (uint64_t)(pcu < 1 ? 1 : pcu) * (uint64_t)prop.multiProcessorCount;
+                if (pg > need) pg = need;
+                if (pg > roll_grid) pg = roll_grid;
+                roll_policy_grid = (unsigned)(pg < 1 ? 1 : pg);
+            }
             const size_t per_lane = (size_t)(kSolverCap - vc_near_limit);
             MGYM_HIP(hipMalloc(&roll_vc_far, per_lane * (size_t)roll_grid * 32 * sizeof(VConstraint)));
             if (getenv("MGYM_LL_ROLL_TRACE")) {   // diagnosis: what every wave did when (written to that file after each launch; synchronises)
@@ -1231,6 +1266,11 @@ struct LunarLanderEnv final : Env {
                 MGYM_HIP(hipStreamWaitEvent(stream, ev_join, 0));
             }
         }
+        return rollout_finish(K);
+    }
+    // after the launches of a rollout: diagnosis output, and what the launches have changed behind the step's back
+    int rollout_finish(int K) {
+        int st = MGYM_OK;
         if (roll_trace) {
             std::vector<unsigned long long> h((size_t)roll_grid * kRollTraceLen);
             MGYM_HIP(hipStreamSynchronize(stream));
@@ -1260,6 +1300,57 @@ struct LunarLanderEnv final : Env {
         if (fused_tail) { st = rebuild_list(); if (st != MGYM_OK) return st; }
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
+    }
+    // mgym_rollout_linear / mgym_rollout_uniform: the persistent launch with the action source `policy` (ll_roll.h), or K x (ll_policy_kernel, step())
+    int policy_rollout(int policy, RollPolicy pol, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
+        uint32_t* ao = static_cast<uint32_t*>(actions_out);
+        pol.next = next_act;
+        if (!roll_enabled || K < roll_min_k || capturing()) {
+            const unsigned g = (unsigned)((n + 255) / 256);
+            for (int t = 0; t < K; ++t) {
+                uint32_t* a = ao ? ao + (size_t)t * n : next_act;
+                if (policy == ROLL_ACT_LINEAR) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_LINEAR>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
+                else hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_UNIFORM>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
+                MGYM_HIP(hipGetLastError());
+                int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
+                              trunc ? trunc + (size_t)t * n : nullptr);
+                if (st != MGYM_OK) return st;
+            }
+            return MGYM_OK;
+        }
+        int st = join_helpers();
+        if (st != MGYM_OK) return st;
+        LLDev rd = dev; rd.split = 0;
+        rd.vc_far = static_cast<VConstraint*>(roll_vc_far); rd.vc_far_late = rd.vc_far;
+        for (int k0 = 0; k0 < K; k0 += (int)kRollMaxK) {
+            const int kc = K - k0 < (int)kRollMaxK ? K - k0 : (int)kRollMaxK;
+            LLIo io{nullptr, obs_out ? obs_out + (size_t)k0 * 8 * n : nullptr, reward ? reward + (size_t)k0 * n : nullptr,
+                    done ? done + (size_t)k0 * n : nullptr, trunc ? trunc + (size_t)k0 * n : nullptr};
+            RollPolicy p = pol;
+            p.t0 = (uint32_t)k0;
+            p.act_out = ao ? ao + (size_t)k0 * n : nullptr;
+            RollQ q = rq; q.K = (uint32_t)kc;
+            if (roll_trace) MGYM_HIP(hipMemsetAsync(roll_trace, 0, (size_t)roll_grid * kRollTraceLen * sizeof(unsigned long long), stream));
+            ll_rollout_begin(stream, q, (uint32_t)n);
+            ll_rollout_policy_launch(stream, roll_policy_grid, rd, io, q, p, policy);   // (never with the free-flight helper waves)
+        }
+        return rollout_finish(K);
+    }
+    int rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        if (n == 0 || K == 0) return MGYM_OK;
+        RollPolicy pol{};
+        pol.seed = policy_seed;
+        pol.call = policy_calls++;
+        return policy_rollout(ROLL_ACT_UNIFORM, pol, K, actions_out, obs_out, reward, done, trunc);
+    }
+    int rollout_linear(const float* policy, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        if (n == 0 || K == 0) return MGYM_OK;
+        RollPolicy pol{};
+        for (int j = 0; j < 4; ++j) {   // policy: 4 rows of (w_j0 .. w_j7, b_j)
+            for (int c = 0; c < 8; ++c) pol.lin.w[j][c] = policy[9 * j + c];
+            pol.lin.b[j] = policy[9 * j + 8];
+        }
+        return policy_rollout(ROLL_ACT_LINEAR, pol, K, actions_out, obs_out, reward, done, trunc);
     }
     bool staging() const { return staged && dev.disp == nullptr; }  // (a dispersion override would be baked into prepared states)
     bool capturing() const {

@@ -44,6 +44,10 @@ class BadConfigError(MgymError, ValueError):
     """assert!(-12.0 < gravity && gravity < 0.0) — lunar_lander.rs:292-296"""
 
 
+class PolicyShapeError(MgymError, ValueError):
+    """rollout_linear_device: the policy does not hold the number of floats the family takes (status ERR_BAD_ARG)"""
+
+
 _EXC = {L.ERR_INVALID_ACTION: InvalidActionError, L.ERR_NOT_RESET: NotResetError, L.ERR_BAD_CONFIG: BadConfigError}
 
 
@@ -180,17 +184,20 @@ class VecEnv:
                                       _ptr(trunc_out)))
 
     def rollout_uniform_device(self, policy_seed, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
-        """K fused steps under the on-device uniform random policy (mgym_rollout_uniform; CartPole, MountainCar, MountainCarContinuous)."""
+        """K fused steps under the on-device uniform random policy (mgym_rollout_uniform; every family — include/mgym.h documents the draws)."""
         _check(self._lib.mgym_rollout_uniform(self._h, int(policy_seed), int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out),
                                               _ptr(done_out), _ptr(trunc_out)))
 
     def rollout_linear_device(self, policy, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device linear policy (mgym_rollout_linear): policy = obs_dim weights + bias (CartPole: action 1 if the score is
-        positive; MountainCarContinuous: the score is the force), or one such row per action (MountainCar: the index of the largest score).  Host floats."""
-        n_pol = 3 * (self.obs_dim + 1) if self.kind == L.MOUNTAINCAR else self.obs_dim + 1   # MountainCar: a row of (weights, bias) per action
+        positive; MountainCarContinuous: the score is the force), or one such row per action (MountainCar: 3 rows, LunarLander: 4 rows of 8 weights + bias;
+        the index of the largest score, the first of equal ones).  Host floats.  A policy of the wrong length raises PolicyShapeError (an MgymError with
+        status ERR_BAD_ARG and a ValueError)."""
+        rows = {L.MOUNTAINCAR: 3, L.LUNARLANDER: 4}.get(self.kind, 1)   # a row of (weights, bias) per action for the argmax families
+        n_pol = rows * (self.obs_dim + 1)
         pol_in = np.asarray(policy, np.float32).ravel()
         if pol_in.size != n_pol:
-            raise ValueError(f"policy must hold {n_pol} floats for this family, got {pol_in.size}")
+            raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {n_pol} floats for this family, got {pol_in.size}")
         pol = (C.c_float * n_pol)(*[float(v) for v in pol_in])
         _check(self._lib.mgym_rollout_linear(self._h, pol, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out),
                                              _ptr(trunc_out)))

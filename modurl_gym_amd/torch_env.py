@@ -131,6 +131,36 @@ class TorchVecEnv:
         self.env.rollout_device(a, K, obs, rew, done, trunc)
         return obs, rew, done.view(torch.bool), trunc.view(torch.bool)
 
+    def _policy_outputs(self, K):
+        torch = self._torch
+        act = torch.empty((K, self.n), dtype=torch.float32 if self.action_is_float else torch.int32, device=self.device)
+        obs = torch.empty((K, self.obs_dim, self.n), dtype=torch.float32, device=self.device)
+        rew = torch.empty((K, self.n), dtype=torch.float32, device=self.device)
+        done = torch.empty((K, self.n), dtype=torch.uint8, device=self.device)
+        trunc = torch.empty((K, self.n), dtype=torch.uint8, device=self.device)
+        return act, obs, rew, done, trunc
+
+    def rollout_linear(self, policy, K):
+        """K fused steps under the on-device linear policy (mgym_rollout_linear; `policy`: host floats or a tensor, the layout
+        VecEnv.rollout_linear_device documents): returns (actions [K, n], obs [K, obs_dim, n], reward [K, n], done [K, n], truncated [K, n])
+        as fresh tensors, stream-ordered on torch's current stream (actions int32, float32 for MountainCarContinuous)."""
+        self._bind_stream()
+        if isinstance(policy, self._torch.Tensor):
+            policy = policy.detach().to("cpu", self._torch.float32).numpy()   # (the weights are read on the host, during the call)
+        K = int(K)
+        act, obs, rew, done, trunc = self._policy_outputs(K)
+        self.env.rollout_linear_device(policy, K, act, obs, rew, done, trunc)
+        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+
+    def rollout_uniform(self, seed, K):
+        """K fused steps under the on-device uniform random policy (mgym_rollout_uniform, include/mgym.h): returns (actions, obs, reward,
+        done, truncated) like rollout_linear."""
+        self._bind_stream()
+        K = int(K)
+        act, obs, rew, done, trunc = self._policy_outputs(K)
+        self.env.rollout_uniform_device(int(seed), K, act, obs, rew, done, trunc)
+        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+
     def observation_view(self):
         """Zero-copy [obs_dim, n] tensor over the engine-owned observation columns (column stride n_pad)."""
         ptr, stride = self.env.observation_device()

@@ -143,9 +143,9 @@ impl VecGym {
     }
 
     /// K fused steps under an on-device linear policy (`mgym_rollout_linear`): the loop `let a = policy(&obs); env.step(a)` of
-    /// cartpole.rs:251-348 / mountain_car.rs:293-330 without leaving the GPU.  `policy`: CartPole 4 weights + bias (action 1 if the score
-    /// is positive); MountainCar three rows of (w_position, w_velocity, bias), the action is the index of the largest score;
-    /// MountainCarContinuous one such row, the score is the force.
+    /// cartpole.rs:251-348 / mountain_car.rs:293-330 / lunar_lander.rs:919-1167 without leaving the GPU.  `policy`: CartPole 4 weights + bias
+    /// (action 1 if the score is positive); MountainCar three rows of (w_position, w_velocity, bias), LunarLander four rows of (w_0 .. w_7, bias):
+    /// the action is the index of the largest score, the first of equal ones; MountainCarContinuous one row, the score is the force.
     /// # Safety
     /// the output pointers are device pointers of `[K][n]` (`[K][obs_dim][n]` for `obs`) elements, or null.
     pub unsafe fn rollout_linear(
@@ -158,13 +158,14 @@ impl VecGym {
         done: *mut u8,
         truncated: *mut u8,
     ) -> Result<(), MgymError> {
-        let want: usize = if self.cfg.kind == MGYM_MOUNTAINCAR { 9 } else { (self.spec.obs_dim + 1) as usize };
+        let rows: usize = if self.cfg.kind == MGYM_MOUNTAINCAR { 3 } else if self.cfg.kind == MGYM_LUNARLANDER { 4 } else { 1 };
+        let want: usize = rows * (self.spec.obs_dim + 1) as usize;
         if policy.len() != want {
             return Err(MgymError { status: MGYM_ERR_BAD_ARG, message: format!("rollout_linear: {} policy floats for this family, got {}", want, policy.len()) });
         }
         check(unsafe { mgym_rollout_linear(self.env, policy.as_ptr(), k, actions_out, obs, reward, done, truncated) })
     }
-    /// K fused steps under the on-device uniform random policy (`mgym_rollout_uniform`; CartPole, MountainCar, MountainCarContinuous): no action table.
+    /// K fused steps under the on-device uniform random policy (`mgym_rollout_uniform`; every family, the draws as `include/mgym.h` documents them): no action table.
     /// `actions_out` (`[K][n]` u32, may be null) receives the drawn actions.
     #[allow(clippy::too_many_arguments)]
     pub fn rollout_uniform(
