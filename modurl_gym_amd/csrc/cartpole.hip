@@ -26,7 +26,8 @@
 // (~4.5 % per step under a random policy) but nearly every WAVE holds one, so resetting in place would make
 // every wave pay Philox4x32-10 (quarter-rate integer multiplies) four times over.  Instead each wave
 // compacts its finished envs with __ballot + popcount prefix sums into a wave-private LDS list (no block
-// barrier, no atomics), the wave's first lanes draw all new states in ONE pass, owners read theirs back.
+// barrier, no atomics), the wave's first lanes draw all new states in ONE pass (two lanes per env, one Philox
+// evaluation each), owners read theirs back.  The step kernel stores reward, done and truncated before that pass.
 // The same ballots feed the per-handle finished-episode counter (mgym_episode_count).
 #include "common.h"
 #include "cartpole_step.h"
@@ -58,13 +59,16 @@ struct CartPoleLane {
 
 // reset(): cartpole.rs:238-249 — state ~ U[-0.05, 0.05)^4 sampled in f64 then cast,
 // steps_since_reset = 0, steps_beyond_terminated = None.  `episode` = Philox counter word 2.
-__device__ __forceinline__ void cartpole_draw(uint64_t seed, uint64_t gid, uint32_t episode, float out[4]) {
-    Philox4 a = env_draw(seed, gid, episode, SLOT_RESET0);
-    Philox4 b = env_draw(seed, gid, episode, SLOT_RESET1);
+// Half h of the new state (h = 0: x, x_dot from SLOT_RESET0; h = 1: theta, theta_dot from SLOT_RESET1) is one
+// Philox evaluation: the halves are independent, so two lanes can draw one env's state.
+__device__ __forceinline__ void cartpole_draw_half(uint64_t seed, uint64_t gid, uint32_t episode, uint32_t h, float out[2]) {
+    Philox4 a = env_draw(seed, gid, episode, SLOT_RESET0 + h);
     out[0] = uniform_f64_to_f32(-0.05, 0.05, a.w[0], a.w[1]);
     out[1] = uniform_f64_to_f32(-0.05, 0.05, a.w[2], a.w[3]);
-    out[2] = uniform_f64_to_f32(-0.05, 0.05, b.w[0], b.w[1]);
-    out[3] = uniform_f64_to_f32(-0.05, 0.05, b.w[2], b.w[3]);
+}
+__device__ __forceinline__ void cartpole_draw(uint64_t seed, uint64_t gid, uint32_t episode, float out[4]) {
+    cartpole_draw_half(seed, gid, episode, 0u, out);
+    cartpole_draw_half(seed, gid, episode, 1u, out + 2);
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -95,13 +99,13 @@ struct WaveResetScratch {
     float fresh[64 * VEC][4];   // new states by list slot
 };
 
-// Steps the VEC environments of every lane of the wave (fast form when the whole wave qualifies), then — RESET —
-// replaces the finished ones by fresh episodes.  `wave_first` = index of the wave's first environment.
-// Returns the number of finished envs in this wave pass.  Every lane of the wave must call this (wave collectives).
-template <int VEC, bool EULER, bool SB, bool RESET>
-__device__ __forceinline__ uint32_t cartpole_wave_step(const CartPoleDev& d, CartPoleLane (&s)[VEC], const uint32_t (&a)[VEC], const bool (&valid)[VEC],
-                                                       float (&r)[VEC], uint32_t (&dn)[VEC], uint32_t (&tr)[VEC], uint64_t wave_first,
-                                                       WaveResetScratch<VEC>& lds, bool& bad) {
+// A wave pass is two calls, and every lane of the wave makes both (wave collectives):
+//   cartpole_wave_advance  steps the VEC environments of every lane (fast form when the whole wave qualifies);
+//                          reward / done / truncated are final after it (the step kernel stores them before the reset)
+//   cartpole_wave_reset    counts the finished envs and — RESET — replaces them by fresh episodes in place
+template <int VEC, bool EULER, bool SB>
+__device__ __forceinline__ void cartpole_wave_advance(CartPoleLane (&s)[VEC], const uint32_t (&a)[VEC], const bool (&valid)[VEC],
+                                                      float (&r)[VEC], uint32_t (&dn)[VEC], uint32_t (&tr)[VEC], bool& bad) {
     constexpr CartPoleParams P = cartpole_params(EULER ? 1 : 0, SB ? 1 : 0);
     bool ok = true;
 #pragma unroll
@@ -114,6 +118,16 @@ __device__ __forceinline__ uint32_t cartpole_wave_step(const CartPoleDev& d, Car
         for (int k = 0; k < VEC; ++k)
             if (!cartpole_step_ref(P, s[k].x, s[k].xd, s[k].th, s[k].thd, s[k].ctr, a[k], r[k], dn[k], tr[k]) && valid[k]) bad = true;
     }
+}
+
+// `wave_first` = index of the wave's first environment.  Returns the number of finished envs in this wave pass.
+// The draw pass gives each listed env two lanes, one per Philox evaluation (cartpole_draw_half): lane j draws half
+// j & 1 of list entry j >> 1, so one pass serves up to 32 finished envs (a wave holds ~11.5 per step at 1 Mi envs
+// under a random policy) and half as many Philox rounds sit in the pass as with one lane per env.
+template <int VEC, bool RESET>
+__device__ __forceinline__ uint32_t cartpole_wave_reset(const CartPoleDev& d, CartPoleLane (&s)[VEC], const bool (&valid)[VEC],
+                                                        const uint32_t (&dn)[VEC], const uint32_t (&tr)[VEC], uint64_t wave_first,
+                                                        WaveResetScratch<VEC>& lds) {
     // done-mask reduction: ballots + popcounts give every finished env its slot in the wave's list
     const int lane = threadIdx.x & 63;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -132,11 +146,11 @@ __device__ __forceinline__ uint32_t cartpole_wave_step(const CartPoleDev& d, Car
             if (slot[k] != 0xffffffffu) lds.ent[slot[k]] = (s[k].ctr & (kCpEpMask << kCpEpShift)) | (uint32_t)(lane * VEC + k);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        for (uint32_t j = (uint32_t)lane; j < total; j += 64u) {  // one pass unless > 64 envs of the wave finished at once
-            const uint32_t e = lds.ent[j];
-            float f[4];
-            cartpole_draw(d.seed, d.env_id_base + wave_first + (e & 0xfffu), e >> kCpEpShift, f);
-            lds.fresh[j][0] = f[0]; lds.fresh[j][1] = f[1]; lds.fresh[j][2] = f[2]; lds.fresh[j][3] = f[3];
+        for (uint32_t j = (uint32_t)lane; j < 2u * total; j += 64u) {  // one pass unless > 32 envs of the wave finished at once
+            const uint32_t e = lds.ent[j >> 1], h = j & 1u;
+            float f[2];
+            cartpole_draw_half(d.seed, d.env_id_base + wave_first + (e & 0xfffu), e >> kCpEpShift, h, f);
+            *reinterpret_cast<float2*>(&lds.fresh[j >> 1][2u * h]) = make_float2(f[0], f[1]);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -153,10 +167,22 @@ __device__ __forceinline__ uint32_t cartpole_wave_step(const CartPoleDev& d, Car
     return total;
 }
 
+// Every thread of the block calls this once, at the end of the kernel.
+template <int WAVES>
 __device__ __forceinline__ void cartpole_flush_counts(const CartPoleDev& d, uint32_t finished, bool bad) {
-    // one fire-and-forget atomic per wave, spread over kDoneShards addresses; the (rare) error bit likewise
-    if ((threadIdx.x & 63) == 0 && finished)
-        atomicAdd(d.done_count + ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (kDoneShards - 1)), (unsigned long long)finished);
+    // the block's waves add their counts in LDS, then one fire-and-forget atomic per block, spread over kDoneShards
+    // addresses.  The shards share 16 cache lines and memory-side atomics on one line serialise: one atomic per wave
+    // (4096 per launch at 1 Mi envs) left a 0.44 us tail on the launch, measured against a build without the count.
+    __shared__ uint32_t wave_fin[WAVES];
+    if (WAVES > 1) {
+        if ((threadIdx.x & 63) == 0) wave_fin[threadIdx.x >> 6] = finished;
+        __syncthreads();
+        finished = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) finished += wave_fin[w];
+    }
+    if (threadIdx.x == 0 && finished)
+        atomicAdd(d.done_count + (blockIdx.x & (kDoneShards - 1)), (unsigned long long)finished);
     if (__any(bad)) {
         if ((threadIdx.x & 63) == 0) atomicOr(d.err, DEV_ERR_INVALID_ACTION);
     }
@@ -230,8 +256,24 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
                 a[0] = *at<uint32_t>(ba, off4);
             }
         }
+        cartpole_wave_advance<VEC, EULER, SB>(s, a, valid, r, dn, tr, bad);
+        // reward / done / truncated do not depend on the reset: issued here, their write-out drains while the reset
+        // pass runs (the LDS fences of cartpole_wave_reset keep the compiler from sinking them past it)
+        if (in) {
+            if (VEC == 4) {
+                if (rew) st4<NT>(at<float>(rew + base, off4), r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
+                if (done_out)
+                    st1u<NT>(at<uint32_t>(done_out + base, lane_env), dn[0] | (dn[1 % VEC] << 8) | (dn[2 % VEC] << 16) | (dn[3 % VEC] << 24));
+                if (trunc_out)
+                    st1u<NT>(at<uint32_t>(trunc_out + base, lane_env), tr[0] | (tr[1 % VEC] << 8) | (tr[2 % VEC] << 16) | (tr[3 % VEC] << 24));
+            } else {
+                if (rew) *at<float>(rew + base, off4) = r[0];
+                if (done_out) *at<uint8_t>(done_out + base, lane_env) = (uint8_t)dn[0];
+                if (trunc_out) *at<uint8_t>(trunc_out + base, lane_env) = (uint8_t)tr[0];
+            }
+        }
         const uint64_t wave_first = base + (uint64_t)(threadIdx.x & ~63) * VEC;
-        finished += cartpole_wave_step<VEC, EULER, SB, RESET>(d, s, a, valid, r, dn, tr, wave_first, lds, bad);
+        finished += cartpole_wave_reset<VEC, RESET>(d, s, valid, dn, tr, wave_first, lds);
 
         if (in) {
             if (VEC == 4) {
@@ -248,11 +290,6 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
                     *at<float4>(bo + 2 * d.n, off4) = make_float4(s[0].th, s[1 % VEC].th, s[2 % VEC].th, s[3 % VEC].th);
                     *at<float4>(bo + 3 * d.n, off4) = make_float4(s[0].thd, s[1 % VEC].thd, s[2 % VEC].thd, s[3 % VEC].thd);
                 }
-                if (rew) st4<NT>(at<float>(rew + base, off4), r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
-                if (done_out)
-                    st1u<NT>(at<uint32_t>(done_out + base, lane_env), dn[0] | (dn[1 % VEC] << 8) | (dn[2 % VEC] << 16) | (dn[3 % VEC] << 24));
-                if (trunc_out)
-                    st1u<NT>(at<uint32_t>(trunc_out + base, lane_env), tr[0] | (tr[1 % VEC] << 8) | (tr[2 % VEC] << 16) | (tr[3 % VEC] << 24));
             } else {
                 *at<float>(bx, off4) = s[0].x; *at<float>(bx + col, off4) = s[0].xd; *at<float>(bx + 2 * col, off4) = s[0].th;
                 *at<float>(bx + 3 * col, off4) = s[0].thd; *at<uint32_t>(bx + 4 * col, off4) = s[0].ctr;
@@ -261,13 +298,10 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
                     *at<float>(bo, off4) = s[0].x; *at<float>(bo + d.n, off4) = s[0].xd;
                     *at<float>(bo + 2 * d.n, off4) = s[0].th; *at<float>(bo + 3 * d.n, off4) = s[0].thd;
                 }
-                if (rew) *at<float>(rew + base, off4) = r[0];
-                if (done_out) *at<uint8_t>(done_out + base, lane_env) = (uint8_t)dn[0];
-                if (trunc_out) *at<uint8_t>(trunc_out + base, lane_env) = (uint8_t)tr[0];
             }
         }
     }
-    cartpole_flush_counts(d, finished, bad);
+    cartpole_flush_counts<BLK / 64>(d, finished, bad);
 }
 
 // policy of a fused rollout: actions from the caller's [K][n] table, or drawn on the device
@@ -331,7 +365,10 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
                 for (int k = 0; k < 4; ++k) a[k] = (bits.w[k] >> (t & 31)) & 1u;
                 if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
             }
-            finished += cartpole_wave_step<4, EULER, SB, RESET>(d, s, a, valid, r, dn, tr, wave_first, lds, bad);
+            cartpole_wave_advance<4, EULER, SB>(s, a, valid, r, dn, tr, bad);
+            // stored after the reset pass: storing reward / done / truncated before it (as cartpole_step_kernel does)
+            // made the linear-policy rollout, whose waves rarely reset, 4 % slower
+            finished += cartpole_wave_reset<4, RESET>(d, s, valid, dn, tr, wave_first, lds);
             if (in) {
                 if (rew) __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(r[0]), as_u32(r[1]), as_u32(r[2]), as_u32(r[3])}, rr, off4, so, 2);
                 if (done_out) __builtin_amdgcn_raw_buffer_store_b32(dn[0] | (dn[1] << 8) | (dn[2] << 16) | (dn[3] << 24), rd, lane_env, so >> 2, 2);
@@ -352,7 +389,7 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{s[0].ctr, s[1].ctr, s[2].ctr, s[3].ctr}, rs, off4, sb + 4u * colb, kAux);
         }
     }
-    cartpole_flush_counts(d, finished, bad);
+    cartpole_flush_counts<kWaves>(d, finished, bad);
 }
 
 // Masked reset.  One lane looks at 4 consecutive mask bytes of each mask with a single dword
