@@ -267,6 +267,20 @@ int mgym_timer_stop(mgym_env *env, float *elapsed_ms); /* synchronises */
  * sincos / cos of the LunarLander and MountainCar kernels}; all must be 0. */
 int mgym_selftest_cartpole_math(int device, uint64_t *mismatches);
 
+/* Test seam: the result bits of one entry point of modurl_gym_amd/csrc/mgym_math.h (the glibc-equal f32 sin / cos / tanh the
+ * kernels use), evaluated on the device for the input bit patterns first .. first + count - 1 (first + count <= 2^32).
+ * out is device memory of count words, 2 * count for the sincos forms (sin at out[i], cos at out[count + i]).  Runs on the
+ * null stream and synchronises the device.  tests/test_gpu_math_exhaustive.py compares every pattern with the host's glibc. */
+enum {
+    MGYM_MATH_SINF = 0,      /* mg_sinf */
+    MGYM_MATH_COSF = 1,      /* mg_cosf */
+    MGYM_MATH_SINCOSF = 2,   /* mg_sincosf */
+    MGYM_MATH_SINCOSF_U = 3, /* mg_sincosf_u (LunarLander's lock-step form) */
+    MGYM_MATH_COSF_U = 4,    /* mg_cosf_u (MountainCar's lock-step form) */
+    MGYM_MATH_TANHF = 5      /* mg_tanhf */
+};
+int mgym_math_probe(int device, int fn, uint32_t first, uint64_t count, uint32_t *out);
+
 /* hipGraph capture of a caller-issued launch sequence on the env's stream.  What a captured launch freezes and what it does not:
  *  - environment STATE is read when the graph runs: mgym_set_state, mgym_reset (any form) and eager steps between replays are fine.
  *    (LunarLander: a captured step always carries the launches that reset a finished environment WITHOUT a prepared next episode —

@@ -11,10 +11,18 @@
 //               multiply-subtract range reduction for |x| < 120, a 192-bit 2/pi
 //               table reduction above, then a degree-7/8 odd/even polynomial.
 //   tanhf     : fdlibm s_tanhf.c on top of s_expm1f.c (pure f32 arithmetic).
-// Every operation is an individually rounded IEEE add/mul/div (compile with
-// -ffp-contract=off), so the device result is bit-identical to a non-FMA build of
-// those routines; tests/test_math_host.py compiles this header for the host and
-// compares against the container's glibc over all floats in the fast range.
+// The libm that counts is the one the x86-64 hosts driving the GPUs run: glibc picks
+// the FMA build of sinf/cosf/sincosf (__sinf_fma, __cosf_fma, __sincosf_fma) by ifunc
+// on every CPU with FMA, and that build contracts the range reduction's x - n*pi/2 into
+// one fused multiply-add.  reduce_fast does the same through cp_fma; without it 34
+// floats with 16 < |x| < 120 came out 1 ulp off.  The polynomials give the same f32
+// result fused or not (enumerated), and tanhf has nothing to contract.  Everything
+// else is an individually rounded IEEE add/mul/div (compile with -ffp-contract=off).
+// tests/native/math_glibc_exhaustive.cpp (run by tests/test_ll_host.py) compiles this
+// header for the host and compares every entry point with the host's glibc over all
+// 2^32 bit patterns; tests/test_gpu_math_exhaustive.py does the same for the results
+// the device computes (mgym_math_probe).  On a CPU without FMA glibc runs its other
+// build, which the reference would then follow too; those tests skip there.
 //
 // MG_HD expands to __host__ __device__ under hipcc and to nothing under g++.
 #pragma once
@@ -45,7 +53,8 @@ MG_HD float as_f32(uint32_t u) {
 #endif
 }
 
-// explicit fused multiply-add (the only contraction in the code base: -ffp-contract=off keeps everything else unfused)
+// explicit fused multiply-add: every contraction in the code base is written out through these (-ffp-contract=off keeps
+// everything else unfused) — the range reduction below, the fused lock-step polynomials, and cartpole_math.h's sequences
 MG_HD float cp_fmaf(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 MG_HD double cp_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
@@ -91,7 +100,7 @@ MG_HD double reduce_fast(double x, int* np) {
     double r = x * sc_hpi_inv();
     int n = ((int32_t)r + 0x800000) >> 24;
     *np = n;
-    return x - n * sc_hpi();
+    return cp_fma(-(double)n, sc_hpi(), x);  // glibc's FMA build contracts x - n * pi/2 (see the top of this file)
 }
 
 // 2/pi to 192 bits, 8 new bits per entry.
@@ -210,14 +219,14 @@ MG_HD void mg_sincosf(float y, float* sp, float* cp) {
 // |x| < 120 the range reduction is applied unconditionally — below pi/4 it yields n = 0 and x - 0*pi/2 = x, i.e.
 // exactly the small-argument path — both polynomials are evaluated once, the quadrant swaps/negates them by
 // select (negating every cosine coefficient equals negating the rounded result: round-to-nearest is symmetric).
-// tests/test_math_host.py checks it bit-for-bit against mg_sincosf over the floats.
+// tests/native/cartpole_fast_check.cpp checks it bit-for-bit against mg_sincosf over the floats.
 MG_HD void mg_sincosf_u(float y, float* sp, float* cp) {
     if (abstop12(y) < abstop12(120.0f)) {
         // The two polynomials are evaluated with each  a + b*c  pair fused (12 f64 operations instead of 19).  The fused
         // values differ from the individually rounded ones by < 2^-52 relative, which would change the f32 rounding of the
         // result only within that distance of a rounding boundary: enumerating every f32 with |y| < 120 shows that this
         // happens for none of them (tests/native/cartpole_fast_check.cpp, group sincos_u; mgym_selftest_cartpole_math
-        // repeats the enumeration on the GPU).  The range reduction stays unfused.
+        // repeats the enumeration on the GPU).  The range reduction is reduce_fast's, shared with mg_sincosf.
         int n;
         const double xr = reduce_fast((double)y, &n);
         const double x2 = xr * xr;

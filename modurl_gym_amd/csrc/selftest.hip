@@ -7,7 +7,8 @@
 //   out[3] step   : 2^28 random guard-admitted states, all four <EULER, SB> variants: fast form == reference form
 //   out[4] sincos_u : every f32 with |y| < 120, both signs: the fused lock-step mg_sincosf_u / mg_cosf_u (LunarLander,
 //                   MountainCar) == mg_sincosf / mg_cosf
-// Exposed as mgym_selftest_cartpole_math() (test seam; seconds on an MI355X).
+// Exposed as mgym_selftest_cartpole_math() (test seam; seconds on an MI355X).  mgym_math_probe() (test seam) writes the device's
+// result bits of one mgym_math.h entry point for a span of input patterns; tests/test_gpu_math_exhaustive.py compares all 2^32 with glibc.
 #include "common.h"
 #include "cartpole_step.h"
 
@@ -138,9 +139,58 @@ __global__ void __launch_bounds__(256) selftest_step_kernel(unsigned long long* 
     st_flush(out, bad);
 }
 
+// result bits of one mgym_math.h entry point for the patterns first .. first + count - 1 (mgym_math_probe); the sincos
+// forms write sin to out[i] and cos to out[count + i]
+template <int FN>
+__global__ void __launch_bounds__(256) math_probe_kernel(uint32_t first, uint64_t count, uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        const float y = as_f32(first + (uint32_t)i);
+        if constexpr (FN == MGYM_MATH_SINCOSF || FN == MGYM_MATH_SINCOSF_U) {
+            float s, c;
+            if constexpr (FN == MGYM_MATH_SINCOSF) mg_sincosf(y, &s, &c);
+            else mg_sincosf_u(y, &s, &c);
+            out[i] = as_u32(s);
+            out[count + i] = as_u32(c);
+        } else {
+            float r;
+            if constexpr (FN == MGYM_MATH_SINF) r = mg_sinf(y);
+            else if constexpr (FN == MGYM_MATH_COSF) r = mg_cosf(y);
+            else if constexpr (FN == MGYM_MATH_COSF_U) r = mg_cosf_u(y);
+            else r = mg_tanhf(y);
+            out[i] = as_u32(r);
+        }
+    }
+}
+
 }  // namespace mgym
 
 using namespace mgym;
+
+extern "C" int mgym_math_probe(int device, int fn, uint32_t first, uint64_t count, uint32_t* out) {
+    if (!out || count == 0 || count > 0x100000000ull - first || fn < MGYM_MATH_SINF || fn > MGYM_MATH_TANHF) {
+        set_last_error("mgym_math_probe: NULL output, empty or out-of-range pattern span, or unknown entry point");
+        return MGYM_ERR_BAD_ARG;
+    }
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    MGYM_HIP(hipSetDevice(device));
+    const uint64_t blocks = (count + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536)), block(256);
+    switch (fn) {
+        case MGYM_MATH_SINF: hipLaunchKernelGGL(math_probe_kernel<MGYM_MATH_SINF>, grid, block, 0, nullptr, first, count, out); break;
+        case MGYM_MATH_COSF: hipLaunchKernelGGL(math_probe_kernel<MGYM_MATH_COSF>, grid, block, 0, nullptr, first, count, out); break;
+        case MGYM_MATH_SINCOSF: hipLaunchKernelGGL(math_probe_kernel<MGYM_MATH_SINCOSF>, grid, block, 0, nullptr, first, count, out); break;
+        case MGYM_MATH_SINCOSF_U: hipLaunchKernelGGL(math_probe_kernel<MGYM_MATH_SINCOSF_U>, grid, block, 0, nullptr, first, count, out); break;
+        case MGYM_MATH_COSF_U: hipLaunchKernelGGL(math_probe_kernel<MGYM_MATH_COSF_U>, grid, block, 0, nullptr, first, count, out); break;
+        default: hipLaunchKernelGGL(math_probe_kernel<MGYM_MATH_TANHF>, grid, block, 0, nullptr, first, count, out); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return hip_fail(e, "math_probe", __FILE__, __LINE__);
+    return MGYM_OK;
+}
 
 extern "C" int mgym_selftest_cartpole_math(int device, uint64_t* mismatches /* [5] */) {
     if (!mismatches) { set_last_error("mgym_selftest_cartpole_math: NULL"); return MGYM_ERR_BAD_ARG; }

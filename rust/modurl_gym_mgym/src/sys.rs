@@ -25,6 +25,13 @@ pub const MGYM_LUNARLANDER: c_int = 3;
 
 pub const MGYM_FLAG_AUTO_RESET: u32 = 1;
 
+pub const MGYM_MATH_SINF: c_int = 0;
+pub const MGYM_MATH_COSF: c_int = 1;
+pub const MGYM_MATH_SINCOSF: c_int = 2;
+pub const MGYM_MATH_SINCOSF_U: c_int = 3;
+pub const MGYM_MATH_COSF_U: c_int = 4;
+pub const MGYM_MATH_TANHF: c_int = 5;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct mgym_config {
@@ -106,6 +113,7 @@ unsafe extern "C" {
     ) -> c_int;
     pub fn mgym_episode_count(env: *mut mgym_env, finished: *mut u64) -> c_int;
     pub fn mgym_selftest_cartpole_math(device: c_int, mismatches: *mut u64) -> c_int;
+    pub fn mgym_math_probe(device: c_int, fn_: c_int, first: u32, count: u64, out: *mut u32) -> c_int;
     pub fn mgym_observation(env: *mut mgym_env, obs: *mut *const f32, col_stride: *mut u64) -> c_int;
     pub fn mgym_observation_aos(env: *mut mgym_env, out_aos: *mut f32) -> c_int;
     pub fn mgym_get_state(env: *mut mgym_env, blob: *mut c_void) -> c_int;

@@ -1,6 +1,10 @@
 // CPU check of the LunarLander KERNEL SOURCE (modurl_gym_amd/csrc/ll_*.h compiled for the host through a
 // small shim) against the CPU oracle: same seeds, actions and dispersion, step by step.  Built and run by
 // tests/test_ll_host.py; no GPU involved.  This is a test of the kernel logic, not a product CPU path.
+// Second form, run by tests/test_sincos_mid_range.py:  ll_host_check mid <steps> <general_only 0|1> <angle>...
+// 4 envs per angle (C hex floats): each reset state is turned rigidly about the lander's centre so that the lander's angle is
+// exactly that angle (both legs turned with it), on both sides through the set_state seam; env i then fires action i % 4 every
+// step.  general_only = 1 sends every step through the general path instead of the free-flight one.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -43,14 +47,19 @@ using namespace mgym;
 static bool closef(float a, float b) { return fabsf(a - b) <= 1e-5f * fmaxf(fabsf(a), fabsf(b)) + 1e-6f || (a != a && b != b); }
 
 int main(int argc, char** argv) {
-    const uint64_t n = argc > 1 ? strtoull(argv[1], 0, 0) : 64;
+    const bool mid = argc > 1 && !strcmp(argv[1], "mid");
+    std::vector<float> mid_angles;
+    for (int q = 4; mid && q < argc; ++q) mid_angles.push_back(strtof(argv[q], nullptr));
+    const bool general_only = mid && argc > 3 && atoi(argv[3]) != 0;
+    const uint64_t n = mid ? 4 * mid_angles.size() : (argc > 1 ? strtoull(argv[1], 0, 0) : 64);
     const int steps = argc > 2 ? atoi(argv[2]) : 300;
-    const int wind = argc > 3 ? atoi(argv[3]) : 0;
-    const int deterministic = argc > 4 ? atoi(argv[4]) : 0;
-    const unsigned toi_staged = argc > 5 ? (unsigned)atoi(argv[5]) : 1u;  // 0: the TOI word of the contact cache stays in place (64-lane blocks)
+    const int wind = mid ? 0 : (argc > 3 ? atoi(argv[3]) : 0);
+    const int deterministic = mid ? 0 : (argc > 4 ? atoi(argv[4]) : 0);
+    const unsigned toi_staged = mid ? 1u : (argc > 5 ? (unsigned)atoi(argv[5]) : 1u);  // 0: the TOI word of the contact cache stays in place (64-lane blocks)
     // other physics settings than the defaults (the early exits of the sweep loops rest on bounds derived from the constraint masses, not on
     // these values, and must hold for every setting the builder accepts: lunar_lander.rs:278-296)
-    const float gravity = argc > 6 ? (float)atof(argv[6]) : -10.0f, wind_power = argc > 7 ? (float)atof(argv[7]) : 15.0f, turbulence = argc > 8 ? (float)atof(argv[8]) : 1.5f;
+    const float gravity = !mid && argc > 6 ? (float)atof(argv[6]) : -10.0f, wind_power = !mid && argc > 7 ? (float)atof(argv[7]) : 15.0f,
+                turbulence = !mid && argc > 8 ? (float)atof(argv[8]) : 1.5f;
     const uint64_t seed = 77;
     // product side: SoA state exactly as the kernels keep it
     LLDev d;
@@ -91,12 +100,38 @@ int main(int argc, char** argv) {
         ll_store(d, i, w, e);
         for (int q = 0; q < 8; ++q) { total++; if (state[q] == oobs[q * n + i]) exact++; if (!closef(state[q], oobs[q * n + i])) { if (mism < 10) printf("reset env %lu obs[%d] %.9g vs %.9g\n", (unsigned long)i, q, state[q], oobs[q * n + i]); mism++; } }
     }
+    if (mid) {  // turn every lander (and its legs) so that its angle word is the given angle, the same words on both sides
+        const int cols = ora_vec_state_cols(ov);
+        std::vector<float> blob((size_t)cols * n);
+        ora_vec_get_state(ov, blob.data());
+        for (uint64_t i = 0; i < n; ++i) {
+            float* b = blob.data();
+            const double delta = (double)mid_angles[i / 4] - (double)b[2 * n + i], c = cos(delta), sn = sin(delta);
+            const double cx = b[0 * n + i], cy = b[1 * n + i];
+            b[2 * n + i] = mid_angles[i / 4];
+            for (int base = 6; base <= 12; base += 6) {
+                const double px = b[(size_t)base * n + i] - cx, py = b[(size_t)(base + 1) * n + i] - cy;
+                b[(size_t)base * n + i] = (float)(cx + c * px - sn * py);
+                b[(size_t)(base + 1) * n + i] = (float)(cy + sn * px + c * py);
+                b[(size_t)(base + 2) * n + i] = (float)((double)b[(size_t)(base + 2) * n + i] + delta);
+            }
+        }
+        ora_vec_set_state(ov, blob.data());
+        for (uint64_t i = 0; i < n; ++i) {   // what ll_import_kernel does
+            World w; EnvRegs e; float raw[18];
+            w.t = &h_tmp;
+            ll_load(d, i, w, e, hot);
+            for (int q = 0; q < 18; ++q) raw[q] = blob[(size_t)q * n + i];
+            ll_apply_set_state(w, tab, raw, blob[18 * n + i] > 0.5f, blob[19 * n + i] > 0.5f);
+            ll_store(d, i, w, e);
+        }
+    }
     VConstraint h_vc[kSlots]; PConstraint h_pc[kSlots];
     VConstraint h_vc_far[kSlots];  // constraints 2.. go through the far (global workspace) path here, as in the 32-lane blocks on the GPU (64-lane blocks: 4..)
     CSolverMem mem; mem.vc = h_vc; mem.vc_stride = 1; mem.vc_near = 2; mem.vc_far = h_vc_far; mem.vc_far_stride = 1; mem.pc = h_pc; mem.pc_stride = 1; mem.cap = kSlots;
     uint32_t rs = 12345;
     for (int t = 0; t < steps; ++t) {
-        for (uint64_t i = 0; i < n; ++i) { rs = rs * 1664525u + 1013904223u; act[i] = (rs >> 16) & 3u; }
+        for (uint64_t i = 0; i < n; ++i) { rs = rs * 1664525u + 1013904223u; act[i] = mid ? (uint32_t)(i & 3u) : (rs >> 16) & 3u; }
         ora_vec_step(ov, act.data(), oobs.data(), orew.data(), odone.data(), otr.data(), 1);
         for (uint64_t i = 0; i < n; ++i) {
             float state[8], reward, d0, d1; uint32_t done;
@@ -105,7 +140,7 @@ int main(int argc, char** argv) {
 #endif
             // same dispatch as ll_free_kernel / ll_general_kernel: fast path when eligible and it accepts
             bool fast = false;
-            if (ll_free_eligible(ST(C_FLAGS))) {
+            if (!general_only && ll_free_eligible(ST(C_FLAGS))) {
                 FreeRegs f; EnvRegs e;
                 ll_free_load(d, i, f, e);
                 ll_dispersion(d, i, e, d0, d1);

@@ -1,8 +1,8 @@
 // Host-side check of modurl_gym_amd/csrc/mgym_math.h against the container's glibc.
-// Built and run by tests/test_math_host.py (no GPU).  Prints one line per function:
+// Built and run by tests/test_ll_host.py (no GPU).  Prints one line per function:
 //   <name> total=<n> bad_fast=<n> bad_mid=<n> bad_large=<n>
 // fast: |x| <= 16 (must be 0: covers every angle the environments produce);
-// mid : 16 < |x| < 120 (glibc's FMA ifunc variant rounds a handful of inputs differently);
+// mid : 16 < |x| < 120 (0 where the host has FMA: glibc's FMA build, which mgym_math.h restates);
 // large: |x| >= 120 (table reduction).
 #include <math.h>
 #include <stdio.h>

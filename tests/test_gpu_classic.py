@@ -11,6 +11,7 @@ import pytest
 import modurl_gym_amd as mg
 from harness import VecAdapter, replay
 from oracle import oracle as ora
+from sincos_mid_range import ANGLES as MID_RANGE_ANGLES
 
 pytestmark = pytest.mark.gpu
 
@@ -240,14 +241,15 @@ def test_cartpole_episode_counter_wraps_at_2_pow_20_as_documented():
 
 
 def test_cartpole_large_angles_use_table_reduction():
-    # stepping long after termination spins theta up: exercises reduce_fast beyond pi/4 and the
-    # |x| >= 120 table reduction of mgym_math.h on the device
+    # stepping long after termination spins theta up: exercises reduce_fast beyond pi/4 (16 < |theta| < 120 included, where
+    # the unfused reduction once differed from glibc) and the |x| >= 120 table reduction of mgym_math.h on the device
     n = 8192
     env, ref, _ = both("cartpole", n, seed=4)
     rng = np.random.default_rng(10)
     s = ref.get_state()
-    mag = np.concatenate([rng.uniform(0, 16, n // 2), 10.0 ** rng.uniform(np.log10(120), 6, n // 2)])
-    s[2] = (mag * rng.choice([-1.0, 1.0], n)).astype(np.float32)
+    m = n - len(MID_RANGE_ANGLES)
+    mag = 10.0 ** rng.uniform(np.log10(0.75), 6, m)     # log-uniform over [0.75, 1e6]
+    s[2] = np.concatenate([(mag * rng.choice([-1.0, 1.0], m)).astype(np.float32), MID_RANGE_ANGLES])
     s[3] = rng.uniform(-1, 1, n)
     ref.set_state(s), env.set_state(s)
     a = rng.integers(0, 2, n).astype(np.uint32)

@@ -1,7 +1,8 @@
 """No-GPU check of the LunarLander KERNEL SOURCE: modurl_gym_amd/csrc/ll_{b2,world,env}.h are compiled
 for the host (tests/native/ll_host_check.cpp supplies a shim for the HIP qualifiers) and stepped
 side by side with the CPU oracle on identical seeds, actions and Philox dispersion draws.
-Also covers the device math header against the container's glibc (tests/native/math_host_check.cpp)."""
+Also covers the device math header against the host's glibc (tests/native/math_host_check.cpp, sampled, and
+tests/native/math_glibc_exhaustive.cpp, every bit pattern)."""
 import os
 import re
 import subprocess
@@ -54,9 +55,34 @@ def test_device_math_header_matches_glibc():
     for fn in ("sinf", "cosf", "tanhf", "sincosf_self", "sincosf_uniform_vs_sincosf"):
         assert int(rows[fn]["bad_fast"]) == 0, out      # |x| <= 16: every angle the environments produce
     assert int(rows["sinf"]["bad_large"]) == 0 and int(rows["cosf"]["bad_large"]) == 0
-    # 16 < |x| < 120: glibc's FMA ifunc variant may round a handful of inputs differently
+    # 16 < |x| < 120: reduce_fast fuses x - n*pi/2 as glibc's FMA build does (mgym_math.h), so no input may differ here either
     assert int(rows["sinf"]["bad_mid"]) + int(rows["cosf"]["bad_mid"]) <= 8, out
+    if _host_has_fma():
+        assert int(rows["sinf"]["bad_mid"]) == 0 and int(rows["cosf"]["bad_mid"]) == 0, out
     assert int(rows["tanhf"]["bad_mid"]) == 0 and int(rows["tanhf"]["bad_large"]) == 0
+
+
+def _host_has_fma():
+    with open("/proc/cpuinfo") as f:
+        return any(line.startswith("flags") and " fma " in f" {line.split(':', 1)[1].strip()} " for line in f)
+
+
+def test_device_math_header_matches_glibc_on_every_pattern():
+    """All 2^32 f32 bit patterns, both signs, through every sin/cos entry point of mgym_math.h (mg_sinf, mg_cosf, mg_sincosf,
+    mg_sincosf_u, mg_cosf_u) and mg_tanhf against the host's glibc: no mismatch in any range (NaN results compared as a class).
+    Before reduce_fast fused its subtraction, 34 inputs with 16 < |x| < 120 differed by one ulp (12 sin, 22 cos)."""
+    if not _host_has_fma():
+        pytest.skip("host CPU has no FMA: glibc runs its non-FMA sinf/cosf build, which mgym_math.h does not restate")
+    exe = _build("math_glibc_exhaustive.cpp", "math_glibc_exhaustive", ["-mfma", "-fopenmp"])
+    threads = max(1, min(16, len(os.sched_getaffinity(0))))
+    r = subprocess.run([exe, str(threads)], capture_output=True, text=True)
+    rows = {l.split()[0]: dict(kv.split("=") for kv in l.split()[1:]) for l in r.stdout.strip().splitlines()}
+    assert sorted(rows) == sorted(["sinf", "cosf", "sincosf.sin", "sincosf.cos", "sincosf_u.sin", "sincosf_u.cos", "cosf_u", "tanhf"]), r.stdout + r.stderr
+    for fn, row in rows.items():
+        assert int(row["total"]) == 1 << 32, r.stdout
+        for cls in ("bad_fast", "bad_mid", "bad_large", "bad_nonfinite"):
+            assert int(row[cls]) == 0, f"{fn} {cls}: {r.stdout}"
+    assert r.returncode == 0, r.stdout + r.stderr
 
 
 def test_kernel_source_is_clean_under_asan_and_ubsan():

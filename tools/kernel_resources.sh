@@ -8,7 +8,7 @@ cd "$(dirname "$0")/../modurl_gym_amd/csrc" || exit 1
 import re, sys, subprocess
 cur = None
 for line in sys.stdin:
-    m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
+    m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
     if not m: continue
     k, v = m.groups()
     if k == "Function Name":
@@ -16,7 +16,8 @@ for line in sys.stdin:
         print()
         print(f"{cur:56s}", end="")
     else:
-        print(f" {k.split()[0]}={v}", end="")
+        name = "SGPRs" if k == "TotalSGPRs" else k.split()[0] + ("spill" if k.endswith("Spill") else "")
+        print(f" {name}={v}", end="")
 print()
 '
 rm -f /tmp/kres_$$.o
