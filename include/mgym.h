@@ -91,8 +91,26 @@ typedef struct mgym_config {
     int32_t enable_wind;
     float wind_power;
     float turbulence_power;
-    uint32_t reserved;
+    uint32_t max_episode_steps; /* episode time limit in caller-visible steps; 0 = off (the reference's behaviour).  See below. */
 } mgym_config;
+
+/* max_episode_steps — an episode time limit inside the step kernels (NOT in the reference: its MountainCarV0 and LunarLanderV3 never
+ * truncate, mountain_car.rs:324-329, lunar_lander.rs:1165; this is gymnasium's TimeLimit rule, and the one thing a caller of the fused
+ * mgym_rollout* launches cannot add from outside).  0 = off: every output word and every step / rollout kernel is what it is without the field (MountainCar's reset and state-import
+ * kernels additionally clear a 2-byte count per environment they touch).
+ *   1 .. 65535: MountainCar, MountainCarContinuous, LunarLander.  Larger: MGYM_ERR_BAD_CONFIG.
+ *   CartPole keeps the reference's 500 (cartpole.rs:297): it accepts 0 and 500, which both mean what it does today, and rejects
+ *   anything else with MGYM_ERR_BAD_CONFIG.
+ * Every environment has an ELAPSED count of caller-visible steps since its last reset: 0 after mgym_reset / mgym_reset_done /
+ * mgym_reset_deterministic (for the environments they reset) and after an auto-reset; LunarLander's implicit step(0) inside reset()
+ * (lunar_lander.rs:911-916) does not count.  A step first does exactly what it does without a limit — the same obs, reward and done
+ * words — then elapsed += 1 and truncated = (elapsed >= max_episode_steps).  `done` is not changed by the limit (both flags can be 1
+ * on one step); no reward is added or removed.  The same for every entry point that steps (mgym_step, mgym_rollout,
+ * mgym_rollout_uniform, mgym_rollout_linear, replays of graphs captured from them: the count lives in device memory).
+ * Without MGYM_FLAG_AUTO_RESET an environment stepped past its limit keeps integrating and reports truncated = 1 on every later step
+ * (the count saturates, it never wraps).  With it, "finished" is done | truncated: the environment is reset in the same step by the
+ * same route and with the same Philox keys as a `done` one, and obs_out of that step holds the reset observation.
+ * The final observation of a truncated episode is not delivered under auto-reset. */
 
 /* Space metadata (reference: observation_space()/action_space(), cartpole.rs:58-69,350-356;
  * mountain_car.rs:42-48; lunar_lander.rs:1169-1200). */
@@ -131,13 +149,15 @@ int mgym_reset(mgym_env *env, const uint8_t *mask, float *obs_out);
 int mgym_reset_done(mgym_env *env, const uint8_t *done, const uint8_t *truncated, float *obs_out);
 
 /* Gym::step (cartpole.rs:251-348, mountain_car.rs:293-330, lunar_lander.rs:919-1167).
- * Any of obs_out / reward_out / done_out / trunc_out may be NULL (not written). */
+ * Any of obs_out / reward_out / done_out / trunc_out may be NULL (not written).  trunc_out: CartPole's 500-step rule (cartpole.rs:297);
+ * MountainCar / LunarLander: 0 as in the reference unless mgym_config::max_episode_steps sets a limit. */
 int mgym_step(mgym_env *env, const void *actions, float *obs_out, float *reward_out,
               uint8_t *done_out, uint8_t *trunc_out);
 
 /* K consecutive Gym::step calls on every env in ONE launch (fused rollout).  Results are
  * identical to K calls of mgym_step with the same per-step action columns, including the
- * MGYM_FLAG_AUTO_RESET behaviour between steps; for CartPole/MountainCar the state stays in registers
+ * MGYM_FLAG_AUTO_RESET behaviour between steps and the truncated flags of mgym_config::max_episode_steps (MountainCar keeps the elapsed
+ * count in registers across the K steps: one read and one write per launch); for CartPole/MountainCar the state stays in registers
  * across the K steps, so per-step HBM traffic is the action read and the reward/flag writes only.
  * actions: [K][n_envs]; reward_out/done_out/trunc_out: [K][n_envs] or NULL; obs_out: [K][obs_dim][n_envs] or NULL.
  * LunarLander: ONE persistent launch in which every environment advances as soon as IT is ready (free-flight environments stay in
@@ -221,6 +241,17 @@ int mgym_observation_aos(mgym_env *env, float *out_aos);
 int mgym_get_state(mgym_env *env, void *blob);
 int mgym_set_state(mgym_env *env, const void *blob);
 
+/* The elapsed count of mgym_config::max_episode_steps, for checkpoints and tests: out / in are DEVICE arrays of n_envs uint32.  Both are
+ * ordered on the handle's stream and capturable.
+ *   LunarLander: the step counter of blob column 25 minus 1 (mgym_get_state / mgym_set_state go on carrying it; on import, plus 1);
+ *   kept whether or not a limit is set.
+ *   MountainCar(+Continuous): a counter of its own beside the 3-column blob; mgym_set_state sets it to 0, mgym_set_elapsed_steps
+ *   overrides it, values above 65535 are clamped.  A handle WITHOUT a limit runs the kernels as they were, which do not touch the
+ *   counter: it is 0 after a reset and is not advanced by steps.
+ *   CartPole: MGYM_ERR_BAD_ARG (its counter is blob column 4). */
+int mgym_get_elapsed_steps(mgym_env *env, uint32_t *out);
+int mgym_set_elapsed_steps(mgym_env *env, const uint32_t *in);
+
 /* Test seam ≙ Testable::reset_deterministic (cartpole.rs:437-442: reset() then state = 0;
  * mountain_car.rs:403-408: state = 0; lunar_lander.rs:1249-1442: flat terrain, lander at
  * (W/2, 0.8 H) falling at 1 m/s, deterministic_mode = true) applied to every env. obs_out may be NULL. */
@@ -239,7 +270,7 @@ int mgym_sync(mgym_env *env);
 const char *mgym_last_error(void);
 
 /* Describes how this handle runs, as NUL-terminated "key=value" lines written to buf (at most cap bytes, always terminated;
- * returns MGYM_ERR_BAD_ARG if cap is too small).  Keys every family reports: kind, n_envs, device, auto_reset,
+ * returns MGYM_ERR_BAD_ARG if cap is too small).  Keys every family reports: kind, n_envs, device, auto_reset, max_episode_steps,
  * GPU_MAX_HW_QUEUES (the HIP runtime knob as this process's environment held it when the handle was created, or "unset").
  * LunarLander adds its launch structure — contact_block, launch_order, staged_resets — and `concurrent_streams`: the
  * reference is single-threaded (lunar_lander.rs:240-249), this engine steps one population on up to three streams

@@ -39,7 +39,8 @@ inline void check(int st) {
     }
 }
 
-// n_envs environments of one family on one GPU; buffers are device pointers owned by the caller.
+// n_envs environments of one family on one GPU; buffers are device pointers owned by the caller.  The episode time limit is
+// cfg.max_episode_steps (0 = off, the reference's behaviour; CartPole keeps the reference's 500) — see mgym.h.
 class VecGym {
   public:
     explicit VecGym(const mgym_config& cfg) : cfg_(cfg) {
@@ -71,6 +72,10 @@ class VecGym {
         check(mgym_episode_count(env_, &c));
         return c;
     }
+    // the elapsed count of mgym_config::max_episode_steps (device arrays of n_envs uint32; on the handle's stream)
+    void get_elapsed_steps(uint32_t* out) { check(mgym_get_elapsed_steps(env_, out)); }
+    void set_elapsed_steps(const uint32_t* in) { check(mgym_set_elapsed_steps(env_, in)); }
+    uint32_t max_episode_steps() const { return cfg_.max_episode_steps; }
     const float* observation(uint64_t* col_stride) {
         const float* p = nullptr;
         check(mgym_observation(env_, &p, col_stride));
@@ -177,9 +182,10 @@ class CartPoleV1 : public SingleGym {  // cartpole.rs:13-357
 class MountainCarV0 : public SingleGym {  // mountain_car.rs:10-339
   public:
     struct Builder {
-        int device_ = 0; float goal_velocity_ = 0.0f; uint64_t seed_ = 0;
+        int device_ = 0; float goal_velocity_ = 0.0f; uint64_t seed_ = 0; uint32_t max_episode_steps_ = 0;
         Builder& device(int d) { device_ = d; return *this; }
         Builder& goal_velocity(float v) { goal_velocity_ = v; return *this; }
+        Builder& max_episode_steps(uint32_t k) { max_episode_steps_ = k; return *this; }  // superset: not in the reference (0 = never truncates)
         Builder& seed(uint64_t s) { seed_ = s; return *this; }
         MountainCarV0* build() { return new MountainCarV0(*this); }
     };
@@ -189,6 +195,7 @@ class MountainCarV0 : public SingleGym {  // mountain_car.rs:10-339
     static mgym_config cfg(const Builder& b) {
         mgym_config c = defaults(MGYM_MOUNTAINCAR, b.device_, b.seed_);
         c.goal_velocity = b.goal_velocity_;
+        c.max_episode_steps = b.max_episode_steps_;
         return c;
     }
     explicit MountainCarV0(const Builder& b) : SingleGym(cfg(b)) {}
@@ -198,8 +205,9 @@ class LunarLanderV3 : public SingleGym {  // lunar_lander.rs:232-1201
   public:
     struct Builder {
         int device_ = 0; float gravity_ = -10.0f; bool enable_wind_ = false; float wind_power_ = 15.0f, turbulence_power_ = 1.5f;
-        uint64_t seed_ = 0;
+        uint64_t seed_ = 0; uint32_t max_episode_steps_ = 0;
         Builder& device(int d) { device_ = d; return *this; }
+        Builder& max_episode_steps(uint32_t k) { max_episode_steps_ = k; return *this; }  // superset: not in the reference (0 = never truncates)
         Builder& gravity(float g) { gravity_ = g; return *this; }
         Builder& enable_wind(bool b) { enable_wind_ = b; return *this; }
         Builder& wind_power(float p) { wind_power_ = p; return *this; }
@@ -213,6 +221,7 @@ class LunarLanderV3 : public SingleGym {  // lunar_lander.rs:232-1201
     static mgym_config cfg(const Builder& b) {
         mgym_config c = defaults(MGYM_LUNARLANDER, b.device_, b.seed_);
         c.gravity = b.gravity_; c.enable_wind = b.enable_wind_; c.wind_power = b.wind_power_; c.turbulence_power = b.turbulence_power_;
+        c.max_episode_steps = b.max_episode_steps_;
         return c;
     }
     explicit LunarLanderV3(const Builder& b) : SingleGym(cfg(b)) {}

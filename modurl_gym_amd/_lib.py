@@ -23,7 +23,7 @@ class Config(C.Structure):
                 ("n_envs", C.c_uint64), ("env_id_base", C.c_uint64), ("seed", C.c_uint64),
                 ("sutton_barto_reward", C.c_int32), ("is_euler", C.c_int32), ("goal_velocity", C.c_float),
                 ("gravity", C.c_float), ("enable_wind", C.c_int32), ("wind_power", C.c_float),
-                ("turbulence_power", C.c_float), ("reserved", C.c_uint32)]
+                ("turbulence_power", C.c_float), ("max_episode_steps", C.c_uint32)]
 
 
 class Spec(C.Structure):
@@ -53,6 +53,8 @@ PROTOTYPES = {
     "mgym_observation_aos": (C.c_int, [_vp, _vp]),
     "mgym_get_state": (C.c_int, [_vp, _vp]),
     "mgym_set_state": (C.c_int, [_vp, _vp]),
+    "mgym_get_elapsed_steps": (C.c_int, [_vp, _vp]),
+    "mgym_set_elapsed_steps": (C.c_int, [_vp, _vp]),
     "mgym_set_dispersion_override": (C.c_int, [_vp, _vp]),
     "mgym_get_spec": (C.c_int, [C.c_int, C.POINTER(Spec)]),
     "mgym_sync": (C.c_int, [_vp]),

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "common.h"
+#include "time_limit.h"
 
 namespace mgym {
 
@@ -121,6 +122,14 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
         // lunar_lander.rs:292-296
         char buf[128];
         snprintf(buf, sizeof buf, "gravity (current value: %g) must be between -12 and 0", (double)cfg->gravity);
+        set_last_error(buf);
+        return MGYM_ERR_BAD_CONFIG;
+    }
+    // episode time limit (not in the reference): CartPole keeps the reference's 500 (cartpole.rs:297), the others count in 16 bits
+    if (cfg->kind == MGYM_CARTPOLE ? (cfg->max_episode_steps != 0u && cfg->max_episode_steps != 500u) : cfg->max_episode_steps > kMaxEpisodeSteps) {
+        char buf[160];
+        if (cfg->kind == MGYM_CARTPOLE) snprintf(buf, sizeof buf, "max_episode_steps (current value: %u): CartPole keeps the reference's 500 — 0 or 500 only", cfg->max_episode_steps);
+        else snprintf(buf, sizeof buf, "max_episode_steps (current value: %u) must be between 0 (off) and 65535", cfg->max_episode_steps);
         set_last_error(buf);
         return MGYM_ERR_BAD_CONFIG;
     }
@@ -308,6 +317,18 @@ int mgym_set_state(mgym_env* env, const void* blob) {
     return e->set_state(blob);
 }
 
+int mgym_get_elapsed_steps(mgym_env* env, uint32_t* out) {
+    ENV_OR_FAIL(env);
+    if (!out && e->n) return bad_arg("mgym_get_elapsed_steps: out is NULL");
+    return e->elapsed(out, nullptr);
+}
+
+int mgym_set_elapsed_steps(mgym_env* env, const uint32_t* in) {
+    ENV_OR_FAIL(env);
+    if (!in && e->n) return bad_arg("mgym_set_elapsed_steps: in is NULL");
+    return e->elapsed(nullptr, in);
+}
+
 int mgym_set_dispersion_override(mgym_env* env, const float* disp) {
     ENV_OR_FAIL(env);
     return e->set_dispersion(disp);
@@ -352,7 +373,8 @@ int mgym_get_info(mgym_env* env, char* buf, size_t cap) {
     if (!buf || cap == 0) return bad_arg("mgym_get_info: buf is NULL or cap is 0");
     static const char* const kinds[] = {"cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander"};
     std::string out = std::string("kind=") + kinds[e->kind] + "\nn_envs=" + std::to_string(e->n) + "\ndevice=" + std::to_string(e->cfg.device) +
-                      "\nauto_reset=" + ((e->cfg.flags & MGYM_FLAG_AUTO_RESET) ? "1" : "0") + "\nGPU_MAX_HW_QUEUES=" + e->hwq_env + "\n";
+                      "\nauto_reset=" + ((e->cfg.flags & MGYM_FLAG_AUTO_RESET) ? "1" : "0") + "\nmax_episode_steps=" + std::to_string(e->cfg.max_episode_steps) +
+                      "\nGPU_MAX_HW_QUEUES=" + e->hwq_env + "\n";
     int st = e->info(out);
     if (st != MGYM_OK) return st;
     if (out.size() + 1 > cap) { buf[0] = 0; return bad_arg("mgym_get_info: buffer too small"); }

@@ -125,6 +125,7 @@ struct LLConst {
     float maxMotorTorque;
     V2 poly_v[2][kMaxPoly], poly_n[2][kMaxPoly];
     int poly_count[2];
+    uint32_t max_steps;   // mgym_config::max_episode_steps (time_limit.h; not in the reference); 0: off.  Read where a step is finished, through LLDev::kd
 };
 
 struct Sweep { V2 localCenter, c0, c; float a0, a, alpha0; };

@@ -9,6 +9,7 @@
 
 #include "ll_world.h"
 #include "philox.h"
+#include "time_limit.h"
 
 namespace mgym {
 using namespace ll;
@@ -393,6 +394,10 @@ __device__ __forceinline__ void ll_build_scene(World& w, EnvRegs& e, const PolyT
     e.prev_some = false; e.prev_shaping = 0.0f;
     e.has_world = true; e.deterministic = deterministic;
 }
+
+// truncated flag of a step that ll_post_step has just finished (e.step already advanced, and only read here); the reference's is always
+// false (:1165).  The limit is a word of the constants in device memory — one scalar load where a step ends, no register held across the step
+__device__ __forceinline__ uint32_t ll_truncated(const LLDev& d, const EnvRegs& e) { return tl_ll_truncated(LLK(d).max_steps, e.step); }
 
 __device__ __forceinline__ void ll_dispersion(const LLDev& d, uint64_t i, const EnvRegs& e, float& d0, float& d1) {
     if (d.disp) { d0 = d.disp[i]; d1 = d.disp[d.n + i]; return; }

@@ -240,11 +240,11 @@ LLD void roll_write_obs(const LLDev& d, const LLIo& io, uint32_t t, uint32_t i, 
         for (int q = 0; q < 8; ++q) d.obs[(uint64_t)q * d.n_pad + i] = state[q];
     }
 }
-LLD void roll_write_scalars(const LLDev& d, const LLIo& io, uint32_t t, uint32_t i, float reward, uint32_t done) {
+LLD void roll_write_scalars(const LLDev& d, const LLIo& io, uint32_t t, uint32_t i, float reward, uint32_t done, uint32_t trunc) {
     const uint64_t o = (uint64_t)t * d.n + i;
     if (io.rew) io.rew[o] = reward;
     if (io.done_out) io.done_out[o] = (uint8_t)done;
-    if (io.trunc_out) io.trunc_out[o] = 0;  // :1165 truncated: false
+    if (io.trunc_out) io.trunc_out[o] = (uint8_t)trunc;  // :1165 truncated: false (unless max_episode_steps)
 }
 // the action of step t of environment i by the launch's action source (ll_roll_types.h RollPolicy); the next-action words are agent-scope (sc1) accesses,
 // like the records' leading lines on the free-flight path: their stores are complete before the environment's entry is published (vmcnt(0))
@@ -391,12 +391,13 @@ __device__ __forceinline__ void roll_contact_batch(const LLDev& d, const LLIo& i
             float state[8], reward; uint32_t done;
             ll_step_finish(w, e, action, state, reward, done);
             const uint32_t flags = (q.debug & (32u | 256u)) ? (F_HAS_WORLD | 7u) : ll_store(d, i, w, e);
-            route = (q.debug & (32u | 128u)) ? ROLL_RETIRE : roll_route(d, q, flags, (q.debug & 256u) ? 0u : done, t + 1u);
-            if (!(q.debug & 64u)) roll_write_scalars(d, io, t, i, reward, done);
+            const uint32_t trunc = ll_truncated(d, e);   // finished = done | truncated, to the reset queue like a done one
+            route = (q.debug & (32u | 128u)) ? ROLL_RETIRE : roll_route(d, q, flags, (q.debug & 256u) ? 0u : (done | trunc), t + 1u);
+            if (!(q.debug & 64u)) roll_write_scalars(d, io, t, i, reward, done, trunc);
             if (route != ROLL_TO_RESET && !(q.debug & 64u)) roll_write_obs(d, io, t, i, state, t + 1u == q.K);   // (a finished env's observation comes from its reset)
             roll_write_action<POLICY>(d, pol, t, i, action);
             if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route != ROLL_TO_RESET && t + 1u < q.K) RA_STORE(pol.next + i, ll_linear_action(pol.lin, state)); }   // step t + 1's, from this observation
-            is_done = done != 0u;
+            is_done = (done | trunc) != 0u;
             overflow |= w.overflow;
         }
         finished += (uint32_t)__popcll(__ballot(is_done));
@@ -726,7 +727,8 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                 const int how = ll_free_finish<true>(d, X.i, X.f, X.e, tab, X.s, state, reward, done, moved);
                 if (how == FREE_DONE) {
                     const uint32_t flags = roll_flags_after_step(X.f, X.e);
-                    const int route = roll_route(d, q, flags, done, X.t + 1u);
+                    const uint32_t trunc = ll_truncated(d, X.e);
+                    const int route = roll_route(d, q, flags, done | trunc, X.t + 1u);
                     roll_write_action<POLICY>(d, pol, X.t, X.i, X.act);
                     uint32_t lin_next = 0u;   // LINEAR: step t + 1's action, from this step's observation (straight from the registers)
                     if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route == ROLL_TO_FREE || route == ROLL_TO_CONTACT || route == ROLL_TO_LIGHT) lin_next = ll_linear_action(pol.lin, state); }
@@ -734,9 +736,9 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                         if constexpr (POLICY == ROLL_ACT_LINEAR) X.act = lin_next;
                         else X.act = roll_action<POLICY>(d, io, pol, X.i, X.t + 1u);
                     }
-                    roll_write_scalars(d, io, X.t, X.i, reward, done);
+                    roll_write_scalars(d, io, X.t, X.i, reward, done, trunc);
                     if (route != ROLL_TO_RESET) roll_write_obs(d, io, X.t, X.i, state, X.t + 1u == q.K);
-                    is_done = done != 0u;
+                    is_done = (done | trunc) != 0u;
                     // the slot's registers as a store + load of the record would leave them
                     X.f.flags = flags;
 #pragma unroll

@@ -92,11 +92,12 @@ __device__ __forceinline__ bool ll_free_pass(const LLDev& d, const LLIo& io, con
             if (how == FREE_DONE) {
                 ll_free_store(d, i, f, e);
                 if (io.rew) io.rew[i] = reward;
+                const uint32_t trunc = ll_truncated(d, e);
                 if (io.done_out) io.done_out[i] = (uint8_t)done;
-                if (io.trunc_out) io.trunc_out[i] = 0;  // :1165 truncated: false
+                if (io.trunc_out) io.trunc_out[i] = (uint8_t)trunc;  // :1165 truncated: false (unless max_episode_steps)
                 ll_write_obs(d, io, i, state);
-                to_reset = d.auto_reset && done;
-                is_done = done != 0u;
+                to_reset = d.auto_reset && (done | trunc);
+                is_done = (done | trunc) != 0u;
                 if (to_reset) d.env_class[i] = 2;   // finished: a fresh scene by the end of this call (ll_epilogue_kernel goes by this, not by the flag word)
             } else {
                 // a contact is being created at the end of the step: the contact path finishes it, from the post-solve
@@ -153,11 +154,12 @@ __device__ __forceinline__ void ll_free_lane_finish(const LLDev& d, const LLIo& 
     if (ll_free_finish(d, i, L.f, L.e, tab, L.s, state, reward, done, moved) == FREE_DONE) {
         ll_free_store(d, i, L.f, L.e);
         if (io.rew) io.rew[i] = reward;
+        const uint32_t trunc = ll_truncated(d, L.e);
         if (io.done_out) io.done_out[i] = (uint8_t)done;
-        if (io.trunc_out) io.trunc_out[i] = 0;  // :1165 truncated: false
+        if (io.trunc_out) io.trunc_out[i] = (uint8_t)trunc;  // :1165 truncated: false (unless max_episode_steps)
         ll_write_obs(d, io, i, state);
-        L.to_reset = d.auto_reset && done;
-        L.is_done = done != 0u;
+        L.to_reset = d.auto_reset && (done | trunc);
+        L.is_done = (done | trunc) != 0u;
         if (L.to_reset) d.env_class[i] = 2;
     } else {   // FREE_RESUME: a contact is being created at the end of the step
         ll_free_store_resume(d, i, L.f, L.e, moved);
@@ -217,10 +219,10 @@ ll_free_kernel(LLDev d, LLIo io) {
 }
 
 // outputs of a finished step + its deferred reset (shared by the worklist kernels)
-__device__ __forceinline__ void ll_emit(const LLDev& d, const LLIo& io, uint64_t i, const float state[8], float reward, uint32_t done) {
+__device__ __forceinline__ void ll_emit(const LLDev& d, const LLIo& io, uint64_t i, const float state[8], float reward, uint32_t done, uint32_t trunc) {
     if (io.rew) io.rew[i] = reward;
     if (io.done_out) io.done_out[i] = (uint8_t)done;
-    if (io.trunc_out) io.trunc_out[i] = 0;  // :1165 truncated: false
+    if (io.trunc_out) io.trunc_out[i] = (uint8_t)trunc;  // :1165 truncated: false (unless max_episode_steps)
     ll_write_obs(d, io, i, state);
 }
 
@@ -394,9 +396,10 @@ __device__ __forceinline__ void ll_contact_body(const LLDev& d, const LLIo& io, 
                 float state[8], reward; uint32_t done;
                 ll_step_finish(w, e, action, state, reward, done);
                 ll_store(d, i, w, e);
-                ll_emit(d, io, i, state, reward, done);
-                is_done = done != 0u;
-                to_reset = d.auto_reset && done;
+                const uint32_t trunc = ll_truncated(d, e);
+                ll_emit(d, io, i, state, reward, done, trunc);
+                is_done = (done | trunc) != 0u;
+                to_reset = d.auto_reset && (done | trunc);
                 if (to_reset) d.env_class[i] = 2;   // (see ll_free_pass)
             } else {
                 ll_store(d, i, w, e, true);
@@ -475,9 +478,10 @@ ll_toi_kernel(LLDev d, LLIo io, int round, int budget) {
                 float state[8], reward; uint32_t done;
                 ll_step_finish(w, e, io.act[i], state, reward, done);
                 ll_store(d, i, w, e);
-                ll_emit(d, io, i, state, reward, done);
-                is_done = done != 0u;
-                to_reset = d.auto_reset && done;
+                const uint32_t trunc = ll_truncated(d, e);
+                ll_emit(d, io, i, state, reward, done, trunc);
+                is_done = (done | trunc) != 0u;
+                to_reset = d.auto_reset && (done | trunc);
             } else {
                 ll_store(d, i, w, e, true);
                 to_toi = true;
@@ -556,10 +560,11 @@ ll_general_kernel(LLDev d, LLIo io, const uint32_t* __restrict__ list, const uin
             ll_env_step(w, e, tab, LLK(d), mem, action, d0, d1, state, reward, done);
             if (need_reset) { e.episode += 1u; break; }
             if (io.rew) io.rew[i] = reward;
+            const uint32_t trunc = ll_truncated(d, e);
             if (io.done_out) io.done_out[i] = (uint8_t)done;
-            if (io.trunc_out) io.trunc_out[i] = 0;
-            is_done = done != 0u;
-            if (!(d.auto_reset && done)) break;
+            if (io.trunc_out) io.trunc_out[i] = (uint8_t)trunc;
+            is_done = (done | trunc) != 0u;
+            if (!(d.auto_reset && (done | trunc))) break;
             if (list) { defer_reset = true; break; }  // compacted: ll_reset_kernel draws the new episode
             need_reset = true;
         }
@@ -919,6 +924,16 @@ __global__ void ll_export_kernel(LLDev d, uint32_t* __restrict__ blob) {
     blob[25 * d.n + i] = ST(C_STEP); blob[26 * d.n + i] = ST(C_EPISODE);
 }
 
+// mgym_get_elapsed_steps / mgym_set_elapsed_steps: the step counter (1 after reset(): its implicit step(0), :911-916, is not a caller's step) minus / plus 1
+__global__ void ll_get_elapsed_kernel(LLDev d, uint32_t* __restrict__ out) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d.n) out[i] = tl_ll_elapsed(ST(C_STEP));
+}
+__global__ void ll_set_elapsed_kernel(LLDev d, const uint32_t* __restrict__ in) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d.n) ST(C_STEP) = in[i] < 0xfffffffeu ? in[i] + 1u : 0xffffffffu;
+}
+
 // Testable::set_state (lunar_lander.rs:1444-1554) from blob words 0..19; counters from 25, 26
 __global__ void __launch_bounds__(kLLBlock) ll_import_kernel(LLDev d, const uint32_t* __restrict__ blob) {
     __shared__ PolyTab tab;
@@ -1105,6 +1120,7 @@ struct LunarLanderEnv final : Env {
 #endif
         dev.bucket = bucket;
         ll_make_const(dev.k, cfg.gravity, cfg.enable_wind, cfg.wind_power, cfg.turbulence_power);
+        dev.k.max_steps = cfg.max_episode_steps;
         MGYM_HIP(hipMalloc(&kdev, sizeof(LLConst)));
         MGYM_HIP(hipMemcpyAsync(kdev, &dev.k, sizeof(LLConst), hipMemcpyHostToDevice, stream));
         dev.kd = static_cast<const LLConst*>(kdev);
@@ -1683,6 +1699,14 @@ struct LunarLanderEnv final : Env {
         direct_possible = true;   // imported episode counters need not match the prepared ones
         hipLaunchKernelGGL(ll_import_kernel, dim3((unsigned)((n + kLLBlock - 1) / kLLBlock)), dim3(kLLBlock), 0, stream, dev, static_cast<const uint32_t*>(blob));
         if (fused_tail) { int st = rebuild_list(); if (st != MGYM_OK) return st; }
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+    int elapsed(uint32_t* out, const uint32_t* in) override {   // (the prepared next episodes are untouched: they are keyed by the episode counter alone)
+        if (n == 0) return MGYM_OK;
+        const dim3 g((unsigned)((n + 255) / 256)), b(256);
+        if (out) hipLaunchKernelGGL(ll_get_elapsed_kernel, g, b, 0, stream, dev, out);
+        else hipLaunchKernelGGL(ll_set_elapsed_kernel, g, b, 0, stream, dev, in);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }

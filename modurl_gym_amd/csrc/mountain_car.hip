@@ -11,9 +11,16 @@
 // episode[n] u32 (touched only by reset).  One lane owns 4 consecutive environments
 // (16-byte accesses).  Algorithmic bytes per env-step: 26 (state 8 R + 8 W, action 4 R,
 // reward 4 W, done 1 W, truncated 1 W).
+// Episode time limit (mgym_config::max_episode_steps, not in the reference — time_limit.h): elapsed[n] u16, one lane's 4 environments in ONE
+// 8-byte access, read and written by the time-limited instantiations only (TL = true: mgym_step 26 + 2 R + 2 W = 30 B per env-step; a rollout
+// keeps the count in registers, one read and one write per launch).  A handle without a limit launches the TL = false instantiations, which
+// are the kernels as they were: the count is then left alone (0 after a reset, not advanced).
+#include <type_traits>
+
 #include "common.h"
 #include "mgym_math.h"
 #include "philox.h"
+#include "time_limit.h"
 
 namespace mgym {
 
@@ -30,7 +37,19 @@ struct MountainCarDev {
     unsigned long long* done_count;  // kDoneShards partial counts of finished env-steps (mgym_episode_count)
     MountainCarParams p;
     int auto_reset;
+    uint16_t* elapsed;   // caller-visible steps since the env's last reset, saturating at 65535 (padded to n_pad like the state columns)
+    uint32_t limit;      // max_episode_steps; 0: off
 };
+
+typedef uint16_t mc_u16x4 __attribute__((ext_vector_type(4)));
+// a lane's four counters: one 8-byte access (i0 a multiple of 4)
+__device__ __forceinline__ void mc_load_elapsed4(const MountainCarDev& d, uint64_t i0, uint32_t (&el)[4]) {
+    const mc_u16x4 v = *reinterpret_cast<const mc_u16x4*>(d.elapsed + i0);
+    el[0] = v.x; el[1] = v.y; el[2] = v.z; el[3] = v.w;
+}
+__device__ __forceinline__ void mc_store_elapsed4(const MountainCarDev& d, uint64_t i0, const uint32_t (&el)[4]) {
+    __builtin_nontemporal_store(mc_u16x4{(uint16_t)el[0], (uint16_t)el[1], (uint16_t)el[2], (uint16_t)el[3]}, reinterpret_cast<mc_u16x4*>(d.elapsed + i0));
+}
 
 // done-mask reduction: per-lane counts of finished envs summed over the wave, one fire-and-forget atomic per wave
 __device__ __forceinline__ void mountaincar_flush_counts(const MountainCarDev& d, uint32_t finished, bool bad) {
@@ -91,7 +110,7 @@ __device__ __forceinline__ void mountaincar_step_one(const MountainCarParams& p,
     }
 }
 
-template <int VEC, bool CONT>
+template <int VEC, bool CONT, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out,
                         float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
@@ -103,7 +122,12 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
         const uint64_t i0 = g * VEC;
         float ps[VEC], vs[VEC], r[VEC];
         uint32_t a[VEC], dn[VEC];
+        uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u};   // (time limit only)
         const bool full = (VEC == 1) || (i0 + VEC <= d.n);
+        if constexpr (TL) {
+            if (VEC == 4) mc_load_elapsed4(d, i0, el);   // (the column is padded: a ragged last group may load it whole)
+            else el[0] = d.elapsed[i0];
+        }
         if (VEC == 4 && full) {
             float4 vp = *reinterpret_cast<const float4*>(d.pos + i0);
             float4 vv = *reinterpret_cast<const float4*>(d.vel + i0);
@@ -124,8 +148,10 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             mountaincar_step_one<CONT>(d.p, ps[k], vs[k], a[k], r[k], dn[k], bad);
-            finished += (dn[k] && (i0 + k < d.n)) ? 1u : 0u;
-            if (d.auto_reset && dn[k] && (i0 + k < d.n)) mountaincar_reset_one(d, i0 + k, ps[k], vs[k]);
+            uint32_t fin = dn[k];
+            if constexpr (TL) { el[k] = tl_advance(el[k]); tr[k] = tl_truncated(d.limit, el[k]); fin |= tr[k]; }
+            finished += (fin && (i0 + k < d.n)) ? 1u : 0u;
+            if (d.auto_reset && fin && (i0 + k < d.n)) { mountaincar_reset_one(d, i0 + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
         }
         if (VEC == 4 && full) {
             float4 op = make_float4(ps[0], ps[1 % VEC], ps[2 % VEC], ps[3 % VEC]);
@@ -141,7 +167,8 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
             if (done_out)
                 __builtin_nontemporal_store(dn[0] | (dn[1 % VEC] << 8) | (dn[2 % VEC] << 16) | (dn[3 % VEC] << 24),
                                             reinterpret_cast<uint32_t*>(done_out + i0));
-            if (trunc_out) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(trunc_out + i0));  // :328 truncated: false, always
+            if (trunc_out) __builtin_nontemporal_store(tr[0] | (tr[1] << 8) | (tr[2] << 16) | (tr[3] << 24), reinterpret_cast<uint32_t*>(trunc_out + i0));  // :328 truncated: false, always (TL: the time limit)
+            if constexpr (TL) mc_store_elapsed4(d, i0, el);
         } else {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -151,7 +178,8 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
                     if (obs_out) { obs_out[i] = ps[k]; obs_out[d.n + i] = vs[k]; }
                     if (rew) rew[i] = r[k];
                     if (done_out) done_out[i] = (uint8_t)dn[k];
-                    if (trunc_out) trunc_out[i] = 0;
+                    if (trunc_out) trunc_out[i] = (uint8_t)tr[k];
+                    if constexpr (TL) d.elapsed[i] = (uint16_t)el[k];
                 }
             }
         }
@@ -166,7 +194,7 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
 // reduced with __ballot + popcount for mgym_episode_count; resets are rare here (episodes last >= 100 steps) and stay
 // in place.
 typedef uint32_t mc_u32x4v __attribute__((ext_vector_type(4)));
-template <bool CONT, bool RESET>
+template <bool CONT, bool RESET, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out,
                          float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
@@ -187,18 +215,22 @@ mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, flo
         if (in) va = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(act + base) + off4);
         float ps[4] = {as_f32(vp.x), as_f32(vp.y), as_f32(vp.z), as_f32(vp.w)}, vs[4] = {as_f32(vv.x), as_f32(vv.y), as_f32(vv.z), as_f32(vv.w)}, r[4];
         uint32_t a[4] = {va.x, va.y, va.z, va.w}, dn[4];
+        uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u}, fin[4];   // (el / tr: time limit only)
+        if constexpr (TL) mc_load_elapsed4(d, base + lane_env, el);            // (padded to n_pad like the state columns: every lane may load)
         uint32_t any_done = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             mountaincar_step_one<CONT>(d.p, ps[k], vs[k], a[k], r[k], dn[k], bad);
-            any_done |= dn[k];
+            fin[k] = dn[k];
+            if constexpr (TL) { el[k] = tl_advance(el[k]); tr[k] = tl_truncated(d.limit, el[k]); fin[k] |= tr[k]; }
+            any_done |= fin[k];
         }
         const unsigned long long m = __ballot(in && any_done);
         if (m) {  // rare: count and (RESET) restart the finished envs in place
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                finished += (uint32_t)__popcll(__ballot(in && dn[k]));
-                if (RESET && in && dn[k]) mountaincar_reset_one(d, base + lane_env + k, ps[k], vs[k]);
+                finished += (uint32_t)__popcll(__ballot(in && fin[k]));
+                if (RESET && in && fin[k]) { mountaincar_reset_one(d, base + lane_env + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
             }
         }
         if (in) {
@@ -212,7 +244,8 @@ mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, flo
             if (rew) nt_store4(reinterpret_cast<float*>(reinterpret_cast<char*>(rew + base) + off4), make_float4(r[0], r[1], r[2], r[3]));
             if (done_out)
                 __builtin_nontemporal_store(dn[0] | (dn[1] << 8) | (dn[2] << 16) | (dn[3] << 24), reinterpret_cast<uint32_t*>(done_out + base + lane_env));
-            if (trunc_out) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));  // :328 truncated: false, always
+            if (trunc_out) __builtin_nontemporal_store(tr[0] | (tr[1] << 8) | (tr[2] << 16) | (tr[3] << 24), reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));  // :328 truncated: false, always (TL: the time limit)
+            if constexpr (TL) mc_store_elapsed4(d, base + lane_env, el);
         }
     }
     if ((threadIdx.x & 63) == 0 && finished)
@@ -236,7 +269,7 @@ struct McLinearPolicy { float w[3][2], b[3]; };
 // the force u 2^-23 - 1, uniform over the multiples of 2^-23 in [-1, 1).
 enum { MC_ROLL_TABLE = 0, MC_ROLL_LINEAR = 1, MC_ROLL_UNIFORM = 2 };
 struct McUniformPolicy { uint64_t seed; uint32_t call; };
-template <bool CONT, int POLICY = MC_ROLL_TABLE>
+template <bool CONT, int POLICY = MC_ROLL_TABLE, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
                            uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, McLinearPolicy lin = McLinearPolicy{}, uint32_t* __restrict__ act_out = nullptr,
@@ -251,6 +284,8 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
         float4 vp = *reinterpret_cast<const float4*>(d.pos + i0), vv = *reinterpret_cast<const float4*>(d.vel + i0);
         float ps[4] = {vp.x, vp.y, vp.z, vp.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w};
         Philox4 bits{};
+        uint32_t el[4] = {0u, 0u, 0u, 0u};   // (time limit only: the count lives in registers across the K steps)
+        if constexpr (TL) mc_load_elapsed4(d, i0, el);
         for (int t = 0; t < K; ++t) {
             const uint64_t off = (uint64_t)t * d.n + i0;
             uint32_t a[4], dn[4];
@@ -282,15 +317,18 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                 a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w;
             }
             float r[4];
+            uint32_t tr[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 mountaincar_step_one<CONT>(d.p, ps[k], vs[k], a[k], r[k], dn[k], bad);
-                finished += dn[k];
-                if (d.auto_reset && dn[k]) mountaincar_reset_one(d, i0 + k, ps[k], vs[k]);
+                uint32_t fin = dn[k];
+                if constexpr (TL) { el[k] = tl_advance(el[k]); tr[k] = tl_truncated(d.limit, el[k]); fin |= tr[k]; }
+                finished += fin;
+                if (d.auto_reset && fin) { mountaincar_reset_one(d, i0 + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
             }
             if (rew) nt_store4(rew + off, make_float4(r[0], r[1], r[2], r[3]));
             if (done_out) __builtin_nontemporal_store(dn[0] | (dn[1] << 8) | (dn[2] << 16) | (dn[3] << 24), reinterpret_cast<uint32_t*>(done_out + off));
-            if (trunc_out) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(trunc_out + off));
+            if (trunc_out) __builtin_nontemporal_store(tr[0] | (tr[1] << 8) | (tr[2] << 16) | (tr[3] << 24), reinterpret_cast<uint32_t*>(trunc_out + off));
             if (obs_out) {
                 float* o = obs_out + (uint64_t)t * 2 * d.n + i0;
                 nt_store4(o, make_float4(ps[0], ps[1], ps[2], ps[3]));
@@ -299,6 +337,7 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
         }
         nt_store4(d.pos + i0, make_float4(ps[0], ps[1], ps[2], ps[3]));
         nt_store4(d.vel + i0, make_float4(vs[0], vs[1], vs[2], vs[3]));
+        if constexpr (TL) mc_store_elapsed4(d, i0, el);
     }
     mountaincar_flush_counts(d, finished, bad);
 }
@@ -332,6 +371,7 @@ mountaincar_reset_kernel(MountainCarDev d, const uint8_t* __restrict__ m0, const
                 float p, v;
                 mountaincar_reset_one(d, i, p, v);
                 d.pos[i] = p; d.vel[i] = v;
+                d.elapsed[i] = 0;
                 if (obs_out) { obs_out[i] = p; obs_out[d.n + i] = v; }
             }
         }
@@ -352,16 +392,36 @@ __global__ void mountaincar_import_kernel(MountainCarDev d, const uint32_t* __re
     d.pos[i] = as_f32(blob[i]);
     d.vel[i] = as_f32(blob[d.n + i]);
     d.episode[i] = blob[2 * d.n + i];
+    d.elapsed[i] = 0;   // the blob stays 3 columns: an imported state starts its count at 0 (mgym_set_elapsed_steps overrides)
+}
+
+__global__ void mountaincar_get_elapsed_kernel(MountainCarDev d, uint32_t* __restrict__ out) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d.n) out[i] = d.elapsed[i];
+}
+
+__global__ void mountaincar_set_elapsed_kernel(MountainCarDev d, const uint32_t* __restrict__ in) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d.n) d.elapsed[i] = (uint16_t)tl_clamp(in[i]);
+}
+
+// host-side choice of an instantiation: f(std::bool_constant<continuous>, std::bool_constant<time limit>)
+template <class F>
+static void mc_dispatch(bool continuous, bool tl, F&& f) {
+    if (continuous) { if (tl) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else { if (tl) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
 }
 
 struct MountainCarEnv final : Env {
     bool continuous;
     void* base = nullptr;
+    void* el_base = nullptr;   // elapsed[n_pad] u16
     MountainCarDev dev{};
 
     explicit MountainCarEnv(bool c) : continuous(c) {}
     ~MountainCarEnv() override {
         if (base) (void)hipFree(base);
+        if (el_base) (void)hipFree(el_base);
     }
 
     bool use_step4 = !getenv("MGYM_MC_OLD_KERNEL");  // A/B knob: the per-thread grid-stride kernel of round 1
@@ -375,6 +435,10 @@ struct MountainCarEnv final : Env {
         dev.episode = reinterpret_cast<uint32_t*>(f + 2 * n_pad);
         dev.n = n; dev.seed = cfg.seed; dev.env_id_base = cfg.env_id_base; dev.err = d_err; dev.done_count = d_done;
         dev.auto_reset = (cfg.flags & MGYM_FLAG_AUTO_RESET) ? 1 : 0;
+        MGYM_HIP(hipMalloc(&el_base, n_pad * sizeof(uint16_t)));
+        MGYM_HIP(hipMemsetAsync(el_base, 0, n_pad * sizeof(uint16_t), stream));
+        dev.elapsed = static_cast<uint16_t*>(el_base);
+        dev.limit = cfg.max_episode_steps;
         MountainCarParams& p = dev.p;  // mountain_car.rs:35-40
         p.min_position = -1.2f; p.max_position = 0.6f; p.max_speed = 0.07f;
         p.goal_position = continuous ? 0.45f : 0.5f;
@@ -396,6 +460,7 @@ struct MountainCarEnv final : Env {
     int reset_deterministic(float* obs_out) override {  // mountain_car.rs:403-408: state = zeros (no reset())
         if (n == 0) return MGYM_OK;
         MGYM_HIP(hipMemsetAsync(dev.pos, 0, 2 * n_pad * sizeof(float), stream));
+        MGYM_HIP(hipMemsetAsync(dev.elapsed, 0, n_pad * sizeof(uint16_t), stream));
         if (obs_out) MGYM_HIP(hipMemsetAsync(obs_out, 0, 2 * n * sizeof(float), stream));
         return MGYM_OK;
     }
@@ -406,22 +471,20 @@ struct MountainCarEnv final : Env {
         bool vec_ok = aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) &&
                       (obs_out == nullptr || (aligned(obs_out, 16) && n % 4 == 0));
         dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
+        const bool tl = dev.limit != 0u;
         if (vec_ok && n % 4 == 0 && n <= (1ull << 27) && use_step4) {  // the structured 16-byte kernel
             const bool rs = dev.auto_reset;
-            if (continuous) { if (rs) hipLaunchKernelGGL((mountaincar_step4_kernel<true, true>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-                              else hipLaunchKernelGGL((mountaincar_step4_kernel<true, false>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc); }
-            else { if (rs) hipLaunchKernelGGL((mountaincar_step4_kernel<false, true>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-                   else hipLaunchKernelGGL((mountaincar_step4_kernel<false, false>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc); }
+            mc_dispatch(continuous, tl, [&](auto C, auto T) {
+                if (rs) hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, true, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+                else hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, false, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+            });
             MGYM_HIP(hipGetLastError());
             return MGYM_OK;
         }
-        if (continuous) {
-            if (vec_ok) hipLaunchKernelGGL((mountaincar_step_kernel<4, true>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-            else hipLaunchKernelGGL((mountaincar_step_kernel<1, true>), gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        } else {
-            if (vec_ok) hipLaunchKernelGGL((mountaincar_step_kernel<4, false>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-            else hipLaunchKernelGGL((mountaincar_step_kernel<1, false>), gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }
+        mc_dispatch(continuous, tl, [&](auto C, auto T) {
+            if (vec_ok) hipLaunchKernelGGL((mountaincar_step_kernel<4, decltype(C)::value, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+            else hipLaunchKernelGGL((mountaincar_step_kernel<1, decltype(C)::value, decltype(T)::value>), gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+        });
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
@@ -432,8 +495,9 @@ struct MountainCarEnv final : Env {
         bool vec_ok = n % 4 == 0 && aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && aligned(obs_out, 16);
         if (!vec_ok) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
         dim3 gv(grid_for(n / 4)), b(kBlock);
-        if (continuous) hipLaunchKernelGGL((mountaincar_rollout_kernel<true, MC_ROLL_TABLE>), gv, b, 0, stream, dev, act, K, obs_out, reward, done, trunc, McLinearPolicy{}, (uint32_t*)nullptr, McUniformPolicy{});
-        else hipLaunchKernelGGL((mountaincar_rollout_kernel<false, MC_ROLL_TABLE>), gv, b, 0, stream, dev, act, K, obs_out, reward, done, trunc, McLinearPolicy{}, (uint32_t*)nullptr, McUniformPolicy{});
+        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
+            hipLaunchKernelGGL((mountaincar_rollout_kernel<decltype(C)::value, MC_ROLL_TABLE, decltype(T)::value>), gv, b, 0, stream, dev, act, K, obs_out, reward, done, trunc, McLinearPolicy{}, (uint32_t*)nullptr, McUniformPolicy{});
+        });
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
@@ -448,8 +512,9 @@ struct MountainCarEnv final : Env {
         }
         const McUniformPolicy uni{policy_seed, policy_calls++};
         dim3 gv(grid_for(n / 4)), b(kBlock);
-        if (continuous) hipLaunchKernelGGL((mountaincar_rollout_kernel<true, MC_ROLL_UNIFORM>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni);
-        else hipLaunchKernelGGL((mountaincar_rollout_kernel<false, MC_ROLL_UNIFORM>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni);
+        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
+            hipLaunchKernelGGL((mountaincar_rollout_kernel<decltype(C)::value, MC_ROLL_UNIFORM, decltype(T)::value>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni);
+        });
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
@@ -465,8 +530,9 @@ struct MountainCarEnv final : Env {
         const int rows = continuous ? 1 : 3;   // policy: `rows` rows of (w_position, w_velocity, bias)
         for (int j = 0; j < rows; ++j) { lin.w[j][0] = policy[3 * j + 0]; lin.w[j][1] = policy[3 * j + 1]; lin.b[j] = policy[3 * j + 2]; }
         dim3 gv(grid_for(n / 4)), b(kBlock);
-        if (continuous) hipLaunchKernelGGL((mountaincar_rollout_kernel<true, MC_ROLL_LINEAR>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, lin, ao, McUniformPolicy{});
-        else hipLaunchKernelGGL((mountaincar_rollout_kernel<false, MC_ROLL_LINEAR>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, lin, ao, McUniformPolicy{});
+        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
+            hipLaunchKernelGGL((mountaincar_rollout_kernel<decltype(C)::value, MC_ROLL_LINEAR, decltype(T)::value>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, lin, ao, McUniformPolicy{});
+        });
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
@@ -489,6 +555,15 @@ struct MountainCarEnv final : Env {
         if (n == 0) return MGYM_OK;
         hipLaunchKernelGGL(mountaincar_import_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                            stream, dev, static_cast<const uint32_t*>(blob));
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+
+    int elapsed(uint32_t* out, const uint32_t* in) override {
+        if (n == 0) return MGYM_OK;
+        const dim3 g((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
+        if (out) hipLaunchKernelGGL(mountaincar_get_elapsed_kernel, g, b, 0, stream, dev, out);
+        else hipLaunchKernelGGL(mountaincar_set_elapsed_kernel, g, b, 0, stream, dev, in);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }

@@ -123,7 +123,7 @@ class VecEnv:
 
     def __init__(self, kind, n_envs=1, device=0, seed=0, env_id_base=0, auto_reset=False, stream=None,
                  sutton_barto_reward=False, is_euler=True, goal_velocity=0.0, gravity=-10.0, enable_wind=False,
-                 wind_power=15.0, turbulence_power=1.5):
+                 wind_power=15.0, turbulence_power=1.5, max_episode_steps=0):
         lib = L.load()
         cfg = L.Config()
         _check(lib.mgym_default_config(kind, C.byref(cfg)))
@@ -133,11 +133,16 @@ class VecEnv:
         cfg.goal_velocity = goal_velocity
         cfg.gravity, cfg.enable_wind = gravity, int(enable_wind)
         cfg.wind_power, cfg.turbulence_power = wind_power, turbulence_power
+        # episode time limit (include/mgym.h): 0 = off, the reference's behaviour; CartPole keeps the reference's 500
+        if not 0 <= int(max_episode_steps) <= 0xFFFFFFFF:
+            raise BadConfigError(L.ERR_BAD_CONFIG, f"max_episode_steps must be between 0 and 65535, got {max_episode_steps}")
+        cfg.max_episode_steps = int(max_episode_steps)
         h = C.c_void_p()
         self._h = None
         _check(lib.mgym_create(C.byref(cfg), C.byref(h)))
         self._h, self._lib = h, lib
         self.kind, self.n, self.device = kind, int(n_envs), device
+        self.max_episode_steps = int(max_episode_steps)
         spec = get_spec(kind)
         self.obs_dim, self.n_actions, self.action_is_float = spec.obs_dim, spec.n_actions, bool(spec.action_is_float)
         self.action_dtype = np.float32 if self.action_is_float else np.uint32
@@ -366,6 +371,28 @@ class VecEnv:
         _check(self._lib.mgym_set_state(self._h, d.ptr))
         self.sync()
 
+    def elapsed_steps_device(self, out):
+        """mgym_get_elapsed_steps: caller-visible steps since each env's last reset into a device uint32[n] (on the env's stream)"""
+        _check(self._lib.mgym_get_elapsed_steps(self._h, _ptr(out)))
+
+    def set_elapsed_steps_device(self, src):
+        _check(self._lib.mgym_set_elapsed_steps(self._h, _ptr(src)))
+
+    def elapsed_steps(self):
+        d = DeviceArray(max(self.n, 1), np.uint32, self.device)
+        self.elapsed_steps_device(d)
+        self.sync()
+        return d.numpy()[: self.n]
+
+    def set_elapsed_steps(self, elapsed):
+        a = np.ascontiguousarray(elapsed, np.uint32)
+        assert a.shape == (self.n,)
+        if self.n == 0:
+            return
+        d = DeviceArray.from_numpy(a, self.device)
+        self.set_elapsed_steps_device(d)
+        self.sync()
+
     def set_dispersion(self, disp):
         if disp is None:
             self._disp = None
@@ -419,22 +446,23 @@ class MountainCarV0(_SingleEnv):
     """mountain_car.rs:10-339"""
     KIND = L.MOUNTAINCAR
 
-    def __init__(self, device=0, goal_velocity=0.0, seed=0):
-        super().__init__(device, seed, goal_velocity=goal_velocity)
+    def __init__(self, device=0, goal_velocity=0.0, seed=0, max_episode_steps=0):
+        super().__init__(device, seed, goal_velocity=goal_velocity, max_episode_steps=max_episode_steps)
 
 
 class MountainCarContinuousV0(_SingleEnv):
     """Not in the reference (BASELINE config 3); gymnasium semantics, parity unpinned."""
     KIND = L.MOUNTAINCAR_CONT
 
-    def __init__(self, device=0, goal_velocity=0.0, seed=0):
-        super().__init__(device, seed, goal_velocity=goal_velocity)
+    def __init__(self, device=0, goal_velocity=0.0, seed=0, max_episode_steps=0):
+        super().__init__(device, seed, goal_velocity=goal_velocity, max_episode_steps=max_episode_steps)
 
 
 class LunarLanderV3(_SingleEnv):
     """lunar_lander.rs:232-1201"""
     KIND = L.LUNARLANDER
 
-    def __init__(self, device=0, gravity=-10.0, enable_wind=False, wind_power=15.0, turbulence_power=1.5, seed=0):
+    def __init__(self, device=0, gravity=-10.0, enable_wind=False, wind_power=15.0, turbulence_power=1.5, seed=0,
+                 max_episode_steps=0):
         super().__init__(device, seed, gravity=gravity, enable_wind=enable_wind, wind_power=wind_power,
-                         turbulence_power=turbulence_power)
+                         turbulence_power=turbulence_power, max_episode_steps=max_episode_steps)

@@ -161,6 +161,22 @@ class TorchVecEnv:
         self.env.rollout_uniform_device(int(seed), K, act, obs, rew, done, trunc)
         return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
 
+    def elapsed_steps(self):
+        """Caller-visible steps since each env's last reset (mgym_get_elapsed_steps; the count of `max_episode_steps`, which is passed
+        through `**params`): a fresh int32 [n] tensor, stream-ordered on torch's current stream."""
+        self._bind_stream()
+        out = self._torch.empty(self.n, dtype=self._torch.int32, device=self.device)
+        self.env.elapsed_steps_device(out)
+        return out
+
+    def set_elapsed_steps(self, elapsed):
+        """mgym_set_elapsed_steps from an int32 [n] tensor on the env's device (MountainCar clamps to 65535)."""
+        self._bind_stream()
+        torch = self._torch
+        if elapsed.device != self.device or tuple(elapsed.shape) != (self.n,):
+            raise ValueError("elapsed must be a tensor of shape [n] on the env's device")
+        self.env.set_elapsed_steps_device(elapsed.to(torch.int32).contiguous())
+
     def observation_view(self):
         """Zero-copy [obs_dim, n] tensor over the engine-owned observation columns (column stride n_pad)."""
         ptr, stride = self.env.observation_device()

@@ -167,7 +167,8 @@ pub struct MountainCarV0 {
 #[bon]
 impl MountainCarV0 {
     /// Same builder as the reference (mountain_car.rs:25-34): `device`, `render` (feature `rendering`),
-    /// `goal_velocity` (default 0.0); superset: `gpu`, `seed`.
+    /// `goal_velocity` (default 0.0); superset: `gpu`, `seed`, `max_episode_steps` (episode time limit, 0 = off as in the
+    /// reference, at most 65535; include/mgym.h).
     #[builder]
     pub fn new(
         #[builder(default = &Device::Cpu)] device: &Device,
@@ -177,6 +178,7 @@ impl MountainCarV0 {
         #[builder(default = 0.0)] goal_velocity: f32,
         #[builder(default = 0)] gpu: i32,
         seed: Option<u64>,
+        #[builder(default = 0)] max_episode_steps: u32,
     ) -> Self {
         #[cfg(feature = "rendering")]
         if render {
@@ -187,6 +189,7 @@ impl MountainCarV0 {
         cfg.n_envs = 1;
         cfg.seed = seed_or_entropy(seed);
         cfg.goal_velocity = goal_velocity;
+        cfg.max_episode_steps = max_episode_steps;
         Self { inner: Single::new(cfg), device: device.clone() }
     }
 }
@@ -208,7 +211,7 @@ pub struct LunarLanderV3 {
 impl LunarLanderV3 {
     /// Same builder as the reference (lunar_lander.rs:278-291): gravity −10, enable_wind false, wind_power 15,
     /// turbulence_power 1.5, `device` (by value, default CPU), `render` (feature `rendering`), `seed: Option<u64>`;
-    /// superset: `gpu`.  Panics with the reference's message when gravity is outside (−12, 0) (lunar_lander.rs:292-296)
+    /// superset: `gpu`, `max_episode_steps` (episode time limit, 0 = off as in the reference, at most 65535; include/mgym.h).  Panics with the reference's message when gravity is outside (−12, 0) (lunar_lander.rs:292-296)
     /// and prints its two range recommendations (:298-310).
     #[builder]
     pub fn new(
@@ -222,6 +225,7 @@ impl LunarLanderV3 {
         render: bool,
         seed: Option<u64>,
         #[builder(default = 0)] gpu: i32,
+        #[builder(default = 0)] max_episode_steps: u32,
     ) -> Self {
         assert!(
             -12.0 < gravity && gravity < 0.0,
@@ -246,6 +250,7 @@ impl LunarLanderV3 {
         cfg.enable_wind = enable_wind as i32;
         cfg.wind_power = wind_power;
         cfg.turbulence_power = turbulence_power;
+        cfg.max_episode_steps = max_episode_steps;
         Self { inner: Single::new(cfg), device }
     }
 }

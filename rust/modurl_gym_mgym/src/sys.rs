@@ -49,7 +49,7 @@ pub struct mgym_config {
     pub enable_wind: i32,
     pub wind_power: f32,
     pub turbulence_power: f32,
-    pub reserved: u32,
+    pub max_episode_steps: u32,
 }
 
 #[repr(C)]
@@ -118,6 +118,8 @@ unsafe extern "C" {
     pub fn mgym_observation_aos(env: *mut mgym_env, out_aos: *mut f32) -> c_int;
     pub fn mgym_get_state(env: *mut mgym_env, blob: *mut c_void) -> c_int;
     pub fn mgym_set_state(env: *mut mgym_env, blob: *const c_void) -> c_int;
+    pub fn mgym_get_elapsed_steps(env: *mut mgym_env, out: *mut u32) -> c_int;
+    pub fn mgym_set_elapsed_steps(env: *mut mgym_env, input: *const u32) -> c_int;
     pub fn mgym_reset_deterministic(env: *mut mgym_env, obs_out: *mut f32) -> c_int;
     pub fn mgym_set_dispersion_override(env: *mut mgym_env, disp: *const f32) -> c_int;
     pub fn mgym_get_spec(kind: c_int, spec: *mut mgym_spec) -> c_int;

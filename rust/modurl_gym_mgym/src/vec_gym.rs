@@ -208,6 +208,13 @@ impl VecGym {
     pub fn get_state(&mut self, blob: &mut DeviceBuf<f32>) -> Result<(), MgymError> {
         check(unsafe { mgym_get_state(self.env, blob.as_ptr() as _) })
     }
+    /// The elapsed count of `mgym_config::max_episode_steps` (caller-visible steps since each env's last reset), device `u32[n]`.
+    pub fn get_elapsed_steps(&mut self, out: &mut DeviceBuf<u32>) -> Result<(), MgymError> {
+        check(unsafe { mgym_get_elapsed_steps(self.env, out.as_ptr()) })
+    }
+    pub fn set_elapsed_steps(&mut self, input: &DeviceBuf<u32>) -> Result<(), MgymError> {
+        check(unsafe { mgym_set_elapsed_steps(self.env, input.as_ptr() as *const u32) })
+    }
     pub fn reset_deterministic(&mut self, obs_out: &mut DeviceBuf<f32>) -> Result<(), MgymError> {
         check(unsafe { mgym_reset_deterministic(self.env, obs_out.as_ptr()) })
     }
