@@ -35,7 +35,7 @@ namespace mgym {
 
 // entry -> environment.  The value goes through an empty asm: hipcc (ROCm 7.2, clang 22) otherwise turns `(uint64_t)(ent & 0xffffff) * record
 // bytes` into a 24-bit multiply, drops the mask as redundant for it and then re-forms a full v_mad_u64_u32 on the UNMASKED word — records of
-// entries with a step index > 0 were addressed 16 Mi records too far (found with rocgdb on the faulting wave: ll_load's first load).
+// entries with a step index > 0 were addressed 16 Mi records too far (the faulting wave stood at ll_load's first load).
 LLD uint32_t roll_env_of(uint32_t ent) { uint32_t i = ent & kRollEnvMask; asm volatile("" : "+v"(i)); return i; }
 #define RQ_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define RQ_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)

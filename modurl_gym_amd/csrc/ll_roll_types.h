@@ -57,7 +57,7 @@ struct RollQ {
                                 // launch does not end with a few late starters taking their K steps one 0.6 ms contact batch at a time
     unsigned long long* stat;   // [RS_COUNT] (zeroed before every launch)
     unsigned long long* trace;  // diagnosis (MGYM_LL_ROLL_TRACE=file): [grid][kRollTraceLen] events {ticks since the wave started << 8 | what it begins}; or null
-    uint32_t debug;             // diagnosis (MGYM_LL_ROLL_DEBUG): 1 stop after the seed phase, 2 no free-flight mode (every environment through the contact path), 4 resident waves never switch to a contact batch
+    uint32_t debug;             // diagnosis stage bits (the host passes 0): 1 stop after the seed phase, 2 no free-flight mode (every environment through the contact path), 4 resident waves never switch to a contact batch
 };
 constexpr int kRollTraceLen = 512;
 enum { RT_SEED = 1, RT_CONTACT, RT_LIGHT, RT_RESET, RT_FREE, RT_IDLE, RT_END, RT_TOI };

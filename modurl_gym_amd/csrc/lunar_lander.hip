@@ -26,10 +26,11 @@
 // round 2 — ll_contact_kernel on the caller's stream beside ll_free_kernel + a short second contact launch on a helper stream (fork /
 // join by events), then the same epilogue.  MGYM_LL_STAGED_RESET=0 computes a reset when the episode ends instead of preparing it ahead.
 // mgym_rollout (K >= 8): ONE persistent launch, ll_roll.h.
-// The product library carries these two orders and the knobs its tests use (mgym_get_info lists them).  The older orders and block sizes
-// that only the measurements of rounds 2-3 used — counter memsets + ll_classify_kernel per step, select / copy launches, sequential kernels,
-// follow-up time-of-impact launches, contact blocks of 8 / 16 / 40 / 48 lanes, other free-flight occupancies — are compiled with -DLL_DIAG
-// only (tools/ build their own binaries that way).
+// These two orders (LunarLanderEnv::step_single_launch, step_multi_stream) and the debugging aid MGYM_LL_GENERAL_ONLY (every env through
+// ll_general_kernel: step_general_only) are all there is.  Every environment knob of the wrapper is a row of kLLKnobs, read once by
+// ll_read_options; mgym_get_info lists them from the same table.  The older orders and block sizes that the measurements of rounds 2-3
+// used (sequential kernels, select / copy launches, follow-up time-of-impact launches, contact blocks of 8 .. 48 lanes) are gone; what
+// they left inside the kernels — the toi_budget argument, d.fused_tail, d.bucket == 2, the L_TOI0.. list slots — is inert.
 #include <math.h>
 #include <stdio.h>
 #include <vector>
@@ -228,9 +229,8 @@ __device__ __forceinline__ void ll_emit(const LLDev& d, const LLIo& io, uint64_t
 
 // The contact path over a compacted list (`which` = L_GENERAL, or L_LATE for the second launch of the overlapped order):
 // wind / engines, then b2World::Step — Collide, the 180-sweep island solve, position iterations, new contacts, SolveTOI
-// with all its sub-steps (toi_budget < 0, the default).  With toi_budget >= 0 (MGYM_LL_TOI_ROUNDS, profiling only) SolveTOI
-// stops after that many sub-steps and the env goes, with its unfinished state in the C_MID columns, onto L_TOI0 for
-// ll_toi_kernel.
+// with all its sub-steps (toi_budget < 0: what every launch passes).  With toi_budget >= 0 (a relic of the follow-up time-of-impact
+// launches of round 2) SolveTOI stops after that many sub-steps and the env goes, with its unfinished state in the C_MID columns, onto L_TOI0.
 // where a wave of the contact path takes its environments from: entry q of a list that is filled from both ends
 // (c0 entries from the front — rounded up to c0_up slots —, c1 from the back, `back` = index of the last slot)
 // back_first (the product's bucketing, 64-lane blocks): the c1 touching envs from the back come FIRST (rounded up to c0_up slots, which then
@@ -250,9 +250,7 @@ LLD uint64_t ll_list_entry(const ContactList& L, uint64_t q, uint64_t total) {
 }
 
 // The contact path over a compacted list: wind / engines, then b2World::Step — Collide, the 180-sweep island solve, position
-// iterations, new contacts, SolveTOI with all its sub-steps (toi_budget < 0, the default).  With toi_budget >= 0
-// (MGYM_LL_TOI_ROUNDS, profiling only) SolveTOI stops after that many sub-steps and the env goes, with its unfinished state in the
-// C_MID columns, onto L_TOI0 for ll_toi_kernel.  The wave takes entries q_first + lane, q_first + q_stride + lane, ...
+// iterations, new contacts, SolveTOI with all its sub-steps (toi_budget < 0: what every launch passes; see above).  The wave takes entries q_first + lane, q_first + q_stride + lane, ...
 // (S.tab must have been staged.)
 template <int BLK>
 __device__ __forceinline__ void ll_contact_body(const LLDev& d, const LLIo& io, int toi_budget, const ContactList& CL, uint64_t q_first, uint64_t q_stride,
@@ -442,62 +440,6 @@ ll_contact_kernel(LLDev d, LLIo io, int toi_budget, int which) {
                          (which == L_LATE ? d.vc_far_late : d.vc_far) + (uint64_t)blockIdx.x * BLK, (int)(gridDim.x * BLK), S, not_reset, overflow, finished);
     ll_report(d, not_reset, overflow, finished);
 }
-
-#ifdef LL_DIAG
-// Stage 3 of mgym_step, rounds r = 0 .. kToiRounds-1 over ever shorter lists: continue b2World::SolveTOI of the envs on
-// L_TOI0 + r by `budget` sub-steps (advance the body to its earliest impact, solve the TOI island, re-evaluate that body's
-// times of impact); finished envs get the tail of the step (observation, reward, termination), the others move on to
-// L_TOI0 + r + 1.  The last round runs with budget < 0 (to the end).  Per general env-step the reference does 0 sub-steps
-// 74 % of the time, 1: 17 %, 2: 7 %, >= 3: 2 % (tools/ll_work_stats.c) — inside one launch every wave would wait for its
-// slowest lane through all of them.
-template <int BLK>
-__global__ void __launch_bounds__(BLK)
-ll_toi_kernel(LLDev d, LLIo io, int round, int budget) {
-    __shared__ PolyTab tab;
-    __shared__ VConstraint s_vc[kSolverCap * BLK];
-    LL_HOT_DECL(BLK);
-    LL_TMP_DECL(BLK);
-    stage_tab(tab, LLK(d));
-    PConstraint l_pc[kSolverCap];
-    CSolverMem mem;
-    mem.vc = &s_vc[threadIdx.x]; mem.vc_stride = BLK; mem.vc_near = kSolverCap; mem.vc_far = nullptr; mem.vc_far_stride = 0; mem.pc = l_pc; mem.pc_stride = 1; mem.cap = kSolverCap;
-    uint32_t overflow = 0u;
-    uint32_t finished = 0;
-    const uint32_t* list = d.work_list + (uint64_t)(L_TOI0 + round) * d.n_pad;
-    const uint64_t total = d.work_count[L_TOI0 + round];
-    for (uint64_t q0 = (uint64_t)blockIdx.x * BLK; q0 < total; q0 += (uint64_t)gridDim.x * BLK) {  // block-uniform
-        const uint64_t q = q0 + threadIdx.x;
-        uint64_t i = 0;
-        bool to_toi = false, to_reset = false, is_done = false;
-        if (q < total) {
-            i = list[q];
-            World w; EnvRegs e;
-            w.t = LL_TMP_PTR();
-            ll_load(d, i, w, e, hot, true);
-            if (ll_step_continue(w, tab, LLK(d), mem, budget)) {
-                float state[8], reward; uint32_t done;
-                ll_step_finish(w, e, io.act[i], state, reward, done);
-                ll_store(d, i, w, e);
-                const uint32_t trunc = ll_truncated(d, e);
-                ll_emit(d, io, i, state, reward, done, trunc);
-                is_done = (done | trunc) != 0u;
-                to_reset = d.auto_reset && (done | trunc);
-            } else {
-                ll_store(d, i, w, e, true);
-                to_toi = true;
-            }
-            overflow |= w.overflow;
-        }
-        if (round + 1 < kToiRounds) ll_push(d, L_TOI0 + round + 1, to_toi, (uint32_t)i);  // (never set when budget < 0)
-        ll_push(d, L_RESET, to_reset, (uint32_t)i);
-        finished += (uint32_t)__popcll(__ballot(is_done));
-    }
-    ll_flush_done(d, finished);
-    if (__any(overflow & 1u) && (threadIdx.x & 63) == 0) atomicOr(d.err, DEV_ERR_CONTACT_OVERFLOW);
-    if (__any(overflow & 2u) && (threadIdx.x & 63) == 0) atomicOr(d.err, DEV_ERR_SOLVER_OVERFLOW);
-}
-
-#endif   // LL_DIAG
 
 // Whole general step in ONE launch (no time-of-impact rounds): the declined resets of L_RESET_SLOW (list != nullptr),
 // Testable::reset_deterministic, and the MGYM_LL_GENERAL_ONLY debugging aid.  list == nullptr: every env with
@@ -758,48 +700,6 @@ __global__ void __launch_bounds__(256) ll_policy_kernel(const float* __restrict_
 // reset kernels on a third stream while later steps run, and the auto-reset of a finished env is a copy.
 // The prepared state carries its episode counter: it fits iff shadow episode == live episode + 1; whatever changed the
 // live counter in between (mgym_reset, mgym_set_state) just sends the env down the direct path (L_RESET_DIRECT) once.
-#ifdef LL_DIAG   // (the unfused order's two launches; the fused order does both inside ll_epilogue_kernel)
-// (1) which finished envs have a fitting prepared state: those go onto L_PREP (their reset is the copy below, and their
-//     NEXT reset is prepared afterwards), the others onto L_RESET_DIRECT.  One thread per list entry, one atomic per block and list.
-__global__ void __launch_bounds__(256)
-ll_apply_select_kernel(LLDev d, const uint32_t* __restrict__ shadow) {
-    __shared__ uint32_t s_cnt[5];
-    const uint32_t* list = d.work_list + (uint64_t)L_RESET * d.n_pad;
-    const uint64_t total = d.work_count[L_RESET];
-    for (uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x; q0 < total; q0 += (uint64_t)gridDim.x * blockDim.x) {  // block-uniform
-        const uint64_t q = q0 + threadIdx.x;
-        uint64_t i = 0;
-        bool fits = false, direct = false;
-        if (q < total) {
-            i = list[q];
-            fits = ST_AT(shadow, C_EPISODE) == ST(C_EPISODE) + 1u;
-            direct = !fits;
-        }
-        ll_push_block(d, L_PREP, fits, (uint32_t)i, s_cnt);
-        ll_push_block(d, L_RESET_DIRECT, direct, (uint32_t)i, s_cnt);
-    }
-}
-// (2) the copy: one block per env of L_PREP, one thread per word (the columns of one env lie n_pad words apart)
-__global__ void __launch_bounds__(128)
-ll_apply_copy_kernel(LLDev d, const uint32_t* __restrict__ shadow, const float* __restrict__ shadow_obs, LLIo io) {
-    const uint32_t* list = d.work_list + (uint64_t)L_PREP * d.n_pad;
-    const uint64_t total = d.work_count[L_PREP];
-    const int t = threadIdx.x;
-    for (uint64_t q = blockIdx.x; q < total; q += gridDim.x) {
-        const uint64_t i = list[q];
-        if (t < C_CONTACT) ST(t) = ST_AT(shadow, t);
-        else if (t < C_CONTACT + kSlots) ST(C_CONTACT + 16 * (t - C_CONTACT)) = 0u;  // a fresh world has no contacts
-        else if (t < C_CONTACT + kSlots + 8) {
-            const int k = t - C_CONTACT - kSlots;
-            const float o = shadow_obs[(uint64_t)k * d.n_pad + i];
-            d.obs[(uint64_t)k * d.n_pad + i] = o;
-            if (io.obs_out) io.obs_out[(uint64_t)k * d.n + i] = o;
-        }
-    }
-}
-
-#endif   // LL_DIAG
-
 // The END of a step in the fused order, one launch instead of counter memsets + classify (next step) + select + copy:
 //  (1) staged resets: every finished env (L_RESET) whose prepared next episode fits gets it copied in (and goes onto L_PREP: its
 //      NEXT reset is prepared afterwards), the others go onto L_RESET_DIRECT for the reset kernel behind this one;
@@ -954,19 +854,55 @@ __global__ void __launch_bounds__(kLLBlock) ll_import_kernel(LLDev d, const uint
     ll_store(d, i, w, e);
 }
 
-// tuning values of the persistent rollout launch: fixed in the product, read from the environment in -DLL_DIAG builds (tools/ll_roll_sweep.sh)
-#ifdef LL_DIAG
-#define LL_TUNE(name, dflt) (getenv(name) ? (uint32_t)atoi(getenv(name)) : (dflt))
-#else
-#define LL_TUNE(name, dflt) (dflt)
-#endif
+// Every environment knob of the wrapper.  ll_read_options() is the only place in this file that reads the environment (once per handle, when it is
+// made); mgym_get_info's knobs= line is this table's names.  A default of -1 means "by population": init() resolves it.
+struct LLOptions {
+    int general_only, gen_block, single_launch, staged, bucket, contact_blocks, vc_near, roll_enabled, roll_min_k, roll_helper, roll_stats, roll_trace;
+    std::string roll_trace_file;
+};
+struct LLKnob { const char* name; int LLOptions::*value; int dflt; bool by_presence /* set at all = 1, whatever the value */; const char* meaning; };
+static const LLKnob kLLKnobs[] = {
+    {"MGYM_LL_GENERAL_ONLY", &LLOptions::general_only, 0, true, "debugging aid: every env through ll_general_kernel, no worklists, no staged resets, no persistent rollout"},
+    {"MGYM_LL_GENERAL_BLOCK", &LLOptions::gen_block, 0, false, "lanes per block of the contact path, 32 or 64; 0: by population"},
+    {"MGYM_LL_SINGLE_LAUNCH", &LLOptions::single_launch, 1, false, "1: contact path, free-flight path and reset preparation in ONE launch (needs 32-lane contact blocks); 0: the multi-stream order"},
+    {"MGYM_LL_STAGED_RESET", &LLOptions::staged, 1, false, ">= 1: auto-resets are prepared ahead and copied in (ll_epilogue_kernel); 0: computed when the episode ends"},
+    {"MGYM_LL_BUCKET", &LLOptions::bucket, -1, false, "multi-stream order, the contact list by kind: 0 in index order, 1 (and above) touching envs first in blocks of their own; -1: by population"},
+    {"MGYM_LL_CONTACT_BLOCKS", &LLOptions::contact_blocks, -1, false, "single-launch step: blocks the contact list is dealt out over (0: always 32 lanes per block); -1: 900"},
+    {"MGYM_LL_VC_NEAR", &LLOptions::vc_near, kVcNearLds, false, "test knob: velocity constraints per lane kept in LDS, 0 .. kVcNearLds (the rest in the far workspace)"},
+    {"MGYM_LL_ROLLOUT", &LLOptions::roll_enabled, -1, false, "mgym_rollout as one persistent launch: 0 never (K x step), 1 always; -1: by population"},
+    {"MGYM_LL_ROLLOUT_MIN_K", &LLOptions::roll_min_k, -1, false, "shorter rollouts run as K x step; -1: by population"},
+    {"MGYM_LL_ROLL_HELPER", &LLOptions::roll_helper, 0, false, "free-flight helper waves beside the rollout's main launch: 0 never, 1 always, -1 by population"},
+    {"MGYM_LL_ROLL_STATS", &LLOptions::roll_stats, 0, true, "diagnosis: after every rollout, where its waves spent their time (stderr; synchronises)"},
+    {"MGYM_LL_ROLL_TRACE", &LLOptions::roll_trace, 0, true, "diagnosis: =file, what every wave of a rollout launch did when (written after each launch; synchronises)"},
+};
+static LLOptions ll_read_options() {
+    LLOptions o{};
+    for (const LLKnob& k : kLLKnobs) {
+        const char* v = getenv(k.name);
+        o.*k.value = !v ? k.dflt : k.by_presence ? 1 : atoi(v);
+        if (v && k.value == &LLOptions::roll_trace) o.roll_trace_file = v;
+    }
+    return o;
+}
+
+// Tuning values of the persistent rollout launch (what each one means: RollQ, ll_roll_types.h), as the sweeps of round 4 left them
+// (measured with a since-removed diagnostic build that read them from the environment).
+constexpr uint32_t kRollContactMin = 32u, kRollHeavyMin = 16u, kRollHeavyMax = 32u, kRollTailLive = 32768u, kRollTailLanes = 4u;
+constexpr uint32_t kRollToiSplit = 7u, kRollToiMin = 24u, kRollKeepMin = 24u;
+// (with the helper waves on — the main waves live on the contact path — light batches that keep their residents too, and a rotation after 3 steps: 262 144 envs
+// K = 64 0.68 -> 0.62 ms per step, K = 16 0.77 -> 0.76, K = 8 unchanged; profiles/r04_lunarlander/rollout_tuning_with_helper_waves.txt)
+constexpr uint32_t kRollKeep = 3u, kRollFair = 0u, kRollHeavyNarrow = 12u;
+constexpr uint32_t kRollResetMin = 16u, kRollFreeMin = 32u, kRollResidency = 3u, kRollRefillMin = 8u, kRollHelperMin = 256u;
+constexpr unsigned kRollMainPerCu = 3u, kRollHelperPerCu = 2u;   // with the helper waves: main waves / helper blocks per CU (see init())
+static_assert(kRollHeavyMax >= 1u && kRollHeavyMax <= 32u && kRollTailLanes >= 1u && kRollTailLanes <= 32u && kRollHeavyNarrow >= 1u && kRollHeavyNarrow <= kRollHeavyMax, "batches are at most 32 lanes wide");
+
 struct LunarLanderEnv final : Env {
     void* base = nullptr;
     void* obs_base = nullptr;
     void* work_base = nullptr;
     void* kdev = nullptr;
     void* vc_far_base = nullptr;
-    hipStream_t aux = nullptr;          // helper stream of the overlapped launch order
+    hipStream_t aux = nullptr;          // helper stream of the multi-stream launch order
     hipStream_t roll_aux = nullptr;     // the rollout's free-flight helper waves: a stream of their own at the default priority (created with the helpers)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     void* shadow_base = nullptr;        // staged resets: shadow state columns [C_COUNT][n_pad] and observation [8][n_pad]
@@ -976,65 +912,19 @@ struct LunarLanderEnv final : Env {
     // Staged resets: every env has a fitting prepared episode (shadow episode == live + 1) from the moment a staged reset of ALL envs
     // has prepared them, and keeps one (each copy-in queues the next preparation; a fresh scene spawns far above the highest terrain, so
     // preparing it on the free-flight path cannot fail) UNLESS something else moves an episode counter or resets without preparing:
-    // mgym_set_state, a dispersion override, a masked or unstaged reset, steps captured into a graph (they reset directly).  Only then
+    // mgym_set_state, a dispersion override, a masked or unstaged reset, a rollout's persistent launch.  Only then
     // can a finished env need the direct path, and only then does step() launch its two (normally empty) kernels behind the epilogue.
     bool direct_possible = true;
     bool prep_due = false;              // a preparation has been marked (mark_prepare) and not launched yet
     bool ev_prep_valid = false;
-    int staged_in_graph = getenv("MGYM_LL_STAGED_IN_GRAPH") ? atoi(getenv("MGYM_LL_STAGED_IN_GRAPH")) : 1;  // fused order: captured steps keep the staged resets (0: they reset directly)
     bool prep_pending = false;          // work was put on aux2 that `stream` has not waited for yet
-    int staged = getenv("MGYM_LL_STAGED_RESET") ? atoi(getenv("MGYM_LL_STAGED_RESET")) : 1;  // 1 (default): auto-resets are prepared ahead (see ll_apply_select_kernel)
-    uint8_t* env_class = nullptr;       // [n] class of each env for this step (ll_classify_kernel): 0 free flight, 1 contact path
-#ifdef LL_DIAG
-    int overlap = getenv("MGYM_LL_OVERLAP") ? atoi(getenv("MGYM_LL_OVERLAP")) : -1;  // 1 (default): contact kernel beside the free-flight kernel (see step()); 0: one after the other
-#else
-    int overlap = 1;
-#endif
+    uint8_t* env_class = nullptr;       // [n] class of each env for this step (ll_classify_kernel / ll_epilogue_kernel): 0 free flight, 1 contact path
     LLDev dev{};
-    bool general_only = getenv("MGYM_LL_GENERAL_ONLY") != nullptr;
-    int gen_block = getenv("MGYM_LL_GENERAL_BLOCK") ? atoi(getenv("MGYM_LL_GENERAL_BLOCK")) : 0;   // lanes per block of the contact kernel; 0: by population (init)
-    // the contact list by kind (multi-stream order): -1 by population (init) | 0 in index order | 1 the envs with a touching contact at the back of
-    // the list and taken FIRST, in blocks of their own (the long blocks start first, the short ones fill the end) | 2 (-DLL_DIAG) dealt out evenly.
-    // ms per step, 0 | 1, same box (profiles/r04_lunarlander/contact_list_by_kind.txt): 524 288 envs 1.37 | 1.57 (the step is still its slowest block, and a
-    // block of 64 touching envs is slower than one with a few of them), 655 360: 1.58 | 1.60, 786 432: 2.11 | 1.70, 1 Mi: 2.45 | 2.20, 2 Mi: 5.44 | 4.67
-    // (bound by SIMD occupancy: blocks of one kind keep more of their lanes busy).  The two ends as launches of their own — the touching end in 32-lane
-    // blocks with their helper lanes, the rest in 64-lane blocks — were slower at every size (1 Mi: 2.97): built, measured, not kept.
-    int bucket = getenv("MGYM_LL_BUCKET") ? atoi(getenv("MGYM_LL_BUCKET")) : -1;
-#ifdef LL_DIAG
-    int toi_block = getenv("MGYM_LL_TOI_BLOCK") ? atoi(getenv("MGYM_LL_TOI_BLOCK")) : 32;          // lanes per block of the time-of-impact round kernels
-#endif
-    // Launch structure of the contact path.  Measured on MI355X (profiles/r02_lunarlander/tune_launch_structure.txt), 262 144
-    // envs, ms per step: whole world.step in the contact kernel, envs in index order 1.96 (default) | the same with
-    // touching / non-touching envs bucketed into separate waves 2.12 | time-of-impact sub-steps in 1 / 4 follow-up
-    // launches over compacted lists 2.33 / 3.02 | 16- or 8-lane blocks 2.6-3.7.  The kernel's duration is its SLOWEST
-    // wave's dependent chain (island solve + up to 5 sub-steps of ~0.16 ms each), not a throughput limit: concentrating
-    // heavy lanes (bucketing) lengthens that wave, and follow-up launches serialise the same chain behind launch
-    // boundaries and a state round trip.  The alternatives stay selectable for profiling:
-#ifdef LL_DIAG
-    int toi_first = getenv("MGYM_LL_TOI_FIRST") ? atoi(getenv("MGYM_LL_TOI_FIRST")) : 0;  // with MGYM_LL_TOI_ROUNDS: sub-steps taken inside the contact kernel first
-    int toi_rounds = getenv("MGYM_LL_TOI_ROUNDS") ? atoi(getenv("MGYM_LL_TOI_ROUNDS")) : 0;  // 0: none; 1 .. kToiRounds launches of ll_toi_kernel
-    int fused_tail = getenv("MGYM_LL_FUSED_TAIL") ? atoi(getenv("MGYM_LL_FUSED_TAIL")) : 1;  // 1 (default): the fused order of step() (ll_epilogue_kernel); needs the overlapped order and none of the profiling knobs
-#else
-    static constexpr int toi_rounds = 0;
-    int fused_tail = 1;   // (0 only with MGYM_LL_GENERAL_ONLY, the debugging aid that sends every env through ll_general_kernel)
-#endif
-    int single_launch = getenv("MGYM_LL_SINGLE_LAUNCH") ? atoi(getenv("MGYM_LL_SINGLE_LAUNCH")) : 1;  // 1 (default): contact path, free-flight path and reset preparation in ONE launch (ll_step_kernel); needs the fused order and 32-lane contact blocks
-    int contact_blocks = getenv("MGYM_LL_CONTACT_BLOCKS") ? atoi(getenv("MGYM_LL_CONTACT_BLOCKS")) : -1;  // single-launch step: blocks the contact list is dealt out over (default 900: as many as run at once beside the free-flight role; 0: always 32 lanes per block)
-    int resume = getenv("MGYM_LL_RESUME") ? atoi(getenv("MGYM_LL_RESUME")) : 1;  // 1 (default): envs the free-flight kernel stops at a new contact are resumed after their island solve (0: redone from the old state)
-#ifdef LL_DIAG
-    int free_occ = getenv("MGYM_LL_FREE_OCC") ? atoi(getenv("MGYM_LL_FREE_OCC")) : 2;  // waves/SIMD the free kernel is compiled for
-#endif
-    int vc_near_limit = kVcNearLds;     // velocity constraints per lane the contact kernel keeps in LDS (init(); MGYM_LL_VC_NEAR lowers it: test knob)
-    // mgym_rollout as ONE persistent launch (ll_roll.h); MGYM_LL_ROLLOUT=0: K x step(), 1: always, unset: below 491 520 envs — above, K steps of the
-    // multi-stream order are as fast or faster (524 288 envs, K = 64: 1.34 ms per step against 1.30; 1 Mi: 2.63 against 2.15: both bound by SIMD
-    // occupancy there, and the step's free-flight kernel runs at two waves per SIMD; profiles/r04_lunarlander/rollout_by_population.txt)
-    int roll_enabled = getenv("MGYM_LL_ROLLOUT") ? atoi(getenv("MGYM_LL_ROLLOUT")) : -1;
-    // free-flight helper waves beside the main launch: 0 never (the default), 1 always, -1 by population (from 163 840 envs).  OFF by default: with them a launch hung —
-    // waves of both kernels standing still — once in ~75 stress runs (tools/ll_roll_stress.sh: 4 hangs in ~350 runs, on either helper stream), never in 100 runs without them
-    // or in the day's hundreds of runs before they existed; the cause was not found in the time left of round 4.  They are worth 4-6 %.
-    int roll_helper = getenv("MGYM_LL_ROLL_HELPER") ? atoi(getenv("MGYM_LL_ROLL_HELPER")) : 0;
+    // The knobs as read, until init() has resolved them: from then on the values this handle runs with (staged, single_launch and roll_enabled also
+    // depend on the configuration).
+    LLOptions opt = ll_read_options();
+    bool fused_tail = true;             // the contact list of the NEXT step is kept valid at all times (rebuild_list); false only for the general-only debugging aid
     unsigned roll_helper_grid = 0;
-    int roll_min_k = getenv("MGYM_LL_ROLLOUT_MIN_K") ? atoi(getenv("MGYM_LL_ROLLOUT_MIN_K")) : -1;   // (-1: 8 from 163 840 envs, 12 below: init)   // shorter rollouts: K x step() (the launch's last environments take their last steps alone: ~2-3 ms, measured)
     void* roll_ring = nullptr;
     void* roll_ctl = nullptr;
     void* roll_vc_far = nullptr;
@@ -1070,24 +960,71 @@ struct LunarLanderEnv final : Env {
     }
 
     int init() override {
-        // Contact-kernel block size and launch order (profiles/r02_lunarlander/population_block_overlap_matrix.txt, ms per step,
+        // ---- the knobs that default by population, and what the configuration leaves of the others ----
+        // Contact-path block size and launch order (profiles/r02_lunarlander/population_block_overlap_matrix.txt, ms per step,
         // 32-lane / 64-lane blocks, sequential -> overlapped order):
         //     131 072 envs  1.47 -> 1.26 / 1.62 -> 1.39        524 288 envs  2.60 -> 2.09 / 2.35 -> 1.73
         //     262 144 envs  1.64 -> 1.30 / 1.89 -> 1.55      2 097 152 envs  7.59 -> 7.74 / 6.82 -> 6.16
         // 32-lane blocks (which also afford the World record in LDS) give the shortest waves: best while the whole
         // worklist is co-resident.  Beyond that the kernel is bound by wave slots — one 512-register wave per SIMD, four
         // blocks per CU by LDS — and 64-lane blocks (World record in scratch, working storage in LDS) carry twice
-        // the environments per slot.  The overlapped order (contact kernel beside the free-flight kernel, see step()) pays
+        // the environments per slot.  The overlapped order (contact kernel beside the free-flight kernel, see step_multi_stream()) pays
         // at every size once the blocks are chosen this way.
         // (round 3, single-launch step with 32-lane blocks against the multi-stream order with 64-lane blocks: 393 216 envs 1.54 / 1.57 ms,
         // 524 288: 2.04 / 1.68, 1 Mi: 3.81 / 2.86, 2 Mi: 7.38 / 6.11 — profiles/r03_lunarlander/population_block_matrix.txt)
         // (round 4, after the 64-lane blocks began to deal their time-of-impact evaluations out over the wave: 360 448 envs 1.26 / 1.29, 393 216: 1.39 / 1.30,
         // 425 984: 1.46 / 1.29 — profiles/r04_lunarlander/block_switch_by_population.txt)
-        if (gen_block == 0) gen_block = n >= 376832 ? 64 : 32;
-#ifndef LL_DIAG
-        if (gen_block != 32 && gen_block != 64) { set_last_error("MGYM_LL_GENERAL_BLOCK: 32 or 64 (other contact-block sizes exist in -DLL_DIAG builds only)"); return MGYM_ERR_BAD_CONFIG; }
-#endif
-        if (overlap < 0) overlap = 1;
+        // The contact path stays ONE kernel that takes world.step with all its sub-steps, envs in index order (profiles/r02_lunarlander/tune_launch_structure.txt,
+        // 262 144 envs, ms per step: 1.96 | touching / non-touching envs bucketed into separate waves 2.12 | time-of-impact sub-steps in 1 / 4 follow-up
+        // launches over compacted lists 2.33 / 3.02 | 16- or 8-lane blocks 2.6-3.7; measured in round 2 with a since-removed diagnostic build).  Its duration
+        // is its SLOWEST wave's dependent chain (island solve + up to 5 sub-steps of ~0.16 ms each), not a throughput limit: concentrating heavy lanes
+        // lengthens that wave, and follow-up launches serialise the same chain behind launch boundaries and a state round trip.
+        if (opt.gen_block == 0) opt.gen_block = n >= 376832 ? 64 : 32;
+        if (opt.gen_block != 32 && opt.gen_block != 64) { set_last_error("MGYM_LL_GENERAL_BLOCK: 32 or 64"); return MGYM_ERR_BAD_CONFIG; }
+        fused_tail = !opt.general_only;
+        opt.single_launch = opt.single_launch && fused_tail && opt.gen_block == 32;
+        // The contact list by kind (multi-stream order): 0 in index order | 1 the envs with a touching contact at the back of the list and taken FIRST, in
+        // blocks of their own (the long blocks start first, the short ones fill the end).  ms per step, 0 | 1, same box
+        // (profiles/r04_lunarlander/contact_list_by_kind.txt): 524 288 envs 1.37 | 1.57 (the step is still its slowest block, and a
+        // block of 64 touching envs is slower than one with a few of them), 655 360: 1.58 | 1.60, 786 432: 2.11 | 1.70, 1 Mi: 2.45 | 2.20, 2 Mi: 5.44 | 4.67
+        // (bound by SIMD occupancy: blocks of one kind keep more of their lanes busy).  The two ends as launches of their own — the touching end in 32-lane
+        // blocks with their helper lanes, the rest in 64-lane blocks — were slower at every size (1 Mi: 2.97): built, measured, not kept.
+        if (opt.bucket < 0) opt.bucket = (!opt.single_launch && opt.gen_block == 64 && n >= 688128) ? 1 : 0;
+        if (opt.single_launch) opt.bucket = 0;   // (its contact role deals ONE list out over its blocks)
+        if (opt.bucket > 1) opt.bucket = 1;
+        // contact blocks that run at once beside the free-flight role: 900 of the 1 024 one-wave-per-SIMD slots (measured 750 .. 1 000 at
+        // 65 536 .. 327 680 envs: flat within 1-2 % from 850 up, profiles/r03_lunarlander/block_lanes_by_population.txt)
+        if (opt.contact_blocks < 0) opt.contact_blocks = 900;
+        if (opt.vc_near < 0) opt.vc_near = 0;
+        if (opt.vc_near > kVcNearLds) opt.vc_near = kVcNearLds;
+        // Staged resets (pay while the step is bound by the contact kernel's chain: 131 072 envs 1.43 -> 1.36 ms per step, 262 144 1.50 -> 1.46,
+        // 393 216 1.67 -> 1.60; a population that fills every wave slot gains nothing from moving the reset work and loses to the
+        // extra launches: 524 288 envs 1.86 -> 1.83, 1 Mi envs 3.53 -> 3.84 — with one column per word.  With records the copy of a prepared
+        // state moves nine whole lines and staging pays at every size: 524 288 envs 1.55 -> 1.46, 786 432 2.27 -> 2.18, 1 Mi 2.57 -> 2.52,
+        // 2 Mi 5.67 -> 5.56 — profiles/r03_lunarlander/population_block_matrix.txt)
+        opt.staged = opt.staged >= 1 && (cfg.flags & MGYM_FLAG_AUTO_RESET) && !opt.general_only;
+        // mgym_rollout as ONE persistent launch (ll_roll.h) below 491 520 envs — above, K steps of the multi-stream order are as fast or faster
+        // (524 288 envs, K = 64: 1.34 ms per step against 1.30; 1 Mi: 2.63 against 2.15: both bound by SIMD occupancy there, and the step's
+        // free-flight kernel runs at two waves per SIMD; profiles/r04_lunarlander/rollout_by_population.txt).
+        // (Records are addressed by 32-bit byte offsets there: n_pad x 1152 B < 4 GiB.)
+        if (opt.roll_enabled < 0) opt.roll_enabled = n < 491520 ? 1 : 0;
+        opt.roll_enabled = opt.roll_enabled && !opt.general_only && n > 0 && n <= kRollEnvMask && (uint64_t)n_pad * kRec * 4ull < 0xffffffffull;
+        // Shorter rollouts run as K x step() (the launch's last environments take their last steps alone: ~2-3 ms, measured).
+        // 8-step rollouts of small populations are no faster than 8 steps (131 072 envs: 0.88 ms per step-equivalent against 0.85, 65 536: 0.80 / 0.80; K = 16: 0.70 / 0.85
+        // and 0.62 / 0.79): the persistent launch from 12 steps there, from 8 at 163 840 envs and more
+        if (opt.roll_min_k < 0) opt.roll_min_k = n >= 163840 ? 8 : 12;
+        // Free-flight helper waves (ll_rollout_free_kernel) beside the rollout's main launch.  OFF by default: with them a launch hung — waves of both kernels
+        // standing still — once in ~75 repeated runs (4 hangs in ~350 runs, on either helper stream), never in 100 runs without them or in the day's hundreds
+        // of runs before they existed; the cause was not found in the time left of round 4.  They are worth 4-6 %.
+        // The main waves fill a SIMD each (256 + 256 registers), so they get three SIMDs of every CU and the helpers — two waves per SIMD — the fourth.
+        // 262 144 envs, ms per step-equivalent without | with (profiles/r04_lunarlander/rollout_helper_waves.txt): K = 8 0.91 | 0.87, K = 16 0.81 | 0.77,
+        // K = 64 0.71 | 0.68; the helpers then take 86 % of the free-flight steps at 46 us of SIMD time per 64 env-steps against 79 in a main wave, and the
+        // 768 main waves are busy with the contact path throughout (35 of 45 ms).  Two SIMDs per CU for the helpers: 1.05 (the contact path is the larger
+        // share); four main waves per CU: no helper ever becomes resident and the launch runs as before (0.71) — the helpers are an accelerator, never a dependency.
+        // Small populations end a launch with a longer tail than busy phase, and there a fourth main wave per CU is worth more than the helpers:
+        // 65 536 envs K = 16 0.71 | 0.81, 98 304: 0.66 | 0.70, 131 072: 0.72 | 0.64 (K = 8: 0.78 | 0.82), 196 608: 0.77 | 0.73 (K = 8: 0.90 | 0.85) — by population: on from 163 840 envs.
+        if (opt.roll_helper < 0) opt.roll_helper = n >= 163840 ? 1 : 0;
+
         obs_dim = 8;
         state_cols = 27;
         MGYM_HIP(hipMalloc(&base, (size_t)ll_state_words(n_pad) * sizeof(uint32_t)));
@@ -1105,44 +1042,31 @@ struct LunarLanderEnv final : Env {
         dev.disp = nullptr;
         dev.n = n; dev.n_pad = n_pad; dev.seed = cfg.seed; dev.env_id_base = cfg.env_id_base; dev.err = d_err; dev.done_count = d_done;
         dev.auto_reset = (cfg.flags & MGYM_FLAG_AUTO_RESET) ? 1 : 0;
-        dev.resume = resume && !general_only;
-        // contact blocks that run at once beside the free-flight role: 900 of the 1 024 one-wave-per-SIMD slots (measured 750 .. 1 000 at
-        // 65 536 .. 327 680 envs: flat within 1-2 % from 850 up, profiles/r03_lunarlander/block_lanes_by_population.txt)
-        if (contact_blocks < 0) contact_blocks = 900;
-        dev.contact_blocks = contact_blocks;
-        fused_tail = fused_tail && overlap && !general_only && toi_rounds == 0;
+        dev.resume = !opt.general_only;   // envs the free-flight path stops at a new contact are resumed after their island solve
+        dev.contact_blocks = opt.contact_blocks;
         dev.fused_tail = fused_tail;
-        single_launch = single_launch && fused_tail && gen_block == 32 && resume;
-        if (bucket < 0) bucket = (!single_launch && gen_block == 64 && n >= 688128) ? 1 : 0;
-        if (single_launch) bucket = 0;   // (its contact role deals ONE list out over its blocks)
-#ifndef LL_DIAG
-        if (bucket > 1) bucket = 1;
-#endif
-        dev.bucket = bucket;
+        dev.bucket = opt.bucket;
         ll_make_const(dev.k, cfg.gravity, cfg.enable_wind, cfg.wind_power, cfg.turbulence_power);
         dev.k.max_steps = cfg.max_episode_steps;
         MGYM_HIP(hipMalloc(&kdev, sizeof(LLConst)));
         MGYM_HIP(hipMemcpyAsync(kdev, &dev.k, sizeof(LLConst), hipMemcpyHostToDevice, stream));
         dev.kd = static_cast<const LLConst*>(kdev);
         // far velocity constraints of the contact kernel: one column per lane of its (bounded) grid, [constraint][lane].  The main
-        // launch and the late launch of the overlapped order run concurrently, so each gets a slice of its own, sized from the
+        // launch and the late launch of the multi-stream order run concurrently, so each gets a slice of its own, sized from the
         // grids step() really launches (MGYM_LL_VC_NEAR=0, a test knob, sends every constraint there: kSolverCap per lane).
-        vc_near_limit = getenv("MGYM_LL_VC_NEAR") ? atoi(getenv("MGYM_LL_VC_NEAR")) : kVcNearLds;
-        if (vc_near_limit < 0) vc_near_limit = 0;
-        if (vc_near_limit > kVcNearLds) vc_near_limit = kVcNearLds;
+        const size_t per_lane = (size_t)(kSolverCap - opt.vc_near);
         {
-            const size_t per_lane = (size_t)(kSolverCap - vc_near_limit);
             // (single-launch step: every wave of the free-flight role may take envs through the contact path itself: a slice per such block)
-            const size_t lanes_main = (size_t)main_contact_grid() * gen_block, lanes_late = (size_t)(single_launch ? free2_grid() : late_contact_grid()) * 32;
+            const size_t lanes_main = (size_t)main_contact_grid() * opt.gen_block, lanes_late = (size_t)(opt.single_launch ? free2_grid() : late_contact_grid()) * 32;
             MGYM_HIP(hipMalloc(&vc_far_base, per_lane * (lanes_main + lanes_late) * sizeof(VConstraint)));
             dev.vc_far = static_cast<VConstraint*>(vc_far_base);
             dev.vc_far_late = dev.vc_far + per_lane * lanes_main;
-            dev.vc_near = vc_near_limit;
+            dev.vc_near = opt.vc_near;
         }
         {   // the helper stream carries the work that is NOT on the critical path: lowest priority (1 Mi envs: 3.65 -> 3.52 ms per step)
             int lo = 0, hi = 0;
             MGYM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            MGYM_HIP(hipStreamCreateWithPriority(&aux, hipStreamNonBlocking, getenv("MGYM_LL_AUX_PRIO") ? atoi(getenv("MGYM_LL_AUX_PRIO")) : lo));
+            MGYM_HIP(hipStreamCreateWithPriority(&aux, hipStreamNonBlocking, lo));
         }
         MGYM_HIP(hipMalloc((void**)&env_class, n_pad));
         MGYM_HIP(hipMemsetAsync(env_class, 0, n_pad, stream));
@@ -1151,13 +1075,7 @@ struct LunarLanderEnv final : Env {
         MGYM_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
         dev.split = 0;
         dev.prep = 0; dev.episode_src = nullptr;
-        // (pays while the step is bound by the contact kernel's chain: 131 072 envs 1.43 -> 1.36 ms per step, 262 144 1.50 -> 1.46,
-        // 393 216 1.67 -> 1.60; a population that fills every wave slot gains nothing from moving the reset work and loses to the
-        // extra launches: 524 288 envs 1.86 -> 1.83, 1 Mi envs 3.53 -> 3.84 — with one column per word.  With records the copy of a prepared
-        // state moves nine whole lines and staging pays at every size: 524 288 envs 1.55 -> 1.46, 786 432 2.27 -> 2.18, 1 Mi 2.57 -> 2.52,
-        // 2 Mi 5.67 -> 5.56 — profiles/r03_lunarlander/population_block_matrix.txt)
-        staged = staged >= 1 && (cfg.flags & MGYM_FLAG_AUTO_RESET) && !general_only;
-        if (staged) {
+        if (opt.staged) {
             MGYM_HIP(hipMalloc(&shadow_base, (size_t)ll_state_words(n_pad) * sizeof(uint32_t)));
             MGYM_HIP(hipMemsetAsync(shadow_base, 0, (size_t)ll_state_words(n_pad) * sizeof(uint32_t), stream));
             MGYM_HIP(hipMalloc(&shadow_obs, (size_t)8 * n_pad * sizeof(float)));
@@ -1170,13 +1088,8 @@ struct LunarLanderEnv final : Env {
             MGYM_HIP(hipEventCreateWithFlags(&ev_free_done, hipEventDisableTiming));
         }
         // mgym_rollout's persistent launch: rings of >= n slots per queue, one wave per SIMD as many as are resident at once, a slice of
-        // far-constraint workspace per wave.  (Records are addressed by 32-bit byte offsets there: n_pad x 1152 B < 4 GiB.)
-        if (roll_enabled < 0) roll_enabled = n < 491520 ? 1 : 0;
-        roll_enabled = roll_enabled && !general_only && n > 0 && n <= kRollEnvMask && (uint64_t)n_pad * kRec * 4ull < 0xffffffffull;
-        // 8-step rollouts of small populations are no faster than 8 steps (131 072 envs: 0.88 ms per step-equivalent against 0.85, 65 536: 0.80 / 0.80; K = 16: 0.70 / 0.85
-        // and 0.62 / 0.79): the persistent launch from 12 steps there, from 8 at 163 840 envs and more
-        if (roll_min_k < 0) roll_min_k = n >= 163840 ? 8 : 12;
-        if (roll_enabled) {
+        // far-constraint workspace per wave.
+        if (opt.roll_enabled) {
             uint64_t cap = 64;
             while (cap < n) cap <<= 1;
             rq.mask = (uint32_t)(cap - 1);
@@ -1185,30 +1098,10 @@ struct LunarLanderEnv final : Env {
             rq.ring = static_cast<unsigned long long*>(roll_ring);
             rq.ctl = static_cast<uint32_t*>(roll_ctl);
             rq.stat = reinterpret_cast<unsigned long long*>(rq.ctl + RC_WORDS * 32);
-            rq.contact_min = LL_TUNE("MGYM_LL_ROLL_CONTACT_MIN", 32u);
-            rq.heavy_min = LL_TUNE("MGYM_LL_ROLL_HEAVY_MIN", 16u);
-            rq.heavy_max = LL_TUNE("MGYM_LL_ROLL_HEAVY_MAX", 32u);
-            if (rq.heavy_max > 32u) rq.heavy_max = 32u;
-            if (rq.heavy_max < 1u) rq.heavy_max = 1u;
-            rq.tail_live = LL_TUNE("MGYM_LL_ROLL_TAIL_LIVE", 32768u);
-            rq.tail_lanes = LL_TUNE("MGYM_LL_ROLL_TAIL_LANES", 4u);
-            if (rq.tail_lanes > 32u) rq.tail_lanes = 32u;
-            if (rq.tail_lanes < 1u) rq.tail_lanes = 1u;
-            rq.toi_split = LL_TUNE("MGYM_LL_ROLL_TOI_SPLIT", 7u);
-            rq.toi_min = LL_TUNE("MGYM_LL_ROLL_TOI_MIN", 24u);
-            rq.keep_min = LL_TUNE("MGYM_LL_ROLL_KEEP_MIN", 24u);
-            // (with the helper waves on — the main waves live on the contact path — light batches that keep their residents too, and a rotation after 3 steps: 262 144 envs
-            // K = 64 0.68 -> 0.62 ms per step, K = 16 0.77 -> 0.76, K = 8 unchanged; profiles/r04_lunarlander/rollout_tuning_with_helper_waves.txt)
-            rq.keep = LL_TUNE("MGYM_LL_ROLL_KEEP", 3u);
-            rq.fair = LL_TUNE("MGYM_LL_ROLL_FAIR", 0u);
-            rq.heavy_narrow = LL_TUNE("MGYM_LL_ROLL_HEAVY_NARROW", 12u);
-            if (rq.heavy_narrow > rq.heavy_max) rq.heavy_narrow = rq.heavy_max;
-            if (rq.heavy_narrow < 1u) rq.heavy_narrow = 1u;
-            rq.reset_min = LL_TUNE("MGYM_LL_ROLL_RESET_MIN", 16u);
-            rq.free_min = LL_TUNE("MGYM_LL_ROLL_FREE_MIN", 32u);
-            rq.residency = LL_TUNE("MGYM_LL_ROLL_RESIDENCY", 3u);
-            rq.refill_min = LL_TUNE("MGYM_LL_ROLL_REFILL_MIN", 8u);
-            rq.debug = LL_TUNE("MGYM_LL_ROLL_DEBUG", 0u);
+            rq.contact_min = kRollContactMin; rq.heavy_min = kRollHeavyMin; rq.heavy_max = kRollHeavyMax; rq.tail_live = kRollTailLive; rq.tail_lanes = kRollTailLanes;
+            rq.toi_split = kRollToiSplit; rq.toi_min = kRollToiMin; rq.keep_min = kRollKeepMin; rq.keep = kRollKeep; rq.fair = kRollFair; rq.heavy_narrow = kRollHeavyNarrow;
+            rq.reset_min = kRollResetMin; rq.free_min = kRollFreeMin; rq.residency = kRollResidency; rq.refill_min = kRollRefillMin; rq.helper_min = kRollHelperMin;
+            rq.debug = 0u;
             ll_rollout_ring_init(stream, rq);
             int per_cu = 0, dev_id = 0;
             hipDeviceProp_t prop;
@@ -1217,26 +1110,13 @@ struct LunarLanderEnv final : Env {
             if (ll_rollout_blocks_per_cu(&per_cu) != MGYM_OK) return MGYM_ERR_HIP;
             if (per_cu < 1) per_cu = 1;
             uint64_t g = (uint64_t)per_cu * (uint64_t)prop.multiProcessorCount;
-            // Free-flight helper waves (ll_rollout_free_kernel) beside the main launch: the main waves fill a SIMD each (256 + 256 registers), so they
-            // get three SIMDs of every CU and the helpers — two waves per SIMD — the fourth.  262 144 envs, ms per step-equivalent without | with
-            // (profiles/r04_lunarlander/rollout_helper_waves.txt): K = 8 0.91 | 0.87, K = 16 0.81 | 0.77, K = 64 0.71 | 0.68; the helpers then take 86 % of the
-            // free-flight steps at 46 us of SIMD time per 64 env-steps against 79 in a main wave, and the 768 main waves are busy with the contact
-            // path throughout (35 of 45 ms).  Two SIMDs per CU for the helpers: 1.05 (the contact path is the larger share); four main waves per CU:
-            // no helper ever becomes resident and the launch runs as before (0.71) — the helpers are an accelerator, never a dependency.
-            // Small populations end a launch with a longer tail than busy phase, and there a fourth main wave per CU is worth more than the helpers:
-            // 65 536 envs K = 16 0.71 | 0.81, 98 304: 0.66 | 0.70, 131 072: 0.72 | 0.64 (K = 8: 0.78 | 0.82), 196 608: 0.77 | 0.73 (K = 8: 0.90 | 0.85) — on from 163 840 envs.
-            if (roll_helper < 0) roll_helper = n >= 163840 ? 1 : 0;
             roll_helper_grid = 0;
-            if (roll_helper && per_cu >= 4) {
-                const unsigned main_per_cu = LL_TUNE("MGYM_LL_ROLL_MAIN_PER_CU", 3u), help_per_cu = LL_TUNE("MGYM_LL_ROLL_HELPER_PER_CU", 2u);
-                if ((int)main_per_cu < per_cu && main_per_cu >= 1) g = (uint64_t)main_per_cu * (uint64_t)prop.multiProcessorCount;
-                roll_helper_grid = help_per_cu * (unsigned)prop.multiProcessorCount;
+            if (opt.roll_helper && per_cu >= 4) {   // three main waves per CU, the helpers on the fourth SIMD (see above)
+                if ((int)kRollMainPerCu < per_cu) g = (uint64_t)kRollMainPerCu * (uint64_t)prop.multiProcessorCount;
+                roll_helper_grid = kRollHelperPerCu * (unsigned)prop.multiProcessorCount;
                 if ((uint64_t)roll_helper_grid * 64 > n) roll_helper_grid = (unsigned)(n / 64);
-                // (MGYM_LL_ROLL_HELPER_LOWPRIO=1: on the step's helper stream, which has the lowest priority)
-                if (roll_helper_grid && !(getenv("MGYM_LL_ROLL_HELPER_LOWPRIO") && atoi(getenv("MGYM_LL_ROLL_HELPER_LOWPRIO")))) MGYM_HIP(hipStreamCreateWithFlags(&roll_aux, hipStreamNonBlocking));
+                if (roll_helper_grid) MGYM_HIP(hipStreamCreateWithFlags(&roll_aux, hipStreamNonBlocking));
             }
-            rq.helper_min = LL_TUNE("MGYM_LL_ROLL_HELPER_MIN", 256u);
-            if (LL_TUNE("MGYM_LL_ROLL_GRID", 0u)) g = (uint64_t)LL_TUNE("MGYM_LL_ROLL_GRID", 0u);
             const uint64_t need = (n + 31) / 32;   // more waves than 32-lane batches can never be busy
             if (g > need) g = need;
             if (g < 1) g = 1;
@@ -1249,79 +1129,89 @@ struct LunarLanderEnv final : Env {
                 if (pg > roll_grid) pg = roll_grid;
                 roll_policy_grid = (unsigned)(pg < 1 ? 1 : pg);
             }
-            const size_t per_lane = (size_t)(kSolverCap - vc_near_limit);
             MGYM_HIP(hipMalloc(&roll_vc_far, per_lane * (size_t)roll_grid * 32 * sizeof(VConstraint)));
-            if (getenv("MGYM_LL_ROLL_TRACE")) {   // diagnosis: what every wave did when (written to that file after each launch; synchronises)
+            if (opt.roll_trace) {
                 MGYM_HIP(hipMalloc(&roll_trace, (size_t)roll_grid * kRollTraceLen * sizeof(unsigned long long)));
                 rq.trace = static_cast<unsigned long long*>(roll_trace);
             }
         }
         return MGYM_OK;
     }
-    // K steps of every environment in ONE persistent launch (ll_roll.h): identical per-environment results to K calls of step()
-    int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (!roll_enabled || n == 0 || K < roll_min_k) return Env::rollout(actions, K, obs_out, reward, done, trunc);
+    // The persistent launches of a K-step rollout (ll_roll.h), kRollMaxK steps at a time: launch(k0, rd, io, q) puts the kernels of the chunk that
+    // starts at step k0 behind ll_rollout_begin.  Identical per-environment results to K calls of step().
+    template <class Launch>
+    int roll_chunks(const uint32_t* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, Launch launch) {
         int st = join_helpers();
         if (st != MGYM_OK) return st;
         LLDev rd = dev; rd.split = 0;
         rd.vc_far = static_cast<VConstraint*>(roll_vc_far); rd.vc_far_late = rd.vc_far;
         for (int k0 = 0; k0 < K; k0 += (int)kRollMaxK) {
             const int kc = K - k0 < (int)kRollMaxK ? K - k0 : (int)kRollMaxK;
-            LLIo io{static_cast<const uint32_t*>(actions) + (size_t)k0 * n, obs_out ? obs_out + (size_t)k0 * 8 * n : nullptr, reward ? reward + (size_t)k0 * n : nullptr,
+            LLIo io{actions ? actions + (size_t)k0 * n : nullptr, obs_out ? obs_out + (size_t)k0 * 8 * n : nullptr, reward ? reward + (size_t)k0 * n : nullptr,
                     done ? done + (size_t)k0 * n : nullptr, trunc ? trunc + (size_t)k0 * n : nullptr};
             RollQ q = rq; q.K = (uint32_t)kc;
             if (roll_trace) MGYM_HIP(hipMemsetAsync(roll_trace, 0, (size_t)roll_grid * kRollTraceLen * sizeof(unsigned long long), stream));
             ll_rollout_begin(stream, q, (uint32_t)n);
-            if (roll_helper_grid) MGYM_HIP(hipEventRecord(ev_fork, stream));
-            ll_rollout_launch(stream, roll_grid, rd, io, q);
-            if (roll_helper_grid) {   // the helper waves beside it, on the helper stream (fork / join by events: stream-ordered for the caller, capturable)
-                hipStream_t hs = roll_aux ? roll_aux : aux;
-                MGYM_HIP(hipStreamWaitEvent(hs, ev_fork, 0));
-                ll_rollout_helper_launch(hs, roll_helper_grid, rd, io, q);
-                MGYM_HIP(hipEventRecord(ev_join, hs));
-                MGYM_HIP(hipStreamWaitEvent(stream, ev_join, 0));
-            }
+            st = launch(k0, rd, io, q);
+            if (st != MGYM_OK) return st;
         }
-        return rollout_finish(K);
-    }
-    // after the launches of a rollout: diagnosis output, and what the launches have changed behind the step's back
-    int rollout_finish(int K) {
-        int st = MGYM_OK;
-        if (roll_trace) {
-            std::vector<unsigned long long> h((size_t)roll_grid * kRollTraceLen);
-            MGYM_HIP(hipStreamSynchronize(stream));
-            MGYM_HIP(hipMemcpy(h.data(), roll_trace, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            if (FILE* f = fopen(getenv("MGYM_LL_ROLL_TRACE"), "wb")) { const unsigned hdr[2] = {roll_grid, (unsigned)kRollTraceLen}; fwrite(hdr, sizeof hdr, 1, f); fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
-        }
-        if (getenv("MGYM_LL_ROLL_STATS")) {   // diagnosis: where the waves of the last launch spent their time (synchronises)
-            unsigned long long h[RS_COUNT];
-            MGYM_HIP(hipStreamSynchronize(stream));
-            MGYM_HIP(hipMemcpy(h, rq.stat, sizeof h, hipMemcpyDeviceToHost));
-            const double w = h[RS_N_WAVES] ? (double)h[RS_N_WAVES] : 1.0, us = 0.01;
-            auto per = [&](int t, int nn) { return h[nn] ? h[t] * us / h[nn] : 0.0; };
-            fprintf(stderr, "ll_rollout K=%d waves=%.0f: per wave us: total %.0f seed %.0f | touching-contact %.0f (%.1f batches of %.1f lanes, %.0f us each) | light-contact %.0f (%.1f batches of %.1f lanes, %.0f us each) | "
-                            "sub-steps %.0f (%.1f batches of %.1f lanes, %.0f us each) | reset %.0f (%.1f lanes) | free %.0f (%.1f steps of %.1f lanes, %.1f us each: begin %.1f issue %.1f sweeps %.1f finish %.1f queue %.1f; %.1f refills %.1f switches %.1f rotations) | idle %.0f, %.1f looks without work\n",
-                    K, w, h[RS_T_TOTAL] * us / w, h[RS_T_SEED] * us / w,
-                    h[RS_T_CONTACT] * us / w, h[RS_N_CONTACT_BATCHES] / w, h[RS_N_CONTACT_BATCHES] ? (double)h[RS_N_CONTACT_LANES] / h[RS_N_CONTACT_BATCHES] : 0.0, per(RS_T_CONTACT, RS_N_CONTACT_BATCHES),
-                    h[RS_T_LIGHT] * us / w, h[RS_N_LIGHT_BATCHES] / w, h[RS_N_LIGHT_BATCHES] ? (double)h[RS_N_LIGHT_LANES] / h[RS_N_LIGHT_BATCHES] : 0.0, per(RS_T_LIGHT, RS_N_LIGHT_BATCHES),
-                    h[RS_T_TOI] * us / w, h[RS_N_TOI_BATCHES] / w, h[RS_N_TOI_BATCHES] ? (double)h[RS_N_TOI_LANES] / h[RS_N_TOI_BATCHES] : 0.0, per(RS_T_TOI, RS_N_TOI_BATCHES),
-                    h[RS_T_RESET] * us / w, h[RS_N_RESET_LANES] / w,
-                    h[RS_T_FREE] * us / w, h[RS_N_FREE_STEPS] / w, h[RS_N_FREE_STEPS] ? (double)h[RS_N_FREE_LANE_STEPS] / h[RS_N_FREE_STEPS] : 0.0, per(RS_T_FREE, RS_N_FREE_STEPS),
-                    per(RS_T_FREE_BEGIN, RS_N_FREE_STEPS), per(RS_T_FREE_ISSUE, RS_N_FREE_STEPS), per(RS_T_FREE_SWEEPS, RS_N_FREE_STEPS), per(RS_T_FREE_FINISH, RS_N_FREE_STEPS), per(RS_T_FREE_QUEUE, RS_N_FREE_STEPS),
-                    h[RS_N_REFILLS] / w, h[RS_N_SWITCHES] / w, h[RS_N_ROTATIONS] / w, h[RS_T_IDLE] * us / w, h[RS_N_MAIN] / w);
-            if (roll_helper_grid) fprintf(stderr, "   free-flight helper waves (%u blocks): %.0f wave-steps of %.1f lanes (main waves: %.0f wave-steps)\n", roll_helper_grid, (double)h[RS_N_HELPER_STEPS],
-                                          h[RS_N_HELPER_STEPS] ? (double)h[RS_N_HELPER_LANE_STEPS] / h[RS_N_HELPER_STEPS] : 0.0, (double)h[RS_N_FREE_STEPS]);
-        }
-        if (staged) direct_possible = true;   // episodes that ended inside the launch were reset there: their prepared successors no longer fit
+        // diagnosis output, then what the launches have changed behind the step's back
+        if (roll_trace) { st = roll_write_trace(); if (st != MGYM_OK) return st; }
+        if (opt.roll_stats) { st = roll_print_stats(K); if (st != MGYM_OK) return st; }
+        if (opt.staged) direct_possible = true;   // episodes that ended inside the launch were reset there: their prepared successors no longer fit
         if (fused_tail) { st = rebuild_list(); if (st != MGYM_OK) return st; }
         MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+    // mgym_rollout
+    int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        if (!opt.roll_enabled || n == 0 || K < opt.roll_min_k) return Env::rollout(actions, K, obs_out, reward, done, trunc);
+        return roll_chunks(static_cast<const uint32_t*>(actions), K, obs_out, reward, done, trunc, [this](int, const LLDev& rd, const LLIo& io, const RollQ& q) {
+            if (roll_helper_grid) MGYM_HIP(hipEventRecord(ev_fork, stream));
+            ll_rollout_launch(stream, roll_grid, rd, io, q);
+            if (roll_helper_grid) {   // the helper waves beside it, on their own stream (fork / join by events: stream-ordered for the caller, capturable)
+                MGYM_HIP(hipStreamWaitEvent(roll_aux, ev_fork, 0));
+                ll_rollout_helper_launch(roll_aux, roll_helper_grid, rd, io, q);
+                MGYM_HIP(hipEventRecord(ev_join, roll_aux));
+                MGYM_HIP(hipStreamWaitEvent(stream, ev_join, 0));
+            }
+            return (int)MGYM_OK;
+        });
+    }
+    // MGYM_LL_ROLL_TRACE=file: what every wave of the last launch did when (synchronises)
+    int roll_write_trace() {
+        std::vector<unsigned long long> h((size_t)roll_grid * kRollTraceLen);
+        MGYM_HIP(hipStreamSynchronize(stream));
+        MGYM_HIP(hipMemcpy(h.data(), roll_trace, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (FILE* f = fopen(opt.roll_trace_file.c_str(), "wb")) { const unsigned hdr[2] = {roll_grid, (unsigned)kRollTraceLen}; fwrite(hdr, sizeof hdr, 1, f); fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
+        return MGYM_OK;
+    }
+    // MGYM_LL_ROLL_STATS: where the waves of the last launch spent their time (synchronises)
+    int roll_print_stats(int K) {
+        unsigned long long h[RS_COUNT];
+        MGYM_HIP(hipStreamSynchronize(stream));
+        MGYM_HIP(hipMemcpy(h, rq.stat, sizeof h, hipMemcpyDeviceToHost));
+        const double w = h[RS_N_WAVES] ? (double)h[RS_N_WAVES] : 1.0, us = 0.01;
+        auto per = [&](int t, int nn) { return h[nn] ? h[t] * us / h[nn] : 0.0; };
+        fprintf(stderr, "ll_rollout K=%d waves=%.0f: per wave us: total %.0f seed %.0f | touching-contact %.0f (%.1f batches of %.1f lanes, %.0f us each) | light-contact %.0f (%.1f batches of %.1f lanes, %.0f us each) | "
+                        "sub-steps %.0f (%.1f batches of %.1f lanes, %.0f us each) | reset %.0f (%.1f lanes) | free %.0f (%.1f steps of %.1f lanes, %.1f us each: begin %.1f issue %.1f sweeps %.1f finish %.1f queue %.1f; %.1f refills %.1f switches %.1f rotations) | idle %.0f, %.1f looks without work\n",
+                K, w, h[RS_T_TOTAL] * us / w, h[RS_T_SEED] * us / w,
+                h[RS_T_CONTACT] * us / w, h[RS_N_CONTACT_BATCHES] / w, h[RS_N_CONTACT_BATCHES] ? (double)h[RS_N_CONTACT_LANES] / h[RS_N_CONTACT_BATCHES] : 0.0, per(RS_T_CONTACT, RS_N_CONTACT_BATCHES),
+                h[RS_T_LIGHT] * us / w, h[RS_N_LIGHT_BATCHES] / w, h[RS_N_LIGHT_BATCHES] ? (double)h[RS_N_LIGHT_LANES] / h[RS_N_LIGHT_BATCHES] : 0.0, per(RS_T_LIGHT, RS_N_LIGHT_BATCHES),
+                h[RS_T_TOI] * us / w, h[RS_N_TOI_BATCHES] / w, h[RS_N_TOI_BATCHES] ? (double)h[RS_N_TOI_LANES] / h[RS_N_TOI_BATCHES] : 0.0, per(RS_T_TOI, RS_N_TOI_BATCHES),
+                h[RS_T_RESET] * us / w, h[RS_N_RESET_LANES] / w,
+                h[RS_T_FREE] * us / w, h[RS_N_FREE_STEPS] / w, h[RS_N_FREE_STEPS] ? (double)h[RS_N_FREE_LANE_STEPS] / h[RS_N_FREE_STEPS] : 0.0, per(RS_T_FREE, RS_N_FREE_STEPS),
+                per(RS_T_FREE_BEGIN, RS_N_FREE_STEPS), per(RS_T_FREE_ISSUE, RS_N_FREE_STEPS), per(RS_T_FREE_SWEEPS, RS_N_FREE_STEPS), per(RS_T_FREE_FINISH, RS_N_FREE_STEPS), per(RS_T_FREE_QUEUE, RS_N_FREE_STEPS),
+                h[RS_N_REFILLS] / w, h[RS_N_SWITCHES] / w, h[RS_N_ROTATIONS] / w, h[RS_T_IDLE] * us / w, h[RS_N_MAIN] / w);
+        if (roll_helper_grid) fprintf(stderr, "   free-flight helper waves (%u blocks): %.0f wave-steps of %.1f lanes (main waves: %.0f wave-steps)\n", roll_helper_grid, (double)h[RS_N_HELPER_STEPS],
+                                      h[RS_N_HELPER_STEPS] ? (double)h[RS_N_HELPER_LANE_STEPS] / h[RS_N_HELPER_STEPS] : 0.0, (double)h[RS_N_FREE_STEPS]);
         return MGYM_OK;
     }
     // mgym_rollout_linear / mgym_rollout_uniform: the persistent launch with the action source `policy` (ll_roll.h), or K x (ll_policy_kernel, step())
     int policy_rollout(int policy, RollPolicy pol, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
         pol.next = next_act;
-        if (!roll_enabled || K < roll_min_k || capturing()) {
+        if (!opt.roll_enabled || K < opt.roll_min_k || capturing()) {
             const unsigned g = (unsigned)((n + 255) / 256);
             for (int t = 0; t < K; ++t) {
                 uint32_t* a = ao ? ao + (size_t)t * n : next_act;
@@ -1334,23 +1224,13 @@ struct LunarLanderEnv final : Env {
             }
             return MGYM_OK;
         }
-        int st = join_helpers();
-        if (st != MGYM_OK) return st;
-        LLDev rd = dev; rd.split = 0;
-        rd.vc_far = static_cast<VConstraint*>(roll_vc_far); rd.vc_far_late = rd.vc_far;
-        for (int k0 = 0; k0 < K; k0 += (int)kRollMaxK) {
-            const int kc = K - k0 < (int)kRollMaxK ? K - k0 : (int)kRollMaxK;
-            LLIo io{nullptr, obs_out ? obs_out + (size_t)k0 * 8 * n : nullptr, reward ? reward + (size_t)k0 * n : nullptr,
-                    done ? done + (size_t)k0 * n : nullptr, trunc ? trunc + (size_t)k0 * n : nullptr};
+        return roll_chunks(nullptr, K, obs_out, reward, done, trunc, [this, policy, pol, ao](int k0, const LLDev& rd, const LLIo& io, const RollQ& q) {
             RollPolicy p = pol;
             p.t0 = (uint32_t)k0;
             p.act_out = ao ? ao + (size_t)k0 * n : nullptr;
-            RollQ q = rq; q.K = (uint32_t)kc;
-            if (roll_trace) MGYM_HIP(hipMemsetAsync(roll_trace, 0, (size_t)roll_grid * kRollTraceLen * sizeof(unsigned long long), stream));
-            ll_rollout_begin(stream, q, (uint32_t)n);
             ll_rollout_policy_launch(stream, roll_policy_grid, rd, io, q, p, policy);   // (never with the free-flight helper waves)
-        }
-        return rollout_finish(K);
+            return (int)MGYM_OK;
+        });
     }
     int rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
@@ -1368,19 +1248,13 @@ struct LunarLanderEnv final : Env {
         }
         return policy_rollout(ROLL_ACT_LINEAR, pol, K, actions_out, obs_out, reward, done, trunc);
     }
-    bool staging() const { return staged && dev.disp == nullptr; }  // (a dispersion override would be baked into prepared states)
+    // Are auto-resets staged right now?  (A dispersion override would be baked into prepared states.)  Also while the caller's stream is being
+    // captured: the preparation branch goes into the graph (every event it needs is recorded inside the capture: see step_multi_stream()).
+    bool staging() const { return opt.staged && dev.disp == nullptr; }
     bool capturing() const {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(stream, &cs) != hipSuccess) return false;
         return cs != hipStreamCaptureStatusNone;
-    }
-    // Staged resets while the caller's stream is being captured: the fused order takes its preparation branch into the graph (every
-    // event it needs is recorded inside the capture: see step()); the unfused order resets directly in captured steps — replayed as a
-    // hipGraph its extra branch cost more than it saved (profiles/r02_lunarlander/launch_modes.txt) — and their envs' prepared states
-    // are then simply stale (episode check) the next time a step runs eagerly.
-    bool staging_now() const {
-        if (!staging()) return false;
-        return (fused_tail && staged_in_graph) || !capturing();
     }
     // Preparation state.  prep_due: L_PREP may hold envs (put there by an epilogue) that no preparation launch has been issued for;
     // ev_prep_valid: ev_prep is a real record on `stream` behind that epilogue (a record made while capturing is not);
@@ -1403,7 +1277,7 @@ struct LunarLanderEnv final : Env {
         return MGYM_OK;
     }
     // prepare the next reset of the envs on L_PREP (or of every env), after what `stream` holds so far.
-    // Fused order: the preparation that follows a step is only MARKED (mark_prepare) and launched by the next step() behind its
+    // Multi-stream order: the preparation that follows a step is only MARKED (mark_prepare) and launched by the next step() behind its
     // free-flight kernel (after_free) — started at once it competes with the contact kernel for the SIMDs at the very moment that
     // kernel's one-wave-per-SIMD blocks are being placed (contact kernel 1.04 -> 1.15 ms, itself 0.11 -> 0.7 ms).
     int mark_prepare(bool in_capture) {
@@ -1442,7 +1316,7 @@ struct LunarLanderEnv final : Env {
         if (b > 65536) b = 65536;
         return dim3((unsigned)(b ? b : 1));
     }
-    unsigned main_contact_grid() const { return (unsigned)(((uint64_t)work_grid().x * 64 + gen_block - 1) / gen_block); }  // blocks of gen_block lanes
+    unsigned main_contact_grid() const { return (unsigned)(((uint64_t)work_grid().x * 64 + opt.gen_block - 1) / opt.gen_block); }  // blocks of opt.gen_block lanes
     unsigned late_contact_grid() const { return work_grid().x < 256 ? work_grid().x : 256; }                               // blocks of 32 lanes
     dim3 work_grid() const {  // the worklist length is only known on the device: fixed grid, grid-stride inside
         uint64_t b = (n + kLLBlock - 1) / kLLBlock;
@@ -1474,10 +1348,10 @@ struct LunarLanderEnv final : Env {
         if (n == 0) return MGYM_OK;
         LLIo io{nullptr, obs_out, nullptr, nullptr, nullptr};
         MGYM_HIP(hipMemsetAsync(dev.work_count, 0, L_COUNT * sizeof(uint32_t), stream));
-        if (general_only && all) {  // debugging aid: reset + implicit step on the general path
+        if (opt.general_only && all) {  // debugging aid: reset + implicit step on the general path
             hipLaunchKernelGGL(ll_general_kernel<64>, grid(), dim3(kLLBlock), 0, stream, dev, io, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 1);
         } else {
-            const bool stage = staging_now() && !capturing();   // (a captured reset computes directly and prepares nothing)
+            const bool stage = staging() && !capturing();   // (a captured reset computes directly and prepares nothing)
             if (stage) { int st = join_helpers(); if (st != MGYM_OK) return st; }
             if (!all) hipLaunchKernelGGL(ll_mask_scan_kernel, dim3(grid_for(n)), dim3(256), 0, stream, dev, m0, m1);
             launch_resets(io, all, L_RESET, stage);
@@ -1503,154 +1377,84 @@ struct LunarLanderEnv final : Env {
         return MGYM_OK;
     }
     void launch_free(hipStream_t s, const LLDev& d, const LLIo& io) {
-#ifdef LL_DIAG
-        if (free_occ == 1) { hipLaunchKernelGGL(ll_free_kernel<1>, grid(), dim3(kLLBlock), 0, s, d, io); return; }
-        if (free_occ == 3) { hipLaunchKernelGGL(ll_free_kernel<3>, grid(), dim3(kLLBlock), 0, s, d, io); return; }
-#endif
         hipLaunchKernelGGL(ll_free_kernel<2>, grid(), dim3(kLLBlock), 0, s, d, io);   // two waves per SIMD (profiles/r02_lunarlander/tune_free_kernel_occupancy_overlapped.txt)
     }
-    void launch_contact(hipStream_t s, int block, unsigned gb, const LLDev& d, const LLIo& io, int toi_budget, int which) {
-        switch (block) {
-#ifdef LL_DIAG
-        case 8: hipLaunchKernelGGL(ll_contact_kernel<8>, dim3(gb), dim3(ll_contact_threads(8)), 0, s, d, io, toi_budget, which); break;
-        case 16: hipLaunchKernelGGL(ll_contact_kernel<16>, dim3(gb), dim3(ll_contact_threads(16)), 0, s, d, io, toi_budget, which); break;
-        case 40: hipLaunchKernelGGL(ll_contact_kernel<40>, dim3(gb), dim3(ll_contact_threads(40)), 0, s, d, io, toi_budget, which); break;
-        case 48: hipLaunchKernelGGL(ll_contact_kernel<48>, dim3(gb), dim3(ll_contact_threads(48)), 0, s, d, io, toi_budget, which); break;
-#endif
-        case 64: hipLaunchKernelGGL(ll_contact_kernel<64>, dim3(gb), dim3(ll_contact_threads(64)), 0, s, d, io, toi_budget, which); break;
-        default: hipLaunchKernelGGL(ll_contact_kernel<32>, dim3(gb), dim3(ll_contact_threads(32)), 0, s, d, io, toi_budget, which); break;
-        }
+    void launch_contact(hipStream_t s, int block, unsigned gb, const LLDev& d, const LLIo& io, int which) {
+        if (block == 64) hipLaunchKernelGGL(ll_contact_kernel<64>, dim3(gb), dim3(ll_contact_threads(64)), 0, s, d, io, -1, which);
+        else hipLaunchKernelGGL(ll_contact_kernel<32>, dim3(gb), dim3(ll_contact_threads(32)), 0, s, d, io, -1, which);
     }
+    // This step's contact list and class bytes were built by the previous call's last kernel (ll_epilogue_kernel, or rebuild_list() after whatever
+    // else changed the state), so both orders start on the contact path at once and end with the same tail.
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0) return MGYM_OK;
-        LLIo io{static_cast<const uint32_t*>(actions), obs_out, reward, done, trunc};
-        if (general_only) {  // debugging aid (MGYM_LL_GENERAL_ONLY=1): every env through the general kernel
-            hipLaunchKernelGGL(ll_general_kernel<64>, grid(), dim3(kLLBlock), 0, stream, dev, io, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0);
-            MGYM_HIP(hipGetLastError());
-            return MGYM_OK;
-        }
-        const unsigned gb = main_contact_grid();
-        if (fused_tail) {
-            // Fused order (the default): this step's contact list and class bytes were built by the previous call's last kernel, so
-            // the contact kernel starts at once; beside it, on the helper stream, the free-flight kernel and the short contact launch
-            // for the envs it hands over; after the join ONE epilogue launch: prepared resets copied in, next step's list, counters.
-            LLDev sd = dev; sd.split = 1;
-            if (single_launch) {
-                // ONE launch for the step (ll_step_kernel) and one for its end (ll_epilogue_kernel), both on the caller's stream: no
-                // helper streams, no events — nothing depends on hardware queues or on how a graph executor schedules branches.
-                const bool stage1 = dev.auto_reset && staging();
-                LLDev sh = sd;
-                if (stage1) {
-                    sh.st = static_cast<uint32_t*>(shadow_base); sh.obs = static_cast<float*>(shadow_obs);
-                    sh.episode_src = dev.st; sh.prep = 0; sh.split = 0;
-                }
-                const unsigned g_contact = gb, g_free = free2_grid(), g_prep = stage1 ? 128u : 0u;
-                hipLaunchKernelGGL(ll_step_kernel<32>, dim3(g_contact + g_free + g_prep), dim3(64), 0, stream, sd, sh, io, g_contact, g_free);
-                LLIo rio1{nullptr, obs_out, nullptr, nullptr, nullptr};
-                // A step that is being CAPTURED always carries the two (normally empty) direct-reset launches: whether a finished env will
-                // find a fitting prepared episode is decided when the graph RUNS — after a later mgym_set_state, say — not now.
-                const bool direct_now = direct_possible || capturing();
-                if (stage1) {
-                    hipLaunchKernelGGL(ll_epilogue_kernel, dim3(classify_grid()), dim3(1024), 0, stream, dev, (const uint32_t*)shadow_base, (const float*)shadow_obs, rio1, 1, direct_now ? 1 : 0);
-                    if (direct_now) launch_resets(rio1, false, L_RESET_DIRECT, true);   // (two launches, normally empty)
-                } else {
-                    if (dev.auto_reset) launch_resets(rio1, false);
-                    if (dev.auto_reset && staged) direct_possible = true;   // resets computed here leave no prepared successor behind
-                    hipLaunchKernelGGL(ll_epilogue_kernel, dim3(classify_grid()), dim3(1024), 0, stream, dev, (const uint32_t*)nullptr, (const float*)nullptr, rio1, 0, 1);
-                }
-                MGYM_HIP(hipGetLastError());
-                return MGYM_OK;
-            }
-            const bool stage = dev.auto_reset && staging_now();
-            const bool cap = stage && capturing();
-            if (stage && !cap && prep_due && !ev_prep_valid) {   // marked by a captured step: the record has to be made now, BEFORE this step's contact kernel
-                MGYM_HIP(hipEventRecord(ev_prep, stream));
-                ev_prep_valid = true;
-            }
-            MGYM_HIP(hipEventRecord(ev_fork, stream));
-            MGYM_HIP(hipStreamWaitEvent(aux, ev_fork, 0));
-            launch_contact(stream, gen_block, gb, sd, io, -1, L_GENERAL);
-            launch_free(aux, sd, io);
-            if (stage && (cap || prep_due)) {   // the preparation the previous step marked: behind the free-flight kernel, beside the late contact launch
-                MGYM_HIP(hipEventRecord(ev_free_done, aux));
-                int st = launch_prepare(false, true, true, cap);
-                if (st != MGYM_OK) return st;
-            }
-            launch_contact(aux, 32, late_contact_grid(), sd, io, -1, L_LATE);
-            MGYM_HIP(hipEventRecord(ev_join, aux));
-            MGYM_HIP(hipStreamWaitEvent(stream, ev_join, 0));
-            LLIo rio{nullptr, obs_out, nullptr, nullptr, nullptr};
-            if (stage) {
-                int st = join_helpers();
-                if (st != MGYM_OK) return st;
-                const bool direct_now = direct_possible || capturing();   // (see the single-launch order above)
-                hipLaunchKernelGGL(ll_epilogue_kernel, dim3(classify_grid()), dim3(1024), 0, stream, dev, (const uint32_t*)shadow_base, (const float*)shadow_obs, rio, 1, direct_now ? 1 : 0);
-                if (direct_now) launch_resets(rio, false, L_RESET_DIRECT, true);   // (two launches, normally empty)
-                st = mark_prepare(cap);
-                if (st != MGYM_OK) return st;
-            } else {
-                if (dev.auto_reset) launch_resets(rio, false);
-                if (dev.auto_reset && staged) direct_possible = true;   // resets computed here leave no prepared successor behind
-                hipLaunchKernelGGL(ll_epilogue_kernel, dim3(classify_grid()), dim3(1024), 0, stream, dev, (const uint32_t*)nullptr, (const float*)nullptr, rio, 0, 1);
-            }
-            MGYM_HIP(hipGetLastError());
-            return MGYM_OK;
-        }
-#ifdef LL_DIAG   // the unfused orders of rounds 1-2 (MGYM_LL_FUSED_TAIL=0, MGYM_LL_OVERLAP=0, MGYM_LL_TOI_ROUNDS, MGYM_LL_BUCKET): profiling builds only
-        MGYM_HIP(hipMemsetAsync(dev.work_count, 0, L_COUNT * sizeof(uint32_t), stream));
-        const int first_budget = toi_rounds > 0 ? toi_first : -1;  // sub-steps the contact kernel takes itself before handing an env to ll_toi_kernel
-        if (overlap) {
-            // Overlapped order (see ll_classify_kernel): the contact kernel starts at once on the caller's stream; beside it,
-            // on the helper stream, the free-flight kernel over everyone else, followed by a short contact launch for the
-            // envs it declined (a contact was created at the end of their step).  Stream-ordered for the caller and
-            // capturable (fork / join by events).  262 144 envs: 1.82 -> 1.52 ms per step (table in init()).
-            LLDev sd = dev; sd.split = 1;
-            hipLaunchKernelGGL(ll_classify_kernel, dim3(classify_grid()), dim3(1024), 0, stream, sd);
-            MGYM_HIP(hipEventRecord(ev_fork, stream));
-            launch_contact(stream, gen_block, gb, sd, io, first_budget, L_GENERAL);
-            MGYM_HIP(hipStreamWaitEvent(aux, ev_fork, 0));
-            launch_free(aux, sd, io);
-            launch_contact(aux, 32, late_contact_grid(), sd, io, first_budget, L_LATE);
-            MGYM_HIP(hipEventRecord(ev_join, aux));
-            MGYM_HIP(hipStreamWaitEvent(stream, ev_join, 0));
-        } else {
-            launch_free(stream, dev, io);
-            // contact path on the compacted list, then the time-of-impact rounds over ever shorter lists (fixed grids,
-            // grid-stride inside: the list lengths only exist on the device)
-            launch_contact(stream, gen_block, gb, dev, io, first_budget, L_GENERAL);
-        }
-        for (int r = 0; r < toi_rounds; ++r) {
-            unsigned g = (work_grid().x * (64 / toi_block)) >> (r + 1);
-            if (g < 64) g = 64;
-            const int budget = r + 1 < toi_rounds ? 1 : -1;   // the last round runs every remaining sub-step
-            switch (toi_block) {
-            case 8: hipLaunchKernelGGL(ll_toi_kernel<8>, dim3(g), dim3(8), 0, stream, dev, io, r, budget); break;
-            case 16: hipLaunchKernelGGL(ll_toi_kernel<16>, dim3(g), dim3(16), 0, stream, dev, io, r, budget); break;
-            case 64: hipLaunchKernelGGL(ll_toi_kernel<64>, dim3(g), dim3(64), 0, stream, dev, io, r, budget); break;
-            default: hipLaunchKernelGGL(ll_toi_kernel<32>, dim3(g), dim3(32), 0, stream, dev, io, r, budget); break;
-            }
-        }
-        if (dev.auto_reset) {  // finished envs were compacted onto L_RESET by both kernels; outputs of the step stay as written
-            LLIo rio{nullptr, obs_out, nullptr, nullptr, nullptr};
-            if (staging_now()) {
-                int st = join_helpers();
-                if (st != MGYM_OK) return st;
-                hipLaunchKernelGGL(ll_apply_select_kernel, dim3(work_grid().x < 64 ? work_grid().x : 64), dim3(256), 0, stream, dev, (const uint32_t*)shadow_base);
-                hipLaunchKernelGGL(ll_apply_copy_kernel, dim3(work_grid().x < 2048 ? work_grid().x : 2048), dim3(128), 0, stream, dev,
-                                   (const uint32_t*)shadow_base, (const float*)shadow_obs, rio);
-                launch_resets(rio, false, L_RESET_DIRECT, true);   // normally empty
-                st = launch_prepare(false);
-                if (st != MGYM_OK) return st;
-            } else {
-                launch_resets(rio, false);
-            }
-        }
+        const LLIo io{static_cast<const uint32_t*>(actions), obs_out, reward, done, trunc};
+        if (opt.general_only) return step_general_only(io);
+        return opt.single_launch ? step_single_launch(io) : step_multi_stream(io);
+    }
+    // debugging aid (MGYM_LL_GENERAL_ONLY): every env through the general kernel
+    int step_general_only(const LLIo& io) {
+        hipLaunchKernelGGL(ll_general_kernel<64>, grid(), dim3(kLLBlock), 0, stream, dev, io, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
-#else
-        set_last_error("LunarLander step: no launch order selected");   // (unreachable: general_only returned above, the fused order is the only other one)
-        return MGYM_ERR_BAD_CONFIG;
-#endif
+    }
+    // ONE launch for the step (ll_step_kernel) and one for its end (ll_epilogue_kernel), both on the caller's stream: no
+    // helper streams, no events — nothing depends on hardware queues or on how a graph executor schedules branches.
+    int step_single_launch(const LLIo& io) {
+        LLDev sd = dev; sd.split = 1;
+        const bool stage = dev.auto_reset && staging();
+        LLDev sh = sd;
+        if (stage) {
+            sh.st = static_cast<uint32_t*>(shadow_base); sh.obs = static_cast<float*>(shadow_obs);
+            sh.episode_src = dev.st; sh.prep = 0; sh.split = 0;
+        }
+        const unsigned g_contact = main_contact_grid(), g_free = free2_grid(), g_prep = stage ? 128u : 0u;
+        hipLaunchKernelGGL(ll_step_kernel<32>, dim3(g_contact + g_free + g_prep), dim3(64), 0, stream, sd, sh, io, g_contact, g_free);
+        step_tail(stage, stage && capturing(), LLIo{nullptr, io.obs_out, nullptr, nullptr, nullptr});
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+    // The contact kernel on the caller's stream; beside it, on the helper stream, the free-flight kernel and the short contact launch
+    // for the envs it hands over (fork / join by events: stream-ordered for the caller, capturable); after the join the tail.
+    int step_multi_stream(const LLIo& io) {
+        LLDev sd = dev; sd.split = 1;
+        const bool stage = dev.auto_reset && staging();
+        const bool cap = stage && capturing();
+        if (stage && !cap && prep_due && !ev_prep_valid) {   // marked by a captured step: the record has to be made now, BEFORE this step's contact kernel
+            MGYM_HIP(hipEventRecord(ev_prep, stream));
+            ev_prep_valid = true;
+        }
+        MGYM_HIP(hipEventRecord(ev_fork, stream));
+        MGYM_HIP(hipStreamWaitEvent(aux, ev_fork, 0));
+        launch_contact(stream, opt.gen_block, main_contact_grid(), sd, io, L_GENERAL);
+        launch_free(aux, sd, io);
+        if (stage && (cap || prep_due)) {   // the preparation the previous step marked: behind the free-flight kernel, beside the late contact launch
+            MGYM_HIP(hipEventRecord(ev_free_done, aux));
+            int st = launch_prepare(false, true, true, cap);
+            if (st != MGYM_OK) return st;
+        }
+        launch_contact(aux, 32, late_contact_grid(), sd, io, L_LATE);
+        MGYM_HIP(hipEventRecord(ev_join, aux));
+        MGYM_HIP(hipStreamWaitEvent(stream, ev_join, 0));
+        if (stage) { int st = join_helpers(); if (st != MGYM_OK) return st; }
+        step_tail(stage, cap, LLIo{nullptr, io.obs_out, nullptr, nullptr, nullptr});
+        if (stage) { int st = mark_prepare(cap); if (st != MGYM_OK) return st; }
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+    // The end of a step in both orders, on the caller's stream: ONE epilogue launch (prepared resets copied in, the next step's contact list and
+    // class bytes, counters) and the resets that have to be computed: before it every reset when nothing is staged, behind it the direct ones.
+    void step_tail(bool stage, bool in_capture, const LLIo& rio) {
+        if (stage) {
+            // A step that is being CAPTURED always carries the two (normally empty) direct-reset launches: whether a finished env will
+            // find a fitting prepared episode is decided when the graph RUNS — after a later mgym_set_state, say — not now.
+            const bool direct_now = direct_possible || in_capture;
+            hipLaunchKernelGGL(ll_epilogue_kernel, dim3(classify_grid()), dim3(1024), 0, stream, dev, (const uint32_t*)shadow_base, (const float*)shadow_obs, rio, 1, direct_now ? 1 : 0);
+            if (direct_now) launch_resets(rio, false, L_RESET_DIRECT, true);   // (two launches, normally empty)
+        } else {
+            if (dev.auto_reset) launch_resets(rio, false);
+            if (dev.auto_reset && opt.staged) direct_possible = true;   // resets computed here leave no prepared successor behind
+            hipLaunchKernelGGL(ll_epilogue_kernel, dim3(classify_grid()), dim3(1024), 0, stream, dev, (const uint32_t*)nullptr, (const float*)nullptr, rio, 0, 1);
+        }
     }
     int observation(const float** obs, uint64_t* col_stride) override {
         *obs = dev.obs; *col_stride = n_pad;
@@ -1658,11 +1462,11 @@ struct LunarLanderEnv final : Env {
     }
     // mgym_get_info: the launch structure of this handle and whether its streams really run side by side
     int info(std::string& out) override {
-        out += "contact_block=" + std::to_string(gen_block) + "\nlaunch_order=" + (single_launch ? "single_launch" : overlap ? "overlapped" : "sequential") +
-               "\nstaged_resets=" + (staged ? "1" : "0") + "\ncontact_list_by_kind=" + std::to_string(dev.bucket) + "\ncontact_blocks_target=" + std::to_string(single_launch ? dev.contact_blocks : 0) +
-               "\nknobs=MGYM_LL_GENERAL_BLOCK(32|64) MGYM_LL_SINGLE_LAUNCH MGYM_LL_STAGED_RESET MGYM_LL_STAGED_IN_GRAPH MGYM_LL_CONTACT_BLOCKS MGYM_LL_VC_NEAR MGYM_LL_RESUME MGYM_LL_GENERAL_ONLY "
-               "MGYM_LL_AUX_PRIO MGYM_LL_BUCKET MGYM_LL_ROLLOUT MGYM_LL_ROLLOUT_MIN_K MGYM_LL_ROLL_HELPER MGYM_LL_ROLL_STATS MGYM_LL_ROLL_TRACE" +
-               "\nrollout=" + (roll_enabled ? "persistent_launch" : "k_steps") + "\nrollout_min_k=" + std::to_string(roll_min_k) + "\nrollout_waves=" + std::to_string(roll_grid) + "\nrollout_helper_blocks=" + std::to_string(roll_helper_grid) + "\n";
+        out += "contact_block=" + std::to_string(opt.gen_block) + "\nlaunch_order=" + (opt.single_launch ? "single_launch" : "overlapped") +
+               "\nstaged_resets=" + (opt.staged ? "1" : "0") + "\ncontact_list_by_kind=" + std::to_string(dev.bucket) + "\ncontact_blocks_target=" + std::to_string(opt.single_launch ? dev.contact_blocks : 0) +
+               "\nknobs=";
+        for (const LLKnob& k : kLLKnobs) out += std::string(&k == kLLKnobs ? "" : " ") + k.name;
+        out += std::string("\nrollout=") + (opt.roll_enabled ? "persistent_launch" : "k_steps") + "\nrollout_min_k=" + std::to_string(opt.roll_min_k) + "\nrollout_waves=" + std::to_string(roll_grid) + "\nrollout_helper_blocks=" + std::to_string(roll_helper_grid) + "\n";
         if (capturing()) { set_last_error("mgym_get_info: the stream is being captured (the call launches probe kernels and synchronises)"); return MGYM_ERR_BAD_ARG; }
         hipStream_t ss[3] = {stream, aux, aux2};
         const int ns = aux2 ? 3 : 2;
@@ -1713,7 +1517,7 @@ struct LunarLanderEnv final : Env {
     int set_dispersion(const float* disp) override {
         direct_possible = true;
         if (disp != dev.disp) ++config_epoch;   // the dispersion source is a kernel argument: graphs captured under the other one are refused (abi.hip)
-        if (staged) {  // states prepared under the other dispersion source no longer fit: episode 0 never equals a live counter + 1
+        if (opt.staged) {  // states prepared under the other dispersion source no longer fit: episode 0 never equals a live counter + 1
             int st = join_helpers();
             if (st != MGYM_OK) return st;
             MGYM_HIP(clear_shadow_episodes());

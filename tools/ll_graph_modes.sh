@@ -7,6 +7,5 @@ n=$1
 for rep in 1 2 3; do
   echo -n "instantiation $rep  eager:                          "; run "$n" --launch eager
   echo -n "instantiation $rep  graph, staged resets in graph:  "; run "$n" --launch graph
-  echo -n "instantiation $rep  graph, captured steps reset directly (MGYM_LL_STAGED_IN_GRAPH=0): "; MGYM_LL_STAGED_IN_GRAPH=0 run "$n" --launch graph
 done
 echo -n "one graph of exactly 16 step launches: "; python bench.py --workload lunar_lander ${n:+--envs $n} --steps 16 --warmup 640 --no-cpu-baseline --no-extra --launch graph 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f ms/step [%s]' % (d['ms_per_step'], d['config']['launch']))"

@@ -9,12 +9,12 @@
 #include <stdint.h>
 #define LL_WHATIF_BUILD 1
 #define LL_WHATIF(w, bit) (((w).whatif & (bit)) != 0u)
-#define LL_DIAG 1   // the measurement-only launch orders and block sizes (lunar_lander.hip)
 #include "../modurl_gym_amd/csrc/lunar_lander.hip"
 // (the persistent rollout launch lives in ll_roll.hip; these stand-alone measurement binaries never call it)
 namespace mgym { int ll_rollout_blocks_per_cu(int* per_cu) { *per_cu = 1; return 0; } void ll_rollout_ring_init(hipStream_t, const RollQ&) {}
 void ll_rollout_begin(hipStream_t, const RollQ&, uint32_t) {} void ll_rollout_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&) {}
-void ll_rollout_helper_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&) {} }
+void ll_rollout_helper_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&) {}
+int ll_rollout_policy_blocks_per_cu(int* per_cu) { *per_cu = 1; return 0; } void ll_rollout_policy_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&, const RollPolicy&, int) {} }
 
 #include <stdio.h>
 #include <vector>
