@@ -312,6 +312,28 @@ enum {
 };
 int mgym_math_probe(int device, int fn, uint32_t first, uint64_t count, uint32_t *out);
 
+/* Test seam: LunarLander's collision-geometry primitives (modurl_gym_amd/csrc/ll_b2.h) evaluated on the device as pure functions,
+ * one case per lane.  in and out are device memory, columns [cols][count] of 32-bit words; integer fields are bit patterns.  The
+ * ground edge v1-v2 is in the world frame, pi selects the polygon (0 lander hexagon, 1 leg box).
+ *   SHAPES    in ignored (may be NULL), count must be 1.  out, 30 columns per polygon (pi 0, then pi 1): vertex count, 6 vertices
+ *             x,y, 6 normals x,y (unused slots 0), mass, invMass, invI, localCenter x,y - as the kernels' staged tables hold them.
+ *   DISTANCE  in: v1.x v1.y v2.x v2.y pi p.x p.y angle (polygon transform: p, rot(angle)).
+ *             out: b2Distance with an empty simplex cache; b2Distance called again with the cache the first call wrote; that
+ *             cache's vertex count.
+ *   MANIFOLD  in: as DISTANCE.  out: pointCount, type (1 face A = the edge, 2 face B = the polygon; 0 without points), world normal
+ *             x,y, then per point: world point x,y, separation (distance from the reference plane minus both polygon radii), the
+ *             contact-feature id (indexA | indexB << 8 | typeA << 16 | typeB << 24); unused points 0.
+ *   TOI       in: v1.x v1.y v2.x v2.y pi c0.x c0.y a0 c.x c.y a (the polygon body's sweep; localCenter is the engine's, alpha0 = 0).
+ *             out: b2TimeOfImpact's state (0 unknown, 1 failed, 2 overlapped, 3 touching, 4 separated), t.
+ * Runs on the null stream and synchronises the device.  tests/test_gpu_ll_geom.py checks the results against a float64 reference. */
+enum {
+    MGYM_LL_GEOM_SHAPES = 0,
+    MGYM_LL_GEOM_DISTANCE = 1,
+    MGYM_LL_GEOM_MANIFOLD = 2,
+    MGYM_LL_GEOM_TOI = 3
+};
+int mgym_ll_geom_probe(int device, int fn, uint64_t count, const float *in, float *out);
+
 /* hipGraph capture of a caller-issued launch sequence on the env's stream.  What a captured launch freezes and what it does not:
  *  - environment STATE is read when the graph runs: mgym_set_state, mgym_reset (any form) and eager steps between replays are fine.
  *    (LunarLander: a captured step always carries the launches that reset a finished environment WITHOUT a prepared next episode —

@@ -9,8 +9,13 @@
 //                   MountainCar) == mg_sincosf / mg_cosf
 // Exposed as mgym_selftest_cartpole_math() (test seam; seconds on an MI355X).  mgym_math_probe() (test seam) writes the device's
 // result bits of one mgym_math.h entry point for a span of input patterns; tests/test_gpu_math_exhaustive.py compares all 2^32 with glibc.
+// mgym_ll_geom_probe() (test seam) runs LunarLander's collision-geometry primitives (ll_b2.h: b2Distance, b2TimeOfImpact,
+// b2CollideEdgeAndPolygon + b2WorldManifold, the polygon tables and mass data) as pure functions, one case per lane;
+// tests/test_gpu_ll_geom.py checks them against a float64 reference and, word for word, against the oracle and the host build.
 #include "common.h"
 #include "cartpole_step.h"
+#include "ll_kernel_common.h"
+#include "ll_geom_probe.h"
 
 namespace mgym {
 
@@ -163,9 +168,50 @@ __global__ void __launch_bounds__(256) math_probe_kernel(uint32_t first, uint64_
     }
 }
 
+// one case per lane (ll_geom_probe.h).  As in every product kernel the polygon table and collide_edge_polygon's per-lane buffer are
+// LDS: that function casts both to the LDS address space.
+constexpr int kGeomBlock = 64;
+template <int FN>
+__global__ void __launch_bounds__(kGeomBlock) ll_geom_probe_kernel(LLConst k, uint64_t count, const float* __restrict__ in, float* __restrict__ out) {
+    __shared__ PolyTab tab;
+    __shared__ V2 s_tmp[kGeomBlock * 2 * kMaxPoly];
+    stage_tab(tab, k);
+    const uint64_t i = (uint64_t)blockIdx.x * kGeomBlock + threadIdx.x;
+    if (i >= count) return;  // ragged tail (past the barrier of stage_tab)
+    ll_geom_probe_case<FN>(k, tab, s_tmp + threadIdx.x * (2 * kMaxPoly), count, i, in, out);
+}
+
 }  // namespace mgym
 
 using namespace mgym;
+
+static_assert(MGYM_LL_GEOM_SHAPES == GEOM_SHAPES && MGYM_LL_GEOM_DISTANCE == GEOM_DISTANCE && MGYM_LL_GEOM_MANIFOLD == GEOM_MANIFOLD &&
+              MGYM_LL_GEOM_TOI == GEOM_TOI, "mgym.h and ll_geom_probe.h number the probes alike");
+
+extern "C" int mgym_ll_geom_probe(int device, int fn, uint64_t count, const float* in, float* out) {
+    const bool shapes = fn == MGYM_LL_GEOM_SHAPES;
+    if (fn < MGYM_LL_GEOM_SHAPES || fn > MGYM_LL_GEOM_TOI || !out || (!shapes && !in) || count == 0 || count > (1ull << 31) || (shapes && count != 1)) {
+        set_last_error("mgym_ll_geom_probe: unknown probe, NULL columns, or a case count of 0, above 2^31 or (SHAPES) other than 1");
+        return MGYM_ERR_BAD_ARG;
+    }
+    LLConst k;
+    ll_make_const(k, -10.0f, 0, 15.0f, 1.5f);
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    MGYM_HIP(hipSetDevice(device));
+    const dim3 grid((unsigned)((count + kGeomBlock - 1) / kGeomBlock)), block(kGeomBlock);
+    switch (fn) {
+        case MGYM_LL_GEOM_SHAPES: hipLaunchKernelGGL(ll_geom_probe_kernel<GEOM_SHAPES>, grid, block, 0, nullptr, k, count, in, out); break;
+        case MGYM_LL_GEOM_DISTANCE: hipLaunchKernelGGL(ll_geom_probe_kernel<GEOM_DISTANCE>, grid, block, 0, nullptr, k, count, in, out); break;
+        case MGYM_LL_GEOM_MANIFOLD: hipLaunchKernelGGL(ll_geom_probe_kernel<GEOM_MANIFOLD>, grid, block, 0, nullptr, k, count, in, out); break;
+        default: hipLaunchKernelGGL(ll_geom_probe_kernel<GEOM_TOI>, grid, block, 0, nullptr, k, count, in, out); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return hip_fail(e, "ll_geom_probe", __FILE__, __LINE__);
+    return MGYM_OK;
+}
 
 extern "C" int mgym_math_probe(int device, int fn, uint32_t first, uint64_t count, uint32_t* out) {
     if (!out || count == 0 || count > 0x100000000ull - first || fn < MGYM_MATH_SINF || fn > MGYM_MATH_TANHF) {

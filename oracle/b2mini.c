@@ -1809,3 +1809,92 @@ void b2w_step(b2world *w, float dt, int velIters, int posIters) {
 #endif
     for (int b = 1; b <= w->n_dyn; ++b) { w->bodies[b].force = V(0.0f, 0.0f); w->bodies[b].torque = 0.0f; } /* ClearForces */
 }
+
+/* ------------------------------------------------------------------------- geometry probe (test seam) */
+/* The collision-geometry primitives above called as pure functions, one case per index, on the polygons of bodies 1 (pi 0) and
+ * 2 (pi 1) of `w`; ground transform and sweep A are the identity.  Columns [cols][count] of 32-bit words, integer fields as bit
+ * patterns — the layout of mgym_ll_geom_probe (include/mgym.h), whose words these must equal. */
+static float bits_f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+static uint32_t f_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+#define GEOM_SLOTS 6 /* vertex slots per polygon in the probe's SHAPES columns (the kernels' table size) */
+
+int b2w_geom_probe(const b2world *w, int fn, uint64_t count, const float *in, float *out) {
+    if (fn < 0 || fn > 3 || !out || (fn != 0 && !in) || count == 0 || (fn == 0 && count != 1)) return -1;
+    b2xf ident; ident.p = V(0.0f, 0.0f); ident.q = rot_set(0.0f);
+    b2sweep sweepA; memset(&sweepA, 0, sizeof sweepA);
+#define IN(c) in[(uint64_t)(c) * count + i]
+#define OUT(c) out[(uint64_t)(c) * count + i]
+    if (fn == 0) {
+        const uint64_t i = 0;
+        for (int p = 0; p < 2; ++p) {
+            const b2poly *poly = &w->polys[p];
+            const b2body *b = &w->bodies[1 + p];
+            const int c0 = p * (1 + 4 * GEOM_SLOTS + 5);
+            OUT(c0) = bits_f((uint32_t)poly->count);
+            for (int q = 0; q < GEOM_SLOTS; ++q) {
+                const int on = q < poly->count;
+                OUT(c0 + 1 + 2 * q) = on ? poly->v[q].x : 0.0f; OUT(c0 + 2 + 2 * q) = on ? poly->v[q].y : 0.0f;
+                OUT(c0 + 1 + 2 * GEOM_SLOTS + 2 * q) = on ? poly->n[q].x : 0.0f; OUT(c0 + 2 + 2 * GEOM_SLOTS + 2 * q) = on ? poly->n[q].y : 0.0f;
+            }
+            const int m0 = c0 + 1 + 4 * GEOM_SLOTS;
+            OUT(m0) = b->mass; OUT(m0 + 1) = b->invMass; OUT(m0 + 2) = b->invI;
+            OUT(m0 + 3) = b->sw.localCenter.x; OUT(m0 + 4) = b->sw.localCenter.y;
+        }
+        return 0;
+    }
+    for (uint64_t i = 0; i < count; ++i) {
+        b2edge edge; edge.v1 = V(IN(0), IN(1)); edge.v2 = V(IN(2), IN(3)); edge.radius = b2_polygonRadius;
+        const int pi = (int)(f_bits(IN(4)) & 1u);
+        const b2poly *poly = &w->polys[pi];
+        b2v ev[2]; ev[0] = edge.v1; ev[1] = edge.v2;
+        dproxy pA = {ev, 2, b2_polygonRadius}, pB = {poly->v, poly->count, poly->radius};
+        if (fn == 3) {
+            b2sweep sweepB;
+            sweepB.localCenter = w->bodies[1 + pi].sw.localCenter;
+            sweepB.c0 = V(IN(5), IN(6)); sweepB.a0 = IN(7);
+            sweepB.c = V(IN(8), IN(9)); sweepB.a = IN(10);
+            sweepB.alpha0 = 0.0f;
+            float t;
+            int state = time_of_impact(&pA, &pB, sweepA, sweepB, &t);
+            OUT(0) = bits_f((uint32_t)state); OUT(1) = t;
+            continue;
+        }
+        b2xf xf; xf.p = V(IN(5), IN(6)); xf.q = rot_set(IN(7));
+        if (fn == 1) {
+            scache cache; cache.count = 0; cache.metric = 0.0f;
+            float cold = gjk_distance(&cache, &pA, ident, &pB, xf);
+            int cached = cache.count;
+            float warm = gjk_distance(&cache, &pA, ident, &pB, xf);
+            OUT(0) = cold; OUT(1) = warm; OUT(2) = bits_f((uint32_t)cached);
+        } else {
+            b2manifold m; memset(&m, 0, sizeof m);
+            collide_edge_polygon(&m, &edge, ident, poly, xf);
+            b2v normal = V(0.0f, 0.0f), pts[2];
+            world_manifold(&m, ident, edge.radius, xf, poly->radius, &normal, pts);
+            OUT(0) = bits_f((uint32_t)m.pointCount);
+            OUT(1) = bits_f(m.pointCount ? (uint32_t)m.type : 0u);
+            OUT(2) = normal.x; OUT(3) = normal.y;
+            /* separation as b2WorldManifold has it: the clip point's distance from the reference plane minus both radii */
+            b2v pn = V(0.0f, 0.0f), pp = pn;
+            if (m.pointCount > 0) {
+                if (m.type == B2_FACE_A) { pn = rmul(ident.q, m.localNormal); pp = xmul(ident, m.localPoint); }
+                else { pn = rmul(xf.q, m.localNormal); pp = xmul(xf, m.localPoint); }
+            }
+            for (int q = 0; q < 2; ++q) {
+                const int on = q < m.pointCount;
+                float sep = 0.0f;
+                if (on) {
+                    b2v clip = m.type == B2_FACE_A ? xmul(xf, m.points[q].localPoint) : xmul(ident, m.points[q].localPoint);
+                    sep = (dot(vsub(clip, pp), pn) - edge.radius) - poly->radius;
+                }
+                b2cf id = m.points[q].id;
+                OUT(4 + 4 * q) = on ? pts[q].x : 0.0f; OUT(5 + 4 * q) = on ? pts[q].y : 0.0f;
+                OUT(6 + 4 * q) = sep;
+                OUT(7 + 4 * q) = bits_f(on ? (uint32_t)id.indexA | ((uint32_t)id.indexB << 8) | ((uint32_t)id.typeA << 16) | ((uint32_t)id.typeB << 24) : 0u);
+            }
+        }
+    }
+#undef IN
+#undef OUT
+    return 0;
+}

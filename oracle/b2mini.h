@@ -15,8 +15,11 @@
  *   b2RevoluteJoint (motor + lower/upper limit impulses + point constraint),
  *   b2Island::Solve / SolveTOI, b2World::Step / Solve / SolveTOI,
  *   b2Distance (GJK) and b2TimeOfImpact (conservative advancement).
- * Parity pin for all of it: only the reference's LunarLander golden trajectory at its own
- * tolerances (obs 0.2, reward 5.0; lunar_lander.rs:1647-1655).  Where Box2D's result depends on
+ * Parity pins: the reference's LunarLander golden trajectory at its own tolerances (obs 0.2,
+ * reward 5.0; lunar_lander.rs:1647-1655) for all of it; and, for the collision geometry alone
+ * (shapes and mass data, b2Distance, b2CollideEdgeAndPolygon + b2WorldManifold, b2TimeOfImpact),
+ * a float64 reference computed from the numbers alone (tests/ll_geom_ref.py through
+ * b2w_geom_probe, tests/test_ll_geom_host.py).  The solvers have no such pin.  Where Box2D's result depends on
  * dynamic-tree traversal order (order of newly created contacts) this restatement uses a fixed
  * rule (moved proxies in body order, partners by ascending proxy id) — documented deviation.
  */
@@ -123,5 +126,9 @@ void b2b_set_awake(b2world *w, int body, int flag);
 void b2b_apply_force_to_center(b2world *w, int body, b2v f, int wake);
 void b2b_apply_torque(b2world *w, int body, float t, int wake);
 void b2b_apply_linear_impulse(b2world *w, int body, b2v impulse, b2v point, int wake);
+
+/* test seam: b2Distance / b2CollideEdgeAndPolygon + b2WorldManifold / b2TimeOfImpact / the shapes and mass data as pure functions on
+ * the polygons of bodies 1 and 2 of `w` (b2mini.c, "geometry probe"); 0, or -1 for a bad argument */
+int b2w_geom_probe(const b2world *w, int fn, uint64_t count, const float *in, float *out);
 
 #endif

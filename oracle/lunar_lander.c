@@ -285,3 +285,17 @@ void ora_lunarlander_export(const ora_lunarlander *e, float *blob) {
 void ora_lunarlander_import(ora_lunarlander *e, const float *blob) {
     ora_lunarlander_set_state(e, blob, blob[18] > 0.5f, blob[19] > 0.5f);
 }
+
+/* Test seam (oracle.h): the mini-Box2D's collision geometry on the two shapes of the scene, created by the calls reset() makes
+ * (lander hexagon :828-842, leg box :875-879) on bodies at the origin. */
+int ora_b2_geom_probe(int fn, uint64_t count, const float *in, float *out) {
+    static b2world w; /* single-threaded test seam */
+    b2w_init(&w, bv(0.0f, -10.0f));
+    int lander = b2w_add_body(&w, bv(0.0f, 0.0f), 0.0f, 1);
+    b2v verts[6];
+    for (int i = 0; i < 6; ++i) verts[i] = bv(LANDER_POLY[i][0] / SCALE, LANDER_POLY[i][1] / SCALE);
+    b2w_set_polygon(&w, lander, verts, 6, 5.0f, 0.1f);
+    int leg = b2w_add_body(&w, bv(0.0f, 0.0f), 0.0f, 2);
+    b2w_set_box(&w, leg, LEG_W / SCALE, LEG_H / SCALE, 1.0f, 0.2f);
+    return b2w_geom_probe(&w, fn, count, in, out) == 0 ? ORA_OK : ORA_BAD_CONFIG;
+}

@@ -120,6 +120,9 @@ void ora_lunarlander_set_state(ora_lunarlander *e, const float raw[18], int leg0
 int ora_lunarlander_state_floats(void);
 void ora_lunarlander_export(const ora_lunarlander *e, float *blob);
 void ora_lunarlander_import(ora_lunarlander *e, const float *blob);
+/* test seam: the mini-Box2D's collision geometry as pure functions on the lander hexagon (pi 0) and the leg box (pi 1), built as
+ * reset() builds them; fn, columns and words as mgym_ll_geom_probe of include/mgym.h (host memory).  ORA_OK or ORA_BAD_CONFIG. */
+int ora_b2_geom_probe(int fn, uint64_t count, const float *in, float *out);
 
 /* ------------------------------------------------------ batched drivers --- */
 /* Array-of-envs drivers used by the parity tests and the cpu_baseline timing.

@@ -32,6 +32,11 @@ pub const MGYM_MATH_SINCOSF_U: c_int = 3;
 pub const MGYM_MATH_COSF_U: c_int = 4;
 pub const MGYM_MATH_TANHF: c_int = 5;
 
+pub const MGYM_LL_GEOM_SHAPES: c_int = 0;
+pub const MGYM_LL_GEOM_DISTANCE: c_int = 1;
+pub const MGYM_LL_GEOM_MANIFOLD: c_int = 2;
+pub const MGYM_LL_GEOM_TOI: c_int = 3;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct mgym_config {
@@ -114,6 +119,7 @@ unsafe extern "C" {
     pub fn mgym_episode_count(env: *mut mgym_env, finished: *mut u64) -> c_int;
     pub fn mgym_selftest_cartpole_math(device: c_int, mismatches: *mut u64) -> c_int;
     pub fn mgym_math_probe(device: c_int, fn_: c_int, first: u32, count: u64, out: *mut u32) -> c_int;
+    pub fn mgym_ll_geom_probe(device: c_int, fn_: c_int, count: u64, in_: *const f32, out: *mut f32) -> c_int;
     pub fn mgym_observation(env: *mut mgym_env, obs: *mut *const f32, col_stride: *mut u64) -> c_int;
     pub fn mgym_observation_aos(env: *mut mgym_env, out_aos: *mut f32) -> c_int;
     pub fn mgym_get_state(env: *mut mgym_env, blob: *mut c_void) -> c_int;
