@@ -206,6 +206,33 @@ int mgym_rollout_uniform(mgym_env *env, uint64_t policy_seed, int32_t K, void *a
 int mgym_rollout_linear(mgym_env *env, const float *policy, int32_t K, void *actions_out, float *obs_out,
                         float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
 
+/* mgym_rollout under an on-device policy with ONE HIDDEN LAYER (the small MLP a trainer actually has: 4 / 2 / 8 inputs, up to 64 hidden units, ReLU or
+ * tanh), evaluated where the observation already sits in registers — no [n][H] activation and no observation or action round trip through memory.
+ * Symbols: D = obs_dim; A = n_actions for the discrete families (CartPole 2, MountainCar 3, LunarLander 4) and 1 for MountainCarContinuous;
+ * H = hidden, 1 <= H <= 64.
+ * `policy` is a HOST pointer, read during the call, to H (D + 1) + A (H + 1) floats in nn.Linear order: W1[H][D] row-major, b1[H], W2[A][H] row-major, b2[A].
+ * At every step env i uses the observation o it holds BEFORE the step (as mgym_rollout_linear: at the first step of the call the handle's current
+ * observation, later the one the previous step returned — under MGYM_FLAG_AUTO_RESET, for an env that finished there, its reset observation):
+ *   hidden pre-activation  pre_j = b1[j], then for q = 0 .. D-1 ascending  pre_j = fmaf(W1[j][q], o[q], pre_j);
+ *   hidden activation      MGYM_ACT_RELU: h_j = pre_j > 0.0f ? pre_j : 0.0f (NaN and -0 both give +0);  MGYM_ACT_TANH: h_j = tanhf(pre_j), glibc's, bit for bit
+ *                          (mg_tanhf of csrc/mgym_math.h);
+ *   scores                 s_a = b2[a], then for j = 0 .. H-1 ascending  s_a = fmaf(W2[a][j], h_j, s_a);
+ *   discrete action        the sequential strict argmax of mgym_rollout_linear's LunarLander form: start with action 0 and best = s_0; row a replaces it when
+ *                          s_a > best; the first of equal scores wins, a NaN never replaces an earlier score, a NaN s_0 gives action 0;
+ *   MountainCarContinuous  s_0 is the force, handed to the step as it is (actions_out then holds f32 words).
+ * Each fmaf is ONE correctly rounded f32 fused multiply-add (C's fmaf); nothing else is fused and nothing is reassociated.  That is what a v_fma_f32 loop,
+ * a packed-FMA loop, an f32 MFMA with the bias as its C input and glibc's fmaf on the host all compute, so the words do not depend on the form the engine runs.
+ * Everything else is as mgym_rollout_linear: actions_out ([K][n_envs], may be NULL) receives the actions taken, the output shapes are the same, and the K
+ * steps equal K mgym_step calls fed those actions, word for word, MGYM_FLAG_AUTO_RESET and mgym_config::max_episode_steps included.  CartPole and
+ * MountainCar: n_envs a multiple of 4 and the buffers 16-byte aligned (CartPole: K * n_envs below 2^30), the state stays in registers across the K steps.
+ * LunarLander: any n_envs; this entry point is K x (a policy kernel, mgym_step) at every K — the persistent launch of mgym_rollout does not carry this
+ * policy; a handle that was never reset reports MGYM_ERR_NOT_RESET at the next mgym_sync.
+ * Errors, reported before any launch with the argument named in mgym_last_error: NULL policy, hidden outside 1 .. 64, an unknown activation -> MGYM_ERR_BAD_ARG.
+ * Under graph capture the weights are frozen into the captured launches, as the linear policy's are. */
+enum { MGYM_ACT_RELU = 0, MGYM_ACT_TANH = 1 };
+int mgym_rollout_mlp(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, int32_t K,
+                     void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
+
 /* Number of env-steps of this handle that returned done or truncated since mgym_create (StepInfo.done / .truncated,
  * cartpole.rs:300-305): accumulated inside the step kernels by __ballot/popcount reductions of the done mask,
  * one fire-and-forget atomic per wave.  Synchronises the stream. */

@@ -63,6 +63,10 @@ class VecGym {
     void rollout_linear(const float* policy, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_linear(env_, policy, K, actions_out, obs, reward, done, trunc));
     }
+    // K fused steps under the on-device one-hidden-layer policy: policy = W1[H][D], b1[H], W2[A][H], b2[A] (host floats), activation MGYM_ACT_RELU / MGYM_ACT_TANH
+    void rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
+        check(mgym_rollout_mlp(env_, policy, hidden, activation, K, actions_out, obs, reward, done, trunc));
+    }
     void rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_uniform(env_, policy_seed, K, actions_out, obs, reward, done, trunc));
     }

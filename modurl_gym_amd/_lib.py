@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libmgym.so")
 OK, ERR_INVALID_ACTION, ERR_NOT_RESET, ERR_BAD_CONFIG, ERR_HIP, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_CAPACITY = range(8)
 CARTPOLE, MOUNTAINCAR, MOUNTAINCAR_CONT, LUNARLANDER = range(4)
 FLAG_AUTO_RESET = 1
+ACT_RELU, ACT_TANH = range(2)   # mgym_rollout_mlp hidden activations
 MATH_SINF, MATH_COSF, MATH_SINCOSF, MATH_SINCOSF_U, MATH_COSF_U, MATH_TANHF = range(6)   # mgym_math_probe entry points
 LL_GEOM_SHAPES, LL_GEOM_DISTANCE, LL_GEOM_MANIFOLD, LL_GEOM_TOI = range(4)   # mgym_ll_geom_probe probes
 
@@ -49,6 +50,7 @@ PROTOTYPES = {
     "mgym_rollout": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "mgym_rollout_uniform": (C.c_int, [_vp, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_rollout_linear": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "mgym_rollout_mlp": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_episode_count": (C.c_int, [_vp, _u64p]),
     "mgym_observation": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "mgym_observation_aos": (C.c_int, [_vp, _vp]),

@@ -275,6 +275,16 @@ int mgym_rollout_linear(mgym_env* env, const float* policy, int32_t K, void* act
     return e->rollout_linear(policy, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
+int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, int32_t K, void* actions_out, float* obs_out,
+                     float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
+    ENV_OR_FAIL(env);
+    if (K < 0) return bad_arg("mgym_rollout_mlp: K < 0");
+    if (!policy) return bad_arg("mgym_rollout_mlp: policy is NULL");
+    if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp: hidden must be between 1 and 64");
+    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
+    return e->rollout_mlp(policy, hidden, activation, K, actions_out, obs_out, reward_out, done_out, trunc_out);
+}
+
 int mgym_episode_count(mgym_env* env, uint64_t* finished) {
     ENV_OR_FAIL(env);
     if (!finished) return bad_arg("mgym_episode_count: NULL");

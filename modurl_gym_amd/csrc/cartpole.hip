@@ -12,7 +12,7 @@
 // addressed through ONE buffer resource — descriptor and column / pass offsets in SGPRs, one constant
 // VGPR lane offset, no per-lane address arithmetic; the physics constants (cartpole.rs:45-56: none is a
 // builder argument) are compile-time constants; outputs leave with non-temporal stores.
-// No MFMA: the path is element-wise.
+// No MFMA: the physics is element-wise, and the one contraction (the hidden layer of mgym_rollout_mlp) was measured faster as packed VALU FMAs.
 //
 // Algorithmic HBM bytes per env-step (obs_out == NULL, zero-copy observation): 50
 //   state 16 R + 16 W, action 4 R, reward 4 W, done 1 W, truncated 1 W, ctr 4 R + 4 W.
@@ -31,6 +31,7 @@
 // The same ballots feed the per-handle finished-episode counter (mgym_episode_count).
 #include "common.h"
 #include "cartpole_step.h"
+#include "mlp_policy.h"
 #include "philox.h"
 
 namespace mgym {
@@ -305,8 +306,15 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
 }
 
 // policy of a fused rollout: actions from the caller's [K][n] table, or drawn on the device
-enum { ROLL_TABLE = 0, ROLL_UNIFORM = 1, ROLL_LINEAR = 2 };
+enum { ROLL_TABLE = 0, ROLL_UNIFORM = 1, ROLL_LINEAR = 2, ROLL_MLP_RELU = 3, ROLL_MLP_TANH = 4 };
 struct LinearPolicy { float w[4], b; };   // action = ((w0 x + w1 x_dot) + w2 theta) + w3 theta_dot + b > 0 (mgym_rollout_linear)
+// mgym_rollout_mlp: the weight pack of mlp_policy.h takes the place of the five linear words in the kernel's arguments (1 804 bytes by value; the other
+// policies' instantiations keep the arguments they had)
+typedef MlpPack<4, 2> CpMlpPack;
+constexpr bool cp_roll_is_mlp(int policy) { return policy == ROLL_MLP_RELU || policy == ROLL_MLP_TANH; }
+template <int POLICY> struct CpPolicyArg { typedef LinearPolicy type; };
+template <> struct CpPolicyArg<ROLL_MLP_RELU> { typedef CpMlpPack type; };
+template <> struct CpPolicyArg<ROLL_MLP_TANH> { typedef CpMlpPack type; };
 
 // Fused K-step rollout (mgym_rollout / mgym_rollout_uniform): one lane keeps its 4 environments in registers for
 // K steps; per step it reads one 16-B action word (or takes the next bit of its Philox policy stream) and writes
@@ -314,7 +322,7 @@ struct LinearPolicy { float w[4], b; };   // action = ((w0 x + w1 x_dot) + w2 th
 // cartpole_step_kernel by construction: same per-wave function.
 template <bool EULER, bool SB, bool RESET, int POLICY>
 __global__ void __launch_bounds__(kBlock)
-cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_t* __restrict__ act_out, uint64_t policy_seed, uint32_t policy_call, LinearPolicy lin,
+cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_t* __restrict__ act_out, uint64_t policy_seed, uint32_t policy_call, typename CpPolicyArg<POLICY>::type lin,
                         int K, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
     __shared__ WaveResetScratch<4> lds_[RESET ? kWaves : 1];
     constexpr uint64_t kPerBlock = (uint64_t)kBlock * 4;
@@ -350,9 +358,14 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
         for (int t = 0; t < K; ++t, so += nb4) {
             uint32_t a[4] = {0u, 0u, 0u, 0u}, dn[4], tr[4];
             float r[4];
-            if (POLICY == ROLL_TABLE) {
+            if constexpr (POLICY == ROLL_TABLE) {
                 if (in) { const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(ra, off4, so, 2); a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w; }
-            } else if (POLICY == ROLL_LINEAR) {
+            } else if constexpr (cp_roll_is_mlp(POLICY)) {
+                // hidden-layer policy on the observations the lane's four envs hold before the step (mlp_policy.h: fmaf chains from the bias, ascending index)
+                const float o[4][4] = {{s[0].x, s[0].xd, s[0].th, s[0].thd}, {s[1].x, s[1].xd, s[1].th, s[1].thd}, {s[2].x, s[2].xd, s[2].th, s[2].thd}, {s[3].x, s[3].xd, s[3].th, s[3].thd}};
+                mlp_actions<4, 2, POLICY == ROLL_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, false, 4>(lin, o, a);
+                if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
+            } else if constexpr (POLICY == ROLL_LINEAR) {
                 // linear policy on the observation the env holds before the step, in the documented order (the file is compiled with -ffp-contract=off)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = ((((lin.w[0] * s[k].x + lin.w[1] * s[k].xd) + lin.w[2] * s[k].th) + lin.w[3] * s[k].thd) + lin.b > 0.0f) ? 1u : 0u;
@@ -559,7 +572,7 @@ struct CartPoleEnv final : Env {
 
     template <int POLICY>
     void launch_rollout(dim3 g, const uint32_t* act, uint32_t* act_out, uint64_t pseed, uint32_t pcall, int K, float* obs_out, float* reward,
-                        uint8_t* done, uint8_t* trunc, LinearPolicy lin = LinearPolicy{}) {
+                        uint8_t* done, uint8_t* trunc, const typename CpPolicyArg<POLICY>::type& lin = typename CpPolicyArg<POLICY>::type{}) {
         const bool eu = cfg.is_euler, sb = cfg.sutton_barto_reward, rs = auto_reset;
         dim3 b(kBlock);
 #define MGYM_CP_ROLL(E, S, R) hipLaunchKernelGGL((cartpole_rollout_kernel<E, S, R, POLICY>), g, b, 0, stream, dev, act, act_out, pseed, pcall, lin, K, obs_out, reward, done, trunc)
@@ -606,6 +619,22 @@ struct CartPoleEnv final : Env {
         for (int q = 0; q < 4; ++q) lin.w[q] = policy[q];
         lin.b = policy[4];
         launch_rollout<ROLL_LINEAR>(dim3(grid_for(n / 4)), nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, lin);
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+
+    int rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        if (n == 0 || K == 0) return MGYM_OK;
+        uint32_t* ao = static_cast<uint32_t*>(actions_out);
+        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16) ||
+            (uint64_t)K * n * 4 >= (1ull << 32)) {
+            set_last_error("mgym_rollout_mlp: n_envs must be a multiple of 4, the buffers 16-byte aligned, and K * n_envs below 2^30");
+            return MGYM_ERR_BAD_ARG;
+        }
+        CpMlpPack pack;
+        mlp_pack<4, 2>(policy, hidden, pack);
+        if (activation == MGYM_ACT_TANH) launch_rollout<ROLL_MLP_TANH>(dim3(grid_for(n / 4)), nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack);
+        else launch_rollout<ROLL_MLP_RELU>(dim3(grid_for(n / 4)), nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }

@@ -72,6 +72,11 @@ struct Env {
         set_last_error("mgym_rollout_linear: not available for this environment family");
         return MGYM_ERR_BAD_ARG;
     }
+    // K fused steps under an on-device one-hidden-layer policy (mlp_policy.h); policy = W1[H][D], b1[H], W2[A][H], b2[A] (host), checked by the ABI
+    virtual int rollout_mlp(const float*, int, int, int, void*, float*, float*, uint8_t*, uint8_t*) {
+        set_last_error("mgym_rollout_mlp: not available for this environment family");
+        return MGYM_ERR_BAD_ARG;
+    }
     virtual int observation(const float** obs, uint64_t* col_stride) = 0;
     virtual int get_state(void* blob) = 0;
     virtual int set_state(const void* blob) = 0;

@@ -39,6 +39,7 @@
 
 #include "ll_kernel_common.h"
 #include "ll_roll_types.h"
+#include "mlp_policy.h"
 
 namespace mgym {
 
@@ -694,6 +695,20 @@ __global__ void __launch_bounds__(256) ll_policy_kernel(const float* __restrict_
     }
 }
 
+// mgym_rollout_mlp, K-step form only: the step's action column from the hidden-layer policy of mlp_policy.h, one environment per lane over the [8][n_pad]
+// observation columns.  The weight pack is a kernel argument (3 348 bytes by value: scalar loads, and a captured graph carries it).
+template <int ACT>
+__global__ void __launch_bounds__(256) ll_policy_mlp_kernel(const float* __restrict__ obs, uint64_t n, uint64_t n_pad, MlpPack<8, 4> pack, uint32_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float o[1][8];
+    uint32_t a[1];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[0][c] = obs[(uint64_t)c * n_pad + i];
+    mlp_actions<8, 4, ACT, false, 1>(pack, o, a);
+    out[i] = a[0];
+}
+
 // Staged resets.  The state an env has after reset() — scene, implicit step(0), observation — is a pure function of
 // (seed, env id, episode counter), so it does not have to be computed when the episode ends, on the critical path of
 // that step (reset kernel: 0.11 ms behind the contact kernel): it is PREPARED in advance, in shadow columns, by the same
@@ -1247,6 +1262,24 @@ struct LunarLanderEnv final : Env {
             pol.lin.b[j] = policy[9 * j + 8];
         }
         return policy_rollout(ROLL_ACT_LINEAR, pol, K, actions_out, obs_out, reward, done, trunc);
+    }
+    // mgym_rollout_mlp: K x (ll_policy_mlp_kernel, step()) — the persistent launch has no hidden-layer action source
+    int rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        if (n == 0 || K == 0) return MGYM_OK;
+        uint32_t* ao = static_cast<uint32_t*>(actions_out);
+        MlpPack<8, 4> pack;
+        mlp_pack<8, 4>(policy, hidden, pack);
+        const unsigned g = (unsigned)((n + 255) / 256);
+        for (int t = 0; t < K; ++t) {
+            uint32_t* a = ao ? ao + (size_t)t * n : next_act;
+            if (activation == MGYM_ACT_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
+            else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
+            MGYM_HIP(hipGetLastError());
+            int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
+                          trunc ? trunc + (size_t)t * n : nullptr);
+            if (st != MGYM_OK) return st;
+        }
+        return MGYM_OK;
     }
     // Are auto-resets staged right now?  (A dispersion override would be baked into prepared states.)  Also while the caller's stream is being
     // captured: the preparation branch goes into the graph (every event it needs is recorded inside the capture: see step_multi_stream()).

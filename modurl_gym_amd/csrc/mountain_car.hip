@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "mgym_math.h"
+#include "mlp_policy.h"
 #include "philox.h"
 #include "time_limit.h"
 
@@ -267,12 +268,18 @@ struct McLinearPolicy { float w[3][2], b[3]; };
 // (g, number of earlier mgym_rollout_uniform calls on this handle, SLOT_POLICY + block).  Discrete(3): step t takes, for env g + k, half (t % 2) of word k
 // of block t / 2 (low half first), h, and the action (3 h) >> 16 — each action within 2^-16 of 1/3.  Box(-1, 1): word k of block t, top 24 bits u:
 // the force u 2^-23 - 1, uniform over the multiples of 2^-23 in [-1, 1).
-enum { MC_ROLL_TABLE = 0, MC_ROLL_LINEAR = 1, MC_ROLL_UNIFORM = 2 };
+enum { MC_ROLL_TABLE = 0, MC_ROLL_LINEAR = 1, MC_ROLL_UNIFORM = 2, MC_ROLL_MLP_RELU = 3, MC_ROLL_MLP_TANH = 4 };
 struct McUniformPolicy { uint64_t seed; uint32_t call; };
+// mgym_rollout_mlp: the weight pack of mlp_policy.h (A = 3 scores, or the one force of MountainCarContinuous) takes the place of the linear words in the
+// kernel's arguments; the other policies' instantiations keep the arguments they had
+constexpr bool mc_roll_is_mlp(int policy) { return policy == MC_ROLL_MLP_RELU || policy == MC_ROLL_MLP_TANH; }
+template <bool CONT, int POLICY> struct McPolicyArg { typedef McLinearPolicy type; };
+template <bool CONT> struct McPolicyArg<CONT, MC_ROLL_MLP_RELU> { typedef MlpPack<2, CONT ? 1 : 3> type; };
+template <bool CONT> struct McPolicyArg<CONT, MC_ROLL_MLP_TANH> { typedef MlpPack<2, CONT ? 1 : 3> type; };
 template <bool CONT, int POLICY = MC_ROLL_TABLE, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
-                           uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, McLinearPolicy lin = McLinearPolicy{}, uint32_t* __restrict__ act_out = nullptr,
+                           uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, typename McPolicyArg<CONT, POLICY>::type lin = {}, uint32_t* __restrict__ act_out = nullptr,
                            McUniformPolicy uni = McUniformPolicy{}) {
     constexpr bool LINEAR = POLICY == MC_ROLL_LINEAR;
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
@@ -298,6 +305,11 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                     if constexpr (CONT) a[k] = __float_as_uint((float)(bits.w[k] >> 8) * 1.1920928955078125e-07f - 1.0f);
                     else a[k] = ((((t & 1) ? bits.w[k] >> 16 : bits.w[k] & 0xffffu)) * 3u) >> 16;
                 }
+                if (act_out) __builtin_nontemporal_store(mc_u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<mc_u32x4*>(act_out + off));
+            } else if constexpr (mc_roll_is_mlp(POLICY)) {
+                // hidden-layer policy on (position, velocity) of the lane's four envs before the step (mlp_policy.h)
+                const float o[4][2] = {{ps[0], vs[0]}, {ps[1], vs[1]}, {ps[2], vs[2]}, {ps[3], vs[3]}};
+                mlp_actions<2, CONT ? 1 : 3, POLICY == MC_ROLL_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, CONT, 4>(lin, o, a);
                 if (act_out) __builtin_nontemporal_store(mc_u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<mc_u32x4*>(act_out + off));
             } else if constexpr (LINEAR) {
 #pragma unroll
@@ -532,6 +544,26 @@ struct MountainCarEnv final : Env {
         dim3 gv(grid_for(n / 4)), b(kBlock);
         mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
             hipLaunchKernelGGL((mountaincar_rollout_kernel<decltype(C)::value, MC_ROLL_LINEAR, decltype(T)::value>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, lin, ao, McUniformPolicy{});
+        });
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+
+    int rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        if (n == 0 || K == 0) return MGYM_OK;
+        uint32_t* ao = static_cast<uint32_t*>(actions_out);
+        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16)) {
+            set_last_error("mgym_rollout_mlp: n_envs must be a multiple of 4 and the buffers 16-byte aligned");
+            return MGYM_ERR_BAD_ARG;
+        }
+        dim3 gv(grid_for(n / 4)), b(kBlock);
+        const bool tanh_act = activation == MGYM_ACT_TANH;
+        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
+            constexpr bool CONT = decltype(C)::value, TL = decltype(T)::value;
+            MlpPack<2, CONT ? 1 : 3> pack;
+            mlp_pack<2, CONT ? 1 : 3>(policy, hidden, pack);
+            if (tanh_act) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, MC_ROLL_MLP_TANH, TL>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, pack, ao, McUniformPolicy{});
+            else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, MC_ROLL_MLP_RELU, TL>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, pack, ao, McUniformPolicy{});
         });
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;

@@ -219,6 +219,50 @@ class VecEnv:
         sh = lambda x, shape: x.numpy().reshape(-1)[: int(np.prod(shape))].reshape(shape)
         return (sh(da, (K, self.n)), sh(do, (K, self.obs_dim, self.n)), sh(dr, (K, self.n)), sh(dd, (K, self.n)), sh(dt, (K, self.n)))
 
+    def mlp_dims(self):
+        """(D, A) of mgym_rollout_mlp for this family: obs_dim inputs; one score per action, or the one force of MountainCarContinuous"""
+        return self.obs_dim, (1 if self.action_is_float else self.n_actions)
+
+    def pack_mlp(self, w1, b1, w2, b2):
+        """nn.Linear-layout weights (w1 [H, D], b1 [H], w2 [A, H], b2 [A]; arrays or anything np.asarray takes) -> (policy, H): the H (D + 1) + A (H + 1)
+        float32 words mgym_rollout_mlp reads.  Shapes are checked against the family (PolicyShapeError); H itself is checked by the engine."""
+        D, A = self.mlp_dims()
+        w1, b1, w2, b2 = (np.asarray(x, np.float32) for x in (w1, b1, w2, b2))
+        H = w1.shape[0] if w1.ndim == 2 else -1
+        if w1.shape != (H, D) or b1.shape != (H,) or w2.shape != (A, H) or b2.shape != (A,):
+            raise PolicyShapeError(L.ERR_BAD_ARG, f"{KIND_NAMES[self.kind]} takes w1 [H, {D}], b1 [H], w2 [{A}, H], b2 [{A}]; got "
+                                                  f"{w1.shape}, {b1.shape}, {w2.shape}, {b2.shape}")
+        return np.concatenate([w1.ravel(), b1, w2.ravel(), b2]).astype(np.float32), H
+
+    def rollout_mlp_device(self, policy, hidden, activation, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
+        """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): `policy` = the packed host floats of pack_mlp (or None, which the
+        engine rejects), `hidden` = H, `activation` = "relu" / "tanh" or the MGYM_ACT_* value.  A policy of the wrong length for H raises PolicyShapeError."""
+        act = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH}.get(activation, activation)
+        if not isinstance(act, (int, np.integer)):
+            raise PolicyShapeError(L.ERR_BAD_ARG, f'activation must be "relu", "tanh" or an MGYM_ACT_* value, got {activation!r}')
+        pol = None
+        if policy is not None:
+            D, A = self.mlp_dims()
+            pol_in = np.asarray(policy, np.float32).ravel()
+            if 1 <= int(hidden) <= 64 and pol_in.size != int(hidden) * (D + 1) + A * (int(hidden) + 1):
+                raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {int(hidden) * (D + 1) + A * (int(hidden) + 1)} floats for hidden = {hidden}, got {pol_in.size}")
+            pol = np.ascontiguousarray(pol_in).ctypes.data_as(C.POINTER(C.c_float))
+        _check(self._lib.mgym_rollout_mlp(self._h, pol, int(hidden), int(act), int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out),
+                                          _ptr(trunc_out)))
+
+    def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
+        """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc); actions float32 for MountainCarContinuous"""
+        policy, H = self.pack_mlp(w1, b1, w2, b2)
+        n = max(self.n, 1)
+        da = DeviceArray((K, n), self.action_dtype, self.device)
+        do = DeviceArray((K, self.obs_dim, n), np.float32, self.device)
+        dr = DeviceArray((K, n), np.float32, self.device)
+        dd, dt = DeviceArray((K, n), np.uint8, self.device), DeviceArray((K, n), np.uint8, self.device)
+        self.rollout_mlp_device(policy, H, activation, K, da, do, dr, dd, dt)
+        self.sync()
+        sh = lambda x, shape: x.numpy().reshape(-1)[: int(np.prod(shape))].reshape(shape)
+        return (sh(da, (K, self.n)), sh(do, (K, self.obs_dim, self.n)), sh(dr, (K, self.n)), sh(dd, (K, self.n)), sh(dt, (K, self.n)))
+
     def rollout_uniform(self, policy_seed, K):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""
         n = max(self.n, 1)

@@ -152,6 +152,18 @@ class TorchVecEnv:
         self.env.rollout_linear_device(policy, K, act, obs, rew, done, trunc)
         return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
 
+    def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
+        """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): w1 [H, D], b1 [H], w2 [A, H], b2 [A] are tensors (or arrays) in
+        nn.Linear layout — `rollout_mlp(net[0].weight, net[0].bias, net[2].weight, net[2].bias, K)` for nn.Sequential(Linear, ReLU / Tanh, Linear) — read on the
+        host during the call; activation "relu" or "tanh".  Returns (actions, obs, reward, done, truncated) like rollout_linear."""
+        self._bind_stream()
+        host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2)]
+        policy, H = self.env.pack_mlp(*host)
+        K = int(K)
+        act, obs, rew, done, trunc = self._policy_outputs(K)
+        self.env.rollout_mlp_device(policy, H, activation, K, act, obs, rew, done, trunc)
+        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+
     def rollout_uniform(self, seed, K):
         """K fused steps under the on-device uniform random policy (mgym_rollout_uniform, include/mgym.h): returns (actions, obs, reward,
         done, truncated) like rollout_linear."""

@@ -25,6 +25,9 @@ pub const MGYM_LUNARLANDER: c_int = 3;
 
 pub const MGYM_FLAG_AUTO_RESET: u32 = 1;
 
+pub const MGYM_ACT_RELU: i32 = 0;
+pub const MGYM_ACT_TANH: i32 = 1;
+
 pub const MGYM_MATH_SINF: c_int = 0;
 pub const MGYM_MATH_COSF: c_int = 1;
 pub const MGYM_MATH_SINCOSF: c_int = 2;
@@ -109,6 +112,18 @@ unsafe extern "C" {
     pub fn mgym_rollout_linear(
         env: *mut mgym_env,
         policy: *const f32,
+        k: i32,
+        actions_out: *mut c_void,
+        obs_out: *mut f32,
+        reward_out: *mut f32,
+        done_out: *mut u8,
+        trunc_out: *mut u8,
+    ) -> c_int;
+    pub fn mgym_rollout_mlp(
+        env: *mut mgym_env,
+        policy: *const f32,
+        hidden: i32,
+        activation: i32,
         k: i32,
         actions_out: *mut c_void,
         obs_out: *mut f32,

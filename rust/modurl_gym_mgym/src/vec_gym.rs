@@ -165,6 +165,35 @@ impl VecGym {
         }
         check(unsafe { mgym_rollout_linear(self.env, policy.as_ptr(), k, actions_out, obs, reward, done, truncated) })
     }
+    /// K fused steps under an on-device one-hidden-layer policy (`mgym_rollout_mlp`): `policy` holds `W1[H][D]`, `b1[H]`, `W2[A][H]`, `b2[A]` in that order
+    /// (the `weight` / `bias` tensors of two `Linear` layers, flattened), D = obs_dim, A = n_actions (1 for MountainCarContinuous, whose score is the force),
+    /// 1 <= `hidden` <= 64, `activation` = `MGYM_ACT_RELU` or `MGYM_ACT_TANH`.  Both layers are ascending-index `fmaf` chains from the bias; the action is the
+    /// first largest score.  LunarLander runs it as K x (policy kernel, step).
+    /// # Safety
+    /// the output pointers are device pointers of `[K][n]` (`[K][obs_dim][n]` for `obs`) elements, or null.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn rollout_mlp(
+        &mut self,
+        policy: &[f32],
+        hidden: i32,
+        activation: i32,
+        k: i32,
+        actions_out: *mut c_void,
+        obs: *mut f32,
+        reward: *mut f32,
+        done: *mut u8,
+        truncated: *mut u8,
+    ) -> Result<(), MgymError> {
+        let (d, a) = (self.spec.obs_dim as usize, if self.spec.action_is_float != 0 { 1 } else { self.spec.n_actions as usize });
+        if (1..=64).contains(&hidden) {
+            let h = hidden as usize;
+            let want = h * (d + 1) + a * (h + 1);
+            if policy.len() != want {
+                return Err(MgymError { status: MGYM_ERR_BAD_ARG, message: format!("rollout_mlp: {} policy floats for hidden = {}, got {}", want, hidden, policy.len()) });
+            }
+        }
+        check(unsafe { mgym_rollout_mlp(self.env, policy.as_ptr(), hidden, activation, k, actions_out, obs, reward, done, truncated) })
+    }
     /// K fused steps under the on-device uniform random policy (`mgym_rollout_uniform`; every family, the draws as `include/mgym.h` documents them): no action table.
     /// `actions_out` (`[K][n]` u32, may be null) receives the drawn actions.
     #[allow(clippy::too_many_arguments)]

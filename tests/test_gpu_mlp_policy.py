@@ -1,0 +1,309 @@
+"""mgym_rollout_mlp (include/mgym.h): the one-hidden-layer policy inside the CartPole / MountainCar rollout kernels and LunarLander's K-step policy kernel.
+The reference for the actions is modurl_gym_amd/csrc/mlp_policy.h itself, compiled for the host (tests/native/mlp_policy_check.cpp as a shared object;
+tests/test_mlp_policy_host.py pins that build to the documented arithmetic), applied to the observation each env holds before the step; the reference for
+everything else is a second handle stepped with those actions.  Every comparison is of whole words: no tolerance anywhere."""
+import itertools
+
+import numpy as np
+import pytest
+
+import modurl_gym_amd as mg
+from mlp_policy_ref import FAMILIES, RELU, TANH, build_shared, header_actions
+
+pytestmark = pytest.mark.gpu
+
+KINDS = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_continuous": mg.MOUNTAINCAR_CONT, "lunar_lander": mg.LUNARLANDER}
+ACT_NAME = {RELU: "relu", TANH: "tanh"}
+# what a unit of each observation component is worth to the first layer: MountainCar's velocity lives in +-0.07, CartPole's angle in +-0.2
+IN_SCALE = {"cartpole": (2.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "mountain_car_continuous": (2.0, 40.0), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
+# weight seeds, chosen on the CPU (the oracle stepped under the host-compiled header) so that within the 160 steps of the largest population every action of
+# the family occurs, hidden units take both signs and, for LunarLander, legs touch and episodes finish — facts the tests assert again on the GPU's outputs
+SEEDS = {
+    ("cartpole", 1, RELU): 6, ("cartpole", 1, TANH): 1, ("cartpole", 7, RELU): 0, ("cartpole", 7, TANH): 0, ("cartpole", 64, RELU): 0, ("cartpole", 64, TANH): 0,
+    ("mountain_car", 1, RELU): 172, ("mountain_car", 1, TANH): 44, ("mountain_car", 7, RELU): 47, ("mountain_car", 7, TANH): 27, ("mountain_car", 64, RELU): 40, ("mountain_car", 64, TANH): 2,
+    ("mountain_car_continuous", 1, RELU): 48, ("mountain_car_continuous", 1, TANH): 6, ("mountain_car_continuous", 7, RELU): 3, ("mountain_car_continuous", 7, TANH): 0,
+    ("mountain_car_continuous", 64, RELU): 11, ("mountain_car_continuous", 64, TANH): 11,
+    ("lunar_lander", 1, RELU): 87, ("lunar_lander", 1, TANH): 12, ("lunar_lander", 7, RELU): 3, ("lunar_lander", 7, TANH): 0, ("lunar_lander", 64, RELU): 0, ("lunar_lander", 64, TANH): 0,
+}
+HIDDEN_ACT = list(itertools.product((1, 7, 64), (RELU, TANH)))
+K, CALLS = 40, 4
+ENV_SEED = 11
+
+
+def weights(fam, H, act, seed=None):
+    """nn.Linear-layout float32 weights (w1 [H, D], b1 [H], w2 [A, H], b2 [A]) from the family's seed"""
+    D, A, _ = FAMILIES[fam]
+    rng = np.random.default_rng(1000 + (SEEDS[(fam, H, act)] if seed is None else seed))
+    w1 = (rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[fam])).astype(np.float32)
+    b1 = rng.normal(0, 0.5, H).astype(np.float32)
+    w2 = (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32)
+    b2 = rng.normal(0, 0.1, A).astype(np.float32)
+    return w1, b1, w2, b2
+
+
+def packed(w):
+    return np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]]).astype(np.float32)
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def make(fam, n, auto_reset, limit=0, seed=ENV_SEED):
+    extra = {"enable_wind": True} if fam == "lunar_lander" else {}
+    return mg.VecEnv(KINDS[fam], n, seed=seed, auto_reset=auto_reset, max_episode_steps=limit, **extra)
+
+
+@pytest.fixture(scope="module")
+def header():
+    return build_shared()
+
+
+class Facts:
+    """what the weights reach, gathered from the GPU's own outputs"""
+
+    def __init__(self, fam, w):
+        self.fam, self.w = fam, w
+        self.actions, self.pos, self.neg, self.legs, self.done, self.trunc, self.force_pos, self.force_neg = set(), 0, 0, 0, 0, 0, 0, 0
+
+    def see(self, obs_before, acts, obs, done, trunc):
+        with np.errstate(all="ignore"):
+            pre = self.w[0].astype(np.float64) @ obs_before.astype(np.float64) + self.w[1].astype(np.float64)[:, None]
+        self.pos += int((pre > 1e-3).sum())
+        self.neg += int((pre < -1e-3).sum())
+        if self.fam == "mountain_car_continuous":
+            f = acts.view(np.float32)
+            self.force_pos += int((f > 0).sum())
+            self.force_neg += int((f < 0).sum())
+        else:
+            self.actions |= set(int(v) for v in np.unique(acts))
+        if self.fam == "lunar_lander":
+            self.legs += int((obs[6:8] > 0).sum())
+        self.done += int(done.sum())
+        self.trunc += int(trunc.sum())
+
+    def check(self, limit, auto_reset):
+        D, A, cont = FAMILIES[self.fam]
+        assert self.pos > 0 and self.neg > 0, "hidden units take both signs"
+        if cont:
+            assert self.force_pos > 0 and self.force_neg > 0
+        else:
+            assert self.actions == set(range(A)), f"every action occurs: {self.actions}"
+        if self.fam == "lunar_lander":
+            assert self.legs > 0 and self.done > 0, "legs touch and episodes finish within the 160 steps"
+        if self.fam == "cartpole":
+            assert self.done > 0
+        if limit:
+            assert self.trunc > 0, "the time limit truncates inside the rollout"
+
+
+def run_case(header, fam, n, H, act, auto_reset, limit=0):
+    D, A, cont = FAMILIES[fam]
+    w = weights(fam, H, act)
+    pol = packed(w)
+    env, loop = make(fam, n, auto_reset, limit), make(fam, n, auto_reset, limit)
+    obs = loop.reset()
+    assert same(env.reset(), obs)
+    facts = Facts(fam, w)
+    for c in range(CALLS):
+        assert same(env.observation(), obs)   # the first step of a call uses the handle's current observation
+        acts, gobs, grew, gdone, gtrunc = env.rollout_mlp(*w, K, activation=ACT_NAME[act])
+        for t in range(K):
+            a = header_actions(header, D, A, cont, act, H, pol, obs)
+            assert np.array_equal(bits(acts[t]), a), f"call {c} step {t}: actions"
+            o, r, d, tr = loop.step(a.view(np.float32) if cont else a)
+            for g, e, nm in zip((gobs[t], grew[t], gdone[t], gtrunc[t]), (o, r, d, tr), ("obs", "reward", "done", "truncated")):
+                assert same(g, e), f"call {c} step {t}: {nm}"
+            facts.see(obs, a, o, d, tr)
+            obs = o
+    assert same(env.get_state(), loop.get_state())
+    if limit:
+        assert np.array_equal(env.elapsed_steps(), loop.elapsed_steps())
+    assert env.episode_count() == loop.episode_count()
+    env.close(); loop.close()
+    return facts
+
+
+def classic_cases():
+    out = []
+    for fam in ("cartpole", "mountain_car", "mountain_car_continuous"):
+        for ni, n in enumerate((4, 1028)):   # one lane; one full block of the rollout kernel (256 lanes x 4 envs) plus one lane
+            for ci, (H, act) in enumerate(HIDDEN_ACT):
+                auto_reset = bool((ni + ci) % 2)
+                limit = 25 if fam != "cartpole" and (ci // 2 + ni) % 2 == 0 else 0   # MountainCar: both the time-limited and the plain instantiation
+                out.append(pytest.param(fam, n, H, act, auto_reset, limit, id=f"{fam}-n{n}-H{H}-{ACT_NAME[act]}-{'auto' if auto_reset else 'manual'}-limit{limit}"))
+    return out
+
+
+@pytest.mark.parametrize("fam,n,H,act,auto_reset,limit", classic_cases())
+def test_classic_rollout_equals_the_header_and_a_stepping_loop(header, fam, n, H, act, auto_reset, limit):
+    facts = run_case(header, fam, n, H, act, auto_reset, limit)
+    if n == 1028:
+        facts.check(limit, auto_reset)
+
+
+def lunar_cases():
+    out = []
+    for ni, n in enumerate((1, 97, 300)):   # 300 crosses a block of the policy kernel
+        for ci, (H, act) in enumerate(HIDDEN_ACT):
+            auto_reset = bool((ni + ci) % 2)
+            out.append(pytest.param(n, H, act, auto_reset, id=f"n{n}-H{H}-{ACT_NAME[act]}-{'auto' if auto_reset else 'manual'}"))
+    return out
+
+
+@pytest.mark.parametrize("n,H,act,auto_reset", lunar_cases())
+def test_lunar_rollout_equals_the_header_and_a_stepping_loop(header, n, H, act, auto_reset):
+    facts = run_case(header, "lunar_lander", n, H, act, auto_reset)
+    if n == 300:
+        facts.check(0, auto_reset)
+
+
+@pytest.mark.parametrize("fam,limit", [("mountain_car", 25), ("mountain_car_continuous", 25), ("lunar_lander", 60)])
+def test_time_limit_truncates_and_resets_inside_the_rollout(header, fam, limit):
+    """max_episode_steps with auto-reset: truncation, the in-kernel reset and the reset observation the policy sees next, inside one call"""
+    n = 300 if fam == "lunar_lander" else 1028
+    facts = run_case(header, fam, n, 7, TANH, True, limit)
+    assert facts.trunc > 0
+    if fam != "lunar_lander":   # the car never reaches the goal that early: every env is truncated at every 25th step
+        assert facts.trunc + facts.done >= n * (K * CALLS // limit)
+
+
+@pytest.mark.parametrize("fam,n", [("cartpole", 1028), ("mountain_car", 1028), ("lunar_lander", 300)])
+def test_mlp_rollouts_interleave_with_the_other_entry_points(header, fam, n):
+    """an MLP rollout between table, linear and uniform rollouts, a step, a masked reset and set_state: the state blobs stay equal after each"""
+    D, A, cont = FAMILIES[fam]
+    env, loop = make(fam, n, True, seed=23), make(fam, n, True, seed=23)
+    rng = np.random.default_rng(1)
+    obs = loop.reset()
+    assert same(env.reset(), obs)
+    lin = rng.normal(0, 1, (1 if fam == "cartpole" else A) * (D + 1)).astype(np.float32)
+
+    def follow(acts):
+        nonlocal obs
+        for a in acts:
+            obs = loop.step(a)[0]
+        assert same(env.get_state(), loop.get_state())
+        assert same(env.observation(), obs)
+
+    def mlp(H, act, k):
+        nonlocal obs
+        w = weights(fam, H, act)
+        acts = env.rollout_mlp(*w, k, activation=ACT_NAME[act])[0]
+        for t in range(k):   # (the header on the loop's observations, so a wrong action is caught here and not only as a state difference)
+            a = header_actions(header, D, A, cont, act, H, packed(w), obs)
+            assert np.array_equal(acts[t], a), f"H={H} step {t}"
+            obs = loop.step(a)[0]
+        follow([])
+
+    mlp(7, RELU, 16)
+    tab = rng.integers(0, A, (12, n)).astype(np.uint32)
+    env.rollout(tab); follow(tab)
+    mlp(64, TANH, 9)
+    follow(env.rollout_linear(lin, 16)[0])
+    mlp(1, RELU, 5)
+    follow(env.rollout_uniform(5, 16)[0])
+    a = rng.integers(0, A, n).astype(np.uint32)
+    env.step(a); follow([a])
+    m = (rng.random(n) < 0.3).astype(np.uint8)
+    env.reset(m); loop.reset(m); obs = loop.observation()
+    assert same(env.get_state(), loop.get_state())
+    mlp(64, RELU, 20)
+    st = loop.get_state()
+    env.set_state(st); loop.set_state(st); obs = loop.observation()
+    assert same(env.observation(), obs)
+    mlp(7, TANH, 12)
+    env.close(); loop.close()
+
+
+@pytest.mark.parametrize("fam,n", [("cartpole", 1028), ("lunar_lander", 512)])
+def test_captured_mlp_rollout_equals_the_eager_call_and_freezes_the_weights(fam, n):
+    D, A, cont = FAMILIES[fam]
+    Kc, H = 16, 64
+    cap, eag = make(fam, n, True, seed=29), make(fam, n, True, seed=29)
+    assert same(cap.reset(), eag.reset())
+    w = weights(fam, H, TANH)
+    pol = packed(w)
+    bufs = [mg.DeviceArray((Kc, n), np.uint32), mg.DeviceArray((Kc, D, n), np.float32), mg.DeviceArray((Kc, n), np.float32),
+            mg.DeviceArray((Kc, n), np.uint8), mg.DeviceArray((Kc, n), np.uint8)]
+    g = cap.graph_capture(lambda: cap.rollout_mlp_device(pol, H, "tanh", Kc, *bufs))
+    pol[:] = 0.0   # the caller's array may change after the capture: the graph carries the weights it was captured with
+    try:
+        for rep in range(2):
+            cap.graph_launch(g)
+            cap.sync()
+            exp = eag.rollout_mlp(*w, Kc, activation="tanh")
+            for b, e, nm in zip(bufs, exp, ("actions", "obs", "reward", "done", "truncated")):
+                assert same(b.numpy().reshape(-1)[: e.size].reshape(e.shape), e), f"replay {rep}: {nm}"
+            assert same(cap.get_state(), eag.get_state())
+    finally:
+        cap.graph_destroy(g)
+    cap.close(); eag.close()
+
+
+@pytest.mark.parametrize("fam,n", [("cartpole", 1028), ("mountain_car_continuous", 1028), ("lunar_lander", 300)])
+def test_torch_rollout_mlp_equals_vecenv(fam, n):
+    torch = pytest.importorskip("torch")
+    extra = {"enable_wind": True} if fam == "lunar_lander" else {}
+    te = mg.TorchVecEnv(KINDS[fam], n, seed=31, auto_reset=True, **extra)
+    ve = make(fam, n, True, seed=31)
+    te.reset()
+    ve.reset()
+    for c, (H, act) in enumerate(((7, RELU), (64, TANH))):
+        w = weights(fam, H, act)
+        got = te.rollout_mlp(*(torch.from_numpy(x) for x in w), 16, activation=ACT_NAME[act])
+        torch.cuda.synchronize()
+        exp = ve.rollout_mlp(*w, 16, activation=ACT_NAME[act])
+        for g, e, nm in zip(got, exp, ("actions", "obs", "reward", "done", "truncated")):
+            g = g.cpu().numpy()
+            g = g.view(np.uint32) if g.dtype == np.int32 else g.astype(np.uint8) if g.dtype == np.bool_ else g
+            assert same(g, e), f"call {c}: {nm}"
+    ve.close()
+
+
+def test_bad_arguments_are_reported_before_any_launch():
+    L = mg.envs.L
+    env = make("cartpole", 8, False)
+    env.reset()
+    before = env.get_state()
+    w = weights("cartpole", 7, RELU)
+    pol = packed(w)
+
+    def bad(what, *args):
+        with pytest.raises(mg.MgymError) as ei:
+            env.rollout_mlp_device(*args)
+        assert ei.value.status == L.ERR_BAD_ARG and what in str(ei.value), (what, str(ei.value))
+
+    bad("policy", None, 7, "relu", 4)
+    bad("hidden", pol, 0, "relu", 4)
+    bad("hidden", pol, 65, "relu", 4)
+    bad("hidden", pol, -3, "relu", 4)
+    bad("activation", pol, 7, 2, 4)
+    bad("activation", pol, 7, -1, 4)
+    bad("K", pol, 7, "relu", -1)
+    with pytest.raises(mg.envs.PolicyShapeError):          # host side: shapes against the family
+        env.rollout_mlp(w[0][:, :3], w[1], w[2], w[3], 4)
+    with pytest.raises(mg.envs.PolicyShapeError):
+        env.rollout_mlp(w[0], w[1], w[2][:1], w[3][:1], 4)
+    with pytest.raises(mg.envs.PolicyShapeError):
+        env.rollout_mlp_device(pol[:-1], 7, "relu", 4)
+    env.sync()
+    assert same(env.get_state(), before)                   # nothing ran
+    env.close()
+    odd = make("cartpole", 6, False)                       # CartPole and MountainCar: n_envs a multiple of 4, as mgym_rollout_linear
+    odd.reset()
+    with pytest.raises(mg.MgymError) as ei:
+        odd.rollout_mlp(*w, 4)
+    assert ei.value.status == L.ERR_BAD_ARG and "multiple of 4" in str(ei.value)
+    odd.close()
+
+
+def test_lunar_lander_without_reset_reports_not_reset():
+    env = make("lunar_lander", 8, False)
+    with pytest.raises(mg.NotResetError):
+        env.rollout_mlp(*weights("lunar_lander", 7, RELU), 4)
+    env.close()

@@ -11,9 +11,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modurl_gym_amd", "csrc")
-SRC = {"cartpole": ["cartpole.hip", "cartpole_step.h", "cartpole_math.h", "mgym_math.h", "philox.h", "common.h"],
-       "mountain_car": ["mountain_car.hip", "mgym_math.h", "philox.h", "common.h"],
-       "lunar_lander": ["lunar_lander.hip", "ll_roll.h", "ll_env.h", "ll_free.h", "ll_world.h", "ll_b2.h", "mgym_math.h", "philox.h", "common.h"]}
+SRC = {"cartpole": ["cartpole.hip", "cartpole_step.h", "cartpole_math.h", "mgym_math.h", "mlp_policy.h", "philox.h", "common.h"],
+       "mountain_car": ["mountain_car.hip", "mgym_math.h", "mlp_policy.h", "time_limit.h", "philox.h", "common.h"],
+       "lunar_lander": ["lunar_lander.hip", "ll_roll.h", "ll_env.h", "ll_free.h", "ll_world.h", "ll_b2.h", "mgym_math.h", "mlp_policy.h", "time_limit.h", "philox.h", "common.h"]}
 
 
 def sha16(files):
@@ -31,8 +31,10 @@ def main():
         fam = key.split(":")[0].replace("_cont", "").split("_rollout")[0]
         summ = json.load(open(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}", "summary.json")))["kernels"]
         files = SRC[fam]
+        kept = any(d.startswith(rnd + "_") and os.path.isdir(os.path.join(ROOT, "profiles", d)) for d in os.listdir(os.path.join(ROOT, "profiles")))   # (a round may keep only the records, not the summaries)
+        where = f"profiles/{rnd}_*/" if kept else f"round {rnd}, summaries not kept"
         rec = {"src_files": files, "src_sha16": sha16(files),
-               "source": f"profiles/{rnd}_*/ ({tag}): rocprofv3 --pmc in separate passes (tools/profile_pmc.sh), per-launch averages over the "
+               "source": f"{where} ({tag}): rocprofv3 --pmc in separate passes (tools/profile_pmc.sh), per-launch averages over the "
                          f"last quarter of the dispatches; FETCH_SIZE x2 (gfx950 correction for wide coalesced reads), WRITE_SIZE exact"}
         if fam in ("cartpole", "mountain_car"):
             name = next(k for k in summ if ("cartpole_step_kernel" in k or "mountaincar_step" in k) and "pmc" in summ[k])

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""What the hidden-layer policy costs inside the rollout kernels (mgym_rollout_mlp), beside the loop it replaces and the linear policy:
+
+    python tools/mlp_policy_time.py --repeats 5 --out profiles/mlp_policy_time.json
+
+Per family — CartPole and MountainCar at 1 048 576 envs, LunarLander (wind) at 262 144 envs, K = 16, fused auto-reset on — ns per env-step of
+    (a) mlp/H{32,64}/{relu,tanh}   mgym_rollout_mlp, one call per K steps, actions not stored (the packed-VALU form, the one that ships; the record
+                                   profiles/mlp_policy_time.json also holds mlp_mfma/... rows of CartPole, taken in the same processes on a build that
+                                   had the hidden layer on the matrix pipe behind a knob: it was slower and was removed)
+    (b) torch/H{32,64}/{relu,tanh} the loop it replaces: TorchVecEnv with AoS observations [n, D]; per step torch.addmm(b1, obs, W1^T), the activation,
+                                   torch.addmm(b2, h, W2^T), argmax, TorchVecEnv.step — eager kernels, the [n, H] activation through memory
+    (c) linear                     mgym_rollout_linear, for scale
+The weights are seeded normal draws scaled to the observation's range (the timing depends on them only through how often episodes end).  Timing: HIP
+events on the stream the work is issued on (the handle's own timer for (a) and (c), torch events on torch's current stream, which TorchVecEnv
+binds the handle to, for (b)), a warm-up, then a window of at least --window seconds.  Every repeat is a fresh process per family, the cases of a
+process in an order that rotates with the repeat; the summary gives median, min, max and spread ((max - min) / median) over the repeats — the
+spread is the noise figure every comparison is read against."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FAMILIES = [("cartpole", 1 << 20), ("mountain_car", 1 << 20), ("lunar_lander", 1 << 18)]
+IN_SCALE = {"cartpole": (2.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
+K = 16
+
+
+def worker(family, n, window, rotate):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import modurl_gym_amd as mg
+    kind = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "lunar_lander": mg.LUNARLANDER}[family]
+    kw = dict(enable_wind=True) if family == "lunar_lander" else {}
+    spec = mg.get_spec(kind)
+    D, A = spec.obs_dim, spec.n_actions
+
+    def weights(H):
+        rng = np.random.default_rng(100 + H)
+        return ((rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[family])).astype(np.float32), rng.normal(0, 0.5, H).astype(np.float32),
+                (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.1, A).astype(np.float32))
+
+    def window_of(timed):
+        timed(5)                                        # warm-up
+        per = timed(5) / 5                              # ms per launch of K steps
+        count = max(5, int(window * 1000.0 / per) + 1)
+        return timed(count), count
+
+    def fused(call):
+        env = mg.VecEnv(kind, n, seed=7, auto_reset=True, **kw)
+        rew, done, trunc = mg.DeviceArray((K, n), np.float32), mg.DeviceArray((K, n), np.uint8), mg.DeviceArray((K, n), np.uint8)
+        env.reset_device()
+        env.sync()
+
+        def timed(count):
+            env.timer_start()
+            for _ in range(count):
+                call(env, rew, done, trunc)
+            ms = env.timer_stop()
+            env.sync()                                  # (raises on a sticky device error)
+            return ms
+
+        ms, count = window_of(timed)
+        info = env.info()
+        env.close()
+        return ms, count, info
+
+    def torch_loop(H, act):
+        env = mg.TorchVecEnv(kind, n, seed=7, auto_reset=True, obs_layout="aos", **kw)
+        w1, b1, w2, b2 = (torch.from_numpy(x).cuda() for x in weights(H))
+        w1t, w2t = w1.t().contiguous(), w2.t().contiguous()
+        fn = torch.relu if act == "relu" else torch.tanh
+        state = [env.reset()]
+
+        def timed(count):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            obs = state[0]
+            e0.record()
+            for _ in range(count * K):
+                h = fn(torch.addmm(b1, obs, w1t))
+                a = torch.addmm(b2, h, w2t).argmax(1).to(torch.int32)
+                obs = env.step(a)[0]
+            e1.record()
+            e1.synchronize()
+            env.check()
+            state[0] = obs
+            return e0.elapsed_time(e1)
+
+        ms, count = window_of(timed)
+        return ms, count, {}
+
+    cases = []
+    for H in (32, 64):
+        for act in ("relu", "tanh"):
+            w = weights(H)
+            pol = np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]])   # nn.Linear order: W1[H][D], b1[H], W2[A][H], b2[A]
+            cases.append((f"mlp/H{H}/{act}", lambda pol=pol, H=H, act=act: fused(lambda env, r, d, t: env.rollout_mlp_device(pol, H, act, K, None, None, r, d, t))))
+            cases.append((f"torch/H{H}/{act}", lambda H=H, act=act: torch_loop(H, act)))
+    lin = np.random.default_rng(3).normal(0, 1, (1 if family == "cartpole" else A) * (D + 1)).astype(np.float32)
+    cases.append(("linear", lambda: fused(lambda env, r, d, t: env.rollout_linear_device(lin, K, None, None, r, d, t))))
+    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
+    out = []
+    for name, run in cases:
+        ms, count, info = run()
+        out.append(dict(family=family, n_envs=n, K=K, case=name, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n),
+                        env_steps_per_s=count * K * n / (ms * 1e-3), rollout_form=info.get("rollout")))
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def write_record(path, head, table):
+    """one line per case: the record stays readable in a diff"""
+    with open(path, "w") as f:
+        f.write("{\n")
+        for k, v in head.items():
+            f.write(f" {json.dumps(k)}: {json.dumps(v)},\n")
+        f.write(' "summary": {\n' + ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in table.items()) + "\n }\n}\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.3, help="seconds of timed work per case")
+    ap.add_argument("--scale", type=float, default=1.0, help="population scale (smoke runs)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlp_policy_time.json"))
+    ap.add_argument("--worker", nargs=3, metavar=("FAMILY", "N", "ROTATE"))
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args.worker[0], int(args.worker[1]), args.window, int(args.worker[2]))
+    runs = []
+    for rep in range(args.repeats):
+        for family, n in FAMILIES:
+            n = max(1024, int(n * args.scale)) // 1024 * 1024
+            # a fresh child per family and repeat; the parent never opens the GPU
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", family, str(n), str(3 * rep), "--window", str(args.window)],
+                               capture_output=True, text=True, timeout=600)
+            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+            if r.returncode != 0 or not line:
+                print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
+                raise SystemExit(f"worker {family} repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
+            runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
+            print(f"repeat {rep} {family}: done", flush=True)
+    summary = {}
+    for rec in runs:
+        summary.setdefault(f"{rec['family']}/{rec['case']}", []).append(rec["ns_per_env_step"])
+    table = {k: dict(median=statistics.median(v), min=min(v), max=max(v), spread=(max(v) - min(v)) / statistics.median(v),
+                     env_steps_per_s=1e9 / statistics.median(v), repeats=[round(x, 6) for x in v]) for k, v in sorted(summary.items())}
+    head = dict(unit="ns per env-step", K=K, window_s=args.window, repeats=args.repeats, scale=args.scale,
+                n_envs={f: max(1024, int(n * args.scale)) // 1024 * 1024 for f, n in FAMILIES},
+                forms="mlp: the packed-VALU form (v_pk_fma_f32 chains, weights as scalar operands)")
+    write_record(args.out, head, table)
+    for k, v in table.items():
+        print(f"{k:34s} median {v['median']:.4f}  min {v['min']:.4f}  max {v['max']:.4f}  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s")
+
+
+if __name__ == "__main__":
+    main()
