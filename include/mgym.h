@@ -225,8 +225,12 @@ int mgym_rollout_linear(mgym_env *env, const float *policy, int32_t K, void *act
  * Everything else is as mgym_rollout_linear: actions_out ([K][n_envs], may be NULL) receives the actions taken, the output shapes are the same, and the K
  * steps equal K mgym_step calls fed those actions, word for word, MGYM_FLAG_AUTO_RESET and mgym_config::max_episode_steps included.  CartPole and
  * MountainCar: n_envs a multiple of 4 and the buffers 16-byte aligned (CartPole: K * n_envs below 2^30), the state stays in registers across the K steps.
- * LunarLander: any n_envs; this entry point is K x (a policy kernel, mgym_step) at every K — the persistent launch of mgym_rollout does not carry this
- * policy; a handle that was never reset reports MGYM_ERR_NOT_RESET at the next mgym_sync.
+ * LunarLander: any n_envs; by default this entry point is K x (a policy kernel, mgym_step) at every K.  The persistent launch of mgym_rollout (ll_roll.h)
+ * carries this policy too — each environment's next action decided where its observation is produced, ReLU and tanh alike, the same words — and runs it
+ * under the conditions of mgym_rollout_linear (from MGYM_LL_ROLLOUT_MIN_K steps up, below the launch's population limit, not while the stream is being
+ * captured) for an activation that has been measured faster there (none yet) and, with MGYM_LL_ROLLOUT_MLP=1 in the environment at mgym_create, for
+ * both; mgym_get_info's rollout_persistent_launches tells which form ran.  The weights are copied during the call in both forms: consecutive calls on
+ * one stream each use their own.  A handle that was never reset reports MGYM_ERR_NOT_RESET at the next mgym_sync.
  * Errors, reported before any launch with the argument named in mgym_last_error: NULL policy, hidden outside 1 .. 64, an unknown activation -> MGYM_ERR_BAD_ARG.
  * Under graph capture the weights are frozen into the captured launches, as the linear policy's are. */
 enum { MGYM_ACT_RELU = 0, MGYM_ACT_TANH = 1 };
@@ -299,7 +303,10 @@ const char *mgym_last_error(void);
 /* Describes how this handle runs, as NUL-terminated "key=value" lines written to buf (at most cap bytes, always terminated;
  * returns MGYM_ERR_BAD_ARG if cap is too small).  Keys every family reports: kind, n_envs, device, auto_reset, max_episode_steps,
  * GPU_MAX_HW_QUEUES (the HIP runtime knob as this process's environment held it when the handle was created, or "unset").
- * LunarLander adds its launch structure — contact_block, launch_order, staged_resets — and `concurrent_streams`: the
+ * LunarLander adds its launch structure — contact_block, launch_order, staged_resets, the rollout's form (rollout, rollout_min_k, rollout_waves,
+ * rollout_helper_blocks) and rollout_persistent_launches, the number of persistent rollout launches this handle has issued since mgym_create
+ * (mgym_rollout, _linear, _uniform and _mlp alike; a call of more than 240 steps is several launches; 0 for a call that ran as K x mgym_step: the
+ * words are the same either way, this line tells which form ran) — and `concurrent_streams`: the
  * reference is single-threaded (lunar_lander.rs:240-249), this engine steps one population on up to three streams
  * (caller's stream, two helpers), and they only run side by side when the runtime put them on different hardware queues.
  * The call launches a ~50 us probe kernel on each of them at once and reports how many were seen running at the same

@@ -255,13 +255,36 @@ template <int POLICY> using RollPolicyOf = typename std::conditional<POLICY == R
 template <int POLICY, class PolT>
 LLD uint32_t roll_action(const LLDev& d, const LLIo& io, const PolT& pol, uint32_t i, uint32_t t) {
     if constexpr (POLICY == ROLL_ACT_TABLE) return io.act[(uint64_t)t * d.n + i];
-    else if constexpr (POLICY == ROLL_ACT_LINEAR) return RA_LOAD(pol.next + i);
+    else if constexpr (roll_act_observes(POLICY)) return RA_LOAD(pol.next + i);
     else return ll_uniform_action(pol.seed, pol.call, d.env_id_base + i, pol.t0 + t);
 }
 // the action step t has taken, for mgym_rollout_{linear,uniform}'s actions_out (one writer: the wave that finishes the step)
 template <int POLICY, class PolT>
 LLD void roll_write_action(const LLDev& d, const PolT& pol, uint32_t t, uint32_t i, uint32_t a) {
     if constexpr (POLICY != ROLL_ACT_TABLE) { if (pol.act_out) pol.act_out[(uint64_t)t * d.n + i] = a; }
+}
+
+// the action an observation-driven source decides from the observation `state`: step t + 1's, where step t's observation is produced.  The hidden-layer
+// sources are mlp_policy.h's mlp_actions for one environment per lane — the code of the K-step form's ll_policy_mlp_kernel and of the host check, so the
+// words are equal by construction; the pack is addressed in the constant address space (ll_roll_types.h): nothing stores to it while a launch runs.
+template <int POLICY>
+LLD uint32_t roll_decide(const RollPolicy& pol, const float* state) {
+    static_assert(roll_act_observes(POLICY), "only the sources that decide from the observation");
+    if constexpr (POLICY == ROLL_ACT_LINEAR) return ll_linear_action(pol.lin, state);
+    else {
+        // (the constant-space pointer goes through an empty asm: a plain cast there and back is folded away, the loads stay global and — the launch stores
+        // and fences everywhere — become vector loads of a uniform address; with it each unit is s_load_dwordx8 + x4 + x1 and the loop counter a scalar)
+        typedef const __attribute__((address_space(4))) LLMlpPack* ConstPack;
+        ConstPack cp = (ConstPack)pol.mlp;
+        asm("" : "+s"(cp));
+        const LLMlpPack& pack = *(const LLMlpPack*)cp;
+        float o[1][8];
+        uint32_t a[1];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) o[0][c] = state[c];
+        mlp_actions<8, 4, POLICY == ROLL_ACT_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, false, 1>(pack, o, a);
+        return a[0];
+    }
 }
 
 // where an environment goes after step t has been finished with flag word `flags` (t1 = t + 1):
@@ -325,7 +348,7 @@ __device__ __forceinline__ void roll_contact_batch(const LLDev& d, const LLIo& i
         }
         if (q.debug & 16u) { if (have && e.step == 0xfffffff0u) atomicOr(d.err, DEV_ERR_INTERNAL); rq_retire(q, have); return; }   // (diagnosis: ... and the load)
         if (have) {
-            action = roll_action<POLICY>(d, io, pol, i, t);   // (LINEAR: a step that comes back unfinished still finds its own action: the word moves on when it ends)
+            action = roll_action<POLICY>(d, io, pol, i, t);   // (observation-driven sources: a step that comes back unfinished still finds its own action: the word moves on when it ends)
             if (resume_toi) {   // world.step is past its island solve and its time-of-impact evaluations: on with SolveTOI
             } else if (w.resume) {   // the free-flight path has taken this step up to the end of the island solve (ll_free.h)
                 ll_resume_after_island(w);
@@ -396,7 +419,7 @@ __device__ __forceinline__ void roll_contact_batch(const LLDev& d, const LLIo& i
             if (!(q.debug & 64u)) roll_write_scalars(d, io, t, i, reward, done, trunc);
             if (route != ROLL_TO_RESET && !(q.debug & 64u)) roll_write_obs(d, io, t, i, state, t + 1u == q.K);   // (a finished env's observation comes from its reset)
             roll_write_action<POLICY>(d, pol, t, i, action);
-            if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route != ROLL_TO_RESET && t + 1u < q.K) RA_STORE(pol.next + i, ll_linear_action(pol.lin, state)); }   // step t + 1's, from this observation
+            if constexpr (roll_act_observes(POLICY)) { if (route != ROLL_TO_RESET && t + 1u < q.K) RA_STORE(pol.next + i, roll_decide<POLICY>(pol, state)); }   // step t + 1's, from this observation
             is_done = (done | trunc) != 0u;
             overflow |= w.overflow;
         }
@@ -484,7 +507,7 @@ __device__ __forceinline__ void roll_reset_batch(const LLDev& d, const LLIo& io,
             ll_free_store(d, i, f, e);
             roll_write_obs(d, io, t1 - 1u, i, state, t1 == q.K);
             route = t1 >= q.K ? ROLL_RETIRE : ROLL_TO_FREE;
-            if constexpr (POLICY == ROLL_ACT_LINEAR) { if (t1 < q.K) RA_STORE(pol.next + i, ll_linear_action(pol.lin, state)); }   // step t1's, from the reset observation
+            if constexpr (roll_act_observes(POLICY)) { if (t1 < q.K) RA_STORE(pol.next + i, roll_decide<POLICY>(pol, state)); }   // step t1's, from the reset observation
         } else {
             atomicOr(d.err, DEV_ERR_INTERNAL);   // (cannot happen: see above) — the environment is dropped from the launch, loudly
             route = ROLL_RETIRE;
@@ -630,7 +653,7 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                 RollRec r;
                 roll_pack_store(r, X.f, X.e, X.f.flags, X.seq_word);
                 roll_rec_store(rs, X.i, r);
-                if constexpr (POLICY == ROLL_ACT_LINEAR) RA_STORE(pol.next + X.i, X.act);   // decided in the registers (a fresh one's word is still in memory)
+                if constexpr (roll_act_observes(POLICY)) RA_STORE(pol.next + X.i, X.act);   // decided in the registers (a fresh one's word is still in memory)
             }
             Pz.route = ROLL_TO_FREE; Pz.ent = (X.t << 24) | X.i;
             X.have = false;
@@ -730,10 +753,10 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                     const uint32_t trunc = ll_truncated(d, X.e);
                     const int route = roll_route(d, q, flags, done | trunc, X.t + 1u);
                     roll_write_action<POLICY>(d, pol, X.t, X.i, X.act);
-                    uint32_t lin_next = 0u;   // LINEAR: step t + 1's action, from this step's observation (straight from the registers)
-                    if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route == ROLL_TO_FREE || route == ROLL_TO_CONTACT || route == ROLL_TO_LIGHT) lin_next = ll_linear_action(pol.lin, state); }
+                    uint32_t lin_next = 0u;   // observation-driven sources: step t + 1's action, from this step's observation (straight from the registers)
+                    if constexpr (roll_act_observes(POLICY)) { if (route == ROLL_TO_FREE || route == ROLL_TO_CONTACT || route == ROLL_TO_LIGHT) lin_next = roll_decide<POLICY>(pol, state); }
                     if (route == ROLL_TO_FREE) {   // stays on board: next step's action, ahead of this step's stores
-                        if constexpr (POLICY == ROLL_ACT_LINEAR) X.act = lin_next;
+                        if constexpr (roll_act_observes(POLICY)) X.act = lin_next;
                         else X.act = roll_action<POLICY>(d, io, pol, X.i, X.t + 1u);
                     }
                     roll_write_scalars(d, io, X.t, X.i, reward, done, trunc);
@@ -748,7 +771,7 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                         RollRec r;
                         roll_pack_store(r, X.f, X.e, flags, X.seq_word);
                         roll_rec_store(rs, X.i, r);
-                        if constexpr (POLICY == ROLL_ACT_LINEAR) { if (route == ROLL_TO_CONTACT || route == ROLL_TO_LIGHT) RA_STORE(pol.next + X.i, lin_next); }
+                        if constexpr (roll_act_observes(POLICY)) { if (route == ROLL_TO_CONTACT || route == ROLL_TO_LIGHT) RA_STORE(pol.next + X.i, lin_next); }
                         P[z].route = route; P[z].ent = (X.t << 24) | X.i;
                         X.have = false;
                     }
@@ -767,7 +790,7 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
                     for (int b = 0; b < 3; ++b)
                         __builtin_amdgcn_raw_buffer_store_b128(ll_u32x4{as_u32(X.f.b[b].sw.c0.x), as_u32(X.f.b[b].sw.c0.y), as_u32(X.f.b[b].sw.a0), as_u32(0.0f)}, rs, off + 16u * b, 0, 16);
                     __builtin_amdgcn_raw_buffer_store_b128(ll_u32x4{as_u32(0.0f), 0u, 0u, 0u}, rs, off + 48u, 0, 16);
-                    if constexpr (POLICY == ROLL_ACT_LINEAR) RA_STORE(pol.next + X.i, X.act);   // the contact path finishes step t with the same action
+                    if constexpr (roll_act_observes(POLICY)) RA_STORE(pol.next + X.i, X.act);   // the contact path finishes step t with the same action
                     P[z].route = ROLL_TO_LIGHT; P[z].ent = (X.t << 24) | X.i;   // same step index: the step is not finished
                     X.have = false;
                 }
@@ -826,8 +849,8 @@ __device__ __forceinline__ int roll_free_mode(const LLDev& d, const LLIo& io, co
 
 // ---- the launch ----
 // POLICY: the action source (ll_roll_types.h).  ROLL_ACT_TABLE (mgym_rollout) takes no fourth argument — its kernel is the same code as before the
-// policy forms existed; ROLL_ACT_LINEAR / ROLL_ACT_UNIFORM (mgym_rollout_linear / _uniform) take one RollPolicy by value (the weights travel in the
-// kernel arguments: wave-uniform, scalar loads).
+// policy forms existed; the others (mgym_rollout_linear / _uniform / _mlp) take one RollPolicy by value (the linear weights travel in the kernel
+// arguments: wave-uniform, scalar loads; the hidden-layer pack is too large for that and is reached through RollPolicy::mlp).
 LLD RollNoPolicy roll_policy_arg() { return RollNoPolicy{}; }
 LLD RollPolicy roll_policy_arg(const RollPolicy& p) { return p; }
 template <int BLK, int POLICY = ROLL_ACT_TABLE, class... Pol>
@@ -874,15 +897,15 @@ ll_rollout_kernel(LLDev d, LLIo io, RollQ q, Pol... pol_arg) {
                 route = ROLL_RETIRE;
             } else {
                 route = ll_free_eligible(flags) ? ROLL_TO_FREE : (flags & F_TOUCHING) ? ROLL_TO_CONTACT : ROLL_TO_LIGHT;
-                if constexpr (POLICY == ROLL_ACT_LINEAR) {   // step 0's action, from the handle's observation (mgym_observation)
+                if constexpr (roll_act_observes(POLICY)) {   // step 0's action, from the handle's observation (mgym_observation)
                     float o[8];
 #pragma unroll
                     for (int c = 0; c < 8; ++c) o[c] = d.obs[(uint64_t)c * d.n_pad + i];
-                    RA_STORE(pol.next + i, ll_linear_action(pol.lin, o));
+                    RA_STORE(pol.next + i, roll_decide<POLICY>(pol, o));
                 }
             }
         }
-        if constexpr (POLICY == ROLL_ACT_LINEAR) rq_drain();   // the next-action words are stored before the entries are published
+        if constexpr (roll_act_observes(POLICY)) rq_drain();   // the next-action words are stored before the entries are published
         roll_dispatch(d, q, route, (uint32_t)i, 0u);
     }
     st.v[RS_T_SEED] = (unsigned long long)(wall_clock64() - t_begin);

@@ -673,7 +673,8 @@ void ll_rollout_ring_init(hipStream_t s, const RollQ& q);
 void ll_rollout_begin(hipStream_t s, const RollQ& q, uint32_t n);
 void ll_rollout_launch(hipStream_t s, unsigned grid, const LLDev& d, const LLIo& io, const RollQ& q);
 void ll_rollout_helper_launch(hipStream_t s, unsigned grid, const LLDev& d, const LLIo& io, const RollQ& q);
-int ll_rollout_policy_blocks_per_cu(int* per_cu);
+int ll_rollout_policy_blocks_per_cu(int* per_cu, int* mlp_per_cu);
+void ll_rollout_mlp_pack_store(hipStream_t s, const LLMlpPack& pack, LLMlpPack* dst);
 void ll_rollout_policy_launch(hipStream_t s, unsigned grid, const LLDev& d, const LLIo& io, const RollQ& q, const RollPolicy& pol, int policy);
 
 // The K-step form of mgym_rollout_linear / mgym_rollout_uniform (below the persistent launch's minimum K, above its population limit, with
@@ -695,7 +696,7 @@ __global__ void __launch_bounds__(256) ll_policy_kernel(const float* __restrict_
     }
 }
 
-// mgym_rollout_mlp, K-step form only: the step's action column from the hidden-layer policy of mlp_policy.h, one environment per lane over the [8][n_pad]
+// mgym_rollout_mlp, K-step form: the step's action column from the hidden-layer policy of mlp_policy.h, one environment per lane over the [8][n_pad]
 // observation columns.  The weight pack is a kernel argument (3 348 bytes by value: scalar loads, and a captured graph carries it).
 template <int ACT>
 __global__ void __launch_bounds__(256) ll_policy_mlp_kernel(const float* __restrict__ obs, uint64_t n, uint64_t n_pad, MlpPack<8, 4> pack, uint32_t* __restrict__ out) {
@@ -872,7 +873,7 @@ __global__ void __launch_bounds__(kLLBlock) ll_import_kernel(LLDev d, const uint
 // Every environment knob of the wrapper.  ll_read_options() is the only place in this file that reads the environment (once per handle, when it is
 // made); mgym_get_info's knobs= line is this table's names.  A default of -1 means "by population": init() resolves it.
 struct LLOptions {
-    int general_only, gen_block, single_launch, staged, bucket, contact_blocks, vc_near, roll_enabled, roll_min_k, roll_helper, roll_stats, roll_trace;
+    int general_only, gen_block, single_launch, staged, bucket, contact_blocks, vc_near, roll_enabled, roll_min_k, roll_mlp, roll_helper, roll_stats, roll_trace;
     std::string roll_trace_file;
 };
 struct LLKnob { const char* name; int LLOptions::*value; int dflt; bool by_presence /* set at all = 1, whatever the value */; const char* meaning; };
@@ -886,6 +887,7 @@ static const LLKnob kLLKnobs[] = {
     {"MGYM_LL_VC_NEAR", &LLOptions::vc_near, kVcNearLds, false, "test knob: velocity constraints per lane kept in LDS, 0 .. kVcNearLds (the rest in the far workspace)"},
     {"MGYM_LL_ROLLOUT", &LLOptions::roll_enabled, -1, false, "mgym_rollout as one persistent launch: 0 never (K x step), 1 always; -1: by population"},
     {"MGYM_LL_ROLLOUT_MIN_K", &LLOptions::roll_min_k, -1, false, "shorter rollouts run as K x step; -1: by population"},
+    {"MGYM_LL_ROLLOUT_MLP", &LLOptions::roll_mlp, 0, false, "mgym_rollout_mlp: 1 = every activation through the persistent launch, also one that was not measured faster there (kRollMlpPersistent); 0: those run as K x step"},
     {"MGYM_LL_ROLL_HELPER", &LLOptions::roll_helper, 0, false, "free-flight helper waves beside the rollout's main launch: 0 never, 1 always, -1 by population"},
     {"MGYM_LL_ROLL_STATS", &LLOptions::roll_stats, 0, true, "diagnosis: after every rollout, where its waves spent their time (stderr; synchronises)"},
     {"MGYM_LL_ROLL_TRACE", &LLOptions::roll_trace, 0, true, "diagnosis: =file, what every wave of a rollout launch did when (written after each launch; synchronises)"},
@@ -908,6 +910,9 @@ constexpr uint32_t kRollToiSplit = 7u, kRollToiMin = 24u, kRollKeepMin = 24u;
 // K = 64 0.68 -> 0.62 ms per step, K = 16 0.77 -> 0.76, K = 8 unchanged; profiles/r04_lunarlander/rollout_tuning_with_helper_waves.txt)
 constexpr uint32_t kRollKeep = 3u, kRollFair = 0u, kRollHeavyNarrow = 12u;
 constexpr uint32_t kRollResetMin = 16u, kRollFreeMin = 32u, kRollResidency = 3u, kRollRefillMin = 8u, kRollHelperMin = 256u;
+// mgym_rollout_mlp: which hidden activations {ReLU, tanh} run inside the persistent launch by default — the ones measured faster there than as
+// K x (policy kernel, step()) by more than the spread, at H = 32 and H = 64, K = 16 and K = 64 (profiles/ll_mlp_rollout_time.json)
+constexpr bool kRollMlpPersistent[2] = {false, false};
 constexpr unsigned kRollMainPerCu = 3u, kRollHelperPerCu = 2u;   // with the helper waves: main waves / helper blocks per CU (see init())
 static_assert(kRollHeavyMax >= 1u && kRollHeavyMax <= 32u && kRollTailLanes >= 1u && kRollTailLanes <= 32u && kRollHeavyNarrow >= 1u && kRollHeavyNarrow <= kRollHeavyMax, "batches are at most 32 lanes wide");
 
@@ -946,6 +951,9 @@ struct LunarLanderEnv final : Env {
     RollQ rq{};
     unsigned roll_grid = 0;
     unsigned roll_policy_grid = 0;      // waves of the policy forms' persistent launch (no helper waves; at most roll_grid: the far workspace is sized for that)
+    unsigned roll_mlp_grid = 0;         // ... and of the hidden-layer forms', sized from their own instantiations
+    LLMlpPack* roll_mlp_pack = nullptr; // mgym_rollout_mlp's weights as the persistent launch reads them (stored on the stream ahead of each call's launches)
+    unsigned long long roll_launches = 0;   // persistent rollout launches issued so far (mgym_get_info: rollout_persistent_launches)
     void* roll_trace = nullptr;
     uint32_t* next_act = nullptr;       // [n_pad] mgym_rollout_linear: the next action of every environment (persistent launch) / the K-step form's action column
     uint32_t policy_calls = 0;          // mgym_rollout_uniform calls so far (Philox counter word of the policy stream)
@@ -961,6 +969,7 @@ struct LunarLanderEnv final : Env {
         if (roll_vc_far) (void)hipFree(roll_vc_far);
         if (roll_trace) (void)hipFree(roll_trace);
         if (next_act) (void)hipFree(next_act);
+        if (roll_mlp_pack) (void)hipFree(roll_mlp_pack);
         if (aux) (void)hipStreamDestroy(aux);
         if (env_class) (void)hipFree(env_class);
         if (aux2) { (void)hipStreamSynchronize(aux2); (void)hipStreamDestroy(aux2); }
@@ -1137,12 +1146,17 @@ struct LunarLanderEnv final : Env {
             if (g < 1) g = 1;
             roll_grid = (unsigned)g;
             {   // the policy forms: as many waves as are resident at once without helper waves, capped like the table form's
-                int pcu = 0;
-                if (ll_rollout_policy_blocks_per_cu(&pcu) != MGYM_OK) return MGYM_ERR_HIP;
-                uint64_t pg = (uint64_t)(pcu < 1 ? 1 : pcu) * (uint64_t)prop.multiProcessorCount;
-                if (pg > need) pg = need;
-                if (pg > roll_grid) pg = roll_grid;
-                roll_policy_grid = (unsigned)(pg < 1 ? 1 : pg);
+                int pcu = 0, mcu = 0;
+                if (ll_rollout_policy_blocks_per_cu(&pcu, &mcu) != MGYM_OK) return MGYM_ERR_HIP;
+                auto grid_of = [&](int per) {
+                    uint64_t pg = (uint64_t)(per < 1 ? 1 : per) * (uint64_t)prop.multiProcessorCount;
+                    if (pg > need) pg = need;
+                    if (pg > roll_grid) pg = roll_grid;
+                    return (unsigned)(pg < 1 ? 1 : pg);
+                };
+                roll_policy_grid = grid_of(pcu);
+                roll_mlp_grid = grid_of(mcu);
+                MGYM_HIP(hipMalloc((void**)&roll_mlp_pack, sizeof(LLMlpPack)));
             }
             MGYM_HIP(hipMalloc(&roll_vc_far, per_lane * (size_t)roll_grid * 32 * sizeof(VConstraint)));
             if (opt.roll_trace) {
@@ -1169,6 +1183,7 @@ struct LunarLanderEnv final : Env {
             ll_rollout_begin(stream, q, (uint32_t)n);
             st = launch(k0, rd, io, q);
             if (st != MGYM_OK) return st;
+            ++roll_launches;
         }
         // diagnosis output, then what the launches have changed behind the step's back
         if (roll_trace) { st = roll_write_trace(); if (st != MGYM_OK) return st; }
@@ -1222,16 +1237,22 @@ struct LunarLanderEnv final : Env {
                                       h[RS_N_HELPER_STEPS] ? (double)h[RS_N_HELPER_LANE_STEPS] / h[RS_N_HELPER_STEPS] : 0.0, (double)h[RS_N_FREE_STEPS]);
         return MGYM_OK;
     }
-    // mgym_rollout_linear / mgym_rollout_uniform: the persistent launch with the action source `policy` (ll_roll.h), or K x (ll_policy_kernel, step())
-    int policy_rollout(int policy, RollPolicy pol, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
+    // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp, the one place that chooses the form: the persistent launch with the action source
+    // `policy` (ll_roll.h) when the handle has one, K >= rollout_min_k, the stream is not being captured and — hidden-layer sources — the activation runs
+    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).  `pack`: the hidden-layer sources' weights (host), else null.
+    int policy_rollout(int policy, RollPolicy pol, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const LLMlpPack* pack = nullptr) {
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
         pol.next = next_act;
-        if (!opt.roll_enabled || K < opt.roll_min_k || capturing()) {
+        const bool mlp = policy == ROLL_ACT_MLP_RELU || policy == ROLL_ACT_MLP_TANH;
+        const bool persistent = opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
+        if (!persistent) {
             const unsigned g = (unsigned)((n + 255) / 256);
             for (int t = 0; t < K; ++t) {
                 uint32_t* a = ao ? ao + (size_t)t * n : next_act;
                 if (policy == ROLL_ACT_LINEAR) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_LINEAR>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
-                else hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_UNIFORM>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
+                else if (policy == ROLL_ACT_UNIFORM) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_UNIFORM>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
+                else if (policy == ROLL_ACT_MLP_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, *pack, a);   // (the pack as a kernel argument: a captured graph carries it)
+                else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, *pack, a);
                 MGYM_HIP(hipGetLastError());
                 int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
                               trunc ? trunc + (size_t)t * n : nullptr);
@@ -1239,11 +1260,16 @@ struct LunarLanderEnv final : Env {
             }
             return MGYM_OK;
         }
-        return roll_chunks(nullptr, K, obs_out, reward, done, trunc, [this, policy, pol, ao](int k0, const LLDev& rd, const LLIo& io, const RollQ& q) {
+        if (mlp) {   // the pack goes to the handle's buffer by a kernel on the stream: the caller's array is not read after the call, and the next call's weights wait for this call's launches
+            ll_rollout_mlp_pack_store(stream, *pack, roll_mlp_pack);
+            MGYM_HIP(hipGetLastError());
+            pol.mlp = roll_mlp_pack;
+        }
+        return roll_chunks(nullptr, K, obs_out, reward, done, trunc, [this, policy, pol, ao, mlp](int k0, const LLDev& rd, const LLIo& io, const RollQ& q) {
             RollPolicy p = pol;
             p.t0 = (uint32_t)k0;
             p.act_out = ao ? ao + (size_t)k0 * n : nullptr;
-            ll_rollout_policy_launch(stream, roll_policy_grid, rd, io, q, p, policy);   // (never with the free-flight helper waves)
+            ll_rollout_policy_launch(stream, mlp ? roll_mlp_grid : roll_policy_grid, rd, io, q, p, policy);   // (never with the free-flight helper waves)
             return (int)MGYM_OK;
         });
     }
@@ -1263,23 +1289,12 @@ struct LunarLanderEnv final : Env {
         }
         return policy_rollout(ROLL_ACT_LINEAR, pol, K, actions_out, obs_out, reward, done, trunc);
     }
-    // mgym_rollout_mlp: K x (ll_policy_mlp_kernel, step()) — the persistent launch has no hidden-layer action source
+    // mgym_rollout_mlp: the hidden-layer action sources of policy_rollout
     int rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        MlpPack<8, 4> pack;
+        LLMlpPack pack;
         mlp_pack<8, 4>(policy, hidden, pack);
-        const unsigned g = (unsigned)((n + 255) / 256);
-        for (int t = 0; t < K; ++t) {
-            uint32_t* a = ao ? ao + (size_t)t * n : next_act;
-            if (activation == MGYM_ACT_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
-            else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
-            MGYM_HIP(hipGetLastError());
-            int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
-                          trunc ? trunc + (size_t)t * n : nullptr);
-            if (st != MGYM_OK) return st;
-        }
-        return MGYM_OK;
+        return policy_rollout(activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, RollPolicy{}, K, actions_out, obs_out, reward, done, trunc, &pack);
     }
     // Are auto-resets staged right now?  (A dispersion override would be baked into prepared states.)  Also while the caller's stream is being
     // captured: the preparation branch goes into the graph (every event it needs is recorded inside the capture: see step_multi_stream()).
@@ -1499,7 +1514,8 @@ struct LunarLanderEnv final : Env {
                "\nstaged_resets=" + (opt.staged ? "1" : "0") + "\ncontact_list_by_kind=" + std::to_string(dev.bucket) + "\ncontact_blocks_target=" + std::to_string(opt.single_launch ? dev.contact_blocks : 0) +
                "\nknobs=";
         for (const LLKnob& k : kLLKnobs) out += std::string(&k == kLLKnobs ? "" : " ") + k.name;
-        out += std::string("\nrollout=") + (opt.roll_enabled ? "persistent_launch" : "k_steps") + "\nrollout_min_k=" + std::to_string(opt.roll_min_k) + "\nrollout_waves=" + std::to_string(roll_grid) + "\nrollout_helper_blocks=" + std::to_string(roll_helper_grid) + "\n";
+        out += std::string("\nrollout=") + (opt.roll_enabled ? "persistent_launch" : "k_steps") + "\nrollout_min_k=" + std::to_string(opt.roll_min_k) + "\nrollout_waves=" + std::to_string(roll_grid) + "\nrollout_helper_blocks=" + std::to_string(roll_helper_grid) +
+               "\nrollout_persistent_launches=" + std::to_string(roll_launches) + "\n";
         if (capturing()) { set_last_error("mgym_get_info: the stream is being captured (the call launches probe kernels and synchronises)"); return MGYM_ERR_BAD_ARG; }
         hipStream_t ss[3] = {stream, aux, aux2};
         const int ns = aux2 ? 3 : 2;

@@ -168,7 +168,8 @@ impl VecGym {
     /// K fused steps under an on-device one-hidden-layer policy (`mgym_rollout_mlp`): `policy` holds `W1[H][D]`, `b1[H]`, `W2[A][H]`, `b2[A]` in that order
     /// (the `weight` / `bias` tensors of two `Linear` layers, flattened), D = obs_dim, A = n_actions (1 for MountainCarContinuous, whose score is the force),
     /// 1 <= `hidden` <= 64, `activation` = `MGYM_ACT_RELU` or `MGYM_ACT_TANH`.  Both layers are ascending-index `fmaf` chains from the bias; the action is the
-    /// first largest score.  LunarLander runs it as K x (policy kernel, step).
+    /// first largest score.  LunarLander runs it as K x (policy kernel, step) by default, and inside its persistent rollout launch (under the conditions of
+    /// `rollout_linear`) with `MGYM_LL_ROLLOUT_MLP=1` in the environment: the same words either way.
     /// # Safety
     /// the output pointers are device pointers of `[K][n]` (`[K][obs_dim][n]` for `obs`) elements, or null.
     #[allow(clippy::too_many_arguments)]

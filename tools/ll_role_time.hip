@@ -8,7 +8,7 @@
 namespace mgym { int ll_rollout_blocks_per_cu(int* per_cu) { *per_cu = 1; return 0; } void ll_rollout_ring_init(hipStream_t, const RollQ&) {}
 void ll_rollout_begin(hipStream_t, const RollQ&, uint32_t) {} void ll_rollout_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&) {}
 void ll_rollout_helper_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&) {}
-int ll_rollout_policy_blocks_per_cu(int* per_cu) { *per_cu = 1; return 0; } void ll_rollout_policy_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&, const RollPolicy&, int) {} }
+int ll_rollout_policy_blocks_per_cu(int* per_cu, int* mlp_per_cu) { *per_cu = 1; *mlp_per_cu = 1; return 0; } void ll_rollout_mlp_pack_store(hipStream_t, const LLMlpPack&, LLMlpPack*) {} void ll_rollout_policy_launch(hipStream_t, unsigned, const LLDev&, const LLIo&, const RollQ&, const RollPolicy&, int) {} }
 
 #include <stdio.h>
 #include <vector>

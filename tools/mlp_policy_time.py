@@ -10,6 +10,15 @@ Per family — CartPole and MountainCar at 1 048 576 envs, LunarLander (wind) at
     (b) torch/H{32,64}/{relu,tanh} the loop it replaces: TorchVecEnv with AoS observations [n, D]; per step torch.addmm(b1, obs, W1^T), the activation,
                                    torch.addmm(b2, h, W2^T), argmax, TorchVecEnv.step — eager kernels, the [n, H] activation through memory
     (c) linear                     mgym_rollout_linear, for scale
+    (d) table, uniform             mgym_rollout (random actions from a device table) and mgym_rollout_uniform: the rows a change to the shared rollout
+                                   kernels must not move
+--K sets the steps per call (default 16), --families and --cases take comma-separated subsets (e.g. --families lunar_lander --K 64).  A run that is not
+the full default one must name its --out: the default file is the committed record of the full run.  One run is one K on one library; a record that
+compares libraries or Ks is put together from the runs' files:
+
+    python tools/mlp_policy_time.py --merge parent=a16.json after=b16.json parent=a64.json after=b64.json --out profiles/ll_mlp_rollout_time.json
+
+(rows "K<K>/<case>/<label>", the families' prefix dropped when every file holds one family).
 The weights are seeded normal draws scaled to the observation's range (the timing depends on them only through how often episodes end).  Timing: HIP
 events on the stream the work is issued on (the handle's own timer for (a) and (c), torch events on torch's current stream, which TorchVecEnv
 binds the handle to, for (b)), a warm-up, then a window of at least --window seconds.  Every repeat is a fresh process per family, the cases of a
@@ -25,10 +34,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAMILIES = [("cartpole", 1 << 20), ("mountain_car", 1 << 20), ("lunar_lander", 1 << 18)]
 IN_SCALE = {"cartpole": (2.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
-K = 16
 
 
-def worker(family, n, window, rotate):
+def worker(family, n, window, rotate, K, only):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -101,12 +109,17 @@ def worker(family, n, window, rotate):
             cases.append((f"torch/H{H}/{act}", lambda H=H, act=act: torch_loop(H, act)))
     lin = np.random.default_rng(3).normal(0, 1, (1 if family == "cartpole" else A) * (D + 1)).astype(np.float32)
     cases.append(("linear", lambda: fused(lambda env, r, d, t: env.rollout_linear_device(lin, K, None, None, r, d, t))))
+    tab = mg.DeviceArray.from_numpy(np.random.default_rng(5).integers(0, A, (K, n)).astype(np.uint32))
+    cases.append(("table", lambda: fused(lambda env, r, d, t: env.rollout_device(tab, K, None, r, d, t))))
+    cases.append(("uniform", lambda: fused(lambda env, r, d, t: env.rollout_uniform_device(9, K, None, None, r, d, t))))
+    if only:
+        cases = [c for c in cases if c[0].split("/")[0] in only]
     cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
     for name, run in cases:
         ms, count, info = run()
         out.append(dict(family=family, n_envs=n, K=K, case=name, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n),
-                        env_steps_per_s=count * K * n / (ms * 1e-3), rollout_form=info.get("rollout")))
+                        env_steps_per_s=count * K * n / (ms * 1e-3), rollout_form=info.get("rollout"), persistent_launches=info.get("rollout_persistent_launches")))
     print("RESULT " + json.dumps(out), flush=True)
 
 
@@ -119,22 +132,51 @@ def write_record(path, head, table):
         f.write(' "summary": {\n' + ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in table.items()) + "\n }\n}\n")
 
 
+def merge(pairs, out):
+    rows, heads = {}, []
+    for pair in pairs:
+        label, path = pair.split("=", 1)
+        rec = json.load(open(path))
+        heads.append(dict(label=label, K=rec["K"], repeats=rec["repeats"], window_s=rec["window_s"], n_envs=rec["n_envs"]))
+        one = len(rec["n_envs"]) == 1
+        for k, v in rec["summary"].items():
+            rows[f"K{rec['K']}/{k.split('/', 1)[1] if one else k}/{label}"] = v
+    write_record(out, dict(unit="ns per env-step", runs=heads), dict(sorted(rows.items())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.3, help="seconds of timed work per case")
     ap.add_argument("--scale", type=float, default=1.0, help="population scale (smoke runs)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlp_policy_time.json"))
+    ap.add_argument("--out", default=None, help="record file (default, full runs only: profiles/mlp_policy_time.json)")
+    ap.add_argument("--merge", nargs="+", metavar="LABEL=FILE", help="put the records of several runs into one file (--out) and exit")
+    ap.add_argument("--K", type=int, default=16, help="steps per rollout call")
+    ap.add_argument("--families", default=",".join(f for f, _ in FAMILIES), help="comma-separated subset of the families")
+    ap.add_argument("--cases", default="", help="comma-separated subset of mlp,torch,linear,table,uniform (default: all)")
     ap.add_argument("--worker", nargs=3, metavar=("FAMILY", "N", "ROTATE"))
     args = ap.parse_args()
+    K = args.K
+    only = [c for c in args.cases.split(",") if c]
+    if set(only) - {"mlp", "torch", "linear", "table", "uniform"}:
+        raise SystemExit(f"--cases: unknown case in {args.cases!r} (mlp, torch, linear, table, uniform)")
+    full = K == 16 and not only and args.families == ap.get_default("families") and args.scale == 1.0
+    if args.out is None and not args.worker:
+        if args.merge or not full:
+            raise SystemExit("--out is required for a merge and for a run with --K, --families, --cases or --scale: the default file is the full run's record")
+        args.out = os.path.join(ROOT, "profiles", "mlp_policy_time.json")
+    if args.merge:
+        return merge(args.merge, args.out)
     if args.worker:
-        return worker(args.worker[0], int(args.worker[1]), args.window, int(args.worker[2]))
+        return worker(args.worker[0], int(args.worker[1]), args.window, int(args.worker[2]), K, only)
+    families = [(f, n) for f, n in FAMILIES if f in args.families.split(",")]
     runs = []
     for rep in range(args.repeats):
-        for family, n in FAMILIES:
+        for family, n in families:
             n = max(1024, int(n * args.scale)) // 1024 * 1024
             # a fresh child per family and repeat; the parent never opens the GPU
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", family, str(n), str(3 * rep), "--window", str(args.window)],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", family, str(n), str(3 * rep), "--window", str(args.window), "--K", str(K),
+                                "--cases", args.cases],
                                capture_output=True, text=True, timeout=600)
             line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
             if r.returncode != 0 or not line:
@@ -148,7 +190,7 @@ def main():
     table = {k: dict(median=statistics.median(v), min=min(v), max=max(v), spread=(max(v) - min(v)) / statistics.median(v),
                      env_steps_per_s=1e9 / statistics.median(v), repeats=[round(x, 6) for x in v]) for k, v in sorted(summary.items())}
     head = dict(unit="ns per env-step", K=K, window_s=args.window, repeats=args.repeats, scale=args.scale,
-                n_envs={f: max(1024, int(n * args.scale)) // 1024 * 1024 for f, n in FAMILIES},
+                n_envs={f: max(1024, int(n * args.scale)) // 1024 * 1024 for f, n in families},
                 forms="mlp: the packed-VALU form (v_pk_fma_f32 chains, weights as scalar operands)")
     write_record(args.out, head, table)
     for k, v in table.items():
