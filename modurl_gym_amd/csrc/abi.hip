@@ -264,7 +264,7 @@ int mgym_rollout_uniform(mgym_env* env, uint64_t policy_seed, int32_t K, void* a
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_uniform: K < 0");
     if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_uniform: env_id_base must be a multiple of 4 (policy bits are keyed per 4 consecutive global env ids)");
-    return e->rollout_uniform(policy_seed, K, actions_out, obs_out, reward_out, done_out, trunc_out);
+    return e->rollout_policy(PolicyCall{ROLL_ACT_UNIFORM, "mgym_rollout_uniform", nullptr, 0, policy_seed}, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
 int mgym_rollout_linear(mgym_env* env, const float* policy, int32_t K, void* actions_out, float* obs_out, float* reward_out,
@@ -272,7 +272,7 @@ int mgym_rollout_linear(mgym_env* env, const float* policy, int32_t K, void* act
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_linear: K < 0");
     if (!policy) return bad_arg("mgym_rollout_linear: policy is NULL");
-    return e->rollout_linear(policy, K, actions_out, obs_out, reward_out, done_out, trunc_out);
+    return e->rollout_policy(PolicyCall{ROLL_ACT_LINEAR, "mgym_rollout_linear", policy, 0, 0}, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
 int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, int32_t K, void* actions_out, float* obs_out,
@@ -282,7 +282,8 @@ int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t
     if (!policy) return bad_arg("mgym_rollout_mlp: policy is NULL");
     if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp: hidden must be between 1 and 64");
     if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
-    return e->rollout_mlp(policy, hidden, activation, K, actions_out, obs_out, reward_out, done_out, trunc_out);
+    return e->rollout_policy(PolicyCall{activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, "mgym_rollout_mlp", policy, hidden, 0}, K, actions_out, obs_out, reward_out, done_out,
+                             trunc_out);
 }
 
 int mgym_episode_count(mgym_env* env, uint64_t* finished) {

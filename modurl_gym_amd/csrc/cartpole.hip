@@ -33,6 +33,7 @@
 #include "cartpole_step.h"
 #include "mlp_policy.h"
 #include "philox.h"
+#include "soa4.h"
 
 namespace mgym {
 
@@ -50,7 +51,7 @@ struct CartPoleDev {
     __host__ __device__ uint32_t* ctr() const { return reinterpret_cast<uint32_t*>(base + 4 * n_pad); }
 };
 
-constexpr bool kNtStores = true;   // non-temporal output stores: 10.9 us vs 11.4 us at 1 Mi envs (round 1)
+constexpr int kNtAux = 2;   // cache-policy bits of a buffer store, 2 = nt.  Every output leaves with non-temporal stores: 10.9 us vs 11.4 us at 1 Mi envs (round 1)
 constexpr int kWaves = kBlock / 64;
 
 struct CartPoleLane {
@@ -72,26 +73,8 @@ __device__ __forceinline__ void cartpole_draw(uint64_t seed, uint64_t gid, uint3
     cartpole_draw_half(seed, gid, episode, 1u, out + 2);
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <bool NT>
-__device__ __forceinline__ void st4(float* p, float a, float b, float c, float e) {
-    f32x4 v = {a, b, c, e};
-    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-    else *reinterpret_cast<f32x4*>(p) = v;
-}
-template <bool NT>
-__device__ __forceinline__ void st4u(uint32_t* p, uint32_t a, uint32_t b, uint32_t c, uint32_t e) {
-    u32x4 v = {a, b, c, e};
-    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
-    else *reinterpret_cast<u32x4*>(p) = v;
-}
-template <bool NT>
-__device__ __forceinline__ void st1u(uint32_t* p, uint32_t a) {
-    if (NT) __builtin_nontemporal_store(a, p);
-    else *p = a;
-}
+// non-temporal store of one word: a lane's four done / truncated bytes
+__device__ __forceinline__ void st1u(uint32_t* p, uint32_t a) { __builtin_nontemporal_store(a, p); }
 
 // Wave-private scratch of the done-mask compaction: one wave's finished envs (at most 64 * VEC)
 template <int VEC>
@@ -189,19 +172,9 @@ __device__ __forceinline__ void cartpole_flush_counts(const CartPoleDev& d, uint
     }
 }
 
-// 16-byte access at (uniform base pointer) + (32-bit per-lane byte offset): lowers to global_load/store with the
-// base in SGPRs and the lane offset in one VGPR (no 64-bit per-lane address arithmetic, which was ~90 VALU
-// instructions per wave pass when every column address was formed per lane)
-template <typename T> __device__ __forceinline__ const T* at(const void* base, uint32_t byte_off) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + byte_off);
-}
-template <typename T> __device__ __forceinline__ T* at(void* base, uint32_t byte_off) {
-    return reinterpret_cast<T*>(static_cast<char*>(base) + byte_off);
-}
-
 // VEC: envs per lane (4 = 16-byte accesses; 1 = fallback for misaligned caller buffers).
-// RESET: MGYM_FLAG_AUTO_RESET.  NT: non-temporal stores for the output columns.
-template <int VEC, bool EULER, bool SB, bool RESET, bool NT, int BLK>
+// RESET: MGYM_FLAG_AUTO_RESET.
+template <int VEC, bool EULER, bool SB, bool RESET, int BLK>
 __global__ void __launch_bounds__(BLK)
 cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out,
                      float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
@@ -231,7 +204,7 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
 #pragma unroll
         for (int k = 0; k < VEC; ++k) valid[k] = in;
         const uint32_t sb = (uint32_t)base * 4u;  // byte offset of this pass in a column (n <= 2^27: every offset < 2^32)
-        if (VEC == 4) {
+        if constexpr (VEC == 4) {
             // Engine columns: buffer loads — resource descriptor and column/pass offsets in SGPRs, one constant VGPR lane
             // offset, no per-lane address arithmetic.  The columns are padded to n_pad (a multiple of the block's 1024
             // envs), so every lane of the block may load (padding holds zeros and is never stored back).
@@ -244,10 +217,10 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
             const u32x4 vxd = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + colb, 0);
             const u32x4 vc = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + 4u * colb, 0);
             s[0] = {as_f32(vx.x), as_f32(vxd.x), as_f32(vth.x), as_f32(vthd.x), vc.x};
-            s[1 % VEC] = {as_f32(vx.y), as_f32(vxd.y), as_f32(vth.y), as_f32(vthd.y), vc.y};
-            s[2 % VEC] = {as_f32(vx.z), as_f32(vxd.z), as_f32(vth.z), as_f32(vthd.z), vc.z};
-            s[3 % VEC] = {as_f32(vx.w), as_f32(vxd.w), as_f32(vth.w), as_f32(vthd.w), vc.w};
-            a[0] = va.x; a[1 % VEC] = va.y; a[2 % VEC] = va.z; a[3 % VEC] = va.w;
+            s[1] = {as_f32(vx.y), as_f32(vxd.y), as_f32(vth.y), as_f32(vthd.y), vc.y};
+            s[2] = {as_f32(vx.z), as_f32(vxd.z), as_f32(vth.z), as_f32(vthd.z), vc.z};
+            s[3] = {as_f32(vx.w), as_f32(vxd.w), as_f32(vth.w), as_f32(vthd.w), vc.w};
+            a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w;
         } else {
             s[0] = {0.f, 0.f, 0.f, 0.f, 0u};
             a[0] = 0u;
@@ -261,12 +234,10 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
         // reward / done / truncated do not depend on the reset: issued here, their write-out drains while the reset
         // pass runs (the LDS fences of cartpole_wave_reset keep the compiler from sinking them past it)
         if (in) {
-            if (VEC == 4) {
-                if (rew) st4<NT>(at<float>(rew + base, off4), r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
-                if (done_out)
-                    st1u<NT>(at<uint32_t>(done_out + base, lane_env), dn[0] | (dn[1 % VEC] << 8) | (dn[2 % VEC] << 16) | (dn[3 % VEC] << 24));
-                if (trunc_out)
-                    st1u<NT>(at<uint32_t>(trunc_out + base, lane_env), tr[0] | (tr[1 % VEC] << 8) | (tr[2 % VEC] << 16) | (tr[3 % VEC] << 24));
+            if constexpr (VEC == 4) {
+                if (rew) nt_store4(at<float>(rew + base, off4), make_float4(r[0], r[1], r[2], r[3]));
+                if (done_out) st1u(at<uint32_t>(done_out + base, lane_env), pack_bytes4(dn));
+                if (trunc_out) st1u(at<uint32_t>(trunc_out + base, lane_env), pack_bytes4(tr));
             } else {
                 if (rew) *at<float>(rew + base, off4) = r[0];
                 if (done_out) *at<uint8_t>(done_out + base, lane_env) = (uint8_t)dn[0];
@@ -277,19 +248,18 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
         finished += cartpole_wave_reset<VEC, RESET>(d, s, valid, dn, tr, wave_first, lds);
 
         if (in) {
-            if (VEC == 4) {
-                constexpr int kAux = NT ? 2 : 0;  // cache-policy bits of the buffer store: 2 = nt
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].x), as_u32(s[1 % VEC].x), as_u32(s[2 % VEC].x), as_u32(s[3 % VEC].x)}, rs, off4, sb, kAux);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].xd), as_u32(s[1 % VEC].xd), as_u32(s[2 % VEC].xd), as_u32(s[3 % VEC].xd)}, rs, off4, sb + colb, kAux);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].th), as_u32(s[1 % VEC].th), as_u32(s[2 % VEC].th), as_u32(s[3 % VEC].th)}, rs, off4, sb + 2u * colb, kAux);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].thd), as_u32(s[1 % VEC].thd), as_u32(s[2 % VEC].thd), as_u32(s[3 % VEC].thd)}, rs, off4, sb + 3u * colb, kAux);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{s[0].ctr, s[1 % VEC].ctr, s[2 % VEC].ctr, s[3 % VEC].ctr}, rs, off4, sb + 4u * colb, kAux);
+            if constexpr (VEC == 4) {
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].x), as_u32(s[1].x), as_u32(s[2].x), as_u32(s[3].x)}, rs, off4, sb, kNtAux);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].xd), as_u32(s[1].xd), as_u32(s[2].xd), as_u32(s[3].xd)}, rs, off4, sb + colb, kNtAux);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].th), as_u32(s[1].th), as_u32(s[2].th), as_u32(s[3].th)}, rs, off4, sb + 2u * colb, kNtAux);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].thd), as_u32(s[1].thd), as_u32(s[2].thd), as_u32(s[3].thd)}, rs, off4, sb + 3u * colb, kNtAux);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{s[0].ctr, s[1].ctr, s[2].ctr, s[3].ctr}, rs, off4, sb + 4u * colb, kNtAux);
                 if (obs_out) {
                     float* const bo = obs_out + base;
-                    *at<float4>(bo, off4) = make_float4(s[0].x, s[1 % VEC].x, s[2 % VEC].x, s[3 % VEC].x);
-                    *at<float4>(bo + d.n, off4) = make_float4(s[0].xd, s[1 % VEC].xd, s[2 % VEC].xd, s[3 % VEC].xd);
-                    *at<float4>(bo + 2 * d.n, off4) = make_float4(s[0].th, s[1 % VEC].th, s[2 % VEC].th, s[3 % VEC].th);
-                    *at<float4>(bo + 3 * d.n, off4) = make_float4(s[0].thd, s[1 % VEC].thd, s[2 % VEC].thd, s[3 % VEC].thd);
+                    *at<float4>(bo, off4) = make_float4(s[0].x, s[1].x, s[2].x, s[3].x);
+                    *at<float4>(bo + d.n, off4) = make_float4(s[0].xd, s[1].xd, s[2].xd, s[3].xd);
+                    *at<float4>(bo + 2 * d.n, off4) = make_float4(s[0].th, s[1].th, s[2].th, s[3].th);
+                    *at<float4>(bo + 3 * d.n, off4) = make_float4(s[0].thd, s[1].thd, s[2].thd, s[3].thd);
                 }
             } else {
                 *at<float>(bx, off4) = s[0].x; *at<float>(bx + col, off4) = s[0].xd; *at<float>(bx + 2 * col, off4) = s[0].th;
@@ -305,16 +275,12 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
     cartpole_flush_counts<BLK / 64>(d, finished, bad);
 }
 
-// policy of a fused rollout: actions from the caller's [K][n] table, or drawn on the device
-enum { ROLL_TABLE = 0, ROLL_UNIFORM = 1, ROLL_LINEAR = 2, ROLL_MLP_RELU = 3, ROLL_MLP_TANH = 4 };
+// policy of a fused rollout: actions from the caller's [K][n] table, or drawn / decided on the device (the action sources of policy.h)
 struct LinearPolicy { float w[4], b; };   // action = ((w0 x + w1 x_dot) + w2 theta) + w3 theta_dot + b > 0 (mgym_rollout_linear)
 // mgym_rollout_mlp: the weight pack of mlp_policy.h takes the place of the five linear words in the kernel's arguments (1 804 bytes by value; the other
 // policies' instantiations keep the arguments they had)
 typedef MlpPack<4, 2> CpMlpPack;
-constexpr bool cp_roll_is_mlp(int policy) { return policy == ROLL_MLP_RELU || policy == ROLL_MLP_TANH; }
-template <int POLICY> struct CpPolicyArg { typedef LinearPolicy type; };
-template <> struct CpPolicyArg<ROLL_MLP_RELU> { typedef CpMlpPack type; };
-template <> struct CpPolicyArg<ROLL_MLP_TANH> { typedef CpMlpPack type; };
+template <int POLICY> using CpPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), CpMlpPack, LinearPolicy>;
 
 // Fused K-step rollout (mgym_rollout / mgym_rollout_uniform): one lane keeps its 4 environments in registers for
 // K steps; per step it reads one 16-B action word (or takes the next bit of its Philox policy stream) and writes
@@ -322,7 +288,7 @@ template <> struct CpPolicyArg<ROLL_MLP_TANH> { typedef CpMlpPack type; };
 // cartpole_step_kernel by construction: same per-wave function.
 template <bool EULER, bool SB, bool RESET, int POLICY>
 __global__ void __launch_bounds__(kBlock)
-cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_t* __restrict__ act_out, uint64_t policy_seed, uint32_t policy_call, typename CpPolicyArg<POLICY>::type lin,
+cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_t* __restrict__ act_out, uint64_t policy_seed, uint32_t policy_call, CpPolicyArg<POLICY> lin,
                         int K, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
     __shared__ WaveResetScratch<4> lds_[RESET ? kWaves : 1];
     constexpr uint64_t kPerBlock = (uint64_t)kBlock * 4;
@@ -334,7 +300,7 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
     const uint32_t lane_env = threadIdx.x * 4u, off4 = lane_env * 4u;
     const uint32_t colb = (uint32_t)d.n_pad * 4u, nb4 = (uint32_t)d.n * 4u;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(d.base, 0, 0xffffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(POLICY == ROLL_TABLE ? act : act_out), 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(POLICY == ROLL_ACT_TABLE ? act : act_out), 0, 0xffffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(rew, 0, 0xffffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(done_out, 0, 0xffffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(trunc_out, 0, 0xffffffff, 0x00020000);
@@ -353,19 +319,19 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
             s[2] = {as_f32(vx.z), as_f32(vxd.z), as_f32(vth.z), as_f32(vthd.z), vc.z}; s[3] = {as_f32(vx.w), as_f32(vxd.w), as_f32(vth.w), as_f32(vthd.w), vc.w};
         }
         const uint64_t wave_first = base + (uint64_t)(threadIdx.x & ~63) * 4;
-        Philox4 bits{};  // POLICY == ROLL_UNIFORM: 128 policy bits = 32 steps of this lane's 4 envs
+        Philox4 bits{};  // POLICY == ROLL_ACT_UNIFORM: 128 policy bits = 32 steps of this lane's 4 envs
         uint32_t so = sb;  // byte offset of (step t, this pass) in a [K][n] word buffer; byte buffers use so / 4
         for (int t = 0; t < K; ++t, so += nb4) {
             uint32_t a[4] = {0u, 0u, 0u, 0u}, dn[4], tr[4];
             float r[4];
-            if constexpr (POLICY == ROLL_TABLE) {
+            if constexpr (POLICY == ROLL_ACT_TABLE) {
                 if (in) { const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(ra, off4, so, 2); a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w; }
-            } else if constexpr (cp_roll_is_mlp(POLICY)) {
+            } else if constexpr (roll_act_is_mlp(POLICY)) {
                 // hidden-layer policy on the observations the lane's four envs hold before the step (mlp_policy.h: fmaf chains from the bias, ascending index)
                 const float o[4][4] = {{s[0].x, s[0].xd, s[0].th, s[0].thd}, {s[1].x, s[1].xd, s[1].th, s[1].thd}, {s[2].x, s[2].xd, s[2].th, s[2].thd}, {s[3].x, s[3].xd, s[3].th, s[3].thd}};
-                mlp_actions<4, 2, POLICY == ROLL_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, false, 4>(lin, o, a);
+                mlp_actions<4, 2, POLICY == ROLL_ACT_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, false, 4>(lin, o, a);
                 if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
-            } else if constexpr (POLICY == ROLL_LINEAR) {
+            } else if constexpr (POLICY == ROLL_ACT_LINEAR) {
                 // linear policy on the observation the env holds before the step, in the documented order (the file is compiled with -ffp-contract=off)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = ((((lin.w[0] * s[k].x + lin.w[1] * s[k].xd) + lin.w[2] * s[k].th) + lin.w[3] * s[k].thd) + lin.b > 0.0f) ? 1u : 0u;
@@ -384,22 +350,21 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
             finished += cartpole_wave_reset<4, RESET>(d, s, valid, dn, tr, wave_first, lds);
             if (in) {
                 if (rew) __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(r[0]), as_u32(r[1]), as_u32(r[2]), as_u32(r[3])}, rr, off4, so, 2);
-                if (done_out) __builtin_amdgcn_raw_buffer_store_b32(dn[0] | (dn[1] << 8) | (dn[2] << 16) | (dn[3] << 24), rd, lane_env, so >> 2, 2);
-                if (trunc_out) __builtin_amdgcn_raw_buffer_store_b32(tr[0] | (tr[1] << 8) | (tr[2] << 16) | (tr[3] << 24), rt, lane_env, so >> 2, 2);
+                if (done_out) __builtin_amdgcn_raw_buffer_store_b32(pack_bytes4(dn), rd, lane_env, so >> 2, 2);
+                if (trunc_out) __builtin_amdgcn_raw_buffer_store_b32(pack_bytes4(tr), rt, lane_env, so >> 2, 2);
                 if (obs_out) {
                     float* o = obs_out + (uint64_t)t * 4 * d.n + i0;
-                    st4<true>(o, s[0].x, s[1].x, s[2].x, s[3].x); st4<true>(o + d.n, s[0].xd, s[1].xd, s[2].xd, s[3].xd);
-                    st4<true>(o + 2 * d.n, s[0].th, s[1].th, s[2].th, s[3].th); st4<true>(o + 3 * d.n, s[0].thd, s[1].thd, s[2].thd, s[3].thd);
+                    nt_store4(o, make_float4(s[0].x, s[1].x, s[2].x, s[3].x)); nt_store4(o + d.n, make_float4(s[0].xd, s[1].xd, s[2].xd, s[3].xd));
+                    nt_store4(o + 2 * d.n, make_float4(s[0].th, s[1].th, s[2].th, s[3].th)); nt_store4(o + 3 * d.n, make_float4(s[0].thd, s[1].thd, s[2].thd, s[3].thd));
                 }
             }
         }
         if (in) {
-            constexpr int kAux = kNtStores ? 2 : 0;
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].x), as_u32(s[1].x), as_u32(s[2].x), as_u32(s[3].x)}, rs, off4, sb, kAux);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].xd), as_u32(s[1].xd), as_u32(s[2].xd), as_u32(s[3].xd)}, rs, off4, sb + colb, kAux);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].th), as_u32(s[1].th), as_u32(s[2].th), as_u32(s[3].th)}, rs, off4, sb + 2u * colb, kAux);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].thd), as_u32(s[1].thd), as_u32(s[2].thd), as_u32(s[3].thd)}, rs, off4, sb + 3u * colb, kAux);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{s[0].ctr, s[1].ctr, s[2].ctr, s[3].ctr}, rs, off4, sb + 4u * colb, kAux);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].x), as_u32(s[1].x), as_u32(s[2].x), as_u32(s[3].x)}, rs, off4, sb, kNtAux);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].xd), as_u32(s[1].xd), as_u32(s[2].xd), as_u32(s[3].xd)}, rs, off4, sb + colb, kNtAux);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].th), as_u32(s[1].th), as_u32(s[2].th), as_u32(s[3].th)}, rs, off4, sb + 2u * colb, kNtAux);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(s[0].thd), as_u32(s[1].thd), as_u32(s[2].thd), as_u32(s[3].thd)}, rs, off4, sb + 3u * colb, kNtAux);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{s[0].ctr, s[1].ctr, s[2].ctr, s[3].ctr}, rs, off4, sb + 4u * colb, kNtAux);
         }
     }
     cartpole_flush_counts<kWaves>(d, finished, bad);
@@ -489,7 +454,6 @@ struct CartPoleEnv final : Env {
     CartPoleDev dev{};
     bool auto_reset = false;
     int step_block = getenv("MGYM_CARTPOLE_BLOCK") ? atoi(getenv("MGYM_CARTPOLE_BLOCK")) : kBlock;  // threads per block of the step kernel (tuning knob)
-    uint32_t policy_calls = 0;  // mgym_rollout_uniform calls so far (Philox counter word of the policy stream)
 
     ~CartPoleEnv() override {
         if (base) (void)hipFree(base);
@@ -536,19 +500,15 @@ struct CartPoleEnv final : Env {
 
     template <int VEC, bool RESET, int BLK>
     void launch_step_blk(const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
-        const bool eu = cfg.is_euler, sb = cfg.sutton_barto_reward;
         uint64_t nb = (n + (uint64_t)BLK * VEC - 1) / ((uint64_t)BLK * VEC);
         const uint64_t cap = (uint64_t)kMaxBlocks * kBlock / BLK;   // same thread count as the kBlock-sized cap
         dim3 g((unsigned)(nb > cap ? cap : (nb ? nb : 1))), b(BLK);
-#define MGYM_CP_LAUNCH(E, S) hipLaunchKernelGGL((cartpole_step_kernel<VEC, E, S, RESET, kNtStores, BLK>), g, b, 0, stream, dev, act, obs_out, reward, done, trunc)
-        if (eu && !sb) MGYM_CP_LAUNCH(true, false);
-        else if (eu) MGYM_CP_LAUNCH(true, true);
-        else if (!sb) MGYM_CP_LAUNCH(false, false);
-        else MGYM_CP_LAUNCH(false, true);
-#undef MGYM_CP_LAUNCH
+        with_bools([&](auto E, auto S) {
+            hipLaunchKernelGGL((cartpole_step_kernel<VEC, decltype(E)::value, decltype(S)::value, RESET, BLK>), g, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+        }, cfg.is_euler, cfg.sutton_barto_reward);
     }
     template <int VEC, bool RESET>
-    void launch_step(dim3, const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
+    void launch_step(const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
         if (VEC == 4 && step_block == 64) launch_step_blk<VEC, RESET, 64>(act, obs_out, reward, done, trunc);
         else if (VEC == 4 && step_block == 128) launch_step_blk<VEC, RESET, 128>(act, obs_out, reward, done, trunc);
         else launch_step_blk<VEC, RESET, kBlock>(act, obs_out, reward, done, trunc);
@@ -557,84 +517,53 @@ struct CartPoleEnv final : Env {
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        bool vec_ok = n % 4 == 0 && aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && aligned(obs_out, 16);
-        dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n));
-        if (auto_reset) {
-            if (vec_ok) launch_step<4, true>(gv, act, obs_out, reward, done, trunc);
-            else launch_step<1, true>(gs, act, obs_out, reward, done, trunc);
-        } else {
-            if (vec_ok) launch_step<4, false>(gv, act, obs_out, reward, done, trunc);
-            else launch_step<1, false>(gs, act, obs_out, reward, done, trunc);
-        }
+        const bool vec_ok = fused_rollout_args_ok(nullptr, n, 0, false, act, obs_out, reward, done, trunc);   // else one environment per lane
+        with_bools([&](auto V, auto R) { launch_step<decltype(V)::value ? 4 : 1, decltype(R)::value>(act, obs_out, reward, done, trunc); }, vec_ok, auto_reset);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
 
     template <int POLICY>
-    void launch_rollout(dim3 g, const uint32_t* act, uint32_t* act_out, uint64_t pseed, uint32_t pcall, int K, float* obs_out, float* reward,
-                        uint8_t* done, uint8_t* trunc, const typename CpPolicyArg<POLICY>::type& lin = typename CpPolicyArg<POLICY>::type{}) {
-        const bool eu = cfg.is_euler, sb = cfg.sutton_barto_reward, rs = auto_reset;
-        dim3 b(kBlock);
-#define MGYM_CP_ROLL(E, S, R) hipLaunchKernelGGL((cartpole_rollout_kernel<E, S, R, POLICY>), g, b, 0, stream, dev, act, act_out, pseed, pcall, lin, K, obs_out, reward, done, trunc)
-        if (eu && !sb) { if (rs) MGYM_CP_ROLL(true, false, true); else MGYM_CP_ROLL(true, false, false); }
-        else if (eu) { if (rs) MGYM_CP_ROLL(true, true, true); else MGYM_CP_ROLL(true, true, false); }
-        else if (!sb) { if (rs) MGYM_CP_ROLL(false, false, true); else MGYM_CP_ROLL(false, false, false); }
-        else { if (rs) MGYM_CP_ROLL(false, true, true); else MGYM_CP_ROLL(false, true, false); }
-#undef MGYM_CP_ROLL
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, uint64_t pseed, uint32_t pcall, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
+                        const CpPolicyArg<POLICY>& lin = CpPolicyArg<POLICY>{}) {
+        const dim3 g(grid_for(n / 4)), b(kBlock);
+        with_bools([&](auto E, auto S, auto R) {
+            hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(S)::value, decltype(R)::value, POLICY>), g, b, 0, stream, dev, act, act_out, pseed, pcall, lin, K, obs_out,
+                               reward, done, trunc);
+        }, cfg.is_euler, cfg.sutton_barto_reward, auto_reset);
     }
 
     int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        bool vec_ok = n % 4 == 0 && aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && aligned(obs_out, 16) &&
-                      (uint64_t)K * n * 4 < (1ull << 32);  // the fused kernel addresses [K][n] word buffers with 32-bit byte offsets
-        if (!vec_ok) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
-        launch_rollout<ROLL_TABLE>(dim3(grid_for(n / 4)), act, nullptr, 0, 0, K, obs_out, reward, done, trunc);
+        if (!fused_rollout_args_ok(nullptr, n, K, true, act, obs_out, reward, done, trunc)) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
+        launch_rollout<ROLL_ACT_TABLE>(act, nullptr, 0, 0, K, obs_out, reward, done, trunc);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
 
-    int rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+    int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16) ||
-            (uint64_t)K * n * 4 >= (1ull << 32)) {
-            set_last_error("mgym_rollout_uniform: n_envs must be a multiple of 4, the buffers 16-byte aligned, and K * n_envs below 2^30");
-            return MGYM_ERR_BAD_ARG;
+        if (!fused_rollout_args_ok(call.api, n, K, true, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
+        switch (call.source) {
+        case ROLL_ACT_UNIFORM:
+            launch_rollout<ROLL_ACT_UNIFORM>(nullptr, ao, call.seed, uniform_calls++, K, obs_out, reward, done, trunc);
+            break;
+        case ROLL_ACT_LINEAR: {
+            LinearPolicy lin;
+            for (int q = 0; q < 4; ++q) lin.w[q] = call.weights[q];
+            lin.b = call.weights[4];
+            launch_rollout<ROLL_ACT_LINEAR>(nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, lin);
+            break;
         }
-        launch_rollout<ROLL_UNIFORM>(dim3(grid_for(n / 4)), nullptr, ao, policy_seed, policy_calls++, K, obs_out, reward, done, trunc);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int rollout_linear(const float* policy, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16) ||
-            (uint64_t)K * n * 4 >= (1ull << 32)) {
-            set_last_error("mgym_rollout_linear: n_envs must be a multiple of 4, the buffers 16-byte aligned, and K * n_envs below 2^30");
-            return MGYM_ERR_BAD_ARG;
+        default: {   // the hidden-layer sources
+            CpMlpPack pack;
+            mlp_pack<4, 2>(call.weights, call.hidden, pack);
+            with_bools([&](auto T) { launch_rollout<decltype(T)::value ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU>(nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack); },
+                       call.source == ROLL_ACT_MLP_TANH);
         }
-        LinearPolicy lin;
-        for (int q = 0; q < 4; ++q) lin.w[q] = policy[q];
-        lin.b = policy[4];
-        launch_rollout<ROLL_LINEAR>(dim3(grid_for(n / 4)), nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, lin);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16) ||
-            (uint64_t)K * n * 4 >= (1ull << 32)) {
-            set_last_error("mgym_rollout_mlp: n_envs must be a multiple of 4, the buffers 16-byte aligned, and K * n_envs below 2^30");
-            return MGYM_ERR_BAD_ARG;
         }
-        CpMlpPack pack;
-        mlp_pack<4, 2>(policy, hidden, pack);
-        if (activation == MGYM_ACT_TANH) launch_rollout<ROLL_MLP_TANH>(dim3(grid_for(n / 4)), nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack);
-        else launch_rollout<ROLL_MLP_RELU>(dim3(grid_for(n / 4)), nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }

@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include "../../include/mgym.h"
+#include "policy.h"
 
 namespace mgym {
 
@@ -27,6 +29,29 @@ inline int grid_for(uint64_t work_items) {
     if (b < 1) b = 1;
     if (b > (uint64_t)kMaxBlocks) b = kMaxBlocks;
     return (int)b;
+}
+
+// The one way from run-time bools to template arguments: with_bools(f, b0, b1, ..) calls the generic lambda f with one std::bool_constant
+// per bool, f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ..) — every combination is instantiated, the matching one runs.
+template <class F>
+void with_bools(F&& f) { f(); }
+template <class F, class... Rest>
+void with_bools(F&& f, bool b, Rest... rest) {
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// What the fused rollout kernels of the classic families (one lane owns 4 consecutive environments, 16-byte accesses) ask of a call.
+// `bound32`: the kernel addresses [K][n] word buffers with 32-bit byte offsets (CartPole).  `api`: the entry point named in the error
+// message, or null for a caller that falls back to K plain steps instead of failing (mgym_rollout).
+inline bool fused_rollout_args_ok(const char* api, uint64_t n, int K, bool bound32, const void* actions, const float* obs, const float* reward,
+                                  const uint8_t* done, const uint8_t* trunc) {
+    const bool ok = n % 4 == 0 && aligned(actions, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && aligned(obs, 16) &&
+                    (!bound32 || (uint64_t)K * n * 4 < (1ull << 32));
+    if (!ok && api)
+        set_last_error(std::string(api) + (bound32 ? ": n_envs must be a multiple of 4, the buffers 16-byte aligned, and K * n_envs below 2^30"
+                                                   : ": n_envs must be a multiple of 4 and the buffers 16-byte aligned"));
+    return ok;
 }
 
 // device-side sticky status bits (OR-ed into Env::d_err)
@@ -62,21 +87,9 @@ struct Env {
         }
         return MGYM_OK;
     }
-    // K fused steps under the on-device uniform random policy (SURVEY §8f-1 policy hook)
-    virtual int rollout_uniform(uint64_t, int, void*, float*, float*, uint8_t*, uint8_t*) {
-        set_last_error("mgym_rollout_uniform: not available for this environment family");
-        return MGYM_ERR_BAD_ARG;
-    }
-    // K fused steps under an on-device linear policy; policy = obs_dim weights + bias (host)
-    virtual int rollout_linear(const float*, int, void*, float*, float*, uint8_t*, uint8_t*) {
-        set_last_error("mgym_rollout_linear: not available for this environment family");
-        return MGYM_ERR_BAD_ARG;
-    }
-    // K fused steps under an on-device one-hidden-layer policy (mlp_policy.h); policy = W1[H][D], b1[H], W2[A][H], b2[A] (host), checked by the ABI
-    virtual int rollout_mlp(const float*, int, int, int, void*, float*, float*, uint8_t*, uint8_t*) {
-        set_last_error("mgym_rollout_mlp: not available for this environment family");
-        return MGYM_ERR_BAD_ARG;
-    }
+    // K fused steps under an on-device policy (mgym_rollout_uniform / _linear / _mlp): the action source, its weights or seed in `call`
+    virtual int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) = 0;
+    uint32_t uniform_calls = 0;  // mgym_rollout_uniform calls that launched so far (Philox counter word of the policy stream)
     virtual int observation(const float** obs, uint64_t* col_stride) = 0;
     virtual int get_state(void* blob) = 0;
     virtual int set_state(const void* blob) = 0;

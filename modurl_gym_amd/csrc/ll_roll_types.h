@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "ll_policy.h"
 #include "mlp_policy.h"
+#include "policy.h"
 
 namespace mgym {
 
@@ -77,9 +78,7 @@ constexpr long long kRollTimeoutTicks = 12000000000ll;
 //            that publishes the environment; a free-flight resident keeps it in a register (mgym_rollout_linear)
 //   UNIFORM  a pure function of (global id, call, t0 + t): ll_uniform_action (mgym_rollout_uniform)
 //   MLP_RELU / MLP_TANH  as LINEAR — the same word, written in the same places — decided by mlp_policy.h's one-hidden-layer policy (mgym_rollout_mlp)
-enum { ROLL_ACT_TABLE = 0, ROLL_ACT_LINEAR = 1, ROLL_ACT_UNIFORM = 2, ROLL_ACT_MLP_RELU = 3, ROLL_ACT_MLP_TANH = 4 };
-// the sources that decide from the observation: they own next[i]
-constexpr bool roll_act_observes(int policy) { return policy == ROLL_ACT_LINEAR || policy == ROLL_ACT_MLP_RELU || policy == ROLL_ACT_MLP_TANH; }
+// The sources themselves (ROLL_ACT_*) and roll_act_observes — the ones that decide from the observation: they own next[i] — are policy.h's.
 // The hidden-layer weights do not travel by value beside LLDev, LLIo and RollQ (3 348 bytes: the kernel-argument segment would pass 4 KiB) and not in
 // LDS (ContactLds<32> x 4 blocks fills a CU's 160 KiB): one pack per handle in device memory, stored by a kernel ahead of the launch and constant while
 // the launch runs — read through the constant address space, so that the wave-uniform p.unit[j] are scalar loads.

@@ -956,7 +956,6 @@ struct LunarLanderEnv final : Env {
     unsigned long long roll_launches = 0;   // persistent rollout launches issued so far (mgym_get_info: rollout_persistent_launches)
     void* roll_trace = nullptr;
     uint32_t* next_act = nullptr;       // [n_pad] mgym_rollout_linear: the next action of every environment (persistent launch) / the K-step form's action column
-    uint32_t policy_calls = 0;          // mgym_rollout_uniform calls so far (Philox counter word of the policy stream)
 
     ~LunarLanderEnv() override {
         if (base) (void)hipFree(base);
@@ -1237,13 +1236,28 @@ struct LunarLanderEnv final : Env {
                                       h[RS_N_HELPER_STEPS] ? (double)h[RS_N_HELPER_LANE_STEPS] / h[RS_N_HELPER_STEPS] : 0.0, (double)h[RS_N_FREE_STEPS]);
         return MGYM_OK;
     }
-    // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp, the one place that chooses the form: the persistent launch with the action source
-    // `policy` (ll_roll.h) when the handle has one, K >= rollout_min_k, the stream is not being captured and — hidden-layer sources — the activation runs
-    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).  `pack`: the hidden-layer sources' weights (host), else null.
-    int policy_rollout(int policy, RollPolicy pol, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const LLMlpPack* pack = nullptr) {
+    // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp, the one place that unpacks the call and chooses the form: the persistent launch with the
+    // action source `policy` (ll_roll.h) when the handle has one, K >= rollout_min_k, the stream is not being captured and — hidden-layer sources — the activation runs
+    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).
+    int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        if (n == 0 || K == 0) return MGYM_OK;
+        const int policy = call.source;
+        const bool mlp = roll_act_is_mlp(policy);
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
+        RollPolicy pol{};
+        LLMlpPack pack;   // (the hidden-layer sources only: their weights as the kernels read them)
+        if (policy == ROLL_ACT_UNIFORM) {
+            pol.seed = call.seed;
+            pol.call = uniform_calls++;
+        } else if (policy == ROLL_ACT_LINEAR) {
+            for (int j = 0; j < 4; ++j) {   // weights: 4 rows of (w_j0 .. w_j7, b_j)
+                for (int c = 0; c < 8; ++c) pol.lin.w[j][c] = call.weights[9 * j + c];
+                pol.lin.b[j] = call.weights[9 * j + 8];
+            }
+        } else {
+            mlp_pack<8, 4>(call.weights, call.hidden, pack);
+        }
         pol.next = next_act;
-        const bool mlp = policy == ROLL_ACT_MLP_RELU || policy == ROLL_ACT_MLP_TANH;
         const bool persistent = opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
         if (!persistent) {
             const unsigned g = (unsigned)((n + 255) / 256);
@@ -1251,8 +1265,8 @@ struct LunarLanderEnv final : Env {
                 uint32_t* a = ao ? ao + (size_t)t * n : next_act;
                 if (policy == ROLL_ACT_LINEAR) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_LINEAR>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
                 else if (policy == ROLL_ACT_UNIFORM) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_UNIFORM>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
-                else if (policy == ROLL_ACT_MLP_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, *pack, a);   // (the pack as a kernel argument: a captured graph carries it)
-                else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, *pack, a);
+                else if (policy == ROLL_ACT_MLP_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);   // (the pack as a kernel argument: a captured graph carries it)
+                else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
                 MGYM_HIP(hipGetLastError());
                 int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
                               trunc ? trunc + (size_t)t * n : nullptr);
@@ -1261,7 +1275,7 @@ struct LunarLanderEnv final : Env {
             return MGYM_OK;
         }
         if (mlp) {   // the pack goes to the handle's buffer by a kernel on the stream: the caller's array is not read after the call, and the next call's weights wait for this call's launches
-            ll_rollout_mlp_pack_store(stream, *pack, roll_mlp_pack);
+            ll_rollout_mlp_pack_store(stream, pack, roll_mlp_pack);
             MGYM_HIP(hipGetLastError());
             pol.mlp = roll_mlp_pack;
         }
@@ -1272,29 +1286,6 @@ struct LunarLanderEnv final : Env {
             ll_rollout_policy_launch(stream, mlp ? roll_mlp_grid : roll_policy_grid, rd, io, q, p, policy);   // (never with the free-flight helper waves)
             return (int)MGYM_OK;
         });
-    }
-    int rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        RollPolicy pol{};
-        pol.seed = policy_seed;
-        pol.call = policy_calls++;
-        return policy_rollout(ROLL_ACT_UNIFORM, pol, K, actions_out, obs_out, reward, done, trunc);
-    }
-    int rollout_linear(const float* policy, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        RollPolicy pol{};
-        for (int j = 0; j < 4; ++j) {   // policy: 4 rows of (w_j0 .. w_j7, b_j)
-            for (int c = 0; c < 8; ++c) pol.lin.w[j][c] = policy[9 * j + c];
-            pol.lin.b[j] = policy[9 * j + 8];
-        }
-        return policy_rollout(ROLL_ACT_LINEAR, pol, K, actions_out, obs_out, reward, done, trunc);
-    }
-    // mgym_rollout_mlp: the hidden-layer action sources of policy_rollout
-    int rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        LLMlpPack pack;
-        mlp_pack<8, 4>(policy, hidden, pack);
-        return policy_rollout(activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, RollPolicy{}, K, actions_out, obs_out, reward, done, trunc, &pack);
     }
     // Are auto-resets staged right now?  (A dispersion override would be baked into prepared states.)  Also while the caller's stream is being
     // captured: the preparation branch goes into the graph (every event it needs is recorded inside the capture: see step_multi_stream()).

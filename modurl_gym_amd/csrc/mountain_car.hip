@@ -15,12 +15,11 @@
 // 8-byte access, read and written by the time-limited instantiations only (TL = true: mgym_step 26 + 2 R + 2 W = 30 B per env-step; a rollout
 // keeps the count in registers, one read and one write per launch).  A handle without a limit launches the TL = false instantiations, which
 // are the kernels as they were: the count is then left alone (0 after a reset, not advanced).
-#include <type_traits>
-
 #include "common.h"
 #include "mgym_math.h"
 #include "mlp_policy.h"
 #include "philox.h"
+#include "soa4.h"
 #include "time_limit.h"
 
 namespace mgym {
@@ -42,14 +41,13 @@ struct MountainCarDev {
     uint32_t limit;      // max_episode_steps; 0: off
 };
 
-typedef uint16_t mc_u16x4 __attribute__((ext_vector_type(4)));
 // a lane's four counters: one 8-byte access (i0 a multiple of 4)
 __device__ __forceinline__ void mc_load_elapsed4(const MountainCarDev& d, uint64_t i0, uint32_t (&el)[4]) {
-    const mc_u16x4 v = *reinterpret_cast<const mc_u16x4*>(d.elapsed + i0);
+    const u16x4 v = *reinterpret_cast<const u16x4*>(d.elapsed + i0);
     el[0] = v.x; el[1] = v.y; el[2] = v.z; el[3] = v.w;
 }
 __device__ __forceinline__ void mc_store_elapsed4(const MountainCarDev& d, uint64_t i0, const uint32_t (&el)[4]) {
-    __builtin_nontemporal_store(mc_u16x4{(uint16_t)el[0], (uint16_t)el[1], (uint16_t)el[2], (uint16_t)el[3]}, reinterpret_cast<mc_u16x4*>(d.elapsed + i0));
+    __builtin_nontemporal_store(u16x4{(uint16_t)el[0], (uint16_t)el[1], (uint16_t)el[2], (uint16_t)el[3]}, reinterpret_cast<u16x4*>(d.elapsed + i0));
 }
 
 // done-mask reduction: per-lane counts of finished envs summed over the wave, one fire-and-forget atomic per wave
@@ -60,12 +58,6 @@ __device__ __forceinline__ void mountaincar_flush_counts(const MountainCarDev& d
     if (__any(bad)) {
         if ((threadIdx.x & 63) == 0) atomicOr(d.err, DEV_ERR_INVALID_ACTION);
     }
-}
-
-typedef float mc_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void nt_store4(float* p, float4 v) {
-    mc_f32x4 w = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(w, reinterpret_cast<mc_f32x4*>(p));
 }
 
 // f32::clamp: if self < min {min} else if self > max {max} else {self}
@@ -165,10 +157,11 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
                 nt_store4(obs_out + d.n + i0, ov);
             }
             if (rew) nt_store4(rew + i0, make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]));
-            if (done_out)
-                __builtin_nontemporal_store(dn[0] | (dn[1 % VEC] << 8) | (dn[2 % VEC] << 16) | (dn[3 % VEC] << 24),
-                                            reinterpret_cast<uint32_t*>(done_out + i0));
-            if (trunc_out) __builtin_nontemporal_store(tr[0] | (tr[1] << 8) | (tr[2] << 16) | (tr[3] << 24), reinterpret_cast<uint32_t*>(trunc_out + i0));  // :328 truncated: false, always (TL: the time limit)
+            if (done_out) {
+                const uint32_t dn4[4] = {dn[0], dn[1 % VEC], dn[2 % VEC], dn[3 % VEC]};
+                __builtin_nontemporal_store(pack_bytes4(dn4), reinterpret_cast<uint32_t*>(done_out + i0));
+            }
+            if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + i0));  // :328 truncated: false, always (TL: the time limit)
             if constexpr (TL) mc_store_elapsed4(d, i0, el);
         } else {
 #pragma unroll
@@ -194,7 +187,6 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
 // (a multiple of the block's 1024 envs), so every lane may load them — only in-range lanes store.  The done mask is
 // reduced with __ballot + popcount for mgym_episode_count; resets are rare here (episodes last >= 100 steps) and stay
 // in place.
-typedef uint32_t mc_u32x4v __attribute__((ext_vector_type(4)));
 template <bool CONT, bool RESET, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out,
@@ -210,10 +202,10 @@ mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, flo
         const uint32_t rem = left < kPerBlock ? (uint32_t)left : (uint32_t)kPerBlock;
         const bool in = lane_env < rem;
         const uint32_t sb = (uint32_t)base * 4u;
-        const mc_u32x4v vp = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb, 0);
-        const mc_u32x4v vv = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + colb, 0);
+        const u32x4 vp = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb, 0);
+        const u32x4 vv = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + colb, 0);
         uint4 va = CONT ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(1u, 1u, 1u, 1u);
-        if (in) va = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(act + base) + off4);
+        if (in) va = *at<uint4>(act + base, off4);
         float ps[4] = {as_f32(vp.x), as_f32(vp.y), as_f32(vp.z), as_f32(vp.w)}, vs[4] = {as_f32(vv.x), as_f32(vv.y), as_f32(vv.z), as_f32(vv.w)}, r[4];
         uint32_t a[4] = {va.x, va.y, va.z, va.w}, dn[4];
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u}, fin[4];   // (el / tr: time limit only)
@@ -235,17 +227,16 @@ mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, flo
             }
         }
         if (in) {
-            __builtin_amdgcn_raw_buffer_store_b128(mc_u32x4v{as_u32(ps[0]), as_u32(ps[1]), as_u32(ps[2]), as_u32(ps[3])}, rs, off4, sb, 2);
-            __builtin_amdgcn_raw_buffer_store_b128(mc_u32x4v{as_u32(vs[0]), as_u32(vs[1]), as_u32(vs[2]), as_u32(vs[3])}, rs, off4, sb + colb, 2);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(ps[0]), as_u32(ps[1]), as_u32(ps[2]), as_u32(ps[3])}, rs, off4, sb, 2);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{as_u32(vs[0]), as_u32(vs[1]), as_u32(vs[2]), as_u32(vs[3])}, rs, off4, sb + colb, 2);
             if (obs_out) {
-                float* o = reinterpret_cast<float*>(reinterpret_cast<char*>(obs_out + base) + off4);
+                float* o = at<float>(obs_out + base, off4);
                 nt_store4(o, make_float4(ps[0], ps[1], ps[2], ps[3]));
                 nt_store4(o + d.n, make_float4(vs[0], vs[1], vs[2], vs[3]));
             }
-            if (rew) nt_store4(reinterpret_cast<float*>(reinterpret_cast<char*>(rew + base) + off4), make_float4(r[0], r[1], r[2], r[3]));
-            if (done_out)
-                __builtin_nontemporal_store(dn[0] | (dn[1] << 8) | (dn[2] << 16) | (dn[3] << 24), reinterpret_cast<uint32_t*>(done_out + base + lane_env));
-            if (trunc_out) __builtin_nontemporal_store(tr[0] | (tr[1] << 8) | (tr[2] << 16) | (tr[3] << 24), reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));  // :328 truncated: false, always (TL: the time limit)
+            if (rew) nt_store4(at<float>(rew + base, off4), make_float4(r[0], r[1], r[2], r[3]));
+            if (done_out) __builtin_nontemporal_store(pack_bytes4(dn), reinterpret_cast<uint32_t*>(done_out + base + lane_env));
+            if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));  // :328 truncated: false, always (TL: the time limit)
             if constexpr (TL) mc_store_elapsed4(d, base + lane_env, el);
         }
     }
@@ -259,7 +250,6 @@ mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, flo
 // Fused K-step rollout (mgym_rollout): 4 environments per lane stay in registers for K steps; per step one 16-B
 // action word in, reward / done / truncated (and optionally the observation) out.  Same per-env function and the
 // same in-place auto-reset as mountaincar_step_kernel<4, CONT>, hence bit-identical to K separate steps.
-typedef uint32_t mc_u32x4 __attribute__((ext_vector_type(4)));
 // mgym_rollout_linear: the action comes from the observation the env holds before the step instead of a table.  Discrete(3): the index of the largest of
 // the three scores s_j = (w[j][0] * position + w[j][1] * velocity) + b[j] (the first of equal ones); Box(-1, 1): the one score itself as the force (the
 // step clamps it like any action).  f32, in that order, nothing fused.
@@ -268,20 +258,16 @@ struct McLinearPolicy { float w[3][2], b[3]; };
 // (g, number of earlier mgym_rollout_uniform calls on this handle, SLOT_POLICY + block).  Discrete(3): step t takes, for env g + k, half (t % 2) of word k
 // of block t / 2 (low half first), h, and the action (3 h) >> 16 — each action within 2^-16 of 1/3.  Box(-1, 1): word k of block t, top 24 bits u:
 // the force u 2^-23 - 1, uniform over the multiples of 2^-23 in [-1, 1).
-enum { MC_ROLL_TABLE = 0, MC_ROLL_LINEAR = 1, MC_ROLL_UNIFORM = 2, MC_ROLL_MLP_RELU = 3, MC_ROLL_MLP_TANH = 4 };
 struct McUniformPolicy { uint64_t seed; uint32_t call; };
 // mgym_rollout_mlp: the weight pack of mlp_policy.h (A = 3 scores, or the one force of MountainCarContinuous) takes the place of the linear words in the
 // kernel's arguments; the other policies' instantiations keep the arguments they had
-constexpr bool mc_roll_is_mlp(int policy) { return policy == MC_ROLL_MLP_RELU || policy == MC_ROLL_MLP_TANH; }
-template <bool CONT, int POLICY> struct McPolicyArg { typedef McLinearPolicy type; };
-template <bool CONT> struct McPolicyArg<CONT, MC_ROLL_MLP_RELU> { typedef MlpPack<2, CONT ? 1 : 3> type; };
-template <bool CONT> struct McPolicyArg<CONT, MC_ROLL_MLP_TANH> { typedef MlpPack<2, CONT ? 1 : 3> type; };
-template <bool CONT, int POLICY = MC_ROLL_TABLE, bool TL = false>
+template <bool CONT, int POLICY> using McPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<2, CONT ? 1 : 3>, McLinearPolicy>;
+template <bool CONT, int POLICY = ROLL_ACT_TABLE, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
-                           uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, typename McPolicyArg<CONT, POLICY>::type lin = {}, uint32_t* __restrict__ act_out = nullptr,
+                           uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, McPolicyArg<CONT, POLICY> lin = {}, uint32_t* __restrict__ act_out = nullptr,
                            McUniformPolicy uni = McUniformPolicy{}) {
-    constexpr bool LINEAR = POLICY == MC_ROLL_LINEAR;
+    constexpr bool LINEAR = POLICY == ROLL_ACT_LINEAR;
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool bad = false;
@@ -296,7 +282,7 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
         for (int t = 0; t < K; ++t) {
             const uint64_t off = (uint64_t)t * d.n + i0;
             uint32_t a[4], dn[4];
-            if constexpr (POLICY == MC_ROLL_UNIFORM) {
+            if constexpr (POLICY == ROLL_ACT_UNIFORM) {
                 const uint64_t gid = d.env_id_base + i0;
                 if (CONT || (t & 1) == 0)
                     bits = philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), uni.call, SLOT_POLICY + (uint32_t)(CONT ? t : t >> 1), (uint32_t)uni.seed, (uint32_t)(uni.seed >> 32));
@@ -305,12 +291,12 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                     if constexpr (CONT) a[k] = __float_as_uint((float)(bits.w[k] >> 8) * 1.1920928955078125e-07f - 1.0f);
                     else a[k] = ((((t & 1) ? bits.w[k] >> 16 : bits.w[k] & 0xffffu)) * 3u) >> 16;
                 }
-                if (act_out) __builtin_nontemporal_store(mc_u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<mc_u32x4*>(act_out + off));
-            } else if constexpr (mc_roll_is_mlp(POLICY)) {
+                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
+            } else if constexpr (roll_act_is_mlp(POLICY)) {
                 // hidden-layer policy on (position, velocity) of the lane's four envs before the step (mlp_policy.h)
                 const float o[4][2] = {{ps[0], vs[0]}, {ps[1], vs[1]}, {ps[2], vs[2]}, {ps[3], vs[3]}};
-                mlp_actions<2, CONT ? 1 : 3, POLICY == MC_ROLL_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, CONT, 4>(lin, o, a);
-                if (act_out) __builtin_nontemporal_store(mc_u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<mc_u32x4*>(act_out + off));
+                mlp_actions<2, CONT ? 1 : 3, POLICY == ROLL_ACT_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, CONT, 4>(lin, o, a);
+                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
             } else if constexpr (LINEAR) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -323,9 +309,9 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                         a[k] = s2 > sb ? 2u : best;
                     }
                 }
-                if (act_out) __builtin_nontemporal_store(mc_u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<mc_u32x4*>(act_out + off));
+                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
             } else {
-                mc_u32x4 va = __builtin_nontemporal_load(reinterpret_cast<const mc_u32x4*>(act + off));
+                u32x4 va = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(act + off));
                 a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w;
             }
             float r[4];
@@ -339,8 +325,8 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                 if (d.auto_reset && fin) { mountaincar_reset_one(d, i0 + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
             }
             if (rew) nt_store4(rew + off, make_float4(r[0], r[1], r[2], r[3]));
-            if (done_out) __builtin_nontemporal_store(dn[0] | (dn[1] << 8) | (dn[2] << 16) | (dn[3] << 24), reinterpret_cast<uint32_t*>(done_out + off));
-            if (trunc_out) __builtin_nontemporal_store(tr[0] | (tr[1] << 8) | (tr[2] << 16) | (tr[3] << 24), reinterpret_cast<uint32_t*>(trunc_out + off));
+            if (done_out) __builtin_nontemporal_store(pack_bytes4(dn), reinterpret_cast<uint32_t*>(done_out + off));
+            if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + off));
             if (obs_out) {
                 float* o = obs_out + (uint64_t)t * 2 * d.n + i0;
                 nt_store4(o, make_float4(ps[0], ps[1], ps[2], ps[3]));
@@ -417,13 +403,6 @@ __global__ void mountaincar_set_elapsed_kernel(MountainCarDev d, const uint32_t*
     if (i < d.n) d.elapsed[i] = (uint16_t)tl_clamp(in[i]);
 }
 
-// host-side choice of an instantiation: f(std::bool_constant<continuous>, std::bool_constant<time limit>)
-template <class F>
-static void mc_dispatch(bool continuous, bool tl, F&& f) {
-    if (continuous) { if (tl) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
-    else { if (tl) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
-}
-
 struct MountainCarEnv final : Env {
     bool continuous;
     void* base = nullptr;
@@ -485,86 +464,61 @@ struct MountainCarEnv final : Env {
         dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
         const bool tl = dev.limit != 0u;
         if (vec_ok && n % 4 == 0 && n <= (1ull << 27) && use_step4) {  // the structured 16-byte kernel
-            const bool rs = dev.auto_reset;
-            mc_dispatch(continuous, tl, [&](auto C, auto T) {
-                if (rs) hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, true, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-                else hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, false, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-            });
+            with_bools([&](auto C, auto T, auto R) {
+                hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, decltype(R)::value, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+            }, continuous, tl, dev.auto_reset != 0);
             MGYM_HIP(hipGetLastError());
             return MGYM_OK;
         }
-        mc_dispatch(continuous, tl, [&](auto C, auto T) {
-            if (vec_ok) hipLaunchKernelGGL((mountaincar_step_kernel<4, decltype(C)::value, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-            else hipLaunchKernelGGL((mountaincar_step_kernel<1, decltype(C)::value, decltype(T)::value>), gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        });
+        with_bools([&](auto C, auto T, auto V) {
+            hipLaunchKernelGGL((mountaincar_step_kernel<decltype(V)::value ? 4 : 1, decltype(C)::value, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+        }, continuous, tl, vec_ok);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
+    }
+
+    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear weights or the hidden-layer pack, `uni`: the uniform stream
+    template <int POLICY, bool CONT, bool TL>
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
+                        const McPolicyArg<CONT, POLICY>& arg = McPolicyArg<CONT, POLICY>{}, McUniformPolicy uni = McUniformPolicy{}) {
+        hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
     int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        bool vec_ok = n % 4 == 0 && aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && aligned(obs_out, 16);
-        if (!vec_ok) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
-        dim3 gv(grid_for(n / 4)), b(kBlock);
-        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
-            hipLaunchKernelGGL((mountaincar_rollout_kernel<decltype(C)::value, MC_ROLL_TABLE, decltype(T)::value>), gv, b, 0, stream, dev, act, K, obs_out, reward, done, trunc, McLinearPolicy{}, (uint32_t*)nullptr, McUniformPolicy{});
-        });
+        if (!fused_rollout_args_ok(nullptr, n, K, false, act, obs_out, reward, done, trunc)) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
+        with_bools([&](auto C, auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(C)::value, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); },
+                   continuous, dev.limit != 0u);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
 
-    uint32_t policy_calls = 0;  // mgym_rollout_uniform calls so far (Philox counter word of the policy stream)
-    int rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+    int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16)) {
-            set_last_error("mgym_rollout_uniform: n_envs must be a multiple of 4 and the buffers 16-byte aligned");
-            return MGYM_ERR_BAD_ARG;
-        }
-        const McUniformPolicy uni{policy_seed, policy_calls++};
-        dim3 gv(grid_for(n / 4)), b(kBlock);
-        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
-            hipLaunchKernelGGL((mountaincar_rollout_kernel<decltype(C)::value, MC_ROLL_UNIFORM, decltype(T)::value>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni);
-        });
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int rollout_linear(const float* policy, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16)) {
-            set_last_error("mgym_rollout_linear: n_envs must be a multiple of 4 and the buffers 16-byte aligned");
-            return MGYM_ERR_BAD_ARG;
-        }
-        McLinearPolicy lin{};
-        const int rows = continuous ? 1 : 3;   // policy: `rows` rows of (w_position, w_velocity, bias)
-        for (int j = 0; j < rows; ++j) { lin.w[j][0] = policy[3 * j + 0]; lin.w[j][1] = policy[3 * j + 1]; lin.b[j] = policy[3 * j + 2]; }
-        dim3 gv(grid_for(n / 4)), b(kBlock);
-        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
-            hipLaunchKernelGGL((mountaincar_rollout_kernel<decltype(C)::value, MC_ROLL_LINEAR, decltype(T)::value>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, lin, ao, McUniformPolicy{});
-        });
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (n % 4 != 0 || !aligned(ao, 16) || !aligned(reward, 16) || !aligned(done, 4) || !aligned(trunc, 4) || !aligned(obs_out, 16)) {
-            set_last_error("mgym_rollout_mlp: n_envs must be a multiple of 4 and the buffers 16-byte aligned");
-            return MGYM_ERR_BAD_ARG;
-        }
-        dim3 gv(grid_for(n / 4)), b(kBlock);
-        const bool tanh_act = activation == MGYM_ACT_TANH;
-        mc_dispatch(continuous, dev.limit != 0u, [&](auto C, auto T) {
+        if (!fused_rollout_args_ok(call.api, n, K, false, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
+        with_bools([&](auto C, auto T) {
             constexpr bool CONT = decltype(C)::value, TL = decltype(T)::value;
-            MlpPack<2, CONT ? 1 : 3> pack;
-            mlp_pack<2, CONT ? 1 : 3>(policy, hidden, pack);
-            if (tanh_act) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, MC_ROLL_MLP_TANH, TL>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, pack, ao, McUniformPolicy{});
-            else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, MC_ROLL_MLP_RELU, TL>), gv, b, 0, stream, dev, (const uint32_t*)nullptr, K, obs_out, reward, done, trunc, pack, ao, McUniformPolicy{});
-        });
+            switch (call.source) {
+            case ROLL_ACT_UNIFORM:
+                launch_rollout<ROLL_ACT_UNIFORM, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, McLinearPolicy{}, McUniformPolicy{call.seed, uniform_calls++});
+                break;
+            case ROLL_ACT_LINEAR: {
+                McLinearPolicy lin{};
+                constexpr int rows = CONT ? 1 : 3;   // weights: `rows` rows of (w_position, w_velocity, bias)
+                for (int j = 0; j < rows; ++j) { lin.w[j][0] = call.weights[3 * j + 0]; lin.w[j][1] = call.weights[3 * j + 1]; lin.b[j] = call.weights[3 * j + 2]; }
+                launch_rollout<ROLL_ACT_LINEAR, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, lin);
+                break;
+            }
+            default: {   // the hidden-layer sources
+                MlpPack<2, CONT ? 1 : 3> pack;
+                mlp_pack<2, CONT ? 1 : 3>(call.weights, call.hidden, pack);
+                with_bools([&](auto H) { launch_rollout<decltype(H)::value ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack); },
+                           call.source == ROLL_ACT_MLP_TANH);
+            }
+            }
+        }, continuous, dev.limit != 0u);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }

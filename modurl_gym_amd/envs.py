@@ -207,17 +207,22 @@ class VecEnv:
         _check(self._lib.mgym_rollout_linear(self._h, pol, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out),
                                              _ptr(trunc_out)))
 
+    def _rollout_host(self, K, call, action_dtype=np.uint32):
+        """The host-array form of every K-step call: allocate the [K, ..] outputs, run call(actions, obs, reward, done, trunc) on them, sync
+        -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc) as host arrays; without the actions if action_dtype is None."""
+        n = max(self.n, 1)
+        shapes = [(K, self.n), (K, self.obs_dim, self.n), (K, self.n), (K, self.n), (K, self.n)]
+        dtypes = [action_dtype, np.float32, np.float32, np.uint8, np.uint8]
+        if action_dtype is None:
+            shapes, dtypes = shapes[1:], dtypes[1:]
+        outs = [DeviceArray(sh[:-1] + (n,), dt, self.device) for sh, dt in zip(shapes, dtypes)]
+        call(*outs)
+        self.sync()
+        return tuple(x.numpy().reshape(-1)[: int(np.prod(sh))].reshape(sh) for x, sh in zip(outs, shapes))
+
     def rollout_linear(self, policy, K):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""
-        n = max(self.n, 1)
-        da = DeviceArray((K, n), np.uint32, self.device)
-        do = DeviceArray((K, self.obs_dim, n), np.float32, self.device)
-        dr = DeviceArray((K, n), np.float32, self.device)
-        dd, dt = DeviceArray((K, n), np.uint8, self.device), DeviceArray((K, n), np.uint8, self.device)
-        self.rollout_linear_device(policy, K, da, do, dr, dd, dt)
-        self.sync()
-        sh = lambda x, shape: x.numpy().reshape(-1)[: int(np.prod(shape))].reshape(shape)
-        return (sh(da, (K, self.n)), sh(do, (K, self.obs_dim, self.n)), sh(dr, (K, self.n)), sh(dd, (K, self.n)), sh(dt, (K, self.n)))
+        return self._rollout_host(K, lambda *out: self.rollout_linear_device(policy, K, *out))
 
     def mlp_dims(self):
         """(D, A) of mgym_rollout_mlp for this family: obs_dim inputs; one score per action, or the one force of MountainCarContinuous"""
@@ -253,27 +258,11 @@ class VecEnv:
     def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc); actions float32 for MountainCarContinuous"""
         policy, H = self.pack_mlp(w1, b1, w2, b2)
-        n = max(self.n, 1)
-        da = DeviceArray((K, n), self.action_dtype, self.device)
-        do = DeviceArray((K, self.obs_dim, n), np.float32, self.device)
-        dr = DeviceArray((K, n), np.float32, self.device)
-        dd, dt = DeviceArray((K, n), np.uint8, self.device), DeviceArray((K, n), np.uint8, self.device)
-        self.rollout_mlp_device(policy, H, activation, K, da, do, dr, dd, dt)
-        self.sync()
-        sh = lambda x, shape: x.numpy().reshape(-1)[: int(np.prod(shape))].reshape(shape)
-        return (sh(da, (K, self.n)), sh(do, (K, self.obs_dim, self.n)), sh(dr, (K, self.n)), sh(dd, (K, self.n)), sh(dt, (K, self.n)))
+        return self._rollout_host(K, lambda *out: self.rollout_mlp_device(policy, H, activation, K, *out), self.action_dtype)
 
     def rollout_uniform(self, policy_seed, K):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""
-        n = max(self.n, 1)
-        da = DeviceArray((K, n), np.uint32, self.device)
-        do = DeviceArray((K, self.obs_dim, n), np.float32, self.device)
-        dr = DeviceArray((K, n), np.float32, self.device)
-        dd, dt = DeviceArray((K, n), np.uint8, self.device), DeviceArray((K, n), np.uint8, self.device)
-        self.rollout_uniform_device(policy_seed, K, da, do, dr, dd, dt)
-        self.sync()
-        sh = lambda x, shape: x.numpy().reshape(-1)[: int(np.prod(shape))].reshape(shape)
-        return (sh(da, (K, self.n)), sh(do, (K, self.obs_dim, self.n)), sh(dr, (K, self.n)), sh(dd, (K, self.n)), sh(dt, (K, self.n)))
+        return self._rollout_host(K, lambda *out: self.rollout_uniform_device(policy_seed, K, *out))
 
     def episode_count(self):
         """env-steps of this handle that returned done or truncated since creation (mgym_episode_count; synchronises)"""
@@ -295,15 +284,8 @@ class VecEnv:
         a = self._coerce_actions(actions)
         K = a.shape[0]
         assert a.shape == (K, self.n)
-        n = max(self.n, 1)
         da = DeviceArray.from_numpy(a, self.device) if a.size else DeviceArray(1, self.action_dtype, self.device)
-        do = DeviceArray((K, self.obs_dim, n), np.float32, self.device)
-        dr = DeviceArray((K, n), np.float32, self.device)
-        dd, dt = DeviceArray((K, n), np.uint8, self.device), DeviceArray((K, n), np.uint8, self.device)
-        self.rollout_device(da, K, do, dr, dd, dt)
-        self.sync()
-        sh = lambda x, shape: x.numpy().reshape(-1)[: int(np.prod(shape))].reshape(shape)
-        return (sh(do, (K, self.obs_dim, self.n)), sh(dr, (K, self.n)), sh(dd, (K, self.n)), sh(dt, (K, self.n)))
+        return self._rollout_host(K, lambda *out: self.rollout_device(da, K, *out), None)
 
     def observation_device(self):
         p, stride = C.c_void_p(), C.c_uint64()

@@ -11,9 +11,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modurl_gym_amd", "csrc")
-SRC = {"cartpole": ["cartpole.hip", "cartpole_step.h", "cartpole_math.h", "mgym_math.h", "mlp_policy.h", "philox.h", "common.h"],
-       "mountain_car": ["mountain_car.hip", "mgym_math.h", "mlp_policy.h", "time_limit.h", "philox.h", "common.h"],
-       "lunar_lander": ["lunar_lander.hip", "ll_roll.h", "ll_env.h", "ll_free.h", "ll_world.h", "ll_b2.h", "mgym_math.h", "mlp_policy.h", "time_limit.h", "philox.h", "common.h"]}
+SRC = {"cartpole": ["cartpole.hip", "cartpole_step.h", "cartpole_math.h", "mgym_math.h", "mlp_policy.h", "philox.h", "common.h", "policy.h", "soa4.h"],
+       "mountain_car": ["mountain_car.hip", "mgym_math.h", "mlp_policy.h", "time_limit.h", "philox.h", "common.h", "policy.h", "soa4.h"],
+       "lunar_lander": ["lunar_lander.hip", "ll_roll.h", "ll_env.h", "ll_free.h", "ll_world.h", "ll_b2.h", "mgym_math.h", "mlp_policy.h", "time_limit.h", "philox.h", "common.h", "policy.h"]}
 
 
 def sha16(files):
