@@ -237,6 +237,46 @@ enum { MGYM_ACT_RELU = 0, MGYM_ACT_TANH = 1 };
 int mgym_rollout_mlp(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, int32_t K,
                      void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
 
+/* mgym_rollout_mlp with the action DRAWN from the categorical (softmax) distribution over the scores instead of their argmax: what the collector of an
+ * on-policy trainer (REINFORCE, A2C, PPO) runs.  Everything is as in mgym_rollout_mlp — the `policy` layout, hidden 1 .. 64, MGYM_ACT_RELU / MGYM_ACT_TANH, the
+ * scores s_a as fmaf chains from the bias on the observation held before the step, the output shapes, and the rule that the K steps equal K mgym_step calls
+ * fed the actions in actions_out, word for word, MGYM_FLAG_AUTO_RESET and mgym_config::max_episode_steps included — except how a discrete action follows
+ * from the scores.
+ *
+ * The draw.  All arithmetic is f32 with nothing fused.  A is the family's n_actions.
+ *
+ *   m   = s_0;  for a = 1 .. A-1:  if (s_a > m) m = s_a          (the running best of the existing argmax)
+ *   e_a = expm1f(s_a - m) + 1.0f                                   glibc's expm1f, bit for bit (mg_expm1f)
+ *   c_0 = e_0;  c_a = c_{a-1} + e_a                                ascending a
+ *   w   = word (g % 4) of Philox4x32-10(key = policy_seed;
+ *             counter = (lo32(g & ~3), hi32(g & ~3), policy_call, 0x50000000 + t))
+ *   u   = (float)(w >> 8) * 2^-24                                  exact, in [0, 1)
+ *   thr = u * c_{A-1}                                              one multiply
+ *   action = the first a in 0 .. A-2 with thr < c_a, else A-1
+ *
+ * g is the global environment id, env_id_base + i; t is the step index within this call.  The slot base 0x50000000 is this entry point's own: no draw of
+ * the uniform policy (0x40000000 + ...) can coincide with it.
+ *  - The draw is a pure function of (policy_seed, policy_call, g, t) and the scores.
+ *  - It does not depend on how a population is sharded over handles.
+ *  - The handle keeps no count for it, and the count of mgym_rollout_uniform calls is not touched: a caller passes a new policy_call (or seed) for each call
+ *    that is to draw afresh.  The same (seed, call) on the same state draws the same actions again.
+ *  - An action whose score lies about 17 or more below the best has weight 0 or 2^-24: probabilities are resolved to 2^-24.
+ *  - A temperature is the caller dividing W2 and b2 by it beforehand.
+ *  - Non-finite scores give a defined but meaningless action; a NaN makes every comparison false, hence A-1.  This is specified only so that every form
+ *    of the code agrees (NaNs compare as a class: the weight of the best action is computed as (m - m) + 1.0f, the same word as the text's for a finite m).
+ * The learner recomputes log-probabilities (and any value head) in its own forward pass over obs_out and actions_out; none are returned.
+ *
+ * CartPole (A = 2), MountainCar (A = 3): inside the fused rollout kernels, one Philox evaluation per lane per step serving the lane's four environments;
+ * the conditions of mgym_rollout_mlp (n_envs a multiple of 4, 16-byte aligned buffers, CartPole K * n_envs below 2^30) plus env_id_base a multiple of 4.
+ * LunarLander (A = 4): any n_envs, env_id_base a multiple of 4; always K x (a sampling policy kernel, mgym_step) — the persistent launch does not carry this
+ * source, MGYM_LL_ROLLOUT_MLP changes nothing for this entry point and rollout_persistent_launches does not move.
+ * MountainCarContinuous: MGYM_ERR_BAD_ARG (a Gaussian head is not implemented).
+ * Errors are those of mgym_rollout_mlp, each message starting with "mgym_rollout_mlp_sample:".
+ * Under graph capture the weights, the seed and the call word are frozen into the captured launches: a replay draws the same u again (on the state it
+ * finds), so a loop that replays one graph does not explore — capture one graph per call word, or call eagerly. */
+int mgym_rollout_mlp_sample(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, uint64_t policy_seed, uint32_t policy_call,
+                            int32_t K, void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
+
 /* Number of env-steps of this handle that returned done or truncated since mgym_create (StepInfo.done / .truncated,
  * cartpole.rs:300-305): accumulated inside the step kernels by __ballot/popcount reductions of the done mask,
  * one fire-and-forget atomic per wave.  Synchronises the stream. */
@@ -305,7 +345,7 @@ const char *mgym_last_error(void);
  * GPU_MAX_HW_QUEUES (the HIP runtime knob as this process's environment held it when the handle was created, or "unset").
  * LunarLander adds its launch structure — contact_block, launch_order, staged_resets, the rollout's form (rollout, rollout_min_k, rollout_waves,
  * rollout_helper_blocks) and rollout_persistent_launches, the number of persistent rollout launches this handle has issued since mgym_create
- * (mgym_rollout, _linear, _uniform and _mlp alike; a call of more than 240 steps is several launches; 0 for a call that ran as K x mgym_step: the
+ * (mgym_rollout, _linear, _uniform and _mlp alike, never _mlp_sample; a call of more than 240 steps is several launches; 0 for a call that ran as K x mgym_step: the
  * words are the same either way, this line tells which form ran) — and `concurrent_streams`: the
  * reference is single-threaded (lunar_lander.rs:240-249), this engine steps one population on up to three streams
  * (caller's stream, two helpers), and they only run side by side when the runtime put them on different hardware queues.
@@ -345,6 +385,12 @@ enum {
     MGYM_MATH_TANHF = 5      /* mg_tanhf */
 };
 int mgym_math_probe(int device, int fn, uint32_t first, uint64_t count, uint32_t *out);
+
+/* Test seam: the draw of mgym_rollout_mlp_sample (mlp_sample of modurl_gym_amd/csrc/mlp_policy.h) evaluated on the device, one case per lane.
+ * n_actions = A is 2, 3 or 4; scores is [A][count] floats, words [count] Philox words w, actions_out [count], cum_out [A][count] (c_0 .. c_{A-1}) or NULL;
+ * all device memory; count at most 2^31.  Runs on the null stream and synchronises the device.  tests/test_gpu_sample_probe.py compares with the
+ * restatement of the text above. */
+int mgym_sample_probe(int device, int32_t n_actions, uint64_t count, const float *scores, const uint32_t *words, uint32_t *actions_out, float *cum_out);
 
 /* Test seam: LunarLander's collision-geometry primitives (modurl_gym_amd/csrc/ll_b2.h) evaluated on the device as pure functions,
  * one case per lane.  in and out are device memory, columns [cols][count] of 32-bit words; integer fields are bit patterns.  The

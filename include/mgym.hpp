@@ -68,6 +68,12 @@ class VecGym {
     void rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_mlp(env_, policy, hidden, activation, K, actions_out, obs, reward, done, trunc));
     }
+    // the same with the action drawn from the softmax of the scores (mgym_rollout_mlp_sample): a pure function of (policy_seed, policy_call, global env id,
+    // step) and the scores; pass a new policy_call for each call that is to draw afresh.  Discrete families only; LunarLander always K x (policy kernel, step)
+    void rollout_mlp_sample(const float* policy, int hidden, int activation, uint64_t policy_seed, uint32_t policy_call, int K, void* actions_out, float* obs, float* reward,
+                            uint8_t* done, uint8_t* trunc) {
+        check(mgym_rollout_mlp_sample(env_, policy, hidden, activation, policy_seed, policy_call, K, actions_out, obs, reward, done, trunc));
+    }
     void rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_uniform(env_, policy_seed, K, actions_out, obs, reward, done, trunc));
     }

@@ -286,6 +286,19 @@ int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t
                              trunc_out);
 }
 
+int mgym_rollout_mlp_sample(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, uint64_t policy_seed, uint32_t policy_call, int32_t K,
+                            void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
+    ENV_OR_FAIL(env);
+    if (K < 0) return bad_arg("mgym_rollout_mlp_sample: K < 0");
+    if (e->cfg.kind == MGYM_MOUNTAINCAR_CONT) return bad_arg("mgym_rollout_mlp_sample: MountainCarContinuous has no discrete actions to draw from (a Gaussian head is not implemented)");
+    if (!policy) return bad_arg("mgym_rollout_mlp_sample: policy is NULL");
+    if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp_sample: hidden must be between 1 and 64");
+    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp_sample: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
+    if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_sample: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
+    return e->rollout_policy(PolicyCall{activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, "mgym_rollout_mlp_sample", policy, hidden, policy_seed, policy_call},
+                             K, actions_out, obs_out, reward_out, done_out, trunc_out);
+}
+
 int mgym_episode_count(mgym_env* env, uint64_t* finished) {
     ENV_OR_FAIL(env);
     if (!finished) return bad_arg("mgym_episode_count: NULL");

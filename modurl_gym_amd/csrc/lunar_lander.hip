@@ -710,6 +710,26 @@ __global__ void __launch_bounds__(256) ll_policy_mlp_kernel(const float* __restr
     out[i] = a[0];
 }
 
+// mgym_rollout_mlp_sample, the sampling form of ll_policy_mlp_kernel (the only form this source has: the persistent launch does not carry it): the same
+// scores, the action drawn by mlp_policy.h's mlp_sample with word (g % 4) of Philox(key = seed; counter = (g & ~3, call, SLOT_POLICY_SAMPLE + t)), g the
+// global env id.  Every lane evaluates the Philox block of its group of four ids itself.
+template <int ACT>
+__global__ void __launch_bounds__(256) ll_policy_mlp_sample_kernel(const float* __restrict__ obs, uint64_t n, uint64_t n_pad, MlpPack<8, 4> pack, uint64_t env_id_base, uint64_t seed,
+                                                                   uint32_t call, uint32_t t, uint32_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float o[1][8];
+    uint32_t a[1];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[0][c] = obs[(uint64_t)c * n_pad + i];
+    const uint64_t g = env_id_base + i;
+    const Philox4 w = env_draw(seed, g & ~3ull, call, SLOT_POLICY_SAMPLE + t);
+    const uint32_t k = (uint32_t)g & 3u;
+    const uint32_t word[1] = {k == 0u ? w.w[0] : k == 1u ? w.w[1] : k == 2u ? w.w[2] : w.w[3]};
+    mlp_actions<8, 4, ACT, 1>(pack, o, word, a);
+    out[i] = a[0];
+}
+
 // Staged resets.  The state an env has after reset() — scene, implicit step(0), observation — is a pure function of
 // (seed, env id, episode counter), so it does not have to be computed when the episode ends, on the critical path of
 // that step (reset kernel: 0.11 ms behind the contact kernel): it is PREPARED in advance, in shadow columns, by the same
@@ -1236,9 +1256,9 @@ struct LunarLanderEnv final : Env {
                                       h[RS_N_HELPER_STEPS] ? (double)h[RS_N_HELPER_LANE_STEPS] / h[RS_N_HELPER_STEPS] : 0.0, (double)h[RS_N_FREE_STEPS]);
         return MGYM_OK;
     }
-    // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp, the one place that unpacks the call and chooses the form: the persistent launch with the
+    // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp / mgym_rollout_mlp_sample, the one place that unpacks the call and chooses the form: the persistent launch with the
     // action source `policy` (ll_roll.h) when the handle has one, K >= rollout_min_k, the stream is not being captured and — hidden-layer sources — the activation runs
-    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).
+    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).  The sampling sources always run the second form, whatever MGYM_LL_ROLLOUT_MLP says.
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
         const int policy = call.source;
@@ -1258,13 +1278,16 @@ struct LunarLanderEnv final : Env {
             mlp_pack<8, 4>(call.weights, call.hidden, pack);
         }
         pol.next = next_act;
-        const bool persistent = opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
+        const bool sample = roll_act_samples(policy);
+        const bool persistent = !sample && opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
         if (!persistent) {
             const unsigned g = (unsigned)((n + 255) / 256);
             for (int t = 0; t < K; ++t) {
                 uint32_t* a = ao ? ao + (size_t)t * n : next_act;
                 if (policy == ROLL_ACT_LINEAR) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_LINEAR>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
                 else if (policy == ROLL_ACT_UNIFORM) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_UNIFORM>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
+                else if (policy == ROLL_ACT_MLP_TANH_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
+                else if (policy == ROLL_ACT_MLP_RELU_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
                 else if (policy == ROLL_ACT_MLP_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);   // (the pack as a kernel argument: a captured graph carries it)
                 else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
                 MGYM_HIP(hipGetLastError());

@@ -1,4 +1,4 @@
-// mlp_policy.h — the one-hidden-layer policy of mgym_rollout_mlp (include/mgym.h), shared by the rollout kernels of CartPole and MountainCar
+// mlp_policy.h — the one-hidden-layer policy of mgym_rollout_mlp and mgym_rollout_mlp_sample (include/mgym.h), shared by the rollout kernels of CartPole and MountainCar
 // (cartpole.hip, mountain_car.hip: the lane's four environments), LunarLander's policy kernel (lunar_lander.hip: one environment per lane) and the
 // host check tests/native/mlp_policy_check.cpp, which compiles this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
 // -ffp-contract=off: the only fused operations are the cp_fmaf of the two chains.
@@ -94,6 +94,63 @@ MG_HD void mlp_actions(const MlpPack<D, A>& p, const float (&o)[N][D], uint32_t 
     mlp_scores<D, A, ACT, N>(p, o, s);
 #pragma unroll
     for (int k = 0; k < N; ++k) act[k] = CONT ? as_u32(s[k][0]) : mlp_argmax<A>(s[k]);
+}
+
+// ---- mgym_rollout_mlp_sample: the action drawn from the categorical distribution over the scores (include/mgym.h, "The draw") ----
+//   m = the running best of mlp_argmax;  e_a = mg_expm1f(s_a - m) + 1;  c_a = c_{a-1} + e_a;  thr = u * c_{A-1};  the first a with thr < c_a, else A - 1
+// f32, nothing fused.  The best action b (the index mlp_argmax returns) has s_b - m = m - m, which is +0 for a finite m and a NaN otherwise, and
+// mg_expm1f(+0) + 1 = 1, mg_expm1f(NaN) + 1 = NaN: its weight is (m - m) + 1 without the call, the same word for a finite m and a NaN where the text gives
+// one.  So an environment-step costs A - 1 evaluations of mg_expm1f: CartPole one, of -|s_0 - s_1|.
+
+// c_0 .. c_{A-1}
+template <int A>
+MG_HD void mlp_sample_cum(const float (&s)[A], float (&c)[A]) {
+    static_assert(A >= 2, "a draw needs two actions");
+    float m = s[0];
+    int b = 0;
+#pragma unroll
+    for (int a = 1; a < A; ++a)
+        if (s[a] > m) { m = s[a]; b = a; }
+    float ex[A - 1];   // the weights of the other actions in ascending order: entry k is action k below b, k + 1 from b on
+#pragma unroll
+    for (int k = 0; k < A - 1; ++k) ex[k] = mg_expm1f((k >= b ? s[k + 1] : s[k]) - m) + 1.0f;
+    const float eb = (m - m) + 1.0f;
+    float acc = 0.0f;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        const float lo = ex[a > 0 ? a - 1 : 0], hi = ex[a < A - 1 ? a : A - 2];
+        const float e = a == b ? eb : (a > b ? lo : hi);
+        acc = a == 0 ? e : acc + e;
+        c[a] = acc;
+    }
+}
+
+// u = (w >> 8) 2^-24 in [0, 1), thr = u * c_{A-1}: the first a in 0 .. A-2 with thr < c_a, else A - 1 (a NaN makes every comparison false)
+template <int A>
+MG_HD uint32_t mlp_sample_pick(const float (&c)[A], uint32_t w) {
+    const float u = (float)(w >> 8) * 5.9604644775390625e-08f;
+    const float thr = u * c[A - 1];
+    uint32_t act = (uint32_t)(A - 1);
+#pragma unroll
+    for (int a = A - 2; a >= 0; --a)
+        if (thr < c[a]) act = (uint32_t)a;
+    return act;
+}
+
+template <int A>
+MG_HD uint32_t mlp_sample(const float (&s)[A], uint32_t w) {
+    float c[A];
+    mlp_sample_cum<A>(s, c);
+    return mlp_sample_pick<A>(c, w);
+}
+
+// the SAMPLE form of mlp_actions: environment k draws with the word w[k] (discrete families only)
+template <int D, int A, int ACT, int N>
+MG_HD void mlp_actions(const MlpPack<D, A>& p, const float (&o)[N][D], const uint32_t (&w)[N], uint32_t (&act)[N]) {
+    float s[N][A];
+    mlp_scores<D, A, ACT, N>(p, o, s);
+#pragma unroll
+    for (int k = 0; k < N; ++k) act[k] = mlp_sample<A>(s[k], w[k]);
 }
 
 }  // namespace mgym

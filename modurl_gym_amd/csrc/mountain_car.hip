@@ -295,7 +295,16 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 // hidden-layer policy on (position, velocity) of the lane's four envs before the step (mlp_policy.h)
                 const float o[4][2] = {{ps[0], vs[0]}, {ps[1], vs[1]}, {ps[2], vs[2]}, {ps[3], vs[3]}};
-                mlp_actions<2, CONT ? 1 : 3, POLICY == ROLL_ACT_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, CONT, 4>(lin, o, a);
+                constexpr int ACT = roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU;
+                if constexpr (roll_act_samples(POLICY)) {
+                    // mgym_rollout_mlp_sample (Discrete(3) only): one Philox evaluation per lane per step, its four words for the lane's four envs; `uni`
+                    // carries the policy seed and the caller's call word
+                    static_assert(!CONT, "MountainCarContinuous has no categorical draw");
+                    const Philox4 w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
+                    mlp_actions<2, 3, ACT, 4>(lin, o, w.w, a);
+                } else {
+                    mlp_actions<2, CONT ? 1 : 3, ACT, CONT, 4>(lin, o, a);
+                }
                 if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
             } else if constexpr (LINEAR) {
 #pragma unroll
@@ -514,8 +523,12 @@ struct MountainCarEnv final : Env {
             default: {   // the hidden-layer sources
                 MlpPack<2, CONT ? 1 : 3> pack;
                 mlp_pack<2, CONT ? 1 : 3>(call.weights, call.hidden, pack);
-                with_bools([&](auto H) { launch_rollout<decltype(H)::value ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack); },
-                           call.source == ROLL_ACT_MLP_TANH);
+                with_bools([&](auto H, auto S) {
+                    constexpr bool TANH = decltype(H)::value;
+                    if constexpr (!decltype(S)::value) launch_rollout<TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
+                    else if constexpr (!CONT)   // (the C ABI rejects mgym_rollout_mlp_sample on MountainCarContinuous)
+                        launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, McUniformPolicy{call.seed, call.call});
+                }, roll_act_mlp_tanh(call.source), roll_act_samples(call.source));
             }
             }
         }, continuous, dev.limit != 0u);

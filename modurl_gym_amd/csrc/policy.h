@@ -9,20 +9,27 @@ namespace mgym {
 //   LINEAR    one score per action from the observation the env holds before the step (mgym_rollout_linear)
 //   UNIFORM   Philox draws keyed by (policy seed, global env id, number of earlier uniform calls on the handle, step) (mgym_rollout_uniform)
 //   MLP_RELU / MLP_TANH  as LINEAR, decided by mlp_policy.h's one-hidden-layer policy (mgym_rollout_mlp)
+//   MLP_RELU_SAMPLE / MLP_TANH_SAMPLE  the same scores, the action drawn from their softmax with a Philox word keyed by (policy seed, global env id, the
+//             caller's call word, step) (mgym_rollout_mlp_sample).  New sources, not a flag: the instantiations of the others keep their code.
 // How LunarLander's persistent launch carries each of them: ll_roll_types.h.
-enum { ROLL_ACT_TABLE = 0, ROLL_ACT_LINEAR = 1, ROLL_ACT_UNIFORM = 2, ROLL_ACT_MLP_RELU = 3, ROLL_ACT_MLP_TANH = 4 };
-// the hidden-layer sources
-constexpr bool roll_act_is_mlp(int source) { return source == ROLL_ACT_MLP_RELU || source == ROLL_ACT_MLP_TANH; }
+enum { ROLL_ACT_TABLE = 0, ROLL_ACT_LINEAR = 1, ROLL_ACT_UNIFORM = 2, ROLL_ACT_MLP_RELU = 3, ROLL_ACT_MLP_TANH = 4, ROLL_ACT_MLP_RELU_SAMPLE = 5,
+       ROLL_ACT_MLP_TANH_SAMPLE = 6 };
+// the hidden-layer sources that draw their action (LunarLander's persistent launch carries none of them)
+constexpr bool roll_act_samples(int source) { return source == ROLL_ACT_MLP_RELU_SAMPLE || source == ROLL_ACT_MLP_TANH_SAMPLE; }
+// the hidden-layer sources, and whether their activation is tanh
+constexpr bool roll_act_is_mlp(int source) { return source == ROLL_ACT_MLP_RELU || source == ROLL_ACT_MLP_TANH || roll_act_samples(source); }
+constexpr bool roll_act_mlp_tanh(int source) { return source == ROLL_ACT_MLP_TANH || source == ROLL_ACT_MLP_TANH_SAMPLE; }
 // the sources that decide from the observation
 constexpr bool roll_act_observes(int source) { return source == ROLL_ACT_LINEAR || roll_act_is_mlp(source); }
 
-// One call of mgym_rollout_uniform / _linear / _mlp as the C ABI hands it to Env::rollout_policy, its own argument checks passed.
+// One call of mgym_rollout_uniform / _linear / _mlp / _mlp_sample as the C ABI hands it to Env::rollout_policy, its own argument checks passed.
 struct PolicyCall {
-    int source;             // ROLL_ACT_UNIFORM, ROLL_ACT_LINEAR, ROLL_ACT_MLP_RELU or ROLL_ACT_MLP_TANH
+    int source;             // ROLL_ACT_UNIFORM, ROLL_ACT_LINEAR or one of the ROLL_ACT_MLP_* sources
     const char* api;        // the entry point's name: the prefix of every error message
     const float* weights;   // LINEAR: obs_dim weights + bias per score; MLP_*: W1[H][D], b1[H], W2[A][H], b2[A] (host floats); UNIFORM: null
     int hidden;             // MLP_*: H
-    uint64_t seed;          // UNIFORM: the policy seed
+    uint64_t seed;          // UNIFORM, MLP_*_SAMPLE: the policy seed
+    uint32_t call;          // MLP_*_SAMPLE: the caller's call word (UNIFORM counts its calls on the handle instead)
 };
 
 }  // namespace mgym

@@ -16,6 +16,7 @@
 #include "cartpole_step.h"
 #include "ll_kernel_common.h"
 #include "ll_geom_probe.h"
+#include "mlp_policy.h"
 
 namespace mgym {
 
@@ -168,6 +169,24 @@ __global__ void __launch_bounds__(256) math_probe_kernel(uint32_t first, uint64_
     }
 }
 
+// mlp_policy.h's draw for one case per lane (mgym_sample_probe): scores [A][count], one Philox word per case; the action, and c_0 .. c_{A-1} if asked
+template <int A>
+__global__ void __launch_bounds__(256) sample_probe_kernel(uint64_t count, const float* __restrict__ scores, const uint32_t* __restrict__ words, uint32_t* __restrict__ actions,
+                                                           float* __restrict__ cum) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        float s[A], c[A];
+#pragma unroll
+        for (int a = 0; a < A; ++a) s[a] = scores[(uint64_t)a * count + i];
+        actions[i] = mlp_sample<A>(s, words[i]);
+        if (cum) {
+            mlp_sample_cum<A>(s, c);
+#pragma unroll
+            for (int a = 0; a < A; ++a) cum[(uint64_t)a * count + i] = c[a];
+        }
+    }
+}
+
 // one case per lane (ll_geom_probe.h).  As in every product kernel the polygon table and collide_edge_polygon's per-lane buffer are
 // LDS: that function casts both to the LDS address space.
 constexpr int kGeomBlock = 64;
@@ -210,6 +229,28 @@ extern "C" int mgym_ll_geom_probe(int device, int fn, uint64_t count, const floa
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (prev >= 0) (void)hipSetDevice(prev);
     if (e != hipSuccess) return hip_fail(e, "ll_geom_probe", __FILE__, __LINE__);
+    return MGYM_OK;
+}
+
+extern "C" int mgym_sample_probe(int device, int32_t n_actions, uint64_t count, const float* scores, const uint32_t* words, uint32_t* actions_out, float* cum_out) {
+    if (n_actions < 2 || n_actions > 4 || count == 0 || count > (1ull << 31) || !scores || !words || !actions_out) {
+        set_last_error("mgym_sample_probe: n_actions outside 2 .. 4, a case count of 0 or above 2^31, or NULL scores, words or actions_out");
+        return MGYM_ERR_BAD_ARG;
+    }
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    MGYM_HIP(hipSetDevice(device));
+    const uint64_t blocks = (count + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536)), block(256);
+    switch (n_actions) {
+        case 2: hipLaunchKernelGGL(sample_probe_kernel<2>, grid, block, 0, nullptr, count, scores, words, actions_out, cum_out); break;
+        case 3: hipLaunchKernelGGL(sample_probe_kernel<3>, grid, block, 0, nullptr, count, scores, words, actions_out, cum_out); break;
+        default: hipLaunchKernelGGL(sample_probe_kernel<4>, grid, block, 0, nullptr, count, scores, words, actions_out, cum_out); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return hip_fail(e, "sample_probe", __FILE__, __LINE__);
     return MGYM_OK;
 }
 

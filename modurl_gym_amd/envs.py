@@ -239,9 +239,8 @@ class VecEnv:
                                                   f"{w1.shape}, {b1.shape}, {w2.shape}, {b2.shape}")
         return np.concatenate([w1.ravel(), b1, w2.ravel(), b2]).astype(np.float32), H
 
-    def rollout_mlp_device(self, policy, hidden, activation, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
-        """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): `policy` = the packed host floats of pack_mlp (or None, which the
-        engine rejects), `hidden` = H, `activation` = "relu" / "tanh" or the MGYM_ACT_* value.  A policy of the wrong length for H raises PolicyShapeError."""
+    def _mlp_args(self, policy, hidden, activation):
+        """(contiguous float32 policy or None, activation value) of the hidden-layer entry points, the policy's length checked against H and the family"""
         act = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH}.get(activation, activation)
         if not isinstance(act, (int, np.integer)):
             raise PolicyShapeError(L.ERR_BAD_ARG, f'activation must be "relu", "tanh" or an MGYM_ACT_* value, got {activation!r}')
@@ -251,14 +250,33 @@ class VecEnv:
             pol_in = np.asarray(policy, np.float32).ravel()
             if 1 <= int(hidden) <= 64 and pol_in.size != int(hidden) * (D + 1) + A * (int(hidden) + 1):
                 raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {int(hidden) * (D + 1) + A * (int(hidden) + 1)} floats for hidden = {hidden}, got {pol_in.size}")
-            pol = np.ascontiguousarray(pol_in).ctypes.data_as(C.POINTER(C.c_float))
-        _check(self._lib.mgym_rollout_mlp(self._h, pol, int(hidden), int(act), int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out),
-                                          _ptr(trunc_out)))
+            pol = np.ascontiguousarray(pol_in)
+        return pol, int(act)
+
+    def rollout_mlp_device(self, policy, hidden, activation, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
+        """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): `policy` = the packed host floats of pack_mlp (or None, which the
+        engine rejects), `hidden` = H, `activation` = "relu" / "tanh" or the MGYM_ACT_* value.  A policy of the wrong length for H raises PolicyShapeError."""
+        pol, act = self._mlp_args(policy, hidden, activation)
+        _check(self._lib.mgym_rollout_mlp(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, int(K), _ptr(actions_out),
+                                          _ptr(obs_out), _ptr(reward_out), _ptr(done_out), _ptr(trunc_out)))
+
+    def rollout_mlp_sample_device(self, policy, hidden, activation, seed, call, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
+        """rollout_mlp_device with the action drawn from the softmax of the scores (mgym_rollout_mlp_sample; the discrete families): the draw is a pure
+        function of (seed, call, global env id, step) and the scores — include/mgym.h states it to the word.  The handle keeps no count: pass a new `call`
+        (a 32-bit word) for each call that is to draw afresh."""
+        pol, act = self._mlp_args(policy, hidden, activation)
+        _check(self._lib.mgym_rollout_mlp_sample(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, int(seed) & (2**64 - 1),
+                                                 int(call) & 0xFFFFFFFF, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out), _ptr(trunc_out)))
 
     def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc); actions float32 for MountainCarContinuous"""
         policy, H = self.pack_mlp(w1, b1, w2, b2)
         return self._rollout_host(K, lambda *out: self.rollout_mlp_device(policy, H, activation, K, *out), self.action_dtype)
+
+    def rollout_mlp_sample(self, w1, b1, w2, b2, K, seed, call=0, activation="relu"):
+        """host-array form of rollout_mlp_sample_device: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""
+        policy, H = self.pack_mlp(w1, b1, w2, b2)
+        return self._rollout_host(K, lambda *out: self.rollout_mlp_sample_device(policy, H, activation, seed, call, K, *out), self.action_dtype)
 
     def rollout_uniform(self, policy_seed, K):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""

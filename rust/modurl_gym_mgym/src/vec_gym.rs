@@ -195,6 +195,37 @@ impl VecGym {
         }
         check(unsafe { mgym_rollout_mlp(self.env, policy.as_ptr(), hidden, activation, k, actions_out, obs, reward, done, truncated) })
     }
+    /// `rollout_mlp` with the action drawn from the softmax of the scores (`mgym_rollout_mlp_sample`): the draw is a pure function of (`policy_seed`,
+    /// `policy_call`, global env id, step) and the scores, as `include/mgym.h` states it to the word; the handle keeps no count, so pass a new `policy_call` for
+    /// each call that is to draw afresh.  Discrete families only (MountainCarContinuous: `MGYM_ERR_BAD_ARG`); `env_id_base` a multiple of 4; LunarLander always
+    /// runs it as K x (policy kernel, step).
+    /// # Safety
+    /// the output pointers are device pointers of `[K][n]` (`[K][obs_dim][n]` for `obs`) elements, or null.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn rollout_mlp_sample(
+        &mut self,
+        policy: &[f32],
+        hidden: i32,
+        activation: i32,
+        policy_seed: u64,
+        policy_call: u32,
+        k: i32,
+        actions_out: *mut c_void,
+        obs: *mut f32,
+        reward: *mut f32,
+        done: *mut u8,
+        truncated: *mut u8,
+    ) -> Result<(), MgymError> {
+        let (d, a) = (self.spec.obs_dim as usize, if self.spec.action_is_float != 0 { 1 } else { self.spec.n_actions as usize });
+        if (1..=64).contains(&hidden) {
+            let h = hidden as usize;
+            let want = h * (d + 1) + a * (h + 1);
+            if policy.len() != want {
+                return Err(MgymError { status: MGYM_ERR_BAD_ARG, message: format!("rollout_mlp_sample: {} policy floats for hidden = {}, got {}", want, hidden, policy.len()) });
+            }
+        }
+        check(unsafe { mgym_rollout_mlp_sample(self.env, policy.as_ptr(), hidden, activation, policy_seed, policy_call, k, actions_out, obs, reward, done, truncated) })
+    }
     /// K fused steps under the on-device uniform random policy (`mgym_rollout_uniform`; every family, the draws as `include/mgym.h` documents them): no action table.
     /// `actions_out` (`[K][n]` u32, may be null) receives the drawn actions.
     #[allow(clippy::too_many_arguments)]
