@@ -174,62 +174,70 @@ __device__ __forceinline__ void cartpole_flush_counts(const CartPoleDev& d, uint
 
 // VEC: envs per lane (4 = 16-byte accesses; 1 = fallback for misaligned caller buffers).
 // RESET: MGYM_FLAG_AUTO_RESET.
-template <int VEC, bool EULER, bool SB, bool RESET, int BLK>
+// ONE: the single-pass form — the host launched exactly one block per tile of BLK * VEC environments (every population of at most the block cap's
+// tiles: 8 Mi envs at 256 threads), so the instantiation has no loop, no test on n before its loads and no read of the grid size.  !ONE: the
+// grid-stride form of larger populations; the host launches no more blocks than tiles, so a block's first pass needs no test either.
+// The arguments are plain scalars and pointers in the order the kernel first needs them — what the state loads need (base, n_pad), then n and
+// the actions, then the rest — and CartPoleDev is rebuilt from them for the per-wave functions: the leading 14 dwords (base .. done_count)
+// can be asked for as preloaded SGPRs (Makefile, PRELOAD); without that one scalar load and one wait stand before the loads.
+template <int VEC, bool EULER, bool SB, bool RESET, int BLK, bool ONE>
 __global__ void __launch_bounds__(BLK)
-cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out,
-                     float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
+cartpole_step_kernel(float* col0, uint32_t n_pad, uint32_t n, const uint32_t* __restrict__ act, uint64_t seed, uint64_t env_id_base, uint32_t* err,
+                     unsigned long long* done_count, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out,
+                     uint8_t* __restrict__ trunc_out) {
     __shared__ WaveResetScratch<VEC> lds_[RESET ? BLK / 64 : 1];
-    constexpr uint64_t kPerBlock = (uint64_t)BLK * VEC;
-    bool bad = false;
-    uint32_t finished = 0;
-    WaveResetScratch<VEC>& lds = lds_[RESET ? (threadIdx.x >> 6) : 0];
+    constexpr uint32_t kPerBlock = (uint32_t)BLK * VEC;
     const uint32_t lane_env = threadIdx.x * VEC;     // first env of this lane within the block's slice
     const uint32_t off4 = lane_env * 4u;             // its byte offset in a 4-byte column
-    const uint64_t col = d.n_pad;                    // engine column stride (words)
-    const uint32_t colb = (uint32_t)col * 4u;        // ... in bytes
+    const uint32_t colb = n_pad * 4u;                // engine column stride in bytes
     // raw buffer resource over the engine's allocation (stride 0, no bounds clamp, 32-bit data format: gfx9 word 3 = 0x00020000)
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(d.base, 0, 0xffffffff, 0x00020000);
-    for (uint64_t base = (uint64_t)blockIdx.x * kPerBlock; base < d.n; base += (uint64_t)gridDim.x * kPerBlock) {  // wave-uniform
-        // uniform (scalar) bases of this block pass
-        float* const bx = d.base + base;
-        const uint32_t* const ba = act + base;
-        const uint64_t left = d.n - base;
-        const uint32_t rem = left < kPerBlock ? (uint32_t)left : (uint32_t)kPerBlock;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(col0, 0, 0xffffffff, 0x00020000);
+    const CartPoleDev d{col0, n_pad, n, seed, env_id_base, err, done_count};
+    bool bad = false;
+    uint32_t finished = 0;
+    uint32_t base = blockIdx.x * kPerBlock;          // wave-uniform; n <= 2^27: env indices and byte offsets fit 32 bits
+    do {
+        const uint32_t sb = base * 4u;               // byte offset of this pass in a column
         CartPoleLane s[VEC];
         uint32_t a[VEC];
         bool valid[VEC];
         float r[VEC];
         uint32_t dn[VEC], tr[VEC];
-        const bool in = lane_env < rem;  // the host launches VEC = 4 only when n % 4 == 0: a lane is wholly in or out
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) valid[k] = in;
-        const uint32_t sb = (uint32_t)base * 4u;  // byte offset of this pass in a column (n <= 2^27: every offset < 2^32)
+        bool in;  // the host launches VEC = 4 only when n % 4 == 0: a lane is wholly in or out
+        float* const bx = col0 + base;
+        const uint64_t col = n_pad;
         if constexpr (VEC == 4) {
             // Engine columns: buffer loads — resource descriptor and column/pass offsets in SGPRs, one constant VGPR lane
             // offset, no per-lane address arithmetic.  The columns are padded to n_pad (a multiple of the block's 1024
             // envs), so every lane of the block may load (padding holds zeros and is never stored back).
-            // theta, theta_dot and the action first: the sin/cos polynomial can start while x, x_dot, ctr are in flight.
+            // Every load of the pass is issued here, before anything that feeds no address.
             const u32x4 vth = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + 2u * colb, 0);
             const u32x4 vthd = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + 3u * colb, 0);
-            uint4 va = make_uint4(0u, 0u, 0u, 0u);
-            if (in) va = *at<uint4>(ba, off4);  // caller buffer: n words exactly
             const u32x4 vx = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb, 0);
             const u32x4 vxd = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + colb, 0);
             const u32x4 vc = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + 4u * colb, 0);
+            in = lane_env < n - base;
+            uint4 va = make_uint4(0u, 0u, 0u, 0u);
+            if (in) va = *at<uint4>(act + base, off4);  // caller buffer: n words exactly
+            __builtin_amdgcn_sched_barrier(0);
             s[0] = {as_f32(vx.x), as_f32(vxd.x), as_f32(vth.x), as_f32(vthd.x), vc.x};
             s[1] = {as_f32(vx.y), as_f32(vxd.y), as_f32(vth.y), as_f32(vthd.y), vc.y};
             s[2] = {as_f32(vx.z), as_f32(vxd.z), as_f32(vth.z), as_f32(vthd.z), vc.z};
             s[3] = {as_f32(vx.w), as_f32(vxd.w), as_f32(vth.w), as_f32(vthd.w), vc.w};
             a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w;
         } else {
+            in = lane_env < n - base;
             s[0] = {0.f, 0.f, 0.f, 0.f, 0u};
             a[0] = 0u;
             if (in) {
                 s[0] = {*at<float>(bx, off4), *at<float>(bx + col, off4), *at<float>(bx + 2 * col, off4), *at<float>(bx + 3 * col, off4),
                         *at<uint32_t>(bx + 4 * col, off4)};
-                a[0] = *at<uint32_t>(ba, off4);
+                a[0] = *at<uint32_t>(act + base, off4);
             }
         }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) valid[k] = in;
+        WaveResetScratch<VEC>& lds = lds_[RESET ? (threadIdx.x >> 6) : 0];
         cartpole_wave_advance<VEC, EULER, SB>(s, a, valid, r, dn, tr, bad);
         // reward / done / truncated do not depend on the reset: issued here, their write-out drains while the reset
         // pass runs (the LDS fences of cartpole_wave_reset keep the compiler from sinking them past it)
@@ -271,7 +279,9 @@ cartpole_step_kernel(CartPoleDev d, const uint32_t* __restrict__ act, float* __r
                 }
             }
         }
-    }
+        if constexpr (ONE) break;
+        base += gridDim.x * kPerBlock;   // (at most 2^23 envs a stride: no 32-bit wrap below n <= 2^27)
+    } while (base < n);
     cartpole_flush_counts<BLK / 64>(d, finished, bad);
 }
 
@@ -461,6 +471,7 @@ struct CartPoleEnv final : Env {
     CartPoleDev dev{};
     bool auto_reset = false;
     int step_block = getenv("MGYM_CARTPOLE_BLOCK") ? atoi(getenv("MGYM_CARTPOLE_BLOCK")) : kBlock;  // threads per block of the step kernel (tuning knob)
+    int max_blocks = classic_max_blocks(kMaxBlocks);   // block cap of the step kernel, in kBlock-sized blocks (MGYM_CLASSIC_MAX_BLOCKS lowers it)
 
     ~CartPoleEnv() override {
         if (base) (void)hipFree(base);
@@ -507,12 +518,14 @@ struct CartPoleEnv final : Env {
 
     template <int VEC, bool RESET, int BLK>
     void launch_step_blk(const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
-        uint64_t nb = (n + (uint64_t)BLK * VEC - 1) / ((uint64_t)BLK * VEC);
-        const uint64_t cap = (uint64_t)kMaxBlocks * kBlock / BLK;   // same thread count as the kBlock-sized cap
-        dim3 g((unsigned)(nb > cap ? cap : (nb ? nb : 1))), b(BLK);
-        with_bools([&](auto E, auto S) {
-            hipLaunchKernelGGL((cartpole_step_kernel<VEC, decltype(E)::value, decltype(S)::value, RESET, BLK>), g, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }, cfg.is_euler, cfg.sutton_barto_reward);
+        const uint64_t nb = (n + (uint64_t)BLK * VEC - 1) / ((uint64_t)BLK * VEC);   // tiles (n > 0)
+        const uint64_t cap = (uint64_t)max_blocks * kBlock / BLK;   // same thread count as the kBlock-sized cap
+        const bool one = nb <= cap;                                 // one block per tile: the single-pass form
+        dim3 g((unsigned)(one ? nb : cap)), b(BLK);
+        with_bools([&](auto E, auto S, auto O) {
+            hipLaunchKernelGGL((cartpole_step_kernel<VEC, decltype(E)::value, decltype(S)::value, RESET, BLK, decltype(O)::value>), g, b, 0, stream, dev.base,
+                               (uint32_t)dev.n_pad, (uint32_t)dev.n, act, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc);
+        }, cfg.is_euler, cfg.sutton_barto_reward, one);
     }
     template <int VEC, bool RESET>
     void launch_step(const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {

@@ -29,6 +29,11 @@ struct MountainCarParams {
     float force, gravity;  // discrete: 0.001, 0.0025; continuous: power 0.0015 in `force`
 };
 
+// mountain_car.rs:35-40; the family (discrete / continuous) fixes everything but goal_velocity
+__host__ __device__ constexpr MountainCarParams mc_params(bool continuous, float goal_velocity) {
+    return MountainCarParams{-1.2f, 0.6f, 0.07f, continuous ? 0.45f : 0.5f, goal_velocity, continuous ? 0.0015f : 0.001f, 0.0025f};
+}
+
 struct MountainCarDev {
     float *pos, *vel;
     uint32_t* episode;
@@ -187,29 +192,39 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
 // (a multiple of the block's 1024 envs), so every lane may load them — only in-range lanes store.  The done mask is
 // reduced with __ballot + popcount for mgym_episode_count; resets are rare here (episodes last >= 100 steps) and stay
 // in place.
-template <bool CONT, bool RESET, bool TL = false>
+// ONE: the single-pass form — the host launched one block per tile of 1024 environments (every population of at most the block cap's tiles), so
+// the instantiation has no loop, no test on n before its loads and no read of the grid size; !ONE: the grid-stride form of larger populations
+// (no more blocks than tiles, so a block's first pass needs no test either).  The arguments are plain scalars and pointers in the order the
+// kernel first needs them — what the loads need (pos, n_pad, n, actions, the elapsed column), then the rest; the leading 14 dwords (pos .. err)
+// can be asked for as preloaded SGPRs (Makefile, PRELOAD).  MountainCarDev is rebuilt from them for mountaincar_step_one / mountaincar_reset_one: the
+// columns lie n_pad words apart, and the physics constants depend on the family alone (mc_params), all but goal_velocity.
+template <bool CONT, bool RESET, bool TL, bool ONE>
 __global__ void __launch_bounds__(kBlock)
-mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out,
-                         float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
-    constexpr uint64_t kPerBlock = (uint64_t)kBlock * 4;
+mountaincar_step4_kernel(float* pos, uint32_t n_pad, uint32_t n, const uint32_t* __restrict__ act, uint16_t* elapsed, uint64_t seed, uint64_t env_id_base,
+                         uint32_t* err, unsigned long long* done_count, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out,
+                         uint8_t* __restrict__ trunc_out, uint32_t limit, float goal_velocity) {
+    constexpr uint32_t kPerBlock = (uint32_t)kBlock * 4;
     const uint32_t lane_env = threadIdx.x * 4u, off4 = lane_env * 4u;
-    const uint32_t colb = (uint32_t)(d.vel - d.pos) * 4u;  // column stride in bytes
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(d.pos, 0, 0xffffffff, 0x00020000);
+    const uint32_t colb = n_pad * 4u;  // column stride in bytes
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(pos, 0, 0xffffffff, 0x00020000);
+    const MountainCarDev d{pos, pos + n_pad, reinterpret_cast<uint32_t*>(pos + 2 * (uint64_t)n_pad), n, seed, env_id_base, err, done_count,
+                           mc_params(CONT, goal_velocity), RESET ? 1 : 0, elapsed, limit};
     bool bad = false;
     uint32_t finished = 0;
-    for (uint64_t base = (uint64_t)blockIdx.x * kPerBlock; base < d.n; base += (uint64_t)gridDim.x * kPerBlock) {  // block-uniform
-        const uint64_t left = d.n - base;
-        const uint32_t rem = left < kPerBlock ? (uint32_t)left : (uint32_t)kPerBlock;
-        const bool in = lane_env < rem;
-        const uint32_t sb = (uint32_t)base * 4u;
+    uint32_t base = blockIdx.x * kPerBlock;   // block-uniform
+    do {
+        const uint32_t sb = base * 4u;
+        // every load of the pass first
         const u32x4 vp = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb, 0);
         const u32x4 vv = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + colb, 0);
-        uint4 va = CONT ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(1u, 1u, 1u, 1u);
-        if (in) va = *at<uint4>(act + base, off4);
-        float ps[4] = {as_f32(vp.x), as_f32(vp.y), as_f32(vp.z), as_f32(vp.w)}, vs[4] = {as_f32(vv.x), as_f32(vv.y), as_f32(vv.z), as_f32(vv.w)}, r[4];
-        uint32_t a[4] = {va.x, va.y, va.z, va.w}, dn[4];
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u}, fin[4];   // (el / tr: time limit only)
         if constexpr (TL) mc_load_elapsed4(d, base + lane_env, el);            // (padded to n_pad like the state columns: every lane may load)
+        const bool in = lane_env < n - base;
+        uint4 va = CONT ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(1u, 1u, 1u, 1u);
+        if (in) va = *at<uint4>(act + base, off4);
+        __builtin_amdgcn_sched_barrier(0);
+        float ps[4] = {as_f32(vp.x), as_f32(vp.y), as_f32(vp.z), as_f32(vp.w)}, vs[4] = {as_f32(vv.x), as_f32(vv.y), as_f32(vv.z), as_f32(vv.w)}, r[4];
+        uint32_t a[4] = {va.x, va.y, va.z, va.w}, dn[4];
         uint32_t any_done = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -223,7 +238,7 @@ mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, flo
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 finished += (uint32_t)__popcll(__ballot(in && fin[k]));
-                if (RESET && in && fin[k]) { mountaincar_reset_one(d, base + lane_env + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
+                if (RESET && in && fin[k]) { mountaincar_reset_one(d, (uint64_t)base + lane_env + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
             }
         }
         if (in) {
@@ -239,7 +254,9 @@ mountaincar_step4_kernel(MountainCarDev d, const uint32_t* __restrict__ act, flo
             if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));  // :328 truncated: false, always (TL: the time limit)
             if constexpr (TL) mc_store_elapsed4(d, base + lane_env, el);
         }
-    }
+        if constexpr (ONE) break;
+        base += gridDim.x * kPerBlock;   // (at most 2^23 envs a stride: no 32-bit wrap below n <= 2^27)
+    } while (base < n);
     if ((threadIdx.x & 63) == 0 && finished)
         atomicAdd(d.done_count + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kDoneShards - 1)), (unsigned long long)finished);
     if (__any(bad)) {
@@ -425,6 +442,7 @@ struct MountainCarEnv final : Env {
     }
 
     bool use_step4 = !getenv("MGYM_MC_OLD_KERNEL");  // A/B knob: the per-thread grid-stride kernel of round 1
+    int max_blocks = classic_max_blocks(kMaxBlocks);  // block cap of the 16-byte step kernel (MGYM_CLASSIC_MAX_BLOCKS lowers it)
     int init() override {
         obs_dim = 2;
         state_cols = 3;
@@ -439,12 +457,7 @@ struct MountainCarEnv final : Env {
         MGYM_HIP(hipMemsetAsync(el_base, 0, n_pad * sizeof(uint16_t), stream));
         dev.elapsed = static_cast<uint16_t*>(el_base);
         dev.limit = cfg.max_episode_steps;
-        MountainCarParams& p = dev.p;  // mountain_car.rs:35-40
-        p.min_position = -1.2f; p.max_position = 0.6f; p.max_speed = 0.07f;
-        p.goal_position = continuous ? 0.45f : 0.5f;
-        p.goal_velocity = cfg.goal_velocity;
-        p.force = continuous ? 0.0015f : 0.001f;
-        p.gravity = 0.0025f;
+        dev.p = mc_params(continuous, cfg.goal_velocity);
         return MGYM_OK;
     }
 
@@ -473,9 +486,14 @@ struct MountainCarEnv final : Env {
         dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
         const bool tl = dev.limit != 0u;
         if (vec_ok && n % 4 == 0 && n <= (1ull << 27) && use_step4) {  // the structured 16-byte kernel
-            with_bools([&](auto C, auto T, auto R) {
-                hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, decltype(R)::value, decltype(T)::value>), gv, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-            }, continuous, tl, dev.auto_reset != 0);
+            const uint64_t nb = (n + 4 * kBlock - 1) / (4 * kBlock);   // tiles
+            const bool one = nb <= (uint64_t)max_blocks;               // one block per tile: the single-pass form
+            const dim3 g((unsigned)(one ? nb : (uint64_t)max_blocks));
+            with_bools([&](auto C, auto T, auto R, auto O) {
+                hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, decltype(R)::value, decltype(T)::value, decltype(O)::value>), g, b, 0, stream, dev.pos,
+                                   (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc,
+                                   dev.limit, dev.p.goal_velocity);
+            }, continuous, tl, dev.auto_reset != 0, one);
             MGYM_HIP(hipGetLastError());
             return MGYM_OK;
         }

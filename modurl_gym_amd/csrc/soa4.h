@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace mgym {
 
@@ -25,6 +26,15 @@ template <typename T> __device__ __forceinline__ T* at(void* base, uint32_t byte
 __device__ __forceinline__ void nt_store4(float* p, float4 v) {
     f32x4 w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, reinterpret_cast<f32x4*>(p));
+}
+
+// Block cap of the classic step kernels, in kBlock-sized blocks: `compiled` (kMaxBlocks), or MGYM_CLASSIC_MAX_BLOCKS when that is lower (tuning
+// knob, read when a handle is created).  A population of no more tiles than the cap is stepped in the single-pass form (one block per tile), a
+// larger one in the grid-stride form: the knob brings the grid-stride form within reach of a few thousand environments.
+inline int classic_max_blocks(int compiled) {
+    const char* s = getenv("MGYM_CLASSIC_MAX_BLOCKS");
+    const int v = s ? atoi(s) : compiled;
+    return v < 1 ? 1 : (v > compiled ? compiled : v);
 }
 
 // a lane's four flags (0 / 1 each) as the four bytes of one word, environment k in byte k

@@ -1,8 +1,10 @@
 #!/bin/bash
 # Per-kernel registers / scratch / LDS of one .hip file of the engine, from the compiler's resource-usage remarks.
 #   tools/kernel_resources.sh lunar_lander.hip
+#   tools/kernel_resources.sh cartpole.hip -mllvm -amdgpu-kernarg-preload-count=14     (further compiler flags, e.g. the Makefile's per-object ones)
 cd "$(dirname "$0")/../modurl_gym_amd/csrc" || exit 1
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -c "$1" -o /tmp/kres_$$.o \
+F="$1"; shift
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math "$@" -c "$F" -o /tmp/kres_$$.o \
     -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c '
 import re, sys, subprocess
