@@ -18,7 +18,7 @@
  *    (reference: rank-1 f32 tensor of 4 / 2 / 8 per env — cartpole.rs:285-290,
  *    mountain_car.rs:315, lunar_lander.rs:1112-1123).
  *  - Discrete actions are uint32_t[n_envs] (reference: rank-0 u32 tensor,
- *    cartpole.rs:257,377); MountainCarContinuous takes float[n_envs].
+ *    cartpole.rs:257,377); MountainCarContinuous and Pendulum take float[n_envs].
  *  - reward f32, done/truncated uint8 (StepInfo, cartpole.rs:300-305).
  *  - Episode semantics are the reference's: NO auto-reset; stepping a finished env
  *    keeps integrating (cartpole.rs:330-346).  MGYM_FLAG_AUTO_RESET opts into a fused
@@ -61,8 +61,60 @@ typedef enum mgym_kind {
     MGYM_CARTPOLE = 0,         /* CartPoleV1      — src/classic_control/cartpole.rs */
     MGYM_MOUNTAINCAR = 1,      /* MountainCarV0   — src/classic_control/mountain_car.rs */
     MGYM_MOUNTAINCAR_CONT = 2, /* MountainCarContinuous-v0 — NOT in the reference (parity unpinned) */
-    MGYM_LUNARLANDER = 3       /* LunarLanderV3   — src/box_2d/lunar_lander.rs */
+    MGYM_LUNARLANDER = 3,      /* LunarLanderV3   — src/box_2d/lunar_lander.rs */
+    MGYM_PENDULUM = 4          /* Pendulum-v1 — NOT in the reference (parity unpinned); defined below */
 } mgym_kind;
+
+/* MGYM_PENDULUM = 4 is gymnasium's Pendulum-v1 with m = l = 1, dt = 0.05, max_speed = 8 and max_torque = 2.  It is not in the reference: parity
+ * unpinned, as for MGYM_MOUNTAINCAR_CONT.  Gymnasium integrates in float64; this engine is f32, so the f32 words are defined here exactly.  All
+ * arithmetic is f32, nothing is fused and nothing is reassociated.
+ *
+ * Constants:
+ *     PI_F  = 3.14159274f        TWO_PI_F = 6.28318548f
+ *     c_g   = 1.5f * g           one f32 multiply on the host
+ *  - g is mgym_config::gravity.
+ *  - mgym_default_config(MGYM_PENDULUM) sets gravity to 10.0f.
+ *  - mgym_create rejects a non-finite g with MGYM_ERR_BAD_CONFIG.
+ *  - The other config fields are ignored (max_episode_steps, flags and the batching / sharding fields mean what they mean for every family).
+ *
+ * State per environment: th, thdot, and a u32 episode number.  th is not wrapped and grows without bound, as in gymnasium.
+ * The observation is (cos th, sin th, thdot), using mg_cosf and mg_sinf (csrc/mgym_math.h), i.e. glibc's cosf and sinf.
+ *
+ * Step with action word a (an f32):
+ *     if a is NaN: sticky MGYM_ERR_INVALID_ACTION, reward 0, done 0, state untouched
+ *     u      = a < -2 ? -2 : (a > 2 ? 2 : a)
+ *     x      = th + PI_F
+ *     r      = fmodf(x, TWO_PI_F);  if (r < 0) r += TWO_PI_F      (fmod is exact by definition: every correct fmodf gives the same word)
+ *     an     = r - PI_F
+ *     cost   = (an*an + 0.1f*(thdot*thdot)) + 0.001f*(u*u)
+ *     acc    = c_g * sinf(th) + 3.0f * u
+ *     thdot' = clamp(thdot + acc * 0.05f, -8, 8)                  (the same compare form as u)
+ *     th'    = th + thdot' * 0.05f
+ *     obs    = (cosf(th'), sinf(th'), thdot');   reward = -cost;   done = 0 always
+ *  - The NaN case follows the MountainCarContinuous rule (+-inf is a valid action and clamps; under a time limit the elapsed count advances on every
+ *    step, a refused one included, as MountainCar's does).
+ *  - truncated and MGYM_FLAG_AUTO_RESET follow max_episode_steps exactly as they do for MountainCar: the limit is 0 (off, the default) or 1 .. 65535;
+ *    the count is a u16, saturating; the reset is fused in place on done | truncated.  Pendulum has no termination, so with the limit off an episode
+ *    never ends.  Gymnasium registers Pendulum-v1 with a limit of 200.
+ *
+ * Reset: the draw is env_draw(seed, env_id_base + i, episode, SLOT_RESET0) (csrc/philox.h), words w0 .. w3;
+ *     th = uniform_f64_to_f32(-pi, pi, w0, w1) and thdot = uniform_f64_to_f32(-1, 1, w2, w3), with pi the double M_PI
+ * (uniform_f64_to_f32(lo, hi, a, b) = (float)(u53(a, b) * (hi - lo) + lo) in f64, u53 the 53-bit uniform of every family's reset).  Then
+ * episode += 1 and elapsed = 0.  mgym_reset_deterministic sets th = 0, thdot = 0, so the observation is (1, 0, 0); mgym_create leaves that state too.
+ *
+ * mgym_get_spec: obs_dim 3, n_actions 0, action_is_float 1; action_low / action_high -2 / 2; obs_low / obs_high -+(1, 1, 8); state_cols 3.
+ * State blob: columns th, thdot, episode.  mgym_set_state recomputes the stored cos and sin and sets elapsed to 0.  mgym_get_elapsed_steps and
+ * mgym_set_elapsed_steps behave as for MountainCar.  mgym_observation is a zero-copy view: the engine keeps cos, sin, thdot as three adjacent
+ * columns with stride n_pad.
+ *
+ * Policies, all taking the observation held before the step, with actions_out holding f32 words:
+ *  - mgym_rollout_uniform: word g % 4 of Philox(key = policy_seed; counter = (g & ~3 lo, g & ~3 hi, uniform call count, 0x40000000 + t));
+ *    a = (float)(w >> 8) * 2^-22 - 2.0f, which is exact, over the multiples of 2^-22 in [-2, 2); n_envs and env_id_base must be multiples of 4.
+ *  - mgym_rollout_linear: policy holds 4 floats (w_cos, w_sin, w_thdot, b), and a = ((w0*c + w1*s) + w2*thdot) + b.  The step clamps a.
+ *  - mgym_rollout_mlp: D = 3, A = 1, and s_0 is the torque, exactly as in the MountainCarContinuous form.
+ *  - mgym_rollout_mlp_sample: MGYM_ERR_BAD_ARG before any launch (a Gaussian head is not implemented).
+ *  - The fused forms need n_envs to be a multiple of 4 and the buffers 16-byte aligned; mgym_rollout with an action table falls back to K steps
+ *    otherwise, as MountainCar's does. */
 
 enum {
     MGYM_FLAG_AUTO_RESET = 1u /* fused same-step reset of finished envs inside mgym_step (superset; default off) */
@@ -98,7 +150,7 @@ typedef struct mgym_config {
  * truncate, mountain_car.rs:324-329, lunar_lander.rs:1165; this is gymnasium's TimeLimit rule, and the one thing a caller of the fused
  * mgym_rollout* launches cannot add from outside).  0 = off: every output word and every step / rollout kernel is what it is without the field (MountainCar's reset and state-import
  * kernels additionally clear a 2-byte count per environment they touch).
- *   1 .. 65535: MountainCar, MountainCarContinuous, LunarLander.  Larger: MGYM_ERR_BAD_CONFIG.
+ *   1 .. 65535: MountainCar, MountainCarContinuous, Pendulum, LunarLander.  Larger: MGYM_ERR_BAD_CONFIG.
  *   CartPole keeps the reference's 500 (cartpole.rs:297): it accepts 0 and 500, which both mean what it does today, and rejects
  *   anything else with MGYM_ERR_BAD_CONFIG.
  * Every environment has an ELAPSED count of caller-visible steps since its last reset: 0 after mgym_reset / mgym_reset_done /
@@ -270,7 +322,7 @@ int mgym_rollout_mlp(mgym_env *env, const float *policy, int32_t hidden, int32_t
  * the conditions of mgym_rollout_mlp (n_envs a multiple of 4, 16-byte aligned buffers, CartPole K * n_envs below 2^30) plus env_id_base a multiple of 4.
  * LunarLander (A = 4): any n_envs, env_id_base a multiple of 4; always K x (a sampling policy kernel, mgym_step) — the persistent launch does not carry this
  * source, MGYM_LL_ROLLOUT_MLP changes nothing for this entry point and rollout_persistent_launches does not move.
- * MountainCarContinuous: MGYM_ERR_BAD_ARG (a Gaussian head is not implemented).
+ * MountainCarContinuous, Pendulum: MGYM_ERR_BAD_ARG (a Gaussian head is not implemented).
  * Errors are those of mgym_rollout_mlp, each message starting with "mgym_rollout_mlp_sample:".
  * Under graph capture the weights, the seed and the call word are frozen into the captured launches: a replay draws the same u again (on the state it
  * finds), so a loop that replays one graph does not explore — capture one graph per call word, or call eagerly. */
@@ -316,7 +368,7 @@ int mgym_set_state(mgym_env *env, const void *blob);
  * ordered on the handle's stream and capturable.
  *   LunarLander: the step counter of blob column 25 minus 1 (mgym_get_state / mgym_set_state go on carrying it; on import, plus 1);
  *   kept whether or not a limit is set.
- *   MountainCar(+Continuous): a counter of its own beside the 3-column blob; mgym_set_state sets it to 0, mgym_set_elapsed_steps
+ *   MountainCar(+Continuous), Pendulum: a counter of its own beside the 3-column blob; mgym_set_state sets it to 0, mgym_set_elapsed_steps
  *   overrides it, values above 65535 are clamped.  A handle WITHOUT a limit runs the kernels as they were, which do not touch the
  *   counter: it is 0 after a reset and is not advanced by steps.
  *   CartPole: MGYM_ERR_BAD_ARG (its counter is blob column 4). */

@@ -61,7 +61,7 @@ int mgym_abi_version(void) { return MGYM_ABI_VERSION; }
 
 int mgym_default_config(int kind, mgym_config* cfg) {
     if (!cfg) return bad_arg("mgym_default_config: cfg is NULL");
-    if (kind < MGYM_CARTPOLE || kind > MGYM_LUNARLANDER) return bad_arg("mgym_default_config: unknown kind");
+    if (kind < MGYM_CARTPOLE || kind > MGYM_PENDULUM) return bad_arg("mgym_default_config: unknown kind");
     memset(cfg, 0, sizeof *cfg);
     cfg->struct_size = (uint32_t)sizeof *cfg;
     cfg->kind = kind;
@@ -69,7 +69,7 @@ int mgym_default_config(int kind, mgym_config* cfg) {
     cfg->sutton_barto_reward = 0;  // cartpole.rs:39
     cfg->is_euler = 1;             // cartpole.rs:40
     cfg->goal_velocity = 0.0f;     // mountain_car.rs:33
-    cfg->gravity = -10.0f;         // lunar_lander.rs:282
+    cfg->gravity = kind == MGYM_PENDULUM ? 10.0f : -10.0f;  // lunar_lander.rs:282; Pendulum-v1: g = 10 (gymnasium)
     cfg->enable_wind = 0;          // :283
     cfg->wind_power = 15.0f;       // :284
     cfg->turbulence_power = 1.5f;  // :285
@@ -102,6 +102,12 @@ int mgym_get_spec(int kind, mgym_spec* s) {
         for (int k = 0; k < 8; ++k) { s->obs_high[k] = hi[k]; s->obs_low[k] = k < 6 ? -hi[k] : 0.0f; }
         break;
     }
+    case MGYM_PENDULUM: {  // gymnasium Pendulum-v1 (not in the reference): (cos th, sin th, thdot), Box(-2, 2) torque
+        s->obs_dim = 3; s->state_cols = 3; s->n_actions = 0; s->action_is_float = 1; s->action_low = -2.0f; s->action_high = 2.0f;
+        const float hi[3] = {1.0f, 1.0f, 8.0f};
+        for (int k = 0; k < 3; ++k) { s->obs_high[k] = hi[k]; s->obs_low[k] = -hi[k]; }
+        break;
+    }
     default:
         return bad_arg("mgym_get_spec: unknown kind");
     }
@@ -122,6 +128,12 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
         // lunar_lander.rs:292-296
         char buf[128];
         snprintf(buf, sizeof buf, "gravity (current value: %g) must be between -12 and 0", (double)cfg->gravity);
+        set_last_error(buf);
+        return MGYM_ERR_BAD_CONFIG;
+    }
+    if (cfg->kind == MGYM_PENDULUM && !__builtin_isfinite(cfg->gravity)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "gravity (current value: %g) must be finite for Pendulum", (double)cfg->gravity);
         set_last_error(buf);
         return MGYM_ERR_BAD_CONFIG;
     }
@@ -149,6 +161,7 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
     case MGYM_MOUNTAINCAR: impl = make_mountaincar(false); break;
     case MGYM_MOUNTAINCAR_CONT: impl = make_mountaincar(true); break;
     case MGYM_LUNARLANDER: impl = make_lunarlander(); break;
+    case MGYM_PENDULUM: impl = make_pendulum(); break;
     default: return bad_arg("mgym_create: unknown kind");
     }
     if (!impl) { set_last_error("mgym_create: environment family not available in this build"); return MGYM_ERR_BAD_CONFIG; }
@@ -291,6 +304,7 @@ int mgym_rollout_mlp_sample(mgym_env* env, const float* policy, int32_t hidden, 
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_mlp_sample: K < 0");
     if (e->cfg.kind == MGYM_MOUNTAINCAR_CONT) return bad_arg("mgym_rollout_mlp_sample: MountainCarContinuous has no discrete actions to draw from (a Gaussian head is not implemented)");
+    if (e->cfg.kind == MGYM_PENDULUM) return bad_arg("mgym_rollout_mlp_sample: Pendulum has no discrete actions to draw from (a Gaussian head is not implemented)");
     if (!policy) return bad_arg("mgym_rollout_mlp_sample: policy is NULL");
     if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp_sample: hidden must be between 1 and 64");
     if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp_sample: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
@@ -395,7 +409,7 @@ const char* mgym_last_error(void) { return g_last_error.c_str(); }
 int mgym_get_info(mgym_env* env, char* buf, size_t cap) {
     ENV_OR_FAIL(env);
     if (!buf || cap == 0) return bad_arg("mgym_get_info: buf is NULL or cap is 0");
-    static const char* const kinds[] = {"cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander"};
+    static const char* const kinds[] = {"cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander", "pendulum"};
     std::string out = std::string("kind=") + kinds[e->kind] + "\nn_envs=" + std::to_string(e->n) + "\ndevice=" + std::to_string(e->cfg.device) +
                       "\nauto_reset=" + ((e->cfg.flags & MGYM_FLAG_AUTO_RESET) ? "1" : "0") + "\nmax_episode_steps=" + std::to_string(e->cfg.max_episode_steps) +
                       "\nGPU_MAX_HW_QUEUES=" + e->hwq_env + "\n";

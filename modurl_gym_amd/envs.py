@@ -23,7 +23,7 @@ from . import _lib as L
 StepInfo = namedtuple("StepInfo", ["state", "reward", "done", "truncated"])  # modurl::gym::StepInfo
 
 KIND_NAMES = {L.CARTPOLE: "CartPoleV1", L.MOUNTAINCAR: "MountainCarV0",
-              L.MOUNTAINCAR_CONT: "MountainCarContinuousV0", L.LUNARLANDER: "LunarLanderV3"}
+              L.MOUNTAINCAR_CONT: "MountainCarContinuousV0", L.LUNARLANDER: "LunarLanderV3", L.PENDULUM: "PendulumV1"}
 
 
 class MgymError(RuntimeError):
@@ -122,7 +122,7 @@ class VecEnv:
     """n_envs environments of one family on one GPU (one mgym_env handle, one stream)."""
 
     def __init__(self, kind, n_envs=1, device=0, seed=0, env_id_base=0, auto_reset=False, stream=None,
-                 sutton_barto_reward=False, is_euler=True, goal_velocity=0.0, gravity=-10.0, enable_wind=False,
+                 sutton_barto_reward=False, is_euler=True, goal_velocity=0.0, gravity=None, enable_wind=False,
                  wind_power=15.0, turbulence_power=1.5, max_episode_steps=0):
         lib = L.load()
         cfg = L.Config()
@@ -131,7 +131,9 @@ class VecEnv:
         cfg.flags = L.FLAG_AUTO_RESET if auto_reset else 0
         cfg.sutton_barto_reward, cfg.is_euler = int(sutton_barto_reward), int(is_euler)
         cfg.goal_velocity = goal_velocity
-        cfg.gravity, cfg.enable_wind = gravity, int(enable_wind)
+        if gravity is not None:   # None: the family's default (LunarLander -10, Pendulum 10)
+            cfg.gravity = gravity
+        cfg.enable_wind = int(enable_wind)
         cfg.wind_power, cfg.turbulence_power = wind_power, turbulence_power
         # episode time limit (include/mgym.h): 0 = off, the reference's behaviour; CartPole keeps the reference's 500
         if not 0 <= int(max_episode_steps) <= 0xFFFFFFFF:
@@ -195,7 +197,7 @@ class VecEnv:
 
     def rollout_linear_device(self, policy, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device linear policy (mgym_rollout_linear): policy = obs_dim weights + bias (CartPole: action 1 if the score is
-        positive; MountainCarContinuous: the score is the force), or one such row per action (MountainCar: 3 rows, LunarLander: 4 rows of 8 weights + bias;
+        positive; MountainCarContinuous: the score is the force; Pendulum: (w_cos, w_sin, w_thdot, b), the score is the torque), or one such row per action (MountainCar: 3 rows, LunarLander: 4 rows of 8 weights + bias;
         the index of the largest score, the first of equal ones).  Host floats.  A policy of the wrong length raises PolicyShapeError (an MgymError with
         status ERR_BAD_ARG and a ValueError)."""
         rows = {L.MOUNTAINCAR: 3, L.LUNARLANDER: 4}.get(self.kind, 1)   # a row of (weights, bias) per action for the argmax families
@@ -225,7 +227,7 @@ class VecEnv:
         return self._rollout_host(K, lambda *out: self.rollout_linear_device(policy, K, *out))
 
     def mlp_dims(self):
-        """(D, A) of mgym_rollout_mlp for this family: obs_dim inputs; one score per action, or the one force of MountainCarContinuous"""
+        """(D, A) of mgym_rollout_mlp for this family: obs_dim inputs; one score per action, or the one force / torque of MountainCarContinuous / Pendulum"""
         return self.obs_dim, (1 if self.action_is_float else self.n_actions)
 
     def pack_mlp(self, w1, b1, w2, b2):
@@ -500,6 +502,15 @@ class MountainCarContinuousV0(_SingleEnv):
 
     def __init__(self, device=0, goal_velocity=0.0, seed=0, max_episode_steps=0):
         super().__init__(device, seed, goal_velocity=goal_velocity, max_episode_steps=max_episode_steps)
+
+
+class PendulumV1(_SingleEnv):
+    """Not in the reference; gymnasium's Pendulum-v1 in f32 as include/mgym.h defines it, parity unpinned.  gymnasium registers it with
+    max_episode_steps = 200; here the limit is off unless asked for, as for every family."""
+    KIND = L.PENDULUM
+
+    def __init__(self, device=0, g=10.0, seed=0, max_episode_steps=0):
+        super().__init__(device, seed, gravity=g, max_episode_steps=max_episode_steps)
 
 
 class LunarLanderV3(_SingleEnv):

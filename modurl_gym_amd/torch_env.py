@@ -6,7 +6,7 @@ without leaving the GPU or the torch stream:
     env = TorchVecEnv(mg.CARTPOLE, 1 << 20, auto_reset=True)
     obs = env.reset()                                  # torch.float32 [obs_dim, n]  (SoA, like the engine)
     for _ in range(T):
-        actions = policy(obs)                          # torch.int32 [n]  (float32 for MountainCarContinuous)
+        actions = policy(obs)                          # torch.int32 [n]  (float32 for MountainCarContinuous and Pendulum)
         obs, reward, done, truncated = env.step(actions)
     env.check()                                        # surfaces the sticky device status (invalid action ...)
 
@@ -143,7 +143,7 @@ class TorchVecEnv:
     def rollout_linear(self, policy, K):
         """K fused steps under the on-device linear policy (mgym_rollout_linear; `policy`: host floats or a tensor, the layout
         VecEnv.rollout_linear_device documents): returns (actions [K, n], obs [K, obs_dim, n], reward [K, n], done [K, n], truncated [K, n])
-        as fresh tensors, stream-ordered on torch's current stream (actions int32, float32 for MountainCarContinuous)."""
+        as fresh tensors, stream-ordered on torch's current stream (actions int32, float32 for MountainCarContinuous and Pendulum)."""
         self._bind_stream()
         if isinstance(policy, self._torch.Tensor):
             policy = policy.detach().to("cpu", self._torch.float32).numpy()   # (the weights are read on the host, during the call)
