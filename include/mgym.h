@@ -112,7 +112,8 @@ typedef enum mgym_kind {
  *    a = (float)(w >> 8) * 2^-22 - 2.0f, which is exact, over the multiples of 2^-22 in [-2, 2); n_envs and env_id_base must be multiples of 4.
  *  - mgym_rollout_linear: policy holds 4 floats (w_cos, w_sin, w_thdot, b), and a = ((w0*c + w1*s) + w2*thdot) + b.  The step clamps a.
  *  - mgym_rollout_mlp: D = 3, A = 1, and s_0 is the torque, exactly as in the MountainCarContinuous form.
- *  - mgym_rollout_mlp_sample: MGYM_ERR_BAD_ARG before any launch (a Gaussian head is not implemented).
+ *  - mgym_rollout_mlp_sample: MGYM_ERR_BAD_ARG before any launch (no discrete actions to draw from).
+ *  - mgym_rollout_mlp_gauss: D = 3, A = 1, the torque is s_0 + sigma * z (the text of that entry point); the step clamps it.
  *  - The fused forms need n_envs to be a multiple of 4 and the buffers 16-byte aligned; mgym_rollout with an action table falls back to K steps
  *    otherwise, as MountainCar's does. */
 
@@ -322,12 +323,68 @@ int mgym_rollout_mlp(mgym_env *env, const float *policy, int32_t hidden, int32_t
  * the conditions of mgym_rollout_mlp (n_envs a multiple of 4, 16-byte aligned buffers, CartPole K * n_envs below 2^30) plus env_id_base a multiple of 4.
  * LunarLander (A = 4): any n_envs, env_id_base a multiple of 4; always K x (a sampling policy kernel, mgym_step) — the persistent launch does not carry this
  * source, MGYM_LL_ROLLOUT_MLP changes nothing for this entry point and rollout_persistent_launches does not move.
- * MountainCarContinuous, Pendulum: MGYM_ERR_BAD_ARG (a Gaussian head is not implemented).
+ * MountainCarContinuous, Pendulum: MGYM_ERR_BAD_ARG — these have no discrete actions; their drawn form is mgym_rollout_mlp_gauss below.
  * Errors are those of mgym_rollout_mlp, each message starting with "mgym_rollout_mlp_sample:".
  * Under graph capture the weights, the seed and the call word are frozen into the captured launches: a replay draws the same u again (on the state it
  * finds), so a loop that replays one graph does not explore — capture one graph per call word, or call eagerly. */
 int mgym_rollout_mlp_sample(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, uint64_t policy_seed, uint32_t policy_call,
                             int32_t K, void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
+
+/* mgym_rollout_mlp for the two CONTINUOUS families with the action DRAWN from a diagonal Gaussian around the score: a = mu + sigma * z, sigma a
+ * state-independent standard deviation passed by the caller (the usual continuous PPO / A2C parameterisation; a second output row for a state-dependent
+ * sigma is not offered).  As in mgym_rollout_mlp with D = 2 (MountainCarContinuous) or 3 (Pendulum) and A = 1: the `policy` layout, hidden 1 .. 64,
+ * MGYM_ACT_RELU / MGYM_ACT_TANH, the fmaf chain from the bias on the observation held before the step, the output shapes, the conditions of the fused form
+ * (n_envs a multiple of 4, 16-byte aligned buffers), and the rule that the K steps equal K mgym_step calls fed the actions in actions_out, word for word,
+ * MGYM_FLAG_AUTO_RESET and mgym_config::max_episode_steps included.
+ *
+ * The action.  mu is the one score s_0.  a = mu + sigma * z: one f32 multiply, then one f32 add, nothing fused.  actions_out receives a BEFORE any clamp;
+ * the step clamps as it does for any action.  The learner needs the unclamped word for its log-probability and recovers z as (a - mu) / sigma in its own
+ * forward pass over obs_out and actions_out; as with mgym_rollout_mlp_sample no log-probabilities are returned.  sigma == 0 gives a = mu, the words of
+ * mgym_rollout_mlp (a -0 mu becomes +0: equal as a value).  A NaN mu gives a NaN action and the step's sticky MGYM_ERR_INVALID_ACTION.
+ *
+ * The draw of z.  A pure function of (policy_seed, policy_call, g, t), g = env_id_base + i the global environment id and t the step index within this call:
+ * independent of how a population is sharded over handles, and the handle keeps no count for it (the count of mgym_rollout_uniform calls is not touched) —
+ * pass a new policy_call (or seed) for each call that is to draw afresh; the same (seed, call) on the same state draws the same actions again.  One Philox
+ * evaluation serves four consecutive ids:
+ *
+ *   (w0, w1, w2, w3) = Philox4x32-10(key = policy_seed; counter = (lo32(g & ~3), hi32(g & ~3), policy_call, 0x60000000 + t))
+ *
+ * 0x60000000 is this entry point's own slot base (csrc/philox.h), disjoint from the uniform policy's 0x40000000 + ... and the categorical draw's
+ * 0x50000000 + ....  Environments with g % 4 in {0, 1} share the pair (wa, wb) = (w0, w1), those with g % 4 in {2, 3} the pair (w2, w3).  One Box-Muller
+ * transform per pair gives two independent normals: the even member of the pair takes the cosine branch, the odd member the sine branch.
+ *
+ *   k1 = wa >> 8;  k2 = wb >> 8                        24 bits each
+ *   n  = 2 * k1 + 1                                    odd, 1 .. 2^25 - 1;  u1 = n * 2^-25 lies in (0, 1), never 0 or 1
+ *   L  = mg_log_u25(n)                                 f64, ln(u1): defined below
+ *   q  = (float)(-2.0 * L)                             one f64 multiply, one rounding to f32
+ *   r  = sqrtf(q)                                      the correctly rounded f32 square root
+ *   phi = ((float)k2 * 2^-24f) * 6.28318548f           the first product is exact, one f32 rounding; phi in [0, 2 pi)
+ *   s, c = sinf(phi), cosf(phi)                        glibc's, bit for bit (mg_sinf / mg_cosf of csrc/mgym_math.h, any of its forms: all are word-equal)
+ *   z_even = r * c;   z_odd = r * s                    f32
+ *
+ * |z| <= sqrt(50 ln 2) = 5.88705 (k1 = 0), and the tails are resolved to 2^-25.
+ *
+ * mg_log_u25(n), all f64, every operation individually rounded (no fused multiply-add), so that a language without one restates it:
+ *
+ *   x = (double)n = m * 2^e with m in [1, 2) (read from the bits);  if (m > 0x1.6a09e667f3bcdp+0) { m = m * 0.5; e = e + 1; }
+ *   s  = (m - 1.0) / (m + 1.0)                         IEEE f64 division
+ *   s2 = s * s
+ *   p  = 2/15;  then for c in (2/13, 2/11, 2/9, 2/7, 2/5, 2/3, 2):  p = p * s2 + c        (each constant the nearest double)
+ *   p  = p * s
+ *   L  = (double)(e - 25) * 0x1.62e42fefa39efp-1 + p
+ *
+ * This is ln m = 2 atanh(s) as the odd series up to s^15 with |s| <= 0.1716: over all 2^24 values of k1 it stays within 3.4e-14 relative of a float64
+ * reference built from log / log1p (the first dropped term), there is no cancellation (when e = 25 the second term is all of L), and q > 0 always.  No
+ * library logarithm is used anywhere: none is defined to the word.
+ *
+ * Families: MountainCarContinuous and Pendulum, inside their fused rollout kernels, one Philox evaluation per lane per step serving the lane's four
+ * environments; env_id_base must be a multiple of 4.  Any other kind: MGYM_ERR_BAD_ARG ("... has discrete actions: use mgym_rollout_mlp_sample").
+ * sigma must be finite and >= 0: a NaN, an infinity or a negative value is MGYM_ERR_BAD_ARG naming sigma, before any launch.  The other errors are those
+ * of mgym_rollout_mlp, each message starting with "mgym_rollout_mlp_gauss:".
+ * Under graph capture the weights, sigma, the seed and the call word are frozen into the captured launch: a replay draws the same z again (on the state it
+ * finds) — capture one graph per call word, or call eagerly. */
+int mgym_rollout_mlp_gauss(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, float sigma, uint64_t policy_seed,
+                           uint32_t policy_call, int32_t K, void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
 
 /* Number of env-steps of this handle that returned done or truncated since mgym_create (StepInfo.done / .truncated,
  * cartpole.rs:300-305): accumulated inside the step kernels by __ballot/popcount reductions of the done mask,
@@ -443,6 +500,11 @@ int mgym_math_probe(int device, int fn, uint32_t first, uint64_t count, uint32_t
  * all device memory; count at most 2^31.  Runs on the null stream and synchronises the device.  tests/test_gpu_sample_probe.py compares with the
  * restatement of the text above. */
 int mgym_sample_probe(int device, int32_t n_actions, uint64_t count, const float *scores, const uint32_t *words, uint32_t *actions_out, float *cum_out);
+
+/* Test seam: the Box-Muller pair of mgym_rollout_mlp_gauss (mlp_gauss_pair of modurl_gym_amd/csrc/mlp_policy.h) evaluated on the device, one pair of Philox
+ * words (wa, wb) per lane: z_even_out and z_odd_out [count], and q_out [count] (q = -2 ln(u1) as an f32) or NULL; all device memory; count at most 2^31.
+ * Runs on the null stream and synchronises the device.  tests/test_gpu_gauss_probe.py compares with the host-compiled header. */
+int mgym_gauss_probe(int device, uint64_t count, const uint32_t *wa, const uint32_t *wb, float *z_even_out, float *z_odd_out, float *q_out);
 
 /* Test seam: LunarLander's collision-geometry primitives (modurl_gym_amd/csrc/ll_b2.h) evaluated on the device as pure functions,
  * one case per lane.  in and out are device memory, columns [cols][count] of 32-bit words; integer fields are bit patterns.  The

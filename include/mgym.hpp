@@ -74,6 +74,12 @@ class VecGym {
                             uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_mlp_sample(env_, policy, hidden, activation, policy_seed, policy_call, K, actions_out, obs, reward, done, trunc));
     }
+    // MountainCarContinuous and Pendulum: the action drawn from a Gaussian around the score, a = mu + sigma * z (mgym_rollout_mlp_gauss): sigma finite and >= 0, z a
+    // pure function of (policy_seed, policy_call, global env id, step); actions_out receives the f32 words before the step's clamp
+    void rollout_mlp_gauss(const float* policy, int hidden, int activation, float sigma, uint64_t policy_seed, uint32_t policy_call, int K, void* actions_out, float* obs,
+                           float* reward, uint8_t* done, uint8_t* trunc) {
+        check(mgym_rollout_mlp_gauss(env_, policy, hidden, activation, sigma, policy_seed, policy_call, K, actions_out, obs, reward, done, trunc));
+    }
     void rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_uniform(env_, policy_seed, K, actions_out, obs, reward, done, trunc));
     }

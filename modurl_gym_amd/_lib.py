@@ -52,6 +52,7 @@ PROTOTYPES = {
     "mgym_rollout_linear": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_rollout_mlp": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_rollout_mlp_sample": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "mgym_rollout_mlp_gauss": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_episode_count": (C.c_int, [_vp, _u64p]),
     "mgym_observation": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "mgym_observation_aos": (C.c_int, [_vp, _vp]),
@@ -74,6 +75,7 @@ PROTOTYPES = {
     "mgym_selftest_cartpole_math": (C.c_int, [C.c_int, _u64p]),
     "mgym_math_probe": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint64, _vp]),
     "mgym_sample_probe": (C.c_int, [C.c_int, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "mgym_gauss_probe": (C.c_int, [C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "mgym_ll_geom_probe": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _vp, _vp]),
     "mgym_graph_begin": (C.c_int, [_vp]),
     "mgym_graph_end": (C.c_int, [_vp, C.POINTER(_vp)]),

@@ -313,6 +313,23 @@ int mgym_rollout_mlp_sample(mgym_env* env, const float* policy, int32_t hidden, 
                              K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
+int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, float sigma, uint64_t policy_seed, uint32_t policy_call, int32_t K,
+                           void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
+    ENV_OR_FAIL(env);
+    if (K < 0) return bad_arg("mgym_rollout_mlp_gauss: K < 0");
+    if (e->cfg.kind != MGYM_MOUNTAINCAR_CONT && e->cfg.kind != MGYM_PENDULUM) {
+        static const char* const names[] = {"CartPole", "MountainCar", "", "LunarLander"};
+        return bad_arg((std::string("mgym_rollout_mlp_gauss: ") + names[e->cfg.kind] + " has discrete actions: use mgym_rollout_mlp_sample").c_str());
+    }
+    if (!policy) return bad_arg("mgym_rollout_mlp_gauss: policy is NULL");
+    if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp_gauss: hidden must be between 1 and 64");
+    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp_gauss: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
+    if (!(sigma >= 0.0f) || sigma > 3.402823466e+38f) return bad_arg("mgym_rollout_mlp_gauss: sigma must be finite and >= 0");   // (a NaN fails the first test)
+    if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_gauss: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
+    return e->rollout_policy(PolicyCall{activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH_GAUSS : ROLL_ACT_MLP_RELU_GAUSS, "mgym_rollout_mlp_gauss", policy, hidden, policy_seed, policy_call, sigma},
+                             K, actions_out, obs_out, reward_out, done_out, trunc_out);
+}
+
 int mgym_episode_count(mgym_env* env, uint64_t* finished) {
     ENV_OR_FAIL(env);
     if (!finished) return bad_arg("mgym_episode_count: NULL");

@@ -1,6 +1,6 @@
-// mlp_policy.h — the one-hidden-layer policy of mgym_rollout_mlp and mgym_rollout_mlp_sample (include/mgym.h), shared by the rollout kernels of CartPole and MountainCar
-// (cartpole.hip, mountain_car.hip: the lane's four environments), LunarLander's policy kernel (lunar_lander.hip: one environment per lane) and the
-// host check tests/native/mlp_policy_check.cpp, which compiles this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
+// mlp_policy.h — the one-hidden-layer policy of mgym_rollout_mlp, mgym_rollout_mlp_sample and mgym_rollout_mlp_gauss (include/mgym.h), shared by the rollout
+// kernels of CartPole, MountainCar and Pendulum (cartpole.hip, mountain_car.hip, pendulum.hip: the lane's four environments), LunarLander's policy kernel
+// (lunar_lander.hip: one environment per lane) and the host checks tests/native/mlp_policy_check.cpp, mlp_sample_check.cpp and mlp_gauss_check.cpp, which compile this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
 // -ffp-contract=off: the only fused operations are the cp_fmaf of the two chains.
 //
 //   pre_j = b1[j];  q = 0 .. D-1 ascending:  pre_j = fmaf(W1[j][q], o[q], pre_j)
@@ -151,6 +151,66 @@ MG_HD void mlp_actions(const MlpPack<D, A>& p, const float (&o)[N][D], const uin
     mlp_scores<D, A, ACT, N>(p, o, s);
 #pragma unroll
     for (int k = 0; k < N; ++k) act[k] = mlp_sample<A>(s[k], w[k]);
+}
+
+// ---- mgym_rollout_mlp_gauss: the one score is the mean of a Gaussian, a = mu + sigma * z (include/mgym.h, "The draw of z") ----
+// One Box-Muller transform turns a pair of Philox words into two independent normals, r cos(phi) for the even member of an environment pair and r sin(phi)
+// for the odd one, with r = sqrt(-2 ln u1).  The logarithm is the project's own: no library's log is defined to the word, and this one is a handful of
+// individually rounded f64 operations that numpy restates.
+
+// ln(n 2^-25) for an odd n in 1 .. 2^25 - 1, in f64: n = m 2^e with m in (sqrt(1/2), sqrt(2)], s = (m - 1) / (m + 1), ln m = 2 atanh(s) as the odd series up
+// to s^15 (|s| <= 0.1716: the first dropped term is 3.3e-14 of the result), Horner in s^2 from 2/15 down to 2, then (e - 25) ln2 + that.  Nothing fused; when
+// e = 25 the first product is 0 and the series is all of L, so nothing cancels.
+MG_HD double mg_log_u25(uint32_t n) {
+    int e = 31 - __builtin_clz(n);
+    double m = (double)(n << (24 - e)) * 0x1p-24;   // the mantissa of (double)n, in [1, 2): both steps exact
+    if (m > 0x1.6a09e667f3bcdp+0) { m *= 0.5; e += 1; }
+    const double s = (m - 1.0) / (m + 1.0);
+    const double s2 = s * s;
+    double p = 2.0 / 15.0;
+    p = p * s2 + 2.0 / 13.0;
+    p = p * s2 + 2.0 / 11.0;
+    p = p * s2 + 2.0 / 9.0;
+    p = p * s2 + 2.0 / 7.0;
+    p = p * s2 + 2.0 / 5.0;
+    p = p * s2 + 2.0 / 3.0;
+    p = p * s2 + 2.0;
+    p = p * s;
+    return (double)(e - 25) * 0x1.62e42fefa39efp-1 + p;
+}
+
+// q = -2 ln(u1) as an f32, u1 = (2 (wa >> 8) + 1) 2^-25 in (0, 1): one f64 multiply, one rounding to f32; 5.96e-8 <= q <= 34.66
+MG_HD float mlp_gauss_q(uint32_t wa) { return (float)(-2.0 * mg_log_u25(2u * (wa >> 8) + 1u)); }
+
+// the correctly rounded f32 square root (hipcc's default for gfx950, sqrtss on the host)
+MG_HD float mlp_sqrtf(float x) { return __builtin_sqrtf(x); }
+
+// the two normals of one pair of words
+MG_HD void mlp_gauss_pair(uint32_t wa, uint32_t wb, float* z_even, float* z_odd) {
+    const float r = mlp_sqrtf(mlp_gauss_q(wa));
+    const float phi = ((float)(wb >> 8) * 5.9604644775390625e-08f) * 6.28318548f;   // at most (1 - 2^-24) * 6.28318548f, below 2 pi
+    // so mg_sincosf_u (word-equal to mg_sinf / mg_cosf) always takes its lock-step form for |y| < 120; saying so drops its out-of-line path for larger
+    // arguments from these kernels, which hands its two results back through memory and would be their only scratch
+    if (!(abstop12(phi) < abstop12(120.0f))) __builtin_unreachable();
+    float s, c;
+    mg_sincosf_u(phi, &s, &c);
+    *z_even = r * c;
+    *z_odd = r * s;
+}
+
+// the GAUSS form of mlp_actions, N = 4: the lane's four environments (global ids g .. g + 3, g a multiple of 4) take the four normals of one Philox block w —
+// (w0, w1) for the first pair, (w2, w3) for the second — and the action word is that of mu + sigma * z, an f32 multiply and an f32 add, before any clamp
+template <int D, int ACT>
+MG_HD void mlp_actions(const MlpPack<D, 1>& p, const float (&o)[4][D], const uint32_t (&w)[4], float sigma, uint32_t (&act)[4]) {
+    float mu[4][1];
+    mlp_scores<D, 1, ACT, 4>(p, o, mu);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        float ze, zo;
+        mlp_gauss_pair(w[2 * h], w[2 * h + 1], &ze, &zo);
+        act[2 * h] = as_u32(mu[2 * h][0] + sigma * ze);
+        act[2 * h + 1] = as_u32(mu[2 * h + 1][0] + sigma * zo);
+    }
 }
 
 }  // namespace mgym

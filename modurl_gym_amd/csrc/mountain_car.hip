@@ -279,11 +279,13 @@ struct McUniformPolicy { uint64_t seed; uint32_t call; };
 // mgym_rollout_mlp: the weight pack of mlp_policy.h (A = 3 scores, or the one force of MountainCarContinuous) takes the place of the linear words in the
 // kernel's arguments; the other policies' instantiations keep the arguments they had
 template <bool CONT, int POLICY> using McPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<2, CONT ? 1 : 3>, McLinearPolicy>;
+// mgym_rollout_mlp_gauss (MountainCarContinuous only): sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
+template <int POLICY> using McDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, McUniformPolicy>;
 template <bool CONT, int POLICY = ROLL_ACT_TABLE, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
                            uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, McPolicyArg<CONT, POLICY> lin = {}, uint32_t* __restrict__ act_out = nullptr,
-                           McUniformPolicy uni = McUniformPolicy{}) {
+                           McDrawArg<POLICY> uni = {}) {
     constexpr bool LINEAR = POLICY == ROLL_ACT_LINEAR;
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -319,6 +321,11 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                     static_assert(!CONT, "MountainCarContinuous has no categorical draw");
                     const Philox4 w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
                     mlp_actions<2, 3, ACT, 4>(lin, o, w.w, a);
+                } else if constexpr (roll_act_gauss(POLICY)) {
+                    // mgym_rollout_mlp_gauss (Box(-1, 1) only): one Philox evaluation per lane per step, its two word pairs for the lane's two env pairs
+                    static_assert(CONT, "MountainCar has discrete actions: no Gaussian draw");
+                    const Philox4 w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_GAUSS + (uint32_t)t);
+                    mlp_actions<2, ACT>(lin, o, w.w, uni.sigma, a);
                 } else {
                     mlp_actions<2, CONT ? 1 : 3, ACT, CONT, 4>(lin, o, a);
                 }
@@ -504,10 +511,10 @@ struct MountainCarEnv final : Env {
         return MGYM_OK;
     }
 
-    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear weights or the hidden-layer pack, `uni`: the uniform stream
+    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear weights or the hidden-layer pack, `uni`: the uniform stream, or the Gaussian draw's sigma, seed and call word
     template <int POLICY, bool CONT, bool TL>
     void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
-                        const McPolicyArg<CONT, POLICY>& arg = McPolicyArg<CONT, POLICY>{}, McUniformPolicy uni = McUniformPolicy{}) {
+                        const McPolicyArg<CONT, POLICY>& arg = McPolicyArg<CONT, POLICY>{}, McDrawArg<POLICY> uni = {}) {
         hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
@@ -541,6 +548,14 @@ struct MountainCarEnv final : Env {
             default: {   // the hidden-layer sources
                 MlpPack<2, CONT ? 1 : 3> pack;
                 mlp_pack<2, CONT ? 1 : 3>(call.weights, call.hidden, pack);
+                if (roll_act_gauss(call.source)) {   // (the C ABI rejects mgym_rollout_mlp_gauss on discrete MountainCar)
+                    if constexpr (CONT) {
+                        const GaussDraw g{call.seed, call.call, call.sigma};
+                        if (roll_act_mlp_tanh(call.source)) launch_rollout<ROLL_ACT_MLP_TANH_GAUSS, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
+                        else launch_rollout<ROLL_ACT_MLP_RELU_GAUSS, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
+                    }
+                    break;
+                }
                 with_bools([&](auto H, auto S) {
                     constexpr bool TANH = decltype(H)::value;
                     if constexpr (!decltype(S)::value) launch_rollout<TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);

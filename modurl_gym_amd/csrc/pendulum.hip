@@ -228,11 +228,13 @@ pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 // The policies decide from (cos, sin, thdot) held before the step (pendulum_step.h); actions_out holds f32 words.
 struct PdUniformPolicy { uint64_t seed; uint32_t call; };
 template <int POLICY> using PdPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<3, 1>, PdLinearPolicy>;
+// mgym_rollout_mlp_gauss: sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
+template <int POLICY> using PdDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, PdUniformPolicy>;
 template <int POLICY = ROLL_ACT_TABLE, bool TL = false>
 __global__ void __launch_bounds__(kBlock)
 pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
                         uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, PdPolicyArg<POLICY> pol = {}, uint32_t* __restrict__ act_out = nullptr,
-                        PdUniformPolicy uni = PdUniformPolicy{}) {
+                        PdDrawArg<POLICY> uni = {}) {
     static_assert(!roll_act_samples(POLICY), "Pendulum has no categorical draw");
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -250,6 +252,10 @@ pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, 
             uint32_t a[4];
             if constexpr (POLICY == ROLL_ACT_UNIFORM) {
                 pendulum_uniform_actions(uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, a);
+            } else if constexpr (roll_act_gauss(POLICY)) {
+                // mgym_rollout_mlp_gauss: one Philox evaluation per lane per step, its two word pairs for the lane's two env pairs
+                const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
+                pendulum_gauss_actions<roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU>(pol, o, uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, uni.sigma, a);
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
                 pendulum_mlp_actions<roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU, 4>(pol, o, a);
@@ -434,10 +440,10 @@ struct PendulumEnv final : Env {
         return MGYM_OK;
     }
 
-    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream
+    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the Gaussian draw's sigma, seed and call word
     template <int POLICY, bool TL>
     void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
-                        const PdPolicyArg<POLICY>& arg = PdPolicyArg<POLICY>{}, PdUniformPolicy uni = PdUniformPolicy{}) {
+                        const PdPolicyArg<POLICY>& arg = PdPolicyArg<POLICY>{}, PdDrawArg<POLICY> uni = {}) {
         hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
@@ -467,7 +473,10 @@ struct PendulumEnv final : Env {
             default: {   // the hidden-layer sources
                 MlpPack<3, 1> pack;
                 mlp_pack<3, 1>(call.weights, call.hidden, pack);
-                if (roll_act_mlp_tanh(call.source)) launch_rollout<ROLL_ACT_MLP_TANH, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
+                const GaussDraw g{call.seed, call.call, call.sigma};
+                if (call.source == ROLL_ACT_MLP_TANH_GAUSS) launch_rollout<ROLL_ACT_MLP_TANH_GAUSS, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
+                else if (call.source == ROLL_ACT_MLP_RELU_GAUSS) launch_rollout<ROLL_ACT_MLP_RELU_GAUSS, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
+                else if (roll_act_mlp_tanh(call.source)) launch_rollout<ROLL_ACT_MLP_TANH, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
                 else launch_rollout<ROLL_ACT_MLP_RELU, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
             }
             }

@@ -106,4 +106,13 @@ MG_HD uint32_t pendulum_linear_action(const PdLinearPolicy& p, float cs, float s
 template <int ACT, int N>
 MG_HD void pendulum_mlp_actions(const MlpPack<3, 1>& p, const float (&o)[N][3], uint32_t (&a)[N]) { mlp_actions<3, 1, ACT, true, N>(p, o, a); }
 
+// mgym_rollout_mlp_gauss: the torque is s_0 + sigma * z, the four envs with global ids g .. g + 3 (g a multiple of 4) taking the four normals of one Philox
+// block keyed by the policy seed, counter (g lo, g hi, call, SLOT_POLICY_GAUSS + t) (mlp_policy.h's GAUSS form; the step clamps the torque)
+template <int ACT>
+__device__ __forceinline__ void pendulum_gauss_actions(const MlpPack<3, 1>& p, const float (&o)[4][3], uint64_t policy_seed, uint32_t call, uint64_t g, uint32_t t, float sigma,
+                                                       uint32_t (&a)[4]) {
+    const Philox4 b = env_draw(policy_seed, g, call, SLOT_POLICY_GAUSS + t);
+    mlp_actions<3, ACT>(p, o, b.w, sigma, a);
+}
+
 }  // namespace mgym

@@ -11,25 +11,33 @@ namespace mgym {
 //   MLP_RELU / MLP_TANH  as LINEAR, decided by mlp_policy.h's one-hidden-layer policy (mgym_rollout_mlp)
 //   MLP_RELU_SAMPLE / MLP_TANH_SAMPLE  the same scores, the action drawn from their softmax with a Philox word keyed by (policy seed, global env id, the
 //             caller's call word, step) (mgym_rollout_mlp_sample).  New sources, not a flag: the instantiations of the others keep their code.
+//   MLP_RELU_GAUSS / MLP_TANH_GAUSS  the continuous families' one score as the mean of a Gaussian: the action is mu + sigma * z, z a Box-Muller normal from a
+//             Philox block keyed the same way (mgym_rollout_mlp_gauss).  New sources again, for the same reason.
 // How LunarLander's persistent launch carries each of them: ll_roll_types.h.
 enum { ROLL_ACT_TABLE = 0, ROLL_ACT_LINEAR = 1, ROLL_ACT_UNIFORM = 2, ROLL_ACT_MLP_RELU = 3, ROLL_ACT_MLP_TANH = 4, ROLL_ACT_MLP_RELU_SAMPLE = 5,
-       ROLL_ACT_MLP_TANH_SAMPLE = 6 };
-// the hidden-layer sources that draw their action (LunarLander's persistent launch carries none of them)
+       ROLL_ACT_MLP_TANH_SAMPLE = 6, ROLL_ACT_MLP_RELU_GAUSS = 7, ROLL_ACT_MLP_TANH_GAUSS = 8 };
+// the hidden-layer sources that draw their action from the categorical distribution (LunarLander's persistent launch carries none of them)
 constexpr bool roll_act_samples(int source) { return source == ROLL_ACT_MLP_RELU_SAMPLE || source == ROLL_ACT_MLP_TANH_SAMPLE; }
+// the hidden-layer sources that draw a continuous action around their score (MountainCarContinuous and Pendulum only)
+constexpr bool roll_act_gauss(int source) { return source == ROLL_ACT_MLP_RELU_GAUSS || source == ROLL_ACT_MLP_TANH_GAUSS; }
 // the hidden-layer sources, and whether their activation is tanh
-constexpr bool roll_act_is_mlp(int source) { return source == ROLL_ACT_MLP_RELU || source == ROLL_ACT_MLP_TANH || roll_act_samples(source); }
-constexpr bool roll_act_mlp_tanh(int source) { return source == ROLL_ACT_MLP_TANH || source == ROLL_ACT_MLP_TANH_SAMPLE; }
+constexpr bool roll_act_is_mlp(int source) { return source == ROLL_ACT_MLP_RELU || source == ROLL_ACT_MLP_TANH || roll_act_samples(source) || roll_act_gauss(source); }
+constexpr bool roll_act_mlp_tanh(int source) { return source == ROLL_ACT_MLP_TANH || source == ROLL_ACT_MLP_TANH_SAMPLE || source == ROLL_ACT_MLP_TANH_GAUSS; }
 // the sources that decide from the observation
 constexpr bool roll_act_observes(int source) { return source == ROLL_ACT_LINEAR || roll_act_is_mlp(source); }
 
-// One call of mgym_rollout_uniform / _linear / _mlp / _mlp_sample as the C ABI hands it to Env::rollout_policy, its own argument checks passed.
+// One call of mgym_rollout_uniform / _linear / _mlp / _mlp_sample / _mlp_gauss as the C ABI hands it to Env::rollout_policy, its own argument checks passed.
 struct PolicyCall {
     int source;             // ROLL_ACT_UNIFORM, ROLL_ACT_LINEAR or one of the ROLL_ACT_MLP_* sources
     const char* api;        // the entry point's name: the prefix of every error message
     const float* weights;   // LINEAR: obs_dim weights + bias per score; MLP_*: W1[H][D], b1[H], W2[A][H], b2[A] (host floats); UNIFORM: null
     int hidden;             // MLP_*: H
-    uint64_t seed;          // UNIFORM, MLP_*_SAMPLE: the policy seed
-    uint32_t call;          // MLP_*_SAMPLE: the caller's call word (UNIFORM counts its calls on the handle instead)
+    uint64_t seed;          // UNIFORM, MLP_*_SAMPLE, MLP_*_GAUSS: the policy seed
+    uint32_t call;          // MLP_*_SAMPLE, MLP_*_GAUSS: the caller's call word (UNIFORM counts its calls on the handle instead)
+    float sigma;            // MLP_*_GAUSS: the standard deviation, finite and >= 0
 };
+
+// what a drawing hidden-layer source takes beside its MlpPack as a kernel argument
+struct GaussDraw { uint64_t seed; uint32_t call; float sigma; };
 
 }  // namespace mgym

@@ -187,6 +187,19 @@ __global__ void __launch_bounds__(256) sample_probe_kernel(uint64_t count, const
     }
 }
 
+// mlp_policy.h's Box-Muller pair for one pair of Philox words per lane (mgym_gauss_probe): the two normals, and q = -2 ln(u1) as an f32 if asked
+__global__ void __launch_bounds__(256) gauss_probe_kernel(uint64_t count, const uint32_t* __restrict__ wa, const uint32_t* __restrict__ wb, float* __restrict__ z_even,
+                                                          float* __restrict__ z_odd, float* __restrict__ q) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        float ze, zo;
+        mlp_gauss_pair(wa[i], wb[i], &ze, &zo);
+        z_even[i] = ze;
+        z_odd[i] = zo;
+        if (q) q[i] = mlp_gauss_q(wa[i]);
+    }
+}
+
 // one case per lane (ll_geom_probe.h).  As in every product kernel the polygon table and collide_edge_polygon's per-lane buffer are
 // LDS: that function casts both to the LDS address space.
 constexpr int kGeomBlock = 64;
@@ -251,6 +264,24 @@ extern "C" int mgym_sample_probe(int device, int32_t n_actions, uint64_t count, 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (prev >= 0) (void)hipSetDevice(prev);
     if (e != hipSuccess) return hip_fail(e, "sample_probe", __FILE__, __LINE__);
+    return MGYM_OK;
+}
+
+extern "C" int mgym_gauss_probe(int device, uint64_t count, const uint32_t* wa, const uint32_t* wb, float* z_even_out, float* z_odd_out, float* q_out) {
+    if (count == 0 || count > (1ull << 31) || !wa || !wb || !z_even_out || !z_odd_out) {
+        set_last_error("mgym_gauss_probe: a case count of 0 or above 2^31, or NULL wa, wb, z_even_out or z_odd_out");
+        return MGYM_ERR_BAD_ARG;
+    }
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    MGYM_HIP(hipSetDevice(device));
+    const uint64_t blocks = (count + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536)), block(256);
+    hipLaunchKernelGGL(gauss_probe_kernel, grid, block, 0, nullptr, count, wa, wb, z_even_out, z_odd_out, q_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return hip_fail(e, "gauss_probe", __FILE__, __LINE__);
     return MGYM_OK;
 }
 

@@ -270,6 +270,15 @@ class VecEnv:
         _check(self._lib.mgym_rollout_mlp_sample(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, int(seed) & (2**64 - 1),
                                                  int(call) & 0xFFFFFFFF, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out), _ptr(trunc_out)))
 
+    def rollout_mlp_gauss_device(self, policy, hidden, activation, sigma, seed, call, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
+        """rollout_mlp_device for MountainCarContinuous and Pendulum with the action drawn from a Gaussian around the score (mgym_rollout_mlp_gauss):
+        a = mu + sigma * z, `sigma` finite and >= 0, z a pure function of (seed, call, global env id, step) — include/mgym.h states it to the word.
+        actions_out receives a before the step's clamp.  The handle keeps no count: pass a new `call` (a 32-bit word) for each call that is to draw afresh."""
+        pol, act = self._mlp_args(policy, hidden, activation)
+        _check(self._lib.mgym_rollout_mlp_gauss(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, float(sigma),
+                                                int(seed) & (2**64 - 1), int(call) & 0xFFFFFFFF, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out),
+                                                _ptr(done_out), _ptr(trunc_out)))
+
     def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc); actions float32 for MountainCarContinuous"""
         policy, H = self.pack_mlp(w1, b1, w2, b2)
@@ -279,6 +288,11 @@ class VecEnv:
         """host-array form of rollout_mlp_sample_device: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""
         policy, H = self.pack_mlp(w1, b1, w2, b2)
         return self._rollout_host(K, lambda *out: self.rollout_mlp_sample_device(policy, H, activation, seed, call, K, *out), self.action_dtype)
+
+    def rollout_mlp_gauss(self, w1, b1, w2, b2, K, sigma, seed, call=0, activation="relu"):
+        """host-array form of rollout_mlp_gauss_device: -> (actions [K, n] float32, obs [K, obs_dim, n], reward [K, n], done, trunc)"""
+        policy, H = self.pack_mlp(w1, b1, w2, b2)
+        return self._rollout_host(K, lambda *out: self.rollout_mlp_gauss_device(policy, H, activation, sigma, seed, call, K, *out), np.float32)
 
     def rollout_uniform(self, policy_seed, K):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""

@@ -176,6 +176,19 @@ class TorchVecEnv:
         self.env.rollout_mlp_sample_device(policy, H, activation, seed, call, K, act, obs, rew, done, trunc)
         return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
 
+    def rollout_mlp_gauss(self, w1, b1, w2, b2, K, sigma, seed, call=0, activation="relu"):
+        """rollout_mlp for MountainCarContinuous and Pendulum with the action drawn from a Gaussian around the score, a = mu + sigma * z with a
+        state-independent `sigma` >= 0 (mgym_rollout_mlp_gauss) — the collector of a continuous-control on-policy trainer.  z is a pure function of (seed,
+        call, global env id, step): pass a new `call` for each call that is to draw afresh.  Returns (actions, obs, reward, done, truncated) like rollout_mlp;
+        the actions are float32 and not clamped (the step clamps), so the learner's forward pass over obs and actions gives the log-probabilities."""
+        self._bind_stream()
+        host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2)]
+        policy, H = self.env.pack_mlp(*host)
+        K = int(K)
+        act, obs, rew, done, trunc = self._policy_outputs(K)
+        self.env.rollout_mlp_gauss_device(policy, H, activation, float(sigma), seed, call, K, act, obs, rew, done, trunc)
+        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+
     def rollout_uniform(self, seed, K):
         """K fused steps under the on-device uniform random policy (mgym_rollout_uniform, include/mgym.h): returns (actions, obs, reward,
         done, truncated) like rollout_linear."""

@@ -146,6 +146,21 @@ unsafe extern "C" {
         done_out: *mut u8,
         trunc_out: *mut u8,
     ) -> c_int;
+    pub fn mgym_rollout_mlp_gauss(
+        env: *mut mgym_env,
+        policy: *const f32,
+        hidden: i32,
+        activation: i32,
+        sigma: f32,
+        policy_seed: u64,
+        policy_call: u32,
+        k: i32,
+        actions_out: *mut c_void,
+        obs_out: *mut f32,
+        reward_out: *mut f32,
+        done_out: *mut u8,
+        trunc_out: *mut u8,
+    ) -> c_int;
     pub fn mgym_episode_count(env: *mut mgym_env, finished: *mut u64) -> c_int;
     pub fn mgym_selftest_cartpole_math(device: c_int, mismatches: *mut u64) -> c_int;
     pub fn mgym_math_probe(device: c_int, fn_: c_int, first: u32, count: u64, out: *mut u32) -> c_int;
@@ -157,6 +172,15 @@ unsafe extern "C" {
         words: *const u32,
         actions_out: *mut u32,
         cum_out: *mut f32,
+    ) -> c_int;
+    pub fn mgym_gauss_probe(
+        device: c_int,
+        count: u64,
+        wa: *const u32,
+        wb: *const u32,
+        z_even_out: *mut f32,
+        z_odd_out: *mut f32,
+        q_out: *mut f32,
     ) -> c_int;
     pub fn mgym_ll_geom_probe(device: c_int, fn_: c_int, count: u64, in_: *const f32, out: *mut f32) -> c_int;
     pub fn mgym_observation(env: *mut mgym_env, obs: *mut *const f32, col_stride: *mut u64) -> c_int;

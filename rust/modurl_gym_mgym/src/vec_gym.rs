@@ -226,6 +226,38 @@ impl VecGym {
         }
         check(unsafe { mgym_rollout_mlp_sample(self.env, policy.as_ptr(), hidden, activation, policy_seed, policy_call, k, actions_out, obs, reward, done, truncated) })
     }
+    /// `rollout_mlp` for MountainCarContinuous and Pendulum with the action drawn from a Gaussian around the score (`mgym_rollout_mlp_gauss`): a = mu + sigma * z,
+    /// `sigma` finite and >= 0, z a pure function of (`policy_seed`, `policy_call`, global env id, step) as `include/mgym.h` states it to the word; the handle keeps
+    /// no count, so pass a new `policy_call` for each call that is to draw afresh.  `actions_out` receives the f32 words before the step's clamp.  The discrete
+    /// families: `MGYM_ERR_BAD_ARG`; `env_id_base` a multiple of 4.
+    /// # Safety
+    /// the output pointers are device pointers of `[K][n]` (`[K][obs_dim][n]` for `obs`) elements, or null.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn rollout_mlp_gauss(
+        &mut self,
+        policy: &[f32],
+        hidden: i32,
+        activation: i32,
+        sigma: f32,
+        policy_seed: u64,
+        policy_call: u32,
+        k: i32,
+        actions_out: *mut c_void,
+        obs: *mut f32,
+        reward: *mut f32,
+        done: *mut u8,
+        truncated: *mut u8,
+    ) -> Result<(), MgymError> {
+        let d = self.spec.obs_dim as usize;
+        if (1..=64).contains(&hidden) {
+            let h = hidden as usize;
+            let want = h * (d + 1) + (h + 1);
+            if policy.len() != want {
+                return Err(MgymError { status: MGYM_ERR_BAD_ARG, message: format!("rollout_mlp_gauss: {} policy floats for hidden = {}, got {}", want, hidden, policy.len()) });
+            }
+        }
+        check(unsafe { mgym_rollout_mlp_gauss(self.env, policy.as_ptr(), hidden, activation, sigma, policy_seed, policy_call, k, actions_out, obs, reward, done, truncated) })
+    }
     /// K fused steps under the on-device uniform random policy (`mgym_rollout_uniform`; every family, the draws as `include/mgym.h` documents them): no action table.
     /// `actions_out` (`[K][n]` u32, may be null) receives the drawn actions.
     #[allow(clippy::too_many_arguments)]
