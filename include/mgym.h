@@ -163,7 +163,8 @@ typedef struct mgym_config {
  * Without MGYM_FLAG_AUTO_RESET an environment stepped past its limit keeps integrating and reports truncated = 1 on every later step
  * (the count saturates, it never wraps).  With it, "finished" is done | truncated: the environment is reset in the same step by the
  * same route and with the same Philox keys as a `done` one, and obs_out of that step holds the reset observation.
- * The final observation of a truncated episode is not delivered under auto-reset. */
+ * The final observation of an episode that ends under auto-reset (by either flag) is delivered through mgym_set_final_obs_out for CartPole,
+ * MountainCar, MountainCarContinuous and Pendulum; for LunarLander it is not delivered yet. */
 
 /* Space metadata (reference: observation_space()/action_space(), cartpole.rs:58-69,350-356;
  * mountain_car.rs:42-48; lunar_lander.rs:1169-1200). */
@@ -385,6 +386,25 @@ int mgym_rollout_mlp_sample(mgym_env *env, const float *policy, int32_t hidden, 
  * finds) — capture one graph per call word, or call eagerly. */
 int mgym_rollout_mlp_gauss(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, float sigma, uint64_t policy_seed,
                            uint32_t policy_call, int32_t K, void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
+
+/* The final observations of auto-reset episodes (gymnasium's final_obs / final_observation): what a learner bootstraps a truncated episode from.
+ * final_obs_out is a DEVICE pointer to [steps_cap][obs_dim][n_envs] floats — the layout of a rollout's obs_out — and stays set on the handle until it
+ * is replaced.  NULL turns the channel off and is always accepted (steps_cap is ignored then).
+ * While it is set, every call that steps writes to it — mgym_step, mgym_rollout (its K x step form too), mgym_rollout_uniform, _linear, _mlp, _mlp_sample,
+ * _mlp_gauss — and nothing else does (mgym_reset* never).  Take env i at step t of the call (mgym_step: t = 0): if that step returns done | truncated, the
+ * call writes the obs_dim words final_obs_out[(t * obs_dim + k) * n_envs + i], k = 0 .. obs_dim - 1: the observation this step produced BEFORE the fused
+ * reset — exactly the words obs_out would hold for that env-step on a handle without MGYM_FLAG_AUTO_RESET.  No other word of the buffer is written
+ * (read it where done | truncated is set), and obs_out and every other output are unchanged word for word.  The stores are sparse 4-byte ones made by
+ * the lane that owns the environment: any n_envs, 4-byte alignment.  A handle with the channel off launches exactly the kernels it always did.
+ * MGYM_ERR_BAD_ARG, the message naming the argument: a non-NULL final_obs_out on a handle without MGYM_FLAG_AUTO_RESET (obs_out already holds the final
+ * observation there); steps_cap < 1; a pointer that is not 4-byte aligned; MGYM_LUNARLANDER (not offered yet: its resets run through shadow records,
+ * staged copies and the persistent rollout's queues).  A stepping call with K > steps_cap: MGYM_ERR_BAD_ARG naming the entry point, before any launch,
+ * the state untouched.
+ * Graph capture: the pointer is frozen into captured launches like every output pointer; setting it later does not invalidate earlier graphs, and
+ * each captured call indexes t from 0.
+ * Not a compacted list of finished env-steps: that would be smaller, but needs atomics and has a run-dependent order; the dense buffer is
+ * deterministic and can be checked word for word against a handle without auto-reset. */
+int mgym_set_final_obs_out(mgym_env *env, float *final_obs_out, int32_t steps_cap);
 
 /* Number of env-steps of this handle that returned done or truncated since mgym_create (StepInfo.done / .truncated,
  * cartpole.rs:300-305): accumulated inside the step kernels by __ballot/popcount reductions of the done mask,

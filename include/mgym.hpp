@@ -92,6 +92,9 @@ class VecGym {
     // the elapsed count of mgym_config::max_episode_steps (device arrays of n_envs uint32; on the handle's stream)
     void get_elapsed_steps(uint32_t* out) { check(mgym_get_elapsed_steps(env_, out)); }
     void set_elapsed_steps(const uint32_t* in) { check(mgym_set_elapsed_steps(env_, in)); }
+    // The final observations of auto-reset episodes (mgym_set_final_obs_out): a device buffer [steps_cap][obs_dim][n_envs], written by every stepping call
+    // where done | truncated is set, with the observation the step produced before the fused reset; nullptr turns the channel off.
+    void set_final_obs_out(float* final_obs_out, int32_t steps_cap) { check(mgym_set_final_obs_out(env_, final_obs_out, steps_cap)); }
     uint32_t max_episode_steps() const { return cfg_.max_episode_steps; }
     const float* observation(uint64_t* col_stride) {
         const float* p = nullptr;

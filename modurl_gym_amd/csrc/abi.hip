@@ -215,6 +215,12 @@ int mgym_destroy(mgym_env* env) {
     return MGYM_OK;
 }
 
+// mgym_set_final_obs_out: a call that steps K times needs K slabs — refused before any launch, the state untouched
+#define FINAL_CAP_OR_FAIL(api, K)                                                                                                     \
+    if (e->final_obs && (K) > e->final_cap)                                                                                            \
+        return bad_arg((std::string(api ": K = ") + std::to_string(K) + " exceeds steps_cap = " + std::to_string(e->final_cap) +      \
+                        " of mgym_set_final_obs_out").c_str());
+
 #define ENV_OR_FAIL(env)                                        \
     if (!(env) || !(env)->impl) return bad_arg("NULL env handle"); \
     Env* e = (env)->impl;                                       \
@@ -260,6 +266,7 @@ int mgym_rollout(mgym_env* env, const void* actions, int32_t K, float* obs_out, 
                  uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout: K < 0");
+    FINAL_CAP_OR_FAIL("mgym_rollout", K);
     if (!actions && e->n && K) return bad_arg("mgym_rollout: actions is NULL");
     if (e->cfg.kind == MGYM_LUNARLANDER) {
         // While the stream is being captured a LunarLander rollout records K steps, not its persistent launch: replays of a captured persistent
@@ -276,6 +283,7 @@ int mgym_rollout_uniform(mgym_env* env, uint64_t policy_seed, int32_t K, void* a
                          uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_uniform: K < 0");
+    FINAL_CAP_OR_FAIL("mgym_rollout_uniform", K);
     if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_uniform: env_id_base must be a multiple of 4 (policy bits are keyed per 4 consecutive global env ids)");
     return e->rollout_policy(PolicyCall{ROLL_ACT_UNIFORM, "mgym_rollout_uniform", nullptr, 0, policy_seed}, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
@@ -284,6 +292,7 @@ int mgym_rollout_linear(mgym_env* env, const float* policy, int32_t K, void* act
                         uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_linear: K < 0");
+    FINAL_CAP_OR_FAIL("mgym_rollout_linear", K);
     if (!policy) return bad_arg("mgym_rollout_linear: policy is NULL");
     return e->rollout_policy(PolicyCall{ROLL_ACT_LINEAR, "mgym_rollout_linear", policy, 0, 0}, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
@@ -292,6 +301,7 @@ int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t
                      float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_mlp: K < 0");
+    FINAL_CAP_OR_FAIL("mgym_rollout_mlp", K);
     if (!policy) return bad_arg("mgym_rollout_mlp: policy is NULL");
     if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp: hidden must be between 1 and 64");
     if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
@@ -303,6 +313,7 @@ int mgym_rollout_mlp_sample(mgym_env* env, const float* policy, int32_t hidden, 
                             void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_mlp_sample: K < 0");
+    FINAL_CAP_OR_FAIL("mgym_rollout_mlp_sample", K);
     if (e->cfg.kind == MGYM_MOUNTAINCAR_CONT) return bad_arg("mgym_rollout_mlp_sample: MountainCarContinuous has no discrete actions to draw from (a Gaussian head is not implemented)");
     if (e->cfg.kind == MGYM_PENDULUM) return bad_arg("mgym_rollout_mlp_sample: Pendulum has no discrete actions to draw from (a Gaussian head is not implemented)");
     if (!policy) return bad_arg("mgym_rollout_mlp_sample: policy is NULL");
@@ -317,6 +328,7 @@ int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, i
                            void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
     if (K < 0) return bad_arg("mgym_rollout_mlp_gauss: K < 0");
+    FINAL_CAP_OR_FAIL("mgym_rollout_mlp_gauss", K);
     if (e->cfg.kind != MGYM_MOUNTAINCAR_CONT && e->cfg.kind != MGYM_PENDULUM) {
         static const char* const names[] = {"CartPole", "MountainCar", "", "LunarLander"};
         return bad_arg((std::string("mgym_rollout_mlp_gauss: ") + names[e->cfg.kind] + " has discrete actions: use mgym_rollout_mlp_sample").c_str());
@@ -328,6 +340,21 @@ int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, i
     if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_gauss: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
     return e->rollout_policy(PolicyCall{activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH_GAUSS : ROLL_ACT_MLP_RELU_GAUSS, "mgym_rollout_mlp_gauss", policy, hidden, policy_seed, policy_call, sigma},
                              K, actions_out, obs_out, reward_out, done_out, trunc_out);
+}
+
+int mgym_set_final_obs_out(mgym_env* env, float* final_obs_out, int32_t steps_cap) {
+    ENV_OR_FAIL(env);
+    if (final_obs_out) {
+        if (e->cfg.kind == MGYM_LUNARLANDER) return bad_arg("mgym_set_final_obs_out: final_obs_out is not offered for LunarLander yet (CartPole, MountainCar, MountainCarContinuous and Pendulum only)");
+        if (!(e->cfg.flags & MGYM_FLAG_AUTO_RESET))
+            return bad_arg("mgym_set_final_obs_out: final_obs_out on a handle without MGYM_FLAG_AUTO_RESET: obs_out already holds the final observation there");
+        if (steps_cap < 1) return bad_arg("mgym_set_final_obs_out: steps_cap must be at least 1");
+        if (!aligned(final_obs_out, 4)) return bad_arg("mgym_set_final_obs_out: final_obs_out must be 4-byte aligned");
+    }
+    // (config_epoch stays: graphs captured earlier keep the pointer they froze, like every output pointer)
+    e->final_obs = final_obs_out;
+    e->final_cap = final_obs_out ? steps_cap : 0;
+    return MGYM_OK;
 }
 
 int mgym_episode_count(mgym_env* env, uint64_t* finished) {

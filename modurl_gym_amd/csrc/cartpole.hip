@@ -180,11 +180,12 @@ __device__ __forceinline__ void cartpole_flush_counts(const CartPoleDev& d, uint
 // The arguments are plain scalars and pointers in the order the kernel first needs them — what the state loads need (base, n_pad), then n and
 // the actions, then the rest — and CartPoleDev is rebuilt from them for the per-wave functions: the leading 14 dwords (base .. done_count)
 // can be asked for as preloaded SGPRs (Makefile, PRELOAD); without that one scalar load and one wait stand before the loads.
-template <int VEC, bool EULER, bool SB, bool RESET, int BLK, bool ONE>
+// Fin: mgym_set_final_obs_out (soa4.h) — `fin` is the step's [4][n] slab; a finished env's four words leave with reward / done / truncated, ahead of the reset pass.
+template <int VEC, bool EULER, bool SB, bool RESET, int BLK, bool ONE, class... Fin>
 __global__ void __launch_bounds__(BLK)
 cartpole_step_kernel(float* col0, uint32_t n_pad, uint32_t n, const uint32_t* __restrict__ act, uint64_t seed, uint64_t env_id_base, uint32_t* err,
                      unsigned long long* done_count, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out,
-                     uint8_t* __restrict__ trunc_out) {
+                     uint8_t* __restrict__ trunc_out, Fin... fin) {
     __shared__ WaveResetScratch<VEC> lds_[RESET ? BLK / 64 : 1];
     constexpr uint32_t kPerBlock = (uint32_t)BLK * VEC;
     const uint32_t lane_env = threadIdx.x * VEC;     // first env of this lane within the block's slice
@@ -251,6 +252,11 @@ cartpole_step_kernel(float* col0, uint32_t n_pad, uint32_t n, const uint32_t* __
                 if (done_out) *at<uint8_t>(done_out + base, lane_env) = (uint8_t)dn[0];
                 if (trunc_out) *at<uint8_t>(trunc_out + base, lane_env) = (uint8_t)tr[0];
             }
+            if constexpr (has_final<Fin...>) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k)
+                    if (dn[k] | tr[k]) final_store<4>(at<float>(final_ptr(fin...) + base, off4) + k, n, {s[k].x, s[k].xd, s[k].th, s[k].thd});
+            }
         }
         const uint64_t wave_first = base + (uint64_t)(threadIdx.x & ~63) * VEC;
         finished += cartpole_wave_reset<VEC, RESET>(d, s, valid, dn, tr, wave_first, lds);
@@ -296,10 +302,11 @@ template <int POLICY> using CpPolicyArg = std::conditional_t<roll_act_is_mlp(POL
 // K steps; per step it reads one 16-B action word (or takes the next bit of its Philox policy stream) and writes
 // reward / done / truncated (and the observation / the drawn actions if asked).  Identical to K launches of
 // cartpole_step_kernel by construction: same per-wave function.
-template <bool EULER, bool SB, bool RESET, int POLICY>
+// Fin: the call's [K][4][n] final observations — stored before the reset pass, which replaces the registers (the other outputs of a step leave after it)
+template <bool EULER, bool SB, bool RESET, int POLICY, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_t* __restrict__ act_out, uint64_t policy_seed, uint32_t policy_call, CpPolicyArg<POLICY> lin,
-                        int K, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
+                        int K, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, Fin... fin) {
     __shared__ WaveResetScratch<4> lds_[RESET ? kWaves : 1];
     constexpr uint64_t kPerBlock = (uint64_t)kBlock * 4;
     bool bad = false;
@@ -362,6 +369,13 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
                 if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
             }
             cartpole_wave_advance<4, EULER, SB>(s, a, valid, r, dn, tr, bad);
+            if constexpr (has_final<Fin...>) {
+                if (in) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (dn[k] | tr[k]) final_store<4>(final_ptr(fin...) + (uint64_t)t * 4 * d.n + i0 + k, d.n, {s[k].x, s[k].xd, s[k].th, s[k].thd});
+                }
+            }
             // stored after the reset pass: storing reward / done / truncated before it (as cartpole_step_kernel does)
             // made the linear-policy rollout, whose waves rarely reset, 4 % slower
             finished += cartpole_wave_reset<4, RESET>(d, s, valid, dn, tr, wave_first, lds);
@@ -516,19 +530,22 @@ struct CartPoleEnv final : Env {
         return MGYM_OK;
     }
 
-    template <int VEC, bool RESET, int BLK>
-    void launch_step_blk(const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
+    template <int VEC, bool RESET, int BLK, class... Fin>
+    void launch_step_blk(const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, Fin... fin) {
         const uint64_t nb = (n + (uint64_t)BLK * VEC - 1) / ((uint64_t)BLK * VEC);   // tiles (n > 0)
         const uint64_t cap = (uint64_t)max_blocks * kBlock / BLK;   // same thread count as the kBlock-sized cap
         const bool one = nb <= cap;                                 // one block per tile: the single-pass form
         dim3 g((unsigned)(one ? nb : cap)), b(BLK);
         with_bools([&](auto E, auto S, auto O) {
-            hipLaunchKernelGGL((cartpole_step_kernel<VEC, decltype(E)::value, decltype(S)::value, RESET, BLK, decltype(O)::value>), g, b, 0, stream, dev.base,
-                               (uint32_t)dev.n_pad, (uint32_t)dev.n, act, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc);
+            hipLaunchKernelGGL((cartpole_step_kernel<VEC, decltype(E)::value, decltype(S)::value, RESET, BLK, decltype(O)::value, Fin...>), g, b, 0, stream, dev.base,
+                               (uint32_t)dev.n_pad, (uint32_t)dev.n, act, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, fin...);
         }, cfg.is_euler, cfg.sutton_barto_reward, one);
     }
     template <int VEC, bool RESET>
     void launch_step(const uint32_t* act, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
+        if constexpr (RESET) {
+            if (final_obs) { launch_step_blk<VEC, true, kBlock>(act, obs_out, reward, done, trunc, final_obs); return; }   // (mgym_set_final_obs_out; the block-size knob is not offered there)
+        }
         if (VEC == 4 && step_block == 64) launch_step_blk<VEC, RESET, 64>(act, obs_out, reward, done, trunc);
         else if (VEC == 4 && step_block == 128) launch_step_blk<VEC, RESET, 128>(act, obs_out, reward, done, trunc);
         else launch_step_blk<VEC, RESET, kBlock>(act, obs_out, reward, done, trunc);
@@ -547,6 +564,13 @@ struct CartPoleEnv final : Env {
     void launch_rollout(const uint32_t* act, uint32_t* act_out, uint64_t pseed, uint32_t pcall, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
                         const CpPolicyArg<POLICY>& lin = CpPolicyArg<POLICY>{}) {
         const dim3 g(grid_for(n / 4)), b(kBlock);
+        if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
+            with_bools([&](auto E, auto S) {
+                hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(S)::value, true, POLICY, float*>), g, b, 0, stream, dev, act, act_out, pseed, pcall, lin, K, obs_out,
+                                   reward, done, trunc, final_obs);
+            }, cfg.is_euler, cfg.sutton_barto_reward);
+            return;
+        }
         with_bools([&](auto E, auto S, auto R) {
             hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(S)::value, decltype(R)::value, POLICY>), g, b, 0, stream, dev, act, act_out, pseed, pcall, lin, K, obs_out,
                                reward, done, trunc);

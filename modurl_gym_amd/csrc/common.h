@@ -79,14 +79,20 @@ struct Env {
     virtual int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) = 0;
     // K fused steps; default: K launches of step() with strided per-step buffers
     virtual int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
-        for (int k = 0; k < K; ++k) {
+        float* const fin0 = final_obs;   // step k of the call writes its finished envs' observations to slab k (mgym_set_final_obs_out)
+        int st = MGYM_OK;
+        for (int k = 0; k < K && st == MGYM_OK; ++k) {
             const char* a = static_cast<const char*>(actions) + (size_t)k * n * 4;
-            int st = step(a, obs_out ? obs_out + (size_t)k * obs_dim * n : nullptr, reward ? reward + (size_t)k * n : nullptr,
-                          done ? done + (size_t)k * n : nullptr, trunc ? trunc + (size_t)k * n : nullptr);
-            if (st != MGYM_OK) return st;
+            if (fin0) final_obs = fin0 + (size_t)k * obs_dim * n;
+            st = step(a, obs_out ? obs_out + (size_t)k * obs_dim * n : nullptr, reward ? reward + (size_t)k * n : nullptr,
+                      done ? done + (size_t)k * n : nullptr, trunc ? trunc + (size_t)k * n : nullptr);
         }
-        return MGYM_OK;
+        final_obs = fin0;
+        return st;
     }
+    // mgym_set_final_obs_out: [final_cap][obs_dim][n] floats of the caller's, or null (the channel is off); only auto-reset handles of the classic families hold one
+    float* final_obs = nullptr;
+    int32_t final_cap = 0;
     // K fused steps under an on-device policy (mgym_rollout_uniform / _linear / _mlp): the action source, its weights or seed in `call`
     virtual int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) = 0;
     uint32_t uniform_calls = 0;  // mgym_rollout_uniform calls that launched so far (Philox counter word of the policy stream)

@@ -108,10 +108,11 @@ __device__ __forceinline__ void mountaincar_step_one(const MountainCarParams& p,
     }
 }
 
-template <int VEC, bool CONT, bool TL = false>
+// Fin (here and in the kernels below): mgym_set_final_obs_out (soa4.h) — `fin` is the step's [2][n] slab, or the call's [K][2][n] in a rollout.
+template <int VEC, bool CONT, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out,
-                        float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out) {
+                        float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, Fin... fin_out) {
     const uint64_t groups = (d.n + VEC - 1) / VEC;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool bad = false;
@@ -149,7 +150,10 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
             uint32_t fin = dn[k];
             if constexpr (TL) { el[k] = tl_advance(el[k]); tr[k] = tl_truncated(d.limit, el[k]); fin |= tr[k]; }
             finished += (fin && (i0 + k < d.n)) ? 1u : 0u;
-            if (d.auto_reset && fin && (i0 + k < d.n)) { mountaincar_reset_one(d, i0 + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
+            if (d.auto_reset && fin && (i0 + k < d.n)) {
+                if constexpr (has_final<Fin...>) final_store<2>(final_ptr(fin_out...) + i0 + k, d.n, {ps[k], vs[k]});
+                mountaincar_reset_one(d, i0 + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u;
+            }
         }
         if (VEC == 4 && full) {
             float4 op = make_float4(ps[0], ps[1 % VEC], ps[2 % VEC], ps[3 % VEC]);
@@ -198,11 +202,11 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
 // kernel first needs them — what the loads need (pos, n_pad, n, actions, the elapsed column), then the rest; the leading 14 dwords (pos .. err)
 // can be asked for as preloaded SGPRs (Makefile, PRELOAD).  MountainCarDev is rebuilt from them for mountaincar_step_one / mountaincar_reset_one: the
 // columns lie n_pad words apart, and the physics constants depend on the family alone (mc_params), all but goal_velocity.
-template <bool CONT, bool RESET, bool TL, bool ONE>
+template <bool CONT, bool RESET, bool TL, bool ONE, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_step4_kernel(float* pos, uint32_t n_pad, uint32_t n, const uint32_t* __restrict__ act, uint16_t* elapsed, uint64_t seed, uint64_t env_id_base,
                          uint32_t* err, unsigned long long* done_count, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out,
-                         uint8_t* __restrict__ trunc_out, uint32_t limit, float goal_velocity) {
+                         uint8_t* __restrict__ trunc_out, uint32_t limit, float goal_velocity, Fin... fin_out) {
     constexpr uint32_t kPerBlock = (uint32_t)kBlock * 4;
     const uint32_t lane_env = threadIdx.x * 4u, off4 = lane_env * 4u;
     const uint32_t colb = n_pad * 4u;  // column stride in bytes
@@ -238,7 +242,10 @@ mountaincar_step4_kernel(float* pos, uint32_t n_pad, uint32_t n, const uint32_t*
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 finished += (uint32_t)__popcll(__ballot(in && fin[k]));
-                if (RESET && in && fin[k]) { mountaincar_reset_one(d, (uint64_t)base + lane_env + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
+                if (RESET && in && fin[k]) {
+                    if constexpr (has_final<Fin...>) final_store<2>(final_ptr(fin_out...) + base + lane_env + k, n, {ps[k], vs[k]});
+                    mountaincar_reset_one(d, (uint64_t)base + lane_env + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u;
+                }
             }
         }
         if (in) {
@@ -281,11 +288,11 @@ struct McUniformPolicy { uint64_t seed; uint32_t call; };
 template <bool CONT, int POLICY> using McPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<2, CONT ? 1 : 3>, McLinearPolicy>;
 // mgym_rollout_mlp_gauss (MountainCarContinuous only): sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
 template <int POLICY> using McDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, McUniformPolicy>;
-template <bool CONT, int POLICY = ROLL_ACT_TABLE, bool TL = false>
+template <bool CONT, int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
                            uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, McPolicyArg<CONT, POLICY> lin = {}, uint32_t* __restrict__ act_out = nullptr,
-                           McDrawArg<POLICY> uni = {}) {
+                           McDrawArg<POLICY> uni = {}, Fin... fin_out) {
     constexpr bool LINEAR = POLICY == ROLL_ACT_LINEAR;
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -355,7 +362,10 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                 uint32_t fin = dn[k];
                 if constexpr (TL) { el[k] = tl_advance(el[k]); tr[k] = tl_truncated(d.limit, el[k]); fin |= tr[k]; }
                 finished += fin;
-                if (d.auto_reset && fin) { mountaincar_reset_one(d, i0 + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u; }
+                if (d.auto_reset && fin) {
+                    if constexpr (has_final<Fin...>) final_store<2>(final_ptr(fin_out...) + (uint64_t)t * 2 * d.n + i0 + k, d.n, {ps[k], vs[k]});
+                    mountaincar_reset_one(d, i0 + k, ps[k], vs[k]); if constexpr (TL) el[k] = 0u;
+                }
             }
             if (rew) nt_store4(rew + off, make_float4(r[0], r[1], r[2], r[3]));
             if (done_out) __builtin_nontemporal_store(pack_bytes4(dn), reinterpret_cast<uint32_t*>(done_out + off));
@@ -496,6 +506,15 @@ struct MountainCarEnv final : Env {
             const uint64_t nb = (n + 4 * kBlock - 1) / (4 * kBlock);   // tiles
             const bool one = nb <= (uint64_t)max_blocks;               // one block per tile: the single-pass form
             const dim3 g((unsigned)(one ? nb : (uint64_t)max_blocks));
+            if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
+                with_bools([&](auto C, auto T, auto O) {
+                    hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, true, decltype(T)::value, decltype(O)::value, float*>), g, b, 0, stream, dev.pos, (uint32_t)n_pad,
+                                       (uint32_t)n, act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.p.goal_velocity,
+                                       final_obs);
+                }, continuous, tl, one);
+                MGYM_HIP(hipGetLastError());
+                return MGYM_OK;
+            }
             with_bools([&](auto C, auto T, auto R, auto O) {
                 hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, decltype(R)::value, decltype(T)::value, decltype(O)::value>), g, b, 0, stream, dev.pos,
                                    (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc,
@@ -505,7 +524,9 @@ struct MountainCarEnv final : Env {
             return MGYM_OK;
         }
         with_bools([&](auto C, auto T, auto V) {
-            hipLaunchKernelGGL((mountaincar_step_kernel<decltype(V)::value ? 4 : 1, decltype(C)::value, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
+            constexpr int VEC = decltype(V)::value ? 4 : 1;
+            if (final_obs) hipLaunchKernelGGL((mountaincar_step_kernel<VEC, decltype(C)::value, decltype(T)::value, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
+            else hipLaunchKernelGGL((mountaincar_step_kernel<VEC, decltype(C)::value, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
         }, continuous, tl, vec_ok);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
@@ -515,7 +536,8 @@ struct MountainCarEnv final : Env {
     template <int POLICY, bool CONT, bool TL>
     void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
                         const McPolicyArg<CONT, POLICY>& arg = McPolicyArg<CONT, POLICY>{}, McDrawArg<POLICY> uni = {}) {
-        hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
+        if (final_obs) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, final_obs);
+        else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
     int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {

@@ -53,10 +53,11 @@ __device__ __forceinline__ void pendulum_reset_env(const PendulumDev& d, uint64_
 }
 
 // The generic step kernel: any n, any alignment of the caller's buffers (VEC = 1), or 4 environments per lane with a ragged last group (VEC = 4)
-template <int VEC, bool TL>
+// Fin (here and in the kernels below): mgym_set_final_obs_out (soa4.h) — `fin` is the step's [3][n] slab, or the call's [K][3][n] in a rollout.
+template <int VEC, bool TL, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 pendulum_step_kernel(PendulumDev d, const uint32_t* __restrict__ act, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out,
-                     uint8_t* __restrict__ trunc_out) {
+                     uint8_t* __restrict__ trunc_out, Fin... fin) {
     const uint64_t groups = (d.n + VEC - 1) / VEC;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool bad = false;
@@ -97,7 +98,10 @@ pendulum_step_kernel(PendulumDev d, const uint32_t* __restrict__ act, float* __r
             const bool ok = pendulum_env_step<TL>(d.c_g, d.limit, th[k], td[k], cs[k], sn[k], el[k], a[k], r[k], tr[k]);
             if (!ok) { bad = true; if (in) cs[k] = d.cs[i0 + k]; }
             finished += (tr[k] && in) ? 1u : 0u;
-            if (d.auto_reset && tr[k] && in) { pendulum_reset_env(d, i0 + k, th[k], td[k], cs[k], sn[k]); el[k] = 0u; }
+            if (d.auto_reset && tr[k] && in) {
+                if constexpr (has_final<Fin...>) final_store<3>(final_ptr(fin...) + i0 + k, d.n, {cs[k], sn[k], td[k]});
+                pendulum_reset_env(d, i0 + k, th[k], td[k], cs[k], sn[k]); el[k] = 0u;
+            }
         }
         if (VEC == 4 && full) {
             const float4 oc = make_float4(cs[0], cs[1 % VEC], cs[2 % VEC], cs[3 % VEC]), os = make_float4(sn[0], sn[1 % VEC], sn[2 % VEC], sn[3 % VEC]);
@@ -141,11 +145,11 @@ pendulum_step_kernel(PendulumDev d, const uint32_t* __restrict__ act, float* __r
 // ONE: the single-pass form, one block per tile of 1024 environments (populations of at most the block cap's tiles) — no loop, no test on n before the
 // loads, no read of the grid size; !ONE: the grid-stride form.  The arguments are plain scalars and pointers in the order the kernel first needs
 // them; the leading 14 dwords (cs .. err) can be asked for as preloaded SGPRs (Makefile, PRELOAD).
-template <bool RESET, bool TL, bool ONE>
+template <bool RESET, bool TL, bool ONE, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t* __restrict__ act, uint16_t* elapsed, uint64_t seed, uint64_t env_id_base,
                       uint32_t* err, unsigned long long* done_count, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out,
-                      uint8_t* __restrict__ trunc_out, uint32_t limit, float c_g) {
+                      uint8_t* __restrict__ trunc_out, uint32_t limit, float c_g, Fin... fin) {
     constexpr uint32_t kPerBlock = (uint32_t)kBlock * 4;
     const uint32_t lane_env = threadIdx.x * 4u, off4 = lane_env * 4u;
     const uint32_t colb = n_pad * 4u;  // column stride in bytes
@@ -190,7 +194,10 @@ pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     finished += (uint32_t)__popcll(__ballot(in && tr[k]));
-                    if (RESET && in && tr[k]) { pendulum_reset_env(d, (uint64_t)base + lane_env + k, th[k], td[k], cs[k], sn[k]); el[k] = 0u; }
+                    if (RESET && in && tr[k]) {
+                        if constexpr (has_final<Fin...>) final_store<3>(final_ptr(fin...) + base + lane_env + k, n, {cs[k], sn[k], td[k]});
+                        pendulum_reset_env(d, (uint64_t)base + lane_env + k, th[k], td[k], cs[k], sn[k]); el[k] = 0u;
+                    }
                 }
             }
         }
@@ -230,11 +237,11 @@ struct PdUniformPolicy { uint64_t seed; uint32_t call; };
 template <int POLICY> using PdPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<3, 1>, PdLinearPolicy>;
 // mgym_rollout_mlp_gauss: sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
 template <int POLICY> using PdDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, PdUniformPolicy>;
-template <int POLICY = ROLL_ACT_TABLE, bool TL = false>
+template <int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
                         uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, PdPolicyArg<POLICY> pol = {}, uint32_t* __restrict__ act_out = nullptr,
-                        PdDrawArg<POLICY> uni = {}) {
+                        PdDrawArg<POLICY> uni = {}, Fin... fin) {
     static_assert(!roll_act_samples(POLICY), "Pendulum has no categorical draw");
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -275,7 +282,10 @@ pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, 
             for (int k = 0; k < 4; ++k) {
                 if (!pendulum_env_step<TL>(d.c_g, d.limit, th[k], td[k], cs[k], sn[k], el[k], a[k], r[k], tr[k])) bad = true;   // (cs is live here: a NaN action leaves it)
                 finished += tr[k];
-                if (d.auto_reset && tr[k]) { pendulum_reset_env(d, i0 + k, th[k], td[k], cs[k], sn[k]); el[k] = 0u; }
+                if (d.auto_reset && tr[k]) {
+                    if constexpr (has_final<Fin...>) final_store<3>(final_ptr(fin...) + (uint64_t)t * 3 * d.n + i0 + k, d.n, {cs[k], sn[k], td[k]});
+                    pendulum_reset_env(d, i0 + k, th[k], td[k], cs[k], sn[k]); el[k] = 0u;
+                }
             }
             if (rew) nt_store4(rew + off, make_float4(r[0], r[1], r[2], r[3]));
             if (done_out) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(done_out + off));   // done = 0, always
@@ -426,10 +436,25 @@ struct PendulumEnv final : Env {
             const uint64_t nb = (n + 4 * kBlock - 1) / (4 * kBlock);   // tiles
             const bool one = nb <= (uint64_t)max_blocks;               // one block per tile: the single-pass form
             const dim3 g((unsigned)(one ? nb : (uint64_t)max_blocks));
+            if (final_live()) {
+                with_bools([&](auto O) {
+                    hipLaunchKernelGGL((pendulum_step4_kernel<true, true, decltype(O)::value, float*>), g, b, 0, stream, dev.cs, (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed, dev.seed,
+                                       dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.c_g, final_obs);
+                }, one);
+                MGYM_HIP(hipGetLastError());
+                return MGYM_OK;
+            }
             with_bools([&](auto R, auto T, auto O) {
                 hipLaunchKernelGGL((pendulum_step4_kernel<decltype(R)::value, decltype(T)::value, decltype(O)::value>), g, b, 0, stream, dev.cs, (uint32_t)n_pad, (uint32_t)n, act,
                                    dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.c_g);
             }, dev.auto_reset != 0, tl, one);
+            MGYM_HIP(hipGetLastError());
+            return MGYM_OK;
+        }
+        if (final_live()) {
+            with_bools([&](auto V) {
+                hipLaunchKernelGGL((pendulum_step_kernel<decltype(V)::value ? 4 : 1, true, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
+            }, vec_ok);
             MGYM_HIP(hipGetLastError());
             return MGYM_OK;
         }
@@ -444,8 +469,17 @@ struct PendulumEnv final : Env {
     template <int POLICY, bool TL>
     void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
                         const PdPolicyArg<POLICY>& arg = PdPolicyArg<POLICY>{}, PdDrawArg<POLICY> uni = {}) {
+        if constexpr (TL) {
+            if (final_live()) {
+                hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, true, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, final_obs);
+                return;
+            }
+        }
         hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
+
+    // the channel of mgym_set_final_obs_out has something to deliver: without a time limit no Pendulum episode ever ends (and only auto-reset handles hold a pointer)
+    bool final_live() const { return final_obs != nullptr && dev.limit != 0u; }
 
     int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;

@@ -176,6 +176,13 @@ class VecEnv:
         return dict(line.split("=", 1) for line in buf.value.decode().splitlines() if "=" in line)
 
     # ---- raw device-pointer path (what bench.py and a Rust/C caller use) --------------
+    def set_final_obs_out_device(self, final_obs_out, steps_cap=0):
+        """mgym_set_final_obs_out: a device buffer [steps_cap][obs_dim][n] (pointer, DeviceArray or tensor) that every stepping call fills, where
+        done | truncated is set, with the observation the step produced before the fused reset; None turns the channel off.  The caller keeps
+        the buffer alive while it is set (auto-reset handles of CartPole, MountainCar(+Continuous) and Pendulum)."""
+        _check(self._lib.mgym_set_final_obs_out(self._h, _ptr(final_obs_out), int(steps_cap)))
+        self._final_obs = final_obs_out   # (keeps a DeviceArray / tensor alive)
+
     def reset_device(self, mask=None, obs_out=None):
         _check(self._lib.mgym_reset(self._h, _ptr(mask), _ptr(obs_out)))
 

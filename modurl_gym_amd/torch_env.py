@@ -38,12 +38,14 @@ class _DeviceSpan:
 class TorchVecEnv:
     """`VecEnv` whose inputs/outputs are torch tensors on the env's GPU, stream-ordered with torch."""
 
-    def __init__(self, kind, n_envs, device=None, seed=0, env_id_base=0, auto_reset=True, obs_layout="soa", **params):
+    def __init__(self, kind, n_envs, device=None, seed=0, env_id_base=0, auto_reset=True, obs_layout="soa", final_obs_steps=0, **params):
         import torch
         if not torch.cuda.is_available():
             raise E.MgymError(E.L.ERR_NO_DEVICE, "TorchVecEnv needs a GPU (there is no CPU path)")
         if obs_layout not in ("soa", "aos"):
             raise ValueError("obs_layout must be 'soa' or 'aos'")
+        if int(final_obs_steps) > 0 and obs_layout != "soa":
+            raise ValueError("final_obs_steps needs obs_layout='soa' (the final observations are delivered in the engine's column layout only)")
         self._torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.env = E.VecEnv(kind, n_envs, device=self.device.index, seed=seed, env_id_base=env_id_base,
@@ -58,6 +60,11 @@ class TorchVecEnv:
         self._rew = torch.empty(self.n, dtype=f32, device=self.device)
         self._done = torch.empty(self.n, dtype=u8, device=self.device)
         self._trunc = torch.empty(self.n, dtype=u8, device=self.device)
+        # final observations of auto-reset episodes (mgym_set_final_obs_out): [final_obs_steps, obs_dim, n], written where done | truncated is set
+        self.final_obs = None
+        if int(final_obs_steps) > 0:
+            self.final_obs = torch.zeros((int(final_obs_steps), self.obs_dim, self.n), dtype=f32, device=self.device)
+            self.env.set_final_obs_out_device(self.final_obs, int(final_obs_steps))
 
     # ---- plumbing -----------------------------------------------------------------------
     def _bind_stream(self):
@@ -197,6 +204,16 @@ class TorchVecEnv:
         act, obs, rew, done, trunc = self._policy_outputs(K)
         self.env.rollout_uniform_device(int(seed), K, act, obs, rew, done, trunc)
         return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+
+    def bootstrap_obs(self, obs, done, truncated):
+        """The observation a learner evaluates V on after each env-step of the last call: `obs` ([K, obs_dim, n], or [obs_dim, n] from step) with the final
+        observation in the place of the reset one wherever the episode ended (needs final_obs_steps >= K at construction)."""
+        if self.final_obs is None:
+            raise ValueError("bootstrap_obs needs final_obs_steps > 0 at construction")
+        fin = done | truncated
+        if obs.dim() == 2:
+            return self._torch.where(fin[None, :], self.final_obs[0], obs)
+        return self._torch.where(fin[:, None, :], self.final_obs[: obs.shape[0]], obs)
 
     def elapsed_steps(self):
         """Caller-visible steps since each env's last reset (mgym_get_elapsed_steps; the count of `max_episode_steps`, which is passed

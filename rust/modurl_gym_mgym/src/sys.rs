@@ -189,6 +189,7 @@ unsafe extern "C" {
     pub fn mgym_set_state(env: *mut mgym_env, blob: *const c_void) -> c_int;
     pub fn mgym_get_elapsed_steps(env: *mut mgym_env, out: *mut u32) -> c_int;
     pub fn mgym_set_elapsed_steps(env: *mut mgym_env, input: *const u32) -> c_int;
+    pub fn mgym_set_final_obs_out(env: *mut mgym_env, final_obs_out: *mut f32, steps_cap: i32) -> c_int;
     pub fn mgym_reset_deterministic(env: *mut mgym_env, obs_out: *mut f32) -> c_int;
     pub fn mgym_set_dispersion_override(env: *mut mgym_env, disp: *const f32) -> c_int;
     pub fn mgym_get_spec(kind: c_int, spec: *mut mgym_spec) -> c_int;

@@ -308,6 +308,12 @@ impl VecGym {
     pub fn set_elapsed_steps(&mut self, input: &DeviceBuf<u32>) -> Result<(), MgymError> {
         check(unsafe { mgym_set_elapsed_steps(self.env, input.as_ptr() as *const u32) })
     }
+    /// The final observations of auto-reset episodes (`mgym_set_final_obs_out`): `buf` holds `[steps_cap][obs_dim][n_envs]` floats and is written by every
+    /// stepping call where `done | truncated` is set, with the observation the step produced before the fused reset; `None` turns the channel off.
+    /// The caller keeps `buf` alive while it is set.
+    pub fn set_final_obs_out(&mut self, buf: Option<&mut DeviceBuf<f32>>, steps_cap: i32) -> Result<(), MgymError> {
+        check(unsafe { mgym_set_final_obs_out(self.env, buf.map_or(std::ptr::null_mut(), |b| b.as_ptr()), steps_cap) })
+    }
     pub fn reset_deterministic(&mut self, obs_out: &mut DeviceBuf<f32>) -> Result<(), MgymError> {
         check(unsafe { mgym_reset_deterministic(self.env, obs_out.as_ptr()) })
     }
