@@ -62,7 +62,10 @@ typedef enum mgym_kind {
     MGYM_MOUNTAINCAR = 1,      /* MountainCarV0   — src/classic_control/mountain_car.rs */
     MGYM_MOUNTAINCAR_CONT = 2, /* MountainCarContinuous-v0 — NOT in the reference (parity unpinned) */
     MGYM_LUNARLANDER = 3,      /* LunarLanderV3   — src/box_2d/lunar_lander.rs */
-    MGYM_PENDULUM = 4          /* Pendulum-v1 — NOT in the reference (parity unpinned); defined below */
+    MGYM_PENDULUM = 4,         /* Pendulum-v1 — NOT in the reference (parity unpinned); defined below */
+    MGYM_ACROBOT = 6           /* Acrobot-v1 — NOT in the reference (parity unpinned); defined below.  5 is not assigned: it stays the
+                                  "unknown kind" it has always been (MGYM_ERR_BAD_ARG from every entry point that takes a kind), and a
+                                  later family does not take it either */
 } mgym_kind;
 
 /* MGYM_PENDULUM = 4 is gymnasium's Pendulum-v1 with m = l = 1, dt = 0.05, max_speed = 8 and max_torque = 2.  It is not in the reference: parity
@@ -117,6 +120,61 @@ typedef enum mgym_kind {
  *  - The fused forms need n_envs to be a multiple of 4 and the buffers 16-byte aligned; mgym_rollout with an action table falls back to K steps
  *    otherwise, as MountainCar's does. */
 
+/* MGYM_ACROBOT = 6 is gymnasium's Acrobot-v1: the "book" dynamics with m1 = m2 = l1 = 1, lc1 = lc2 = 0.5, I1 = I2 = 1, g = 9.8, dt = 0.2, one RK4 step and
+ * no torque noise.  It is not in the reference: parity unpinned, as for MGYM_PENDULUM.  Gymnasium integrates in float64; this engine is f32, so the f32
+ * words are defined here exactly.  All arithmetic is f32, every operation is individually rounded, nothing is fused and nothing is reassociated.  The
+ * cos(x - pi/2) terms of the dynamics are written as sines and sin(th1 + th2) by the addition formula, so one (sin, cos) pair per angle serves a
+ * derivative evaluation.
+ *
+ *     PI_F = 3.14159274f   TWO_PI_F = 6.28318548f   V1 = (float)(4 pi)   V2 = (float)(9 pi)
+ *     h = 0.1f   dt = 0.2f   dt6 = 0.2f / 6.0f (one f32 divide)
+ *
+ *     deriv(th1, th2, w1, w2, tau):
+ *         s1, c1 = sinf(th1), cosf(th1);   s2, c2 = sinf(th2), cosf(th2)     mg_sinf / mg_cosf (csrc/mgym_math.h), i.e. glibc's
+ *         s12  = s1*c2 + c1*s2
+ *         d1   = 3.5f + c2
+ *         d2   = 1.25f + 0.5f*c2
+ *         phi2 = 4.9f * s12
+ *         phi1 = (((-(0.5f*(w2*w2))*s2) - (w2*w1)*s2) + 14.7f*s1) + phi2
+ *         dd2  = (((tau + (d2/d1)*phi1) - (0.5f*(w1*w1))*s2) - phi2) / (1.25f - (d2*d2)/d1)
+ *         dd1  = -((d2*dd2 + phi1) / d1)
+ *         return (w1, w2, dd1, dd2)
+ *
+ *     step, action word a (u32):
+ *         a > 2: sticky MGYM_ERR_INVALID_ACTION, reward 0, done 0, state untouched (MountainCar's rule, the elapsed count included: it advances)
+ *         tau = (float)a - 1.0f
+ *         k1 = deriv(y);  k2 = deriv(y + h*k1);  k3 = deriv(y + h*k2);  k4 = deriv(y + dt*k3)      (componentwise, one multiply and one add)
+ *         y' = y + dt6 * (((k1 + 2.0f*k2) + 2.0f*k3) + k4)
+ *         th1', th2':  if (x > PI_F || x < -PI_F) { r = fmodf(x + PI_F, TWO_PI_F); if (r < 0) r += TWO_PI_F; x = r - PI_F; }
+ *         w1' = clamp(w1', -V1, V1);  w2' = clamp(w2', -V2, V2)      (Pendulum's compare form: a NaN passes through)
+ *         obs = (cos th1', sin th1', cos th2', sin th2', w1', w2')
+ *         done = (-c1' - (c1'*c2' - s1'*s2')) > 1.0f          from the observation's own words
+ *         reward = done ? 0.0f : -1.0f
+ *  - The wrap is loop-free on purpose: gymnasium's `while x > pi: x -= 2 pi` never ends for an infinity, and no data-dependent loop appears anywhere in
+ *    the step.  A non-finite state (reachable only through mgym_set_state) yields NaNs, done = 0, and the call returns.
+ *  - A finished environment that is stepped again keeps integrating: done is recomputed by every step, nothing is sticky.
+ *  - max_episode_steps (0 = off, 1 .. 65535; gymnasium registers Acrobot-v1 with 500) and MGYM_FLAG_AUTO_RESET (the fused reset on done | truncated)
+ *    follow MountainCar's rules exactly.  The other config fields (gravity, wind, ...) are ignored.
+ *
+ * Reset: th1, th2 = uniform_f64_to_f32(-0.1, 0.1, w0, w1), (.., w2, w3) of env_draw(seed, env_id_base + i, episode, SLOT_RESET0) and w1, w2 the same of
+ * env_draw(.., SLOT_RESET1) (csrc/philox.h).  Then episode += 1 and elapsed = 0.  mgym_reset_deterministic sets the four state words to 0, so the
+ * observation is (1, 0, 1, 0, 0, 0); mgym_create leaves that state too.
+ *
+ * mgym_get_spec: obs_dim 6, n_actions 3, action_is_float 0; obs_high (1, 1, 1, 1, V1, V2), obs_low its negative; state_cols 5.
+ * State blob: columns th1, th2, w1, w2, episode.  mgym_set_state takes the angle and velocity words as they are (no wrap, no clamp), recomputes the
+ * stored cos and sin words and sets elapsed to 0.  mgym_get_elapsed_steps and mgym_set_elapsed_steps behave as for MountainCar.  mgym_observation is a
+ * zero-copy view: the engine keeps the six observation words as adjacent columns with stride n_pad.
+ *
+ * Policies, all taking the observation o held before the step, with actions_out holding u32 words:
+ *  - mgym_rollout_uniform: MountainCar's Discrete(3) draw — word g % 4 of Philox(key = policy_seed; counter = (g & ~3 lo, g & ~3 hi, uniform call count,
+ *    0x40000000 + t / 2)), its low half at even t and its high half at odd t, h, and a = (3 h) >> 16.
+ *  - mgym_rollout_linear: policy holds three rows of (6 weights, bias), 21 floats; s_j = ((((((w_j0 o0 + w_j1 o1) + w_j2 o2) + w_j3 o3) + w_j4 o4) + w_j5 o5) + b_j
+ *    and the sequential strict argmax of the LunarLander form.
+ *  - mgym_rollout_mlp: D = 6, A = 3.  mgym_rollout_mlp_sample: A = 3.  mgym_rollout_mlp_gauss: MGYM_ERR_BAD_ARG before any launch (discrete actions).
+ *  - The fused forms need n_envs to be a multiple of 4 and the buffers 16-byte aligned (env_id_base a multiple of 4 where a draw is involved);
+ *    mgym_rollout with an action table falls back to K steps otherwise, as MountainCar's does.
+ *  - mgym_set_final_obs_out is offered. */
+
 enum {
     MGYM_FLAG_AUTO_RESET = 1u /* fused same-step reset of finished envs inside mgym_step (superset; default off) */
 };
@@ -151,7 +209,7 @@ typedef struct mgym_config {
  * truncate, mountain_car.rs:324-329, lunar_lander.rs:1165; this is gymnasium's TimeLimit rule, and the one thing a caller of the fused
  * mgym_rollout* launches cannot add from outside).  0 = off: every output word and every step / rollout kernel is what it is without the field (MountainCar's reset and state-import
  * kernels additionally clear a 2-byte count per environment they touch).
- *   1 .. 65535: MountainCar, MountainCarContinuous, Pendulum, LunarLander.  Larger: MGYM_ERR_BAD_CONFIG.
+ *   1 .. 65535: MountainCar, MountainCarContinuous, Pendulum, Acrobot, LunarLander.  Larger: MGYM_ERR_BAD_CONFIG.
  *   CartPole keeps the reference's 500 (cartpole.rs:297): it accepts 0 and 500, which both mean what it does today, and rejects
  *   anything else with MGYM_ERR_BAD_CONFIG.
  * Every environment has an ELAPSED count of caller-visible steps since its last reset: 0 after mgym_reset / mgym_reset_done /
@@ -164,7 +222,7 @@ typedef struct mgym_config {
  * (the count saturates, it never wraps).  With it, "finished" is done | truncated: the environment is reset in the same step by the
  * same route and with the same Philox keys as a `done` one, and obs_out of that step holds the reset observation.
  * The final observation of an episode that ends under auto-reset (by either flag) is delivered through mgym_set_final_obs_out for CartPole,
- * MountainCar, MountainCarContinuous and Pendulum; for LunarLander it is not delivered yet. */
+ * MountainCar, MountainCarContinuous, Pendulum and Acrobot; for LunarLander it is not delivered yet. */
 
 /* Space metadata (reference: observation_space()/action_space(), cartpole.rs:58-69,350-356;
  * mountain_car.rs:42-48; lunar_lander.rs:1169-1200). */

@@ -14,13 +14,13 @@ import os as _os
 # setenv("GPU_MAX_HW_QUEUES", "8", 0) before their first HIP call; `mgym_get_info` reports what a handle got.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from ._lib import (CARTPOLE, LUNARLANDER, MOUNTAINCAR, MOUNTAINCAR_CONT, PENDULUM, LIB_PATH, PROTOTYPES)  # noqa: F401
+from ._lib import (ACROBOT, CARTPOLE, LUNARLANDER, MOUNTAINCAR, MOUNTAINCAR_CONT, PENDULUM, LIB_PATH, PROTOTYPES)  # noqa: F401
 from .envs import (BadConfigError, CartPoleV1, DeviceArray, InvalidActionError, LunarLanderV3,  # noqa: F401
-                   MgymError, MountainCarContinuousV0, MountainCarV0, NotResetError, PendulumV1, PolicyShapeError, StepInfo, VecEnv,
+                   MgymError, AcrobotV1, MountainCarContinuousV0, MountainCarV0, NotResetError, PendulumV1, PolicyShapeError, StepInfo, VecEnv,
                    device_count, get_spec)
 from .shard import Shard, all_reduce_episode_count, mixed_population, population_plan, shard_range  # noqa: F401
 from .torch_env import TorchVecEnv  # noqa: F401
 
-__all__ = ["CartPoleV1", "MountainCarV0", "MountainCarContinuousV0", "LunarLanderV3", "PendulumV1", "VecEnv", "StepInfo",
+__all__ = ["CartPoleV1", "MountainCarV0", "MountainCarContinuousV0", "LunarLanderV3", "PendulumV1", "AcrobotV1", "VecEnv", "StepInfo",
            "DeviceArray", "MgymError", "InvalidActionError", "NotResetError", "BadConfigError", "PolicyShapeError", "device_count",
            "get_spec", "shard_range", "mixed_population", "population_plan", "all_reduce_episode_count", "Shard", "TorchVecEnv"]

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libmgym.so")
 
 OK, ERR_INVALID_ACTION, ERR_NOT_RESET, ERR_BAD_CONFIG, ERR_HIP, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_CAPACITY = range(8)
 CARTPOLE, MOUNTAINCAR, MOUNTAINCAR_CONT, LUNARLANDER, PENDULUM = range(5)
+ACROBOT = 6   # (5 is not assigned)
 FLAG_AUTO_RESET = 1
 ACT_RELU, ACT_TANH = range(2)   # mgym_rollout_mlp hidden activations
 MATH_SINF, MATH_COSF, MATH_SINCOSF, MATH_SINCOSF_U, MATH_COSF_U, MATH_TANHF = range(6)   # mgym_math_probe entry points

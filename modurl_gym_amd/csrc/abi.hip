@@ -55,13 +55,15 @@ struct mgym_env {
     Env* impl;
 };
 
+constexpr int kKindUnassigned = 5;   // between MGYM_PENDULUM and MGYM_ACROBOT: no family, refused like any unknown kind
+
 extern "C" {
 
 int mgym_abi_version(void) { return MGYM_ABI_VERSION; }
 
 int mgym_default_config(int kind, mgym_config* cfg) {
     if (!cfg) return bad_arg("mgym_default_config: cfg is NULL");
-    if (kind < MGYM_CARTPOLE || kind > MGYM_PENDULUM) return bad_arg("mgym_default_config: unknown kind");
+    if (kind < MGYM_CARTPOLE || kind > MGYM_ACROBOT || kind == kKindUnassigned) return bad_arg("mgym_default_config: unknown kind");
     memset(cfg, 0, sizeof *cfg);
     cfg->struct_size = (uint32_t)sizeof *cfg;
     cfg->kind = kind;
@@ -106,6 +108,12 @@ int mgym_get_spec(int kind, mgym_spec* s) {
         s->obs_dim = 3; s->state_cols = 3; s->n_actions = 0; s->action_is_float = 1; s->action_low = -2.0f; s->action_high = 2.0f;
         const float hi[3] = {1.0f, 1.0f, 8.0f};
         for (int k = 0; k < 3; ++k) { s->obs_high[k] = hi[k]; s->obs_low[k] = -hi[k]; }
+        break;
+    }
+    case MGYM_ACROBOT: {  // gymnasium Acrobot-v1 (not in the reference): (cos th1, sin th1, cos th2, sin th2, w1, w2), Discrete(3) torque
+        s->obs_dim = 6; s->n_actions = 3; s->state_cols = 5;
+        const float hi[6] = {1.0f, 1.0f, 1.0f, 1.0f, (float)(4.0 * 3.14159265358979323846), (float)(9.0 * 3.14159265358979323846)};
+        for (int k = 0; k < 6; ++k) { s->obs_high[k] = hi[k]; s->obs_low[k] = -hi[k]; }
         break;
     }
     default:
@@ -162,6 +170,7 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
     case MGYM_MOUNTAINCAR_CONT: impl = make_mountaincar(true); break;
     case MGYM_LUNARLANDER: impl = make_lunarlander(); break;
     case MGYM_PENDULUM: impl = make_pendulum(); break;
+    case MGYM_ACROBOT: impl = make_acrobot(); break;
     default: return bad_arg("mgym_create: unknown kind");
     }
     if (!impl) { set_last_error("mgym_create: environment family not available in this build"); return MGYM_ERR_BAD_CONFIG; }
@@ -330,7 +339,7 @@ int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, i
     if (K < 0) return bad_arg("mgym_rollout_mlp_gauss: K < 0");
     FINAL_CAP_OR_FAIL("mgym_rollout_mlp_gauss", K);
     if (e->cfg.kind != MGYM_MOUNTAINCAR_CONT && e->cfg.kind != MGYM_PENDULUM) {
-        static const char* const names[] = {"CartPole", "MountainCar", "", "LunarLander"};
+        static const char* const names[] = {"CartPole", "MountainCar", "", "LunarLander", "", "", "Acrobot"};
         return bad_arg((std::string("mgym_rollout_mlp_gauss: ") + names[e->cfg.kind] + " has discrete actions: use mgym_rollout_mlp_sample").c_str());
     }
     if (!policy) return bad_arg("mgym_rollout_mlp_gauss: policy is NULL");
@@ -345,7 +354,7 @@ int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, i
 int mgym_set_final_obs_out(mgym_env* env, float* final_obs_out, int32_t steps_cap) {
     ENV_OR_FAIL(env);
     if (final_obs_out) {
-        if (e->cfg.kind == MGYM_LUNARLANDER) return bad_arg("mgym_set_final_obs_out: final_obs_out is not offered for LunarLander yet (CartPole, MountainCar, MountainCarContinuous and Pendulum only)");
+        if (e->cfg.kind == MGYM_LUNARLANDER) return bad_arg("mgym_set_final_obs_out: final_obs_out is not offered for LunarLander yet (CartPole, MountainCar, MountainCarContinuous, Pendulum and Acrobot only)");
         if (!(e->cfg.flags & MGYM_FLAG_AUTO_RESET))
             return bad_arg("mgym_set_final_obs_out: final_obs_out on a handle without MGYM_FLAG_AUTO_RESET: obs_out already holds the final observation there");
         if (steps_cap < 1) return bad_arg("mgym_set_final_obs_out: steps_cap must be at least 1");
@@ -453,7 +462,7 @@ const char* mgym_last_error(void) { return g_last_error.c_str(); }
 int mgym_get_info(mgym_env* env, char* buf, size_t cap) {
     ENV_OR_FAIL(env);
     if (!buf || cap == 0) return bad_arg("mgym_get_info: buf is NULL or cap is 0");
-    static const char* const kinds[] = {"cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander", "pendulum"};
+    static const char* const kinds[] = {"cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander", "pendulum", "", "acrobot"};
     std::string out = std::string("kind=") + kinds[e->kind] + "\nn_envs=" + std::to_string(e->n) + "\ndevice=" + std::to_string(e->cfg.device) +
                       "\nauto_reset=" + ((e->cfg.flags & MGYM_FLAG_AUTO_RESET) ? "1" : "0") + "\nmax_episode_steps=" + std::to_string(e->cfg.max_episode_steps) +
                       "\nGPU_MAX_HW_QUEUES=" + e->hwq_env + "\n";

@@ -109,7 +109,7 @@ struct Env {
     uint64_t config_epoch = 0;   // moves whenever something changes that captured launches have frozen into their arguments (abi.hip GraphBox)
     std::string hwq_env;   // GPU_MAX_HW_QUEUES as the environment held it at mgym_create ("unset" if absent)
     // mgym_get_elapsed_steps (out) / mgym_set_elapsed_steps (in): exactly one is non-null, a device array of n uint32; CartPole's counter is blob column 4
-    virtual int elapsed(uint32_t*, const uint32_t*) { set_last_error("elapsed steps: MountainCar, Pendulum and LunarLander only (CartPole's counter is state blob column 4)"); return MGYM_ERR_BAD_ARG; }
+    virtual int elapsed(uint32_t*, const uint32_t*) { set_last_error("elapsed steps: MountainCar, Pendulum, Acrobot and LunarLander only (CartPole's counter is state blob column 4)"); return MGYM_ERR_BAD_ARG; }
     virtual int set_dispersion(const float*) { set_last_error("dispersion override: LunarLander only"); return MGYM_ERR_BAD_ARG; }
 };
 
@@ -117,5 +117,6 @@ Env* make_cartpole();
 Env* make_mountaincar(bool continuous);
 Env* make_lunarlander();
 Env* make_pendulum();
+Env* make_acrobot();
 
 }  // namespace mgym

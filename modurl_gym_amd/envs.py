@@ -23,7 +23,7 @@ from . import _lib as L
 StepInfo = namedtuple("StepInfo", ["state", "reward", "done", "truncated"])  # modurl::gym::StepInfo
 
 KIND_NAMES = {L.CARTPOLE: "CartPoleV1", L.MOUNTAINCAR: "MountainCarV0",
-              L.MOUNTAINCAR_CONT: "MountainCarContinuousV0", L.LUNARLANDER: "LunarLanderV3", L.PENDULUM: "PendulumV1"}
+              L.MOUNTAINCAR_CONT: "MountainCarContinuousV0", L.LUNARLANDER: "LunarLanderV3", L.PENDULUM: "PendulumV1", L.ACROBOT: "AcrobotV1"}
 
 
 class MgymError(RuntimeError):
@@ -204,10 +204,10 @@ class VecEnv:
 
     def rollout_linear_device(self, policy, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device linear policy (mgym_rollout_linear): policy = obs_dim weights + bias (CartPole: action 1 if the score is
-        positive; MountainCarContinuous: the score is the force; Pendulum: (w_cos, w_sin, w_thdot, b), the score is the torque), or one such row per action (MountainCar: 3 rows, LunarLander: 4 rows of 8 weights + bias;
+        positive; MountainCarContinuous: the score is the force; Pendulum: (w_cos, w_sin, w_thdot, b), the score is the torque), or one such row per action (MountainCar: 3 rows, Acrobot: 3 rows of 6 weights + bias, LunarLander: 4 rows of 8 weights + bias;
         the index of the largest score, the first of equal ones).  Host floats.  A policy of the wrong length raises PolicyShapeError (an MgymError with
         status ERR_BAD_ARG and a ValueError)."""
-        rows = {L.MOUNTAINCAR: 3, L.LUNARLANDER: 4}.get(self.kind, 1)   # a row of (weights, bias) per action for the argmax families
+        rows = {L.MOUNTAINCAR: 3, L.ACROBOT: 3, L.LUNARLANDER: 4}.get(self.kind, 1)   # a row of (weights, bias) per action for the argmax families
         n_pol = rows * (self.obs_dim + 1)
         pol_in = np.asarray(policy, np.float32).ravel()
         if pol_in.size != n_pol:
@@ -532,6 +532,15 @@ class PendulumV1(_SingleEnv):
 
     def __init__(self, device=0, g=10.0, seed=0, max_episode_steps=0):
         super().__init__(device, seed, gravity=g, max_episode_steps=max_episode_steps)
+
+
+class AcrobotV1(_SingleEnv):
+    """Not in the reference; gymnasium's Acrobot-v1 ("book" dynamics, RK4, no torque noise) in f32 as include/mgym.h defines it, parity unpinned.
+    gymnasium registers it with max_episode_steps = 500; here the limit is off unless asked for, as for every family."""
+    KIND = L.ACROBOT
+
+    def __init__(self, device=0, seed=0, max_episode_steps=0):
+        super().__init__(device, seed, max_episode_steps=max_episode_steps)
 
 
 class LunarLanderV3(_SingleEnv):

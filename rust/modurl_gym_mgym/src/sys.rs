@@ -23,6 +23,7 @@ pub const MGYM_MOUNTAINCAR: c_int = 1;
 pub const MGYM_MOUNTAINCAR_CONT: c_int = 2;
 pub const MGYM_LUNARLANDER: c_int = 3;
 pub const MGYM_PENDULUM: c_int = 4;
+pub const MGYM_ACROBOT: c_int = 6;
 
 pub const MGYM_FLAG_AUTO_RESET: u32 = 1;
 
