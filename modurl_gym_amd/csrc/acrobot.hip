@@ -12,9 +12,8 @@
 // time limit + 2 R + 2 W = 78.  A rollout keeps the eight words and the count in registers over its K steps: 10 per env-step.
 // This is the one classic family whose step is arithmetic, not traffic: four derivative evaluations with four IEEE divides each and eight f64
 // sincos pairs per environment-step.
-#include "common.h"
+#include "classic_env.h"
 #include "acrobot_step.h"
-#include "soa4.h"
 
 namespace mgym {
 
@@ -73,25 +72,6 @@ __device__ __forceinline__ void ab_store_obs4(float* o, uint64_t n, const AbEnv 
     for (int c = 0; c < 6; ++c) nt_store4(o + (uint64_t)c * n, ab_col4(e, c));
 }
 
-// a lane's four counters: one 8-byte access (i0 a multiple of 4)
-__device__ __forceinline__ void ab_load_elapsed4(const uint16_t* elapsed, uint64_t i0, uint32_t (&el)[4]) {
-    const u16x4 v = *reinterpret_cast<const u16x4*>(elapsed + i0);
-    el[0] = v.x; el[1] = v.y; el[2] = v.z; el[3] = v.w;
-}
-__device__ __forceinline__ void ab_store_elapsed4(uint16_t* elapsed, uint64_t i0, const uint32_t (&el)[4]) {
-    __builtin_nontemporal_store(u16x4{(uint16_t)el[0], (uint16_t)el[1], (uint16_t)el[2], (uint16_t)el[3]}, reinterpret_cast<u16x4*>(elapsed + i0));
-}
-
-// per-lane counts of finished envs summed over the wave, one fire-and-forget atomic per wave; the sticky invalid-action bit
-__device__ __forceinline__ void acrobot_flush_counts(const AcrobotDev& d, uint32_t finished, bool bad) {
-    for (int o = 32; o > 0; o >>= 1) finished += __shfl_down(finished, o);
-    if ((threadIdx.x & 63) == 0 && finished)
-        atomicAdd(d.done_count + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kDoneShards - 1)), (unsigned long long)finished);
-    if (__any(bad)) {
-        if ((threadIdx.x & 63) == 0) atomicOr(d.err, DEV_ERR_INVALID_ACTION);
-    }
-}
-
 // the fused reset of env i: the draws of its current episode, episode + 1 (the caller clears its count)
 __device__ __forceinline__ void acrobot_reset_env(const AcrobotDev& d, uint64_t i, AbEnv& e) {
     const uint32_t ep = d.episode[i];
@@ -121,7 +101,7 @@ acrobot_step_kernel(AcrobotDev d, const uint32_t* __restrict__ act, float* __res
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u};   // (time limit only)
         const bool full = (VEC == 1) || (i0 + VEC <= d.n);
         if constexpr (TL) {
-            if (VEC == 4) ab_load_elapsed4(d.elapsed, i0, el);   // (the column is padded: a ragged last group may load it whole)
+            if (VEC == 4) load_elapsed4(d.elapsed, i0, el);   // (the column is padded: a ragged last group may load it whole)
             else el[0] = d.elapsed[i0];
         }
         if (VEC == 4) {
@@ -156,7 +136,7 @@ acrobot_step_kernel(AcrobotDev d, const uint32_t* __restrict__ act, float* __res
             if (rew) nt_store4(rew + i0, make_float4(r[0], r[1], r[2], r[3]));
             if (done_out) __builtin_nontemporal_store(pack_bytes4(dn), reinterpret_cast<uint32_t*>(done_out + i0));
             if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + i0));
-            if constexpr (TL) ab_store_elapsed4(d.elapsed, i0, el);
+            if constexpr (TL) store_elapsed4(d.elapsed, i0, el);
         } else {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -175,7 +155,7 @@ acrobot_step_kernel(AcrobotDev d, const uint32_t* __restrict__ act, float* __res
             }
         }
     }
-    acrobot_flush_counts(d, finished, bad);
+    flush_counts(d.done_count, d.err, finished, bad);
 }
 
 // The 16-byte path (caller buffers aligned, n % 4 == 0, n <= 2^26), the form of mountaincar_step4_kernel: one lane owns 4 consecutive
@@ -206,7 +186,7 @@ acrobot_step4_kernel(float* obs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 #pragma unroll
         for (int c = 0; c < 8; ++c) v[c] = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + (uint32_t)c * colb, 0);
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u};   // (time limit only)
-        if constexpr (TL) ab_load_elapsed4(elapsed, base + lane_env, el);   // (padded to n_pad like the state columns: every lane may load)
+        if constexpr (TL) load_elapsed4(elapsed, base + lane_env, el);   // (padded to n_pad like the state columns: every lane may load)
         const bool in = lane_env < n - base;
         uint4 va = make_uint4(1u, 1u, 1u, 1u);
         if (in) va = *at<uint4>(act + base, off4);
@@ -246,7 +226,7 @@ acrobot_step4_kernel(float* obs_col, uint32_t n_pad, uint32_t n, const uint32_t*
             if (rew) nt_store4(at<float>(rew + base, off4), make_float4(r[0], r[1], r[2], r[3]));
             if (done_out) __builtin_nontemporal_store(pack_bytes4(dn), reinterpret_cast<uint32_t*>(done_out + base + lane_env));
             if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));
-            if constexpr (TL) ab_store_elapsed4(elapsed, base + lane_env, el);
+            if constexpr (TL) store_elapsed4(elapsed, base + lane_env, el);
         }
         if constexpr (ONE) break;
         base += gridDim.x * kPerBlock;   // (at most 2^23 envs a stride: no 32-bit wrap below n <= 2^26)
@@ -262,13 +242,12 @@ acrobot_step4_kernel(float* obs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 // registers for K steps; per step one 16-B action word in (TABLE) or out, reward / done / truncated (and optionally the observation) out.  Same
 // per-env function and the same in-place auto-reset as the step kernels, hence bit-identical to K separate steps.
 // The policies decide from the six observation words held before the step (acrobot_step.h); actions_out holds u32 words.
-struct AbUniformPolicy { uint64_t seed; uint32_t call; };
 template <int POLICY> using AbPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<6, 3>, AbLinearPolicy>;
 template <int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 acrobot_rollout_kernel(AcrobotDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
                        uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, AbPolicyArg<POLICY> pol = {}, uint32_t* __restrict__ act_out = nullptr,
-                       AbUniformPolicy uni = {}, Fin... fin) {
+                       UniformDraw uni = {}, Fin... fin) {
     static_assert(!roll_act_gauss(POLICY), "Acrobot has discrete actions: no Gaussian draw");
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -280,7 +259,7 @@ acrobot_rollout_kernel(AcrobotDev d, const uint32_t* __restrict__ act, int K, fl
         ab_load4(d, i0, e);
         Philox4 bits{};
         uint32_t el[4] = {0u, 0u, 0u, 0u};   // (time limit only: the count lives in registers across the K steps)
-        if constexpr (TL) ab_load_elapsed4(d.elapsed, i0, el);
+        if constexpr (TL) load_elapsed4(d.elapsed, i0, el);
         for (int t = 0; t < K; ++t) {
             const uint64_t off = (uint64_t)t * d.n + i0;
             uint32_t a[4];
@@ -333,9 +312,9 @@ acrobot_rollout_kernel(AcrobotDev d, const uint32_t* __restrict__ act, int K, fl
             if (obs_out) ab_store_obs4(obs_out + (uint64_t)t * 6 * d.n + i0, d.n, e);
         }
         ab_store4(d, i0, e);
-        if constexpr (TL) ab_store_elapsed4(d.elapsed, i0, el);
+        if constexpr (TL) store_elapsed4(d.elapsed, i0, el);
     }
-    acrobot_flush_counts(d, finished, bad);
+    flush_counts(d.done_count, d.err, finished, bad);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -344,20 +323,7 @@ acrobot_reset_kernel(AcrobotDev d, const uint8_t* __restrict__ m0, const uint8_t
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
         const uint64_t i0 = g * 4;
-        uint32_t m = 0;
-        if (all) {
-            m = 0x01010101u;
-        } else if (masks_aligned && i0 + 4 <= d.n) {
-            if (m0) m |= *reinterpret_cast<const uint32_t*>(m0 + i0);
-            if (m1) m |= *reinterpret_cast<const uint32_t*>(m1 + i0);
-        } else {
-            for (int k = 0; k < 4 && i0 + k < d.n; ++k) {
-                uint32_t b = 0;
-                if (m0) b |= m0[i0 + k];
-                if (m1) b |= m1[i0 + k];
-                m |= (b ? 1u : 0u) << (8 * k);
-            }
-        }
+        const uint32_t m = reset_mask4(m0, m1, all, masks_aligned, i0, d.n);
         if (m == 0) continue;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -412,71 +378,34 @@ __global__ void acrobot_import_kernel(AcrobotDev d, const uint32_t* __restrict__
     d.elapsed[i] = 0;   // an imported state starts its count at 0 (mgym_set_elapsed_steps overrides)
 }
 
-__global__ void acrobot_get_elapsed_kernel(AcrobotDev d, uint32_t* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < d.n) out[i] = d.elapsed[i];
-}
-
-__global__ void acrobot_set_elapsed_kernel(AcrobotDev d, const uint32_t* __restrict__ in) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < d.n) d.elapsed[i] = (uint16_t)tl_clamp(in[i]);
-}
-
-struct AcrobotEnv final : Env {
-    void* base = nullptr;
-    void* el_base = nullptr;   // elapsed[n_pad] u16
+struct AcrobotEnv final : ClassicEnv {
     AcrobotDev dev{};
-    int max_blocks = classic_max_blocks(kMaxBlocks);  // block cap of the 16-byte step kernel (MGYM_CLASSIC_MAX_BLOCKS lowers it)
-
-    ~AcrobotEnv() override {
-        if (base) (void)hipFree(base);
-        if (el_base) (void)hipFree(el_base);
-    }
 
     int init() override {
         obs_dim = 6;
         state_cols = 5;
-        MGYM_HIP(hipMalloc(&base, 9 * n_pad * sizeof(float)));
-        MGYM_HIP(hipMemsetAsync(base, 0, 9 * n_pad * sizeof(float), stream));
-        float* f = static_cast<float*>(base);
+        if (const int st = alloc(9)) return st;
+        float* f = cols;
         MGYM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f), 0x3f800000, n_pad, stream));               // th1 = 0: cos = 1
         MGYM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f + 2 * n_pad), 0x3f800000, n_pad, stream));   // th2 = 0: cos = 1
         dev.obs = f; dev.n_pad = n_pad;
         dev.episode = reinterpret_cast<uint32_t*>(f + 8 * n_pad);
-        dev.n = n; dev.seed = cfg.seed; dev.env_id_base = cfg.env_id_base; dev.err = d_err; dev.done_count = d_done;
-        dev.auto_reset = (cfg.flags & MGYM_FLAG_AUTO_RESET) ? 1 : 0;
-        MGYM_HIP(hipMalloc(&el_base, n_pad * sizeof(uint16_t)));
-        MGYM_HIP(hipMemsetAsync(el_base, 0, n_pad * sizeof(uint16_t), stream));
-        dev.elapsed = static_cast<uint16_t*>(el_base);
-        dev.limit = cfg.max_episode_steps;
+        fill_common(dev);
         return MGYM_OK;
     }
 
-    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override {
-        if (n == 0) return MGYM_OK;
-        const int al = aligned(m0, 4) && aligned(m1, 4);
-        hipLaunchKernelGGL(acrobot_reset_kernel, dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, stream, dev, m0, m1, all ? 1 : 0, al, obs_out);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int reset_deterministic(float* obs_out) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(acrobot_zero_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, dev, obs_out);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override { return launch_reset(acrobot_reset_kernel, dev, m0, m1, all, obs_out); }
+    int reset_deterministic(float* obs_out) override { return launch_per_env(acrobot_zero_kernel, dev, obs_out); }
 
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        const bool vec_ok = aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && (obs_out == nullptr || (aligned(obs_out, 16) && n % 4 == 0));
+        const bool vec = vec_ok(act, obs_out, reward, done, trunc);
         const dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
         const bool tl = dev.limit != 0u;
-        if (vec_ok && n % 4 == 0 && n <= (1ull << 26)) {  // the structured 16-byte kernel
-            const uint64_t nb = (n + 4 * kBlock - 1) / (4 * kBlock);   // tiles
-            const bool one = nb <= (uint64_t)max_blocks;               // one block per tile: the single-pass form
-            const dim3 g((unsigned)(one ? nb : (uint64_t)max_blocks));
+        if (vec && n % 4 == 0 && n <= (1ull << 26)) {  // the structured 16-byte kernel
+            dim3 g;
+            const bool one = step4_grid(g);
             if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
                 with_bools([&](auto T, auto O) {
                     hipLaunchKernelGGL((acrobot_step4_kernel<true, decltype(T)::value, decltype(O)::value, float*>), g, b, 0, stream, dev.obs, (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed,
@@ -496,7 +425,7 @@ struct AcrobotEnv final : Env {
             constexpr int VEC = decltype(V)::value ? 4 : 1;
             if (final_obs) hipLaunchKernelGGL((acrobot_step_kernel<VEC, decltype(T)::value, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
             else hipLaunchKernelGGL((acrobot_step_kernel<VEC, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }, tl, vec_ok);
+        }, tl, vec);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
@@ -504,18 +433,13 @@ struct AcrobotEnv final : Env {
     // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the categorical draw's seed and call word
     template <int POLICY, bool TL>
     void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
-                        const AbPolicyArg<POLICY>& arg = AbPolicyArg<POLICY>{}, AbUniformPolicy uni = {}) {
+                        const AbPolicyArg<POLICY>& arg = AbPolicyArg<POLICY>{}, UniformDraw uni = {}) {
         if (final_obs) hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, final_obs);
         else hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
-    int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        const uint32_t* act = static_cast<const uint32_t*>(actions);
-        if (!fused_rollout_args_ok(nullptr, n, K, false, act, obs_out, reward, done, trunc)) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
+    void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         with_bools([&](auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); }, dev.limit != 0u);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
     }
 
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
@@ -527,7 +451,7 @@ struct AcrobotEnv final : Env {
             constexpr bool TL = decltype(T)::value;
             switch (call.source) {
             case ROLL_ACT_UNIFORM:
-                launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, AbLinearPolicy{}, AbUniformPolicy{call.seed, uniform_calls++});
+                launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, AbLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});
                 break;
             case ROLL_ACT_LINEAR: {
                 AbLinearPolicy lin{};   // weights: 3 rows of (6 weights, bias)
@@ -544,7 +468,7 @@ struct AcrobotEnv final : Env {
                 with_bools([&](auto H, auto S) {
                     constexpr bool TANH = decltype(H)::value;
                     if constexpr (!decltype(S)::value) launch_rollout<TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
-                    else launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, AbUniformPolicy{call.seed, call.call});
+                    else launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
                 }, roll_act_mlp_tanh(call.source), roll_act_samples(call.source));
             }
             }
@@ -553,34 +477,8 @@ struct AcrobotEnv final : Env {
         return MGYM_OK;
     }
 
-    int observation(const float** obs, uint64_t* col_stride) override {
-        *obs = dev.obs;
-        *col_stride = n_pad;
-        return MGYM_OK;
-    }
-
-    int get_state(void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(acrobot_export_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, dev, static_cast<uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int set_state(const void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(acrobot_import_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, dev, static_cast<const uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int elapsed(uint32_t* out, const uint32_t* in) override {
-        if (n == 0) return MGYM_OK;
-        const dim3 g((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
-        if (out) hipLaunchKernelGGL(acrobot_get_elapsed_kernel, g, b, 0, stream, dev, out);
-        else hipLaunchKernelGGL(acrobot_set_elapsed_kernel, g, b, 0, stream, dev, in);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int get_state(void* blob) override { return launch_per_env(acrobot_export_kernel, dev, static_cast<uint32_t*>(blob)); }
+    int set_state(const void* blob) override { return launch_per_env(acrobot_import_kernel, dev, static_cast<const uint32_t*>(blob)); }
 };
 
 Env* make_acrobot() { return new AcrobotEnv(); }

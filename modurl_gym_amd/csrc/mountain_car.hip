@@ -15,11 +15,10 @@
 // 8-byte access, read and written by the time-limited instantiations only (TL = true: mgym_step 26 + 2 R + 2 W = 30 B per env-step; a rollout
 // keeps the count in registers, one read and one write per launch).  A handle without a limit launches the TL = false instantiations, which
 // are the kernels as they were: the count is then left alone (0 after a reset, not advanced).
-#include "common.h"
+#include "classic_env.h"
 #include "mgym_math.h"
 #include "mlp_policy.h"
 #include "philox.h"
-#include "soa4.h"
 #include "time_limit.h"
 
 namespace mgym {
@@ -45,25 +44,6 @@ struct MountainCarDev {
     uint16_t* elapsed;   // caller-visible steps since the env's last reset, saturating at 65535 (padded to n_pad like the state columns)
     uint32_t limit;      // max_episode_steps; 0: off
 };
-
-// a lane's four counters: one 8-byte access (i0 a multiple of 4)
-__device__ __forceinline__ void mc_load_elapsed4(const MountainCarDev& d, uint64_t i0, uint32_t (&el)[4]) {
-    const u16x4 v = *reinterpret_cast<const u16x4*>(d.elapsed + i0);
-    el[0] = v.x; el[1] = v.y; el[2] = v.z; el[3] = v.w;
-}
-__device__ __forceinline__ void mc_store_elapsed4(const MountainCarDev& d, uint64_t i0, const uint32_t (&el)[4]) {
-    __builtin_nontemporal_store(u16x4{(uint16_t)el[0], (uint16_t)el[1], (uint16_t)el[2], (uint16_t)el[3]}, reinterpret_cast<u16x4*>(d.elapsed + i0));
-}
-
-// done-mask reduction: per-lane counts of finished envs summed over the wave, one fire-and-forget atomic per wave
-__device__ __forceinline__ void mountaincar_flush_counts(const MountainCarDev& d, uint32_t finished, bool bad) {
-    for (int o = 32; o > 0; o >>= 1) finished += __shfl_down(finished, o);
-    if ((threadIdx.x & 63) == 0 && finished)
-        atomicAdd(d.done_count + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kDoneShards - 1)), (unsigned long long)finished);
-    if (__any(bad)) {
-        if ((threadIdx.x & 63) == 0) atomicOr(d.err, DEV_ERR_INVALID_ACTION);
-    }
-}
 
 // f32::clamp: if self < min {min} else if self > max {max} else {self}
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -124,7 +104,7 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u};   // (time limit only)
         const bool full = (VEC == 1) || (i0 + VEC <= d.n);
         if constexpr (TL) {
-            if (VEC == 4) mc_load_elapsed4(d, i0, el);   // (the column is padded: a ragged last group may load it whole)
+            if (VEC == 4) load_elapsed4(d.elapsed, i0, el);   // (the column is padded: a ragged last group may load it whole)
             else el[0] = d.elapsed[i0];
         }
         if (VEC == 4 && full) {
@@ -171,7 +151,7 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
                 __builtin_nontemporal_store(pack_bytes4(dn4), reinterpret_cast<uint32_t*>(done_out + i0));
             }
             if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + i0));  // :328 truncated: false, always (TL: the time limit)
-            if constexpr (TL) mc_store_elapsed4(d, i0, el);
+            if constexpr (TL) store_elapsed4(d.elapsed, i0, el);
         } else {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -187,7 +167,7 @@ mountaincar_step_kernel(MountainCarDev d, const uint32_t* __restrict__ act, floa
             }
         }
     }
-    mountaincar_flush_counts(d, finished, bad);
+    flush_counts(d.done_count, d.err, finished, bad);
 }
 
 // The 16-byte path (caller buffers aligned, n % 4 == 0): one lane owns 4 consecutive environments; block-uniform passes;
@@ -222,7 +202,7 @@ mountaincar_step4_kernel(float* pos, uint32_t n_pad, uint32_t n, const uint32_t*
         const u32x4 vp = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb, 0);
         const u32x4 vv = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + colb, 0);
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u}, fin[4];   // (el / tr: time limit only)
-        if constexpr (TL) mc_load_elapsed4(d, base + lane_env, el);            // (padded to n_pad like the state columns: every lane may load)
+        if constexpr (TL) load_elapsed4(d.elapsed, base + lane_env, el);            // (padded to n_pad like the state columns: every lane may load)
         const bool in = lane_env < n - base;
         uint4 va = CONT ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(1u, 1u, 1u, 1u);
         if (in) va = *at<uint4>(act + base, off4);
@@ -259,7 +239,7 @@ mountaincar_step4_kernel(float* pos, uint32_t n_pad, uint32_t n, const uint32_t*
             if (rew) nt_store4(at<float>(rew + base, off4), make_float4(r[0], r[1], r[2], r[3]));
             if (done_out) __builtin_nontemporal_store(pack_bytes4(dn), reinterpret_cast<uint32_t*>(done_out + base + lane_env));
             if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));  // :328 truncated: false, always (TL: the time limit)
-            if constexpr (TL) mc_store_elapsed4(d, base + lane_env, el);
+            if constexpr (TL) store_elapsed4(d.elapsed, base + lane_env, el);
         }
         if constexpr (ONE) break;
         base += gridDim.x * kPerBlock;   // (at most 2^23 envs a stride: no 32-bit wrap below n <= 2^27)
@@ -278,16 +258,15 @@ mountaincar_step4_kernel(float* pos, uint32_t n_pad, uint32_t n, const uint32_t*
 // the three scores s_j = (w[j][0] * position + w[j][1] * velocity) + b[j] (the first of equal ones); Box(-1, 1): the one score itself as the force (the
 // step clamps it like any action).  f32, in that order, nothing fused.
 struct McLinearPolicy { float w[3][2], b[3]; };
-// mgym_rollout_uniform: the lane's four envs (global ids g .. g + 3, g a multiple of 4) share one Philox stream keyed by the policy seed, counter =
+// mgym_rollout_uniform (UniformDraw, policy.h): the lane's four envs (global ids g .. g + 3, g a multiple of 4) share one Philox stream keyed by the policy seed, counter =
 // (g, number of earlier mgym_rollout_uniform calls on this handle, SLOT_POLICY + block).  Discrete(3): step t takes, for env g + k, half (t % 2) of word k
 // of block t / 2 (low half first), h, and the action (3 h) >> 16 — each action within 2^-16 of 1/3.  Box(-1, 1): word k of block t, top 24 bits u:
 // the force u 2^-23 - 1, uniform over the multiples of 2^-23 in [-1, 1).
-struct McUniformPolicy { uint64_t seed; uint32_t call; };
 // mgym_rollout_mlp: the weight pack of mlp_policy.h (A = 3 scores, or the one force of MountainCarContinuous) takes the place of the linear words in the
 // kernel's arguments; the other policies' instantiations keep the arguments they had
 template <bool CONT, int POLICY> using McPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<2, CONT ? 1 : 3>, McLinearPolicy>;
 // mgym_rollout_mlp_gauss (MountainCarContinuous only): sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
-template <int POLICY> using McDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, McUniformPolicy>;
+template <int POLICY> using McDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, UniformDraw>;
 template <bool CONT, int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
@@ -304,7 +283,7 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
         float ps[4] = {vp.x, vp.y, vp.z, vp.w}, vs[4] = {vv.x, vv.y, vv.z, vv.w};
         Philox4 bits{};
         uint32_t el[4] = {0u, 0u, 0u, 0u};   // (time limit only: the count lives in registers across the K steps)
-        if constexpr (TL) mc_load_elapsed4(d, i0, el);
+        if constexpr (TL) load_elapsed4(d.elapsed, i0, el);
         for (int t = 0; t < K; ++t) {
             const uint64_t off = (uint64_t)t * d.n + i0;
             uint32_t a[4], dn[4];
@@ -378,9 +357,9 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
         }
         nt_store4(d.pos + i0, make_float4(ps[0], ps[1], ps[2], ps[3]));
         nt_store4(d.vel + i0, make_float4(vs[0], vs[1], vs[2], vs[3]));
-        if constexpr (TL) mc_store_elapsed4(d, i0, el);
+        if constexpr (TL) store_elapsed4(d.elapsed, i0, el);
     }
-    mountaincar_flush_counts(d, finished, bad);
+    flush_counts(d.done_count, d.err, finished, bad);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -390,20 +369,7 @@ mountaincar_reset_kernel(MountainCarDev d, const uint8_t* __restrict__ m0, const
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
         const uint64_t i0 = g * 4;
-        uint32_t m = 0;
-        if (all) {
-            m = 0x01010101u;
-        } else if (masks_aligned && i0 + 4 <= d.n) {
-            if (m0) m |= *reinterpret_cast<const uint32_t*>(m0 + i0);
-            if (m1) m |= *reinterpret_cast<const uint32_t*>(m1 + i0);
-        } else {
-            for (int k = 0; k < 4 && i0 + k < d.n; ++k) {
-                uint32_t b = 0;
-                if (m0) b |= m0[i0 + k];
-                if (m1) b |= m1[i0 + k];
-                m |= (b ? 1u : 0u) << (8 * k);
-            }
-        }
+        const uint32_t m = reset_mask4(m0, m1, all, masks_aligned, i0, d.n);
         if (m == 0) continue;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -436,56 +402,24 @@ __global__ void mountaincar_import_kernel(MountainCarDev d, const uint32_t* __re
     d.elapsed[i] = 0;   // the blob stays 3 columns: an imported state starts its count at 0 (mgym_set_elapsed_steps overrides)
 }
 
-__global__ void mountaincar_get_elapsed_kernel(MountainCarDev d, uint32_t* __restrict__ out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < d.n) out[i] = d.elapsed[i];
-}
-
-__global__ void mountaincar_set_elapsed_kernel(MountainCarDev d, const uint32_t* __restrict__ in) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < d.n) d.elapsed[i] = (uint16_t)tl_clamp(in[i]);
-}
-
-struct MountainCarEnv final : Env {
+struct MountainCarEnv final : ClassicEnv {
     bool continuous;
-    void* base = nullptr;
-    void* el_base = nullptr;   // elapsed[n_pad] u16
     MountainCarDev dev{};
 
     explicit MountainCarEnv(bool c) : continuous(c) {}
-    ~MountainCarEnv() override {
-        if (base) (void)hipFree(base);
-        if (el_base) (void)hipFree(el_base);
-    }
 
-    bool use_step4 = !getenv("MGYM_MC_OLD_KERNEL");  // A/B knob: the per-thread grid-stride kernel of round 1
-    int max_blocks = classic_max_blocks(kMaxBlocks);  // block cap of the 16-byte step kernel (MGYM_CLASSIC_MAX_BLOCKS lowers it)
     int init() override {
         obs_dim = 2;
         state_cols = 3;
-        MGYM_HIP(hipMalloc(&base, 3 * n_pad * sizeof(float)));
-        MGYM_HIP(hipMemsetAsync(base, 0, 3 * n_pad * sizeof(float), stream));  // mountain_car.rs:51 zeros
-        float* f = static_cast<float*>(base);
-        dev.pos = f; dev.vel = f + n_pad;
-        dev.episode = reinterpret_cast<uint32_t*>(f + 2 * n_pad);
-        dev.n = n; dev.seed = cfg.seed; dev.env_id_base = cfg.env_id_base; dev.err = d_err; dev.done_count = d_done;
-        dev.auto_reset = (cfg.flags & MGYM_FLAG_AUTO_RESET) ? 1 : 0;
-        MGYM_HIP(hipMalloc(&el_base, n_pad * sizeof(uint16_t)));
-        MGYM_HIP(hipMemsetAsync(el_base, 0, n_pad * sizeof(uint16_t), stream));
-        dev.elapsed = static_cast<uint16_t*>(el_base);
-        dev.limit = cfg.max_episode_steps;
+        if (const int st = alloc(3)) return st;  // mountain_car.rs:51 zeros
+        dev.pos = cols; dev.vel = cols + n_pad;
+        dev.episode = reinterpret_cast<uint32_t*>(cols + 2 * n_pad);
+        fill_common(dev);
         dev.p = mc_params(continuous, cfg.goal_velocity);
         return MGYM_OK;
     }
 
-    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override {
-        if (n == 0) return MGYM_OK;
-        int al = aligned(m0, 4) && aligned(m1, 4);
-        hipLaunchKernelGGL(mountaincar_reset_kernel, dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, stream, dev, m0, m1,
-                           all ? 1 : 0, al, obs_out);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override { return launch_reset(mountaincar_reset_kernel, dev, m0, m1, all, obs_out); }
 
     int reset_deterministic(float* obs_out) override {  // mountain_car.rs:403-408: state = zeros (no reset())
         if (n == 0) return MGYM_OK;
@@ -498,14 +432,12 @@ struct MountainCarEnv final : Env {
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        bool vec_ok = aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) &&
-                      (obs_out == nullptr || (aligned(obs_out, 16) && n % 4 == 0));
+        const bool vec = vec_ok(act, obs_out, reward, done, trunc);
         dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
         const bool tl = dev.limit != 0u;
-        if (vec_ok && n % 4 == 0 && n <= (1ull << 27) && use_step4) {  // the structured 16-byte kernel
-            const uint64_t nb = (n + 4 * kBlock - 1) / (4 * kBlock);   // tiles
-            const bool one = nb <= (uint64_t)max_blocks;               // one block per tile: the single-pass form
-            const dim3 g((unsigned)(one ? nb : (uint64_t)max_blocks));
+        if (vec && n % 4 == 0 && n <= (1ull << 27)) {  // the structured 16-byte kernel
+            dim3 g;
+            const bool one = step4_grid(g);
             if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
                 with_bools([&](auto C, auto T, auto O) {
                     hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, true, decltype(T)::value, decltype(O)::value, float*>), g, b, 0, stream, dev.pos, (uint32_t)n_pad,
@@ -527,7 +459,7 @@ struct MountainCarEnv final : Env {
             constexpr int VEC = decltype(V)::value ? 4 : 1;
             if (final_obs) hipLaunchKernelGGL((mountaincar_step_kernel<VEC, decltype(C)::value, decltype(T)::value, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
             else hipLaunchKernelGGL((mountaincar_step_kernel<VEC, decltype(C)::value, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }, continuous, tl, vec_ok);
+        }, continuous, tl, vec);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
@@ -540,14 +472,9 @@ struct MountainCarEnv final : Env {
         else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
-    int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        const uint32_t* act = static_cast<const uint32_t*>(actions);
-        if (!fused_rollout_args_ok(nullptr, n, K, false, act, obs_out, reward, done, trunc)) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
+    void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         with_bools([&](auto C, auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(C)::value, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); },
                    continuous, dev.limit != 0u);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
     }
 
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
@@ -558,7 +485,7 @@ struct MountainCarEnv final : Env {
             constexpr bool CONT = decltype(C)::value, TL = decltype(T)::value;
             switch (call.source) {
             case ROLL_ACT_UNIFORM:
-                launch_rollout<ROLL_ACT_UNIFORM, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, McLinearPolicy{}, McUniformPolicy{call.seed, uniform_calls++});
+                launch_rollout<ROLL_ACT_UNIFORM, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, McLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});
                 break;
             case ROLL_ACT_LINEAR: {
                 McLinearPolicy lin{};
@@ -582,7 +509,7 @@ struct MountainCarEnv final : Env {
                     constexpr bool TANH = decltype(H)::value;
                     if constexpr (!decltype(S)::value) launch_rollout<TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
                     else if constexpr (!CONT)   // (the C ABI rejects mgym_rollout_mlp_sample on MountainCarContinuous)
-                        launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, McUniformPolicy{call.seed, call.call});
+                        launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
                 }, roll_act_mlp_tanh(call.source), roll_act_samples(call.source));
             }
             }
@@ -591,36 +518,8 @@ struct MountainCarEnv final : Env {
         return MGYM_OK;
     }
 
-    int observation(const float** obs, uint64_t* col_stride) override {
-        *obs = dev.pos;
-        *col_stride = n_pad;
-        return MGYM_OK;
-    }
-
-    int get_state(void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(mountaincar_export_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                           stream, dev, static_cast<uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int set_state(const void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(mountaincar_import_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                           stream, dev, static_cast<const uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int elapsed(uint32_t* out, const uint32_t* in) override {
-        if (n == 0) return MGYM_OK;
-        const dim3 g((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
-        if (out) hipLaunchKernelGGL(mountaincar_get_elapsed_kernel, g, b, 0, stream, dev, out);
-        else hipLaunchKernelGGL(mountaincar_set_elapsed_kernel, g, b, 0, stream, dev, in);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int get_state(void* blob) override { return launch_per_env(mountaincar_export_kernel, dev, static_cast<uint32_t*>(blob)); }
+    int set_state(const void* blob) override { return launch_per_env(mountaincar_import_kernel, dev, static_cast<const uint32_t*>(blob)); }
 };
 
 Env* make_mountaincar(bool continuous) { return new MountainCarEnv(continuous); }

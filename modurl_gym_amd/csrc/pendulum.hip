@@ -8,9 +8,8 @@
 // owns 4 consecutive environments (16-byte accesses).  The step reads the stored sin word as sinf(th) instead of reducing th a second time.
 // Algorithmic bytes per env-step of mgym_step: 38 (th, thdot, sin 12 R; cos, sin, thdot, th 16 W; action 4 R; reward 4 W; done 1 W; truncated
 // 1 W), with a time limit + 2 R + 2 W = 42.  A rollout keeps th, thdot, cos, sin and the count in registers over its K steps: 10 per env-step.
-#include "common.h"
+#include "classic_env.h"
 #include "pendulum_step.h"
-#include "soa4.h"
 
 namespace mgym {
 
@@ -25,25 +24,6 @@ struct PendulumDev {
     uint16_t* elapsed;   // caller-visible steps since the env's last reset, saturating at 65535 (padded to n_pad like the state columns)
     uint32_t limit;      // max_episode_steps; 0: off
 };
-
-// a lane's four counters: one 8-byte access (i0 a multiple of 4)
-__device__ __forceinline__ void pd_load_elapsed4(const uint16_t* elapsed, uint64_t i0, uint32_t (&el)[4]) {
-    const u16x4 v = *reinterpret_cast<const u16x4*>(elapsed + i0);
-    el[0] = v.x; el[1] = v.y; el[2] = v.z; el[3] = v.w;
-}
-__device__ __forceinline__ void pd_store_elapsed4(uint16_t* elapsed, uint64_t i0, const uint32_t (&el)[4]) {
-    __builtin_nontemporal_store(u16x4{(uint16_t)el[0], (uint16_t)el[1], (uint16_t)el[2], (uint16_t)el[3]}, reinterpret_cast<u16x4*>(elapsed + i0));
-}
-
-// per-lane counts of finished envs summed over the wave, one fire-and-forget atomic per wave; the sticky invalid-action bit
-__device__ __forceinline__ void pendulum_flush_counts(const PendulumDev& d, uint32_t finished, bool bad) {
-    for (int o = 32; o > 0; o >>= 1) finished += __shfl_down(finished, o);
-    if ((threadIdx.x & 63) == 0 && finished)
-        atomicAdd(d.done_count + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kDoneShards - 1)), (unsigned long long)finished);
-    if (__any(bad)) {
-        if ((threadIdx.x & 63) == 0) atomicOr(d.err, DEV_ERR_INVALID_ACTION);
-    }
-}
 
 // the fused reset of env i: the draw of its current episode, episode + 1 (the caller clears its count)
 __device__ __forceinline__ void pendulum_reset_env(const PendulumDev& d, uint64_t i, float& th, float& thdot, float& cs, float& sn) {
@@ -69,7 +49,7 @@ pendulum_step_kernel(PendulumDev d, const uint32_t* __restrict__ act, float* __r
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u};   // (time limit only)
         const bool full = (VEC == 1) || (i0 + VEC <= d.n);
         if constexpr (TL) {
-            if (VEC == 4) pd_load_elapsed4(d.elapsed, i0, el);   // (the column is padded: a ragged last group may load it whole)
+            if (VEC == 4) load_elapsed4(d.elapsed, i0, el);   // (the column is padded: a ragged last group may load it whole)
             else el[0] = d.elapsed[i0];
         }
         if (VEC == 4 && full) {
@@ -118,7 +98,7 @@ pendulum_step_kernel(PendulumDev d, const uint32_t* __restrict__ act, float* __r
             if (rew) nt_store4(rew + i0, make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]));
             if (done_out) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(done_out + i0));   // done = 0, always
             if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + i0));
-            if constexpr (TL) pd_store_elapsed4(d.elapsed, i0, el);
+            if constexpr (TL) store_elapsed4(d.elapsed, i0, el);
         } else {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -134,7 +114,7 @@ pendulum_step_kernel(PendulumDev d, const uint32_t* __restrict__ act, float* __r
             }
         }
     }
-    pendulum_flush_counts(d, finished, bad);
+    flush_counts(d.done_count, d.err, finished, bad);
 }
 
 // The 16-byte path (caller buffers aligned, n % 4 == 0, n <= 2^27), the form of mountaincar_step4_kernel: one lane owns 4 consecutive
@@ -166,7 +146,7 @@ pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t*
         const u32x4 vd = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + 2u * colb, 0);
         const u32x4 vt = __builtin_amdgcn_raw_buffer_load_b128(rs, off4, sb + 3u * colb, 0);
         uint32_t el[4] = {0u, 0u, 0u, 0u}, tr[4] = {0u, 0u, 0u, 0u};   // (time limit only)
-        if constexpr (TL) pd_load_elapsed4(elapsed, base + lane_env, el);   // (padded to n_pad like the state columns: every lane may load)
+        if constexpr (TL) load_elapsed4(elapsed, base + lane_env, el);   // (padded to n_pad like the state columns: every lane may load)
         const bool in = lane_env < n - base;
         uint4 va = make_uint4(0u, 0u, 0u, 0u);
         if (in) va = *at<uint4>(act + base, off4);
@@ -217,7 +197,7 @@ pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t*
             if (rew) nt_store4(at<float>(rew + base, off4), make_float4(r[0], r[1], r[2], r[3]));
             if (done_out) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t*>(done_out + base + lane_env));   // done = 0, always
             if (trunc_out) __builtin_nontemporal_store(pack_bytes4(tr), reinterpret_cast<uint32_t*>(trunc_out + base + lane_env));
-            if constexpr (TL) pd_store_elapsed4(elapsed, base + lane_env, el);
+            if constexpr (TL) store_elapsed4(elapsed, base + lane_env, el);
         }
         if constexpr (ONE) break;
         base += gridDim.x * kPerBlock;   // (at most 2^23 envs a stride: no 32-bit wrap below n <= 2^27)
@@ -233,10 +213,9 @@ pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 // for K steps; per step one 16-B action word in (TABLE) or out, reward / done / truncated (and optionally the observation) out.  Same per-env
 // function and the same in-place auto-reset as the step kernels, hence bit-identical to K separate steps.  One sincos per environment-step.
 // The policies decide from (cos, sin, thdot) held before the step (pendulum_step.h); actions_out holds f32 words.
-struct PdUniformPolicy { uint64_t seed; uint32_t call; };
 template <int POLICY> using PdPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<3, 1>, PdLinearPolicy>;
 // mgym_rollout_mlp_gauss: sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
-template <int POLICY> using PdDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, PdUniformPolicy>;
+template <int POLICY> using PdDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, UniformDraw>;
 template <int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
@@ -253,7 +232,7 @@ pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, 
         const float4 v2 = *reinterpret_cast<const float4*>(d.cs + i0), v3 = *reinterpret_cast<const float4*>(d.sn + i0);
         float th[4] = {v0.x, v0.y, v0.z, v0.w}, td[4] = {v1.x, v1.y, v1.z, v1.w}, cs[4] = {v2.x, v2.y, v2.z, v2.w}, sn[4] = {v3.x, v3.y, v3.z, v3.w};
         uint32_t el[4] = {0u, 0u, 0u, 0u};   // (time limit only: the count lives in registers across the K steps)
-        if constexpr (TL) pd_load_elapsed4(d.elapsed, i0, el);
+        if constexpr (TL) load_elapsed4(d.elapsed, i0, el);
         for (int t = 0; t < K; ++t) {
             const uint64_t off = (uint64_t)t * d.n + i0;
             uint32_t a[4];
@@ -301,9 +280,9 @@ pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, 
         nt_store4(d.sn + i0, make_float4(sn[0], sn[1], sn[2], sn[3]));
         nt_store4(d.thdot + i0, make_float4(td[0], td[1], td[2], td[3]));
         nt_store4(d.th + i0, make_float4(th[0], th[1], th[2], th[3]));
-        if constexpr (TL) pd_store_elapsed4(d.elapsed, i0, el);
+        if constexpr (TL) store_elapsed4(d.elapsed, i0, el);
     }
-    pendulum_flush_counts(d, finished, bad);
+    flush_counts(d.done_count, d.err, finished, bad);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -312,20 +291,7 @@ pendulum_reset_kernel(PendulumDev d, const uint8_t* __restrict__ m0, const uint8
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
         const uint64_t i0 = g * 4;
-        uint32_t m = 0;
-        if (all) {
-            m = 0x01010101u;
-        } else if (masks_aligned && i0 + 4 <= d.n) {
-            if (m0) m |= *reinterpret_cast<const uint32_t*>(m0 + i0);
-            if (m1) m |= *reinterpret_cast<const uint32_t*>(m1 + i0);
-        } else {
-            for (int k = 0; k < 4 && i0 + k < d.n; ++k) {
-                uint32_t b = 0;
-                if (m0) b |= m0[i0 + k];
-                if (m1) b |= m1[i0 + k];
-                m |= (b ? 1u : 0u) << (8 * k);
-            }
-        }
+        const uint32_t m = reset_mask4(m0, m1, all, masks_aligned, i0, d.n);
         if (m == 0) continue;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -371,71 +337,34 @@ __global__ void pendulum_import_kernel(PendulumDev d, const uint32_t* __restrict
     d.elapsed[i] = 0;   // the blob stays 3 columns: an imported state starts its count at 0 (mgym_set_elapsed_steps overrides)
 }
 
-__global__ void pendulum_get_elapsed_kernel(PendulumDev d, uint32_t* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < d.n) out[i] = d.elapsed[i];
-}
-
-__global__ void pendulum_set_elapsed_kernel(PendulumDev d, const uint32_t* __restrict__ in) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < d.n) d.elapsed[i] = (uint16_t)tl_clamp(in[i]);
-}
-
-struct PendulumEnv final : Env {
-    void* base = nullptr;
-    void* el_base = nullptr;   // elapsed[n_pad] u16
+struct PendulumEnv final : ClassicEnv {
     PendulumDev dev{};
-    int max_blocks = classic_max_blocks(kMaxBlocks);  // block cap of the 16-byte step kernel (MGYM_CLASSIC_MAX_BLOCKS lowers it)
-
-    ~PendulumEnv() override {
-        if (base) (void)hipFree(base);
-        if (el_base) (void)hipFree(el_base);
-    }
 
     int init() override {
         obs_dim = 3;
         state_cols = 3;
-        MGYM_HIP(hipMalloc(&base, 5 * n_pad * sizeof(float)));
-        MGYM_HIP(hipMemsetAsync(base, 0, 5 * n_pad * sizeof(float), stream));
-        float* f = static_cast<float*>(base);
+        if (const int st = alloc(5)) return st;
+        float* f = cols;
         MGYM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f), 0x3f800000, n_pad, stream));   // th = 0: cos = 1
         dev.cs = f; dev.sn = f + n_pad; dev.thdot = f + 2 * n_pad; dev.th = f + 3 * n_pad;
         dev.episode = reinterpret_cast<uint32_t*>(f + 4 * n_pad);
-        dev.n = n; dev.seed = cfg.seed; dev.env_id_base = cfg.env_id_base; dev.err = d_err; dev.done_count = d_done;
-        dev.auto_reset = (cfg.flags & MGYM_FLAG_AUTO_RESET) ? 1 : 0;
-        MGYM_HIP(hipMalloc(&el_base, n_pad * sizeof(uint16_t)));
-        MGYM_HIP(hipMemsetAsync(el_base, 0, n_pad * sizeof(uint16_t), stream));
-        dev.elapsed = static_cast<uint16_t*>(el_base);
-        dev.limit = cfg.max_episode_steps;
+        fill_common(dev);
         dev.c_g = pendulum_c_g(cfg.gravity);
         return MGYM_OK;
     }
 
-    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override {
-        if (n == 0) return MGYM_OK;
-        const int al = aligned(m0, 4) && aligned(m1, 4);
-        hipLaunchKernelGGL(pendulum_reset_kernel, dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, stream, dev, m0, m1, all ? 1 : 0, al, obs_out);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int reset_deterministic(float* obs_out) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(pendulum_zero_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, dev, obs_out);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override { return launch_reset(pendulum_reset_kernel, dev, m0, m1, all, obs_out); }
+    int reset_deterministic(float* obs_out) override { return launch_per_env(pendulum_zero_kernel, dev, obs_out); }
 
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        const bool vec_ok = aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && (obs_out == nullptr || (aligned(obs_out, 16) && n % 4 == 0));
+        const bool vec = vec_ok(act, obs_out, reward, done, trunc);
         const dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
         const bool tl = dev.limit != 0u;
-        if (vec_ok && n % 4 == 0 && n <= (1ull << 27)) {  // the structured 16-byte kernel
-            const uint64_t nb = (n + 4 * kBlock - 1) / (4 * kBlock);   // tiles
-            const bool one = nb <= (uint64_t)max_blocks;               // one block per tile: the single-pass form
-            const dim3 g((unsigned)(one ? nb : (uint64_t)max_blocks));
+        if (vec && n % 4 == 0 && n <= (1ull << 27)) {  // the structured 16-byte kernel
+            dim3 g;
+            const bool one = step4_grid(g);
             if (final_live()) {
                 with_bools([&](auto O) {
                     hipLaunchKernelGGL((pendulum_step4_kernel<true, true, decltype(O)::value, float*>), g, b, 0, stream, dev.cs, (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed, dev.seed,
@@ -454,13 +383,13 @@ struct PendulumEnv final : Env {
         if (final_live()) {
             with_bools([&](auto V) {
                 hipLaunchKernelGGL((pendulum_step_kernel<decltype(V)::value ? 4 : 1, true, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
-            }, vec_ok);
+            }, vec);
             MGYM_HIP(hipGetLastError());
             return MGYM_OK;
         }
         with_bools([&](auto T, auto V) {
             hipLaunchKernelGGL((pendulum_step_kernel<decltype(V)::value ? 4 : 1, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }, tl, vec_ok);
+        }, tl, vec);
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
@@ -481,13 +410,8 @@ struct PendulumEnv final : Env {
     // the channel of mgym_set_final_obs_out has something to deliver: without a time limit no Pendulum episode ever ends (and only auto-reset handles hold a pointer)
     bool final_live() const { return final_obs != nullptr && dev.limit != 0u; }
 
-    int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        const uint32_t* act = static_cast<const uint32_t*>(actions);
-        if (!fused_rollout_args_ok(nullptr, n, K, false, act, obs_out, reward, done, trunc)) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
+    void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         with_bools([&](auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); }, dev.limit != 0u);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
     }
 
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
@@ -499,7 +423,7 @@ struct PendulumEnv final : Env {
             constexpr bool TL = decltype(T)::value;
             switch (call.source) {
             case ROLL_ACT_UNIFORM:
-                launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, PdLinearPolicy{}, PdUniformPolicy{call.seed, uniform_calls++});
+                launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, PdLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});
                 break;
             case ROLL_ACT_LINEAR:
                 launch_rollout<ROLL_ACT_LINEAR, TL>(nullptr, ao, K, obs_out, reward, done, trunc, PdLinearPolicy{{call.weights[0], call.weights[1], call.weights[2]}, call.weights[3]});
@@ -519,34 +443,8 @@ struct PendulumEnv final : Env {
         return MGYM_OK;
     }
 
-    int observation(const float** obs, uint64_t* col_stride) override {
-        *obs = dev.cs;
-        *col_stride = n_pad;
-        return MGYM_OK;
-    }
-
-    int get_state(void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(pendulum_export_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, dev, static_cast<uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int set_state(const void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(pendulum_import_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, dev, static_cast<const uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int elapsed(uint32_t* out, const uint32_t* in) override {
-        if (n == 0) return MGYM_OK;
-        const dim3 g((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
-        if (out) hipLaunchKernelGGL(pendulum_get_elapsed_kernel, g, b, 0, stream, dev, out);
-        else hipLaunchKernelGGL(pendulum_set_elapsed_kernel, g, b, 0, stream, dev, in);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int get_state(void* blob) override { return launch_per_env(pendulum_export_kernel, dev, static_cast<uint32_t*>(blob)); }
+    int set_state(const void* blob) override { return launch_per_env(pendulum_import_kernel, dev, static_cast<const uint32_t*>(blob)); }
 };
 
 Env* make_pendulum() { return new PendulumEnv(); }

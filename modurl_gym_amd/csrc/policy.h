@@ -37,7 +37,9 @@ struct PolicyCall {
     float sigma;            // MLP_*_GAUSS: the standard deviation, finite and >= 0
 };
 
-// what a drawing hidden-layer source takes beside its MlpPack as a kernel argument
+// the uniform stream of a classic family's rollout kernel (policy seed, call word); the categorical draw of MLP_*_SAMPLE travels in it too
+struct UniformDraw { uint64_t seed; uint32_t call; };
+// what a Gaussian-drawing hidden-layer source takes in its place
 struct GaussDraw { uint64_t seed; uint32_t call; float sigma; };
 
 }  // namespace mgym

@@ -1,9 +1,11 @@
-// soa4.h — device helpers of the struct-of-arrays kernels in which one lane owns 4 consecutive environments (cartpole.hip, mountain_car.hip):
-// every column is read and written with one 16-byte access per lane, the 4 done bytes with one word.
+// soa4.h — device helpers of the struct-of-arrays kernels in which one lane owns 4 consecutive environments (cartpole.hip, mountain_car.hip,
+// pendulum.hip, acrobot.hip): every column is read and written with one 16-byte access per lane, the 4 done bytes with one word.  The elapsed
+// counters, the wave's count flush and the reset mask gather below are those of the last three (CartPole keeps its own: DESIGN.md §4).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "common.h"
 
 namespace mgym {
 
@@ -39,6 +41,46 @@ inline int classic_max_blocks(int compiled) {
 
 // a lane's four flags (0 / 1 each) as the four bytes of one word, environment k in byte k
 __device__ __forceinline__ uint32_t pack_bytes4(const uint32_t (&b)[4]) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
+
+// a lane's four elapsed counters (u16 each): one 8-byte access (i0 a multiple of 4)
+__device__ __forceinline__ void load_elapsed4(const uint16_t* elapsed, uint64_t i0, uint32_t (&el)[4]) {
+    const u16x4 v = *reinterpret_cast<const u16x4*>(elapsed + i0);
+    el[0] = v.x; el[1] = v.y; el[2] = v.z; el[3] = v.w;
+}
+__device__ __forceinline__ void store_elapsed4(uint16_t* elapsed, uint64_t i0, const uint32_t (&el)[4]) {
+    __builtin_nontemporal_store(u16x4{(uint16_t)el[0], (uint16_t)el[1], (uint16_t)el[2], (uint16_t)el[3]}, reinterpret_cast<u16x4*>(elapsed + i0));
+}
+
+// per-lane counts of finished envs summed over the wave, one fire-and-forget atomic per wave; the sticky invalid-action bit.  (The step4 kernels
+// count with __ballot and keep their tail written out: a helper shared with this one moved instructions in them.)
+__device__ __forceinline__ void flush_counts(unsigned long long* done_count, uint32_t* err, uint32_t finished, bool bad) {
+    for (int o = 32; o > 0; o >>= 1) finished += __shfl_down(finished, o);
+    if ((threadIdx.x & 63) == 0 && finished)
+        atomicAdd(done_count + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kDoneShards - 1)), (unsigned long long)finished);
+    if (__any(bad)) {
+        if ((threadIdx.x & 63) == 0) atomicOr(err, DEV_ERR_INVALID_ACTION);
+    }
+}
+
+// mgym_reset / mgym_reset_done: the mask word of the lane's four envs i0 .. i0 + 3, env k in byte k (nonzero: reset it) — every env (`all`), or the
+// OR of the caller's byte masks m0 and m1 (either may be null): one word each where both are 4-byte aligned and the group is whole, bytes otherwise
+__device__ __forceinline__ uint32_t reset_mask4(const uint8_t* m0, const uint8_t* m1, int all, int masks_aligned, uint64_t i0, uint64_t n) {
+    uint32_t m = 0;
+    if (all) {
+        m = 0x01010101u;
+    } else if (masks_aligned && i0 + 4 <= n) {
+        if (m0) m |= *reinterpret_cast<const uint32_t*>(m0 + i0);
+        if (m1) m |= *reinterpret_cast<const uint32_t*>(m1 + i0);
+    } else {
+        for (int k = 0; k < 4 && i0 + k < n; ++k) {
+            uint32_t b = 0;
+            if (m0) b |= m0[i0 + k];
+            if (m1) b |= m1[i0 + k];
+            m |= (b ? 1u : 0u) << (8 * k);
+        }
+    }
+    return m;
+}
 
 // mgym_set_final_obs_out.  The stepping kernels end their template parameters with `class... Fin` and their arguments with `Fin... fin`: the pack is
 // empty (the kernel as it always was: same arguments, same code) or one float* (the channel's instantiation, launched only while a pointer is set).
