@@ -40,7 +40,7 @@ class AbRun(C.Structure):
                 ("auto_reset", C.c_int32), ("policy", C.c_int32), ("weights", C.c_void_p), ("hidden", C.c_int32), ("policy_seed", C.c_uint64),
                 ("call", C.c_uint32), ("actions_in", C.c_void_p), ("state_in", C.c_void_p), ("actions_out", C.c_void_p), ("obs0", C.c_void_p),
                 ("obs", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("trunc", C.c_void_p), ("elapsed_out", C.c_void_p),
-                ("state_out", C.c_void_p), ("finished", C.c_uint64), ("bad", C.c_int32)]
+                ("state_out", C.c_void_p), ("finished", C.c_uint64), ("bad", C.c_int32), ("flush", C.c_int32)]
 
 
 _shared = None
@@ -339,8 +339,8 @@ def step_f64(th1, th2, w1, w2, a):
 
 # ---- the host-compiled header ----
 def header_run(n, steps, seed=0, env_id_base=0, limit=0, auto_reset=False, policy=POL_TABLE, weights=None, hidden=0, policy_seed=0, call=0,
-               actions=None, state=None):
-    """acrobot_run of tests/native/acrobot_check.cpp -> dict(actions, obs0, obs, reward, done, trunc, elapsed, state, finished, bad)"""
+               actions=None, state=None, flush=False):
+    """acrobot_run of tests/native/acrobot_check.cpp -> dict(actions, obs0, obs, reward, done, trunc, elapsed, state, finished, bad); flush: with denormals flushed to zero (x86)"""
     lib = build_shared()
     w = np.ascontiguousarray(weights if weights is not None else np.zeros(21), F)
     acts = np.ascontiguousarray(actions if actions is not None else np.zeros((steps, n)), np.uint32)
@@ -350,7 +350,7 @@ def header_run(n, steps, seed=0, env_id_base=0, limit=0, auto_reset=False, polic
                done=np.zeros((steps, n), np.uint8), trunc=np.zeros((steps, n), np.uint8), elapsed=np.zeros(n, np.uint32), state=np.zeros((5, n), np.uint32))
     p = AbRun(n, steps, int(seed), int(env_id_base), int(limit), int(auto_reset), int(policy), w.ctypes.data, int(hidden), int(policy_seed), int(call),
               acts.ctypes.data, None if st is None else st.ctypes.data, out["actions"].ctypes.data, out["obs0"].ctypes.data, out["obs"].ctypes.data,
-              out["reward"].ctypes.data, out["done"].ctypes.data, out["trunc"].ctypes.data, out["elapsed"].ctypes.data, out["state"].ctypes.data, 0, 0)
+              out["reward"].ctypes.data, out["done"].ctypes.data, out["trunc"].ctypes.data, out["elapsed"].ctypes.data, out["state"].ctypes.data, 0, 0, int(flush))
     assert lib.acrobot_run(C.byref(p)) == 0
     out["finished"], out["bad"] = int(p.finished), bool(p.bad)
     return out

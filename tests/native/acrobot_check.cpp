@@ -16,6 +16,24 @@
 #include "../../modurl_gym_amd/csrc/acrobot_step.h"
 using namespace mgym;
 
+// flush = 1: the x86 flush-to-zero and denormals-are-zero bits (MXCSR 15 and 6) are set for the duration of the run and restored after it: what a
+// build that flushes denormals would compute, for the check that the edge cases of tests/classic_edge_cases.py would notice one
+#if defined(__x86_64__) || defined(__i386__)
+#include <xmmintrin.h>
+struct FlushScope {
+    unsigned saved;
+    bool on;
+    explicit FlushScope(bool flush) : saved(_mm_getcsr()), on(flush) { if (on) _mm_setcsr(saved | 0x8040u); }
+    ~FlushScope() { if (on) _mm_setcsr(saved); }
+    static bool supported() { return true; }
+};
+#else
+struct FlushScope {
+    explicit FlushScope(bool) {}
+    static bool supported() { return false; }
+};
+#endif
+
 enum { POL_TABLE = 0, POL_LINEAR = 1, POL_UNIFORM = 2, POL_MLP_RELU = 3, POL_MLP_TANH = 4, POL_MLP_RELU_SAMPLE = 5, POL_MLP_TANH_SAMPLE = 6 };
 
 struct AbRun {
@@ -29,6 +47,7 @@ struct AbRun {
     uint32_t *elapsed_out, *state_out;   // [n], [5][n]
     uint64_t finished;            // env-steps with done | truncated (mgym_episode_count)
     int32_t bad;                  // an action above 2 was seen (the sticky MGYM_ERR_INVALID_ACTION)
+    int32_t flush;                // run with denormals flushed to zero (inputs and results); 0 in every other use
 };
 
 template <bool TL>
@@ -109,6 +128,8 @@ static void run(AbRun& p) {
 extern "C" int acrobot_run(AbRun* p) {
     const bool draws = p && (p->policy == POL_UNIFORM || p->policy >= POL_MLP_RELU_SAMPLE);
     if (!p || (draws && (p->n % 4 || p->env_id_base % 4)) || p->limit > kMaxEpisodeSteps) return 1;
+    if (p->flush && !FlushScope::supported()) return 2;
+    const FlushScope scope(p->flush != 0);
     if (p->limit) run<true>(*p); else run<false>(*p);
     return 0;
 }
