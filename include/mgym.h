@@ -327,7 +327,7 @@ int mgym_rollout_linear(mgym_env *env, const float *policy, int32_t K, void *act
  * observation, later the one the previous step returned — under MGYM_FLAG_AUTO_RESET, for an env that finished there, its reset observation):
  *   hidden pre-activation  pre_j = b1[j], then for q = 0 .. D-1 ascending  pre_j = fmaf(W1[j][q], o[q], pre_j);
  *   hidden activation      MGYM_ACT_RELU: h_j = pre_j > 0.0f ? pre_j : 0.0f (NaN and -0 both give +0);  MGYM_ACT_TANH: h_j = tanhf(pre_j), glibc's, bit for bit
- *                          (mg_tanhf of csrc/mgym_math.h);
+ *                          (mg_tanhf of csrc/mgym_math.h);  MGYM_ACT_TANH_FAST: h_j = mg_tanhf_fast(pre_j), the cheap tanh defined below;
  *   scores                 s_a = b2[a], then for j = 0 .. H-1 ascending  s_a = fmaf(W2[a][j], h_j, s_a);
  *   discrete action        the sequential strict argmax of mgym_rollout_linear's LunarLander form: start with action 0 and best = s_0; row a replaces it when
  *                          s_a > best; the first of equal scores wins, a NaN never replaces an earlier score, a NaN s_0 gives action 0;
@@ -341,17 +341,47 @@ int mgym_rollout_linear(mgym_env *env, const float *policy, int32_t K, void *act
  * carries this policy too — each environment's next action decided where its observation is produced, ReLU and tanh alike, the same words — and runs it
  * under the conditions of mgym_rollout_linear (from MGYM_LL_ROLLOUT_MIN_K steps up, below the launch's population limit, not while the stream is being
  * captured) for an activation that has been measured faster there (none yet) and, with MGYM_LL_ROLLOUT_MLP=1 in the environment at mgym_create, for
- * both; mgym_get_info's rollout_persistent_launches tells which form ran.  The weights are copied during the call in both forms: consecutive calls on
+ * both; mgym_get_info's rollout_persistent_launches tells which form ran.  MGYM_ACT_TANH_FAST is not among them: the persistent launch has no form for it,
+ * so on LunarLander it always runs as K x (a policy kernel, mgym_step), MGYM_LL_ROLLOUT_MLP=1 included, and rollout_persistent_launches does not move.  The weights are copied during the call in both forms: consecutive calls on
  * one stream each use their own.  A handle that was never reset reports MGYM_ERR_NOT_RESET at the next mgym_sync.
  * Errors, reported before any launch with the argument named in mgym_last_error: NULL policy, hidden outside 1 .. 64, an unknown activation -> MGYM_ERR_BAD_ARG.
- * Under graph capture the weights are frozen into the captured launches, as the linear policy's are. */
-enum { MGYM_ACT_RELU = 0, MGYM_ACT_TANH = 1 };
+ * Under graph capture the weights are frozen into the captured launches, as the linear policy's are.
+ *
+ * MGYM_ACT_TANH_FAST = 3:  h_j = mg_tanhf_fast(pre_j), a tanh for collectors.  MGYM_ACT_TANH is glibc's tanhf to the bit and is nearly all of a launch's time; the
+ * hidden units of a collector's policy need no such thing (the learner recomputes with its own tanh), only words that are defined here and that a host
+ * reproduces.  All arithmetic is f32; every fmaf is one correctly rounded fused multiply-add; nothing else is fused and nothing is reassociated; the divide is
+ * the IEEE-correct f32 divide.  Branch-free: about 30 VALU instructions, one divide.
+ *
+ *   x is a NaN: the result is a NaN (compared as a class)
+ *   a  = |x|;  a = a < 10.0f ? a : 10.0f                 (an infinity gives 10)
+ *   u  = -2.0f * a                                       exact
+ *   n  = rintf(u * 0x1.715476p+0f)                       one f32 multiply, then round to nearest integer, ties to even: n in -29 .. 0
+ *   r  = fmaf(n, -0x1.62e4p-1f, u)
+ *   r  = fmaf(n, -0x1.7f7d1cp-20f, r)                    |r| <= ~0.347: u = n ln2 + r
+ *   q  = 0x1.a01a02p-13f                                 1/5040
+ *   q  = fmaf(q, r, 0x1.6c16c2p-10f)                     1/720
+ *   q  = fmaf(q, r, 0x1.111112p-7f)                      1/120
+ *   q  = fmaf(q, r, 0x1.555556p-5f)                      1/24
+ *   q  = fmaf(q, r, 0x1.555556p-3f)                      1/6
+ *   q  = fmaf(q, r, 0.5f)
+ *   p  = fmaf(q, r * r, r)                               expm1(r), relative accuracy kept down to r = 0
+ *   s  = the f32 with bits (127 + n) << 23               2^n, always a normal number
+ *   em = fmaf(s, p, s - 1.0f)                            expm1(u) = 2^n expm1(r) + (2^n - 1); s - 1 is exact for n >= -24
+ *   z  = (-em) / (em + 2.0f)                             tanh(a) = -expm1(-2a) / (expm1(-2a) + 2); the denominator lies in [1, 2]
+ *   result = copysignf(z, x)                             odd by construction; +-0 give +-0
+ *
+ * Enumerated over all 2^31 non-negative patterns with glibc's fmaf (tests/test_tanh_fast_host.py) against float64 tanh: the largest error is 2.50 f32
+ * spacings of the exact value and the largest absolute error 1.49e-7, both at x = 4.5050907 (pattern 0x409029b4); no result exceeds 1.0f, the results never
+ * decrease as x grows, n stays within -29 .. 0, the first x with result 1.0f is 8.4910536 (0x4107db5b), an infinity gives 1.0f.  The device's words equal the host's
+ * (tests/test_gpu_tanh_fast_probe.py).  The value 2 is not assigned: it stays the unknown activation it has always been (MGYM_ERR_BAD_ARG naming `activation` from
+ * all three entry points), and a later activation does not take it either. */
+enum { MGYM_ACT_RELU = 0, MGYM_ACT_TANH = 1, MGYM_ACT_TANH_FAST = 3 };
 int mgym_rollout_mlp(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, int32_t K,
                      void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
 
 /* mgym_rollout_mlp with the action DRAWN from the categorical (softmax) distribution over the scores instead of their argmax: what the collector of an
- * on-policy trainer (REINFORCE, A2C, PPO) runs.  Everything is as in mgym_rollout_mlp — the `policy` layout, hidden 1 .. 64, MGYM_ACT_RELU / MGYM_ACT_TANH, the
- * scores s_a as fmaf chains from the bias on the observation held before the step, the output shapes, and the rule that the K steps equal K mgym_step calls
+ * on-policy trainer (REINFORCE, A2C, PPO) runs.  Everything is as in mgym_rollout_mlp — the `policy` layout, hidden 1 .. 64, MGYM_ACT_RELU / MGYM_ACT_TANH /
+ * MGYM_ACT_TANH_FAST, the scores s_a as fmaf chains from the bias on the observation held before the step, the output shapes, and the rule that the K steps equal K mgym_step calls
  * fed the actions in actions_out, word for word, MGYM_FLAG_AUTO_RESET and mgym_config::max_episode_steps included — except how a discrete action follows
  * from the scores.
  *
@@ -392,7 +422,7 @@ int mgym_rollout_mlp_sample(mgym_env *env, const float *policy, int32_t hidden, 
 /* mgym_rollout_mlp for the two CONTINUOUS families with the action DRAWN from a diagonal Gaussian around the score: a = mu + sigma * z, sigma a
  * state-independent standard deviation passed by the caller (the usual continuous PPO / A2C parameterisation; a second output row for a state-dependent
  * sigma is not offered).  As in mgym_rollout_mlp with D = 2 (MountainCarContinuous) or 3 (Pendulum) and A = 1: the `policy` layout, hidden 1 .. 64,
- * MGYM_ACT_RELU / MGYM_ACT_TANH, the fmaf chain from the bias on the observation held before the step, the output shapes, the conditions of the fused form
+ * MGYM_ACT_RELU / MGYM_ACT_TANH / MGYM_ACT_TANH_FAST, the fmaf chain from the bias on the observation held before the step, the output shapes, the conditions of the fused form
  * (n_envs a multiple of 4, 16-byte aligned buffers), and the rule that the K steps equal K mgym_step calls fed the actions in actions_out, word for word,
  * MGYM_FLAG_AUTO_RESET and mgym_config::max_episode_steps included.
  *
@@ -572,6 +602,13 @@ enum {
     MGYM_MATH_TANHF = 5      /* mg_tanhf */
 };
 int mgym_math_probe(int device, int fn, uint32_t first, uint64_t count, uint32_t *out);
+
+/* Test seam: the result bits of the hidden activation of mgym_rollout_mlp (mlp_activate of modurl_gym_amd/csrc/mlp_policy.h) evaluated on the device for the
+ * input bit patterns first .. first + count - 1 (first + count <= 2^32); out is device memory of count words.  activation is MGYM_ACT_RELU, MGYM_ACT_TANH or
+ * MGYM_ACT_TANH_FAST; anything else, a NULL out, an empty or out-of-range span -> MGYM_ERR_BAD_ARG.  Runs on the null stream and synchronises the device.
+ * A seam of its own: mgym_math_probe keeps the entry points of mgym_math.h that follow glibc.  tests/test_gpu_tanh_fast_probe.py compares with the
+ * host-compiled header. */
+int mgym_act_probe(int device, int activation, uint32_t first, uint64_t count, uint32_t *out);
 
 /* Test seam: the draw of mgym_rollout_mlp_sample (mlp_sample of modurl_gym_amd/csrc/mlp_policy.h) evaluated on the device, one case per lane.
  * n_actions = A is 2, 3 or 4; scores is [A][count] floats, words [count] Philox words w, actions_out [count], cum_out [A][count] (c_0 .. c_{A-1}) or NULL;

@@ -63,7 +63,7 @@ class VecGym {
     void rollout_linear(const float* policy, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_linear(env_, policy, K, actions_out, obs, reward, done, trunc));
     }
-    // K fused steps under the on-device one-hidden-layer policy: policy = W1[H][D], b1[H], W2[A][H], b2[A] (host floats), activation MGYM_ACT_RELU / MGYM_ACT_TANH
+    // K fused steps under the on-device one-hidden-layer policy: policy = W1[H][D], b1[H], W2[A][H], b2[A] (host floats), activation MGYM_ACT_RELU / MGYM_ACT_TANH / MGYM_ACT_TANH_FAST (the cheap, word-defined tanh)
     // (LunarLander: K x (policy kernel, step) by default; inside its persistent rollout launch with MGYM_LL_ROLLOUT_MLP=1; the same words)
     void rollout_mlp(const float* policy, int hidden, int activation, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_mlp(env_, policy, hidden, activation, K, actions_out, obs, reward, done, trunc));

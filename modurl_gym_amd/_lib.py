@@ -16,7 +16,7 @@ OK, ERR_INVALID_ACTION, ERR_NOT_RESET, ERR_BAD_CONFIG, ERR_HIP, ERR_BAD_ARG, ERR
 CARTPOLE, MOUNTAINCAR, MOUNTAINCAR_CONT, LUNARLANDER, PENDULUM = range(5)
 ACROBOT = 6   # (5 is not assigned)
 FLAG_AUTO_RESET = 1
-ACT_RELU, ACT_TANH = range(2)   # mgym_rollout_mlp hidden activations
+ACT_RELU, ACT_TANH, ACT_TANH_FAST = 0, 1, 3   # mgym_rollout_mlp hidden activations (2 is not assigned)
 MATH_SINF, MATH_COSF, MATH_SINCOSF, MATH_SINCOSF_U, MATH_COSF_U, MATH_TANHF = range(6)   # mgym_math_probe entry points
 LL_GEOM_SHAPES, LL_GEOM_DISTANCE, LL_GEOM_MANIFOLD, LL_GEOM_TOI = range(4)   # mgym_ll_geom_probe probes
 
@@ -76,6 +76,7 @@ PROTOTYPES = {
     "mgym_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "mgym_selftest_cartpole_math": (C.c_int, [C.c_int, _u64p]),
     "mgym_math_probe": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint64, _vp]),
+    "mgym_act_probe": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint64, _vp]),
     "mgym_sample_probe": (C.c_int, [C.c_int, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
     "mgym_gauss_probe": (C.c_int, [C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "mgym_ll_geom_probe": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _vp, _vp]),

@@ -306,6 +306,10 @@ int mgym_rollout_linear(mgym_env* env, const float* policy, int32_t K, void* act
     return e->rollout_policy(PolicyCall{ROLL_ACT_LINEAR, "mgym_rollout_linear", policy, 0, 0}, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
+// the hidden activations of the three hidden-layer entry points (2 is not one)
+static_assert(MGYM_ACT_RELU == MLP_ACT_RELU && MGYM_ACT_TANH == MLP_ACT_TANH && MGYM_ACT_TANH_FAST == MLP_ACT_TANH_FAST, "mgym.h and mlp_policy.h number the activations alike");
+static bool act_known(int32_t activation) { return activation == MGYM_ACT_RELU || activation == MGYM_ACT_TANH || activation == MGYM_ACT_TANH_FAST; }
+
 int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, int32_t K, void* actions_out, float* obs_out,
                      float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
@@ -313,8 +317,8 @@ int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t
     FINAL_CAP_OR_FAIL("mgym_rollout_mlp", K);
     if (!policy) return bad_arg("mgym_rollout_mlp: policy is NULL");
     if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp: hidden must be between 1 and 64");
-    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
-    return e->rollout_policy(PolicyCall{activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, "mgym_rollout_mlp", policy, hidden, 0}, K, actions_out, obs_out, reward_out, done_out,
+    if (!act_known(activation)) return bad_arg("mgym_rollout_mlp: activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    return e->rollout_policy(PolicyCall{roll_act_mlp_plain(activation), "mgym_rollout_mlp", policy, hidden, 0}, K, actions_out, obs_out, reward_out, done_out,
                              trunc_out);
 }
 
@@ -327,9 +331,9 @@ int mgym_rollout_mlp_sample(mgym_env* env, const float* policy, int32_t hidden, 
     if (e->cfg.kind == MGYM_PENDULUM) return bad_arg("mgym_rollout_mlp_sample: Pendulum has no discrete actions to draw from (a Gaussian head is not implemented)");
     if (!policy) return bad_arg("mgym_rollout_mlp_sample: policy is NULL");
     if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp_sample: hidden must be between 1 and 64");
-    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp_sample: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
+    if (!act_known(activation)) return bad_arg("mgym_rollout_mlp_sample: activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
     if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_sample: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
-    return e->rollout_policy(PolicyCall{activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, "mgym_rollout_mlp_sample", policy, hidden, policy_seed, policy_call},
+    return e->rollout_policy(PolicyCall{roll_act_mlp_sample(activation), "mgym_rollout_mlp_sample", policy, hidden, policy_seed, policy_call},
                              K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
@@ -344,10 +348,10 @@ int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, i
     }
     if (!policy) return bad_arg("mgym_rollout_mlp_gauss: policy is NULL");
     if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp_gauss: hidden must be between 1 and 64");
-    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH) return bad_arg("mgym_rollout_mlp_gauss: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH");
+    if (!act_known(activation)) return bad_arg("mgym_rollout_mlp_gauss: activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
     if (!(sigma >= 0.0f) || sigma > 3.402823466e+38f) return bad_arg("mgym_rollout_mlp_gauss: sigma must be finite and >= 0");   // (a NaN fails the first test)
     if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_gauss: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
-    return e->rollout_policy(PolicyCall{activation == MGYM_ACT_TANH ? ROLL_ACT_MLP_TANH_GAUSS : ROLL_ACT_MLP_RELU_GAUSS, "mgym_rollout_mlp_gauss", policy, hidden, policy_seed, policy_call, sigma},
+    return e->rollout_policy(PolicyCall{roll_act_mlp_gauss(activation), "mgym_rollout_mlp_gauss", policy, hidden, policy_seed, policy_call, sigma},
                              K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 

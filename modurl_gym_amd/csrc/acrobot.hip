@@ -271,7 +271,7 @@ acrobot_rollout_kernel(AcrobotDev d, const uint32_t* __restrict__ act, int K, fl
                 float o[4][6];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acrobot_obs(e[k], o[k]);
-                constexpr int ACT = roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU;
+                constexpr int ACT = roll_act_mlp_act(POLICY);
                 if constexpr (roll_act_samples(POLICY)) {
                     // mgym_rollout_mlp_sample: one Philox evaluation per lane per step, its four words for the lane's four envs
                     const Philox4 w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
@@ -465,11 +465,11 @@ struct AcrobotEnv final : ClassicEnv {
             default: {   // the hidden-layer sources
                 MlpPack<6, 3> pack;
                 mlp_pack<6, 3>(call.weights, call.hidden, pack);
-                with_bools([&](auto H, auto S) {
-                    constexpr bool TANH = decltype(H)::value;
-                    if constexpr (!decltype(S)::value) launch_rollout<TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
-                    else launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
-                }, roll_act_mlp_tanh(call.source), roll_act_samples(call.source));
+                with_mlp_act([&](auto H) {
+                    constexpr int ACT = decltype(H)::value;
+                    if (!roll_act_samples(call.source)) launch_rollout<roll_act_mlp_plain(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
+                    else launch_rollout<roll_act_mlp_sample(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
+                }, call.source);
             }
             }
         }, dev.limit != 0u);

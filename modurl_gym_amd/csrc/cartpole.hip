@@ -346,7 +346,7 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 // hidden-layer policy on the observations the lane's four envs hold before the step (mlp_policy.h: fmaf chains from the bias, ascending index)
                 const float o[4][4] = {{s[0].x, s[0].xd, s[0].th, s[0].thd}, {s[1].x, s[1].xd, s[1].th, s[1].thd}, {s[2].x, s[2].xd, s[2].th, s[2].thd}, {s[3].x, s[3].xd, s[3].th, s[3].thd}};
-                constexpr int ACT = roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU;
+                constexpr int ACT = roll_act_mlp_act(POLICY);
                 if constexpr (roll_act_samples(POLICY)) {
                     // mgym_rollout_mlp_sample: one Philox evaluation per lane per step, its four words for the lane's four envs (policy_call: the caller's call word)
                     const Philox4 w = env_draw(policy_seed, d.env_id_base + i0, policy_call, SLOT_POLICY_SAMPLE + (uint32_t)t);
@@ -604,11 +604,11 @@ struct CartPoleEnv final : Env {
         default: {   // the hidden-layer sources
             CpMlpPack pack;
             mlp_pack<4, 2>(call.weights, call.hidden, pack);
-            with_bools([&](auto T, auto S) {
-                constexpr bool TANH = decltype(T)::value;
-                if constexpr (decltype(S)::value) launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE>(nullptr, ao, call.seed, call.call, K, obs_out, reward, done, trunc, pack);
-                else launch_rollout<TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU>(nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack);
-            }, roll_act_mlp_tanh(call.source), roll_act_samples(call.source));
+            with_mlp_act([&](auto H) {
+                constexpr int ACT = decltype(H)::value;
+                if (roll_act_samples(call.source)) launch_rollout<roll_act_mlp_sample(ACT)>(nullptr, ao, call.seed, call.call, K, obs_out, reward, done, trunc, pack);
+                else launch_rollout<roll_act_mlp_plain(ACT)>(nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack);
+            }, call.source);
         }
         }
         MGYM_HIP(hipGetLastError());

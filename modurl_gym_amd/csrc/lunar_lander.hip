@@ -1258,7 +1258,8 @@ struct LunarLanderEnv final : Env {
     }
     // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp / mgym_rollout_mlp_sample, the one place that unpacks the call and chooses the form: the persistent launch with the
     // action source `policy` (ll_roll.h) when the handle has one, K >= rollout_min_k, the stream is not being captured and — hidden-layer sources — the activation runs
-    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).  The sampling sources always run the second form, whatever MGYM_LL_ROLLOUT_MLP says.
+    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).  The sampling sources always run the second form, whatever MGYM_LL_ROLLOUT_MLP says,
+    // and so do the MGYM_ACT_TANH_FAST sources: the persistent kernel has no instantiation for them.
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
         const int policy = call.source;
@@ -1279,15 +1280,18 @@ struct LunarLanderEnv final : Env {
         }
         pol.next = next_act;
         const bool sample = roll_act_samples(policy);
-        const bool persistent = !sample && opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
+        const bool fast = mlp && roll_act_mlp_act(policy) == MLP_ACT_TANH_FAST;
+        const bool persistent = !sample && !fast && opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
         if (!persistent) {
             const unsigned g = (unsigned)((n + 255) / 256);
             for (int t = 0; t < K; ++t) {
                 uint32_t* a = ao ? ao + (size_t)t * n : next_act;
                 if (policy == ROLL_ACT_LINEAR) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_LINEAR>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
                 else if (policy == ROLL_ACT_UNIFORM) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_UNIFORM>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
+                else if (policy == ROLL_ACT_MLP_TANH_FAST_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_TANH_FAST>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
                 else if (policy == ROLL_ACT_MLP_TANH_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
                 else if (policy == ROLL_ACT_MLP_RELU_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
+                else if (policy == ROLL_ACT_MLP_TANH_FAST) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH_FAST>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
                 else if (policy == ROLL_ACT_MLP_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);   // (the pack as a kernel argument: a captured graph carries it)
                 else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
                 MGYM_HIP(hipGetLastError());

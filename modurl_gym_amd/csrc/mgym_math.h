@@ -381,4 +381,30 @@ MG_HD float mg_tanhf(float x) {
     return pos ? z : -z;
 }
 
+// ---- the cheap tanh of MGYM_ACT_TANH_FAST: include/mgym.h defines it operation by operation, and this is that text ----
+// tanh(a) = -em / (em + 2) with em = expm1(-2a) <= 0, a = min(|x|, 10): u = -2a = n ln2 + r by a two-constant Cody-Waite step, expm1(r) as r + r^2 q(r) (the
+// Taylor coefficients 1/2 .. 1/5040), em = 2^n expm1(r) + (2^n - 1).  No data-dependent branch: the clamp and the NaN rule are selects, rintf is v_rndne_f32,
+// the one divide is the IEEE f32 divide.  Every fmaf is written out through cp_fmaf and nothing else is fused (-ffp-contract=off).
+MG_HD float mg_tanhf_fast(float x) {
+    const uint32_t bx = as_u32(x);
+    float a = as_f32(bx & 0x7fffffffu);
+    a = a < 10.0f ? a : 10.0f;                      // (an infinity and a NaN give 10)
+    const float u = -2.0f * a;
+    const float n = __builtin_rintf(u * 0x1.715476p+0f);   // -29 .. 0
+    float r = cp_fmaf(n, -0x1.62e4p-1f, u);
+    r = cp_fmaf(n, -0x1.7f7d1cp-20f, r);
+    float q = 0x1.a01a02p-13f;
+    q = cp_fmaf(q, r, 0x1.6c16c2p-10f);
+    q = cp_fmaf(q, r, 0x1.111112p-7f);
+    q = cp_fmaf(q, r, 0x1.555556p-5f);
+    q = cp_fmaf(q, r, 0x1.555556p-3f);
+    q = cp_fmaf(q, r, 0.5f);
+    const float p = cp_fmaf(q, r * r, r);
+    const float s = as_f32((uint32_t)(127 + (int32_t)n) << 23);
+    const float em = cp_fmaf(s, p, s - 1.0f);
+    const float z = (-em) / (em + 2.0f);
+    const float res = as_f32((as_u32(z) & 0x7fffffffu) | (bx & 0x80000000u));
+    return x != x ? x : res;
+}
+
 }  // namespace mgym

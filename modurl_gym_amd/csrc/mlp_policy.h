@@ -1,10 +1,10 @@
 // mlp_policy.h — the one-hidden-layer policy of mgym_rollout_mlp, mgym_rollout_mlp_sample and mgym_rollout_mlp_gauss (include/mgym.h), shared by the rollout
 // kernels of CartPole, MountainCar and Pendulum (cartpole.hip, mountain_car.hip, pendulum.hip: the lane's four environments), LunarLander's policy kernel
-// (lunar_lander.hip: one environment per lane) and the host checks tests/native/mlp_policy_check.cpp, mlp_sample_check.cpp and mlp_gauss_check.cpp, which compile this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
+// (lunar_lander.hip: one environment per lane) and the host checks tests/native/mlp_policy_check.cpp, mlp_sample_check.cpp, mlp_gauss_check.cpp and mlp_tanh_fast_check.cpp, which compile this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
 // -ffp-contract=off: the only fused operations are the cp_fmaf of the two chains.
 //
 //   pre_j = b1[j];  q = 0 .. D-1 ascending:  pre_j = fmaf(W1[j][q], o[q], pre_j)
-//   h_j   = pre_j > 0 ? pre_j : +0  (ReLU: NaN and -0 give +0)   |   mg_tanhf(pre_j)
+//   h_j   = pre_j > 0 ? pre_j : +0  (ReLU: NaN and -0 give +0)   |   mg_tanhf(pre_j)   |   mg_tanhf_fast(pre_j)
 //   s_a   = b2[a];  j = 0 .. H-1 ascending:  s_a = fmaf(W2[a][j], h_j, s_a)
 // Every chain is a k-ordered sequence of correctly rounded f32 fused multiply-adds that starts at the bias — which is also what an f32 MFMA
 // computes with the bias as its C input, and what glibc's fmaf computes on the host.
@@ -15,7 +15,7 @@
 namespace mgym {
 
 constexpr int kMlpMaxHidden = 64;
-enum { MLP_ACT_RELU = 0, MLP_ACT_TANH = 1 };   // = MGYM_ACT_RELU / MGYM_ACT_TANH
+enum { MLP_ACT_RELU = 0, MLP_ACT_TANH = 1, MLP_ACT_TANH_FAST = 3 };   // = MGYM_ACT_RELU / MGYM_ACT_TANH / MGYM_ACT_TANH_FAST (2 is not an activation)
 
 // The weights as the kernels read them, passed BY VALUE as a kernel argument (wave-uniform: scalar loads from the kernel-argument segment, and a
 // captured graph carries them).  Hidden unit j's words are contiguous — W1[j][0 .. D-1], b1[j], W2[0 .. A-1][j] — so one unit is one run of scalar
@@ -46,6 +46,7 @@ MG_HD void mlp_pack(const float* policy, int H, MlpPack<D, A>& p) {
 template <int ACT>
 MG_HD float mlp_activate(float pre) {
     if (ACT == MLP_ACT_TANH) return mg_tanhf(pre);
+    if (ACT == MLP_ACT_TANH_FAST) return mg_tanhf_fast(pre);
     return pre > 0.0f ? pre : 0.0f;
 }
 
@@ -72,6 +73,12 @@ MG_HD void mlp_scores(const MlpPack<D, A>& p, const float (&o)[N][D], float (&s)
             const float h = mlp_hidden<D, ACT>(u, o[k]);
 #pragma unroll
             for (int a = 0; a < A; ++a) s[k][a] = cp_fmaf(u[D + 1 + a], h, s[k][a]);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MLP_TANH_FAST_NO_BARRIER)
+            // the branch-free activation leaves a lane's N environments' chains free to interleave, and the compiler then keeps all of them live at once; a
+            // scheduling barrier after each environment (or packed pair) orders them as the branches of mg_tanhf do: up to 16 fewer VGPRs, and the launch
+            // measured beside a build without it (make EXTRA=-DMLP_TANH_FAST_NO_BARRIER) in profiles/tanh_fast_kernel_resources.txt
+            if (ACT == MLP_ACT_TANH_FAST && N > 1) __builtin_amdgcn_sched_barrier(0);
+#endif
         }
     }
 }

@@ -300,7 +300,7 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 // hidden-layer policy on (position, velocity) of the lane's four envs before the step (mlp_policy.h)
                 const float o[4][2] = {{ps[0], vs[0]}, {ps[1], vs[1]}, {ps[2], vs[2]}, {ps[3], vs[3]}};
-                constexpr int ACT = roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU;
+                constexpr int ACT = roll_act_mlp_act(POLICY);
                 if constexpr (roll_act_samples(POLICY)) {
                     // mgym_rollout_mlp_sample (Discrete(3) only): one Philox evaluation per lane per step, its four words for the lane's four envs; `uni`
                     // carries the policy seed and the caller's call word
@@ -497,20 +497,16 @@ struct MountainCarEnv final : ClassicEnv {
             default: {   // the hidden-layer sources
                 MlpPack<2, CONT ? 1 : 3> pack;
                 mlp_pack<2, CONT ? 1 : 3>(call.weights, call.hidden, pack);
-                if (roll_act_gauss(call.source)) {   // (the C ABI rejects mgym_rollout_mlp_gauss on discrete MountainCar)
-                    if constexpr (CONT) {
-                        const GaussDraw g{call.seed, call.call, call.sigma};
-                        if (roll_act_mlp_tanh(call.source)) launch_rollout<ROLL_ACT_MLP_TANH_GAUSS, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
-                        else launch_rollout<ROLL_ACT_MLP_RELU_GAUSS, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
+                with_mlp_act([&](auto H) {
+                    constexpr int ACT = decltype(H)::value;
+                    if (roll_act_gauss(call.source)) {   // (the C ABI rejects mgym_rollout_mlp_gauss on discrete MountainCar)
+                        if constexpr (CONT) launch_rollout<roll_act_mlp_gauss(ACT), CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, GaussDraw{call.seed, call.call, call.sigma});
+                    } else if (!roll_act_samples(call.source)) {
+                        launch_rollout<roll_act_mlp_plain(ACT), CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
+                    } else if constexpr (!CONT) {   // (the C ABI rejects mgym_rollout_mlp_sample on MountainCarContinuous)
+                        launch_rollout<roll_act_mlp_sample(ACT), CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
                     }
-                    break;
-                }
-                with_bools([&](auto H, auto S) {
-                    constexpr bool TANH = decltype(H)::value;
-                    if constexpr (!decltype(S)::value) launch_rollout<TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
-                    else if constexpr (!CONT)   // (the C ABI rejects mgym_rollout_mlp_sample on MountainCarContinuous)
-                        launch_rollout<TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
-                }, roll_act_mlp_tanh(call.source), roll_act_samples(call.source));
+                }, call.source);
             }
             }
         }, continuous, dev.limit != 0u);

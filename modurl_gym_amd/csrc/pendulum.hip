@@ -241,10 +241,10 @@ pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, 
             } else if constexpr (roll_act_gauss(POLICY)) {
                 // mgym_rollout_mlp_gauss: one Philox evaluation per lane per step, its two word pairs for the lane's two env pairs
                 const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
-                pendulum_gauss_actions<roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU>(pol, o, uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, uni.sigma, a);
+                pendulum_gauss_actions<roll_act_mlp_act(POLICY)>(pol, o, uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, uni.sigma, a);
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
-                pendulum_mlp_actions<roll_act_mlp_tanh(POLICY) ? MLP_ACT_TANH : MLP_ACT_RELU, 4>(pol, o, a);
+                pendulum_mlp_actions<roll_act_mlp_act(POLICY), 4>(pol, o, a);
             } else if constexpr (POLICY == ROLL_ACT_LINEAR) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = pendulum_linear_action(pol, cs[k], sn[k], td[k]);
@@ -431,11 +431,11 @@ struct PendulumEnv final : ClassicEnv {
             default: {   // the hidden-layer sources
                 MlpPack<3, 1> pack;
                 mlp_pack<3, 1>(call.weights, call.hidden, pack);
-                const GaussDraw g{call.seed, call.call, call.sigma};
-                if (call.source == ROLL_ACT_MLP_TANH_GAUSS) launch_rollout<ROLL_ACT_MLP_TANH_GAUSS, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
-                else if (call.source == ROLL_ACT_MLP_RELU_GAUSS) launch_rollout<ROLL_ACT_MLP_RELU_GAUSS, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, g);
-                else if (roll_act_mlp_tanh(call.source)) launch_rollout<ROLL_ACT_MLP_TANH, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
-                else launch_rollout<ROLL_ACT_MLP_RELU, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
+                with_mlp_act([&](auto H) {
+                    constexpr int ACT = decltype(H)::value;
+                    if (roll_act_gauss(call.source)) launch_rollout<roll_act_mlp_gauss(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, GaussDraw{call.seed, call.call, call.sigma});
+                    else launch_rollout<roll_act_mlp_plain(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
+                }, call.source);
             }
             }
         }, dev.limit != 0u);

@@ -1,6 +1,8 @@
 // policy.h — where a fused rollout takes its actions from: the one description every family's kernels and host wrappers share.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
+#include "mlp_policy.h"
 
 namespace mgym {
 
@@ -13,16 +15,39 @@ namespace mgym {
 //             caller's call word, step) (mgym_rollout_mlp_sample).  New sources, not a flag: the instantiations of the others keep their code.
 //   MLP_RELU_GAUSS / MLP_TANH_GAUSS  the continuous families' one score as the mean of a Gaussian: the action is mu + sigma * z, z a Box-Muller normal from a
 //             Philox block keyed the same way (mgym_rollout_mlp_gauss).  New sources again, for the same reason.
+//   MLP_TANH_FAST / MLP_TANH_FAST_SAMPLE / MLP_TANH_FAST_GAUSS  the three forms above with mg_tanhf_fast as the hidden activation (MGYM_ACT_TANH_FAST).  New
+//             sources once more: the nine before them keep their numbers and their code.  LunarLander's persistent launch carries none of them.
 // How LunarLander's persistent launch carries each of them: ll_roll_types.h.
 enum { ROLL_ACT_TABLE = 0, ROLL_ACT_LINEAR = 1, ROLL_ACT_UNIFORM = 2, ROLL_ACT_MLP_RELU = 3, ROLL_ACT_MLP_TANH = 4, ROLL_ACT_MLP_RELU_SAMPLE = 5,
-       ROLL_ACT_MLP_TANH_SAMPLE = 6, ROLL_ACT_MLP_RELU_GAUSS = 7, ROLL_ACT_MLP_TANH_GAUSS = 8 };
+       ROLL_ACT_MLP_TANH_SAMPLE = 6, ROLL_ACT_MLP_RELU_GAUSS = 7, ROLL_ACT_MLP_TANH_GAUSS = 8, ROLL_ACT_MLP_TANH_FAST = 9, ROLL_ACT_MLP_TANH_FAST_SAMPLE = 10,
+       ROLL_ACT_MLP_TANH_FAST_GAUSS = 11 };
 // the hidden-layer sources that draw their action from the categorical distribution (LunarLander's persistent launch carries none of them)
-constexpr bool roll_act_samples(int source) { return source == ROLL_ACT_MLP_RELU_SAMPLE || source == ROLL_ACT_MLP_TANH_SAMPLE; }
+constexpr bool roll_act_samples(int source) { return source == ROLL_ACT_MLP_RELU_SAMPLE || source == ROLL_ACT_MLP_TANH_SAMPLE || source == ROLL_ACT_MLP_TANH_FAST_SAMPLE; }
 // the hidden-layer sources that draw a continuous action around their score (MountainCarContinuous and Pendulum only)
-constexpr bool roll_act_gauss(int source) { return source == ROLL_ACT_MLP_RELU_GAUSS || source == ROLL_ACT_MLP_TANH_GAUSS; }
-// the hidden-layer sources, and whether their activation is tanh
-constexpr bool roll_act_is_mlp(int source) { return source == ROLL_ACT_MLP_RELU || source == ROLL_ACT_MLP_TANH || roll_act_samples(source) || roll_act_gauss(source); }
-constexpr bool roll_act_mlp_tanh(int source) { return source == ROLL_ACT_MLP_TANH || source == ROLL_ACT_MLP_TANH_SAMPLE || source == ROLL_ACT_MLP_TANH_GAUSS; }
+constexpr bool roll_act_gauss(int source) { return source == ROLL_ACT_MLP_RELU_GAUSS || source == ROLL_ACT_MLP_TANH_GAUSS || source == ROLL_ACT_MLP_TANH_FAST_GAUSS; }
+// the hidden-layer sources
+constexpr bool roll_act_is_mlp(int source) {
+    return source == ROLL_ACT_MLP_RELU || source == ROLL_ACT_MLP_TANH || source == ROLL_ACT_MLP_TANH_FAST || roll_act_samples(source) || roll_act_gauss(source);
+}
+// the hidden activation of a hidden-layer source (mlp_policy.h's MLP_ACT_*): the one mapping the kernels and the host wrappers read
+constexpr int roll_act_mlp_act(int source) {
+    return source == ROLL_ACT_MLP_TANH || source == ROLL_ACT_MLP_TANH_SAMPLE || source == ROLL_ACT_MLP_TANH_GAUSS ? MLP_ACT_TANH
+           : source == ROLL_ACT_MLP_TANH_FAST || source == ROLL_ACT_MLP_TANH_FAST_SAMPLE || source == ROLL_ACT_MLP_TANH_FAST_GAUSS ? MLP_ACT_TANH_FAST
+                                                                                                                                  : MLP_ACT_RELU;
+}
+// and back: the argmax / score, SAMPLE and GAUSS source of an activation
+constexpr int roll_act_mlp_plain(int act) { return act == MLP_ACT_TANH_FAST ? ROLL_ACT_MLP_TANH_FAST : act == MLP_ACT_TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU; }
+constexpr int roll_act_mlp_sample(int act) { return act == MLP_ACT_TANH_FAST ? ROLL_ACT_MLP_TANH_FAST_SAMPLE : act == MLP_ACT_TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE; }
+constexpr int roll_act_mlp_gauss(int act) { return act == MLP_ACT_TANH_FAST ? ROLL_ACT_MLP_TANH_FAST_GAUSS : act == MLP_ACT_TANH ? ROLL_ACT_MLP_TANH_GAUSS : ROLL_ACT_MLP_RELU_GAUSS; }
+// from a run-time source to its activation as a template argument, as with_bools (common.h) does for bools: f(std::integral_constant<int, MLP_ACT_*>{})
+template <class F>
+void with_mlp_act(F&& f, int source) {
+    switch (roll_act_mlp_act(source)) {
+    case MLP_ACT_TANH_FAST: f(std::integral_constant<int, MLP_ACT_TANH_FAST>{}); break;
+    case MLP_ACT_TANH: f(std::integral_constant<int, MLP_ACT_TANH>{}); break;
+    default: f(std::integral_constant<int, MLP_ACT_RELU>{}); break;
+    }
+}
 // the sources that decide from the observation
 constexpr bool roll_act_observes(int source) { return source == ROLL_ACT_LINEAR || roll_act_is_mlp(source); }
 

@@ -169,6 +169,13 @@ __global__ void __launch_bounds__(256) math_probe_kernel(uint32_t first, uint64_
     }
 }
 
+// result bits of mlp_policy.h's hidden activation for the patterns first .. first + count - 1 (mgym_act_probe)
+template <int ACT>
+__global__ void __launch_bounds__(256) act_probe_kernel(uint32_t first, uint64_t count, uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) out[i] = as_u32(mlp_activate<ACT>(as_f32(first + (uint32_t)i)));
+}
+
 // mlp_policy.h's draw for one case per lane (mgym_sample_probe): scores [A][count], one Philox word per case; the action, and c_0 .. c_{A-1} if asked
 template <int A>
 __global__ void __launch_bounds__(256) sample_probe_kernel(uint64_t count, const float* __restrict__ scores, const uint32_t* __restrict__ words, uint32_t* __restrict__ actions,
@@ -307,6 +314,28 @@ extern "C" int mgym_math_probe(int device, int fn, uint32_t first, uint64_t coun
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (prev >= 0) (void)hipSetDevice(prev);
     if (e != hipSuccess) return hip_fail(e, "math_probe", __FILE__, __LINE__);
+    return MGYM_OK;
+}
+
+extern "C" int mgym_act_probe(int device, int activation, uint32_t first, uint64_t count, uint32_t* out) {
+    if (!out || count == 0 || count > 0x100000000ull - first || (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH && activation != MGYM_ACT_TANH_FAST)) {
+        set_last_error("mgym_act_probe: NULL output, empty or out-of-range pattern span, or unknown activation");
+        return MGYM_ERR_BAD_ARG;
+    }
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    MGYM_HIP(hipSetDevice(device));
+    const uint64_t blocks = (count + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536)), block(256);
+    switch (activation) {
+        case MGYM_ACT_RELU: hipLaunchKernelGGL(act_probe_kernel<MLP_ACT_RELU>, grid, block, 0, nullptr, first, count, out); break;
+        case MGYM_ACT_TANH: hipLaunchKernelGGL(act_probe_kernel<MLP_ACT_TANH>, grid, block, 0, nullptr, first, count, out); break;
+        default: hipLaunchKernelGGL(act_probe_kernel<MLP_ACT_TANH_FAST>, grid, block, 0, nullptr, first, count, out); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return hip_fail(e, "act_probe", __FILE__, __LINE__);
     return MGYM_OK;
 }
 

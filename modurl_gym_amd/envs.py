@@ -250,9 +250,9 @@ class VecEnv:
 
     def _mlp_args(self, policy, hidden, activation):
         """(contiguous float32 policy or None, activation value) of the hidden-layer entry points, the policy's length checked against H and the family"""
-        act = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH}.get(activation, activation)
+        act = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH, "tanh_fast": L.ACT_TANH_FAST}.get(activation, activation)
         if not isinstance(act, (int, np.integer)):
-            raise PolicyShapeError(L.ERR_BAD_ARG, f'activation must be "relu", "tanh" or an MGYM_ACT_* value, got {activation!r}')
+            raise PolicyShapeError(L.ERR_BAD_ARG, f'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value, got {activation!r}')
         pol = None
         if policy is not None:
             D, A = self.mlp_dims()
@@ -264,7 +264,8 @@ class VecEnv:
 
     def rollout_mlp_device(self, policy, hidden, activation, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): `policy` = the packed host floats of pack_mlp (or None, which the
-        engine rejects), `hidden` = H, `activation` = "relu" / "tanh" or the MGYM_ACT_* value.  A policy of the wrong length for H raises PolicyShapeError."""
+        engine rejects), `hidden` = H, `activation` = "relu" / "tanh" / "tanh_fast" or the MGYM_ACT_* value ("tanh" is glibc's tanhf to the bit and most of the
+        launch's time; "tanh_fast" is the cheap tanh include/mgym.h defines word for word, within 2.5 f32 spacings of tanh).  A policy of the wrong length for H raises PolicyShapeError."""
         pol, act = self._mlp_args(policy, hidden, activation)
         _check(self._lib.mgym_rollout_mlp(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, int(K), _ptr(actions_out),
                                           _ptr(obs_out), _ptr(reward_out), _ptr(done_out), _ptr(trunc_out)))

@@ -162,7 +162,7 @@ class TorchVecEnv:
     def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
         """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): w1 [H, D], b1 [H], w2 [A, H], b2 [A] are tensors (or arrays) in
         nn.Linear layout — `rollout_mlp(net[0].weight, net[0].bias, net[2].weight, net[2].bias, K)` for nn.Sequential(Linear, ReLU / Tanh, Linear) — read on the
-        host during the call; activation "relu" or "tanh".  Returns (actions, obs, reward, done, truncated) like rollout_linear."""
+        host during the call; activation "relu", "tanh" or "tanh_fast" (the cheap tanh of include/mgym.h: what a collector wants).  Returns (actions, obs, reward, done, truncated) like rollout_linear."""
         self._bind_stream()
         host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2)]
         policy, H = self.env.pack_mlp(*host)

@@ -29,6 +29,7 @@ pub const MGYM_FLAG_AUTO_RESET: u32 = 1;
 
 pub const MGYM_ACT_RELU: i32 = 0;
 pub const MGYM_ACT_TANH: i32 = 1;
+pub const MGYM_ACT_TANH_FAST: i32 = 3; // 2 is not assigned
 
 pub const MGYM_MATH_SINF: c_int = 0;
 pub const MGYM_MATH_COSF: c_int = 1;
@@ -165,6 +166,7 @@ unsafe extern "C" {
     pub fn mgym_episode_count(env: *mut mgym_env, finished: *mut u64) -> c_int;
     pub fn mgym_selftest_cartpole_math(device: c_int, mismatches: *mut u64) -> c_int;
     pub fn mgym_math_probe(device: c_int, fn_: c_int, first: u32, count: u64, out: *mut u32) -> c_int;
+    pub fn mgym_act_probe(device: c_int, activation: c_int, first: u32, count: u64, out: *mut u32) -> c_int;
     pub fn mgym_sample_probe(
         device: c_int,
         n_actions: i32,

@@ -33,6 +33,9 @@ def kernels(path):
     if md >= 0:
         # one YAML list entry per kernel: "  - .agpr_count ... .args: ... .name: <kernel> ... .symbol"
         for ent in re.split(r"^  - (?=\.agpr_count)", text[md:], flags=re.M)[1:]:
+            # the list's last entry ends where the next top-level key (amdhsa.target) begins, and has no line end of its own
+            ent = re.split(r"\n(?=\S)", ent, maxsplit=1)[0].rstrip("\n")
+            assert ent.startswith(".agpr_count")
             nm = re.search(r"^\s+\.name:\s+(\S+)", ent, re.M)
             if nm:
                 meta[nm.group(1)] = ent
