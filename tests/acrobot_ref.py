@@ -1,38 +1,35 @@
 """References for Acrobot-v1 (MGYM_ACROBOT), shared by test_acrobot_ref.py, test_acrobot_host.py and test_gpu_acrobot.py.  No test here.
 
  * AcrobotRef — the word-exact reference: the text of include/mgym.h restated on numpy float32 arrays, one rounded operation per line.  sinf, cosf,
-   fmodf (and the policies' fmaf / tanhf) are glibc's, obtained as tests/pendulum_ref.py obtains them; Philox, the reset's 53-bit uniform and the
-   categorical draw come from tests/pendulum_ref.py and tests/mlp_sample_ref.py.
+   fmodf are glibc's over whole arrays (tests/glibc_f32.py); the hidden-layer policy is tests/mlp_ref.py's, Philox and the reset's 53-bit uniform
+   tests/philox_ref.py's, the categorical draw tests/mlp_sample_ref.py's.
  * step_f64 — gymnasium's step in float64 (the text of gymnasium/envs/classic_control/acrobot.py with book_or_nips = "book" and torque_noise_max = 0:
    gymnasium is not a dependency): rk4, wrap with its while loops, bound, the book dynamics with cos(x - pi/2).
  * the build of tests/native/acrobot_check.cpp — modurl_gym_amd/csrc/acrobot_step.h compiled for the host — as a shared object and as a program.
 """
 import ctypes as C
+import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 
+import mlp_ref as M
 import mlp_sample_ref as S
-import pendulum_ref as P
-from mlp_policy_ref import mlp_ref, n_floats, split  # noqa: F401
-from pendulum_ref import clamp, cosf, env_draw, fmaf, fmodf, same_words, sinf, tanhf, uniform_f64_to_f32, words_of  # noqa: F401
+import native_build
+from glibc_f32 import cosf, fmodf, sinf
+from mlp_ref import RELU, TANH, argmax_words
+from pendulum_ref import clamp
+from philox_ref import SLOT_POLICY, env_draw, own_word, uniform_f64_to_f32
+from words import same_words, words_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "acrobot_check.cpp")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
+SRC = "acrobot_check.cpp"
 F = np.float32
 PI_F, TWO_PI_F = F(3.14159274), F(6.28318548)
 V1, V2 = F(4 * math.pi), F(9 * math.pi)
 H_F, DT_F = F(0.1), F(0.2)
 DT6 = F(F(0.2) / F(6.0))
-M32 = np.uint64(0xFFFFFFFF)
-SLOT_POLICY = 0x40000000
 POL_TABLE, POL_LINEAR, POL_UNIFORM, POL_MLP_RELU, POL_MLP_TANH, POL_MLP_RELU_SAMPLE, POL_MLP_TANH_SAMPLE = range(7)
-RELU, TANH = 0, 1
-D, A = 6, 3
+D, A, _ = M.FAMILIES["acrobot"]
 
 
 class AbRun(C.Structure):
@@ -43,26 +40,15 @@ class AbRun(C.Structure):
                 ("state_out", C.c_void_p), ("finished", C.c_uint64), ("bad", C.c_int32), ("flush", C.c_int32)]
 
 
-_shared = None
+@functools.lru_cache(maxsize=None)
+def check_lib():
+    lib = C.CDLL(native_build.shared(SRC))
+    lib.acrobot_run.restype, lib.acrobot_run.argtypes = C.c_int, [C.POINTER(AbRun)]
+    return lib
 
 
-def build_shared():
-    global _shared
-    if _shared is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libacrobot_check.so")
-        subprocess.run(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC, "-lm"], check=True)
-        lib = C.CDLL(so)
-        lib.acrobot_run.restype, lib.acrobot_run.argtypes = C.c_int, [C.POINTER(AbRun)]
-        _shared = lib
-    return _shared
-
-
-def build_program(extra=(), name="acrobot_check"):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, name)
-    subprocess.run(["g++", *FLAGS, *extra, "-o", exe, SRC, "-lm"], check=True)
-    return exe
+def check_program():
+    return native_build.program(SRC)
 
 
 # ---- the text of include/mgym.h ----
@@ -160,22 +146,9 @@ def reset_draw(seed, gid, episode):
 
 def uniform_actions(policy_seed, call, gid, t):
     """mgym_rollout_uniform's action of env gid at step t of the handle's uniform call number `call` (MountainCar's Discrete(3) draw)"""
-    gid = np.asarray(gid, np.uint64)
-    g4 = gid & ~np.uint64(3)
-    w = S.philox4x32_10(g4 & M32, g4 >> np.uint64(32), np.uint64(call), np.uint64(SLOT_POLICY + int(t) // 2), int(policy_seed) & 0xFFFFFFFF, (int(policy_seed) >> 32) & 0xFFFFFFFF)
-    word = np.choose((gid & np.uint64(3)).astype(np.intp), w).astype(np.uint32)
+    word = own_word(policy_seed, call, gid, SLOT_POLICY + int(t) // 2)
     h = (word >> np.uint32(16)) if int(t) & 1 else (word & np.uint32(0xFFFF))
     return ((h * np.uint32(3)) >> np.uint32(16)).astype(np.uint32)
-
-
-def argmax_words(s):
-    """the sequential strict argmax over scores [A, n]: the first of equal scores wins, a NaN never replaces an earlier score"""
-    best, act = s[0].copy(), np.zeros(s.shape[1], np.uint32)
-    with np.errstate(all="ignore"):
-        for j in range(1, s.shape[0]):
-            m = s[j] > best
-            best, act = np.where(m, s[j], best), np.where(m, np.uint32(j), act)
-    return act.astype(np.uint32)
 
 
 def linear_scores(policy, obs):
@@ -188,22 +161,6 @@ def linear_scores(policy, obs):
                 s = s + w[j, q] * obs[q]
             out.append((s + w[j, 6]).astype(F))
     return np.stack(out)
-
-
-def mlp_scores(policy, H, act, obs):
-    """mgym_rollout_mlp's scores with D = 6, A = 3 over an observation [6, n]: the fmaf chains of include/mgym.h, every fmaf and tanhf glibc's"""
-    w1, b1, w2, b2 = split(policy, D, A, H)
-    n = obs.shape[1]
-    with np.errstate(all="ignore"):
-        s = [np.full(n, b2[k], F) for k in range(A)]
-        for j in range(H):
-            pre = np.full(n, b1[j], F)
-            for q in range(D):
-                pre = fmaf(w1[j, q], obs[q], pre)
-            h = tanhf(pre) if act == TANH else np.where(pre > F(0), pre, F(0)).astype(F)
-            for k in range(A):
-                s[k] = fmaf(w2[k, j], h, s[k])
-    return np.stack(s)
 
 
 class AcrobotRef:
@@ -283,10 +240,10 @@ class AcrobotRef:
         return self.rollout(K, lambda t, o: argmax_words(linear_scores(policy, o)))
 
     def rollout_mlp(self, policy, H, act, K):
-        return self.rollout(K, lambda t, o: argmax_words(mlp_scores(policy, H, act, o)))
+        return self.rollout(K, lambda t, o: argmax_words(M.scores(policy, D, A, H, o, act)))
 
     def rollout_mlp_sample(self, policy, H, act, seed, call, K):
-        return self.rollout(K, lambda t, o: S.draw(mlp_scores(policy, H, act, o), S.words(seed, call, self.gid, t))[0])
+        return self.rollout(K, lambda t, o: S.draw(M.scores(policy, D, A, H, o, act), S.words(seed, call, self.gid, t))[0])
 
 
 # ---- gymnasium's step in float64 ----
@@ -341,7 +298,7 @@ def step_f64(th1, th2, w1, w2, a):
 def header_run(n, steps, seed=0, env_id_base=0, limit=0, auto_reset=False, policy=POL_TABLE, weights=None, hidden=0, policy_seed=0, call=0,
                actions=None, state=None, flush=False):
     """acrobot_run of tests/native/acrobot_check.cpp -> dict(actions, obs0, obs, reward, done, trunc, elapsed, state, finished, bad); flush: with denormals flushed to zero (x86)"""
-    lib = build_shared()
+    lib = check_lib()
     w = np.ascontiguousarray(weights if weights is not None else np.zeros(21), F)
     acts = np.ascontiguousarray(actions if actions is not None else np.zeros((steps, n)), np.uint32)
     st = None if state is None else np.ascontiguousarray(state, np.uint32)

@@ -5,7 +5,6 @@ device (mgym_ll_geom_probe).  Every check prints its figures before it asserts.
 Slack: fp = 16 spacings of float32 at the case's largest absolute coordinate (ll_geom_ref.fp_slack) — derived, not tuned.  The
 other constants are Box2D's (ll_geom_ref.RADIUS / TARGET / TOL); margins that are not are explained where they are used."""
 import ctypes as C
-import functools
 import os
 import subprocess
 import tempfile
@@ -14,8 +13,8 @@ import numpy as np
 
 import ll_geom_cases as gc
 import ll_geom_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import native_build
+from words import same  # noqa: F401  (exact words: what the probes' outputs are compared by)
 
 SHAPES, DISTANCE, MANIFOLD, TOI = range(4)
 IN_COLS = {SHAPES: 0, DISTANCE: 8, MANIFOLD: 8, TOI: 11}
@@ -29,10 +28,6 @@ CF_VERTEX, CF_FACE = 0, 1
 
 def words(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same_words(a, b):
-    return a.shape == b.shape and np.array_equal(words(a), words(b))
 
 
 def unpack_shapes(out):
@@ -286,14 +281,8 @@ def oracle_probe(fn, cases=None):
     return out
 
 
-@functools.lru_cache(maxsize=None)
 def host_exe():
-    build = os.path.join(ROOT, "tests", "native", "_build")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "ll_geom_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe,
-                    os.path.join(ROOT, "tests", "native", "ll_geom_check.cpp"), "-lm"], check=True)
-    return exe
+    return native_build.program("ll_geom_check.cpp")
 
 
 def host_probe(fn, cases=None):

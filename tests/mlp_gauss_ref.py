@@ -1,26 +1,19 @@
 """Shared by test_mlp_gauss_host.py, test_gpu_gauss_probe.py and test_gpu_mlp_gauss.py: a numpy restatement of the draw of mgym_rollout_mlp_gauss, written
 from the text of include/mgym.h ("The draw of z") — numpy float64 for mg_log_u25 (numpy has no fused multiply-add), numpy float32 for the rest, glibc's sinf /
-cosf / fmaf / tanhf through tests/pendulum_ref.py, the vectorised Philox4x32-10 of tests/mlp_sample_ref.py — the cases the tests share, and the build of
+cosf (tests/glibc_f32.py), the block keying of tests/philox_ref.py; mu is tests/mlp_ref.py's one score — the cases the tests share, and the build of
 tests/native/mlp_gauss_check.cpp (modurl_gym_amd/csrc/mlp_policy.h compiled for the host) as a shared object.  No test here."""
 import ctypes as C
+import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 
-import pendulum_ref as P
-from mlp_policy_ref import split
-from mlp_sample_ref import philox4x32_10
+import native_build
+from glibc_f32 import cosf, sinf
+from philox_ref import M32, SLOT_POLICY_GAUSS, block_words
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "mlp_gauss_check.cpp")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
-SLOT_GAUSS = 0x60000000
-M32 = np.uint64(0xFFFFFFFF)
+SRC = "mlp_gauss_check.cpp"
 F = np.float32
-RELU, TANH = 0, 1
 SQRT2 = float.fromhex("0x1.6a09e667f3bcdp+0")
 LN2 = float.fromhex("0x1.62e42fefa39efp-1")
 R_MAX = 5.8871   # above the largest r = sqrt(-2 ln 2^-25) = sqrt(50 ln 2) = 5.88705...
@@ -63,7 +56,7 @@ def gauss_pair(wa, wb):
     r = np.sqrt(q)
     assert r.dtype == F
     phi = (k2.astype(F) * F(2.0 ** -24)) * F(6.28318548)
-    s, c = P.sinf(phi), P.cosf(phi)
+    s, c = sinf(phi), cosf(phi)
     return r * c, r * s, q
 
 
@@ -71,8 +64,7 @@ def pair_words(seed, call, g, t):
     """(wa, wb, odd) of env g at step t: the pair (w0, w1) for g % 4 in {0, 1}, (w2, w3) for {2, 3}, of
     Philox4x32-10(key = seed; counter = (lo32(g & ~3), hi32(g & ~3), call, 0x60000000 + t)); odd = g % 2"""
     g = np.asarray(g, np.uint64)
-    g4 = g & ~np.uint64(3)
-    w = philox4x32_10(g4 & M32, g4 >> np.uint64(32), np.uint64(call), np.uint64(SLOT_GAUSS + int(t)), int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    w = block_words(seed, call, g, SLOT_POLICY_GAUSS + int(t))
     second = ((g >> np.uint64(1)) & np.uint64(1)).astype(bool)
     return np.where(second, w[2], w[0]), np.where(second, w[3], w[1]), (g & np.uint64(1)).astype(bool)
 
@@ -84,21 +76,6 @@ def normals(seed, call, g, t):
     return np.where(odd, zo, ze).astype(F)
 
 
-def mlp_mu(policy, D, H, act, obs):
-    """mgym_rollout_mlp's one score (A = 1) over an observation [D, n]: the fmaf chains of include/mgym.h, every fmaf and tanhf glibc's"""
-    w1, b1, w2, b2 = split(policy, D, 1, H)
-    n = obs.shape[1]
-    with np.errstate(all="ignore"):
-        s = np.full(n, b2[0], F)
-        for j in range(H):
-            pre = np.full(n, b1[j], F)
-            for q in range(D):
-                pre = P.fmaf(w1[j, q], obs[q], pre)
-            h = P.tanhf(pre) if act == TANH else np.where(pre > F(0), pre, F(0)).astype(F)
-            s = P.fmaf(w2[0, j], h, s)
-    return s
-
-
 def gauss_actions(mu, sigma, seed, call, g, t):
     """a = mu + sigma * z: an f32 multiply, then an f32 add"""
     with np.errstate(all="ignore"):
@@ -106,26 +83,14 @@ def gauss_actions(mu, sigma, seed, call, g, t):
         return (np.asarray(mu, F) + sz).astype(F)
 
 
-def same_words(got, exp):
-    return P.same_words(got, exp)
-
-
 # ---- the host-compiled header ----
-_shared = None
-
-
-def build_shared():
-    global _shared
-    if _shared is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libmlp_gauss_check.so")
-        subprocess.run(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC, "-lm"], check=True)
-        lib = C.CDLL(so)
-        lib.mlp_gauss_eval.restype, lib.mlp_gauss_eval.argtypes = None, [C.c_uint64] + [C.c_void_p] * 6
-        lib.mlp_gauss_actions.restype = C.c_int
-        lib.mlp_gauss_actions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        _shared = lib
-    return _shared
+@functools.lru_cache(maxsize=None)
+def check_lib():
+    lib = C.CDLL(native_build.shared(SRC))
+    lib.mlp_gauss_eval.restype, lib.mlp_gauss_eval.argtypes = None, [C.c_uint64] + [C.c_void_p] * 6
+    lib.mlp_gauss_actions.restype = C.c_int
+    lib.mlp_gauss_actions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    return lib
 
 
 def header_pair(wa, wb, want_log=False):
@@ -133,21 +98,25 @@ def header_pair(wa, wb, want_log=False):
     wa, wb = np.ascontiguousarray(wa, np.uint32), np.ascontiguousarray(wb, np.uint32)
     n = wa.size
     ze, zo, q, L = np.zeros(n, F), np.zeros(n, F), np.zeros(n, F), np.zeros(n, np.float64)
-    build_shared().mlp_gauss_eval(n, wa.ctypes.data, wb.ctypes.data, ze.ctypes.data, zo.ctypes.data, q.ctypes.data, L.ctypes.data if want_log else None)
+    check_lib().mlp_gauss_eval(n, wa.ctypes.data, wb.ctypes.data, ze.ctypes.data, zo.ctypes.data, q.ctypes.data, L.ctypes.data if want_log else None)
     return (ze, zo, q, L) if want_log else (ze, zo, q)
+
+
+def lane_words(seed, call, g0, n, t):
+    """the words [4, n / 4] of the blocks g0, g0 + 4, .. at step t: what the lane form of the header takes (g0 and n multiples of 4)"""
+    assert n % 4 == 0 and g0 % 4 == 0
+    g4 = np.uint64(g0) + np.uint64(4) * np.arange(n // 4, dtype=np.uint64)
+    return np.ascontiguousarray(np.stack(block_words(seed, call, g4, SLOT_POLICY_GAUSS + int(t))), np.uint32)
 
 
 def header_actions(policy, D, H, act, sigma, obs, seed, call, g0, t):
     """the lane form of the host-compiled header on an observation [D, n] for the ids g0 .. g0 + n - 1 (g0 and n multiples of 4) -> action words as float32"""
     obs = np.ascontiguousarray(obs, F)
     n = obs.shape[1]
-    assert n % 4 == 0 and g0 % 4 == 0
-    g4 = np.uint64(g0) + np.uint64(4) * np.arange(n // 4, dtype=np.uint64)
-    w = np.ascontiguousarray(np.stack(philox4x32_10(g4 & M32, g4 >> np.uint64(32), np.uint64(call), np.uint64(SLOT_GAUSS + int(t)), int(seed) & 0xFFFFFFFF,
-                                                   (int(seed) >> 32) & 0xFFFFFFFF)), np.uint32)
+    w = lane_words(seed, call, g0, n, t)
     pol = np.ascontiguousarray(policy, F)
     out = np.zeros(n, np.uint32)
-    assert build_shared().mlp_gauss_actions(D, act, H, pol.ctypes.data, float(F(sigma)), n, obs.ctypes.data, w.ctypes.data, out.ctypes.data) == 0
+    assert check_lib().mlp_gauss_actions(D, act, H, pol.ctypes.data, float(F(sigma)), n, obs.ctypes.data, w.ctypes.data, out.ctypes.data) == 0
     return out.view(F)
 
 

@@ -1,93 +1,36 @@
 """Shared by test_mlp_sample_host.py, test_gpu_sample_probe.py and test_gpu_mlp_sample.py: a Python restatement of the draw of mgym_rollout_mlp_sample,
-written from the text of include/mgym.h ("The draw") — glibc's expm1f through ctypes, numpy float32 for the subtraction, the adds and the one multiply, and
-a vectorised Philox4x32-10 that test_mlp_sample_host.py checks against oracle.oracle.philox — the cases the tests share, and the build of
+written from the text of include/mgym.h ("The draw") — glibc's expm1f (tests/glibc_f32.py), numpy float32 for the subtraction, the adds and the one multiply,
+and the Philox4x32-10 of tests/philox_ref.py, which test_mlp_sample_host.py checks against oracle.oracle.philox — the cases the tests share, and the build of
 tests/native/mlp_sample_check.cpp (modurl_gym_amd/csrc/mlp_policy.h compiled for the host) as a shared object and as a program."""
 import ctypes as C
-import ctypes.util
+import functools
 import itertools
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "mlp_sample_check.cpp")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
-SLOT_SAMPLE = 0x50000000
-M32 = np.uint64(0xFFFFFFFF)
+import native_build
+from glibc_f32 import expm1f
+from philox_ref import SLOT_POLICY_SAMPLE, own_word
 
-_libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
-_expm1f = _libm.expm1f
-_expm1f.restype, _expm1f.argtypes = C.c_float, [C.c_float]
-_libc = C.CDLL(None)
-_libc.gnu_get_libc_version.restype = C.c_char_p
+SRC = "mlp_sample_check.cpp"
 
 
-def glibc_has_fdlibm_expm1f():
-    """glibc replaced the fdlibm expm1f (which mg_expm1f restates) by a correctly rounded one in 2.41: the words of the draw are glibc's only before that"""
-    major, minor = (int(v) for v in _libc.gnu_get_libc_version().decode().split(".")[:2])
-    return (major, minor) < (2, 41)
+@functools.lru_cache(maxsize=None)
+def check_lib():
+    """the host-compiled header: lib.mlp_sample_eval(A, n, scores [A][n], words [n], actions [n], cum [A][n] or None) -> 0"""
+    lib = C.CDLL(native_build.shared(SRC))
+    lib.mlp_sample_eval.restype = C.c_int
+    lib.mlp_sample_eval.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return lib
 
 
-def expm1f_scalar(x):
-    """glibc's expm1f on one float, through ctypes"""
-    return np.float32(_expm1f(float(np.float32(x))))
-
-
-_shared = None
-
-
-def build_shared():
-    """the host-compiled header: lib.mlp_sample_eval(A, n, scores [A][n], words [n], actions [n], cum [A][n] or None) -> 0, and lib.glibc_expm1f_bulk(n, x, y),
-    glibc's expm1f called in a loop (the restatement's libm call for whole arrays)"""
-    global _shared
-    if _shared is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libmlp_sample_check.so")
-        subprocess.run(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC, "-lm"], check=True)
-        lib = C.CDLL(so)
-        lib.mlp_sample_eval.restype = C.c_int
-        lib.mlp_sample_eval.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.glibc_expm1f_bulk.restype = None
-        lib.glibc_expm1f_bulk.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p]
-        _shared = lib
-    return _shared
-
-
-def build_program():
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "mlp_sample_check")
-    subprocess.run(["g++", *FLAGS, "-fopenmp", "-o", exe, SRC, "-lm"], check=True)
-    return exe
-
-
-def expm1f(x):
-    """glibc's expm1f over a float32 array"""
-    x = np.ascontiguousarray(x, np.float32)
-    y = np.empty_like(x)
-    build_shared().glibc_expm1f_bulk(x.size, x.ctypes.data, y.ctypes.data)
-    return y
-
-
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 over arrays of counters -> the four output words (uint32 arrays)"""
-    c0, c1, c2, c3 = (np.asarray(v, np.uint64) & M32 for v in np.broadcast_arrays(c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0 & 0xFFFFFFFF), np.uint64(k1 & 0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        hi0, lo0, hi1, lo1 = p0 >> np.uint64(32), p0 & M32, p1 >> np.uint64(32), p1 & M32
-        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
-    return [v.astype(np.uint32) for v in (c0, c1, c2, c3)]
+def check_program():
+    return native_build.program(SRC, extra=("-fopenmp",))
 
 
 def words(seed, call, g, t):
     """w of env g at step t: word (g % 4) of Philox4x32-10(key = seed; counter = (lo32(g & ~3), hi32(g & ~3), call, 0x50000000 + t))"""
-    g = np.asarray(g, np.uint64)
-    g4 = g & ~np.uint64(3)
-    out = philox4x32_10(g4 & M32, g4 >> np.uint64(32), np.uint64(call), np.uint64(SLOT_SAMPLE + int(t)), int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
-    return np.choose((g & np.uint64(3)).astype(np.intp), out)
+    return own_word(seed, call, g, SLOT_POLICY_SAMPLE + int(t))
 
 
 def draw(scores, w):
@@ -117,14 +60,8 @@ def header_draw(scores, w, want_cum=True):
     w = np.ascontiguousarray(w, np.uint32)
     A, n = s.shape
     act, cum = np.zeros(n, np.uint32), np.zeros((A, n), np.float32)
-    assert build_shared().mlp_sample_eval(A, n, s.ctypes.data, w.ctypes.data, act.ctypes.data, cum.ctypes.data if want_cum else None) == 0
+    assert check_lib().mlp_sample_eval(A, n, s.ctypes.data, w.ctypes.data, act.ctypes.data, cum.ctypes.data if want_cum else None) == 0
     return act, cum
-
-
-def same_words(got, exp):
-    """equal bit patterns; NaNs are equal as a class"""
-    g, e = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(exp, np.float32)
-    return bool(np.all((g.view(np.uint32) == e.view(np.uint32)) | (np.isnan(g) & np.isnan(e))))
 
 
 # ---- the cases the host test and the probe test share ----

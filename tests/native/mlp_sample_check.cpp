@@ -1,7 +1,6 @@
 // CPU check of the draw of mgym_rollout_mlp_sample (mlp_sample of modurl_gym_amd/csrc/mlp_policy.h, the lines the kernels compile), built with
 // g++ -ffp-contract=off.
-//   as a shared object (tests/mlp_sample_ref.py): mlp_sample_eval over n cases; glibc_expm1f_bulk, the host's expm1f over an array (the restatement's
-//     one libm call, in a loop)
+//   as a shared object (tests/mlp_sample_ref.py): mlp_sample_eval over n cases
 //   as a program (tests/test_mlp_sample_host.py; -fopenmp): "mlp_sample_check <threads>" runs mg_expm1f(x) and mg_expm1f(x) + 1.0f against glibc's expm1f
 //     on all 2^31 bit patterns with the sign bit set (NaN results compared as a class) and prints "expm1f total=.. bad=.." and "expm1f_plus1 total=.. bad=.."
 #include <math.h>
@@ -33,10 +32,6 @@ extern "C" int mlp_sample_eval(int A, uint64_t n, const float* scores, const uin
     else if (A == 4) eval<4>(n, scores, words, actions, cum);
     else return 1;
     return 0;
-}
-
-extern "C" void glibc_expm1f_bulk(uint64_t n, const float* x, float* y) {
-    for (uint64_t i = 0; i < n; ++i) y[i] = expm1f(x[i]);
 }
 
 static bool same(float a, float b) {

@@ -2,7 +2,7 @@
 // draw, the uniform / linear / hidden-layer policies) — compiled for the host with g++ -ffp-contract=off and driven by the loop the kernels put round
 // them.  Built and run by tests/test_pendulum_host.py (tests/pendulum_ref.py), which compares every word with a numpy restatement of the text of
 // include/mgym.h; no GPU involved.  This is a test of the kernel logic, not a product CPU path.
-//   shared object:  pendulum_run(..) below, and glibc's sinf / cosf / fmodf / fmaf / tanhf over arrays (the restatement's libm calls in bulk)
+//   shared object:  pendulum_run(..) below
 //   program:        pendulum_check   runs a fixed scenario through pendulum_run (every policy, imported states, a NaN action) and prints one
 //                   checksum line per case; it is also what a sanitizer build runs (it has its own main and reads no input)
 #include <math.h>
@@ -120,13 +120,6 @@ int pendulum_run(PdRun* p) {
     if (p->limit) run<true>(*p); else run<false>(*p);
     return 0;
 }
-
-// glibc over arrays: the libm calls of the Python restatement, nothing of the header
-void glibc_sinf_bulk(uint64_t n, const float* x, float* y) { for (uint64_t i = 0; i < n; ++i) y[i] = sinf(x[i]); }
-void glibc_cosf_bulk(uint64_t n, const float* x, float* y) { for (uint64_t i = 0; i < n; ++i) y[i] = cosf(x[i]); }
-void glibc_tanhf_bulk(uint64_t n, const float* x, float* y) { for (uint64_t i = 0; i < n; ++i) y[i] = tanhf(x[i]); }
-void glibc_fmodf_bulk(uint64_t n, const float* x, float m, float* y) { for (uint64_t i = 0; i < n; ++i) y[i] = fmodf(x[i], m); }
-void glibc_fmaf_bulk(uint64_t n, float a, const float* b, const float* c, float* y) { for (uint64_t i = 0; i < n; ++i) y[i] = fmaf(a, b[i], c[i]); }
 
 }  // extern "C"
 

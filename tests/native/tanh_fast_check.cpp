@@ -8,7 +8,6 @@
 //   tanh_fast_bulk       the result words for an array of input words
 //   tanh_fast_compare    result words of the patterns first .. first + count - 1 (from the device: mgym_act_probe) against this build's, NaNs as a class:
 //                        the number that differ and the first such pattern
-//   glibc_fmaf_arrays    out[i] = fmaf(a[i], b[i], c[i]): what tests/tanh_fast_ref.py restates the text with (Python 3.10 has no math.fma)
 // Used by tests/tanh_fast_ref.py; run by tests/test_tanh_fast_host.py.
 #include <math.h>
 #include <stdint.h>
@@ -123,8 +122,4 @@ extern "C" uint64_t tanh_fast_compare(uint32_t first, uint64_t count, const uint
     }
     if (bad && first_bad) *first_bad = first + (uint32_t)where;
     return bad;
-}
-
-extern "C" void glibc_fmaf_arrays(uint64_t count, const float* a, const float* b, const float* c, float* out) {
-    for (uint64_t i = 0; i < count; ++i) out[i] = fmaf(a[i], b[i], c[i]);
 }

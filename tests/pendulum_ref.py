@@ -1,32 +1,29 @@
 """References for Pendulum-v1 (MGYM_PENDULUM), shared by test_pendulum_ref.py, test_pendulum_host.py and test_gpu_pendulum.py.  No test here.
 
  * PendulumRef — the word-exact reference: the text of include/mgym.h restated on numpy float32 arrays, one rounded operation per line.  sinf, cosf,
-   fmodf (and the policy's fmaf / tanhf) are glibc's, called through ctypes over whole arrays by the libm wrappers of tests/native/pendulum_check.cpp
-   (numpy's own f32 sin is not glibc's).  The reset draw and the uniform policy use the vectorised Philox4x32-10 of tests/mlp_sample_ref.py.
+   fmodf are glibc's over whole arrays (tests/glibc_f32.py: numpy's own f32 sin is not glibc's); the hidden-layer policy is tests/mlp_ref.py's; the
+   reset draw and the uniform policy use the Philox4x32-10 of tests/philox_ref.py.
  * step_f64 — gymnasium's step in float64 (the text of gymnasium/envs/classic_control/pendulum.py: gymnasium is not a dependency), angle_normalize with
    Python's % and the true pi.
  * the build of tests/native/pendulum_check.cpp — modurl_gym_amd/csrc/pendulum_step.h compiled for the host — as a shared object and as a program.
 """
 import ctypes as C
+import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 
-from mlp_policy_ref import mlp_ref, n_floats, split  # noqa: F401  (the scalar restatement of the hidden-layer policy: the cross-check of mlp_torque)
-from mlp_sample_ref import philox4x32_10
+import mlp_ref as M
+import native_build
+from glibc_f32 import cosf, fmodf, sinf
+from mlp_ref import RELU, TANH
+from philox_ref import SLOT_POLICY, env_draw, own_word, uniform_f64_to_f32
+from words import same_words, words_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "pendulum_check.cpp")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"]
+SRC = "pendulum_check.cpp"
 F = np.float32
 PI_F, TWO_PI_F = F(3.14159274), F(6.28318548)
-M32 = np.uint64(0xFFFFFFFF)
-SLOT_POLICY = 0x40000000
 POL_TABLE, POL_LINEAR, POL_UNIFORM, POL_MLP_RELU, POL_MLP_TANH = range(5)
-RELU, TANH = 0, 1
 REWARD_MIN = -16.2736044   # -(pi^2 + 0.1 * 8^2 + 0.001 * 2^2)
 BIG_TH = (1e6, -1e6, 12345.678, 3.1415927, -3.1415927, -0.0)   # imported angles: beyond the fast range reduction, at the wrap, and -0
 
@@ -39,75 +36,15 @@ class PdRun(C.Structure):
                 ("finished", C.c_uint64), ("bad", C.c_int32), ("flush", C.c_int32)]
 
 
-_shared = None
+@functools.lru_cache(maxsize=None)
+def check_lib():
+    lib = C.CDLL(native_build.shared(SRC))
+    lib.pendulum_run.restype, lib.pendulum_run.argtypes = C.c_int, [C.POINTER(PdRun)]
+    return lib
 
 
-def build_shared():
-    global _shared
-    if _shared is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libpendulum_check.so")
-        subprocess.run(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC, "-lm"], check=True)
-        lib = C.CDLL(so)
-        lib.pendulum_run.restype, lib.pendulum_run.argtypes = C.c_int, [C.POINTER(PdRun)]
-        for name in ("glibc_sinf_bulk", "glibc_cosf_bulk", "glibc_tanhf_bulk"):
-            getattr(lib, name).restype, getattr(lib, name).argtypes = None, [C.c_uint64, C.c_void_p, C.c_void_p]
-        lib.glibc_fmodf_bulk.restype, lib.glibc_fmodf_bulk.argtypes = None, [C.c_uint64, C.c_void_p, C.c_float, C.c_void_p]
-        lib.glibc_fmaf_bulk.restype, lib.glibc_fmaf_bulk.argtypes = None, [C.c_uint64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-        _shared = lib
-    return _shared
-
-
-def build_program(extra=(), name="pendulum_check"):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, name)
-    subprocess.run(["g++", *FLAGS, *extra, "-o", exe, SRC, "-lm"], check=True)
-    return exe
-
-
-# ---- glibc over float32 arrays ----
-def _unary(name, x):
-    x = np.ascontiguousarray(x, F)
-    y = np.empty_like(x)
-    getattr(build_shared(), name)(x.size, x.ctypes.data, y.ctypes.data)
-    return y
-
-
-def sinf(x):
-    return _unary("glibc_sinf_bulk", x)
-
-
-def cosf(x):
-    return _unary("glibc_cosf_bulk", x)
-
-
-def tanhf(x):
-    return _unary("glibc_tanhf_bulk", x)
-
-
-def fmodf(x, m):
-    x = np.ascontiguousarray(x, F)
-    y = np.empty_like(x)
-    build_shared().glibc_fmodf_bulk(x.size, x.ctypes.data, float(F(m)), y.ctypes.data)
-    return y
-
-
-def fmaf(a, b, c):
-    """fmaf(a, b[i], c[i]) with a scalar a: one correctly rounded fused multiply-add per element"""
-    b, c = np.ascontiguousarray(b, F), np.ascontiguousarray(c, F)
-    y = np.empty_like(b)
-    build_shared().glibc_fmaf_bulk(b.size, float(F(a)), b.ctypes.data, c.ctypes.data, y.ctypes.data)
-    return y
-
-
-def words_of(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def same_words(got, exp):
-    """equal bit patterns; NaNs are equal as a class"""
-    g, e = np.ascontiguousarray(got, F), np.ascontiguousarray(exp, F)
-    return bool(np.all((g.view(np.uint32) == e.view(np.uint32)) | (np.isnan(g) & np.isnan(e))))
+def check_program():
+    return native_build.program(SRC)
 
 
 # ---- the text of include/mgym.h ----
@@ -147,20 +84,6 @@ def step_words(th, thdot, a, c_g):
     return (np.where(nan, th, th2).astype(F), np.where(nan, thdot, thdot2).astype(F), np.where(nan, F(0), reward).astype(F), nan)
 
 
-def env_draw(seed, gid, episode, slot=0):
-    gid = np.asarray(gid, np.uint64)
-    return philox4x32_10(gid & M32, gid >> np.uint64(32), np.asarray(episode, np.uint64), np.uint64(slot), int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
-
-
-def u53(hi, lo):
-    m = ((hi.astype(np.uint64) >> np.uint64(5)) << np.uint64(26)) | (lo.astype(np.uint64) >> np.uint64(6))
-    return m.astype(np.float64) * (1.0 / 9007199254740992.0)
-
-
-def uniform_f64_to_f32(lo, hi, w_hi, w_lo):
-    return (u53(w_hi, w_lo) * (hi - lo) + lo).astype(F)
-
-
 def reset_draw(seed, gid, episode):
     """-> (th, thdot) of the reset of env gid's episode number `episode`"""
     w = env_draw(seed, gid, episode)
@@ -169,10 +92,7 @@ def reset_draw(seed, gid, episode):
 
 def uniform_actions(policy_seed, call, gid, t):
     """mgym_rollout_uniform's torque of env gid at step t of the handle's uniform call number `call`"""
-    gid = np.asarray(gid, np.uint64)
-    g4 = gid & ~np.uint64(3)
-    w = philox4x32_10(g4 & M32, g4 >> np.uint64(32), np.uint64(call), np.uint64(SLOT_POLICY + int(t)), int(policy_seed) & 0xFFFFFFFF, (int(policy_seed) >> 32) & 0xFFFFFFFF)
-    word = np.choose((gid & np.uint64(3)).astype(np.intp), w)
+    word = own_word(policy_seed, call, gid, SLOT_POLICY + int(t))
     return ((word >> np.uint32(8)).astype(F) * F(2.0 ** -22) - F(2.0)).astype(F)
 
 
@@ -180,21 +100,6 @@ def linear_actions(policy, obs):
     w = np.asarray(policy, F)
     with np.errstate(all="ignore"):
         return (((w[0] * obs[0] + w[1] * obs[1]) + w[2] * obs[2]) + w[3]).astype(F)
-
-
-def mlp_torque(policy, H, act, obs):
-    """mgym_rollout_mlp with D = 3, A = 1 over an observation [3, n]: the fmaf chains of include/mgym.h, every fmaf and tanhf glibc's"""
-    w1, b1, w2, b2 = split(policy, 3, 1, H)
-    n = obs.shape[1]
-    with np.errstate(all="ignore"):
-        s = np.full(n, b2[0], F)
-        for j in range(H):
-            pre = np.full(n, b1[j], F)
-            for q in range(3):
-                pre = fmaf(w1[j, q], obs[q], pre)
-            h = tanhf(pre) if act == TANH else np.where(pre > F(0), pre, F(0)).astype(F)
-            s = fmaf(w2[0, j], h, s)
-    return s
 
 
 class PendulumRef:
@@ -267,7 +172,7 @@ class PendulumRef:
         return self.rollout(K, lambda t, o: linear_actions(policy, o))
 
     def rollout_mlp(self, policy, H, act, K):
-        return self.rollout(K, lambda t, o: mlp_torque(policy, H, act, o))
+        return self.rollout(K, lambda t, o: M.scores(policy, 3, 1, H, o, act)[0])
 
 
 # ---- gymnasium's step in float64 ----
@@ -290,7 +195,7 @@ def step_f64(th, thdot, a, g):
 def header_run(n, steps, seed=0, env_id_base=0, g=10.0, limit=0, auto_reset=False, policy=POL_TABLE, weights=None, hidden=0, policy_seed=0, call=0,
                actions=None, state=None, flush=False):
     """pendulum_run of tests/native/pendulum_check.cpp -> dict(actions, obs0, obs, reward, trunc, elapsed, state, finished, bad); flush: with denormals flushed to zero (x86)"""
-    lib = build_shared()
+    lib = check_lib()
     w = np.ascontiguousarray(weights if weights is not None else np.zeros(4), F)
     acts = np.ascontiguousarray(actions if actions is not None else np.zeros((steps, n)), F)
     st = None if state is None else np.ascontiguousarray(state, np.uint32)

@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 
 import acrobot_ref as R
-import mlp_sample_ref as S
+from glibc_f32 import glibc_has_fdlibm_expm1f
+from mlp_policy_ref import mlp_ref
 
 F = np.float32
 N, STEPS, LIMIT = 256, 64, 7
-needs_fdlibm = pytest.mark.skipif(not S.glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")
+needs_fdlibm = pytest.mark.skipif(not glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")
 
 
 def table_actions(seed=3):
@@ -87,9 +88,9 @@ def test_mlp_policy_equals_the_restatement(H, act):
     got = R.header_run(N, STEPS, **kw)
     R.assert_same_run(got, R.ref_run(N, STEPS, **kw), f"mlp H = {H} act {act}")
     assert H == 1 or len(np.unique(got["actions"])) >= 2   # a policy that really depends on the observation (one unit's largest output weight may be action 0's)
-    # the vectorised chains are those of tests/mlp_policy_ref.py: the scalar restatement on the first observations
+    # the chains are those of tests/mlp_ref.py: its one-observation form (mlp_policy_ref.mlp_ref) on the first observations
     for i in range(0, N, 37):
-        word, _, _ = R.mlp_ref(6, 3, 0, act, H, w, got["obs0"][:, i])
+        word, _, _ = mlp_ref(6, 3, 0, act, H, w, got["obs0"][:, i])
         assert word == int(got["actions"][0, i])
 
 
@@ -158,7 +159,7 @@ def test_an_infinity_a_nan_and_an_invalid_action_return_and_equal_the_restatemen
 
 def test_program_runs_its_scenario():
     """the stand-alone program (what a sanitizer build runs) goes through every policy; its first table case is reproducible from here"""
-    exe = R.build_program()
+    exe = R.check_program()
     out = subprocess.run([exe], capture_output=True, text=True, check=True, timeout=120).stdout.splitlines()
     assert len(out) == 9 and all(line.startswith(f"case {i} ") for i, line in enumerate(out))
     fields = [dict(zip(line.split()[2::2], (int(v) for v in line.split()[3::2]))) for line in out]

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import acrobot_ref as R
-import mlp_sample_ref as S
+from glibc_f32 import glibc_has_fdlibm_expm1f
+from words import bits, same
 import modurl_gym_amd as mg
 from modurl_gym_amd import _lib as L
 
@@ -30,16 +31,7 @@ def form_env(form, limit, auto, monkeypatch):
         monkeypatch.setenv("MGYM_CLASSIC_MAX_BLOCKS", max_blocks)   # read when the handle is created
     return make(n, limit, auto), n, offset, with_obs
 MODES = [(LIMIT, True), (0, False), (LIMIT, False), (0, True)]   # (max_episode_steps, auto_reset)
-needs_fdlibm = pytest.mark.skipif(not S.glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")
-
-
-def words(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(got, exp):
-    return np.array_equal(words(got), words(exp))
+needs_fdlibm = pytest.mark.skipif(not glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")
 
 
 def table_actions(n, steps=STEPS):
@@ -55,7 +47,7 @@ def near_swing_up(n):
     w1, w2 = sign * rng.uniform(0.3, 2.5, n), rng.uniform(-1.0, 1.0, n)
     rest = np.arange(n) % 5 == 0
     th1[rest], w1[rest] = 0.05, 0.0
-    return np.stack([words(v.astype(F)) for v in (th1, th2, w1, w2)] + [np.arange(n, dtype=np.uint32) * 3])
+    return np.stack([bits(v.astype(F)) for v in (th1, th2, w1, w2)] + [np.arange(n, dtype=np.uint32) * 3])
 
 
 def make(n, limit, auto, **kw):
@@ -250,7 +242,7 @@ def test_state_and_elapsed_round_trip():
     env.reset()
     env.step(np.ones(n, np.uint32))
     big = np.array([1e6, -12345.678, 3.1415927, -3.1415927, -0.0, 119.9, 125.0], F)
-    blob = np.stack([words(np.resize(big, n)), words(np.resize(big[::-1], n)), words(((np.arange(n) % 17) - 8).astype(F)), words(((np.arange(n) % 41) - 20).astype(F)),
+    blob = np.stack([bits(np.resize(big, n)), bits(np.resize(big[::-1], n)), bits(((np.arange(n) % 17) - 8).astype(F)), bits(((np.arange(n) % 41) - 20).astype(F)),
                      np.arange(n, dtype=np.uint32)])
     env.set_state(blob.view(F))
     th1, th2 = blob[0].view(F), blob[1].view(F)
@@ -371,7 +363,7 @@ def test_final_observations_equal_a_twin_without_auto_reset(src, limit, monkeypa
     tobs, tfin = twin_finals(n, limit, list(used))
     mask = np.broadcast_to(tfin[:, None, :], got.shape)
     assert tfin[:2].sum() >= 8 and (limit == 0 or tfin[6:].sum() >= 8), "the case has endings of both kinds"
-    assert np.array_equal(got[mask], words(tobs)[mask]), f"{src}: final words differ from the twin's"
+    assert np.array_equal(got[mask], bits(tobs)[mask]), f"{src}: final words differ from the twin's"
     assert np.all(got[~mask] == FILL), f"{src}: words outside the finished env-steps were written"
 
 

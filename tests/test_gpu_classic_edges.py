@@ -16,7 +16,9 @@ import acrobot_ref as AR
 import classic_edge_cases as E
 import modurl_gym_amd as mg
 import pendulum_ref as PR
+from mlp_ref import argmax_words
 from oracle import oracle as ora
+from words import same_words
 
 pytestmark = pytest.mark.gpu
 
@@ -125,11 +127,6 @@ class Ref:
     @property
     def finished(self):
         return self.r.finished
-
-
-def same_words(got, exp):
-    g, e = np.ascontiguousarray(got, F), np.ascontiguousarray(exp, F)
-    return bool(np.all((g.view(np.uint32) == e.view(np.uint32)) | (np.isnan(g) & np.isnan(e))))
 
 
 def same_state(fam, got, exp):
@@ -302,7 +299,7 @@ def constant_policies(fam):
         for act in range(3):
             pol = np.zeros((3, D + 1), F)
             pol[act, D] = 1.0
-            ref = (lambda obs, pol=pol: AR.argmax_words(np.stack([zero_sum(obs) + pol[j, D] for j in range(3)])))
+            ref = (lambda obs, pol=pol: argmax_words(np.stack([zero_sum(obs) + pol[j, D] for j in range(3)])))
             out.append((f"a{act}", pol.ravel(), ref))
     else:
         top = 1.0 if fam.kind == mg.MOUNTAINCAR_CONT else 2.0

@@ -8,7 +8,8 @@ import pytest
 
 import modurl_gym_amd as mg
 from oracle import oracle as ora
-from time_limit_ref import TimeLimitRef, same
+from time_limit_ref import TimeLimitRef
+from words import same
 
 pytestmark = pytest.mark.gpu
 

@@ -19,7 +19,7 @@ import pytest
 
 import modurl_gym_amd as mg
 from modurl_gym_amd import _lib
-from time_limit_ref import bits, same
+from words import bits, same
 
 pytestmark = pytest.mark.gpu
 

@@ -20,7 +20,7 @@ COUNTS = (1, 65, gc.N_RANDOM)
 def polys():
     out = ck.device_probe(ck.SHAPES)
     ck.check_shapes(out, "device")
-    assert ck.same_words(out, ck.oracle_probe(ck.SHAPES))
+    assert ck.same(out, ck.oracle_probe(ck.SHAPES))
     return ck.impl_polygons(out)
 
 
@@ -47,21 +47,21 @@ def test_shapes(polys):
 def test_distance(count):
     out = ck.run_set(ck.device_probe, "distance", ck.DISTANCE, count)
     ck.check_distance(_prefix(gc.reference("distance"), count), out, f"device distance[:{count}]")
-    assert ck.same_words(out, ck.run_set(ck.oracle_probe, "distance", ck.DISTANCE, count))
+    assert ck.same(out, ck.run_set(ck.oracle_probe, "distance", ck.DISTANCE, count))
 
 
 @pytest.mark.parametrize("count", COUNTS)
 def test_manifold(polys, count):
     out = ck.run_set(ck.device_probe, "manifold", ck.MANIFOLD, count)
     ck.check_manifold(_prefix(gc.reference("manifold"), count), out, polys, f"device manifold[:{count}]")
-    assert ck.same_words(out, ck.run_set(ck.oracle_probe, "manifold", ck.MANIFOLD, count))
+    assert ck.same(out, ck.run_set(ck.oracle_probe, "manifold", ck.MANIFOLD, count))
 
 
 @pytest.mark.parametrize("count", COUNTS)
 def test_time_of_impact(count):
     out = ck.run_set(ck.device_probe, "toi", ck.TOI, count)
     ck.check_toi(_prefix(gc.reference("toi"), count), out, f"device toi[:{count}]")
-    assert ck.same_words(out, ck.run_set(ck.oracle_probe, "toi", ck.TOI, count))
+    assert ck.same(out, ck.run_set(ck.oracle_probe, "toi", ck.TOI, count))
 
 
 def test_hand_built_cases(polys):
@@ -72,9 +72,9 @@ def test_hand_built_cases(polys):
     ck.check_manifold(gc.reference("hand_static"), m, polys, "device hand_static", require_parallel=ck.HAND_PARALLEL)
     ck.check_toi(gc.reference("hand_sweeps"), t, "device hand_sweeps")
     # every case and column as bit patterns (no column needs comparing by value: not even the sign of a zero differs)
-    assert ck.same_words(d, ck.run_set(ck.oracle_probe, "hand_static", ck.DISTANCE))
-    assert ck.same_words(m, ck.run_set(ck.oracle_probe, "hand_static", ck.MANIFOLD))
-    assert ck.same_words(t, ck.run_set(ck.oracle_probe, "hand_sweeps", ck.TOI))
+    assert ck.same(d, ck.run_set(ck.oracle_probe, "hand_static", ck.DISTANCE))
+    assert ck.same(m, ck.run_set(ck.oracle_probe, "hand_static", ck.MANIFOLD))
+    assert ck.same(t, ck.run_set(ck.oracle_probe, "hand_sweeps", ck.TOI))
 
 
 def test_probe_rejects_bad_arguments():

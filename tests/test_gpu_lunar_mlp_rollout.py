@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
-from mlp_policy_ref import RELU, TANH, build_shared, header_actions
+from mlp_policy_ref import FAMILIES, RELU, TANH, header_actions, header_eval
+from mlp_ref import normal_weights, packed
+from words import same
 
 pytestmark = pytest.mark.gpu
 
@@ -16,7 +18,7 @@ ACT_NAME = {RELU: "relu", TANH: "tanh"}
 # (seed, global id), so they are the first 300 of a larger handle too)
 IN_SCALE = (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)
 SEEDS = {(1, RELU): 87, (1, TANH): 12, (7, RELU): 3, (7, TANH): 0, (64, RELU): 0, (64, TANH): 0}
-D, A = 8, 4
+D, A, _ = FAMILIES["lunar_lander"]
 ENV_SEED = 11
 MODES = {"persistent": {"MGYM_LL_ROLLOUT_MIN_K": "8", "MGYM_LL_ROLLOUT_MLP": "1"}, "default_mlp": {"MGYM_LL_ROLLOUT_MIN_K": "8"}, "disabled": {"MGYM_LL_ROLLOUT": "0"},
          "large": {"MGYM_LL_ROLLOUT_MLP": "1"}}
@@ -25,25 +27,7 @@ PERSISTENT_BY_DEFAULT = {RELU: False, TANH: False}
 
 
 def weights(H, act):
-    rng = np.random.default_rng(1000 + SEEDS[(H, act)])
-    w1 = (rng.normal(0, 1, (H, D)) * np.array(IN_SCALE)).astype(np.float32)
-    b1 = rng.normal(0, 0.5, H).astype(np.float32)
-    w2 = (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32)
-    b2 = rng.normal(0, 0.1, A).astype(np.float32)
-    return w1, b1, w2, b2
-
-
-def packed(w):
-    return np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]]).astype(np.float32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
+    return normal_weights(np.random.default_rng(1000 + SEEDS[(H, act)]), D, A, H, IN_SCALE)
 
 
 def make(monkeypatch, mode, n, auto_reset=True, limit=0, seed=ENV_SEED):
@@ -65,7 +49,7 @@ def launches(env):
 
 @pytest.fixture(scope="module")
 def header():
-    return build_shared()
+    return header_eval()
 
 
 class Loop:

@@ -6,6 +6,7 @@ import pytest
 
 import modurl_gym_amd as mg
 from oracle import oracle as ora
+from words import same
 
 pytestmark = pytest.mark.gpu
 
@@ -47,11 +48,6 @@ def uni_actions(seed, call, t, n, base=0):
         for k in range(min(4, n - g0)):
             a[g0 + k] = (int(w[k]) >> (2 * (t % 16))) & 3
     return a
-
-
-def same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32) if a.dtype == np.float32 else a,
-                          np.ascontiguousarray(b).view(np.uint32) if b.dtype == np.float32 else b)
 
 
 MODES = {"persistent": {"MGYM_LL_ROLLOUT_MIN_K": "8"}, "k_steps_small_k": {"MGYM_LL_ROLLOUT_MIN_K": "8"}, "k_steps_disabled": {"MGYM_LL_ROLLOUT": "0"}}

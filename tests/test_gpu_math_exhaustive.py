@@ -4,27 +4,20 @@ compiled for the host; this one sees what only the device build can get wrong (f
 selection by the device compiler).  Compare rule (tests/native/math_glibc_exhaustive.cpp): NaN meets NaN, everything else bit for bit."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import native_build
 from modurl_gym_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
 CHUNK = 1 << 26   # patterns per probe launch: 8 result rows of 256 MiB
 ROWS = ("sinf", "cosf", "sincosf.sin", "sincosf.cos", "sincosf_u.sin", "sincosf_u.cos", "cosf_u", "tanhf")
 # entry point -> first result row (the sincos forms fill two: sin, then cos)
 PROBES = ((_lib.MATH_SINF, 0), (_lib.MATH_COSF, 1), (_lib.MATH_SINCOSF, 2), (_lib.MATH_SINCOSF_U, 4), (_lib.MATH_COSF_U, 6), (_lib.MATH_TANHF, 7))
 CLASSES = ("|x|<=16", "16<|x|<120", "|x|>=120", "inf/nan")
-
-
-def _host_has_fma():
-    with open("/proc/cpuinfo") as f:
-        return any(line.startswith("flags") and " fma " in f" {line.split(':', 1)[1].strip()} " for line in f)
 
 
 def _threads():
@@ -33,13 +26,9 @@ def _threads():
 
 @pytest.fixture(scope="module")
 def glibc_helper():
-    if not _host_has_fma():
+    if not native_build.host_has_fma():
         pytest.skip("host CPU has no FMA: glibc runs its non-FMA sinf/cosf build, which mgym_math.h does not restate")
-    os.makedirs(BUILD, exist_ok=True)
-    so = os.path.join(BUILD, "libmg_glibc.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-fopenmp", "-fPIC", "-shared",
-                    "-DMG_GLIBC_LIB", "-o", so, os.path.join(ROOT, "tests", "native", "math_glibc_exhaustive.cpp"), "-lm"], check=True)
-    h = C.CDLL(so)
+    h = C.CDLL(native_build.shared("math_glibc_exhaustive.cpp", "mg_glibc", extra=("-mfma", "-fopenmp", "-DMG_GLIBC_LIB")))
     h.mg_glibc_compare.restype = C.c_uint64
     h.mg_glibc_compare.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int,
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]

@@ -1,6 +1,6 @@
 """mgym_rollout_mlp_gauss (include/mgym.h): Gaussian-sampled continuous actions inside the MountainCarContinuous and Pendulum rollout kernels.  The reference
-for the actions is the numpy restatement of the documented draw (tests/mlp_gauss_ref.py: the restated fmaf chains for mu, the restated Box-Muller normal for
-z, a = mu + sigma * z) applied to the observation each env holds before the step; the reference for everything else is a second handle stepped with those
+for the actions is the numpy restatement of the documented draw (the fmaf chains of tests/mlp_ref.py for mu, the Box-Muller normal of tests/mlp_gauss_ref.py
+for z, a = mu + sigma * z) applied to the observation each env holds before the step; the reference for everything else is a second handle stepped with those
 actions.  Whole words, no tolerance.  The distribution is not tested here: it follows from word equality with the specification, whose distribution
 tests/test_mlp_gauss_host.py checks."""
 import numpy as np
@@ -8,14 +8,17 @@ import pytest
 
 import modurl_gym_amd as mg
 import mlp_gauss_ref as R
+import mlp_ref as M
+from mlp_ref import RELU, TANH, packed
+from words import bits, same
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 KINDS = {"mountain_car_continuous": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM}
-DIMS = {"mountain_car_continuous": 2, "pendulum": 3}
+DIMS = {fam: M.FAMILIES[fam][0] for fam in KINDS}
 IN_SCALE = {"mountain_car_continuous": (2.0, 40.0), "pendulum": (1.0, 1.0, 0.3)}
-ACT_NAME = {R.RELU: "relu", R.TANH: "tanh"}
+ACT_NAME = {RELU: "relu", TANH: "tanh"}
 N, K, HALF = 2056, 7, 1028            # 514 lanes: two full blocks of the rollout kernel and a two-lane tail
 BASE = (1 << 32) - HALF               # the ids straddle 2^32
 POLICY_SEED, CALL, SIGMA = 0xC0FFEE1234, 5, 0.6
@@ -23,26 +26,8 @@ ENV_SEED, LIMIT = 11, 3               # resets fall inside the call (steps 2 and
 
 
 def weights(fam, H, act):
-    D = DIMS[fam]
     rng = np.random.default_rng(3000 + 10 * H + act + (100 if fam == "pendulum" else 0))
-    w1 = (rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[fam])).astype(F)
-    b1 = rng.normal(0, 0.5, H).astype(F)
-    w2 = (rng.normal(0, 1, (1, H)) / np.sqrt(H)).astype(F)
-    b2 = rng.normal(0, 0.3, 1).astype(F)
-    return w1, b1, w2, b2
-
-
-def packed(w):
-    return np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]]).astype(F)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
+    return M.normal_weights(rng, DIMS[fam], 1, H, IN_SCALE[fam], b2_scale=0.3)
 
 
 def make(fam, n=N, base=BASE, limit=LIMIT, auto_reset=True):
@@ -50,7 +35,7 @@ def make(fam, n=N, base=BASE, limit=LIMIT, auto_reset=True):
 
 
 @pytest.mark.parametrize("H", [1, 5, 64])
-@pytest.mark.parametrize("act", [R.RELU, R.TANH], ids=["relu", "tanh"])
+@pytest.mark.parametrize("act", [RELU, TANH], ids=["relu", "tanh"])
 @pytest.mark.parametrize("fam", ["mountain_car_continuous", "pendulum"])
 def test_rollout_equals_the_restated_draw_and_a_stepping_loop(fam, act, H):
     D, w = DIMS[fam], weights(fam, H, act)
@@ -64,7 +49,7 @@ def test_rollout_equals_the_restated_draw_and_a_stepping_loop(fam, act, H):
     assert acts.dtype == np.float32 and acts.shape == (K, N)
     moved = 0
     for t in range(K):
-        mu = R.mlp_mu(pol, D, H, act, obs)                 # the observation held before step t: the handle's, then obs_out[t - 1]
+        mu = M.scores(pol, D, 1, H, obs, act)[0]                 # the observation held before step t: the handle's, then obs_out[t - 1]
         a = R.gauss_actions(mu, SIGMA, POLICY_SEED, CALL, g, t)
         bad = np.nonzero(bits(acts[t]) != bits(a))[0]
         assert bad.size == 0, f"step {t}: {bad.size} actions differ; env {bad[0]}: device {acts[t][bad[0]]!r}, restatement {a[bad[0]]!r}, mu {mu[bad[0]]!r}"
@@ -120,7 +105,7 @@ def test_torch_rollout_mlp_gauss_equals_vecenv():
     ve = mg.VecEnv(KINDS[fam], N, seed=31, auto_reset=True, env_id_base=BASE, max_episode_steps=LIMIT)
     te.reset()
     ve.reset()
-    w = weights(fam, 5, R.TANH)
+    w = weights(fam, 5, TANH)
     got = te.rollout_mlp_gauss(*(torch.from_numpy(x) for x in w), K, SIGMA, POLICY_SEED, call=CALL, activation="tanh")
     torch.cuda.synchronize()
     exp = ve.rollout_mlp_gauss(*w, K, SIGMA, POLICY_SEED, CALL, activation="tanh")
@@ -146,7 +131,7 @@ def test_bad_arguments_are_reported_before_any_launch():
         env.close()
 
     for fam in KINDS:
-        pol = packed(weights(fam, 5, R.RELU))
+        pol = packed(weights(fam, 5, RELU))
         env = make(fam, 8, 0)
         env.reset()
         before = env.get_state()

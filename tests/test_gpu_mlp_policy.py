@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
-from mlp_policy_ref import FAMILIES, RELU, TANH, build_shared, header_actions
+from mlp_policy_ref import FAMILIES, RELU, TANH, header_actions, header_eval
+from mlp_ref import normal_weights, packed
+from words import bits, same
 
 pytestmark = pytest.mark.gpu
 
@@ -33,25 +35,7 @@ ENV_SEED = 11
 def weights(fam, H, act, seed=None):
     """nn.Linear-layout float32 weights (w1 [H, D], b1 [H], w2 [A, H], b2 [A]) from the family's seed"""
     D, A, _ = FAMILIES[fam]
-    rng = np.random.default_rng(1000 + (SEEDS[(fam, H, act)] if seed is None else seed))
-    w1 = (rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[fam])).astype(np.float32)
-    b1 = rng.normal(0, 0.5, H).astype(np.float32)
-    w2 = (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32)
-    b2 = rng.normal(0, 0.1, A).astype(np.float32)
-    return w1, b1, w2, b2
-
-
-def packed(w):
-    return np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]]).astype(np.float32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
+    return normal_weights(np.random.default_rng(1000 + (SEEDS[(fam, H, act)] if seed is None else seed)), D, A, H, IN_SCALE[fam])
 
 
 def make(fam, n, auto_reset, limit=0, seed=ENV_SEED):
@@ -61,7 +45,7 @@ def make(fam, n, auto_reset, limit=0, seed=ENV_SEED):
 
 @pytest.fixture(scope="module")
 def header():
-    return build_shared()
+    return header_eval()
 
 
 class Facts:

@@ -7,9 +7,12 @@ import pytest
 
 import modurl_gym_amd as mg
 import mlp_sample_ref as R
-from mlp_policy_ref import FAMILIES, RELU, TANH, build_shared, n_floats
+from glibc_f32 import glibc_has_fdlibm_expm1f
+from mlp_policy_ref import FAMILIES, RELU, TANH, header_eval, n_floats
+from mlp_ref import normal_weights, packed
+from words import same
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not R.glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")]
 
 KINDS = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_continuous": mg.MOUNTAINCAR_CONT, "lunar_lander": mg.LUNARLANDER}
 ACT_NAME = {RELU: "relu", TANH: "tanh"}
@@ -28,25 +31,7 @@ ENV_SEED = 11
 def weights(fam, H, act):
     """nn.Linear-layout float32 weights (w1 [H, D], b1 [H], w2 [A, H], b2 [A]) from the family's seed"""
     D, A, _ = FAMILIES[fam]
-    rng = np.random.default_rng(2000 + SEEDS[(fam, H, act)])
-    w1 = (rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[fam])).astype(np.float32)
-    b1 = rng.normal(0, 0.5, H).astype(np.float32)
-    w2 = (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32)
-    b2 = rng.normal(0, 0.3, A).astype(np.float32)
-    return w1, b1, w2, b2
-
-
-def packed(w):
-    return np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]]).astype(np.float32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
+    return normal_weights(np.random.default_rng(2000 + SEEDS[(fam, H, act)]), D, A, H, IN_SCALE[fam], b2_scale=0.3)
 
 
 def make(fam, n, auto_reset, limit=0, seed=ENV_SEED, base=0):
@@ -56,7 +41,7 @@ def make(fam, n, auto_reset, limit=0, seed=ENV_SEED, base=0):
 
 @pytest.fixture(scope="module")
 def header():
-    return build_shared()
+    return header_eval()
 
 
 def header_scores(fn, D, A, act, H, policy, obs):

@@ -1,5 +1,5 @@
 """MGYM_ACT_TANH_FAST through mgym_rollout_mlp, mgym_rollout_mlp_sample and mgym_rollout_mlp_gauss on every family that has them.  The reference for the
-actions is the restatement of include/mgym.h (tests/tanh_fast_ref.py as the hidden activation inside the restated fmaf chains, then the argmax, the
+actions is the restatement of include/mgym.h (tests/tanh_fast_ref.py as the hidden activation inside the fmaf chains of tests/mlp_ref.py, then the argmax, the
 categorical draw of tests/mlp_sample_ref.py or the Gaussian draw of tests/mlp_gauss_ref.py) evaluated on the observation each environment holds before the
 step; the reference for everything else is a second handle stepped with the actions the call wrote.  Whole words, no tolerance.
 
@@ -9,7 +9,11 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+import mlp_ref as M
 import tanh_fast_ref as T
+from glibc_f32 import tanhf
+from mlp_ref import packed
+from words import bits, same
 
 pytestmark = pytest.mark.gpu
 
@@ -23,31 +27,14 @@ IN_SCALE = {"cartpole": (1.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "moun
             "acrobot": (1.0, 1.0, 1.0, 1.0, 0.3, 0.2), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
 FORM_NAME = {T.ARGMAX: "mlp", T.SAMPLE: "mlp_sample", T.GAUSS: "mlp_gauss"}
 CLASSIC = [f for f in KINDS if f != "lunar_lander"]
-ROLLOUT_CASES = [(fam, form, H, n) for fam in CLASSIC for form in ((T.ARGMAX, T.GAUSS) if T.FAMILIES[fam][1] == 1 else (T.ARGMAX, T.SAMPLE))
+ROLLOUT_CASES = [(fam, form, H, n) for fam in CLASSIC for form in ((T.ARGMAX, T.GAUSS) if M.FAMILIES[fam][1] == 1 else (T.ARGMAX, T.SAMPLE))
                  for H, n in ((1, 260), (5, 260), (64, 260), (5, 4))]
 
 
 def weights(fam, H, form):
-    D, A = T.FAMILIES[fam]
+    D, A, _ = M.FAMILIES[fam]
     rng = np.random.default_rng(7000 + 100 * list(KINDS).index(fam) + 10 * form + H)
-    w1 = (rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[fam])).astype(F)
-    b1 = rng.normal(0, 0.5, H).astype(F)
-    w2 = (rng.normal(0, 2, (A, H)) / np.sqrt(H)).astype(F)
-    b2 = rng.normal(0, 0.1, A).astype(F)
-    return w1, b1, w2, b2
-
-
-def packed(w):
-    return np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]]).astype(F)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
+    return M.normal_weights(rng, D, A, H, IN_SCALE[fam], w2_scale=2.0)
 
 
 def make(fam, n, auto_reset=True, base=BASE, **kw):
@@ -80,7 +67,7 @@ def call(env, form, w, activation="tanh_fast", K=K):
 def check_against_restatement_and_steps(fam, form, H, got, obs, stepper, twin=None):
     """every action word against the restatement on the observation held before the step; obs, reward and flags against mgym_step fed actions_out.
     -> the final observations [(t, finished mask, twin obs)] when a handle without auto-reset is given"""
-    D, A = T.FAMILIES[fam]
+    D, A, _ = M.FAMILIES[fam]
     pol = packed(weights(fam, H, form))
     acts, gobs, grew, gdone, gtrunc = got
     n = acts.shape[1]
@@ -110,7 +97,7 @@ def test_rollout_equals_the_restatement_and_a_stepping_loop(fam, form, H, n):
     obs = env.observation()
     assert same(obs, stepper.observation())
     got = call(env, form, w)
-    assert got[0].shape == (K, n) and got[1].shape == (K, T.FAMILIES[fam][0], n)
+    assert got[0].shape == (K, n) and got[1].shape == (K, M.FAMILIES[fam][0], n)
     check_against_restatement_and_steps(fam, form, H, got, obs, stepper)
     fin = got[3].astype(bool) | got[4].astype(bool)
     assert fin.any() and not fin.all(), "endings (and their fused resets) fall inside the call, and not everywhere"
@@ -126,8 +113,8 @@ FILL = 0x7FC0DEAD   # a NaN word no step produces
 @pytest.mark.parametrize("fam", CLASSIC)
 def test_final_observation_channel(fam):
     """one case per family with mgym_set_final_obs_out set: everything else as with the channel unset, the finals those of a handle without auto-reset"""
-    form = T.GAUSS if T.FAMILIES[fam][1] == 1 else T.SAMPLE
-    H, n, D = 5, 260, T.FAMILIES[fam][0]
+    form = T.GAUSS if M.FAMILIES[fam][1] == 1 else T.SAMPLE
+    H, n, D = 5, 260, M.FAMILIES[fam][0]
     w = weights(fam, H, form)
     env, stepper, twin = make(fam, n), make(fam, n), make(fam, n, auto_reset=False)
     prepare(env, fam), prepare(stepper, fam), twin.reset()
@@ -222,8 +209,7 @@ def test_discrete_action_turns_on_the_last_bit_of_the_activation(fam, form):
     restatement gives s_0 = 0 and action 0 at e (a tie; for the draw u_e < 1/2), and with tanhf in its place s_0 <= -8 and action 1.  The device must give 0:
     a launch that ran the exact-tanh instantiation of the source would not."""
     import mlp_sample_ref as S
-    import pendulum_ref as P
-    D, A = T.FAMILIES[fam]
+    D, A, _ = M.FAMILIES[fam]
     n = 260
     env = make(fam, n, enable_wind=True) if fam == "lunar_lander" else make(fam, n)
     env.reset()
@@ -237,7 +223,7 @@ def test_discrete_action_turns_on_the_last_bit_of_the_activation(fam, form):
         pre = np.full(n, b1[0], F)
         for q in range(D):
             pre = T.fmaf(w1[0, q], obs[q], pre)
-        h_fast, h_exact = T.tanh_fast(pre), P.tanhf(pre)
+        h_fast, h_exact = T.tanh_fast(pre), tanhf(pre)
         cand = np.flatnonzero((h_exact < h_fast) & (h_fast >= 0.5) & (h_fast < 0.99) & (u > 0.05) & (u < 0.5))
         if cand.size:
             break
@@ -249,7 +235,7 @@ def test_discrete_action_turns_on_the_last_bit_of_the_activation(fam, form):
     w = (w1, b1, w2, b2)
     pol = packed(w)
     fast, s_fast = T.policy_actions(form, pol, D, A, 1, obs, 0.0, POLICY_SEED, CALL, g, 0)
-    exact, s_exact = T.policy_actions(form, pol, D, A, 1, obs, 0.0, POLICY_SEED, CALL, g, 0, activation=P.tanhf)
+    exact, s_exact = T.policy_actions(form, pol, D, A, 1, obs, 0.0, POLICY_SEED, CALL, g, 0, activation=tanhf)
     assert s_fast[0][e] == 0.0 and s_exact[0][e] <= -8.0 and fast[e] == 0 and exact[e] == 1   # the policy separates the activations at e
     got = call(env, form, w, K=1)
     assert int(got[0][0][e]) == 0, "the action of the exact tanh at the pivot environment"

@@ -6,6 +6,7 @@ import pytest
 
 import modurl_gym_amd as mg
 import pendulum_ref as R
+from words import bits, same
 from modurl_gym_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
@@ -17,15 +18,6 @@ SEED = 0x51A7E5
 # misaligned or obs_out cannot be written 16 bytes at a time, and four per lane with a ragged last group when n % 4 != 0 and obs_out is NULL.
 FORMS = {"single_pass": (2052, None, 0, True), "grid_stride": (2052, "1", 0, True), "generic_1027": (1027, None, 0, True),
          "generic_offset_reward": (2052, None, 4, True), "generic_ragged_no_obs_out": (1027, None, 0, False)}
-
-
-def words(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(got, exp):
-    return np.array_equal(words(got), words(exp))
 
 
 def step_actions(n):
@@ -173,7 +165,7 @@ def test_policy_rollouts(policy):
             exp = ref.rollout_mlp(np.concatenate([x.ravel() for x in w]), H, R.TANH if act == "tanh" else R.RELU, K)
         for g, e, name in zip(got, exp, ("actions", "obs", "reward", "done", "truncated")):
             assert same(g, e), f"{policy} call {rnd}: {name}"
-        acts = words(got[0]).view(F)
+        acts = bits(got[0]).view(F)
         assert len(np.unique(acts)) > n // 4 and (policy != "uniform" or (acts.min() >= -2 and acts.max() < 2))
         fed = table.rollout(acts)   # the same K steps from an action table
         assert all(same(g, f) for g, f in zip(got[1:], fed)), f"{policy}: differs from mgym_rollout fed its actions"
@@ -188,7 +180,7 @@ def test_set_state_recomputes_cos_and_sin():
     n = 1027
     th = np.array([R.BIG_TH[i % len(R.BIG_TH)] for i in range(n)], F)
     thdot = ((np.arange(n) % 17) - 8).astype(F)
-    blob = np.stack([words(th), words(thdot), np.arange(n, dtype=np.uint32)])
+    blob = np.stack([bits(th), bits(thdot), np.arange(n, dtype=np.uint32)])
     env = mg.VecEnv(mg.PENDULUM, n, seed=1, max_episode_steps=LIMIT)
     env.reset()
     env.step(np.zeros(n, F))

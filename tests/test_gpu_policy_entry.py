@@ -7,6 +7,7 @@ import pytest
 
 import modurl_gym_amd as mg
 from modurl_gym_amd.envs import DeviceArray
+from words import same
 
 pytestmark = pytest.mark.gpu
 
@@ -14,10 +15,6 @@ L = mg.envs.L
 CLASSIC = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_cont": mg.MOUNTAINCAR_CONT}
 N, K = 8, 4
 SEEDS = (11, 12)
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a, b.view(np.uint32) if b.dtype == np.float32 else b)
 
 
 def linear_policy(env):

@@ -6,9 +6,11 @@ import pytest
 
 import modurl_gym_amd as mg
 import mlp_sample_ref as R
+from glibc_f32 import glibc_has_fdlibm_expm1f
+from words import same_words
 from modurl_gym_amd import _lib
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not R.glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")]
 
 
 def probe(scores, words, want_cum=True):
@@ -25,7 +27,7 @@ def check(A, s, w):
     ract, rcum = R.draw(s, w)
     bad = np.nonzero(act != ract)[0]
     assert bad.size == 0, f"{bad.size} actions differ; case {bad[0]}: scores {s[:, bad[0]]}, word {w[bad[0]]:#x}: device {act[bad[0]]}, restatement {ract[bad[0]]}"
-    assert R.same_words(cum, rcum)
+    assert same_words(cum, rcum)
     return act
 
 

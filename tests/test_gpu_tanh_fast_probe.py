@@ -7,14 +7,15 @@ Patterns: every one from 0 to just past the clamp, [0, 0x41200100), in chunks as
 ranges are probed and compared whole, which contains the sampled sets; so is the negative side below the clamp.  All 2^32 patterns take
 about a second and a half on an MI355X."""
 import ctypes as C
-import os
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
+import native_build
 import tanh_fast_ref as T
+from glibc_f32 import tanhf
+from words import same_words
 from modurl_gym_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -24,23 +25,10 @@ RANGES = {"below_clamp": (0x00000000, T.CLAMP_END), "above_clamp": (T.CLAMP_END,
           "negative_below_clamp": (0x80000000, 0x80000000 + T.CLAMP_END)}
 
 
-def _host_has_fma():
-    with open("/proc/cpuinfo") as f:
-        return any(line.startswith("flags") and " fma " in f" {line.split(':', 1)[1].strip()} " for line in f)
-
-
 @pytest.fixture(scope="module")
 def host():
     """the host build of the header; with the CPU's own FMA instruction where it has one (one correctly rounded operation, as glibc's fmaf is, and inline)"""
-    if not _host_has_fma():
-        return T.build_shared()
-    so = os.path.join(T.BUILD, "libtanh_fast_check_fma.so")
-    os.makedirs(T.BUILD, exist_ok=True)
-    subprocess.run(["g++", *T.FLAGS, "-mfma", "-fopenmp", "-shared", "-fPIC", "-o", so, T.SRC, "-lm"], check=True)
-    lib = C.CDLL(so)
-    lib.tanh_fast_compare.restype, lib.tanh_fast_compare.argtypes = C.c_uint64, [C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.tanh_fast_bulk.restype, lib.tanh_fast_bulk.argtypes = None, [C.c_uint64, C.c_void_p, C.c_void_p]
-    return lib
+    return T.check_lib(fma=native_build.host_has_fma())
 
 
 @pytest.fixture(scope="module")
@@ -75,11 +63,11 @@ def test_device_words_equal_the_host_build(host, device_buffer, name):
 def test_the_fma_build_of_the_host_header_is_the_glibc_fmaf_build(host):
     """the comparison above may run the host header with the CPU's FMA instruction: the same words as the build that calls glibc's fmaf"""
     idx = np.arange(1 << 18, dtype=np.uint64)
-    from mlp_sample_ref import philox4x32_10
+    from philox_ref import philox4x32_10
     w = np.ascontiguousarray(np.concatenate(philox4x32_10(idx, 1, 2, 3, 0x1234, 0x5678)), np.uint32)
     out = np.empty_like(w)
     host.tanh_fast_bulk(w.size, w.ctypes.data, out.ctypes.data)
-    assert T.same_words(out, T.header_tanh_fast(w))
+    assert same_words(out, T.header_tanh_fast(w))
 
 
 def test_argument_checks_and_the_other_activations(device_buffer):
@@ -93,7 +81,6 @@ def test_argument_checks_and_the_other_activations(device_buffer):
     assert lib.mgym_act_probe(0, _lib.ACT_TANH_FAST, 1, 1 << 32, dev) == _lib.ERR_BAD_ARG
     assert lib.mgym_act_probe(0, _lib.ACT_TANH_FAST, 0xFFFFFFF0, 17, dev) == _lib.ERR_BAD_ARG
     # RELU and TANH are accepted, and their words are mlp_activate's: pre > 0 ? pre : +0, and glibc's tanhf (which mg_tanhf equals: test_gpu_math_exhaustive.py)
-    import pendulum_ref as P
     n = 1 << 16
     for first in (0x3F000000, 0xBF000000, 0x00000000, 0x7F7FFF00, 0xFFFF0000):
         n_span = min(n, (1 << 32) - first)
@@ -106,4 +93,4 @@ def test_argument_checks_and_the_other_activations(device_buffer):
         assert np.array_equal(got, relu.view(np.uint32)), hex(first)
         assert lib.mgym_act_probe(0, _lib.ACT_TANH, first, n_span, dev) == _lib.OK, lib.mgym_last_error()
         assert lib.mgym_memcpy_d2h(0, got.ctypes.data, dev, n_span * 4) == _lib.OK
-        assert P.same_words(got.view(np.float32), P.tanhf(x)), hex(first)
+        assert same_words(got.view(np.float32), tanhf(x)), hex(first)

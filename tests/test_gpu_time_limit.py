@@ -3,18 +3,18 @@ LunarLander, through every entry point that steps: mgym_step, mgym_rollout, mgym
 captured graphs.  The checker is the unchanged CPU oracle inside the Python TimeLimit wrapper of tests/time_limit_ref.py (after every
 oracle step elapsed += 1, truncated = elapsed >= limit, `done` untouched; with auto-reset the envs with either flag are reset and their
 reset observation replaces the step's).  Every comparison is bit for bit."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+import native_build
 from oracle import oracle as ora
-from time_limit_ref import TimeLimitRef, same
+from time_limit_ref import TimeLimitRef
+from words import same
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("obs", "reward", "done", "truncated")
 
 # ---- MountainCar / MountainCarContinuous ------------------------------------------------------------------------------------------
@@ -595,12 +595,7 @@ def test_single_env_classes_and_the_cpp_mirror_step_to_truncation():
     ll.reset()
     assert [ll.step(np.uint32(0)).truncated for _ in range(4)] == [False, False, True, True]   # no auto-reset: it stays up
     ll.close()
-    out = os.path.join(ROOT, "tests", "native", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, "time_limit_mirror_test")
-    lib = os.path.join(ROOT, "modurl_gym_amd")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "native", "time_limit_mirror_test.cpp"),
-                    f"-L{lib}", "-lmgym", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"], check=True)
+    exe = native_build.program("time_limit_mirror_test.cpp", base=(), extra=("-O1", "-std=c++17"), link=native_build.MGYM_LINK)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "time limit mirror ok" in r.stdout

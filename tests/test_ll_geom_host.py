@@ -86,8 +86,8 @@ def test_oracle_and_host_build_agree_word_for_word(name, fn):
     """every case and column as bit patterns (no column needs comparing by value: not even the sign of a zero differs)"""
     a, b = ck.run_set(ck.oracle_probe, name, fn), ck.run_set(ck.host_probe, name, fn)
     diff = np.nonzero(ck.words(a) != ck.words(b))
-    assert ck.same_words(a, b), (name, fn, len(diff[0]), diff[0][:8], diff[1][:8])
-    assert ck.same_words(ck.oracle_probe(ck.SHAPES), ck.host_probe(ck.SHAPES))
+    assert ck.same(a, b), (name, fn, len(diff[0]), diff[0][:8], diff[1][:8])
+    assert ck.same(ck.oracle_probe(ck.SHAPES), ck.host_probe(ck.SHAPES))
 
 
 def test_probes_reject_bad_arguments():

@@ -9,26 +9,14 @@ import subprocess
 
 import pytest
 
+import native_build
 from oracle import oracle as ora
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-
-
-def _build(src, out, extra=()):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, out)
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe, os.path.join(ROOT, "tests", "native", src),
-           *extra, "-lm"]
-    subprocess.run(cmd, check=True)
-    return exe
 
 
 @pytest.fixture(scope="module")
 def ll_host():
     ora.build()
-    odir = os.path.join(ROOT, "oracle", "_build")
-    return _build("ll_host_check.cpp", "ll_host_check", [f"-L{odir}", "-loracle", f"-Wl,-rpath,{odir}"])
+    return native_build.program("ll_host_check.cpp", link=(*native_build.ORACLE_LINK, "-lm"))
 
 
 @pytest.mark.parametrize("n,steps,wind,det,toi_staged,physics", [(64, 300, 0, 1, 1, ()), (256, 400, 0, 0, 1, ()), (256, 400, 1, 0, 1, ()), (256, 300, 1, 0, 0, ()),
@@ -49,7 +37,7 @@ def test_kernel_source_matches_oracle_on_cpu(ll_host, n, steps, wind, det, toi_s
 
 
 def test_device_math_header_matches_glibc():
-    exe = _build("math_host_check.cpp", "math_host_check")
+    exe = native_build.program("math_host_check.cpp")
     out = subprocess.run([exe, "997"], capture_output=True, text=True, check=True).stdout
     rows = {l.split()[0]: dict(kv.split("=") for kv in l.split()[1:]) for l in out.strip().splitlines()}
     for fn in ("sinf", "cosf", "tanhf", "sincosf_self", "sincosf_uniform_vs_sincosf"):
@@ -57,23 +45,18 @@ def test_device_math_header_matches_glibc():
     assert int(rows["sinf"]["bad_large"]) == 0 and int(rows["cosf"]["bad_large"]) == 0
     # 16 < |x| < 120: reduce_fast fuses x - n*pi/2 as glibc's FMA build does (mgym_math.h), so no input may differ here either
     assert int(rows["sinf"]["bad_mid"]) + int(rows["cosf"]["bad_mid"]) <= 8, out
-    if _host_has_fma():
+    if native_build.host_has_fma():
         assert int(rows["sinf"]["bad_mid"]) == 0 and int(rows["cosf"]["bad_mid"]) == 0, out
     assert int(rows["tanhf"]["bad_mid"]) == 0 and int(rows["tanhf"]["bad_large"]) == 0
-
-
-def _host_has_fma():
-    with open("/proc/cpuinfo") as f:
-        return any(line.startswith("flags") and " fma " in f" {line.split(':', 1)[1].strip()} " for line in f)
 
 
 def test_device_math_header_matches_glibc_on_every_pattern():
     """All 2^32 f32 bit patterns, both signs, through every sin/cos entry point of mgym_math.h (mg_sinf, mg_cosf, mg_sincosf,
     mg_sincosf_u, mg_cosf_u) and mg_tanhf against the host's glibc: no mismatch in any range (NaN results compared as a class).
     Before reduce_fast fused its subtraction, 34 inputs with 16 < |x| < 120 differed by one ulp (12 sin, 22 cos)."""
-    if not _host_has_fma():
+    if not native_build.host_has_fma():
         pytest.skip("host CPU has no FMA: glibc runs its non-FMA sinf/cosf build, which mgym_math.h does not restate")
-    exe = _build("math_glibc_exhaustive.cpp", "math_glibc_exhaustive", ["-mfma", "-fopenmp"])
+    exe = native_build.program("math_glibc_exhaustive.cpp", extra=("-mfma", "-fopenmp"))
     threads = max(1, min(16, len(os.sched_getaffinity(0))))
     r = subprocess.run([exe, str(threads)], capture_output=True, text=True)
     rows = {l.split()[0]: dict(kv.split("=") for kv in l.split()[1:]) for l in r.stdout.strip().splitlines()}
@@ -89,12 +72,8 @@ def test_kernel_source_is_clean_under_asan_and_ubsan():
     """GPU AddressSanitizer is not available on the pool, and an out-of-bounds index in a kernel can take a GPU
     down: run the same kernel source on the host under ASan + UBSan (contact cache, constraint tables, worklists)."""
     ora.build()
-    odir = os.path.join(ROOT, "oracle", "_build")
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "ll_host_check_san")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(ROOT, "tests", "native", "ll_host_check.cpp"),
-                    f"-L{odir}", "-loracle", f"-Wl,-rpath,{odir}", "-lm"], check=True)
+    exe = native_build.program("ll_host_check.cpp", "ll_host_check_san", base=(), link=(*native_build.ORACLE_LINK, "-lm"),
+                               extra=("-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
     r = subprocess.run([exe, "128", "350", "1", "0"], capture_output=True, text=True, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

@@ -1,25 +1,18 @@
 """No-GPU check of the LunarLander policy header: modurl_gym_amd/csrc/ll_policy.h (what the persistent rollout launch and the K-step
 form's policy kernel evaluate) compiled for the host by tests/native/ll_policy_check.cpp, against numpy / oracle.philox restatements of the
 documented policies (include/mgym.h mgym_rollout_linear / mgym_rollout_uniform, LunarLander)."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import native_build
 from oracle import oracle as ora
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
 
 
 @pytest.fixture(scope="module")
 def check_exe():
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "ll_policy_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe,
-                    os.path.join(ROOT, "tests", "native", "ll_policy_check.cpp"), "-lm"], check=True)
-    return exe
+    return native_build.program("ll_policy_check.cpp")
 
 
 def run(exe, lines):

@@ -6,8 +6,10 @@ import numpy as np
 import pytest
 
 import mlp_gauss_ref as R
-from mlp_sample_ref import philox4x32_10
+import mlp_ref as M
 from oracle import oracle as ora
+from philox_ref import SLOT_POLICY_GAUSS, philox4x32_10
+from words import same_words
 
 F = np.float32
 
@@ -71,7 +73,7 @@ def test_gauss_philox_words_are_the_oracles():
 
 
 @pytest.mark.parametrize("D", [2, 3])
-@pytest.mark.parametrize("act", [R.RELU, R.TANH])
+@pytest.mark.parametrize("act", [M.RELU, M.TANH])
 def test_lane_form_equals_the_restatement(D, act):
     """the GAUSS form of mlp_actions (four environments per Philox block) against mu from the restated fmaf chains and a = mu + sigma * z; ids straddle 2^32"""
     rng = np.random.default_rng(40 + D + act)
@@ -83,16 +85,16 @@ def test_lane_form_equals_the_restatement(D, act):
         pol = np.concatenate([w1.ravel(), b1, w2.ravel(), b2]).astype(F)
         obs = rng.uniform(-2, 2, (D, n)).astype(F)
         obs[0, :4] = [np.nan, np.inf, -0.0, 0.0]
-        mu = R.mlp_mu(pol, D, H, act, obs)
+        mu = M.scores(pol, D, 1, H, obs, act)[0]
         for sigma in (0.0, 0.3, 2.5):
             got = R.header_actions(pol, D, H, act, sigma, obs, 0xC0FFEE1234, 9, g0, 3)
             exp = R.gauss_actions(mu, sigma, 0xC0FFEE1234, 9, g, 3)
-            assert R.same_words(got, exp), (H, sigma)
+            assert same_words(got, exp), (H, sigma)
             if sigma == 0.0:
                 assert np.array_equal(got[4:], mu[4:])          # a = mu as values
             else:
                 assert (got[4:] != mu[4:]).sum() > n - 16
-        assert np.isnan(got[0]) == (act == R.TANH)              # a NaN mu gives a NaN action (ReLU turns a NaN pre-activation into +0)
+        assert np.isnan(got[0]) == (act == M.TANH)              # a NaN mu gives a NaN action (ReLU turns a NaN pre-activation into +0)
 
 
 def test_the_specified_draw_is_standard_normal():
@@ -115,9 +117,9 @@ def test_ids_beyond_2_pow_32_use_the_high_counter_word():
     lo, hi = np.arange(8, dtype=np.uint64), np.uint64(1 << 32) + np.arange(8, dtype=np.uint64)
     zl, zh = R.normals(seed, call, lo, t), R.normals(seed, call, hi, t)
     assert not np.array_equal(zl, zh)
-    w = philox4x32_10(np.uint64(4), np.uint64(1), np.uint64(call), np.uint64(R.SLOT_GAUSS + t), seed, 0)
+    w = philox4x32_10(np.uint64(4), np.uint64(1), np.uint64(call), np.uint64(SLOT_POLICY_GAUSS + t), seed, 0)
     ze, zo, _ = R.gauss_pair(np.array([w[0][()], w[2][()]], np.uint32), np.array([w[1][()], w[3][()]], np.uint32))
-    assert R.same_words(zh[4:], np.array([ze[0], zo[0], ze[1], zo[1]], F))
+    assert same_words(zh[4:], np.array([ze[0], zo[0], ze[1], zo[1]], F))
     # a population straddling 2^32 draws what its two halves draw
     base = (1 << 32) - 4
     whole = R.dist_actions(n=8, K=3, base=base)

@@ -1,20 +1,23 @@
 """No-GPU check of the MLP policy header: modurl_gym_amd/csrc/mlp_policy.h (the lines the CartPole / MountainCar rollout kernels and LunarLander's
 policy kernel compile) built for the host by tests/native/mlp_policy_check.cpp with -ffp-contract=off, against the Python restatement of
-include/mgym.h's mgym_rollout_mlp text in tests/mlp_policy_ref.py (glibc fmaf / tanhf) — the action word and every score, bit for bit."""
+include/mgym.h's mgym_rollout_mlp text in tests/mlp_ref.py (glibc fmaf / tanhf) — the action word and every score, bit for bit."""
+import itertools
 import subprocess
 
 import numpy as np
 import pytest
 
-from mlp_policy_ref import FAMILIES, RELU, TANH, build_program, build_shared, header_actions, mlp_ref, n_floats, split
+import mlp_ref as M
+from mlp_policy_ref import RELU, TANH, check_program, header_actions, header_eval, mlp_refs, n_floats, split
 
+FAMILIES = {fam: M.FAMILIES[fam] for fam in ("cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander")}   # the families of mlp_policy_check.cpp
 HIDDEN = (1, 2, 7, 32, 64)
 KINDS = (("ordinary", 40), ("ties", 15), ("zeros", 15), ("huge", 15), ("inf", 15))
 
 
 @pytest.fixture(scope="module")
 def check_exe():
-    return build_program()
+    return check_program()
 
 
 def hexs(a):
@@ -80,9 +83,13 @@ def test_header_matches_the_restatement_of_the_documented_policy(check_exe):
     assert len(out) == len(cs)
     seen = {"tie": 0, "nan_first": 0, "nan_later": 0, "relu_pos": 0, "relu_nonpos": 0, "neg_zero_pre": 0, "nan_pre": 0, "inf_score": 0}
     actions = {fam: set() for fam in FAMILIES}
-    for line, (kind, D, A, cont, act, H, pol, o) in zip(out, cs):
+    refs = []   # the restatement, the cases of one shape at once
+    for shape, group in itertools.groupby(cs, key=lambda c: c[1:6]):
+        group = list(group)
+        a, s, pres = mlp_refs(*shape, [c[6] for c in group], [c[7] for c in group])
+        refs += [(int(a[i]), [float(v) for v in s[i]], [float(v) for v in pres[i]]) for i in range(len(group))]
+    for line, (kind, D, A, cont, act, H, pol, o), (action, s, pres) in zip(out, cs, refs):
         got = [int(v, 16) for v in line.split()]
-        action, s, pres = mlp_ref(D, A, cont, act, H, pol, o)
         exp = [action] + [int(np.float32(v).view(np.uint32)) for v in s]
         assert len(got) == len(exp)
         assert (same_word(got[0], exp[0]) if cont else got[0] == exp[0]) and all(same_word(g, e) for g, e in zip(got[1:], exp[1:])), \
@@ -118,7 +125,7 @@ def test_relu_of_negative_zero_and_nan_is_positive_zero(check_exe):
 
 def test_shared_object_form_equals_the_program(check_exe):
     """the bulk form test_gpu_mlp_policy.py uses is the same header: same actions as the program on one batch per family"""
-    fn = build_shared()
+    fn = header_eval()
     rng = np.random.default_rng(21)
     for D, A, cont in FAMILIES.values():
         H, n = 7, 33

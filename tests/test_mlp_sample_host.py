@@ -8,19 +8,22 @@ import subprocess
 import numpy as np
 import pytest
 
+import glibc_f32
 import mlp_sample_ref as R
+import philox_ref
 from oracle import oracle as ora
+from words import same_words
 
-needs_fdlibm = pytest.mark.skipif(not R.glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")
+needs_fdlibm = pytest.mark.skipif(not glibc_f32.glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")
 
 
 def test_vectorised_philox_equals_the_oracle():
     ora.build()
     rng = np.random.default_rng(5)
     ctr = rng.integers(0, 1 << 32, (64, 4), dtype=np.uint64)
-    ctr[:4] = [[0, 0, 0, 0], [0xFFFFFFFF] * 4, [4, 0, 3, R.SLOT_SAMPLE], [0xFFFFFFFC, 1, 0, R.SLOT_SAMPLE + 63]]
+    ctr[:4] = [[0, 0, 0, 0], [0xFFFFFFFF] * 4, [4, 0, 3, philox_ref.SLOT_POLICY_SAMPLE], [0xFFFFFFFC, 1, 0, philox_ref.SLOT_POLICY_SAMPLE + 63]]
     key = (0x34567811, 0x12)
-    got = np.stack(R.philox4x32_10(ctr[:, 0], ctr[:, 1], ctr[:, 2], ctr[:, 3], *key), axis=1)
+    got = np.stack(philox_ref.philox4x32_10(ctr[:, 0], ctr[:, 1], ctr[:, 2], ctr[:, 3], *key), axis=1)
     for row, c in zip(got, ctr):
         assert [int(v) for v in row] == ora.philox([int(v) for v in c], key)
     # words(): env g takes word g % 4 of the block of g & ~3, the key is the seed's two halves, the counter carries call and slot + t
@@ -33,7 +36,7 @@ def test_vectorised_philox_equals_the_oracle():
 @needs_fdlibm
 def test_bulk_expm1f_is_the_libm_call():
     x = np.concatenate([-np.exp2(np.random.default_rng(1).uniform(-150, 7, 4000)), [0.0, -0.0, -np.inf, np.nan, -104.0, -17.0]]).astype(np.float32)
-    assert R.same_words(R.expm1f(x), np.array([R.expm1f_scalar(v) for v in x], np.float32))
+    assert same_words(glibc_f32.expm1f(x), np.array([glibc_f32.expm1f_scalar(v) for v in x], np.float32))
 
 
 @needs_fdlibm
@@ -43,7 +46,7 @@ def test_header_equals_the_restatement_on_seeded_cases(A):
     assert s.shape == (A, 1 << 16) and np.abs(s).max() <= 20.0
     act, cum = R.header_draw(s, w)
     ract, rcum = R.draw(s, w)
-    assert np.array_equal(act, ract) and R.same_words(cum, rcum)
+    assert np.array_equal(act, ract) and same_words(cum, rcum)
     assert set(np.unique(act)) == set(range(A))
     assert (act != np.argmax(s, axis=0)).sum() > 1000   # a draw, not the argmax
     assert np.array_equal(R.header_draw(s, w, want_cum=False)[0], act)
@@ -57,15 +60,15 @@ def test_header_equals_the_restatement_on_hand_built_cases(A):
     ract, rcum = R.draw(s, w)
     bad = np.nonzero(act != ract)[0]
     assert bad.size == 0, f"case {bad[0]}: scores {s[:, bad[0]]}, word {w[bad[0]]:#x}: header {act[bad[0]]}, restatement {ract[bad[0]]}"
-    assert R.same_words(cum, rcum)
+    assert same_words(cum, rcum)
     # facts of the text, on the restatement: a NaN anywhere in c_{A-1} gives A - 1; equal scores give c_a = a + 1; a gap of 104 has weight 0, 17 has 2^-24
     nan_last = np.isnan(rcum[A - 1])
     assert nan_last.sum() > 50 and np.all(ract[nan_last] == A - 1)
     eq = np.all(s == s[0], axis=0) & np.isfinite(s[0])
     assert eq.sum() >= 5 * len(R.SPECIAL_WORDS) and all(np.all(rcum[a, eq] == a + 1) for a in range(A))
     assert np.all(ract[eq & (w == 0)] == 0) and np.all(ract[eq & (w == 0xFFFFFFFF)] == A - 1)
-    assert R.expm1f_scalar(-104.0) + np.float32(1) == 0.0 and R.expm1f_scalar(-17.0) + np.float32(1) == np.float32(2.0 ** -24)
-    assert R.expm1f_scalar(-16.5) + np.float32(1) == np.float32(2.0 ** -24) and R.expm1f_scalar(-18.0) + np.float32(1) == 0.0
+    assert glibc_f32.expm1f_scalar(-104.0) + np.float32(1) == 0.0 and glibc_f32.expm1f_scalar(-17.0) + np.float32(1) == np.float32(2.0 ** -24)
+    assert glibc_f32.expm1f_scalar(-16.5) + np.float32(1) == np.float32(2.0 ** -24) and glibc_f32.expm1f_scalar(-18.0) + np.float32(1) == 0.0
 
 
 @needs_fdlibm
@@ -77,18 +80,13 @@ def test_header_equals_the_restatement_on_the_gap_sweep(A):
     assert gap.min() > -112.0 and (gap == 0).any(axis=0).all() and ((gap < 0) & (gap > -1e-38)).sum() > 1000
     act, cum = R.header_draw(s, w)
     ract, rcum = R.draw(s, w)
-    assert np.array_equal(act, ract) and R.same_words(cum, rcum)
-
-
-def _host_has_fma():
-    with open("/proc/cpuinfo") as f:
-        return any(line.startswith("flags") and " fma " in f" {line.split(':', 1)[1].strip()} " for line in f)
+    assert np.array_equal(act, ract) and same_words(cum, rcum)
 
 
 @needs_fdlibm
 def test_expm1f_equals_glibc_on_every_negative_pattern():
     """mg_expm1f(x) and mg_expm1f(x) + 1.0f against glibc on all 2^31 patterns with the sign bit set (NaN results as a class): the draw is specified to the word"""
-    exe = R.build_program()
+    exe = R.check_program()
     threads = max(1, min(16, len(os.sched_getaffinity(0))))
     r = subprocess.run([exe, str(threads)], capture_output=True, text=True)
     rows = {l.split()[0]: dict(kv.split("=") for kv in l.split()[1:]) for l in r.stdout.strip().splitlines()}

@@ -4,18 +4,20 @@ activation — every score and every action word, for the argmax, the categorica
 import numpy as np
 import pytest
 
+import mlp_ref as M
 import tanh_fast_ref as T
+from words import same_words
 
 F = np.float32
 HIDDEN = (1, 7, 64)
 N = 64   # environments per case (a multiple of 4: the Gaussian form works on lanes of four)
-CASES = [(fam, form, H) for fam, (D, A) in T.FAMILIES.items() for form in ((T.ARGMAX, T.GAUSS) if A == 1 else (T.ARGMAX, T.SAMPLE)) for H in HIDDEN]
+CASES = [(fam, form, H) for fam, (D, A, _) in M.FAMILIES.items() for form in ((T.ARGMAX, T.GAUSS) if A == 1 else (T.ARGMAX, T.SAMPLE)) for H in HIDDEN]
 
 
 def make_case(rng, D, A, H):
     """weights that put pre-activations across the activation's whole range: the linear part near 0, the bend, the clamp; some +-0, huge and NaN inputs"""
     pol = rng.normal(0, 1.5, T.n_floats(D, A, H)).astype(F)
-    w1, b1, w2, b2 = T.split(pol, D, A, H)
+    w1, b1, w2, b2 = M.split(pol, D, A, H)
     w1 *= rng.choice(np.array([1e-3, 0.3, 1.0, 4.0, 30.0], F), (H, 1))
     obs = rng.normal(0, 1.0, (D, N)).astype(F)
     obs[:, 0] = 0.0
@@ -30,7 +32,7 @@ def make_case(rng, D, A, H):
 
 @pytest.mark.parametrize("fam,form,H", CASES, ids=[f"{fam}-{('argmax', 'sample', 'gauss')[form]}-H{H}" for fam, form, H in CASES])
 def test_header_matches_the_restated_chains(fam, form, H):
-    D, A = T.FAMILIES[fam]
+    D, A, _ = M.FAMILIES[fam]
     rng = np.random.default_rng(1000 * D + 100 * A + 10 * form + H)
     for rep in range(3):
         pol, obs = make_case(rng, D, A, H)
@@ -38,9 +40,9 @@ def test_header_matches_the_restated_chains(fam, form, H):
         g = np.uint64(g0) + np.arange(N, dtype=np.uint64)
         got_a, got_s = T.header_policy_actions(form, pol, D, A, H, obs, sigma, seed, call, g0, t)
         exp_a, exp_s = T.policy_actions(form, pol, D, A, H, obs, sigma, seed, call, g, t)
-        assert T.same_words(got_s, exp_s), (fam, form, H, rep)
+        assert same_words(got_s, exp_s), (fam, form, H, rep)
         if A == 1:   # action words are floats: NaNs compare as a class
-            assert T.same_words(got_a, exp_a), (fam, form, H, rep)
+            assert same_words(got_a, exp_a), (fam, form, H, rep)
         else:
             assert np.array_equal(got_a, exp_a), (fam, form, H, rep)
             assert got_a.max() < A
@@ -48,19 +50,18 @@ def test_header_matches_the_restated_chains(fam, form, H):
 
 def test_discrete_actions_all_occur_and_the_activation_is_not_relu_or_exact_tanh():
     """the scores really go through mg_tanhf_fast: on ordinary inputs they differ from the exact-tanh chain in some last bits and are nowhere ReLU's"""
-    import mlp_gauss_ref as G
     assert len(CASES) == 6 * 2 * len(HIDDEN)   # every family's (D, A) with the argmax and with the draw it has
     rng = np.random.default_rng(5)
     D, A, H = 3, 1, 64
     pol = rng.normal(0, 1.0, T.n_floats(D, A, H)).astype(F)
     obs = rng.normal(0, 1.0, (D, 256)).astype(F)
     _, s = T.header_policy_actions(T.ARGMAX, pol, D, A, H, obs)
-    exact, relu = G.mlp_mu(pol, D, H, 1, obs), G.mlp_mu(pol, D, H, 0, obs)
+    exact, relu = M.scores(pol, D, 1, H, obs, M.TANH)[0], M.scores(pol, D, 1, H, obs, M.RELU)[0]
     assert np.abs(s[0] - exact).max() < 1e-4 and not np.array_equal(s[0], exact)
     assert np.abs(s[0] - relu).max() > 1e-2
     seen = set()
     for fam in ("cartpole", "mountain_car", "acrobot", "lunar_lander"):
-        D, A = T.FAMILIES[fam]
+        D, A, _ = M.FAMILIES[fam]
         pol = rng.normal(0, 1.5, T.n_floats(D, A, 7)).astype(F)
         a, _ = T.header_policy_actions(T.ARGMAX, pol, D, A, 7, rng.normal(0, 2.0, (D, 256)).astype(F))
         seen.add((fam, len(set(a.tolist())) == A))

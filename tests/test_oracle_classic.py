@@ -208,12 +208,9 @@ def test_cartpole_fast_math_is_bit_identical_exhaustively():
     whole fast-form step on 7e7 random guard-admitted states.  ~10 s on 8 cores; no GPU."""
     import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    build = os.path.join(root, "tests", "native", "_build")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "cartpole_fast_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-pthread", "-o", exe,
-                    os.path.join(root, "tests", "native", "cartpole_fast_check.cpp"), "-lm"], check=True)
+
+    import native_build
+    exe = native_build.program("cartpole_fast_check.cpp", extra=("-mfma", "-pthread"))
     r = subprocess.run([exe, str(min(8, os.cpu_count() or 1)), "1"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     rows = {l.split()[0]: dict(kv.split("=") for kv in l.split()[1:]) for l in r.stdout.strip().splitlines()}

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pendulum_ref as R
+from mlp_policy_ref import mlp_ref
 
 F = np.float32
 N, STEPS, LIMIT = 256, 64, 7
@@ -69,10 +70,10 @@ def test_mlp_policy_equals_the_restatement(H, act):
     got = R.header_run(N, STEPS, **kw)
     R.assert_same_run(got, R.ref_run(N, STEPS, **kw), f"mlp H = {H} act {act}")
     assert len(np.unique(got["actions"])) > N   # a policy that really depends on the observation
-    # the vectorised chains are those of tests/mlp_policy_ref.py: the scalar restatement on the first observations
+    # the chains are those of tests/mlp_ref.py: its one-observation form (mlp_policy_ref.mlp_ref) on the first observations
     obs0 = got["obs0"]
     for i in range(0, N, 37):
-        word, _, _ = R.mlp_ref(3, 1, 1, act, H, w, obs0[:, i])
+        word, _, _ = mlp_ref(3, 1, 1, act, H, w, obs0[:, i])
         assert word == int(R.words_of(got["actions"][0, i:i + 1])[0])
 
 
@@ -107,7 +108,7 @@ def test_imported_large_angles_and_a_nan_action():
 
 def test_program_runs_its_scenario():
     """the stand-alone program (what a sanitizer build runs) goes through every policy; its table cases are reproducible from here"""
-    exe = R.build_program()
+    exe = R.check_program()
     out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()
     assert len(out) == 7 and all(line.startswith(f"case {i} ") for i, line in enumerate(out))
     fields = [dict(zip(line.split()[2::2], (int(v) for v in line.split()[3::2]))) for line in out]

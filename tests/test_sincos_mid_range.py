@@ -2,36 +2,23 @@
 mgym_math.h's sin / cos once differed from glibc (tests/sincos_mid_range.py), word for word against the CPU oracle, which calls
 the host's glibc.  CartPole: tests/native/cartpole_mid_check.cpp, all four <is_euler, sutton_barto> variants.  LunarLander:
 tests/native/ll_host_check.cpp in its `mid` form, free-flight and general paths."""
-import os
 import re
 import subprocess
 
 import pytest
 
+import native_build
 from oracle import oracle as ora
 from sincos_mid_range import HEX
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
 
-
-def _host_has_fma():
-    with open("/proc/cpuinfo") as f:
-        return any(line.startswith("flags") and " fma " in f" {line.split(':', 1)[1].strip()} " for line in f)
-
-
-pytestmark = pytest.mark.skipif(not _host_has_fma(), reason="host CPU has no FMA: glibc runs its non-FMA sinf/cosf build, "
+pytestmark = pytest.mark.skipif(not native_build.host_has_fma(), reason="host CPU has no FMA: glibc runs its non-FMA sinf/cosf build, "
                                                             "which mgym_math.h does not restate")
 
 
 def _build(src, out):
     ora.build()
-    odir = os.path.join(ROOT, "oracle", "_build")
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, out)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-o", exe,
-                    os.path.join(ROOT, "tests", "native", src), f"-L{odir}", "-loracle", f"-Wl,-rpath,{odir}", "-lm"], check=True)
-    return exe
+    return native_build.program(src, out, extra=("-mfma",), link=(*native_build.ORACLE_LINK, "-lm"))
 
 
 def test_cartpole_kernel_source_at_the_mid_range_angles_equals_oracle():

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import tanh_fast_ref as T
-from mlp_sample_ref import philox4x32_10
+from philox_ref import philox4x32_10
 
 F = np.float32
 MAX_SPACINGS = 4.0

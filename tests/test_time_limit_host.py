@@ -1,26 +1,20 @@
 """No-GPU check of the episode time limit's kernel logic: the decision header modurl_gym_amd/csrc/time_limit.h and LunarLander's
 per-env step / reset source compiled for the host (tests/native/time_limit_check.cpp), against the CPU oracle inside the Python
 time-limit wrapper (tests/time_limit_ref.py) — every output word equal."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import native_build
 from oracle import oracle as ora
-from time_limit_ref import TimeLimitRef, same
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
+from time_limit_ref import TimeLimitRef
+from words import same
 
 
 @pytest.fixture(scope="module")
 def exe():
-    os.makedirs(BUILD, exist_ok=True)
-    out = os.path.join(BUILD, "time_limit_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", out,
-                    os.path.join(ROOT, "tests", "native", "time_limit_check.cpp"), "-lm"], check=True)
-    return out
+    return native_build.program("time_limit_check.cpp")
 
 
 @pytest.mark.parametrize("limit", [40, 100])

@@ -37,12 +37,3 @@ class TimeLimitRef:
             obs = np.where(fin[None, :], ro, obs)
             self.elapsed[fin] = 0
         return obs, rew, done, trunc
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
