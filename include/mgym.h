@@ -475,11 +475,44 @@ int mgym_rollout_mlp_sample(mgym_env *env, const float *policy, int32_t hidden, 
 int mgym_rollout_mlp_gauss(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, float sigma, uint64_t policy_seed,
                            uint32_t policy_call, int32_t K, void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
 
+/* K fused steps under a policy with TWO hidden layers: Linear(D, H1) - act - Linear(H1, H2) - act - Linear(H2, A), the default network of the common PPO / A2C
+ * code bases, so that a collector runs the network its learner trains.  `policy` is a HOST pointer, read during the call, in nn.Linear order:
+ *   W1[H1][D], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A]          1 <= H1 = hidden1 <= 64, 1 <= H2 = hidden2 <= 64; D and A per family as in mgym_rollout_mlp.
+ * The words — o is the observation the environment holds before the step, every link one correctly rounded f32 fmaf, nothing else fused, nothing
+ * reassociated, and each chain over exactly its D, H1 or H2 terms (no chain is padded: fmaf(+0, +0, -0) is +0, and the sign of a zero reaches the action):
+ *   pre1_j = b1[j];  q = 0 .. D-1  ascending: pre1_j = fmaf(W1[j][q], o[q], pre1_j);   h1_j = act(pre1_j)
+ *   pre2_k = b2[k];  j = 0 .. H1-1 ascending: pre2_k = fmaf(W2[k][j], h1_j, pre2_k);   h2_k = act(pre2_k)
+ *   s_a    = b3[a];  k = 0 .. H2-1 ascending: s_a    = fmaf(W3[a][k], h2_k, s_a)
+ * (modurl_gym_amd/csrc/mlp2_policy.h is this text as the kernels and a g++ build compile it.)
+ * activation: the one hidden activation of both layers, MGYM_ACT_RELU or MGYM_ACT_TANH_FAST with their definitions above.  MGYM_ACT_TANH is refused
+ * (MGYM_ERR_BAD_ARG naming activation): the exact tanh already makes the one-layer call slower than a torch loop at 64 units, and two layers double that.
+ * head: what becomes of the scores, word for word what the one-layer entry points do with theirs —
+ *   MGYM_HEAD_GREEDY  every family: the strict sequential argmax (discrete families), s_0 itself (MountainCarContinuous, Pendulum), as mgym_rollout_mlp
+ *   MGYM_HEAD_SAMPLE  the discrete families: the categorical draw of mgym_rollout_mlp_sample — same text, same slot base 0x50000000, same key
+ *                     (policy_seed, policy_call, global env id, t)
+ *   MGYM_HEAD_GAUSS   MountainCarContinuous, Pendulum: mu + sigma * z of mgym_rollout_mlp_gauss — same text, slot base 0x60000000
+ * sigma, policy_seed and policy_call are ignored by the heads that do not use them.
+ * Everything else is as mgym_rollout_mlp: the K steps equal K mgym_step calls fed actions_out, word for word, MGYM_FLAG_AUTO_RESET and max_episode_steps
+ * included; the output shapes; the conditions of the classic families' fused form (n_envs a multiple of 4, 16-byte alignment, CartPole's K * n_envs bound);
+ * env_id_base a multiple of 4 for a drawing head; mgym_set_final_obs_out is honoured, its K > steps_cap refusal too.  The classic families decide inside
+ * their fused rollout kernels; LunarLander runs K x (policy kernel, mgym_step) for any n_envs and never its persistent launch.
+ * The weights do not fit a kernel argument (up to 20 KB): each handle owns a device buffer for them, allocated at mgym_create, and the call fills it on the
+ * handle's stream ahead of its launches by small kernels that take the weights in slices as arguments.  So nothing is allocated in the call, consecutive
+ * calls on one stream each find their own weights, and under graph capture the weights, sigma, the seed and the call word are frozen into the captured
+ * launches.
+ * Errors, all MGYM_ERR_BAD_ARG before any launch with the state untouched, each message starting with "mgym_rollout_mlp2:": a NULL policy; hidden1 or hidden2
+ * outside 1 .. 64 (naming which); activation (MGYM_ACT_TANH as above; 2 and any other value are unknown); an unknown head; MGYM_HEAD_SAMPLE on a continuous
+ * family or MGYM_HEAD_GAUSS on a discrete one; under MGYM_HEAD_GAUSS a sigma that is NaN, infinite or negative; env_id_base % 4 != 0 under a drawing head. */
+enum { MGYM_HEAD_GREEDY = 0, MGYM_HEAD_SAMPLE = 1, MGYM_HEAD_GAUSS = 2 };
+int mgym_rollout_mlp2(mgym_env *env, const float *policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head,
+                      float sigma, uint64_t policy_seed, uint32_t policy_call, int32_t K,
+                      void *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *trunc_out);
+
 /* The final observations of auto-reset episodes (gymnasium's final_obs / final_observation): what a learner bootstraps a truncated episode from.
  * final_obs_out is a DEVICE pointer to [steps_cap][obs_dim][n_envs] floats — the layout of a rollout's obs_out — and stays set on the handle until it
  * is replaced.  NULL turns the channel off and is always accepted (steps_cap is ignored then).
  * While it is set, every call that steps writes to it — mgym_step, mgym_rollout (its K x step form too), mgym_rollout_uniform, _linear, _mlp, _mlp_sample,
- * _mlp_gauss — and nothing else does (mgym_reset* never).  Take env i at step t of the call (mgym_step: t = 0): if that step returns done | truncated, the
+ * _mlp_gauss, _mlp2 — and nothing else does (mgym_reset* never).  Take env i at step t of the call (mgym_step: t = 0): if that step returns done | truncated, the
  * call writes the obs_dim words final_obs_out[(t * obs_dim + k) * n_envs + i], k = 0 .. obs_dim - 1: the observation this step produced BEFORE the fused
  * reset — exactly the words obs_out would hold for that env-step on a handle without MGYM_FLAG_AUTO_RESET.  No other word of the buffer is written
  * (read it where done | truncated is set), and obs_out and every other output are unchanged word for word.  The stores are sparse 4-byte ones made by

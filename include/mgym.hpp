@@ -80,6 +80,13 @@ class VecGym {
                            float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_mlp_gauss(env_, policy, hidden, activation, sigma, policy_seed, policy_call, K, actions_out, obs, reward, done, trunc));
     }
+    // two hidden layers, Linear(D, H1) - act - Linear(H1, H2) - act - Linear(H2, A) (mgym_rollout_mlp2): policy = W1[H1][D], b1[H1], W2[H2][H1], b2[H2], W3[A][H2],
+    // b3[A] host floats; activation MGYM_ACT_RELU or MGYM_ACT_TANH_FAST; head MGYM_HEAD_GREEDY, MGYM_HEAD_SAMPLE (discrete families) or MGYM_HEAD_GAUSS
+    // (MountainCarContinuous, Pendulum); sigma, policy_seed and policy_call are ignored by the heads that do not use them
+    void rollout_mlp2(const float* policy, int hidden1, int hidden2, int activation, int head, float sigma, uint64_t policy_seed, uint32_t policy_call, int K,
+                      void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
+        check(mgym_rollout_mlp2(env_, policy, hidden1, hidden2, activation, head, sigma, policy_seed, policy_call, K, actions_out, obs, reward, done, trunc));
+    }
     void rollout_uniform(uint64_t policy_seed, int K, void* actions_out, float* obs, float* reward, uint8_t* done, uint8_t* trunc) {
         check(mgym_rollout_uniform(env_, policy_seed, K, actions_out, obs, reward, done, trunc));
     }

@@ -17,6 +17,7 @@ CARTPOLE, MOUNTAINCAR, MOUNTAINCAR_CONT, LUNARLANDER, PENDULUM = range(5)
 ACROBOT = 6   # (5 is not assigned)
 FLAG_AUTO_RESET = 1
 ACT_RELU, ACT_TANH, ACT_TANH_FAST = 0, 1, 3   # mgym_rollout_mlp hidden activations (2 is not assigned)
+HEAD_GREEDY, HEAD_SAMPLE, HEAD_GAUSS = 0, 1, 2   # mgym_rollout_mlp2 heads
 MATH_SINF, MATH_COSF, MATH_SINCOSF, MATH_SINCOSF_U, MATH_COSF_U, MATH_TANHF = range(6)   # mgym_math_probe entry points
 LL_GEOM_SHAPES, LL_GEOM_DISTANCE, LL_GEOM_MANIFOLD, LL_GEOM_TOI = range(4)   # mgym_ll_geom_probe probes
 
@@ -54,6 +55,7 @@ PROTOTYPES = {
     "mgym_rollout_mlp": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_rollout_mlp_sample": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_rollout_mlp_gauss": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "mgym_rollout_mlp2": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "mgym_episode_count": (C.c_int, [_vp, _u64p]),
     "mgym_observation": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "mgym_observation_aos": (C.c_int, [_vp, _vp]),

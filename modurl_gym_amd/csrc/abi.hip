@@ -51,6 +51,29 @@ __global__ void obs_to_aos_kernel(const float* __restrict__ soa, uint64_t stride
     for (int k = 0; k < obs_dim; ++k) aos[i * obs_dim + k] = soa[(uint64_t)k * stride + i];
 }
 
+// mgym_rollout_mlp2: a slice of the weight pack, by value (a kernel argument holds 4 KiB), stored to the handle's buffer
+constexpr int kMlp2Slice = 1000;
+struct Mlp2Slice { float w[kMlp2Slice]; };
+static_assert(sizeof(Mlp2Slice) + 16 <= 4096, "mlp2_pack_kernel: by-value kernel arguments above 4096 bytes");
+__global__ void __launch_bounds__(256) mlp2_pack_kernel(Mlp2Slice slice, float* __restrict__ dst, int count) {
+    for (int i = threadIdx.x; i < count; i += blockDim.x) dst[i] = slice.w[i];
+}
+
+int mgym::Env::mlp2_store(const PolicyCall& call, int D, int A) {
+    static_assert(kMlp2PackMax == 5192, "the pack of mlp2_policy.h at its largest");
+    float pack[kMlp2PackMax];
+    mlp2_pack(call.weights, D, A, call.hidden, call.hidden2, pack);
+    const int total = mlp2_pack_floats(D, call.hidden, call.hidden2);
+    for (int at = 0; at < total; at += kMlp2Slice) {
+        Mlp2Slice slice{};   // (value-initialised: the words past `count` travel in the launch and in a captured graph node too)
+        const int count = total - at < kMlp2Slice ? total - at : kMlp2Slice;
+        memcpy(slice.w, pack + at, (size_t)count * sizeof(float));
+        hipLaunchKernelGGL(mlp2_pack_kernel, dim3(1), dim3(256), 0, stream, slice, mlp2_dev + at, count);
+        MGYM_HIP(hipGetLastError());
+    }
+    return MGYM_OK;
+}
+
 struct mgym_env {
     Env* impl;
 };
@@ -189,6 +212,7 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
         if (hipMalloc((void**)&impl->d_done, kDoneShards * sizeof(unsigned long long)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipHostMalloc((void**)&impl->h_done, kDoneShards * sizeof(unsigned long long), 0) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipHostMalloc failed"); break; }
         if (hipMemsetAsync(impl->d_done, 0, kDoneShards * sizeof(unsigned long long), impl->stream) != hipSuccess) { st = MGYM_ERR_HIP; break; }
+        if (hipMalloc((void**)&impl->mlp2_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipEventCreate(&impl->ev0) != hipSuccess || hipEventCreate(&impl->ev1) != hipSuccess) { st = MGYM_ERR_HIP; break; }
         st = impl->init();
         if (st != MGYM_OK) break;
@@ -216,6 +240,7 @@ int mgym_destroy(mgym_env* env) {
         if (e->h_err) (void)hipHostFree(e->h_err);
         if (e->d_done) (void)hipFree(e->d_done);
         if (e->h_done) (void)hipHostFree(e->h_done);
+        if (e->mlp2_dev) (void)hipFree(e->mlp2_dev);
         hipStream_t s = e->own_stream ? e->stream : nullptr;
         delete e;
         if (s) (void)hipStreamDestroy(s);
@@ -353,6 +378,33 @@ int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, i
     if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_gauss: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
     return e->rollout_policy(PolicyCall{roll_act_mlp_gauss(activation), "mgym_rollout_mlp_gauss", policy, hidden, policy_seed, policy_call, sigma},
                              K, actions_out, obs_out, reward_out, done_out, trunc_out);
+}
+
+int mgym_rollout_mlp2(mgym_env* env, const float* policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, uint64_t policy_seed,
+                      uint32_t policy_call, int32_t K, void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
+    static_assert(MGYM_HEAD_GREEDY == MLP2_HEAD_GREEDY && MGYM_HEAD_SAMPLE == MLP2_HEAD_SAMPLE && MGYM_HEAD_GAUSS == MLP2_HEAD_GAUSS, "mgym.h and mlp2_policy.h number the heads alike");
+    ENV_OR_FAIL(env);
+    if (K < 0) return bad_arg("mgym_rollout_mlp2: K < 0");
+    FINAL_CAP_OR_FAIL("mgym_rollout_mlp2", K);
+    if (!policy) return bad_arg("mgym_rollout_mlp2: policy is NULL");
+    if (hidden1 < 1 || hidden1 > 64) return bad_arg("mgym_rollout_mlp2: hidden1 must be between 1 and 64");
+    if (hidden2 < 1 || hidden2 > 64) return bad_arg("mgym_rollout_mlp2: hidden2 must be between 1 and 64");
+    if (activation == MGYM_ACT_TANH)
+        return bad_arg("mgym_rollout_mlp2: activation MGYM_ACT_TANH is not offered with two hidden layers (the exact tanh would be nearly all of the launch): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
+    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH_FAST) return bad_arg("mgym_rollout_mlp2: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST");
+    if (head != MGYM_HEAD_GREEDY && head != MGYM_HEAD_SAMPLE && head != MGYM_HEAD_GAUSS) return bad_arg("mgym_rollout_mlp2: head must be MGYM_HEAD_GREEDY, MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
+    const bool continuous = e->cfg.kind == MGYM_MOUNTAINCAR_CONT || e->cfg.kind == MGYM_PENDULUM;
+    static const char* const names[] = {"CartPole", "MountainCar", "MountainCarContinuous", "LunarLander", "Pendulum", "", "Acrobot"};
+    if (head == MGYM_HEAD_SAMPLE && continuous)
+        return bad_arg((std::string("mgym_rollout_mlp2: head MGYM_HEAD_SAMPLE: ") + names[e->cfg.kind] + " has no discrete actions to draw from (use MGYM_HEAD_GAUSS)").c_str());
+    if (head == MGYM_HEAD_GAUSS && !continuous)
+        return bad_arg((std::string("mgym_rollout_mlp2: head MGYM_HEAD_GAUSS: ") + names[e->cfg.kind] + " has discrete actions (use MGYM_HEAD_SAMPLE)").c_str());
+    if (head == MGYM_HEAD_GAUSS && (!(sigma >= 0.0f) || sigma > 3.402823466e+38f)) return bad_arg("mgym_rollout_mlp2: sigma must be finite and >= 0");   // (a NaN fails the first test)
+    if (head != MGYM_HEAD_GREEDY && e->cfg.env_id_base % 4 != 0)
+        return bad_arg("mgym_rollout_mlp2: env_id_base must be a multiple of 4 for a drawing head (one Philox block serves 4 consecutive global env ids)");
+    PolicyCall call{roll_act_mlp2(activation, head), "mgym_rollout_mlp2", policy, hidden1, policy_seed, policy_call, sigma};
+    call.hidden2 = hidden2;
+    return e->rollout_policy(call, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
 int mgym_set_final_obs_out(mgym_env* env, float* final_obs_out, int32_t steps_cap) {

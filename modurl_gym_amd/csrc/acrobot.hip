@@ -242,6 +242,7 @@ acrobot_step4_kernel(float* obs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 // registers for K steps; per step one 16-B action word in (TABLE) or out, reward / done / truncated (and optionally the observation) out.  Same
 // per-env function and the same in-place auto-reset as the step kernels, hence bit-identical to K separate steps.
 // The policies decide from the six observation words held before the step (acrobot_step.h); actions_out holds u32 words.
+// (mgym_rollout_mlp2's sources take the address of the handle's pack and its widths at the head of the trailing pack: soa4.h)
 template <int POLICY> using AbPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<6, 3>, AbLinearPolicy>;
 template <int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
@@ -267,6 +268,15 @@ acrobot_rollout_kernel(AcrobotDev d, const uint32_t* __restrict__ act, int K, fl
                 if ((t & 1) == 0) bits = acrobot_uniform_block(uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = acrobot_uniform_action(bits.w[k], (uint32_t)t);
+            } else if constexpr (roll_act_is_mlp2(POLICY)) {
+                // mgym_rollout_mlp2: the argmax, or (SAMPLE) the draw of mgym_rollout_mlp_sample from the scores
+                static_assert(roll_act_mlp2_head(POLICY) != MLP2_HEAD_GAUSS, "Acrobot has discrete actions: no Gaussian draw");
+                float o[4][6];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acrobot_obs(e[k], o[k]);
+                Philox4 w{};
+                if constexpr (roll_act_mlp2_head(POLICY) == MLP2_HEAD_SAMPLE) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
+                mlp2_actions<6, 3, roll_act_mlp2_act(POLICY), roll_act_mlp2_head(POLICY), 4>(mlp2_net_of(fin...), o, w.w, 0.0f, a);
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 float o[4][6];
 #pragma unroll
@@ -438,6 +448,14 @@ struct AcrobotEnv final : ClassicEnv {
         else hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
+    // the same for a two-hidden-layer source: its Mlp2Net at the head of the trailing pack
+    template <int POLICY, bool TL>
+    void launch_rollout_mlp2(uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const Mlp2Net<6, 3>& net, UniformDraw uni) {
+        const uint32_t* none = nullptr;
+        if (final_obs) hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, Mlp2Net<6, 3>, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, AbLinearPolicy{}, act_out, uni, net, final_obs);
+        else hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, Mlp2Net<6, 3>>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, AbLinearPolicy{}, act_out, uni, net);
+    }
+
     void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         with_bools([&](auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); }, dev.limit != 0u);
     }
@@ -447,8 +465,16 @@ struct AcrobotEnv final : ClassicEnv {
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
         if (roll_act_gauss(call.source)) { set_last_error(std::string(call.api) + ": Acrobot has discrete actions: use mgym_rollout_mlp_sample"); return MGYM_ERR_BAD_ARG; }   // (the C ABI refuses it first)
         if (!fused_rollout_args_ok(call.api, n, K, false, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
+        if (roll_act_is_mlp2(call.source)) { if (const int st = mlp2_store(call, 6, 3)) return st; }
         with_bools([&](auto T) {
             constexpr bool TL = decltype(T)::value;
+            if (roll_act_is_mlp2(call.source)) {   // (the pack is on the stream already)
+                with_mlp2_source([&](auto S) {
+                    constexpr int SRC = decltype(S)::value;
+                    if constexpr (roll_act_mlp2_head(SRC) != MLP2_HEAD_GAUSS) launch_rollout_mlp2<SRC, TL>(ao, K, obs_out, reward, done, trunc, mlp2_net<6, 3>(call), UniformDraw{call.seed, call.call});
+                }, call.source);
+                return;
+            }
             switch (call.source) {
             case ROLL_ACT_UNIFORM:
                 launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, AbLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});

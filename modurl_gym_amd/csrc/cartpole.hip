@@ -296,6 +296,7 @@ struct LinearPolicy { float w[4], b; };   // action = ((w0 x + w1 x_dot) + w2 th
 // mgym_rollout_mlp: the weight pack of mlp_policy.h takes the place of the five linear words in the kernel's arguments (1 804 bytes by value; the other
 // policies' instantiations keep the arguments they had)
 typedef MlpPack<4, 2> CpMlpPack;
+// (mgym_rollout_mlp2's sources take the address of the handle's pack and its widths at the head of the trailing pack: soa4.h)
 template <int POLICY> using CpPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), CpMlpPack, LinearPolicy>;
 
 // Fused K-step rollout (mgym_rollout / mgym_rollout_uniform): one lane keeps its 4 environments in registers for
@@ -343,6 +344,14 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
             float r[4];
             if constexpr (POLICY == ROLL_ACT_TABLE) {
                 if (in) { const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(ra, off4, so, 2); a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w; }
+            } else if constexpr (roll_act_is_mlp2(POLICY)) {
+                // mgym_rollout_mlp2: the argmax, or (SAMPLE) the draw of mgym_rollout_mlp_sample from the scores
+                static_assert(roll_act_mlp2_head(POLICY) != MLP2_HEAD_GAUSS, "CartPole has discrete actions: no Gaussian draw");
+                const float o[4][4] = {{s[0].x, s[0].xd, s[0].th, s[0].thd}, {s[1].x, s[1].xd, s[1].th, s[1].thd}, {s[2].x, s[2].xd, s[2].th, s[2].thd}, {s[3].x, s[3].xd, s[3].th, s[3].thd}};
+                Philox4 w{};
+                if constexpr (roll_act_mlp2_head(POLICY) == MLP2_HEAD_SAMPLE) w = env_draw(policy_seed, d.env_id_base + i0, policy_call, SLOT_POLICY_SAMPLE + (uint32_t)t);
+                mlp2_actions<4, 2, roll_act_mlp2_act(POLICY), roll_act_mlp2_head(POLICY), 4>(mlp2_net_of(fin...), o, w.w, 0.0f, a);
+                if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 // hidden-layer policy on the observations the lane's four envs hold before the step (mlp_policy.h: fmaf chains from the bias, ascending index)
                 const float o[4][4] = {{s[0].x, s[0].xd, s[0].th, s[0].thd}, {s[1].x, s[1].xd, s[1].th, s[1].thd}, {s[2].x, s[2].xd, s[2].th, s[2].thd}, {s[3].x, s[3].xd, s[3].th, s[3].thd}};
@@ -590,6 +599,30 @@ struct CartPoleEnv final : Env {
         if (n == 0 || K == 0) return MGYM_OK;
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
         if (!fused_rollout_args_ok(call.api, n, K, true, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
+        if (roll_act_is_mlp2(call.source)) {   // the pack goes on the stream ahead of the launch
+            if (const int st = mlp2_store(call, 4, 2)) return st;
+            with_mlp2_source([&](auto S) {
+                constexpr int SRC = decltype(S)::value;
+                if constexpr (roll_act_mlp2_head(SRC) != MLP2_HEAD_GAUSS) {
+                    const dim3 g(grid_for(n / 4)), b(kBlock);
+                    const uint32_t* none = nullptr;
+                    const Mlp2Net<4, 2> net = mlp2_net<4, 2>(call);
+                    if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
+                        with_bools([&](auto E, auto B) {
+                            hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(B)::value, true, SRC, Mlp2Net<4, 2>, float*>), g, b, 0, stream, dev, none, ao, call.seed, call.call, LinearPolicy{}, K,
+                                               obs_out, reward, done, trunc, net, final_obs);
+                        }, cfg.is_euler, cfg.sutton_barto_reward);
+                    } else {
+                        with_bools([&](auto E, auto B, auto R) {
+                            hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(B)::value, decltype(R)::value, SRC, Mlp2Net<4, 2>>), g, b, 0, stream, dev, none, ao, call.seed, call.call, LinearPolicy{}, K,
+                                               obs_out, reward, done, trunc, net);
+                        }, cfg.is_euler, cfg.sutton_barto_reward, auto_reset);
+                    }
+                }
+            }, call.source);
+            MGYM_HIP(hipGetLastError());
+            return MGYM_OK;
+        }
         switch (call.source) {
         case ROLL_ACT_UNIFORM:
             launch_rollout<ROLL_ACT_UNIFORM>(nullptr, ao, call.seed, uniform_calls++, K, obs_out, reward, done, trunc);

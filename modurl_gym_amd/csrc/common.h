@@ -95,6 +95,13 @@ struct Env {
     int32_t final_cap = 0;
     // K fused steps under an on-device policy (mgym_rollout_uniform / _linear / _mlp): the action source, its weights or seed in `call`
     virtual int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) = 0;
+    // mgym_rollout_mlp2: the handle's weight pack in device memory (kMlp2PackMax floats, allocated at mgym_create).  mlp2_store lays the call's policy out
+    // as mlp2_policy.h states and stores it on the stream ahead of the call's launches, by kernels that take the pack in slices as arguments: the caller's
+    // array is read during the call only, a captured graph carries the weights, and consecutive calls on one stream each find their own.
+    float* mlp2_dev = nullptr;
+    int mlp2_store(const PolicyCall& call, int D, int A);
+    template <int D, int A>
+    Mlp2Net<D, A> mlp2_net(const PolicyCall& call) const { return Mlp2Net<D, A>{mlp2_dev, call.hidden, call.hidden2, call.sigma}; }
     uint32_t uniform_calls = 0;  // mgym_rollout_uniform calls that launched so far (Philox counter word of the policy stream)
     virtual int observation(const float** obs, uint64_t* col_stride) = 0;
     virtual int get_state(void* blob) = 0;

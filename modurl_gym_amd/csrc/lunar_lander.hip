@@ -730,6 +730,28 @@ __global__ void __launch_bounds__(256) ll_policy_mlp_sample_kernel(const float* 
     out[i] = a[0];
 }
 
+// mgym_rollout_mlp2: the step's action column from the two-hidden-layer policy of mlp2_policy.h, one environment per lane and any n, as ll_policy_mlp_kernel
+// stands beside the step.  The weights are the handle's pack in device memory (Env::mlp2_dev), stored on the stream ahead of the K launches.  SAMPLE: the
+// word of ll_policy_mlp_sample_kernel — (g % 4) of Philox(key = seed; counter = (g & ~3, call, SLOT_POLICY_SAMPLE + t)), g the global env id.
+template <int ACT, bool SAMPLE>
+__global__ void __launch_bounds__(256) ll_policy_mlp2_kernel(const float* __restrict__ obs, uint64_t n, uint64_t n_pad, Mlp2Net<8, 4> net, uint64_t env_id_base, uint64_t seed,
+                                                             uint32_t call, uint32_t t, uint32_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float o[1][8];
+    uint32_t a[1], word[1] = {0u};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[0][c] = obs[(uint64_t)c * n_pad + i];
+    if constexpr (SAMPLE) {
+        const uint64_t g = env_id_base + i;
+        const Philox4 w = env_draw(seed, g & ~3ull, call, SLOT_POLICY_SAMPLE + t);
+        const uint32_t k = (uint32_t)g & 3u;
+        word[0] = k == 0u ? w.w[0] : k == 1u ? w.w[1] : k == 2u ? w.w[2] : w.w[3];
+    }
+    mlp2_actions<8, 4, ACT, SAMPLE ? MLP2_HEAD_SAMPLE : MLP2_HEAD_GREEDY, 1>(net, o, word, 0.0f, a);
+    out[i] = a[0];
+}
+
 // Staged resets.  The state an env has after reset() — scene, implicit step(0), observation — is a pure function of
 // (seed, env id, episode counter), so it does not have to be computed when the episode ends, on the critical path of
 // that step (reset kernel: 0.11 ms behind the contact kernel): it is PREPARED in advance, in shadow columns, by the same
@@ -1265,6 +1287,24 @@ struct LunarLanderEnv final : Env {
         const int policy = call.source;
         const bool mlp = roll_act_is_mlp(policy);
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
+        if (roll_act_is_mlp2(policy)) {   // mgym_rollout_mlp2: always K x (policy kernel, step()), the pack stored on the stream first
+            if (roll_act_mlp2_head(policy) == MLP2_HEAD_GAUSS) { set_last_error(std::string(call.api) + ": LunarLander has discrete actions"); return MGYM_ERR_BAD_ARG; }   // (the C ABI refuses it first)
+            if (const int st = mlp2_store(call, 8, 4)) return st;
+            const Mlp2Net<8, 4> net = mlp2_net<8, 4>(call);
+            const unsigned g = (unsigned)((n + 255) / 256);
+            for (int t = 0; t < K; ++t) {
+                uint32_t* a = ao ? ao + (size_t)t * n : next_act;
+                with_bools([&](auto F, auto S) {
+                    hipLaunchKernelGGL((ll_policy_mlp2_kernel<decltype(F)::value ? MLP_ACT_TANH_FAST : MLP_ACT_RELU, decltype(S)::value>), dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad,
+                                       net, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
+                }, roll_act_mlp2_act(policy) == MLP_ACT_TANH_FAST, roll_act_mlp2_head(policy) == MLP2_HEAD_SAMPLE);
+                MGYM_HIP(hipGetLastError());
+                int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
+                              trunc ? trunc + (size_t)t * n : nullptr);
+                if (st != MGYM_OK) return st;
+            }
+            return MGYM_OK;
+        }
         RollPolicy pol{};
         LLMlpPack pack;   // (the hidden-layer sources only: their weights as the kernels read them)
         if (policy == ROLL_ACT_UNIFORM) {

@@ -264,6 +264,7 @@ struct McLinearPolicy { float w[3][2], b[3]; };
 // the force u 2^-23 - 1, uniform over the multiples of 2^-23 in [-1, 1).
 // mgym_rollout_mlp: the weight pack of mlp_policy.h (A = 3 scores, or the one force of MountainCarContinuous) takes the place of the linear words in the
 // kernel's arguments; the other policies' instantiations keep the arguments they had
+// (mgym_rollout_mlp2's sources take the address of the handle's pack, its widths and sigma at the head of the trailing pack: soa4.h)
 template <bool CONT, int POLICY> using McPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<2, CONT ? 1 : 3>, McLinearPolicy>;
 // mgym_rollout_mlp_gauss (MountainCarContinuous only): sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
 template <int POLICY> using McDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, UniformDraw>;
@@ -296,6 +297,17 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                     if constexpr (CONT) a[k] = __float_as_uint((float)(bits.w[k] >> 8) * 1.1920928955078125e-07f - 1.0f);
                     else a[k] = ((((t & 1) ? bits.w[k] >> 16 : bits.w[k] & 0xffffu)) * 3u) >> 16;
                 }
+                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
+            } else if constexpr (roll_act_is_mlp2(POLICY)) {
+                // mgym_rollout_mlp2: the argmax / the one score, or the draw of mgym_rollout_mlp_sample (Discrete(3)) / mgym_rollout_mlp_gauss (Box(-1, 1))
+                constexpr int HEAD = roll_act_mlp2_head(POLICY);
+                static_assert(HEAD == MLP2_HEAD_GREEDY || (CONT ? HEAD == MLP2_HEAD_GAUSS : HEAD == MLP2_HEAD_SAMPLE), "the heads a family has");
+                const float o[4][2] = {{ps[0], vs[0]}, {ps[1], vs[1]}, {ps[2], vs[2]}, {ps[3], vs[3]}};
+                const Mlp2Net<2, CONT ? 1 : 3>& net = mlp2_net_of(fin_out...);
+                Philox4 w{};
+                if constexpr (HEAD == MLP2_HEAD_SAMPLE) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
+                if constexpr (HEAD == MLP2_HEAD_GAUSS) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_GAUSS + (uint32_t)t);
+                mlp2_actions<2, CONT ? 1 : 3, roll_act_mlp2_act(POLICY), HEAD, 4>(net, o, w.w, net.sigma, a);
                 if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
             } else if constexpr (roll_act_is_mlp(POLICY)) {
                 // hidden-layer policy on (position, velocity) of the lane's four envs before the step (mlp_policy.h)
@@ -481,8 +493,22 @@ struct MountainCarEnv final : ClassicEnv {
         if (n == 0 || K == 0) return MGYM_OK;
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
         if (!fused_rollout_args_ok(call.api, n, K, false, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
+        if (roll_act_is_mlp2(call.source)) { if (const int st = mlp2_store(call, 2, continuous ? 1 : 3)) return st; }
         with_bools([&](auto C, auto T) {
             constexpr bool CONT = decltype(C)::value, TL = decltype(T)::value;
+            if (roll_act_is_mlp2(call.source)) {   // (the pack is on the stream already; the C ABI refuses the head the family does not have)
+                with_mlp2_source([&](auto S) {
+                    constexpr int SRC = decltype(S)::value, HEAD = roll_act_mlp2_head(SRC);
+                    const Mlp2Net<2, CONT ? 1 : 3> net = mlp2_net<2, CONT ? 1 : 3>(call);
+                    if constexpr (HEAD == MLP2_HEAD_GREEDY || (CONT ? HEAD == MLP2_HEAD_GAUSS : HEAD == MLP2_HEAD_SAMPLE)) {
+                        const uint32_t* none = nullptr;
+                        const UniformDraw uni{call.seed, call.call};
+                        if (final_obs) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, SRC, TL, Mlp2Net<2, CONT ? 1 : 3>, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni, net, final_obs);
+                        else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, SRC, TL, Mlp2Net<2, CONT ? 1 : 3>>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni, net);
+                    }
+                }, call.source);
+                return;
+            }
             switch (call.source) {
             case ROLL_ACT_UNIFORM:
                 launch_rollout<ROLL_ACT_UNIFORM, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, McLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});

@@ -213,6 +213,7 @@ pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 // for K steps; per step one 16-B action word in (TABLE) or out, reward / done / truncated (and optionally the observation) out.  Same per-env
 // function and the same in-place auto-reset as the step kernels, hence bit-identical to K separate steps.  One sincos per environment-step.
 // The policies decide from (cos, sin, thdot) held before the step (pendulum_step.h); actions_out holds f32 words.
+// (mgym_rollout_mlp2's sources take the address of the handle's pack, its widths and sigma at the head of the trailing pack: soa4.h)
 template <int POLICY> using PdPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<3, 1>, PdLinearPolicy>;
 // mgym_rollout_mlp_gauss: sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
 template <int POLICY> using PdDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, UniformDraw>;
@@ -238,6 +239,14 @@ pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, 
             uint32_t a[4];
             if constexpr (POLICY == ROLL_ACT_UNIFORM) {
                 pendulum_uniform_actions(uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, a);
+            } else if constexpr (roll_act_is_mlp2(POLICY)) {
+                // mgym_rollout_mlp2: the score, or (GAUSS) the draw of mgym_rollout_mlp_gauss around it
+                static_assert(roll_act_mlp2_head(POLICY) != MLP2_HEAD_SAMPLE, "Pendulum has no categorical draw");
+                const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
+                const Mlp2Net<3, 1>& net = mlp2_net_of(fin...);
+                Philox4 w{};
+                if constexpr (roll_act_mlp2_head(POLICY) == MLP2_HEAD_GAUSS) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_GAUSS + (uint32_t)t);
+                mlp2_actions<3, 1, roll_act_mlp2_act(POLICY), roll_act_mlp2_head(POLICY), 4>(net, o, w.w, net.sigma, a);
             } else if constexpr (roll_act_gauss(POLICY)) {
                 // mgym_rollout_mlp_gauss: one Philox evaluation per lane per step, its two word pairs for the lane's two env pairs
                 const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
@@ -407,6 +416,19 @@ struct PendulumEnv final : ClassicEnv {
         hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
     }
 
+    // the same for a two-hidden-layer source: its Mlp2Net at the head of the trailing pack
+    template <int POLICY, bool TL>
+    void launch_rollout_mlp2(uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const Mlp2Net<3, 1>& net, UniformDraw uni) {
+        const uint32_t* none = nullptr;
+        if constexpr (TL) {
+            if (final_live()) {
+                hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, true, Mlp2Net<3, 1>, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, PdLinearPolicy{}, act_out, uni, net, final_obs);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL, Mlp2Net<3, 1>>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, PdLinearPolicy{}, act_out, uni, net);
+    }
+
     // the channel of mgym_set_final_obs_out has something to deliver: without a time limit no Pendulum episode ever ends (and only auto-reset handles hold a pointer)
     bool final_live() const { return final_obs != nullptr && dev.limit != 0u; }
 
@@ -419,8 +441,16 @@ struct PendulumEnv final : ClassicEnv {
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
         if (roll_act_samples(call.source)) { set_last_error(std::string(call.api) + ": Pendulum has no discrete actions to draw from"); return MGYM_ERR_BAD_ARG; }   // (the C ABI refuses it first)
         if (!fused_rollout_args_ok(call.api, n, K, false, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
+        if (roll_act_is_mlp2(call.source)) { if (const int st = mlp2_store(call, 3, 1)) return st; }
         with_bools([&](auto T) {
             constexpr bool TL = decltype(T)::value;
+            if (roll_act_is_mlp2(call.source)) {   // (the pack is on the stream already)
+                with_mlp2_source([&](auto S) {
+                    constexpr int SRC = decltype(S)::value;
+                    if constexpr (roll_act_mlp2_head(SRC) != MLP2_HEAD_SAMPLE) launch_rollout_mlp2<SRC, TL>(ao, K, obs_out, reward, done, trunc, mlp2_net<3, 1>(call), UniformDraw{call.seed, call.call});
+                }, call.source);
+                return;
+            }
             switch (call.source) {
             case ROLL_ACT_UNIFORM:
                 launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, PdLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});

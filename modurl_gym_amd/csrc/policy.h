@@ -3,6 +3,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "mlp_policy.h"
+#include "mlp2_policy.h"
 
 namespace mgym {
 
@@ -17,10 +18,14 @@ namespace mgym {
 //             Philox block keyed the same way (mgym_rollout_mlp_gauss).  New sources again, for the same reason.
 //   MLP_TANH_FAST / MLP_TANH_FAST_SAMPLE / MLP_TANH_FAST_GAUSS  the three forms above with mg_tanhf_fast as the hidden activation (MGYM_ACT_TANH_FAST).  New
 //             sources once more: the nine before them keep their numbers and their code.  LunarLander's persistent launch carries none of them.
+//   MLP2_*    the two-hidden-layer policy of mlp2_policy.h (mgym_rollout_mlp2): 12 + 2 * head + (1 for MGYM_ACT_TANH_FAST), head = MGYM_HEAD_GREEDY / _SAMPLE /
+//             _GAUSS.  New sources beside the twelve, which keep their numbers and their code; their weights are the handle's pack in device memory, not a
+//             kernel argument.  LunarLander's persistent launch carries none of them.
 // How LunarLander's persistent launch carries each of them: ll_roll_types.h.
 enum { ROLL_ACT_TABLE = 0, ROLL_ACT_LINEAR = 1, ROLL_ACT_UNIFORM = 2, ROLL_ACT_MLP_RELU = 3, ROLL_ACT_MLP_TANH = 4, ROLL_ACT_MLP_RELU_SAMPLE = 5,
        ROLL_ACT_MLP_TANH_SAMPLE = 6, ROLL_ACT_MLP_RELU_GAUSS = 7, ROLL_ACT_MLP_TANH_GAUSS = 8, ROLL_ACT_MLP_TANH_FAST = 9, ROLL_ACT_MLP_TANH_FAST_SAMPLE = 10,
-       ROLL_ACT_MLP_TANH_FAST_GAUSS = 11 };
+       ROLL_ACT_MLP_TANH_FAST_GAUSS = 11, ROLL_ACT_MLP2_RELU = 12, ROLL_ACT_MLP2_TANH_FAST = 13, ROLL_ACT_MLP2_RELU_SAMPLE = 14, ROLL_ACT_MLP2_TANH_FAST_SAMPLE = 15,
+       ROLL_ACT_MLP2_RELU_GAUSS = 16, ROLL_ACT_MLP2_TANH_FAST_GAUSS = 17 };
 // the hidden-layer sources that draw their action from the categorical distribution (LunarLander's persistent launch carries none of them)
 constexpr bool roll_act_samples(int source) { return source == ROLL_ACT_MLP_RELU_SAMPLE || source == ROLL_ACT_MLP_TANH_SAMPLE || source == ROLL_ACT_MLP_TANH_FAST_SAMPLE; }
 // the hidden-layer sources that draw a continuous action around their score (MountainCarContinuous and Pendulum only)
@@ -48,18 +53,36 @@ void with_mlp_act(F&& f, int source) {
     default: f(std::integral_constant<int, MLP_ACT_RELU>{}); break;
     }
 }
+// the two-hidden-layer sources: their activation (MLP_ACT_RELU or MLP_ACT_TANH_FAST), their head (MLP2_HEAD_*; -1 for any other source), and back
+constexpr bool roll_act_is_mlp2(int source) { return source >= ROLL_ACT_MLP2_RELU && source <= ROLL_ACT_MLP2_TANH_FAST_GAUSS; }
+constexpr int roll_act_mlp2_act(int source) { return ((source - ROLL_ACT_MLP2_RELU) & 1) ? MLP_ACT_TANH_FAST : MLP_ACT_RELU; }
+constexpr int roll_act_mlp2_head(int source) { return roll_act_is_mlp2(source) ? (source - ROLL_ACT_MLP2_RELU) / 2 : -1; }
+constexpr int roll_act_mlp2(int act, int head) { return ROLL_ACT_MLP2_RELU + 2 * head + (act == MLP_ACT_TANH_FAST ? 1 : 0); }
+// from a run-time two-hidden-layer source to the source as a template argument: f(std::integral_constant<int, ROLL_ACT_MLP2_*>{})
+template <class F>
+void with_mlp2_source(F&& f, int source) {
+    switch (source) {
+    case ROLL_ACT_MLP2_RELU: f(std::integral_constant<int, ROLL_ACT_MLP2_RELU>{}); break;
+    case ROLL_ACT_MLP2_TANH_FAST: f(std::integral_constant<int, ROLL_ACT_MLP2_TANH_FAST>{}); break;
+    case ROLL_ACT_MLP2_RELU_SAMPLE: f(std::integral_constant<int, ROLL_ACT_MLP2_RELU_SAMPLE>{}); break;
+    case ROLL_ACT_MLP2_TANH_FAST_SAMPLE: f(std::integral_constant<int, ROLL_ACT_MLP2_TANH_FAST_SAMPLE>{}); break;
+    case ROLL_ACT_MLP2_RELU_GAUSS: f(std::integral_constant<int, ROLL_ACT_MLP2_RELU_GAUSS>{}); break;
+    default: f(std::integral_constant<int, ROLL_ACT_MLP2_TANH_FAST_GAUSS>{}); break;
+    }
+}
 // the sources that decide from the observation
 constexpr bool roll_act_observes(int source) { return source == ROLL_ACT_LINEAR || roll_act_is_mlp(source); }
 
-// One call of mgym_rollout_uniform / _linear / _mlp / _mlp_sample / _mlp_gauss as the C ABI hands it to Env::rollout_policy, its own argument checks passed.
+// One call of mgym_rollout_uniform / _linear / _mlp / _mlp_sample / _mlp_gauss / _mlp2 as the C ABI hands it to Env::rollout_policy, its own argument checks passed.
 struct PolicyCall {
-    int source;             // ROLL_ACT_UNIFORM, ROLL_ACT_LINEAR or one of the ROLL_ACT_MLP_* sources
+    int source;             // ROLL_ACT_UNIFORM, ROLL_ACT_LINEAR or one of the ROLL_ACT_MLP_* / ROLL_ACT_MLP2_* sources
     const char* api;        // the entry point's name: the prefix of every error message
     const float* weights;   // LINEAR: obs_dim weights + bias per score; MLP_*: W1[H][D], b1[H], W2[A][H], b2[A] (host floats); UNIFORM: null
     int hidden;             // MLP_*: H
     uint64_t seed;          // UNIFORM, MLP_*_SAMPLE, MLP_*_GAUSS: the policy seed
     uint32_t call;          // MLP_*_SAMPLE, MLP_*_GAUSS: the caller's call word (UNIFORM counts its calls on the handle instead)
     float sigma;            // MLP_*_GAUSS: the standard deviation, finite and >= 0
+    int hidden2 = 0;        // MLP2_*: H2 (`hidden` is H1, `weights` W1[H1][D], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A])
 };
 
 // the uniform stream of a classic family's rollout kernel (policy seed, call word); the categorical draw of MLP_*_SAMPLE travels in it too

@@ -302,6 +302,47 @@ class VecEnv:
         policy, H = self.pack_mlp(w1, b1, w2, b2)
         return self._rollout_host(K, lambda *out: self.rollout_mlp_gauss_device(policy, H, activation, sigma, seed, call, K, *out), np.float32)
 
+    def pack_mlp2(self, w1, b1, w2, b2, w3, b3):
+        """nn.Linear-layout weights of Linear(D, H1) - act - Linear(H1, H2) - act - Linear(H2, A) (w1 [H1, D], b1 [H1], w2 [H2, H1], b2 [H2], w3 [A, H2], b3 [A])
+        -> (policy, H1, H2): the float32 words mgym_rollout_mlp2 reads.  Shapes are checked against the family (PolicyShapeError); H1 and H2 by the engine."""
+        D, A = self.mlp_dims()
+        w1, b1, w2, b2, w3, b3 = (np.asarray(x, np.float32) for x in (w1, b1, w2, b2, w3, b3))
+        H1 = w1.shape[0] if w1.ndim == 2 else -1
+        H2 = w2.shape[0] if w2.ndim == 2 else -1
+        if w1.shape != (H1, D) or b1.shape != (H1,) or w2.shape != (H2, H1) or b2.shape != (H2,) or w3.shape != (A, H2) or b3.shape != (A,):
+            raise PolicyShapeError(L.ERR_BAD_ARG, f"{KIND_NAMES[self.kind]} takes w1 [H1, {D}], b1 [H1], w2 [H2, H1], b2 [H2], w3 [{A}, H2], b3 [{A}]; got "
+                                                  f"{w1.shape}, {b1.shape}, {w2.shape}, {b2.shape}, {w3.shape}, {b3.shape}")
+        return np.concatenate([w1.ravel(), b1, w2.ravel(), b2, w3.ravel(), b3]).astype(np.float32), H1, H2
+
+    def rollout_mlp2_device(self, policy, hidden1, hidden2, activation, head, sigma, seed, call, K, actions_out=None, obs_out=None, reward_out=None, done_out=None,
+                            trunc_out=None):
+        """K fused steps under the on-device two-hidden-layer policy (mgym_rollout_mlp2): `policy` = the packed host floats of pack_mlp2 (or None, which the
+        engine rejects), `activation` = "relu" / "tanh_fast" or the MGYM_ACT_* value (the exact tanh is refused), `head` = "greedy" (argmax / the score), "sample"
+        (the draw of rollout_mlp_sample; discrete families) or "gauss" (mu + sigma * z of rollout_mlp_gauss; MountainCarContinuous, Pendulum) or the MGYM_HEAD_*
+        value.  sigma, seed and call are ignored by the heads that do not use them.  A policy of the wrong length for (H1, H2) raises PolicyShapeError."""
+        act = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH, "tanh_fast": L.ACT_TANH_FAST}.get(activation, activation)
+        hd = {"greedy": L.HEAD_GREEDY, "sample": L.HEAD_SAMPLE, "gauss": L.HEAD_GAUSS}.get(head, head)
+        if not isinstance(act, (int, np.integer)):
+            raise PolicyShapeError(L.ERR_BAD_ARG, f'activation must be "relu", "tanh_fast" or an MGYM_ACT_* value, got {activation!r}')
+        if not isinstance(hd, (int, np.integer)):
+            raise PolicyShapeError(L.ERR_BAD_ARG, f'head must be "greedy", "sample", "gauss" or an MGYM_HEAD_* value, got {head!r}')
+        pol = None
+        if policy is not None:
+            D, A = self.mlp_dims()
+            h1, h2 = int(hidden1), int(hidden2)
+            pol = np.ascontiguousarray(np.asarray(policy, np.float32).ravel())
+            want = h1 * (D + 1) + h2 * (h1 + 1) + A * (h2 + 1)
+            if 1 <= h1 <= 64 and 1 <= h2 <= 64 and pol.size != want:
+                raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {want} floats for hidden1 = {h1}, hidden2 = {h2}, got {pol.size}")
+        _check(self._lib.mgym_rollout_mlp2(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden1), int(hidden2), int(act), int(hd),
+                                           float(sigma), int(seed) & (2**64 - 1), int(call) & 0xFFFFFFFF, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out),
+                                           _ptr(done_out), _ptr(trunc_out)))
+
+    def rollout_mlp2(self, w1, b1, w2, b2, w3, b3, K, activation="relu", head="greedy", sigma=0.0, seed=0, call=0):
+        """host-array form of rollout_mlp2_device: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc); actions float32 for the continuous families"""
+        policy, H1, H2 = self.pack_mlp2(w1, b1, w2, b2, w3, b3)
+        return self._rollout_host(K, lambda *out: self.rollout_mlp2_device(policy, H1, H2, activation, head, sigma, seed, call, K, *out), self.action_dtype)
+
     def rollout_uniform(self, policy_seed, K):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""
         return self._rollout_host(K, lambda *out: self.rollout_uniform_device(policy_seed, K, *out))

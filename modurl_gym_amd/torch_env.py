@@ -196,6 +196,19 @@ class TorchVecEnv:
         self.env.rollout_mlp_gauss_device(policy, H, activation, float(sigma), seed, call, K, act, obs, rew, done, trunc)
         return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
 
+    def rollout_mlp2(self, w1, b1, w2, b2, w3, b3, K, activation="relu", head="greedy", sigma=0.0, seed=0, call=0):
+        """K fused steps under the on-device two-hidden-layer policy (mgym_rollout_mlp2): the six tensors (or arrays) of nn.Sequential(Linear(D, H1), act,
+        Linear(H1, H2), act, Linear(H2, A)) in nn.Linear layout, read on the host during the call; activation "relu" or "tanh_fast"; head "greedy", "sample" (the
+        discrete families: the draw of rollout_mlp_sample) or "gauss" (MountainCarContinuous, Pendulum: mu + sigma * z of rollout_mlp_gauss).  Pass a new `call`
+        for each call that is to draw afresh.  Returns (actions, obs, reward, done, truncated) like rollout_mlp."""
+        self._bind_stream()
+        host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2, w3, b3)]
+        policy, H1, H2 = self.env.pack_mlp2(*host)
+        K = int(K)
+        act, obs, rew, done, trunc = self._policy_outputs(K)
+        self.env.rollout_mlp2_device(policy, H1, H2, activation, head, float(sigma), seed, call, K, act, obs, rew, done, trunc)
+        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+
     def rollout_uniform(self, seed, K):
         """K fused steps under the on-device uniform random policy (mgym_rollout_uniform, include/mgym.h): returns (actions, obs, reward,
         done, truncated) like rollout_linear."""

@@ -30,6 +30,9 @@ pub const MGYM_FLAG_AUTO_RESET: u32 = 1;
 pub const MGYM_ACT_RELU: i32 = 0;
 pub const MGYM_ACT_TANH: i32 = 1;
 pub const MGYM_ACT_TANH_FAST: i32 = 3; // 2 is not assigned
+pub const MGYM_HEAD_GREEDY: i32 = 0;
+pub const MGYM_HEAD_SAMPLE: i32 = 1;
+pub const MGYM_HEAD_GAUSS: i32 = 2;
 
 pub const MGYM_MATH_SINF: c_int = 0;
 pub const MGYM_MATH_COSF: c_int = 1;
@@ -153,6 +156,23 @@ unsafe extern "C" {
         policy: *const f32,
         hidden: i32,
         activation: i32,
+        sigma: f32,
+        policy_seed: u64,
+        policy_call: u32,
+        k: i32,
+        actions_out: *mut c_void,
+        obs_out: *mut f32,
+        reward_out: *mut f32,
+        done_out: *mut u8,
+        trunc_out: *mut u8,
+    ) -> c_int;
+    pub fn mgym_rollout_mlp2(
+        env: *mut mgym_env,
+        policy: *const f32,
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        head: i32,
         sigma: f32,
         policy_seed: u64,
         policy_call: u32,

@@ -258,6 +258,46 @@ impl VecGym {
         }
         check(unsafe { mgym_rollout_mlp_gauss(self.env, policy.as_ptr(), hidden, activation, sigma, policy_seed, policy_call, k, actions_out, obs, reward, done, truncated) })
     }
+    /// K fused steps under the on-device two-hidden-layer policy (`mgym_rollout_mlp2`): `policy` = `W1[H1][D], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A]`
+    /// (nn.Linear order), 1 <= `hidden1`, `hidden2` <= 64, `activation` = `MGYM_ACT_RELU` or `MGYM_ACT_TANH_FAST` (the exact tanh is refused), `head` =
+    /// `MGYM_HEAD_GREEDY`, `MGYM_HEAD_SAMPLE` (discrete families) or `MGYM_HEAD_GAUSS` (MountainCarContinuous, Pendulum).  `sigma`, `policy_seed` and
+    /// `policy_call` are ignored by the heads that do not use them; a drawing head needs `env_id_base` a multiple of 4.
+    /// # Safety
+    /// the output pointers are device pointers of `[K][n]` (`[K][obs_dim][n]` for `obs`) elements, or null.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn rollout_mlp2(
+        &mut self,
+        policy: &[f32],
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        head: i32,
+        sigma: f32,
+        policy_seed: u64,
+        policy_call: u32,
+        k: i32,
+        actions_out: *mut c_void,
+        obs: *mut f32,
+        reward: *mut f32,
+        done: *mut u8,
+        truncated: *mut u8,
+    ) -> Result<(), MgymError> {
+        let d = self.spec.obs_dim as usize;
+        let a = if self.spec.action_is_float != 0 { 1 } else { self.spec.n_actions as usize };
+        if (1..=64).contains(&hidden1) && (1..=64).contains(&hidden2) {
+            let (h1, h2) = (hidden1 as usize, hidden2 as usize);
+            let want = h1 * (d + 1) + h2 * (h1 + 1) + a * (h2 + 1);
+            if policy.len() != want {
+                return Err(MgymError {
+                    status: MGYM_ERR_BAD_ARG,
+                    message: format!("rollout_mlp2: {} policy floats for hidden1 = {}, hidden2 = {}, got {}", want, hidden1, hidden2, policy.len()),
+                });
+            }
+        }
+        check(unsafe {
+            mgym_rollout_mlp2(self.env, policy.as_ptr(), hidden1, hidden2, activation, head, sigma, policy_seed, policy_call, k, actions_out, obs, reward, done, truncated)
+        })
+    }
     /// K fused steps under the on-device uniform random policy (`mgym_rollout_uniform`; every family, the draws as `include/mgym.h` documents them): no action table.
     /// `actions_out` (`[K][n]` u32, may be null) receives the drawn actions.
     #[allow(clippy::too_many_arguments)]
