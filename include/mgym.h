@@ -527,6 +527,65 @@ int mgym_rollout_mlp2(mgym_env *env, const float *policy, int32_t hidden1, int32
  * deterministic and can be checked word for word against a handle without auto-reset. */
 int mgym_set_final_obs_out(mgym_env *env, float *final_obs_out, int32_t steps_cap);
 
+/* Generalised advantage estimation over the outputs of a K-step rollout: one launch, a reverse scan per environment.  A pure function of its arguments: the
+ * handle supplies only the device, the stream and n_envs; every kind is accepted and no state of the handle is read or written.  All pointers are DEVICE
+ * pointers; nothing is allocated or synchronised, so the call is capturable (mgym_graph_begin or an external capture).
+ *   reward, done, trunc   [K][n_envs], the rollout's outputs; done / trunc may be NULL = all 0
+ *   value                 [K][n_envs]: V of the observation each env held BEFORE step t (the one the policy acted on)
+ *   last_value            [n_envs]: V of the observation held after the last step (obs_out[K-1])
+ *   final_value           [K][n_envs] or NULL: V(final observation, mgym_set_final_obs_out), used ONLY where trunc != 0 && done == 0
+ *   adv_out, ret_out      [K][n_envs] each; either may be NULL, not both
+ * The words, for environment i.  All arithmetic is f32; fmaf is one correctly rounded fused multiply-add; nothing else is fused or reassociated.
+ *
+ *   gl = gamma * lambda                       one f32 multiply, on the host
+ *   carry = +0.0f;  nxt = last_value[i]
+ *   for t = K-1 down to 0:
+ *       d = done[t][i] != 0;  u = trunc[t][i] != 0;  fin = d | u
+ *       nv    = fin ? (d ? +0.0f : (final_value ? final_value[t][i] : +0.0f)) : nxt
+ *       c     = fin ? +0.0f : carry
+ *       delta = fmaf(gamma, nv, reward[t][i]) - value[t][i]
+ *       adv   = fmaf(gl, c, delta)
+ *       adv_out[t][i] = adv;   ret_out[t][i] = adv + value[t][i]
+ *       carry = adv;  nxt = value[t][i]
+ *
+ * (modurl_gym_amd/csrc/gae.h is this text as the kernels and a g++ build compile it.)
+ *  - done wins over trunc: a terminated episode has no future, also when both flags are set.
+ *  - The three ?: are selections, not multiplications by a mask.  A word that is not selected cannot reach any result, whatever it holds: final_value where
+ *    the episode did not end by truncation alone (the final-observation buffer holds whatever the caller filled it with there), nxt and carry across an
+ *    episode end.  A NaN there leaves every output finite.  (The kernels load final_value only where it is selected.)
+ *  - final_value == NULL treats truncation as termination (LunarLander has no other form yet).
+ *  - lambda = 1 with value = 0 gives discounted returns-to-go; lambda = 0 gives the one-step TD error.
+ * Four environments per lane and 16-byte accesses when n_envs is a multiple of 4, the float pointers are 16-byte aligned and the flag pointers 4-byte
+ * aligned; otherwise one environment per lane.  The words are the same.
+ * MGYM_ERR_BAD_ARG before any launch, the message naming the argument: K < 1; a NULL reward, value or last_value; adv_out and ret_out both NULL; gamma or
+ * lambda NaN or outside [0, 1]; a float pointer that is not 4-byte aligned; an output pointer equal to an input pointer (overlap beyond pointer equality is
+ * the caller's error and undefined).  n_envs == 0 returns MGYM_OK without a launch. */
+int mgym_gae(mgym_env *env, int32_t K, const float *reward, const uint8_t *done, const uint8_t *trunc, const float *value, const float *last_value,
+             const float *final_value, float gamma, float lambda, float *adv_out, float *ret_out);
+
+/* The return and length of every episode that ends inside a K-step rollout: one launch, a forward scan per environment whose carry the CALLER owns, so
+ * that episodes span calls.  A pure function of its arguments like mgym_gae (every kind, no handle state, capturable); all pointers are DEVICE pointers.
+ *   reward, done, trunc      [K][n_envs]; done / trunc may be NULL = all 0
+ *   ep_return, ep_length     [n_envs], IN and OUT: the return and length so far of the episode each environment is in
+ *   return_out, length_out   [K][n_envs] or NULL each: written ONLY where done | trunc
+ *
+ *   acc = ep_return[i];  len = ep_length[i]
+ *   for t = 0 .. K-1 ascending:
+ *       acc = acc + reward[t][i]     one f32 add;      len = len + 1   (u32)
+ *       if (done[t][i] != 0 || trunc[t][i] != 0):
+ *           return_out[t][i] = acc;  length_out[t][i] = len;  acc = +0.0f;  len = 0
+ *   ep_return[i] = acc;  ep_length[i] = len
+ *
+ *  - No other word of return_out / length_out is written: dense, sparsely written buffers like the final-observation channel, read where done | trunc is
+ *    set, for the reason given there (no atomics, no run-dependent order).
+ *  - The reward of the step that ends an episode belongs to that episode, as in the engine.
+ *  - Two calls of K1 and K2 steps leave the words of one call of K1 + K2 steps.
+ *  - The caller zeroes the carry where it resets environments by hand.  No sum across environments is returned: the learner masks and reduces.
+ * MGYM_ERR_BAD_ARG before any launch, the message naming the argument: K < 1; a NULL reward, ep_return or ep_length; a float or uint32 pointer that is not
+ * 4-byte aligned.  n_envs == 0 returns MGYM_OK without a launch. */
+int mgym_episode_returns(mgym_env *env, int32_t K, const float *reward, const uint8_t *done, const uint8_t *trunc, float *ep_return, uint32_t *ep_length,
+                         float *return_out, uint32_t *length_out);
+
 /* Number of env-steps of this handle that returned done or truncated since mgym_create (StepInfo.done / .truncated,
  * cartpole.rs:300-305): accumulated inside the step kernels by __ballot/popcount reductions of the done mask,
  * one fire-and-forget atomic per wave.  Synchronises the stream. */

@@ -102,6 +102,18 @@ class VecGym {
     // The final observations of auto-reset episodes (mgym_set_final_obs_out): a device buffer [steps_cap][obs_dim][n_envs], written by every stepping call
     // where done | truncated is set, with the observation the step produced before the fused reset; nullptr turns the channel off.
     void set_final_obs_out(float* final_obs_out, int32_t steps_cap) { check(mgym_set_final_obs_out(env_, final_obs_out, steps_cap)); }
+    // Generalised advantage estimation over a rollout's [K][n_envs] outputs in one launch (mgym_gae): device pointers; done / trunc / final_value may be
+    // nullptr, and one of adv_out / ret_out; final_value is read only where trunc && !done
+    void gae(int K, const float* reward, const uint8_t* done, const uint8_t* trunc, const float* value, const float* last_value, const float* final_value,
+             float gamma, float lambda, float* adv_out, float* ret_out) {
+        check(mgym_gae(env_, K, reward, done, trunc, value, last_value, final_value, gamma, lambda, adv_out, ret_out));
+    }
+    // The return and length of the episodes that end inside a rollout (mgym_episode_returns): ep_return / ep_length [n_envs] are the caller's carry of the
+    // running episodes (read and written); return_out / length_out [K][n_envs] (or nullptr) are written only where done | trunc
+    void episode_returns(int K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length, float* return_out,
+                         uint32_t* length_out) {
+        check(mgym_episode_returns(env_, K, reward, done, trunc, ep_return, ep_length, return_out, length_out));
+    }
     uint32_t max_episode_steps() const { return cfg_.max_episode_steps; }
     const float* observation(uint64_t* col_stride) {
         const float* p = nullptr;

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "common.h"
+#include "gae.h"
 #include "time_limit.h"
 
 namespace mgym {
@@ -420,6 +421,44 @@ int mgym_set_final_obs_out(mgym_env* env, float* final_obs_out, int32_t steps_ca
     e->final_obs = final_obs_out;
     e->final_cap = final_obs_out ? steps_cap : 0;
     return MGYM_OK;
+}
+
+int mgym_gae(mgym_env* env, int32_t K, const float* reward, const uint8_t* done, const uint8_t* trunc, const float* value, const float* last_value,
+             const float* final_value, float gamma, float lambda, float* adv_out, float* ret_out) {
+    ENV_OR_FAIL(env);
+    if (K < 1) return bad_arg("mgym_gae: K must be at least 1");
+    if (!reward) return bad_arg("mgym_gae: reward is NULL");
+    if (!value) return bad_arg("mgym_gae: value is NULL");
+    if (!last_value) return bad_arg("mgym_gae: last_value is NULL");
+    if (!adv_out && !ret_out) return bad_arg("mgym_gae: adv_out and ret_out are both NULL");
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return bad_arg("mgym_gae: gamma must lie in [0, 1]");   // (a NaN fails the test)
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return bad_arg("mgym_gae: lambda must lie in [0, 1]");
+    const struct { const char* name; const float* p; bool out; } fp[] = {{"reward", reward, false}, {"value", value, false}, {"last_value", last_value, false},
+                                                                         {"final_value", final_value, false}, {"adv_out", adv_out, true}, {"ret_out", ret_out, true}};
+    for (const auto& f : fp)
+        if (!aligned(f.p, 4)) return bad_arg((std::string("mgym_gae: ") + f.name + " must be 4-byte aligned").c_str());
+    const struct { const char* name; const void* p; } in[] = {{"reward", reward}, {"done", done}, {"trunc", trunc}, {"value", value}, {"last_value", last_value},
+                                                              {"final_value", final_value}};
+    for (const auto& f : fp)
+        for (const auto& g : in)
+            if (f.out && f.p && f.p == g.p) return bad_arg((std::string("mgym_gae: ") + f.name + " is the same pointer as " + g.name).c_str());
+    if (e->n == 0) return MGYM_OK;
+    return gae_launch(e->stream, GaeCall{e->n, K, reward, done, trunc, value, last_value, final_value, gamma, gamma * lambda, adv_out, ret_out});
+}
+
+int mgym_episode_returns(mgym_env* env, int32_t K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length,
+                         float* return_out, uint32_t* length_out) {
+    ENV_OR_FAIL(env);
+    if (K < 1) return bad_arg("mgym_episode_returns: K must be at least 1");
+    if (!reward) return bad_arg("mgym_episode_returns: reward is NULL");
+    if (!ep_return) return bad_arg("mgym_episode_returns: ep_return is NULL");
+    if (!ep_length) return bad_arg("mgym_episode_returns: ep_length is NULL");
+    const struct { const char* name; const void* p; } wp[] = {{"reward", reward}, {"ep_return", ep_return}, {"ep_length", ep_length}, {"return_out", return_out},
+                                                              {"length_out", length_out}};
+    for (const auto& f : wp)
+        if (!aligned(f.p, 4)) return bad_arg((std::string("mgym_episode_returns: ") + f.name + " must be 4-byte aligned").c_str());
+    if (e->n == 0) return MGYM_OK;
+    return episode_returns_launch(e->stream, EpCall{e->n, K, reward, done, trunc, ep_return, ep_length, return_out, length_out});
 }
 
 int mgym_episode_count(mgym_env* env, uint64_t* finished) {

@@ -347,6 +347,50 @@ class VecEnv:
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc)"""
         return self._rollout_host(K, lambda *out: self.rollout_uniform_device(policy_seed, K, *out))
 
+    def gae_device(self, K, reward, done, trunc, value, last_value, final_value, gamma, lam, adv_out=None, ret_out=None):
+        """mgym_gae on device buffers (pointers, DeviceArrays or tensors): reward / value [K, n], done / trunc uint8 [K, n] or None, last_value [n], final_value
+        [K, n] or None (read only where trunc && !done), adv_out / ret_out [K, n] (one may be None).  On the env's stream, nothing synchronised."""
+        _check(self._lib.mgym_gae(self._h, int(K), _ptr(reward), _ptr(done), _ptr(trunc), _ptr(value), _ptr(last_value), _ptr(final_value), float(gamma),
+                                  float(lam), _ptr(adv_out), _ptr(ret_out)))
+
+    def episode_returns_device(self, K, reward, done, trunc, ep_return, ep_length, return_out=None, length_out=None):
+        """mgym_episode_returns on device buffers: reward [K, n], done / trunc uint8 [K, n] or None, the caller's carry ep_return float32 [n] and ep_length
+        uint32 [n] (read and written), return_out / length_out [K, n] or None, written only where done | trunc.  On the env's stream, nothing synchronised."""
+        _check(self._lib.mgym_episode_returns(self._h, int(K), _ptr(reward), _ptr(done), _ptr(trunc), _ptr(ep_return), _ptr(ep_length), _ptr(return_out),
+                                              _ptr(length_out)))
+
+    def _dev(self, a, dtype, shape):
+        """a host array as a DeviceArray of the given shape (None stays None)"""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        assert a.shape == shape, (a.shape, shape)
+        return DeviceArray.from_numpy(a, self.device) if a.size else DeviceArray(1, dtype, self.device)
+
+    def gae(self, reward, done, trunc, value, last_value, final_value=None, gamma=0.99, lam=0.95):
+        """host-array form of gae_device: -> (adv [K, n], ret [K, n])"""
+        K, n = np.shape(reward)[0], self.n
+        r, v, fv = (self._dev(x, np.float32, (K, n)) for x in (reward, value, final_value))
+        d, u = (self._dev(None if x is None else np.asarray(x) != 0, np.uint8, (K, n)) for x in (done, trunc))
+        lv = self._dev(last_value, np.float32, (n,))
+        adv, ret = DeviceArray((K, max(n, 1)), np.float32, self.device), DeviceArray((K, max(n, 1)), np.float32, self.device)
+        self.gae_device(K, r, d, u, v, lv, fv, gamma, lam, adv, ret)
+        self.sync()
+        return tuple(x.numpy().reshape(-1)[: K * n].reshape(K, n) for x in (adv, ret))
+
+    def episode_returns(self, reward, done, trunc, ep_return=None, ep_length=None):
+        """host-array form of episode_returns_device: the carry in (None: zeros) -> (return_out [K, n] float32, length_out [K, n] uint32, both 0 where no
+        episode ended, and the carry out: ep_return [n], ep_length [n])"""
+        K, n = np.shape(reward)[0], self.n
+        r = self._dev(reward, np.float32, (K, n))
+        d, u = (self._dev(None if x is None else np.asarray(x) != 0, np.uint8, (K, n)) for x in (done, trunc))
+        acc = self._dev(np.zeros(n, np.float32) if ep_return is None else ep_return, np.float32, (n,))
+        length = self._dev(np.zeros(n, np.uint32) if ep_length is None else ep_length, np.uint32, (n,))
+        ret, ln = self._dev(np.zeros((K, n), np.float32), np.float32, (K, n)), self._dev(np.zeros((K, n), np.uint32), np.uint32, (K, n))
+        self.episode_returns_device(K, r, d, u, acc, length, ret, ln)
+        self.sync()
+        return (ret.numpy().reshape(-1)[: K * n].reshape(K, n), ln.numpy().reshape(-1)[: K * n].reshape(K, n), acc.numpy()[:n], length.numpy()[:n])
+
     def episode_count(self):
         """env-steps of this handle that returned done or truncated since creation (mgym_episode_count; synchronises)"""
         c = C.c_uint64()

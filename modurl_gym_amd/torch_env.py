@@ -65,6 +65,7 @@ class TorchVecEnv:
         if int(final_obs_steps) > 0:
             self.final_obs = torch.zeros((int(final_obs_steps), self.obs_dim, self.n), dtype=f32, device=self.device)
             self.env.set_final_obs_out_device(self.final_obs, int(final_obs_steps))
+        self._ep_return = self._ep_length = None   # the carry of episode_returns(), created by its first call
 
     # ---- plumbing -----------------------------------------------------------------------
     def _bind_stream(self):
@@ -110,6 +111,11 @@ class TorchVecEnv:
             if mask.dtype != torch.uint8 or tuple(mask.shape) != (self.n,) or mask.device != self.device:
                 raise ValueError("mask must be a uint8/bool tensor of shape [n] on the env's device")
             mask = mask.contiguous()
+        if self._ep_return is not None:   # (episode_returns() has been used: the episodes that are reset start from nothing)
+            if mask is None:
+                self._ep_return.zero_(), self._ep_length.zero_()
+            else:
+                self._ep_return.masked_fill_(mask != 0, 0.0), self._ep_length.masked_fill_(mask != 0, 0)
         self.env.reset_device(mask, self._obs)
         return self._obs_out()
 
@@ -227,6 +233,50 @@ class TorchVecEnv:
         if obs.dim() == 2:
             return self._torch.where(fin[None, :], self.final_obs[0], obs)
         return self._torch.where(fin[:, None, :], self.final_obs[: obs.shape[0]], obs)
+
+    def _kn(self, x, dtype, name, lead):
+        """x as a contiguous tensor of shape lead + (n,) and the given dtype on the env's device (bool flags are viewed as uint8); None stays None"""
+        torch = self._torch
+        if x is None:
+            return None
+        if x.dtype == torch.bool and dtype == torch.uint8:
+            x = x.view(torch.uint8)
+        if x.device != self.device or tuple(x.shape) != tuple(lead) + (self.n,):
+            raise ValueError(f"{name} must have shape {tuple(lead) + (self.n,)} on {self.device}, got {tuple(x.shape)} on {x.device}")
+        return x.to(dtype).contiguous()
+
+    def gae(self, reward, done, truncated, value, last_value, final_value=None, gamma=0.99, lam=0.95):
+        """Generalised advantage estimation over a rollout's outputs in one launch (mgym_gae, include/mgym.h, defined to the f32 word): reward / value [K, n],
+        done / truncated [K, n] bool or uint8 (or None), last_value [n] = V(obs[-1]), final_value [K, n] = V(final_obs[:K]) or None (truncation then counts as
+        termination); value[t] is V of the observation the policy acted on at step t.  final_value is read only where truncated & ~done, so the values of a
+        final-observation buffer's unwritten words never matter.  Returns fresh (adv, ret) [K, n] tensors on torch's current stream."""
+        torch = self._torch
+        self._bind_stream()
+        K = int(reward.shape[0])
+        f32, u8 = torch.float32, torch.uint8
+        r, v, fv = (self._kn(x, f32, nm, (K,)) for x, nm in ((reward, "reward"), (value, "value"), (final_value, "final_value")))
+        d, u = self._kn(done, u8, "done", (K,)), self._kn(truncated, u8, "truncated", (K,))
+        lv = self._kn(last_value, f32, "last_value", ())
+        adv, ret = torch.empty((K, self.n), dtype=f32, device=self.device), torch.empty((K, self.n), dtype=f32, device=self.device)
+        self.env.gae_device(K, r, d, u, v, lv, fv, gamma, lam, adv, ret)
+        return adv, ret
+
+    def episode_returns(self, reward, done, truncated):
+        """The return and length of every episode that ended inside the rollout (mgym_episode_returns): (return_out float32 [K, n], length_out int32 [K, n]),
+        fresh tensors that are 0 except where done | truncated — `length_out > 0` is that mask.  The running episodes' carry lives in this object, created
+        zeroed by the first call, so episodes span calls; reset() zeroes it (reset(mask): where the mask is set)."""
+        torch = self._torch
+        self._bind_stream()
+        K = int(reward.shape[0])
+        r = self._kn(reward, torch.float32, "reward", (K,))
+        d, u = self._kn(done, torch.uint8, "done", (K,)), self._kn(truncated, torch.uint8, "truncated", (K,))
+        if self._ep_return is None:
+            self._ep_return = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+            self._ep_length = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        ret = torch.zeros((K, self.n), dtype=torch.float32, device=self.device)
+        length = torch.zeros((K, self.n), dtype=torch.int32, device=self.device)
+        self.env.episode_returns_device(K, r, d, u, self._ep_return, self._ep_length, ret, length)
+        return ret, length
 
     def elapsed_steps(self):
         """Caller-visible steps since each env's last reset (mgym_get_elapsed_steps; the count of `max_episode_steps`, which is passed

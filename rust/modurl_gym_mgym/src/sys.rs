@@ -213,6 +213,31 @@ unsafe extern "C" {
     pub fn mgym_get_elapsed_steps(env: *mut mgym_env, out: *mut u32) -> c_int;
     pub fn mgym_set_elapsed_steps(env: *mut mgym_env, input: *const u32) -> c_int;
     pub fn mgym_set_final_obs_out(env: *mut mgym_env, final_obs_out: *mut f32, steps_cap: i32) -> c_int;
+    pub fn mgym_gae(
+        env: *mut mgym_env,
+        k: i32,
+        reward: *const f32,
+        done: *const u8,
+        trunc: *const u8,
+        value: *const f32,
+        last_value: *const f32,
+        final_value: *const f32,
+        gamma: f32,
+        lambda: f32,
+        adv_out: *mut f32,
+        ret_out: *mut f32,
+    ) -> c_int;
+    pub fn mgym_episode_returns(
+        env: *mut mgym_env,
+        k: i32,
+        reward: *const f32,
+        done: *const u8,
+        trunc: *const u8,
+        ep_return: *mut f32,
+        ep_length: *mut u32,
+        return_out: *mut f32,
+        length_out: *mut u32,
+    ) -> c_int;
     pub fn mgym_reset_deterministic(env: *mut mgym_env, obs_out: *mut f32) -> c_int;
     pub fn mgym_set_dispersion_override(env: *mut mgym_env, disp: *const f32) -> c_int;
     pub fn mgym_get_spec(kind: c_int, spec: *mut mgym_spec) -> c_int;

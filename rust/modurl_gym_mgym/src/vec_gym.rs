@@ -354,6 +354,41 @@ impl VecGym {
     pub fn set_final_obs_out(&mut self, buf: Option<&mut DeviceBuf<f32>>, steps_cap: i32) -> Result<(), MgymError> {
         check(unsafe { mgym_set_final_obs_out(self.env, buf.map_or(std::ptr::null_mut(), |b| b.as_ptr()), steps_cap) })
     }
+    /// Generalised advantage estimation over a rollout's `[K][n]` outputs in one launch (`mgym_gae`, defined to the f32 word in `include/mgym.h`).  Device
+    /// pointers: `done` / `truncated` / `final_value` may be null, and one of `adv_out` / `ret_out`; `final_value` is read only where `truncated && !done`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn gae(
+        &mut self,
+        k: i32,
+        reward: *const f32,
+        done: *const u8,
+        truncated: *const u8,
+        value: *const f32,
+        last_value: *const f32,
+        final_value: *const f32,
+        gamma: f32,
+        lambda: f32,
+        adv_out: *mut f32,
+        ret_out: *mut f32,
+    ) -> Result<(), MgymError> {
+        check(unsafe { mgym_gae(self.env, k, reward, done, truncated, value, last_value, final_value, gamma, lambda, adv_out, ret_out) })
+    }
+    /// The return and length of the episodes that end inside a rollout (`mgym_episode_returns`): `ep_return` / `ep_length` are the caller's carry of the
+    /// running episodes (read and written); `return_out` / `length_out` (`[K][n]`, may be null) are written only where `done | truncated`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn episode_returns(
+        &mut self,
+        k: i32,
+        reward: *const f32,
+        done: *const u8,
+        truncated: *const u8,
+        ep_return: &mut DeviceBuf<f32>,
+        ep_length: &mut DeviceBuf<u32>,
+        return_out: *mut f32,
+        length_out: *mut u32,
+    ) -> Result<(), MgymError> {
+        check(unsafe { mgym_episode_returns(self.env, k, reward, done, truncated, ep_return.as_ptr(), ep_length.as_ptr(), return_out, length_out) })
+    }
     pub fn reset_deterministic(&mut self, obs_out: &mut DeviceBuf<f32>) -> Result<(), MgymError> {
         check(unsafe { mgym_reset_deterministic(self.env, obs_out.as_ptr()) })
     }
