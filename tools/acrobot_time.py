@@ -3,9 +3,9 @@
 
     python tools/acrobot_time.py --repeats 5 --out profiles/acrobot_time.json
 
-Both families at 1 048 576 envs, fused auto-reset on, max_episode_steps = 500 (gymnasium's limit for both ids), HIP-event timing on the handle's
-stream (torch events for the torch rows), a warm-up, windows of at least --window seconds, a fresh process per repeat with the order of the cases
-rotating.  Per family
+Both families at 1 048 576 envs, fused auto-reset on, max_episode_steps = 500 (gymnasium's limit for both ids); the timing is tools/timing.py's (the
+handle's timer, torch events for the torch rows, a warm-up of 2 launches and a probe of 4 — the engine rows after 20 launches more — and a fresh process
+per repeat).  Per family
     step           mgym_step from a ring of 64 rows of uniform random actions; obs_out NULL (the engine's columns are the observation), reward / done / truncated written
     rollout16      mgym_rollout, K = 16, the same ring, obs_out NULL
     mlp32, mlp64   mgym_rollout_mlp, K = 16, 32 / 64 ReLU units, actions_out and obs_out NULL
@@ -17,11 +17,10 @@ bytes per env-step — what the call must move, counted from its arguments, not 
 8 TB/s: a whole-call rate over peak bandwidth, not a kernel's share of peak.  Acrobot's step is four derivative evaluations and eight f64 sincos
 pairs per environment: which of arithmetic and traffic bounds it is read off that fraction beside CartPole's."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PEAK_BYTES_PER_S = 8e12
@@ -42,21 +41,12 @@ def worker(window, rotate, scale):
     sys.path.insert(0, ROOT)
     import numpy as np
     import modurl_gym_amd as mg
-    n = max(1024, int(N * scale)) // 1024 * 1024
+    n = timing.scaled(N, scale)
     kinds = {"cartpole": mg.CARTPOLE, "acrobot": mg.ACROBOT}
     n_act = {"cartpole": 2, "acrobot": 3}
 
     def weights(family, H):
-        D, A = mg.get_spec(kinds[family]).obs_dim, n_act[family]
-        w = np.random.default_rng(100 + H)
-        return (w.normal(0, 1, (H, D)).astype(np.float32), w.normal(0, 0.5, H).astype(np.float32), (w.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32),
-                w.normal(0, 0.1, A).astype(np.float32))
-
-    def window_of(timed):
-        timed(2)                                                   # warm-up
-        per = timed(4) / 4                                         # ms per call
-        count = max(4, int(window * 1000.0 / per) + 1)
-        return timed(count), count
+        return timing.mlp_weights(mg.get_spec(kinds[family]).obs_dim, n_act[family], H)
 
     def engine(family, case):
         rng = np.random.default_rng(1)
@@ -87,54 +77,40 @@ def worker(window, rotate, scale):
         env.reset_device()
         env.sync()
 
-        def timed(count):
-            env.timer_start()
-            for _ in range(count):
-                launch()
-            ms = env.timer_stop()
-            env.sync()   # (raises on a sticky device error)
-            return ms
-
+        timed = timing.engine_timed(env, launch)
         timed(20)
-        ms, count = window_of(timed)
+        ms, count = timing.window_of(timed, window, 2, 4)
         episodes = env.episode_count()
         env.close()
         return ms, count, k, episodes
 
     def torch_loop(family, case):
-        import torch
         env = mg.TorchVecEnv(kinds[family], n, seed=7, auto_reset=True, obs_layout="aos", max_episode_steps=LIMIT)
-        w1, b1, w2, b2 = (torch.from_numpy(x).cuda() for x in weights(family, 32))
-        w1t, w2t = w1.t().contiguous(), w2.t().contiguous()
-        state = [env.reset()]
-
-        def timed(count):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            obs = state[0]
-            e0.record()
-            for _ in range(count * K):
-                s = torch.addmm(b2, torch.relu(torch.addmm(b1, obs, w1t)), w2t)
-                if case == "torch32":
-                    a = torch.argmax(s, 1).to(torch.int32)
-                else:
-                    a = torch.multinomial(torch.softmax(s, 1), 1).squeeze(1).to(torch.int32)
-                obs = env.step(a)[0]
-            e1.record()
-            e1.synchronize()
-            env.check()
-            state[0] = obs
-            return e0.elapsed_time(e1)
-
-        ms, count = window_of(timed)
+        head = timing.torch_heads()["greedy" if case == "torch32" else "sample"]
+        ms, count = timing.window_of(timing.torch_policy_timed(env, weights(family, 32), "relu", head, K), window, 2, 4)
         return ms, count, K, None
 
     cases = [(f, c) for f in kinds for c in ENGINE_CASES + ("torch32", "torch_sample32")]
-    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
-    for family, case in cases:
+    for family, case in timing.rotated(cases, rotate):
         ms, count, k, episodes = (torch_loop if case.startswith("torch") else engine)(family, case)
         out.append(dict(family=family, case=case, n_envs=n, K=k, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * k * n), episodes=episodes))
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
+
+
+def record(runs, args):
+    """the whole document, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"{rec['family']}/{rec['case']}"), "count")
+    for key, row in table.items():
+        family, case = key.split("/")
+        row.update(env_steps_per_s=1e9 / row["median"])
+        if case in ENGINE_CASES:
+            b = algorithmic_bytes(family, case)
+            row.update(algorithmic_bytes_per_env_step=b, fraction_of_8TBps=b * 1e9 / row["median"] / PEAK_BYTES_PER_S)
+    return dict(unit="ns per env-step", n_envs=timing.scaled(N, args.scale), K=K, max_episode_steps=LIMIT, window_s=args.window,
+                repeats=args.repeats, scale=args.scale, peak_bytes_per_s=PEAK_BYTES_PER_S,
+                note="whole-call rates (events round the launches of a window); the bytes are algorithmic, counted from the arguments; spread = (max - min) / median",
+                summary=table, runs=runs)
 
 
 def main():
@@ -147,36 +123,12 @@ def main():
     args = ap.parse_args()
     if args.worker:
         return worker(args.window, int(args.worker[0]), args.scale)
-    runs = []
-    for rep in range(args.repeats):
-        # a fresh child per repeat, both families in it; the parent never opens the GPU
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", str(rep), "--window", str(args.window), "--scale", str(args.scale)],
-                           capture_output=True, text=True, timeout=900)
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-        if r.returncode != 0 or not line:
-            print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-            raise SystemExit(f"worker repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-        runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
-        print(f"repeat {rep}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        summary.setdefault((rec["family"], rec["case"]), []).append(rec["ns_per_env_step"])
-    table = {}
-    for (family, case), v in sorted(summary.items()):
-        med = statistics.median(v)
-        row = dict(median=med, min=min(v), max=max(v), spread=(max(v) - min(v)) / med, repeats=len(v), env_steps_per_s=1e9 / med)
-        if case in ENGINE_CASES:
-            b = algorithmic_bytes(family, case)
-            row.update(algorithmic_bytes_per_env_step=b, fraction_of_8TBps=b * 1e9 / med / PEAK_BYTES_PER_S)
-        table[f"{family}/{case}"] = row
-    doc = dict(unit="ns per env-step", n_envs=max(1024, int(N * args.scale)) // 1024 * 1024, K=K, max_episode_steps=LIMIT, window_s=args.window,
-               repeats=args.repeats, scale=args.scale, peak_bytes_per_s=PEAK_BYTES_PER_S,
-               note="whole-call rates (events round the launches of a window); the bytes are algorithmic, counted from the arguments; spread = (max - min) / median",
-               summary=table, runs=runs)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    for k_, v in table.items():
+    # both families in one child
+    runs = timing.run_children(lambda _, rep: [os.path.abspath(__file__), "--worker", str(rep), "--window", str(args.window), "--scale", str(args.scale)],
+                               [None], args.repeats, 900)
+    doc = record(runs, args)
+    timing.write_json(args.out, doc)
+    for k_, v in doc["summary"].items():
         extra = f"  {v['algorithmic_bytes_per_env_step']:.2f} B  {100 * v['fraction_of_8TBps']:.1f} % of 8 TB/s" if "fraction_of_8TBps" in v else ""
         print(f"{k_:32s} median {v['median']:.5f} ns  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s{extra}")
 

@@ -4,8 +4,8 @@ tree's with the channel set, in the same run, fresh processes, the order rotatin
 
     python tools/final_obs_time.py --base path/to/parent/libmgym.so --repeats 5 --out profiles/final_obs_time.json
 
-Cases, all at 1 048 576 envs with fused auto-reset (HIP-event timing on the handle's stream as bench.py does, a warm-up, windows of at least
---window seconds):
+Cases, all at 1 048 576 envs with fused auto-reset (the timing is tools/timing.py's: the handle's timer, a warm-up of 30 launches and a probe of 20, a
+fresh process per row and repeat):
     cartpole/step            mgym_step, a ring of 64 rows of uniform random actions
     cartpole/uniform16       mgym_rollout_uniform, K = 16
     mountain_car/uniform16   mgym_rollout_uniform, K = 16, max_episode_steps = 200
@@ -15,11 +15,10 @@ the parent's own repeats, (max - min) / median; the channel-set row is recorded 
 the channel wrote per env-step (4 obs_dim per finished env-step; at most 32 obs_dim where every 4-byte store dirties a 32-byte sector of its own).
 One JSON document: every repeat, and per case and row median, min, max and spread."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RING, K, HIDDEN = 64, 16, 32
@@ -41,7 +40,7 @@ def worker(lib_path, with_channel, window, scale):
         del _lib.PROTOTYPES[name]           # a base library from before mgym_set_final_obs_out
     import modurl_gym_amd as mg
     rng = np.random.default_rng(1)
-    n = max(1024, int((1 << 20) * scale)) // 1024 * 1024
+    n = timing.scaled(1 << 20, scale)
     out = []
     for case in CASES:
         family, form = case.split("/")
@@ -72,17 +71,8 @@ def worker(lib_path, with_channel, window, scale):
         env.reset_device()
         env.sync()
 
-        def timed(count):
-            env.timer_start()
-            for _ in range(count):
-                launch()
-            ms = env.timer_stop()
-            env.sync()   # (raises on a sticky device error)
-            return ms
-
-        timed(30)                                  # warm-up
-        per = timed(20) / 20                       # ms per launch
-        count = max(20, int(window * 1000.0 / per) + 1)
+        timed = timing.engine_timed(env, launch)
+        count = timing.calibrate(timed, window, 30, 20)
         before = env.episode_count()
         ms = timed(count)
         finished = env.episode_count() - before
@@ -93,7 +83,27 @@ def worker(lib_path, with_channel, window, scale):
         if with_channel:
             env.set_final_obs_out_device(None)
         env.close()
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
+
+
+def record(runs, args):
+    """the whole document, from the children's records and the command line alone"""
+    tags = [tag for tag in ("parent", "unset", "set") if any(r["row"] == tag for r in runs)]
+    summary = {}
+    for case in CASES:
+        per_row = {}
+        for tag in tags:
+            recs = [r for r in runs if r["case"] == case and r["row"] == tag]
+            per_row[tag] = timing.stats([r["ns_per_env_step"] for r in recs], "count")
+            for field in ("finished_share", "final_bytes_per_env_step", "final_sector_bytes_per_env_step_max"):
+                per_row[tag][field] = timing.median(r[field] for r in recs)
+        ref = per_row.get("parent", per_row["unset"])
+        for tag in per_row:
+            per_row[tag]["vs_" + ("parent" if "parent" in per_row else "unset")] = per_row[tag]["median"] / ref["median"] - 1.0
+        if "parent" in per_row:
+            per_row["unset_within_parent_spread"] = abs(per_row["unset"]["median"] - ref["median"]) <= ref["max"] - ref["min"]
+        summary[case] = per_row
+    return dict(unit="ns per env-step", window_s=args.window, repeats=args.repeats, scale=args.scale, hidden=HIDDEN, summary=summary, runs=runs)
 
 
 def main():
@@ -108,43 +118,16 @@ def main():
     if args.worker:
         return worker(args.worker[0], args.worker[1] == "1", args.window, args.scale)
     new_lib = os.path.join(ROOT, "modurl_gym_amd", "libmgym.so")
-    rows = ([("parent", os.path.abspath(args.base), "0")] if args.base else []) + [("unset", new_lib, "0"), ("set", new_lib, "1")]
-    runs = []
-    for rep in range(args.repeats):
-        order = rows[rep % len(rows):] + rows[:rep % len(rows)]   # the order rotates from repeat to repeat
-        for tag, path, with_channel in order:
-            # a fresh child per row and repeat: one process holds one build of the library, and the parent never opens the GPU
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", path, with_channel, "--window", str(args.window), "--scale", str(args.scale)],
-                               capture_output=True, text=True, timeout=600)
-            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-            if r.returncode != 0 or not line:
-                print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-                raise SystemExit(f"worker {tag} repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-            for rec in json.loads(line[0][7:]):
-                runs.append(dict(rec, row=tag, repeat=rep, position=[t for t, _, _ in order].index(tag)))
-            print(f"repeat {rep} {tag}: done", flush=True)
-    summary = {}
-    for case in CASES:
-        per_row = {}
-        for tag, _, _ in rows:
-            recs = [r for r in runs if r["case"] == case and r["row"] == tag]
-            v = [r["ns_per_env_step"] for r in recs]
-            med = statistics.median(v)
-            per_row[tag] = dict(median=med, min=min(v), max=max(v), spread=(max(v) - min(v)) / med, repeats=len(v),
-                                finished_share=statistics.median(r["finished_share"] for r in recs),
-                                final_bytes_per_env_step=statistics.median(r["final_bytes_per_env_step"] for r in recs),
-                                final_sector_bytes_per_env_step_max=statistics.median(r["final_sector_bytes_per_env_step_max"] for r in recs))
-        ref = per_row.get("parent", per_row["unset"])
-        for tag in per_row:
-            per_row[tag]["vs_" + ("parent" if "parent" in per_row else "unset")] = per_row[tag]["median"] / ref["median"] - 1.0
-        if "parent" in per_row:
-            per_row["unset_within_parent_spread"] = abs(per_row["unset"]["median"] - ref["median"]) <= ref["max"] - ref["min"]
-        summary[case] = per_row
-    doc = dict(unit="ns per env-step", window_s=args.window, repeats=args.repeats, scale=args.scale, hidden=HIDDEN, summary=summary, runs=runs)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    for case, per_row in summary.items():
+    rows = {"unset": (new_lib, "0"), "set": (new_lib, "1")}                  # row: (library, channel set)
+    if args.base:
+        rows = {"parent": (os.path.abspath(args.base), "0"), **rows}
+    # one process holds one build of the library; the order of the rows rotates from repeat to repeat
+    runs = timing.run_children(lambda tag, rep: [os.path.abspath(__file__), "--worker", *rows[tag], "--window", str(args.window), "--scale", str(args.scale)],
+                               lambda rep: timing.rotated(list(rows), rep), args.repeats, 600,
+                               fields=lambda tag, rep, position: dict(row=tag, repeat=rep, position=position))
+    doc = record(runs, args)
+    timing.write_json(args.out, doc)
+    for case, per_row in doc["summary"].items():
         for tag, v in per_row.items():
             if isinstance(v, dict):
                 print(f"{case:24s} {tag:7s} median {v['median']:.4f}  min {v['min']:.4f}  max {v['max']:.4f}  spread {100 * v['spread']:.2f} %  finished {100 * v['finished_share']:.2f} %")

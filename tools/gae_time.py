@@ -3,10 +3,9 @@
 
     python tools/gae_time.py --repeats 5 --out profiles/gae_time.json
 
-The timing scheme is that of tools/mlp2_time.py (device events around a window of back-to-back calls after a warm-up, a fresh process per repeat with every case
-in it, the cases in an order that rotates with the repeat, median / min / max / spread over the repeats).  Rows: 1 048 576 and 4 096 environments, K = 16 and
-128.  Inputs are synthetic device tensors (rewards in [-16, 1], values in +-100, done and truncated at a rate of 0.02 each), every output preallocated.  Columns,
-ns per env-step, all in one process:
+The timing is tools/timing.py's (torch events around a window of back-to-back calls, a warm-up and a probe of 3 calls each, a fresh process per repeat with
+every case in it).  Rows: 1 048 576 and 4 096 environments, K = 16 and 128.  Inputs are synthetic device tensors (rewards in [-16, 1], values in +-100, done
+and truncated at a rate of 0.02 each), every output preallocated.  Columns, ns per env-step, all in one process:
     gae            mgym_gae with done, trunc and final_value, both outputs
     returns        mgym_episode_returns with done and trunc, both outputs
     torch_gae      the reverse loop of INTEGRATION.md section 3 written with torch.where (the same selections), K iterations
@@ -16,16 +15,12 @@ and nothing for the sparse final_value; returns: 6 + 16 / K, plus nothing for th
 holds launch gaps too.
 Not measured here: hardware counters, other sizes, a training loop."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from mlp_policy_time import write_record  # noqa: E402
+import timing
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ENVS = (1 << 20, 4096)
 KS = (16, 128)
 GAMMA, LAM, RATE = 0.99, 0.95, 0.02
@@ -41,26 +36,14 @@ def worker(scale, window, rotate):
     import torch
     import modurl_gym_amd as mg
 
-    def window_of(timed):
-        timed(3)                                        # warm-up
-        per = timed(3) / 3                              # ms per call
-        count = max(3, int(window * 1000.0 / per) + 1)
-        return timed(count), count
+    def window_of(body):
+        return timing.window_of(timing.torch_timed(body), window, 3, 3)
 
     def inputs(n, K):
         g = torch.Generator(device="cuda").manual_seed(1234 + K)
         u01 = lambda *s: torch.rand(*s, device="cuda", generator=g)
         rew, val, fv = u01(K, n) * 17 - 16, u01(K, n) * 200 - 100, u01(K, n) * 200 - 100
         return dict(rew=rew, val=val, fv=fv, last=u01(n) * 200 - 100, done=u01(K, n) < RATE, trunc=u01(K, n) < RATE)
-
-    def events(body, count):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(count):
-            body()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
 
     def fused(what, n, K):
         x = inputs(n, K)
@@ -74,7 +57,7 @@ def worker(scale, window, rotate):
             acc, ln = torch.zeros(n, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")
             ro, lo = torch.zeros_like(x["rew"]), torch.zeros((K, n), dtype=torch.int32, device="cuda")
             body = lambda: env.env.episode_returns_device(K, x["rew"], d8, u8, acc, ln, ro, lo)
-        out = window_of(lambda count: events(body, count))
+        out = window_of(body)
         env.check()
         env.close()
         return out
@@ -94,7 +77,7 @@ def worker(scale, window, rotate):
                 adv[t] = a
                 torch.add(a, v, out=ret[t])
                 carry, nxt = a, v
-        return window_of(lambda count: events(body, count))
+        return window_of(body)
 
     def torch_returns(n, K):
         x = inputs(n, K)
@@ -111,54 +94,29 @@ def worker(scale, window, rotate):
                 torch.where(fin, ln, izero, out=lo[t])
                 acc, ln = torch.where(fin, zero, acc), torch.where(fin, izero, ln)
             carry[0], carry[1] = acc, ln
-        return window_of(lambda count: events(body, count))
+        return window_of(body)
 
     cases = []
     for n0 in N_ENVS:
-        n = max(1024, int(n0 * scale)) // 1024 * 1024
+        n = timing.scaled(n0, scale)
         for K in KS:
             cases.append((n, K, "gae", lambda n=n, K=K: fused("gae", n, K)))
             cases.append((n, K, "returns", lambda n=n, K=K: fused("returns", n, K)))
             cases.append((n, K, "torch_gae", lambda n=n, K=K: torch_gae(n, K)))
             cases.append((n, K, "torch_returns", lambda n=n, K=K: torch_returns(n, K)))
-    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
-    for n, K, name, run in cases:
+    for n, K, name, run in timing.rotated(cases, rotate):
         ms, count = run()
         out.append(dict(n_envs=n, K=K, case=name, calls=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n)))
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--window", type=float, default=0.2, help="seconds of timed work per case")
-    ap.add_argument("--scale", type=float, default=1.0, help="population scale (smoke runs)")
-    ap.add_argument("--out", required=True, help="record file (the committed record of the full run: profiles/gae_time.json)")
-    ap.add_argument("--worker", nargs=2, metavar=("SCALE", "ROTATE"))
-    args = ap.parse_args()
-    if args.worker:
-        return worker(float(args.worker[0]), args.window, int(args.worker[1]))
-    runs = []
-    for rep in range(args.repeats):
-        # a fresh child per repeat; the parent never opens the GPU
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", str(args.scale), str(5 * rep), "--window", str(args.window), "--out", args.out],
-                           capture_output=True, text=True, timeout=600)
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-        if r.returncode != 0 or not line:
-            print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-            raise SystemExit(f"worker repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-        runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
-        print(f"repeat {rep}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        summary.setdefault(f"n{rec['n_envs']}/K{rec['K']}/{rec['case']}", []).append(rec["ns_per_env_step"])
-    table = {}
-    for k, v in sorted(summary.items()):
-        med, K = statistics.median(v), int(k.split("/")[1][1:])
-        table[k] = dict(median=med, min=min(v), max=max(v), spread=(max(v) - min(v)) / med, env_steps_per_s=1e9 / med, repeats=[round(x, 6) for x in v])
+def record(runs, args):
+    """(head, table) of the record, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"n{rec['n_envs']}/K{rec['K']}/{rec['case']}"), "list")
+    for k, v in table.items():
         if not k.split("/")[2].startswith("torch"):
-            table[k]["share_of_8TBps"] = algorithmic_bytes(k, K) / (med * 1e-9) / PEAK_BYTES_PER_S
+            v["share_of_8TBps"] = algorithmic_bytes(k, int(k.split("/")[1][1:])) / (v["median"] * 1e-9) / PEAK_BYTES_PER_S
     ratios = {}
     for k, v in table.items():
         row, case = k.rsplit("/", 1)
@@ -173,11 +131,27 @@ def main():
                 algorithmic_bytes_per_env_step="gae 18 + 8 / K, returns 6 + 16 / K (sparse final_value reads and return_out / length_out writes not counted)",
                 share_of_8TBps="algorithmic bytes over whole-call time over 8e12 B/s: an end-to-end figure, launch gaps included, not a kernel's share of peak",
                 not_measured="hardware counters, other sizes, a training loop", ratios=ratios)
-    write_record(args.out, head, table)
+    return head, table
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.2, help="seconds of timed work per case")
+    ap.add_argument("--scale", type=float, default=1.0, help="population scale (smoke runs)")
+    ap.add_argument("--out", required=True, help="record file (the committed record of the full run: profiles/gae_time.json)")
+    ap.add_argument("--worker", nargs=2, metavar=("SCALE", "ROTATE"))
+    args = ap.parse_args()
+    if args.worker:
+        return worker(float(args.worker[0]), args.window, int(args.worker[1]))
+    runs = timing.run_children(lambda _, rep: [os.path.abspath(__file__), "--worker", str(args.scale), str(5 * rep), "--window", str(args.window), "--out", args.out],
+                               [None], args.repeats, 600)
+    head, table = record(runs, args)
+    timing.write_record(args.out, head, table)
     for k, v in table.items():
         share = f"  {100 * v['share_of_8TBps']:.1f} % of 8 TB/s" if "share_of_8TBps" in v else ""
         print(f"{k:36s} median {v['median']:.5f}  min {v['min']:.5f}  max {v['max']:.5f}  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s{share}")
-    for k, v in ratios.items():
+    for k, v in head["ratios"].items():
         print(f"{k:36s} torch / fused {v['torch_over_fused']:.1f}  faster beyond the spread: {v['faster_beyond_spread']}")
 
 

@@ -4,26 +4,21 @@ it replaces:
 
     python tools/mlp2_time.py --repeats 5 --out profiles/mlp2_time.json
 
-The timing scheme is that of tools/tanh_fast_time.py (HIP events, K = 16, fused auto-reset on, a fresh process per repeat with every case in it, the cases in an
-order that rotates with the repeat, median / min / max / spread over the repeats).  Rows: CartPole with the greedy and the sampling head, Pendulum
-(max_episode_steps = 200) with the Gaussian head; 1 048 576 and 4 096 envs; widths (32, 32) and (64, 64); ReLU and tanh_fast.  Columns, ns per env-step, all in
-one process:
+K = 16, fused auto-reset on; the timing is tools/timing.py's (a warm-up and a probe of 3 launches each, a fresh process per repeat with every case in it).
+Rows: CartPole with the greedy and the sampling head, Pendulum (max_episode_steps = 200) with the Gaussian head; 1 048 576 and 4 096 envs; widths (32, 32) and
+(64, 64); ReLU and tanh_fast.  Columns, ns per env-step, all in one process:
     mlp2    mgym_rollout_mlp2, one call per K steps (a new call word each where the head draws), actions not stored
     mlp1    the one-hidden-layer call with the same head at H = H1, for scale
     torch   the loop a trainer would run instead: TorchVecEnv with AoS observations; per step three torch.addmm with torch.relu / torch.tanh between them,
             then argmax / torch.multinomial of the softmax / mu + sigma * torch.randn, then TorchVecEnv.step
 Not measured here: hardware counters, other sizes or K, LunarLander, a training loop."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from mlp_policy_time import write_record  # noqa: E402
+import timing
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ENVS = (1 << 20, 4096)
 ROWS = [("cartpole", "greedy"), ("cartpole", "sample"), ("pendulum", "gauss")]
 IN_SCALE = {"cartpole": (1.0, 1.0, 8.0, 1.0), "pendulum": (1.0, 1.0, 0.3)}
@@ -36,7 +31,6 @@ SIGMA = 0.5
 def worker(scale, window, rotate, K, lib):
     sys.path.insert(0, ROOT)
     import numpy as np
-    import torch
     if lib:
         from modurl_gym_amd import _lib
         _lib.LIB_PATH = os.path.abspath(lib)   # before anything loads the library
@@ -50,12 +44,6 @@ def worker(scale, window, rotate, K, lib):
                 (rng.normal(0, 1, (H, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.5, H).astype(np.float32),
                 (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.1, A).astype(np.float32))
 
-    def window_of(timed):
-        timed(3)                                        # warm-up
-        per = timed(3) / 3                              # ms per launch of K steps
-        count = max(3, int(window * 1000.0 / per) + 1)
-        return timed(count), count
-
     def fused(family, head, n, H, act, layers):
         w = weights(family, H)
         env = mg.VecEnv(kinds[family], n, seed=7, auto_reset=True, max_episode_steps=LIMIT[family])
@@ -66,70 +54,58 @@ def worker(scale, window, rotate, K, lib):
         env.sync()
         calls = [0]
 
-        def timed(count):
-            env.timer_start()
-            for _ in range(count):
-                if layers == 2:
-                    env.rollout_mlp2_device(pol2, H, H, act, head, SIGMA, 9, calls[0], K, None, None, rew, done, trunc)
-                elif head == "greedy":
-                    env.rollout_mlp_device(pol1, H, act, K, None, None, rew, done, trunc)
-                elif head == "sample":
-                    env.rollout_mlp_sample_device(pol1, H, act, 9, calls[0], K, None, None, rew, done, trunc)
-                else:
-                    env.rollout_mlp_gauss_device(pol1, H, act, SIGMA, 9, calls[0], K, None, None, rew, done, trunc)
-                calls[0] += 1
-            ms = env.timer_stop()
-            env.sync()                                  # (raises on a sticky device error)
-            return ms
+        def launch():
+            if layers == 2:
+                env.rollout_mlp2_device(pol2, H, H, act, head, SIGMA, 9, calls[0], K, None, None, rew, done, trunc)
+            elif head == "greedy":
+                env.rollout_mlp_device(pol1, H, act, K, None, None, rew, done, trunc)
+            elif head == "sample":
+                env.rollout_mlp_sample_device(pol1, H, act, 9, calls[0], K, None, None, rew, done, trunc)
+            else:
+                env.rollout_mlp_gauss_device(pol1, H, act, SIGMA, 9, calls[0], K, None, None, rew, done, trunc)
+            calls[0] += 1
 
-        out = window_of(timed)
+        out = timing.window_of(timing.engine_timed(env, launch), window, 3, 3)
         env.close()
         return out
 
     def torch_loop(family, head, n, H, act):
         env = mg.TorchVecEnv(kinds[family], n, seed=7, auto_reset=True, obs_layout="aos", max_episode_steps=LIMIT[family])
-        w1, b1, w2, b2, w3, b3 = (torch.from_numpy(x).cuda() for x in weights(family, H))
-        w1t, w2t, w3t = w1.t().contiguous(), w2.t().contiguous(), w3.t().contiguous()
-        f = torch.relu if act == "relu" else torch.tanh
-        state = [env.reset()]
-
-        def timed(count):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            obs = state[0]
-            e0.record()
-            for _ in range(count * K):
-                s = torch.addmm(b3, f(torch.addmm(b2, f(torch.addmm(b1, obs, w1t)), w2t)), w3t)
-                if head == "greedy":
-                    a = s.argmax(1).to(torch.int32)
-                elif head == "sample":
-                    a = torch.multinomial(torch.softmax(s, 1), 1).squeeze(1).to(torch.int32)
-                else:
-                    a = s.squeeze(1) + SIGMA * torch.randn(n, device=s.device, dtype=torch.float32)
-                obs = env.step(a)[0]
-            e1.record()
-            e1.synchronize()
-            env.check()
-            state[0] = obs
-            return e0.elapsed_time(e1)
-
-        return window_of(timed)
+        return timing.window_of(timing.torch_policy_timed(env, weights(family, H), act, timing.torch_heads(SIGMA)[head], K), window, 3, 3)
 
     cases = []
     for family, head in ROWS:
         for n0 in N_ENVS:
-            n = max(1024, int(n0 * scale)) // 1024 * 1024
+            n = timing.scaled(n0, scale)
             for H in WIDTHS:
                 for act in ACTIVATIONS:
                     name = f"{head}/n{n}/{H}x{H}/{act}"
                     cases.append((family, n, name + "/mlp2", lambda f=family, h=head, n=n, H=H, a=act: fused(f, h, n, H, a, 2)))
                     cases.append((family, n, name + "/mlp1", lambda f=family, h=head, n=n, H=H, a=act: fused(f, h, n, H, a, 1)))
                     cases.append((family, n, name + "/torch", lambda f=family, h=head, n=n, H=H, a=act: torch_loop(f, h, n, H, a)))
-    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
-    for family, n, name, run in cases:
+    for family, n, name, run in timing.rotated(cases, rotate):
         ms, count = run()
         out.append(dict(family=family, n_envs=n, K=K, case=name, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n)))
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
+
+
+def record(runs, args):
+    """(head, table) of the record, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"{rec['family']}/{rec['case']}"), "list")
+    # each mlp2 row against the one-layer call and the torch loop of the same run
+    ratios = {}
+    for k, v in table.items():
+        if k.endswith("/mlp2"):
+            base = k[: -len("mlp2")]
+            ratios[k] = dict(torch_over_mlp2=table[base + "torch"]["median"] / v["median"], mlp2_over_mlp1=v["median"] / table[base + "mlp1"]["median"])
+    head = dict(unit="ns per env-step", K=args.K, window_s=args.window, repeats=args.repeats, scale=args.scale, sigma=SIGMA, n_envs=list(N_ENVS),
+                max_episode_steps=LIMIT, lib=os.path.basename(args.lib) if args.lib else "the package's",
+                cases="mlp2: mgym_rollout_mlp2; mlp1: the one-hidden-layer call with the same head at H = H1; torch: three addmm, two activations (torch.relu / torch.tanh), "
+                "argmax | multinomial(softmax) | mu + sigma * randn, step; all of a repeat in one process",
+                static_bound="157 TF / (2 x 4096 flop) = 1.9e10 env-steps/s at (64, 64)",
+                not_measured="hardware counters, other sizes or K, LunarLander, a training loop", ratios=ratios)
+    return head, table
 
 
 def main():
@@ -144,38 +120,13 @@ def main():
     args = ap.parse_args()
     if args.worker:
         return worker(float(args.worker[0]), args.window, int(args.worker[1]), args.K, args.lib)
-    runs = []
-    for rep in range(args.repeats):
-        # a fresh child per repeat; the parent never opens the GPU
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", str(args.scale), str(7 * rep), "--window", str(args.window), "--K", str(args.K),
-                            "--out", args.out, "--lib", args.lib], capture_output=True, text=True, timeout=900)
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-        if r.returncode != 0 or not line:
-            print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-            raise SystemExit(f"worker repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-        runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
-        print(f"repeat {rep}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        summary.setdefault(f"{rec['family']}/{rec['case']}", []).append(rec["ns_per_env_step"])
-    table = {k: dict(median=statistics.median(v), min=min(v), max=max(v), spread=(max(v) - min(v)) / statistics.median(v),
-                     env_steps_per_s=1e9 / statistics.median(v), repeats=[round(x, 6) for x in v]) for k, v in sorted(summary.items())}
-    # each mlp2 row against the one-layer call and the torch loop of the same run
-    ratios = {}
-    for k, v in table.items():
-        if k.endswith("/mlp2"):
-            base = k[: -len("mlp2")]
-            ratios[k] = dict(torch_over_mlp2=table[base + "torch"]["median"] / v["median"], mlp2_over_mlp1=v["median"] / table[base + "mlp1"]["median"])
-    head = dict(unit="ns per env-step", K=args.K, window_s=args.window, repeats=args.repeats, scale=args.scale, sigma=SIGMA, n_envs=list(N_ENVS),
-                max_episode_steps=LIMIT, lib=os.path.basename(args.lib) if args.lib else "the package's",
-                cases="mlp2: mgym_rollout_mlp2; mlp1: the one-hidden-layer call with the same head at H = H1; torch: three addmm, two activations (torch.relu / torch.tanh), "
-                "argmax | multinomial(softmax) | mu + sigma * randn, step; all of a repeat in one process",
-                static_bound="157 TF / (2 x 4096 flop) = 1.9e10 env-steps/s at (64, 64)",
-                not_measured="hardware counters, other sizes or K, LunarLander, a training loop", ratios=ratios)
-    write_record(args.out, head, table)
+    runs = timing.run_children(lambda _, rep: [os.path.abspath(__file__), "--worker", str(args.scale), str(7 * rep), "--window", str(args.window), "--K", str(args.K),
+                                               "--out", args.out, "--lib", args.lib], [None], args.repeats, 900)
+    head, table = record(runs, args)
+    timing.write_record(args.out, head, table)
     for k, v in table.items():
         print(f"{k:52s} median {v['median']:.4f}  min {v['min']:.4f}  max {v['max']:.4f}  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s")
-    for k, v in ratios.items():
+    for k, v in head["ratios"].items():
         print(f"{k:52s} torch / mlp2 {v['torch_over_mlp2']:.2f}  mlp2 / mlp1 {v['mlp2_over_mlp1']:.2f}")
 
 

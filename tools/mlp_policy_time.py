@@ -19,17 +19,14 @@ compares libraries or Ks is put together from the runs' files:
     python tools/mlp_policy_time.py --merge parent=a16.json after=b16.json parent=a64.json after=b64.json --out profiles/ll_mlp_rollout_time.json
 
 (rows "K<K>/<case>/<label>", the families' prefix dropped when every file holds one family).
-The weights are seeded normal draws scaled to the observation's range (the timing depends on them only through how often episodes end).  Timing: HIP
-events on the stream the work is issued on (the handle's own timer for (a) and (c), torch events on torch's current stream, which TorchVecEnv
-binds the handle to, for (b)), a warm-up, then a window of at least --window seconds.  Every repeat is a fresh process per family, the cases of a
-process in an order that rotates with the repeat; the summary gives median, min, max and spread ((max - min) / median) over the repeats — the
-spread is the noise figure every comparison is read against."""
+The timing is tools/timing.py's: the handle's own timer for (a), (c) and (d), torch events for (b), a warm-up and a probe of 5 launches each, a fresh
+process per family and repeat."""
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAMILIES = [("cartpole", 1 << 20), ("mountain_car", 1 << 20), ("lunar_lander", 1 << 18)]
@@ -39,71 +36,31 @@ IN_SCALE = {"cartpole": (2.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "luna
 def worker(family, n, window, rotate, K, only):
     sys.path.insert(0, ROOT)
     import numpy as np
-    import torch
     import modurl_gym_amd as mg
     kind = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "lunar_lander": mg.LUNARLANDER}[family]
     kw = dict(enable_wind=True) if family == "lunar_lander" else {}
     spec = mg.get_spec(kind)
     D, A = spec.obs_dim, spec.n_actions
 
-    def weights(H):
-        rng = np.random.default_rng(100 + H)
-        return ((rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[family])).astype(np.float32), rng.normal(0, 0.5, H).astype(np.float32),
-                (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.1, A).astype(np.float32))
-
-    def window_of(timed):
-        timed(5)                                        # warm-up
-        per = timed(5) / 5                              # ms per launch of K steps
-        count = max(5, int(window * 1000.0 / per) + 1)
-        return timed(count), count
-
     def fused(call):
         env = mg.VecEnv(kind, n, seed=7, auto_reset=True, **kw)
         rew, done, trunc = mg.DeviceArray((K, n), np.float32), mg.DeviceArray((K, n), np.uint8), mg.DeviceArray((K, n), np.uint8)
         env.reset_device()
         env.sync()
-
-        def timed(count):
-            env.timer_start()
-            for _ in range(count):
-                call(env, rew, done, trunc)
-            ms = env.timer_stop()
-            env.sync()                                  # (raises on a sticky device error)
-            return ms
-
-        ms, count = window_of(timed)
+        ms, count = timing.window_of(timing.engine_timed(env, lambda: call(env, rew, done, trunc)), window, 5, 5)
         info = env.info()
         env.close()
         return ms, count, info
 
     def torch_loop(H, act):
         env = mg.TorchVecEnv(kind, n, seed=7, auto_reset=True, obs_layout="aos", **kw)
-        w1, b1, w2, b2 = (torch.from_numpy(x).cuda() for x in weights(H))
-        w1t, w2t = w1.t().contiguous(), w2.t().contiguous()
-        fn = torch.relu if act == "relu" else torch.tanh
-        state = [env.reset()]
-
-        def timed(count):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            obs = state[0]
-            e0.record()
-            for _ in range(count * K):
-                h = fn(torch.addmm(b1, obs, w1t))
-                a = torch.addmm(b2, h, w2t).argmax(1).to(torch.int32)
-                obs = env.step(a)[0]
-            e1.record()
-            e1.synchronize()
-            env.check()
-            state[0] = obs
-            return e0.elapsed_time(e1)
-
-        ms, count = window_of(timed)
-        return ms, count, {}
+        timed = timing.torch_policy_timed(env, timing.mlp_weights(D, A, H, IN_SCALE[family]), act, timing.torch_heads()["greedy"], K)
+        return timing.window_of(timed, window, 5, 5) + ({},)
 
     cases = []
     for H in (32, 64):
         for act in ("relu", "tanh"):
-            w = weights(H)
+            w = timing.mlp_weights(D, A, H, IN_SCALE[family])
             pol = np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]])   # nn.Linear order: W1[H][D], b1[H], W2[A][H], b2[A]
             cases.append((f"mlp/H{H}/{act}", lambda pol=pol, H=H, act=act: fused(lambda env, r, d, t: env.rollout_mlp_device(pol, H, act, K, None, None, r, d, t))))
             cases.append((f"torch/H{H}/{act}", lambda H=H, act=act: torch_loop(H, act)))
@@ -114,22 +71,12 @@ def worker(family, n, window, rotate, K, only):
     cases.append(("uniform", lambda: fused(lambda env, r, d, t: env.rollout_uniform_device(9, K, None, None, r, d, t))))
     if only:
         cases = [c for c in cases if c[0].split("/")[0] in only]
-    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
-    for name, run in cases:
+    for name, run in timing.rotated(cases, rotate):
         ms, count, info = run()
         out.append(dict(family=family, n_envs=n, K=K, case=name, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n),
                         env_steps_per_s=count * K * n / (ms * 1e-3), rollout_form=info.get("rollout"), persistent_launches=info.get("rollout_persistent_launches")))
-    print("RESULT " + json.dumps(out), flush=True)
-
-
-def write_record(path, head, table):
-    """one line per case: the record stays readable in a diff"""
-    with open(path, "w") as f:
-        f.write("{\n")
-        for k, v in head.items():
-            f.write(f" {json.dumps(k)}: {json.dumps(v)},\n")
-        f.write(' "summary": {\n' + ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in table.items()) + "\n }\n}\n")
+    timing.emit(out)
 
 
 def merge(pairs, out):
@@ -141,7 +88,19 @@ def merge(pairs, out):
         one = len(rec["n_envs"]) == 1
         for k, v in rec["summary"].items():
             rows[f"K{rec['K']}/{k.split('/', 1)[1] if one else k}/{label}"] = v
-    write_record(out, dict(unit="ns per env-step", runs=heads), dict(sorted(rows.items())))
+    timing.write_record(out, dict(unit="ns per env-step", runs=heads), dict(sorted(rows.items())))
+
+
+def populations(args):
+    return {f: timing.scaled(n, args.scale) for f, n in FAMILIES if f in args.families.split(",")}
+
+
+def record(runs, args):
+    """(head, table) of the record, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"{rec['family']}/{rec['case']}"), "list")
+    head = dict(unit="ns per env-step", K=args.K, window_s=args.window, repeats=args.repeats, scale=args.scale,
+                n_envs=populations(args), forms="mlp: the packed-VALU form (v_pk_fma_f32 chains, weights as scalar operands)")
+    return head, table
 
 
 def main():
@@ -169,30 +128,11 @@ def main():
         return merge(args.merge, args.out)
     if args.worker:
         return worker(args.worker[0], int(args.worker[1]), args.window, int(args.worker[2]), K, only)
-    families = [(f, n) for f, n in FAMILIES if f in args.families.split(",")]
-    runs = []
-    for rep in range(args.repeats):
-        for family, n in families:
-            n = max(1024, int(n * args.scale)) // 1024 * 1024
-            # a fresh child per family and repeat; the parent never opens the GPU
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", family, str(n), str(3 * rep), "--window", str(args.window), "--K", str(K),
-                                "--cases", args.cases],
-                               capture_output=True, text=True, timeout=600)
-            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-            if r.returncode != 0 or not line:
-                print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-                raise SystemExit(f"worker {family} repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-            runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
-            print(f"repeat {rep} {family}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        summary.setdefault(f"{rec['family']}/{rec['case']}", []).append(rec["ns_per_env_step"])
-    table = {k: dict(median=statistics.median(v), min=min(v), max=max(v), spread=(max(v) - min(v)) / statistics.median(v),
-                     env_steps_per_s=1e9 / statistics.median(v), repeats=[round(x, 6) for x in v]) for k, v in sorted(summary.items())}
-    head = dict(unit="ns per env-step", K=K, window_s=args.window, repeats=args.repeats, scale=args.scale,
-                n_envs={f: max(1024, int(n * args.scale)) // 1024 * 1024 for f, n in families},
-                forms="mlp: the packed-VALU form (v_pk_fma_f32 chains, weights as scalar operands)")
-    write_record(args.out, head, table)
+    sizes = populations(args)
+    runs = timing.run_children(lambda family, rep: [os.path.abspath(__file__), "--worker", family, str(sizes[family]), str(3 * rep), "--window", str(args.window),
+                                                    "--K", str(K), "--cases", args.cases], list(sizes), args.repeats, 600)
+    head, table = record(runs, args)
+    timing.write_record(args.out, head, table)
     for k, v in table.items():
         print(f"{k:34s} median {v['median']:.4f}  min {v['min']:.4f}  max {v['max']:.4f}  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s")
 

@@ -3,46 +3,32 @@
 
     python tools/mlp_sample_time.py --repeats 5 --out profiles/mlp_sample_time.json
 
-The sizes, the weights and the timing scheme are those of tools/mlp_policy_time.py (CartPole and MountainCar at 1 048 576 envs, LunarLander with wind at
-262 144, K = 16, fused auto-reset on, a fresh process per family and repeat, the cases of a process in an order that rotates with the repeat, median / min /
-max / spread over the repeats).  Per family, H in {32, 64} and activation, ns per env-step of
+CartPole and MountainCar at 1 048 576 envs, LunarLander with wind at 262 144, K = 16, fused auto-reset on; the timing is tools/timing.py's (a warm-up and a
+probe of 5 launches each, a fresh process per family and repeat).  Per family, H in {32, 64} and activation, ns per env-step of
     sample/H../..  mgym_rollout_mlp_sample, one call per K steps with a new call word each, actions not stored
     mlp/H../..     mgym_rollout_mlp (argmax) of this build: sample - mlp is the cost of the draw, and these rows against profiles/mlp_policy_time.json show
                    that the existing path has not moved
     torch/H../..   the loop a trainer would run instead: TorchVecEnv with AoS observations; per step two torch.addmm, the activation,
                    torch.multinomial over torch.softmax, TorchVecEnv.step"""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from mlp_policy_time import FAMILIES, IN_SCALE, write_record  # noqa: E402
+FAMILIES = [("cartpole", 1 << 20), ("mountain_car", 1 << 20), ("lunar_lander", 1 << 18)]
+IN_SCALE = {"cartpole": (2.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
 
 
 def worker(family, n, window, rotate, K):
     sys.path.insert(0, ROOT)
     import numpy as np
-    import torch
     import modurl_gym_amd as mg
     kind = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "lunar_lander": mg.LUNARLANDER}[family]
     kw = dict(enable_wind=True) if family == "lunar_lander" else {}
     spec = mg.get_spec(kind)
     D, A = spec.obs_dim, spec.n_actions
-
-    def weights(H):
-        rng = np.random.default_rng(100 + H)
-        return ((rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[family])).astype(np.float32), rng.normal(0, 0.5, H).astype(np.float32),
-                (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.1, A).astype(np.float32))
-
-    def window_of(timed):
-        timed(5)                                        # warm-up
-        per = timed(5) / 5                              # ms per launch of K steps
-        count = max(5, int(window * 1000.0 / per) + 1)
-        return timed(count), count
 
     def fused(call):
         env = mg.VecEnv(kind, n, seed=7, auto_reset=True, **kw)
@@ -51,56 +37,44 @@ def worker(family, n, window, rotate, K):
         env.sync()
         calls = [0]
 
-        def timed(count):
-            env.timer_start()
-            for _ in range(count):
-                call(env, calls[0], rew, done, trunc)
-                calls[0] += 1
-            ms = env.timer_stop()
-            env.sync()                                  # (raises on a sticky device error)
-            return ms
+        def launch():
+            call(env, calls[0], rew, done, trunc)
+            calls[0] += 1
 
-        ms, count = window_of(timed)
+        out = timing.window_of(timing.engine_timed(env, launch), window, 5, 5)
         env.close()
-        return ms, count
+        return out
 
     def torch_loop(H, act):
         env = mg.TorchVecEnv(kind, n, seed=7, auto_reset=True, obs_layout="aos", **kw)
-        w1, b1, w2, b2 = (torch.from_numpy(x).cuda() for x in weights(H))
-        w1t, w2t = w1.t().contiguous(), w2.t().contiguous()
-        fn = torch.relu if act == "relu" else torch.tanh
-        state = [env.reset()]
-
-        def timed(count):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            obs = state[0]
-            e0.record()
-            for _ in range(count * K):
-                h = fn(torch.addmm(b1, obs, w1t))
-                a = torch.multinomial(torch.softmax(torch.addmm(b2, h, w2t), 1), 1).squeeze(1).to(torch.int32)
-                obs = env.step(a)[0]
-            e1.record()
-            e1.synchronize()
-            env.check()
-            state[0] = obs
-            return e0.elapsed_time(e1)
-
-        return window_of(timed)
+        timed = timing.torch_policy_timed(env, timing.mlp_weights(D, A, H, IN_SCALE[family]), act, timing.torch_heads()["sample"], K)
+        return timing.window_of(timed, window, 5, 5)
 
     cases = []
     for H in (32, 64):
         for act in ("relu", "tanh"):
-            w = weights(H)
+            w = timing.mlp_weights(D, A, H, IN_SCALE[family])
             pol = np.concatenate([w[0].ravel(), w[1], w[2].ravel(), w[3]])   # nn.Linear order: W1[H][D], b1[H], W2[A][H], b2[A]
             cases.append((f"sample/H{H}/{act}", lambda pol=pol, H=H, act=act: fused(lambda env, c, r, d, t: env.rollout_mlp_sample_device(pol, H, act, 9, c, K, None, None, r, d, t))))
             cases.append((f"mlp/H{H}/{act}", lambda pol=pol, H=H, act=act: fused(lambda env, c, r, d, t: env.rollout_mlp_device(pol, H, act, K, None, None, r, d, t))))
             cases.append((f"torch/H{H}/{act}", lambda H=H, act=act: torch_loop(H, act)))
-    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
-    for name, run in cases:
+    for name, run in timing.rotated(cases, rotate):
         ms, count = run()
         out.append(dict(family=family, n_envs=n, K=K, case=name, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n)))
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
+
+
+def populations(args):
+    return {f: timing.scaled(n, args.scale) for f, n in FAMILIES if f in args.families.split(",")}
+
+
+def record(runs, args):
+    """(head, table) of the record, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"{rec['family']}/{rec['case']}"), "list")
+    head = dict(unit="ns per env-step", K=args.K, window_s=args.window, repeats=args.repeats, scale=args.scale, n_envs=populations(args),
+                cases="sample: mgym_rollout_mlp_sample; mlp: mgym_rollout_mlp (argmax) of the same build; torch: addmm, activation, addmm, softmax, multinomial, step")
+    return head, table
 
 
 def main():
@@ -108,36 +82,18 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.3, help="seconds of timed work per case")
     ap.add_argument("--scale", type=float, default=1.0, help="population scale (smoke runs)")
-    ap.add_argument("--out", required=True, help="record file (the committed record of the full run: profiles/mlp_sample_time.json)")
+    ap.add_argument("--out", required=True, help="record file (a full run's would be profiles/mlp_sample_time.json: none has been taken)")
     ap.add_argument("--K", type=int, default=16, help="steps per rollout call")
     ap.add_argument("--families", default=",".join(f for f, _ in FAMILIES), help="comma-separated subset of the families")
     ap.add_argument("--worker", nargs=3, metavar=("FAMILY", "N", "ROTATE"))
     args = ap.parse_args()
     if args.worker:
         return worker(args.worker[0], int(args.worker[1]), args.window, int(args.worker[2]), args.K)
-    families = [(f, n) for f, n in FAMILIES if f in args.families.split(",")]
-    runs = []
-    for rep in range(args.repeats):
-        for family, n in families:
-            n = max(1024, int(n * args.scale)) // 1024 * 1024
-            # a fresh child per family and repeat; the parent never opens the GPU
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", family, str(n), str(5 * rep), "--window", str(args.window), "--K", str(args.K),
-                                "--out", args.out], capture_output=True, text=True, timeout=600)
-            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-            if r.returncode != 0 or not line:
-                print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-                raise SystemExit(f"worker {family} repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-            runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
-            print(f"repeat {rep} {family}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        summary.setdefault(f"{rec['family']}/{rec['case']}", []).append(rec["ns_per_env_step"])
-    table = {k: dict(median=statistics.median(v), min=min(v), max=max(v), spread=(max(v) - min(v)) / statistics.median(v),
-                     env_steps_per_s=1e9 / statistics.median(v), repeats=[round(x, 6) for x in v]) for k, v in sorted(summary.items())}
-    head = dict(unit="ns per env-step", K=args.K, window_s=args.window, repeats=args.repeats, scale=args.scale,
-                n_envs={f: max(1024, int(n * args.scale)) // 1024 * 1024 for f, n in families},
-                cases="sample: mgym_rollout_mlp_sample; mlp: mgym_rollout_mlp (argmax) of the same build; torch: addmm, activation, addmm, softmax, multinomial, step")
-    write_record(args.out, head, table)
+    sizes = populations(args)
+    runs = timing.run_children(lambda family, rep: [os.path.abspath(__file__), "--worker", family, str(sizes[family]), str(5 * rep), "--window", str(args.window),
+                                                    "--K", str(args.K), "--out", args.out], list(sizes), args.repeats, 600)
+    head, table = record(runs, args)
+    timing.write_record(args.out, head, table)
     for k, v in table.items():
         print(f"{k:34s} median {v['median']:.4f}  min {v['min']:.4f}  max {v['max']:.4f}  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s")
 

@@ -3,8 +3,8 @@
 
     python tools/pendulum_time.py --repeats 5 --out profiles/pendulum_time.json
 
-Both families at 1 048 576 envs, fused auto-reset on, max_episode_steps = 200 (gymnasium's limit for both ids; Pendulum's only episode boundary), HIP-event
-timing on the handle's stream, a warm-up, windows of at least --window seconds, a fresh process per repeat with the order of the cases rotating.  Per family
+Both families at 1 048 576 envs, fused auto-reset on, max_episode_steps = 200 (gymnasium's limit for both ids; Pendulum's only episode boundary); the timing
+is tools/timing.py's (the handle's timer, a warm-up of 30 launches and a probe of 20, a fresh process per repeat).  Per family
     step         mgym_step from a ring of 64 rows of uniform random actions; obs_out NULL (the engine's columns are the observation), reward / done / truncated written
     rollout16    mgym_rollout, K = 16, the same ring, obs_out NULL
     mlp16        mgym_rollout_mlp, K = 16, 32 ReLU units, actions_out and obs_out NULL
@@ -12,11 +12,10 @@ The record holds, per case, ns per env-step (median / min / max / spread over th
 call must move, counted from its arguments below, not a counter reading — and that traffic at the median rate as a fraction of 8 TB/s.  It is a whole-call
 rate over peak bandwidth, not a kernel's share of peak; mlp16 is bound by the policy's arithmetic, its fraction is given for completeness."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PEAK_BYTES_PER_S = 8e12
@@ -38,13 +37,12 @@ def worker(window, rotate, scale):
     sys.path.insert(0, ROOT)
     import numpy as np
     import modurl_gym_amd as mg
-    n = max(1024, int(N * scale)) // 1024 * 1024
+    n = timing.scaled(N, scale)
     kinds = {"mountain_car_continuous": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM}
     scale_a = {"mountain_car_continuous": 1.0, "pendulum": 2.0}
     cases = [(f, c) for f in kinds for c in ("step", "rollout16", "mlp16")]
-    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
-    for family, case in cases:
+    for family, case in timing.rotated(cases, rotate):
         rng = np.random.default_rng(1)
         env = mg.VecEnv(kinds[family], n, seed=7, auto_reset=True, max_episode_steps=LIMIT)
         d_act = mg.DeviceArray.from_numpy(((rng.random((RING, n), np.float32) * 2 - 1) * scale_a[family]).astype(np.float32))
@@ -63,27 +61,27 @@ def worker(window, rotate, scale):
             launch = lambda: env.rollout_device(next_actions(), K, None, d_rew, d_done, d_trunc)
         else:
             D, A = env.mlp_dims()
-            w = np.random.default_rng(100 + HIDDEN)
-            pol, H = env.pack_mlp(w.normal(0, 1, (HIDDEN, D)), w.normal(0, 0.5, HIDDEN), w.normal(0, 1, (A, HIDDEN)) / np.sqrt(HIDDEN), w.normal(0, 0.1, A))
+            pol, H = env.pack_mlp(*timing.mlp_weights(D, A, HIDDEN))
             launch = lambda: env.rollout_mlp_device(pol, H, "relu", K, None, None, d_rew, d_done, d_trunc)
         env.reset_device()
         env.sync()
 
-        def timed(count):
-            env.timer_start()
-            for _ in range(count):
-                launch()
-            ms = env.timer_stop()
-            env.sync()   # (raises on a sticky device error)
-            return ms
-
-        timed(30)                                  # warm-up
-        per = timed(20) / 20                       # ms per launch
-        count = max(20, int(window * 1000.0 / per) + 1)
-        ms = timed(count)
+        ms, count = timing.window_of(timing.engine_timed(env, launch), window, 30, 20)
         out.append(dict(family=family, case=case, n_envs=n, K=k, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * k * n), episodes=env.episode_count()))
         env.close()
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
+
+
+def record(runs, args):
+    """the whole document, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"{rec['family']}/{rec['case']}"), "count")
+    for key, row in table.items():
+        b = algorithmic_bytes(*key.split("/"))
+        row.update(env_steps_per_s=1e9 / row["median"], algorithmic_bytes_per_env_step=b, fraction_of_8TBps=b * 1e9 / row["median"] / PEAK_BYTES_PER_S)
+    return dict(unit="ns per env-step", n_envs=timing.scaled(N, args.scale), K=K, hidden=HIDDEN, max_episode_steps=LIMIT, window_s=args.window,
+                repeats=args.repeats, scale=args.scale, peak_bytes_per_s=PEAK_BYTES_PER_S,
+                note="whole-call rates (HIP events round the launches of a window); the bytes are algorithmic, counted from the arguments; spread = (max - min) / median",
+                summary=table, runs=runs)
 
 
 def main():
@@ -96,33 +94,12 @@ def main():
     args = ap.parse_args()
     if args.worker:
         return worker(args.window, int(args.worker[0]), args.scale)
-    runs = []
-    for rep in range(args.repeats):
-        # a fresh child per repeat, both families in it; the parent never opens the GPU
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", str(rep), "--window", str(args.window), "--scale", str(args.scale)],
-                           capture_output=True, text=True, timeout=900)
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-        if r.returncode != 0 or not line:
-            print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-            raise SystemExit(f"worker repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-        runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
-        print(f"repeat {rep}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        summary.setdefault((rec["family"], rec["case"]), []).append(rec["ns_per_env_step"])
-    table = {}
-    for (family, case), v in sorted(summary.items()):
-        med, b = statistics.median(v), algorithmic_bytes(family, case)
-        table[f"{family}/{case}"] = dict(median=med, min=min(v), max=max(v), spread=(max(v) - min(v)) / med, repeats=len(v), env_steps_per_s=1e9 / med,
-                                         algorithmic_bytes_per_env_step=b, fraction_of_8TBps=b * 1e9 / med / PEAK_BYTES_PER_S)
-    doc = dict(unit="ns per env-step", n_envs=max(1024, int(N * args.scale)) // 1024 * 1024, K=K, hidden=HIDDEN, max_episode_steps=LIMIT, window_s=args.window,
-               repeats=args.repeats, scale=args.scale, peak_bytes_per_s=PEAK_BYTES_PER_S,
-               note="whole-call rates (HIP events round the launches of a window); the bytes are algorithmic, counted from the arguments; spread = (max - min) / median",
-               summary=table, runs=runs)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    for k_, v in table.items():
+    # both families in one child
+    runs = timing.run_children(lambda _, rep: [os.path.abspath(__file__), "--worker", str(rep), "--window", str(args.window), "--scale", str(args.scale)],
+                               [None], args.repeats, 900)
+    doc = record(runs, args)
+    timing.write_json(args.out, doc)
+    for k_, v in doc["summary"].items():
         print(f"{k_:40s} median {v['median']:.5f} ns  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s  {v['algorithmic_bytes_per_env_step']:.2f} B  "
               f"{100 * v['fraction_of_8TBps']:.1f} % of 8 TB/s")
 

@@ -4,37 +4,32 @@ beside the torch loop (torch.tanh) the rollout replaces:
 
     python tools/tanh_fast_time.py --repeats 5 --out profiles/tanh_fast_time.json
 
-The timing scheme is that of tools/mlp_gauss_time.py (K = 16, fused auto-reset on, a fresh process per repeat with every case in it, the cases in an order
-that rotates with the repeat, median / min / max / spread over the repeats), 1 048 576 envs.  Rows: CartPole through mgym_rollout_mlp and
-mgym_rollout_mlp_sample, MountainCarContinuous and Pendulum (max_episode_steps = 200, gymnasium's registration) through mgym_rollout_mlp_gauss, each with
-32 and 64 hidden units.  Columns, ns per env-step, all in one process:
+1 048 576 envs, K = 16, fused auto-reset on; the timing is tools/timing.py's (a warm-up and a probe of 5 launches each, a fresh process per repeat with every
+case in it).  Rows: CartPole through mgym_rollout_mlp and mgym_rollout_mlp_sample, MountainCarContinuous and Pendulum (max_episode_steps = 200, gymnasium's
+registration) through mgym_rollout_mlp_gauss, each with 32 and 64 hidden units.  Columns, ns per env-step, all in one process:
     relu, tanh, tanh_fast   the fused rollout, one call per K steps (a new call word each where the entry point draws), actions not stored
     torch                   the loop a trainer would run instead: TorchVecEnv with AoS observations; per step two torch.addmm with torch.tanh between them,
                             then argmax / torch.multinomial of the softmax / mu + sigma * torch.randn, then TorchVecEnv.step
 Not measured here: hardware counters, other populations or K, LunarLander, a training loop."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from mlp_policy_time import write_record  # noqa: E402
+import timing
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ENVS = 1 << 20
 ROWS = [("cartpole", "mlp"), ("cartpole", "sample"), ("mountain_car_continuous", "gauss"), ("pendulum", "gauss")]
 IN_SCALE = {"cartpole": (1.0, 1.0, 8.0, 1.0), "mountain_car_continuous": (2.0, 40.0), "pendulum": (1.0, 1.0, 0.3)}
 LIMIT = {"cartpole": 0, "mountain_car_continuous": 0, "pendulum": 200}
 ACTIVATIONS = ("relu", "tanh", "tanh_fast")
 SIGMA = 0.5
+TORCH_HEAD = {"mlp": "greedy", "sample": "sample", "gauss": "gauss"}
 
 
 def worker(n, window, rotate, K, lib):
     sys.path.insert(0, ROOT)
     import numpy as np
-    import torch
     if lib:
         from modurl_gym_amd import _lib
         _lib.LIB_PATH = os.path.abspath(lib)   # before anything loads the library
@@ -42,16 +37,7 @@ def worker(n, window, rotate, K, lib):
     kinds = {"cartpole": mg.CARTPOLE, "mountain_car_continuous": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM}
 
     def weights(family, H):
-        D, A = mg.get_spec(kinds[family]).obs_dim, 2 if family == "cartpole" else 1
-        rng = np.random.default_rng(100 + H)
-        return ((rng.normal(0, 1, (H, D)) * np.array(IN_SCALE[family])).astype(np.float32), rng.normal(0, 0.5, H).astype(np.float32),
-                (rng.normal(0, 1, (A, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.1, A).astype(np.float32))
-
-    def window_of(timed):
-        timed(5)                                        # warm-up
-        per = timed(5) / 5                              # ms per launch of K steps
-        count = max(5, int(window * 1000.0 / per) + 1)
-        return timed(count), count
+        return timing.mlp_weights(mg.get_spec(kinds[family]).obs_dim, 2 if family == "cartpole" else 1, H, IN_SCALE[family])
 
     def fused(family, entry, H, act):
         w = weights(family, H)
@@ -62,50 +48,23 @@ def worker(n, window, rotate, K, lib):
         env.sync()
         calls = [0]
 
-        def timed(count):
-            env.timer_start()
-            for _ in range(count):
-                if entry == "mlp":
-                    env.rollout_mlp_device(pol, H, act, K, None, None, rew, done, trunc)
-                elif entry == "sample":
-                    env.rollout_mlp_sample_device(pol, H, act, 9, calls[0], K, None, None, rew, done, trunc)
-                else:
-                    env.rollout_mlp_gauss_device(pol, H, act, SIGMA, 9, calls[0], K, None, None, rew, done, trunc)
-                calls[0] += 1
-            ms = env.timer_stop()
-            env.sync()                                  # (raises on a sticky device error)
-            return ms
+        def launch():
+            if entry == "mlp":
+                env.rollout_mlp_device(pol, H, act, K, None, None, rew, done, trunc)
+            elif entry == "sample":
+                env.rollout_mlp_sample_device(pol, H, act, 9, calls[0], K, None, None, rew, done, trunc)
+            else:
+                env.rollout_mlp_gauss_device(pol, H, act, SIGMA, 9, calls[0], K, None, None, rew, done, trunc)
+            calls[0] += 1
 
-        out = window_of(timed)
+        out = timing.window_of(timing.engine_timed(env, launch), window, 5, 5)
         env.close()
         return out
 
     def torch_loop(family, entry, H):
         env = mg.TorchVecEnv(kinds[family], n, seed=7, auto_reset=True, obs_layout="aos", max_episode_steps=LIMIT[family])
-        w1, b1, w2, b2 = (torch.from_numpy(x).cuda() for x in weights(family, H))
-        w1t, w2t = w1.t().contiguous(), w2.t().contiguous()
-        state = [env.reset()]
-
-        def timed(count):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            obs = state[0]
-            e0.record()
-            for _ in range(count * K):
-                s = torch.addmm(b2, torch.tanh(torch.addmm(b1, obs, w1t)), w2t)
-                if entry == "mlp":
-                    a = s.argmax(1).to(torch.int32)
-                elif entry == "sample":
-                    a = torch.multinomial(torch.softmax(s, 1), 1).squeeze(1).to(torch.int32)
-                else:
-                    a = s.squeeze(1) + SIGMA * torch.randn(n, device=s.device, dtype=torch.float32)
-                obs = env.step(a)[0]
-            e1.record()
-            e1.synchronize()
-            env.check()
-            state[0] = obs
-            return e0.elapsed_time(e1)
-
-        return window_of(timed)
+        timed = timing.torch_policy_timed(env, weights(family, H), "tanh", timing.torch_heads(SIGMA)[TORCH_HEAD[entry]], K)
+        return timing.window_of(timed, window, 5, 5)
 
     cases = []
     for family, entry in ROWS:
@@ -113,12 +72,28 @@ def worker(n, window, rotate, K, lib):
             for act in ACTIVATIONS:
                 cases.append((family, f"{entry}/H{H}/{act}", lambda f=family, e=entry, H=H, a=act: fused(f, e, H, a)))
             cases.append((family, f"{entry}/H{H}/torch", lambda f=family, e=entry, H=H: torch_loop(f, e, H)))
-    cases = cases[rotate % len(cases):] + cases[: rotate % len(cases)]
     out = []
-    for family, name, run in cases:
+    for family, name, run in timing.rotated(cases, rotate):
         ms, count = run()
         out.append(dict(family=family, n_envs=n, K=K, case=name, launches=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n)))
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
+
+
+def record(runs, args):
+    """(head, table) of the record, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"{rec['family']}/{rec['case']}"), "list")
+    # each tanh_fast row against the tanh row and the torch loop of the same run
+    ratios = {}
+    for k, v in table.items():
+        if k.endswith("/tanh_fast"):
+            base = k[: -len("tanh_fast")]
+            ratios[k] = dict(tanh_over_tanh_fast=table[base + "tanh"]["median"] / v["median"], torch_over_tanh_fast=table[base + "torch"]["median"] / v["median"],
+                             relu_over_tanh_fast=table[base + "relu"]["median"] / v["median"])
+    head = dict(unit="ns per env-step", K=args.K, window_s=args.window, repeats=args.repeats, scale=args.scale, sigma=SIGMA, n_envs=timing.scaled(N_ENVS, args.scale),
+                max_episode_steps=LIMIT, lib=os.path.basename(args.lib) if args.lib else "the package's", cases="relu / tanh / tanh_fast: the fused rollout with that hidden activation; torch: addmm, torch.tanh, addmm, "
+                "argmax | multinomial(softmax) | mu + sigma * randn, step; all of a repeat in one process",
+                not_measured="hardware counters, other populations or K, LunarLander, a training loop", ratios=ratios)
+    return head, table
 
 
 def main():
@@ -133,38 +108,14 @@ def main():
     args = ap.parse_args()
     if args.worker:
         return worker(int(args.worker[0]), args.window, int(args.worker[1]), args.K, args.lib)
-    n = max(1024, int(N_ENVS * args.scale)) // 1024 * 1024
-    runs = []
-    for rep in range(args.repeats):
-        # a fresh child per repeat; the parent never opens the GPU
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", str(n), str(7 * rep), "--window", str(args.window), "--K", str(args.K),
-                            "--out", args.out, "--lib", args.lib], capture_output=True, text=True, timeout=600)
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-        if r.returncode != 0 or not line:
-            print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-            raise SystemExit(f"worker repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-        runs += [dict(rec, repeat=rep) for rec in json.loads(line[0][7:])]
-        print(f"repeat {rep}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        summary.setdefault(f"{rec['family']}/{rec['case']}", []).append(rec["ns_per_env_step"])
-    table = {k: dict(median=statistics.median(v), min=min(v), max=max(v), spread=(max(v) - min(v)) / statistics.median(v),
-                     env_steps_per_s=1e9 / statistics.median(v), repeats=[round(x, 6) for x in v]) for k, v in sorted(summary.items())}
-    # each tanh_fast row against the tanh row and the torch loop of the same run
-    ratios = {}
-    for k, v in table.items():
-        if k.endswith("/tanh_fast"):
-            base = k[: -len("tanh_fast")]
-            ratios[k] = dict(tanh_over_tanh_fast=table[base + "tanh"]["median"] / v["median"], torch_over_tanh_fast=table[base + "torch"]["median"] / v["median"],
-                             relu_over_tanh_fast=table[base + "relu"]["median"] / v["median"])
-    head = dict(unit="ns per env-step", K=args.K, window_s=args.window, repeats=args.repeats, scale=args.scale, sigma=SIGMA, n_envs=n,
-                max_episode_steps=LIMIT, lib=os.path.basename(args.lib) if args.lib else "the package's", cases="relu / tanh / tanh_fast: the fused rollout with that hidden activation; torch: addmm, torch.tanh, addmm, "
-                "argmax | multinomial(softmax) | mu + sigma * randn, step; all of a repeat in one process",
-                not_measured="hardware counters, other populations or K, LunarLander, a training loop", ratios=ratios)
-    write_record(args.out, head, table)
+    n = timing.scaled(N_ENVS, args.scale)
+    runs = timing.run_children(lambda _, rep: [os.path.abspath(__file__), "--worker", str(n), str(7 * rep), "--window", str(args.window), "--K", str(args.K),
+                                               "--out", args.out, "--lib", args.lib], [None], args.repeats, 600)
+    head, table = record(runs, args)
+    timing.write_record(args.out, head, table)
     for k, v in table.items():
         print(f"{k:52s} median {v['median']:.4f}  min {v['min']:.4f}  max {v['max']:.4f}  spread {100 * v['spread']:.2f} %  {v['env_steps_per_s']:.3e} env-steps/s")
-    for k, v in ratios.items():
+    for k, v in head["ratios"].items():
         print(f"{k:52s} tanh / tanh_fast {v['tanh_over_tanh_fast']:.2f}  torch / tanh_fast {v['torch_over_tanh_fast']:.2f}  relu / tanh_fast {v['relu_over_tanh_fast']:.2f}")
 
 

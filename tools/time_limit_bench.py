@@ -4,8 +4,8 @@ commit's — in the same run, alternating, several fresh processes each.
 
     python tools/time_limit_bench.py --base path/to/parent/libmgym.so --repeats 5 --out profiles/time_limit_bench.json
 
-Cases (fused auto-reset on, a ring of 64 rows of uniform random actions, HIP-event timing on the handle's stream as bench.py does, a warm-up,
-windows of at least --window seconds):
+Cases (fused auto-reset on, a ring of 64 rows of uniform random actions; the timing is tools/timing.py's: the handle's timer, a warm-up of 30
+launches and a probe of 20, a fresh process per library and repeat):
     MountainCar, MountainCarContinuous   1 048 576 envs   mgym_step, mgym_rollout K = 16
     LunarLander (wind)                     262 144 envs   mgym_step, mgym_rollout K = 16 and K = 64
 each with limit 0 on both libraries, and on this tree's library also with a limit: 200 for MountainCar (the uniform policy practically never
@@ -18,13 +18,13 @@ first — limit 0 or the limit — alternates from repeat to repeat.  The other 
 The spread of the base library's own repeats is the noise figure every comparison is read against.  One JSON document: every repeat, and per case
 median, min, max and spread (max - min over median)."""
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WARM, PROBE = 30, 20   # launches before the window: they count towards the steps a handle has taken
 
 CASES = [  # (family, n_envs, form, K)
     ("mountain_car", 1 << 20, "step", 1), ("mountain_car", 1 << 20, "rollout", 16),
@@ -54,7 +54,7 @@ def worker(lib_path, with_limit, window, scale, limit_first):
     rng = np.random.default_rng(1)
     out = []
     for family, n, form, K in CASES:
-        n = max(1024, int(n * scale)) // 1024 * 1024
+        n = timing.scaled(n, scale)
         for limit in (([LIMIT[family], 0] if limit_first else [0, LIMIT[family]]) if with_limit else [0]):
             kw = dict(enable_wind=True) if family == "lunar_lander" else {}
             env = mg.VecEnv(kinds[family], n, seed=7, auto_reset=True, max_episode_steps=limit, **kw)
@@ -79,19 +79,8 @@ def worker(lib_path, with_limit, window, scale, limit_first):
             env.reset_device()
             env.sync()
 
-            def timed(count):
-                env.timer_start()
-                for _ in range(count):
-                    launch()
-                ms = env.timer_stop()
-                env.sync()   # (raises on a sticky device error)
-                return ms
-
-            timed(30)                                  # warm-up
-            per = timed(20) / 20                       # ms per launch
-            count = max(20, int(window * 1000.0 / per) + 1)
-            ms = timed(count)
-            steps_per_env = (30 + 20 + count) * K
+            ms, count = timing.window_of(timing.engine_timed(env, launch), window, WARM, PROBE)
+            steps_per_env = (WARM + PROBE + count) * K
             max_elapsed = int(env.elapsed_steps().max()) if limit else None
             if family == "lunar_lander" and limit and steps_per_env >= limit:
                 raise SystemExit(f"{family} {form} K={K}: {steps_per_env} steps per env reach the limit {limit}: not a window without truncations")
@@ -99,7 +88,14 @@ def worker(lib_path, with_limit, window, scale, limit_first):
                             family=family, n_envs=n, form=form, K=K, limit=limit, launches=count, window_ms=ms,
                             ns_per_env_step=ms * 1e6 / (count * K * n), ms_per_launch=ms / count, episodes=env.episode_count()))
             env.close()
-    print("RESULT " + json.dumps(out), flush=True)
+    timing.emit(out)
+
+
+def record(runs, args):
+    """the whole document, from the children's records and the command line alone"""
+    table = timing.summarise(timing.grouped(runs, lambda rec: f"{rec['family']}/{rec['form']}{rec['K'] if rec['form'] == 'rollout' else ''}/limit{rec['limit']}/{rec['lib']}"),
+                             "count")
+    return dict(unit="ns per env-step", window_s=args.window, repeats=args.repeats, scale=args.scale, summary=table, runs=runs)
 
 
 def main():
@@ -114,31 +110,15 @@ def main():
     if args.worker:
         return worker(args.worker[0], args.worker[1] == "1", args.window, args.scale, args.worker[2] == "1")
     new_lib = os.path.join(ROOT, "modurl_gym_amd", "libmgym.so")
-    libs = ([("base", os.path.abspath(args.base), "0")] if args.base else []) + [("new", new_lib, "1")]
-    runs = []
-    for rep in range(args.repeats):           # alternating: base, new, base, new, ...
-        for tag, path, with_limit in libs:
-            # a fresh child per repeat: one process holds one build of the library, and the parent never opens the GPU
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", path, with_limit, str(rep % 2), "--window", str(args.window), "--scale", str(args.scale)],
-                               capture_output=True, text=True, timeout=900)
-            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-            if r.returncode != 0 or not line:
-                print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
-                raise SystemExit(f"worker {tag} repeat {rep} failed with status {r.returncode}")   # nothing more is started on the GPU
-            for rec in json.loads(line[0][7:]):
-                runs.append(dict(rec, lib=tag, repeat=rep, limit_handle_first=bool(rep % 2)))
-            print(f"repeat {rep} {tag}: done", flush=True)
-    summary = {}
-    for rec in runs:
-        key = f"{rec['family']}/{rec['form']}{rec['K'] if rec['form'] == 'rollout' else ''}/limit{rec['limit']}/{rec['lib']}"
-        summary.setdefault(key, []).append(rec["ns_per_env_step"])
-    table = {k: dict(median=statistics.median(v), min=min(v), max=max(v), spread=(max(v) - min(v)) / statistics.median(v), repeats=len(v))
-             for k, v in sorted(summary.items())}
-    doc = dict(unit="ns per env-step", window_s=args.window, repeats=args.repeats, scale=args.scale, summary=table, runs=runs)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    for k, v in table.items():
+    libs = {"new": (new_lib, "1")}                                           # lib: (path, with the limit cases)
+    if args.base:
+        libs = {"base": (os.path.abspath(args.base), "0"), **libs}
+    # alternating: base, new, base, new, ...; one process holds one build of the library
+    runs = timing.run_children(lambda tag, rep: [os.path.abspath(__file__), "--worker", *libs[tag], str(rep % 2), "--window", str(args.window), "--scale", str(args.scale)],
+                               list(libs), args.repeats, 900, fields=lambda tag, rep, position: dict(lib=tag, repeat=rep, limit_handle_first=bool(rep % 2)))
+    doc = record(runs, args)
+    timing.write_json(args.out, doc)
+    for k, v in doc["summary"].items():
         print(f"{k:62s} median {v['median']:.4f}  min {v['min']:.4f}  max {v['max']:.4f}  spread {100 * v['spread']:.2f} %")
 
 
