@@ -242,7 +242,17 @@ int mgym_default_config(int kind, mgym_config *cfg);
 
 /* Replaces {CartPoleV1,MountainCarV0,LunarLanderV3}::builder()...build()
  * (cartpole.rs:37-96, mountain_car.rs:27-69, lunar_lander.rs:281-352).
- * Initial state as constructed by the reference: zeros; CartPole steps_beyond_terminated=Some(0). */
+ * Initial state as constructed by the reference: zeros; CartPole steps_beyond_terminated=Some(0).
+ * Populations per handle.  The 16-byte kernels address the engine's columns by 32-bit byte offsets from one buffer resource, which bounds n_envs:
+ *   CartPole: at most 134 217 728 (2^27) environments; a larger n_envs is refused with MGYM_ERR_BAD_ARG before anything is allocated (shard larger
+ *     populations over handles: env_id_base makes the split invisible).
+ *   MountainCar, MountainCarContinuous, Pendulum: the 16-byte step kernel runs up to 2^27 environments, Acrobot's up to 2^26; beyond that (as for n_envs no
+ *     multiple of 4 or buffers off their alignment) mgym_step runs the generic kernel with 64-bit addresses — the same words, any n_envs.
+ *   LunarLander: any n_envs; mgym_rollout's persistent launch needs n_envs <= 16 777 215 and its records (1152 bytes per environment, n_envs rounded up to
+ *     a multiple of 1024) below 4 GiB, that is at most 3 727 360 environments; beyond that it runs as K steps (mgym_get_info: rollout=k_steps).  (By default the engine
+ *     chooses K steps long before that bound: see mgym_rollout.)
+ * Every [K][n_envs] buffer of the rollout entry points, of mgym_set_final_obs_out, mgym_gae and mgym_episode_returns may exceed 4 GiB: rows are addressed
+ * in 64 bits.  The one exception is CartPole's fused rollout kernel (mgym_rollout below). */
 int mgym_create(const mgym_config *cfg, mgym_env **out);
 int mgym_destroy(mgym_env *env);
 
@@ -272,6 +282,10 @@ int mgym_step(mgym_env *env, const void *actions, float *obs_out, float *reward_
  * count in registers across the K steps: one read and one write per launch); for CartPole/MountainCar the state stays in registers
  * across the K steps, so per-step HBM traffic is the action read and the reward/flag writes only.
  * actions: [K][n_envs]; reward_out/done_out/trunc_out: [K][n_envs] or NULL; obs_out: [K][obs_dim][n_envs] or NULL.
+ * The fused kernels need n_envs a multiple of 4 and the buffers 16-byte aligned (flags 4-byte), and CartPole's, which addresses the [K][n_envs] word
+ * buffers by 32-bit byte offsets, K * n_envs below 2^30 (1 Mi environments x 1023 steps, 2^27 x 7); a call outside these runs as K launches of the step
+ * kernel — the same words.  The policy entry points below have no K-step form for the classic families: there such a call is MGYM_ERR_BAD_ARG (the
+ * message names the entry point), nothing launched, the state, mgym_episode_count and the uniform call count untouched.
  * LunarLander: ONE persistent launch in which every environment advances as soon as IT is ready (free-flight environments stay in
  * registers from step to step, environments on the contact path travel through device queues in batches of their own kind, whatever step
  * index each is at) — a step of mgym_step ends with its slowest environment, K steps of mgym_rollout cost the mean one.  Per-environment

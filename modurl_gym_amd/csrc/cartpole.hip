@@ -314,7 +314,7 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
     uint32_t finished = 0;
     WaveResetScratch<4>& lds = lds_[RESET ? (threadIdx.x >> 6) : 0];
     // per-step buffers through buffer resources: descriptor + (step, pass) offset in SGPRs, one constant VGPR lane offset.
-    // The host wrapper guarantees K * n * 16 < 2^32 (every byte offset fits 32 bits) and n % 4 == 0.
+    // The host wrapper guarantees K * n * 4 < 2^32 (fused_rollout_args_ok: every byte offset into a [K][n] word buffer fits 32 bits) and n % 4 == 0.
     const uint32_t lane_env = threadIdx.x * 4u, off4 = lane_env * 4u;
     const uint32_t colb = (uint32_t)d.n_pad * 4u, nb4 = (uint32_t)d.n * 4u;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(d.base, 0, 0xffffffff, 0x00020000);

@@ -1,0 +1,614 @@
+"""Every kernel at the bounds of its 32-bit addressing: populations on both sides of the guards in the host code (CartPole 2^27; MountainCar,
+MountainCarContinuous and Pendulum 2^27 / 2^27 + 4; Acrobot 2^26 / 2^26 + 4), CartPole's fused rollouts on both sides of K n = 2^30, [K][n] buffers beyond
+4 GiB for every family's rollout, for mgym_gae and mgym_episode_returns, and LunarLander records beyond 4 GiB.  A wrapped offset is silent — it reads and
+writes another environment's words — so every word of every output is checked, on the device: tests/big_population.py states the two references
+(periodicity from a deterministic reset, and handles of 4096 environments at the same global ids).
+
+Large in bytes, small in steps.  Each test states its peak device footprint (FOOTPRINT, checked against its shapes by test_big_population.py), asks for it
+with require_memory, closes its handles and drops its tensors before it returns.  The engine runs on its own stream, torch on its own: `call` synchronises
+torch before an engine call and the engine after it."""
+import time
+
+import numpy as np
+import pytest
+import torch
+
+import big_population as bp
+import modurl_gym_amd as mg
+from big_population import GIB, P
+
+pytestmark = pytest.mark.gpu
+
+L = mg.envs.L
+SEED = 20260
+DEV = "cuda"
+F32, I32, U8 = torch.float32, torch.int32, torch.uint8
+
+# kind, the largest population of the 16-byte step form, actions, engine columns (f32 / u32, n_pad words apart), the floats of a linear policy
+FAMILIES = {
+    "cartpole": dict(kind=mg.CARTPOLE, bound=1 << 27, n_actions=2, box=None, limit=0, lin=5),
+    "mountaincar": dict(kind=mg.MOUNTAINCAR, bound=1 << 27, n_actions=3, box=None, limit=3, lin=9),
+    "mountaincar_cont": dict(kind=mg.MOUNTAINCAR_CONT, bound=1 << 27, n_actions=None, box=(-1.5, 1.5), limit=3, lin=3),
+    "pendulum": dict(kind=mg.PENDULUM, bound=1 << 27, n_actions=None, box=(-2.5, 2.5), limit=3, lin=4),
+    "acrobot": dict(kind=mg.ACROBOT, bound=1 << 26, n_actions=3, box=None, limit=3, lin=21),
+}
+OBS_DIM = {"cartpole": 4, "mountaincar": 2, "mountaincar_cont": 2, "pendulum": 3, "acrobot": 6, "lunarlander": 8}
+STEP_CASES = [("cartpole", 1 << 27)] + [(f, FAMILIES[f]["bound"] + d) for f in ("mountaincar", "mountaincar_cont", "pendulum", "acrobot") for d in (0, 4)]
+WHOLE_STEPS, WINDOW_STEPS, CARTPOLE_WINDOW_STEPS = 6, 7, 12
+N_WINDOWS = 3 + bp.N_SEEDED + 1   # at most: first, last, middle, one column crossing, the seeded ones
+
+CP_BOUND_CASES = [(1 << 20, 1023), (1 << 27, 7), (1 << 20, 1024), (1 << 27, 8)]   # K n = 2^30 - n twice (fused), then 2^30 exactly (K plain steps)
+ROLL_CASES = [("mountaincar", 1 << 27, 9), ("mountaincar_cont", 1 << 27, 9), ("pendulum", 1 << 27, 9), ("acrobot", 1 << 26, 17)]
+FINAL_N, FINAL_K = 1 << 20, 300
+GAE_N, GAE_K = 1 << 22, 257
+EP_SPLIT = (200, 57)
+LL_N, LL_STEPS, LL_EVERY = 3735552, 72, 8   # a multiple of 1024 with n_pad * 1152 B beyond 2^32: the records cross 4 GiB, the persistent rollout is off
+LL_RECORD_BYTES = 1152
+
+
+# ---- footprints -----------------------------------------------------------------------------------------------------------------------------
+def step_outputs(fam, n, lead=()):
+    """(itemsize, dims..) of obs, reward, done, truncated"""
+    k = tuple(lead)
+    return [(4,) + k + (OBS_DIM[fam], n), (4,) + k + (n,), (1,) + k + (n,), (1,) + k + (n,)]
+
+
+def footprint(key):
+    """handles and buffers alive at the peak of the test `key` -> bytes (big_population.need_bytes)"""
+    what, fam, n, K = key
+    small = [(fam, P)]
+    d = OBS_DIM[fam]
+    if what == "whole":      # the action table, the outputs, elapsed; the reset's obs_out and the row-major observation; the handle, the 4096-env twins
+        return bp.need_bytes([(fam, n)] + small * (1 + N_WINDOWS), [(4, K, n)] + step_outputs(fam, n) + [(4, n), (1, n), (4, d, n), (4, n, d)])
+    if what == "windows":    # the action table, the outputs, elapsed, the flags' OR
+        return bp.need_bytes([(fam, n)] + small * N_WINDOWS, [(4, K, n)] + step_outputs(fam, n) + [(4, n), (1, n)])
+    if what == "cp_bound":   # the table, the [K] outputs, the twin's chunk of them (at most an eighth, one step at least), a step of drawn actions twice, two handles
+        ch = max(1, K // 8)
+        return bp.need_bytes([(fam, n)] * 2, [(4, K, n)] + step_outputs(fam, n, (K,)) + step_outputs(fam, n, (ch,)) + [(4, 1, n)] * 2)
+    if what == "cp_uniform":   # actions_out and reward / done / truncated of both handles
+        return bp.need_bytes([(fam, n)] * 2, [(4, K, n)] + step_outputs(fam, n, (K,))[1:] * 2)
+    if what == "cp_final":   # the table, obs_out and the final observations, reward, flags; the twin's chunks of them
+        ch = max(1, K // 8)
+        return bp.need_bytes([(fam, n)] * 2, [(4, K, n), (4, K, d, n)] + step_outputs(fam, n, (K,)) + [(4, ch, d, n)] + step_outputs(fam, n, (ch,)))
+    if what == "roll":       # the table / actions_out, reward and flags of both handles, a step's outputs and elapsed of both
+        return bp.need_bytes([(fam, n)] * 2, [(4, K, n)] + step_outputs(fam, n, (K,))[1:] * 2 + step_outputs(fam, n)[1:] + [(4, n)] * 2)
+    if what == "gae":        # reward (+ 4 words), value, final_value, adv, ret, the flags, last_value
+        return bp.need_bytes([(fam, n)], [(4, K, n)] * 5 + [(4, 4)] + [(1, K, n)] * 2 + [(4, n)])
+    if what == "ep":         # reward (+ 4 words), return_out, length_out, the flags, the carry
+        return bp.need_bytes([(fam, n)], [(4, K, n)] * 3 + [(4, 4)] + [(1, K, n)] * 2 + [(4, n)] * 2)
+    if what == "ll":         # the action table, the outputs, elapsed; the handle and its 4096-env twins
+        return bp.need_bytes([(fam, n)] + small * (N_WINDOWS + 1), [(4, K, n)] + step_outputs(fam, n) + [(4, n)])
+    raise KeyError(key)
+
+
+# declared peak device footprints in GiB (each test's docstring repeats its own); test_big_population.py recomputes them from the shapes
+FOOTPRINT = {
+    ("whole", "cartpole", 1 << 27, WHOLE_STEPS): 14.9, ("windows", "cartpole", 1 << 27, CARTPOLE_WINDOW_STEPS): 13.9,
+    **{("whole", f, (1 << 27) + d, WHOLE_STEPS): 11.2 for f in ("mountaincar", "mountaincar_cont") for d in (0, 4)},
+    **{("windows", f, (1 << 27) + d, WINDOW_STEPS): 9.7 for f in ("mountaincar", "mountaincar_cont") for d in (0, 4)},
+    **{("whole", "pendulum", (1 << 27) + d, WHOLE_STEPS): 13.7 for d in (0, 4)}, **{("windows", "pendulum", (1 << 27) + d, WINDOW_STEPS): 11.2 for d in (0, 4)},
+    **{("whole", "acrobot", (1 << 26) + d, WHOLE_STEPS): 11.1 for d in (0, 4)}, **{("windows", "acrobot", (1 << 26) + d, WINDOW_STEPS): 8.4 for d in (0, 4)},
+    ("cp_bound", "cartpole", 1 << 20, 1023): 30.8, ("cp_bound", "cartpole", 1 << 27, 7): 33.5,
+    ("cp_bound", "cartpole", 1 << 20, 1024): 30.8, ("cp_bound", "cartpole", 1 << 27, 8): 36.8,
+    ("cp_uniform", "cartpole", 1 << 20, 1023): 18.1, ("cp_final", "cartpole", FINAL_N, FINAL_K): 15.8,
+    ("roll", "mountaincar", 1 << 27, 9): 25.3, ("roll", "mountaincar_cont", 1 << 27, 9): 25.3, ("roll", "pendulum", 1 << 27, 9): 27.3, ("roll", "acrobot", 1 << 26, 17): 24.7,
+    ("gae", "cartpole", GAE_N, GAE_K): 24.2, ("ep", "cartpole", GAE_N, GAE_K): 16.2, ("ll", "lunarlander", LL_N, LL_STEPS): 18.4,
+}
+
+
+# ---- plumbing -------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(autouse=True)
+def report(request):
+    """prints the test's wall time and the largest drop of free device memory seen at its marks (run with -s to read them)"""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    free0 = torch.cuda.mem_get_info()[0]
+    low = [free0]
+
+    def mark():
+        low[0] = min(low[0], torch.cuda.mem_get_info()[0])
+
+    t0 = time.perf_counter()
+    yield mark
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    torch.cuda.empty_cache()
+    print(f"\nBOUNDS {request.node.name}: {dt:.2f} s, peak {(free0 - low[0]) / GIB:.2f} GiB")
+
+
+def reserve(key):
+    nbytes = int(round(FOOTPRINT[key] * GIB))
+    bp.require_memory(nbytes)
+
+
+def call(env, fn, *args):
+    """an engine call between the two streams: torch's work is done before it, the engine's after it (and the sticky device status raised)"""
+    torch.cuda.synchronize()
+    fn(*args)
+    env.sync()
+
+
+def make(fam, n, **kw):
+    if fam == "lunarlander":
+        return mg.VecEnv(mg.LUNARLANDER, n, seed=SEED, enable_wind=True, **kw)
+    f = FAMILIES[fam]
+    return mg.VecEnv(f["kind"], n, seed=SEED, max_episode_steps=f["limit"], **kw)
+
+
+def reset_deterministic(env):
+    mg.envs._check(env._lib.mgym_reset_deterministic(env._h, None))
+    env.sync()
+
+
+def table(fam, K, n, seed):
+    f = FAMILIES[fam]
+    return bp.periodic_actions(K, n, P, n_actions=f["n_actions"], box=f["box"], seed=seed, device=DEV)
+
+
+class _Span:
+    def __init__(self, ptr, shape, strides, owner):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2, "strides": tuple(strides)}
+
+
+def engine_columns(env, fam):
+    """zero-copy int32 [columns][n] over the engine's own columns (mgym_observation: the observation's come first, the rest lie behind them)"""
+    cols = 8 if fam == "lunarlander" else bp.ENGINE_COLUMNS[fam]
+    ptr, stride = env.observation_device()
+    return torch.as_tensor(_Span(ptr, (cols, env.n), (4 * stride, 4), env), device=torch.device(DEV, 0))
+
+
+class Outputs:
+    """obs [lead][obs_dim][n], reward [lead][n], done, truncated: sentinel-filled; mis_rew: the reward pointer 4 bytes off its 16-byte alignment"""
+
+    def __init__(self, fam, n, lead=(), obs=True, mis_rew=False):
+        lead = tuple(lead)
+        self.obs = bp.sentinel(lead + (OBS_DIM[fam], n), F32, DEV) if obs else None
+        count = int(np.prod(lead + (n,), dtype=np.int64))
+        self._rew = bp.sentinel((count + 4,), F32, DEV)
+        self.rew = self._rew[1: count + 1].view(lead + (n,)) if mis_rew else self._rew[:count].view(lead + (n,))
+        self.done, self.trunc = bp.sentinel(lead + (n,), U8, DEV), bp.sentinel(lead + (n,), U8, DEV)
+
+    def refill(self):
+        bp.fill_sentinel(*[x for x in (self.obs, self._rew, self.done, self.trunc) if x is not None])
+
+    def args(self, t=None):
+        """(obs_out, reward_out, done_out, trunc_out) of a call, or of slab t"""
+        xs = (self.obs, self.rew, self.done, self.trunc)
+        return tuple(None if x is None else (x if t is None else x[t]) for x in xs)
+
+    def named(self, sl=slice(None)):
+        d = dict(reward=self.rew[sl], done=self.done[sl], truncated=self.trunc[sl])
+        if self.obs is not None:
+            d["obs"] = self.obs[sl]
+        return d
+
+
+same_words = bp.same_words
+
+
+def elapsed_of(env, fam, out):
+    """mgym_get_elapsed_steps into `out` (CartPole has none: its count rides in the engine's counter column)"""
+    if fam != "cartpole":
+        bp.fill_sentinel(out)
+        call(env, env.elapsed_steps_device, out)
+
+
+def finished(o):
+    return bp.count_set(o.done, o.trunc)
+
+
+# ---- 2. the step kernels at both sides of their bound ----------------------------------------------------------------------------------------
+def whole_population(fam, n, mark, mis_rew=False, with_reset=True):
+    F = FAMILIES[fam]
+    env, small = make(fam, n), make(fam, P)
+    twins = []
+    try:
+        reset_deterministic(env), reset_deterministic(small)
+        acts = table(fam, WHOLE_STEPS, n, seed=1)
+        out, sout = Outputs(fam, n, mis_rew=mis_rew), Outputs(fam, P, mis_rew=mis_rew)
+        el, sel = bp.sentinel((n,), I32, DEV), bp.sentinel((P,), I32, DEV)
+        mark()
+        for t in range(WHOLE_STEPS):
+            out.refill(), sout.refill()
+            a_small = acts[t, :P].contiguous()
+            call(env, env.step_device, acts[t], *out.args())
+            call(small, small.step_device, a_small, *sout.args())
+            for (name, big), little in zip(out.named().items(), sout.named().values()):
+                bp.assert_periodic(big, P, f"{fam} n={n} step {t} {name}")
+                assert same_words(big[..., :P], little), f"{fam} n={n} step {t}: the first {P} environments' {name} differ from a {P}-environment handle"
+        cols, scols = engine_columns(env, fam), engine_columns(small, fam)
+        bp.assert_periodic(cols, P, f"{fam} n={n} engine columns")
+        assert same_words(cols[:, :P], scols)
+        if fam != "cartpole":
+            elapsed_of(env, fam, el), elapsed_of(small, fam, sel)
+            bp.assert_periodic(el, P, f"{fam} n={n} elapsed steps")
+            assert same_words(el[:P], sel)
+        if not with_reset:
+            return
+        # masked reset under a periodic mask: the draws are keyed by the global id, so the reference is the windows' handles, driven the same way
+        mask = bp.periodic_bytes(1, n, 0.3, P, seed=2, device=DEV, lead=False)
+        robs, aos = bp.sentinel((OBS_DIM[fam], n), F32, DEV), bp.sentinel((n, OBS_DIM[fam]), F32, DEV)
+        mark()
+        call(env, env.reset_device, mask, robs)
+        call(env, lambda: mg.envs._check(env._lib.mgym_observation_aos(env._h, aos.data_ptr())))
+        wins = bp.windows(n, SEED, (n + 1023) // 1024 * 1024, bp.ENGINE_COLUMNS[fam])
+
+        def make_small(k, a, b):
+            w = make(fam, b - a, env_id_base=a)
+            twins.append(w)
+            reset_deterministic(w)
+            wo = Outputs(fam, b - a)
+            for t in range(WHOLE_STEPS):
+                call(w, w.step_device, acts[t, a:b].contiguous(), *wo.args())
+            wr, wa = bp.sentinel((OBS_DIM[fam], b - a), F32, DEV), bp.sentinel((b - a, OBS_DIM[fam]), F32, DEV)
+            call(w, w.reset_device, mask[a:b].contiguous(), wr)
+            call(w, lambda: mg.envs._check(w._lib.mgym_observation_aos(w._h, wa.data_ptr())))
+            return dict(reset_obs=wr, aos=wa.t(), columns=engine_columns(w, fam))
+
+        bp.assert_windows_equal(dict(reset_obs=robs, aos=aos.t(), columns=engine_columns(env, fam)), make_small, wins, f"{fam} n={n} masked reset:")
+        mark()
+    finally:
+        for e in [env, small] + twins:
+            e.close()
+
+
+@pytest.mark.parametrize("fam,n", STEP_CASES, ids=lambda v: str(v))
+def test_whole_population_is_periodic_under_periodic_actions(fam, n, report):
+    """reset_deterministic, auto-reset off, a limit of 3, 6 steps under a periodic table: observation, reward, done and truncated after every step, the
+    engine's columns and the elapsed counts after the last are the first 4096 environments tiled, and those equal a 4096-environment handle; then a masked
+    reset and mgym_observation_aos against the windows' handles.  Peak footprint: 14.9 GiB (CartPole), 13.7 (Pendulum), 11.2 (MountainCar, MountainCarContinuous), 11.1 (Acrobot)."""
+    reserve(("whole", fam, n, WHOLE_STEPS))
+    whole_population(fam, n, report)
+
+
+def test_cartpole_scalar_step_kernel_at_its_bound(report):
+    """the one-environment-per-lane step kernel (the reward pointer 4 bytes off its alignment) at n = 2^27: its `base` is a 32-bit word too.  The whole
+    population under the periodic table, as above, without the reset.  Peak footprint: 14.9 GiB."""
+    reserve(("whole", "cartpole", 1 << 27, WHOLE_STEPS))
+    whole_population("cartpole", 1 << 27, report, mis_rew=True, with_reset=False)
+
+
+@pytest.mark.parametrize("fam,n", STEP_CASES, ids=lambda v: str(v))
+def test_windows_equal_small_handles_through_resets(fam, n, report):
+    """seeded reset, auto-reset on, env_id_base = 2^32 - n / 2 (the ids straddle 2^32), a limit of 3 and 7 steps of a periodic table (CartPole: 12 steps of
+    action 1, so that poles fall): after every step every output, the engine's columns and the elapsed counts equal, in every window, a 4096-environment
+    handle at the same global ids; mgym_episode_count is the number of flags set.  Peak footprint: 13.9 GiB (CartPole), 11.2 (Pendulum), 9.7 (MountainCar, MountainCarContinuous), 8.4 (Acrobot)."""
+    steps = CARTPOLE_WINDOW_STEPS if fam == "cartpole" else WINDOW_STEPS
+    reserve(("windows", fam, n, steps))
+    base = (1 << 32) - n // 2
+    env = make(fam, n, auto_reset=True, env_id_base=base)
+    wins = bp.windows(n, SEED, (n + 1023) // 1024 * 1024, bp.ENGINE_COLUMNS[fam])
+    assert len(wins) <= N_WINDOWS
+    twins = [make(fam, b - a, auto_reset=True, env_id_base=base + a) for a, b in wins]
+    try:
+        for e in [env] + twins:
+            call(e, e.reset_device, None, None)
+        acts = torch.ones((steps, n), dtype=I32, device=DEV) if fam == "cartpole" else table(fam, steps, n, seed=3)
+        out, el = Outputs(fam, n), bp.sentinel((n,), I32, DEV)
+        wout = [(Outputs(fam, b - a), bp.sentinel((b - a,), I32, DEV)) for a, b in wins]
+        total, wtotal = 0, [0] * len(wins)
+        report()
+        for t in range(steps):
+            out.refill()
+            call(env, env.step_device, acts[t], *out.args())
+            elapsed_of(env, fam, el)
+            total += finished(out)
+            big = dict(out.named(), columns=engine_columns(env, fam), elapsed=el)
+
+            def make_small(k, a, b):
+                w, (wo, wel) = twins[k], wout[k]
+                wo.refill()
+                call(w, w.step_device, acts[t, a:b].contiguous(), *wo.args())
+                elapsed_of(w, fam, wel)
+                wtotal[k] += finished(wo)
+                return dict(wo.named(), columns=engine_columns(w, fam), elapsed=wel)
+
+            bp.assert_windows_equal(big, make_small, wins, f"{fam} n={n} step {t}:")
+        assert total > 0 and env.episode_count() == total, (env.episode_count(), total)
+        for w, c in zip(twins, wtotal):
+            assert w.episode_count() == c
+        report()
+    finally:
+        for e in [env] + twins:
+            e.close()
+
+
+def test_create_refuses_a_cartpole_handle_beyond_its_bound():
+    """n = 2^27 + 4: MGYM_ERR_BAD_ARG with the documented message, and none of the 2.5 GiB of columns allocated"""
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    with pytest.raises(mg.MgymError) as ei:
+        mg.VecEnv(mg.CARTPOLE, (1 << 27) + 4)
+    assert ei.value.status == L.ERR_BAD_ARG
+    assert "mgym_create: a CartPole handle holds at most 134 217 728 environments (shard larger populations over handles)" in str(ei.value)
+    assert free0 - torch.cuda.mem_get_info()[0] < 64 << 20
+    env = mg.VecEnv(mg.CARTPOLE, 4)   # the library is as usable as before
+    env.close()
+
+
+# ---- 3. fused rollouts and the scans across 4 GiB --------------------------------------------------------------------------------------------
+def chunks(K):
+    ch = max(1, K // 8)
+    return [(c, min(ch, K - c)) for c in range(0, K, ch)]
+
+
+def mlp_policy(env, H=4):
+    D, A = env.mlp_dims()
+    r = np.random.default_rng(4)
+    return env.pack_mlp(*(r.uniform(-1, 1, s).astype(np.float32) for s in ((H, D), (H,), (A, H), (A,))))
+
+
+def mlp2_policy(env, H=4):
+    D, A = env.mlp_dims()
+    r = np.random.default_rng(5)
+    return env.pack_mlp2(*(r.uniform(-1, 1, s).astype(np.float32) for s in ((H, D), (H,), (H, H), (H,), (A, H), (A,))))
+
+
+@pytest.mark.parametrize("n,K", CP_BOUND_CASES, ids=lambda v: str(v))
+def test_cartpole_rollout_at_its_bound(n, K, report):
+    """mgym_rollout with K n = 2^30 - n (the fused kernel, its last step's byte offsets just below 2^32) and K n = 2^30 (K plain steps): every output, the
+    engine's columns and mgym_episode_count equal a twin handle that runs the same table in chunks of at most K / 8 steps.  At K n = 2^30 the four policy
+    entry points refuse with MGYM_ERR_BAD_ARG, name themselves and "below 2^30", and leave the state, mgym_episode_count and the uniform call counter as
+    they were.  Peak footprint: 36.8 GiB (n = 2^27, K = 8), 33.5 (K = 7), 30.8 (n = 2^20)."""
+    reserve(("cp_bound", "cartpole", n, K))
+    A, B = make("cartpole", n, auto_reset=True), make("cartpole", n, auto_reset=True)
+    try:
+        call(A, A.reset_device, None, None), call(B, B.reset_device, None, None)
+        acts = table("cartpole", K, n, seed=6)
+        out = Outputs("cartpole", n, (K,))
+        ch = max(1, K // 8)
+        cout = Outputs("cartpole", n, (ch,))
+        report()
+        call(A, A.rollout_device, acts, K, *out.args())
+        for c, k in chunks(K):
+            cout.refill()
+            call(B, B.rollout_device, acts[c: c + k], k, *cout.args())
+            for (name, big), little in zip(out.named(slice(c, c + k)).items(), cout.named(slice(0, k)).values()):
+                assert not bp.has_sentinel(little), f"{name}: the twin left words unwritten in steps {c} .. {c + k - 1}"
+                assert same_words(big, little), f"n={n} K={K}: {name} of steps {c} .. {c + k - 1} differs from the chunked twin"
+        assert same_words(engine_columns(A, "cartpole"), engine_columns(B, "cartpole"))
+        count = A.episode_count()
+        assert count == B.episode_count() == finished(out) and (count > 0 or K < 8)   # (no pole falls within 7 steps of a reset)
+        if K * n < 1 << 30:
+            return
+        (pol, H), (pol2, H1, H2) = mlp_policy(A), mlp2_policy(A)
+        uact, ub = bp.sentinel((1, n), I32, DEV), bp.sentinel((1, n), I32, DEV)
+        report()
+        o = (acts,) + out.args()
+        refused = (("mgym_rollout_uniform", lambda: A.rollout_uniform_device(9, K, *o)),
+                   ("mgym_rollout_linear", lambda: A.rollout_linear_device(np.ones(5, np.float32), K, *o)),
+                   ("mgym_rollout_mlp", lambda: A.rollout_mlp_device(pol, H, "relu", K, *o)),
+                   ("mgym_rollout_mlp2", lambda: A.rollout_mlp2_device(pol2, H1, H2, "relu", "greedy", 0.0, 0, 0, K, *o)))
+        for api, fn in refused:
+            with pytest.raises(mg.MgymError) as ei:
+                fn()
+            assert ei.value.status == L.ERR_BAD_ARG and f"{api}:" in str(ei.value) and "below 2^30" in str(ei.value), str(ei.value)
+        A.sync()
+        assert same_words(engine_columns(A, "cartpole"), engine_columns(B, "cartpole")) and A.episode_count() == count   # (B made none of these calls)
+        # the uniform call counter: A's next uniform call draws the actions of B's first
+        call(A, A.rollout_uniform_device, 9, 1, uact), call(B, B.rollout_uniform_device, 9, 1, ub)
+        assert not bp.has_sentinel(uact) and same_words(uact, ub)
+    finally:
+        A.close(), B.close()
+
+
+def test_cartpole_uniform_rollout_at_its_bound_equals_the_table_rollout_of_its_actions(report):
+    """mgym_rollout_uniform at n = 2^20, K = 1023 (actions_out, reward, done, truncated; obs_out NULL) against mgym_rollout on a twin fed the drawn actions.
+    Peak footprint: 18.1 GiB."""
+    n, K = 1 << 20, 1023
+    reserve(("cp_uniform", "cartpole", n, K))
+    A, B = make("cartpole", n, auto_reset=True), make("cartpole", n, auto_reset=True)
+    try:
+        call(A, A.reset_device, None, None), call(B, B.reset_device, None, None)
+        uact = bp.sentinel((K, n), I32, DEV)
+        oa, ob = Outputs("cartpole", n, (K,), obs=False), Outputs("cartpole", n, (K,), obs=False)
+        report()
+        call(A, A.rollout_uniform_device, 11, K, uact, *oa.args())
+        assert not bp.has_sentinel(uact) and int(uact.min()) == 0 and int(uact.max()) == 1
+        call(B, B.rollout_device, uact, K, *ob.args())
+        for (name, x), y in zip(oa.named().items(), ob.named().values()):
+            assert not bp.has_sentinel(x) and same_words(x, y), name
+        assert same_words(engine_columns(A, "cartpole"), engine_columns(B, "cartpole")) and A.episode_count() == B.episode_count() == finished(oa) > 0
+    finally:
+        A.close(), B.close()
+
+
+def test_cartpole_obs_out_and_final_observations_beyond_4gib(report):
+    """n = 2^20, K = 300: obs_out and the final observations (mgym_set_final_obs_out) are [300][4][n], 4.7 GiB each — the row arithmetic of the rollout's
+    observation stores and of final_store — against a twin that runs chunks of 37 steps.  Peak footprint: 15.8 GiB."""
+    n, K = FINAL_N, FINAL_K
+    reserve(("cp_final", "cartpole", n, K))
+    A, B = make("cartpole", n, auto_reset=True), make("cartpole", n, auto_reset=True)
+    try:
+        call(A, A.reset_device, None, None), call(B, B.reset_device, None, None)
+        acts = table("cartpole", K, n, seed=7)
+        ch = max(1, K // 8)
+        out, cout = Outputs("cartpole", n, (K,)), Outputs("cartpole", n, (ch,))
+        fin, cfin = bp.sentinel((K, 4, n), F32, DEV), bp.sentinel((ch, 4, n), F32, DEV)
+        A.set_final_obs_out_device(fin, K), B.set_final_obs_out_device(cfin, ch)
+        report()
+        call(A, A.rollout_device, acts, K, *out.args())
+        ended = 0
+        for c, k in chunks(K):
+            cout.refill(), bp.fill_sentinel(cfin)
+            call(B, B.rollout_device, acts[c: c + k], k, *cout.args())
+            big = dict(out.named(slice(c, c + k)), final=fin[c: c + k])
+            little = dict(cout.named(slice(0, k)), final=cfin[:k])
+            for name in big:
+                assert same_words(big[name], little[name]), f"{name} of steps {c} .. {c + k - 1} differs from the chunked twin"
+            assert not bp.has_sentinel(little["obs"])
+            # the final observation is written exactly where an episode ended
+            end = ((cout.done[:k] != 0) | (cout.trunc[:k] != 0))
+            written = bp.words(cfin[:k]) != -1
+            assert torch.equal(written, end[:, None, :].expand(-1, 4, -1))
+            ended += int(end.sum())
+        assert ended > n and A.episode_count() == B.episode_count() == ended
+        assert same_words(engine_columns(A, "cartpole"), engine_columns(B, "cartpole"))
+    finally:
+        A.close(), B.close()
+
+
+@pytest.mark.parametrize("fam,n,K", ROLL_CASES, ids=lambda v: str(v))
+def test_rollouts_with_buffers_beyond_4gib(fam, n, K, report):
+    """every [K][n] word buffer beyond 4 GiB: mgym_rollout (obs_out NULL, auto-reset on, a limit of 3) against K plain steps of a twin handle, then
+    mgym_rollout_linear against a table rollout of the twin fed its actions_out.  Peak footprint: 27.3 GiB (Pendulum), 25.3 (MountainCar, MountainCarContinuous), 24.7 (Acrobot)."""
+    reserve(("roll", fam, n, K))
+    A, B = make(fam, n, auto_reset=True), make(fam, n, auto_reset=True)
+    try:
+        call(A, A.reset_device, None, None), call(B, B.reset_device, None, None)
+        acts = table(fam, K, n, seed=8)
+        oa, ob = Outputs(fam, n, (K,), obs=False), Outputs(fam, n, (K,), obs=False)
+        step = Outputs(fam, n, obs=False)
+        ela, elb = bp.sentinel((n,), I32, DEV), bp.sentinel((n,), I32, DEV)
+        report()
+        call(A, A.rollout_device, acts, K, *oa.args())
+        for t in range(K):
+            step.refill()
+            call(B, B.step_device, acts[t], *step.args())
+            for (name, x), y in zip(oa.named(t).items(), step.named().values()):
+                assert not bp.has_sentinel(y) and same_words(x, y), f"{fam} n={n}: {name} of step {t} of the rollout differs from the plain step"
+
+        def same_state(what):
+            elapsed_of(A, fam, ela), elapsed_of(B, fam, elb)
+            assert same_words(engine_columns(A, fam), engine_columns(B, fam)) and same_words(ela, elb), what
+            assert A.episode_count() == B.episode_count(), what
+
+        same_state("after mgym_rollout")
+        assert A.episode_count() == finished(oa) >= 2 * n   # the limit of 3 ends every episode at least twice in 9 steps
+        pol = np.random.default_rng(12).normal(0, 1, FAMILIES[fam]["lin"]).astype(np.float32)
+        oa.refill(), ob.refill(), bp.fill_sentinel(acts)
+        call(A, A.rollout_linear_device, pol, K, acts, *oa.args())
+        assert not bp.has_sentinel(acts)
+        call(B, B.rollout_device, acts, K, *ob.args())
+        for (name, x), y in zip(oa.named().items(), ob.named().values()):
+            assert not bp.has_sentinel(x) and same_words(x, y), f"{fam} n={n}: {name} of mgym_rollout_linear differs from the table rollout of its actions"
+        same_state("after mgym_rollout_linear")
+    finally:
+        A.close(), B.close()
+
+
+def gae_inputs():
+    """periodic in the environment with period P, seeded along t: the [K][P] bases on the host (what tests/gae_ref.py restates) and the [K][n] device tensors"""
+    import gae_ref as R
+    rng = np.random.default_rng(4257)
+    K = GAE_K
+    r, v = rng.uniform(-16, 1, (K, P)).astype(np.float32), rng.uniform(-100, 100, (K, P)).astype(np.float32)
+    lv = rng.uniform(-100, 100, P).astype(np.float32)
+    d = ((rng.random((K, P)) < 0.02) * rng.integers(1, 256, (K, P))).astype(np.uint8)   # any non-zero byte is a set flag
+    u = ((rng.random((K, P)) < 0.02) * rng.integers(1, 256, (K, P))).astype(np.uint8)
+    fv = R.poisoned_final_value(rng, d, u)   # a NaN in every word the definition does not select
+    assert ((d != 0) & (u != 0)).any() and ((d != 0) & (u == 0)).any() and ((d == 0) & (u != 0)).any()
+    return dict(r=r, v=v, lv=lv, d=d, u=u, fv=fv)
+
+
+def reward_buffer(host, n, mis):
+    """the [K][n] tiling of `host` inside a buffer of K n + 4 floats: at its start (16-byte aligned) or one word in"""
+    K = host.shape[0]
+    store = bp.sentinel((K * n + 4,), F32, DEV)
+    view = store[1: K * n + 1] if mis else store[: K * n]
+    src = torch.from_numpy(host).to(DEV)
+    view.view(K, n).unflatten(1, (n // P, P)).copy_(src.unsqueeze(1))
+    return store, view.view(K, n)
+
+
+@pytest.mark.parametrize("mis", [0, 1], ids=["four-per-lane", "one-per-lane"])
+def test_gae_with_buffers_beyond_4gib(mis, report):
+    """mgym_gae at n = 2^22, K = 257: each float buffer is 4.03 GiB.  Inputs periodic in the environment (P = 4096), done and truncated at 2 %, a NaN in
+    every final_value word the definition does not read; adv_out and ret_out are the first 4096 environments tiled, and those equal tests/gae_ref.py word
+    for word.  The reward pointer 4 bytes off its alignment takes the one-environment-per-lane kernel.  Peak footprint: 24.2 GiB."""
+    import gae_ref as R
+    n, K = GAE_N, GAE_K
+    reserve(("gae", "cartpole", n, K))
+    c = gae_inputs()
+    exp = R.gae(c["r"], c["d"], c["u"], c["v"], c["lv"], c["fv"], 0.99, 0.95)
+    env = mg.VecEnv(mg.CARTPOLE, n)
+    try:
+        dev = {k: bp.tile_last(torch.from_numpy(c[k]).to(DEV), n) for k in ("v", "lv", "d", "u", "fv")}
+        store, r = reward_buffer(c["r"], n, mis)
+        assert r.data_ptr() % 16 == 4 * mis
+        adv, ret = bp.sentinel((K, n), F32, DEV), bp.sentinel((K, n), F32, DEV)
+        report()
+        call(env, env.gae_device, K, r, dev["d"], dev["u"], dev["v"], dev["lv"], dev["fv"], 0.99, 0.95, adv, ret)
+        for name, got, e in (("adv_out", adv, exp[0]), ("ret_out", ret, exp[1])):
+            assert np.isfinite(e).all()
+            bp.assert_periodic(got, P, f"mgym_gae {name}")
+            assert np.array_equal(got[:, :P].cpu().numpy().view(np.uint32), e.view(np.uint32)), f"{name}: the first {P} environments differ from the restatement"
+    finally:
+        env.close()
+
+
+@pytest.mark.parametrize("mis", [0, 1], ids=["four-per-lane", "one-per-lane"])
+def test_episode_returns_with_buffers_beyond_4gib(mis, report):
+    """mgym_episode_returns at n = 2^22 as two calls, K = 200 then K = 57 into the rows behind, so the carry is covered: return_out and length_out (written
+    only where an episode ended, the sentinel elsewhere) and the carry are the first 4096 environments tiled, and those equal tests/gae_ref.py.
+    Peak footprint: 16.2 GiB."""
+    import gae_ref as R
+    n, K = GAE_N, GAE_K
+    reserve(("ep", "cartpole", n, K))
+    c = gae_inputs()
+    acc0, len0 = np.full(P, -2.5, np.float32), np.full(P, 3, np.uint32)
+    env = mg.VecEnv(mg.CARTPOLE, n)
+    try:
+        d, u = (bp.tile_last(torch.from_numpy(c[k]).to(DEV), n) for k in ("d", "u"))
+        store, r = reward_buffer(c["r"], n, mis)
+        acc, length = bp.tile_last(torch.from_numpy(acc0).to(DEV), n), bp.tile_last(torch.from_numpy(len0.view(np.int32)).to(DEV), n)
+        ret, ln = bp.sentinel((K, n), F32, DEV), bp.sentinel((K, n), I32, DEV)
+        report()
+        e_acc, e_len = acc0, len0
+        t0 = 0
+        for k in EP_SPLIT:
+            sl = slice(t0, t0 + k)
+            call(env, env.episode_returns_device, k, r[sl], d[sl], u[sl], acc, length, ret[sl], ln[sl])
+            e_acc, e_len, e_ret, e_ln = R.episode_returns(c["r"][sl], c["d"][sl], c["u"][sl], e_acc, e_len, fill=0xFFFFFFFF)
+            for name, got, e in (("return_out", ret[sl], e_ret), ("length_out", ln[sl], e_ln), ("ep_return", acc, e_acc), ("ep_length", length, e_len)):
+                bp.assert_periodic(got, P, f"mgym_episode_returns rows {t0} .. {t0 + k - 1} {name}", written=False)
+                g = bp.words(got)[..., :P].cpu().numpy().view(np.uint32)
+                assert np.array_equal(g, np.ascontiguousarray(e).view(np.uint32)), f"{name} of rows {t0} .. {t0 + k - 1}: the first {P} environments differ from the restatement"
+            t0 += k
+        assert (e_ln != 0xFFFFFFFF).any()
+    finally:
+        env.close()
+
+
+# ---- 4. LunarLander: records beyond 4 GiB -----------------------------------------------------------------------------------------------------
+def test_lunar_lander_records_beyond_4gib(report):
+    """n = 3 735 552 (n_pad * 1152 B >= 2^32: the persistent rollout is off, info()["rollout"] == "k_steps"), the default launch order, seeded reset, wind,
+    auto-reset: 72 mgym_step calls under a periodic table; every 8 steps and at the end every output, the engine's observation and the elapsed counts
+    equal, in every window, a 4096-environment handle at the same global ids.  Peak footprint: 18.4 GiB (twelve handles: half a GiB each whatever the population)."""
+    n = LL_N
+    reserve(("ll", "lunarlander", n, LL_STEPS))
+    env = make("lunarlander", n, auto_reset=True)
+    wins = bp.windows(n, SEED, n, 1, record_bytes=LL_RECORD_BYTES)
+    assert len(wins) <= N_WINDOWS + 1 and any(a * LL_RECORD_BYTES < 1 << 32 <= b * LL_RECORD_BYTES for a, b in wins)
+    twins = [make("lunarlander", b - a, auto_reset=True, env_id_base=a) for a, b in wins]
+    try:
+        assert env.info()["rollout"] == "k_steps"
+        for e in [env] + twins:
+            call(e, e.reset_device, None, None)
+        acts = bp.periodic_actions(LL_STEPS, n, P, n_actions=4, seed=13, device=DEV)
+        out, el = Outputs("lunarlander", n), bp.sentinel((n,), I32, DEV)
+        wout = [(Outputs("lunarlander", b - a), bp.sentinel((b - a,), I32, DEV)) for a, b in wins]
+        total = 0
+        report()
+        for t in range(LL_STEPS):
+            out.refill()
+            call(env, env.step_device, acts[t], *out.args())
+            total += finished(out)
+            for k, (a, b) in enumerate(wins):
+                wout[k][0].refill()
+                call(twins[k], twins[k].step_device, acts[t, a:b].contiguous(), *wout[k][0].args())
+            if (t + 1) % LL_EVERY and t + 1 != LL_STEPS:
+                continue
+            elapsed_of(env, "lunarlander", el)
+
+            def make_small(k, a, b):
+                elapsed_of(twins[k], "lunarlander", wout[k][1])
+                return dict(wout[k][0].named(), columns=engine_columns(twins[k], "lunarlander"), elapsed=wout[k][1])
+
+            bp.assert_windows_equal(dict(out.named(), columns=engine_columns(env, "lunarlander"), elapsed=el), make_small, wins, f"LunarLander step {t}:")
+        assert total > 0 and env.episode_count() == total   # contacts and crashes occurred
+        report()
+    finally:
+        for e in [env] + twins:
+            e.close()
