@@ -401,6 +401,7 @@ struct AcrobotEnv final : ClassicEnv {
         dev.obs = f; dev.n_pad = n_pad;
         dev.episode = reinterpret_cast<uint32_t*>(f + 8 * n_pad);
         fill_common(dev);
+        step4_max = 1ull << 26;   // (acrobot_step4_kernel's 32-bit offsets reach 7 columns in)
         return MGYM_OK;
     }
 
@@ -408,99 +409,45 @@ struct AcrobotEnv final : ClassicEnv {
     int reset_deterministic(float* obs_out) override { return launch_per_env(acrobot_zero_kernel, dev, obs_out); }
 
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        const bool vec = vec_ok(act, obs_out, reward, done, trunc);
-        const dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
-        const bool tl = dev.limit != 0u;
-        if (vec && n % 4 == 0 && n <= (1ull << 26)) {  // the structured 16-byte kernel
-            dim3 g;
-            const bool one = step4_grid(g);
-            if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
-                with_bools([&](auto T, auto O) {
-                    hipLaunchKernelGGL((acrobot_step4_kernel<true, decltype(T)::value, decltype(O)::value, float*>), g, b, 0, stream, dev.obs, (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed,
-                                       dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, final_obs);
-                }, tl, one);
-                MGYM_HIP(hipGetLastError());
-                return MGYM_OK;
-            }
-            with_bools([&](auto R, auto T, auto O) {
-                hipLaunchKernelGGL((acrobot_step4_kernel<decltype(R)::value, decltype(T)::value, decltype(O)::value>), g, b, 0, stream, dev.obs, (uint32_t)n_pad, (uint32_t)n, act,
-                                   dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit);
-            }, dev.auto_reset != 0, tl, one);
-            MGYM_HIP(hipGetLastError());
-            return MGYM_OK;
-        }
-        with_bools([&](auto T, auto V) {
-            constexpr int VEC = decltype(V)::value ? 4 : 1;
-            if (final_obs) hipLaunchKernelGGL((acrobot_step_kernel<VEC, decltype(T)::value, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
-            else hipLaunchKernelGGL((acrobot_step_kernel<VEC, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }, tl, vec);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
+        return launch_step(act, obs_out, reward, done, trunc,
+            [&](dim3 g, auto R, auto T, auto O, auto... fin) {
+                hipLaunchKernelGGL((acrobot_step4_kernel<decltype(R)::value, decltype(T)::value, decltype(O)::value, decltype(fin)...>), g, dim3(kBlock), 0, stream, dev.obs, (uint32_t)n_pad, (uint32_t)n,
+                                   act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, fin...);
+            },
+            [&](dim3 g, auto V, auto T, auto... fin) {
+                hipLaunchKernelGGL((acrobot_step_kernel<decltype(V)::value ? 4 : 1, decltype(T)::value, decltype(fin)...>), g, dim3(kBlock), 0, stream, dev, act, obs_out, reward, done, trunc, fin...);
+            });
     }
 
-    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the categorical draw's seed and call word
-    template <int POLICY, bool TL>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
-                        const AbPolicyArg<POLICY>& arg = AbPolicyArg<POLICY>{}, UniformDraw uni = {}) {
-        if (final_obs) hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, final_obs);
-        else hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
-    }
-
-    // the same for a two-hidden-layer source: its Mlp2Net at the head of the trailing pack
-    template <int POLICY, bool TL>
-    void launch_rollout_mlp2(uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const Mlp2Net<6, 3>& net, UniformDraw uni) {
-        const uint32_t* none = nullptr;
-        if (final_obs) hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, Mlp2Net<6, 3>, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, AbLinearPolicy{}, act_out, uni, net, final_obs);
-        else hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, Mlp2Net<6, 3>>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, AbLinearPolicy{}, act_out, uni, net);
+    // the one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the
+    // categorical draw's seed and call word; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
+    template <int POLICY, class... Net>
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const AbPolicyArg<POLICY>& arg, UniformDraw uni,
+                        Net... net) {
+        with_bools([&](auto T) {
+            constexpr bool TL = decltype(T)::value;
+            if (final_obs) hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, Net..., float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net..., final_obs);
+            else hipLaunchKernelGGL((acrobot_rollout_kernel<POLICY, TL, Net...>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net...);
+        }, dev.limit != 0u);
     }
 
     void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        with_bools([&](auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); }, dev.limit != 0u);
+        launch_rollout<ROLL_ACT_TABLE>(act, nullptr, K, obs_out, reward, done, trunc, AbLinearPolicy{}, UniformDraw{});
     }
 
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (roll_act_gauss(call.source)) { set_last_error(std::string(call.api) + ": Acrobot has discrete actions: use mgym_rollout_mlp_sample"); return MGYM_ERR_BAD_ARG; }   // (the C ABI refuses it first)
-        if (!fused_rollout_args_ok(call.api, n, K, false, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
-        if (roll_act_is_mlp2(call.source)) { if (const int st = mlp2_store(call, 6, 3)) return st; }
-        with_bools([&](auto T) {
-            constexpr bool TL = decltype(T)::value;
-            if (roll_act_is_mlp2(call.source)) {   // (the pack is on the stream already)
-                with_mlp2_source([&](auto S) {
-                    constexpr int SRC = decltype(S)::value;
-                    if constexpr (roll_act_mlp2_head(SRC) != MLP2_HEAD_GAUSS) launch_rollout_mlp2<SRC, TL>(ao, K, obs_out, reward, done, trunc, mlp2_net<6, 3>(call), UniformDraw{call.seed, call.call});
-                }, call.source);
-                return;
-            }
-            switch (call.source) {
-            case ROLL_ACT_UNIFORM:
-                launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, AbLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});
-                break;
-            case ROLL_ACT_LINEAR: {
-                AbLinearPolicy lin{};   // weights: 3 rows of (6 weights, bias)
+        const char* refusal = roll_act_gauss(call.source) ? ": Acrobot has discrete actions: use mgym_rollout_mlp_sample" : nullptr;   // (the C ABI refuses it first)
+        return rollout_policy_classic<6, 3, roll_act_discrete_takes>(call, K, actions_out, obs_out, reward, done, trunc, false, refusal,
+            [](const float* w) {   // weights: 3 rows of (6 weights, bias)
+                AbLinearPolicy lin{};
                 for (int j = 0; j < 3; ++j) {
-                    for (int q = 0; q < 6; ++q) lin.w[j][q] = call.weights[7 * j + q];
-                    lin.b[j] = call.weights[7 * j + 6];
+                    for (int q = 0; q < 6; ++q) lin.w[j][q] = w[7 * j + q];
+                    lin.b[j] = w[7 * j + 6];
                 }
-                launch_rollout<ROLL_ACT_LINEAR, TL>(nullptr, ao, K, obs_out, reward, done, trunc, lin);
-                break;
-            }
-            default: {   // the hidden-layer sources
-                MlpPack<6, 3> pack;
-                mlp_pack<6, 3>(call.weights, call.hidden, pack);
-                with_mlp_act([&](auto H) {
-                    constexpr int ACT = decltype(H)::value;
-                    if (!roll_act_samples(call.source)) launch_rollout<roll_act_mlp_plain(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
-                    else launch_rollout<roll_act_mlp_sample(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
-                }, call.source);
-            }
-            }
-        }, dev.limit != 0u);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
+                return lin;
+            },
+            [&](auto S, const auto& arg, auto... draw_net) { launch_rollout<decltype(S)::value>(nullptr, static_cast<uint32_t*>(actions_out), K, obs_out, reward, done, trunc, arg, draw_net...); });
     }
 
     int get_state(void* blob) override { return launch_per_env(acrobot_export_kernel, dev, static_cast<uint32_t*>(blob)); }

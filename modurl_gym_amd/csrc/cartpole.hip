@@ -522,14 +522,7 @@ struct CartPoleEnv final : Env {
         return MGYM_OK;
     }
 
-    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override {
-        if (n == 0) return MGYM_OK;
-        int al = aligned(m0, 4) && aligned(m1, 4);
-        hipLaunchKernelGGL(cartpole_reset_kernel, dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, stream, dev, m0, m1,
-                           all ? 1 : 0, al, obs_out);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) override { return launch_reset(cartpole_reset_kernel, dev, m0, m1, all, obs_out); }
 
     int reset_deterministic(float* obs_out) override {  // cartpole.rs:437-442: self.reset()? then state = zeros
         int st = reset(nullptr, nullptr, true, nullptr);
@@ -569,20 +562,22 @@ struct CartPoleEnv final : Env {
         return MGYM_OK;
     }
 
-    template <int POLICY>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, uint64_t pseed, uint32_t pcall, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
-                        const CpPolicyArg<POLICY>& lin = CpPolicyArg<POLICY>{}) {
+    // the one launch of the fused rollout kernel with the action source POLICY; `lin`: the linear words or the hidden-layer pack, `uni`: the policy seed and call
+    // word of a drawing source; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
+    template <int POLICY, class... Net>
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const CpPolicyArg<POLICY>& lin, UniformDraw uni,
+                        Net... net) {
         const dim3 g(grid_for(n / 4)), b(kBlock);
         if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
             with_bools([&](auto E, auto S) {
-                hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(S)::value, true, POLICY, float*>), g, b, 0, stream, dev, act, act_out, pseed, pcall, lin, K, obs_out,
-                                   reward, done, trunc, final_obs);
+                hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(S)::value, true, POLICY, Net..., float*>), g, b, 0, stream, dev, act, act_out, uni.seed, uni.call, lin, K,
+                                   obs_out, reward, done, trunc, net..., final_obs);
             }, cfg.is_euler, cfg.sutton_barto_reward);
             return;
         }
         with_bools([&](auto E, auto S, auto R) {
-            hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(S)::value, decltype(R)::value, POLICY>), g, b, 0, stream, dev, act, act_out, pseed, pcall, lin, K, obs_out,
-                               reward, done, trunc);
+            hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(S)::value, decltype(R)::value, POLICY, Net...>), g, b, 0, stream, dev, act, act_out, uni.seed, uni.call, lin, K,
+                               obs_out, reward, done, trunc, net...);
         }, cfg.is_euler, cfg.sutton_barto_reward, auto_reset);
     }
 
@@ -590,62 +585,15 @@ struct CartPoleEnv final : Env {
         if (n == 0 || K == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
         if (!fused_rollout_args_ok(nullptr, n, K, true, act, obs_out, reward, done, trunc)) return Env::rollout(actions, K, obs_out, reward, done, trunc);  // K plain steps
-        launch_rollout<ROLL_ACT_TABLE>(act, nullptr, 0, 0, K, obs_out, reward, done, trunc);
+        launch_rollout<ROLL_ACT_TABLE>(act, nullptr, K, obs_out, reward, done, trunc, LinearPolicy{}, UniformDraw{});
         MGYM_HIP(hipGetLastError());
         return MGYM_OK;
     }
 
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (!fused_rollout_args_ok(call.api, n, K, true, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
-        if (roll_act_is_mlp2(call.source)) {   // the pack goes on the stream ahead of the launch
-            if (const int st = mlp2_store(call, 4, 2)) return st;
-            with_mlp2_source([&](auto S) {
-                constexpr int SRC = decltype(S)::value;
-                if constexpr (roll_act_mlp2_head(SRC) != MLP2_HEAD_GAUSS) {
-                    const dim3 g(grid_for(n / 4)), b(kBlock);
-                    const uint32_t* none = nullptr;
-                    const Mlp2Net<4, 2> net = mlp2_net<4, 2>(call);
-                    if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
-                        with_bools([&](auto E, auto B) {
-                            hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(B)::value, true, SRC, Mlp2Net<4, 2>, float*>), g, b, 0, stream, dev, none, ao, call.seed, call.call, LinearPolicy{}, K,
-                                               obs_out, reward, done, trunc, net, final_obs);
-                        }, cfg.is_euler, cfg.sutton_barto_reward);
-                    } else {
-                        with_bools([&](auto E, auto B, auto R) {
-                            hipLaunchKernelGGL((cartpole_rollout_kernel<decltype(E)::value, decltype(B)::value, decltype(R)::value, SRC, Mlp2Net<4, 2>>), g, b, 0, stream, dev, none, ao, call.seed, call.call, LinearPolicy{}, K,
-                                               obs_out, reward, done, trunc, net);
-                        }, cfg.is_euler, cfg.sutton_barto_reward, auto_reset);
-                    }
-                }
-            }, call.source);
-            MGYM_HIP(hipGetLastError());
-            return MGYM_OK;
-        }
-        switch (call.source) {
-        case ROLL_ACT_UNIFORM:
-            launch_rollout<ROLL_ACT_UNIFORM>(nullptr, ao, call.seed, uniform_calls++, K, obs_out, reward, done, trunc);
-            break;
-        case ROLL_ACT_LINEAR: {
-            LinearPolicy lin;
-            for (int q = 0; q < 4; ++q) lin.w[q] = call.weights[q];
-            lin.b = call.weights[4];
-            launch_rollout<ROLL_ACT_LINEAR>(nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, lin);
-            break;
-        }
-        default: {   // the hidden-layer sources
-            CpMlpPack pack;
-            mlp_pack<4, 2>(call.weights, call.hidden, pack);
-            with_mlp_act([&](auto H) {
-                constexpr int ACT = decltype(H)::value;
-                if (roll_act_samples(call.source)) launch_rollout<roll_act_mlp_sample(ACT)>(nullptr, ao, call.seed, call.call, K, obs_out, reward, done, trunc, pack);
-                else launch_rollout<roll_act_mlp_plain(ACT)>(nullptr, ao, 0, 0, K, obs_out, reward, done, trunc, pack);
-            }, call.source);
-        }
-        }
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
+        return rollout_policy_classic<4, 2, roll_act_discrete_takes>(call, K, actions_out, obs_out, reward, done, trunc, true, nullptr,
+            [](const float* w) { return LinearPolicy{{w[0], w[1], w[2], w[3]}, w[4]}; },
+            [&](auto S, const auto& arg, auto... draw_net) { launch_rollout<decltype(S)::value>(nullptr, static_cast<uint32_t*>(actions_out), K, obs_out, reward, done, trunc, arg, draw_net...); });
     }
 
     int observation(const float** obs, uint64_t* col_stride) override {
@@ -654,21 +602,8 @@ struct CartPoleEnv final : Env {
         return MGYM_OK;
     }
 
-    int get_state(void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(cartpole_export_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           dev, static_cast<uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
-    int set_state(const void* blob) override {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(cartpole_import_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                           dev, static_cast<const uint32_t*>(blob));
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
+    int get_state(void* blob) override { return launch_per_env(cartpole_export_kernel, dev, static_cast<uint32_t*>(blob)); }
+    int set_state(const void* blob) override { return launch_per_env(cartpole_import_kernel, dev, static_cast<const uint32_t*>(blob)); }
 };
 
 Env* make_cartpole() { return new CartPoleEnv(); }

@@ -1,5 +1,6 @@
 // classic_env.h — the host side MountainCar, Pendulum and Acrobot share (mountain_car.hip, pendulum.hip, acrobot.hip): the engine's columns and
-// elapsed counts, the launch geometry of their kernels, and the entry points that do not depend on a family's Dev struct or kernels.
+// elapsed counts, the one step launch (launch_step: kernel, grid and form; a family names its two kernels), and the entry points that do not depend on
+// a family's Dev struct or kernels.
 #pragma once
 #include "common.h"
 #include "soa4.h"
@@ -33,23 +34,6 @@ struct ClassicEnv : Env {
     }
     virtual void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) = 0;
 
-    // one thread per environment: export, import, zero
-    template <class Kernel, class... Args>
-    int launch_per_env(Kernel kernel, Args... args) {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, args...);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-    // a family's reset kernel (Dev, m0, m1, all, masks_aligned, obs_out), one lane per group of 4 environments
-    template <class Kernel, class Dev>
-    int launch_reset(Kernel kernel, const Dev& dev, const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) {
-        if (n == 0) return MGYM_OK;
-        hipLaunchKernelGGL(kernel, dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, stream, dev, m0, m1, all ? 1 : 0, aligned(m0, 4) && aligned(m1, 4) ? 1 : 0, obs_out);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
-    }
-
     // the caller's buffers allow 16-byte accesses (the VEC = 4 kernels; with n % 4 == 0 and n within the family's bound, the step4 kernel)
     bool vec_ok(const void* act, const float* obs_out, const float* reward, const uint8_t* done, const uint8_t* trunc) const {
         return aligned(act, 16) && aligned(reward, 16) && aligned(done, 4) && aligned(trunc, 4) && (obs_out == nullptr || (aligned(obs_out, 16) && n % 4 == 0));
@@ -61,6 +45,31 @@ struct ClassicEnv : Env {
         const bool one = nb <= (uint64_t)max_blocks;
         g = dim3((unsigned)(one ? nb : (uint64_t)max_blocks));
         return one;
+    }
+    uint64_t step4_max = 1ull << 27;   // the largest population the family's step4 kernel addresses (Acrobot: 2^26)
+    // the channel of mgym_set_final_obs_out has something to deliver (only auto-reset handles hold a pointer)
+    virtual bool final_live() const { return final_obs != nullptr; }
+
+    // step() of the three families: the choice of kernel and grid, and the run-time bools as std::bool_constant arguments of the family's two launches.
+    // `step4(grid, RESET, TL, ONE, fin...)` names its structured 16-byte kernel, `step1(grid, VEC4, TL, fin...)` its generic one; fin... is final_obs
+    // where the channel is live (then RESET is on: only auto-reset handles hold a pointer) and nothing otherwise.
+    template <class Step4, class Step1>
+    int launch_step(const void* act, const float* obs_out, const float* reward, const uint8_t* done, const uint8_t* trunc, Step4&& step4, Step1&& step1) {
+        if (n == 0) return MGYM_OK;
+        const bool vec = vec_ok(act, obs_out, reward, done, trunc), tl = cfg.max_episode_steps != 0u, fin = final_live();
+        const dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n));
+        if (vec && n % 4 == 0 && n <= step4_max) {  // the structured 16-byte kernel
+            dim3 g;
+            const bool one = step4_grid(g);
+            if (fin) with_bools([&](auto T, auto O) { step4(g, std::true_type{}, T, O, final_obs); }, tl, one);
+            else with_bools([&](auto R, auto T, auto O) { step4(g, R, T, O); }, (cfg.flags & MGYM_FLAG_AUTO_RESET) != 0, tl, one);
+        } else if (fin) {
+            with_bools([&](auto T, auto V) { step1(decltype(V)::value ? gv : gs, V, T, final_obs); }, tl, vec);
+        } else {
+            with_bools([&](auto T, auto V) { step1(decltype(V)::value ? gv : gs, V, T); }, tl, vec);
+        }
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
     }
 };
 

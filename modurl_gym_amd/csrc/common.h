@@ -103,6 +103,52 @@ struct Env {
     template <int D, int A>
     Mlp2Net<D, A> mlp2_net(const PolicyCall& call) const { return Mlp2Net<D, A>{mlp2_dev, call.hidden, call.hidden2, call.sigma}; }
     uint32_t uniform_calls = 0;  // mgym_rollout_uniform calls that launched so far (Philox counter word of the policy stream)
+    // rollout_policy of the classic families (observation width D, A scores; `bound32`: fused_rollout_args_ok), whose fused kernels differ in name and config
+    // only.  The family hands in what it owns.  TAKES: the sources it has kernels for; none is instantiated for another, and a call with one launches
+    // nothing (the C ABI refuses it first).  `refusal`: the tail of the message where the family refuses the call itself, else null.  `linear`: its
+    // linear-policy struct from call.weights.  `launch(S, arg, draw, net...)`: its one launch template with the source S, the policy argument (the linear
+    // struct, value-initialised where the source reads none, or the hidden-layer pack), the draw (zeros where the source draws nothing), and for
+    // a two-hidden-layer source its Mlp2Net, the head of the kernel's trailing pack (the weights are on the stream by then).
+    template <int D, int A, bool (*TAKES)(int), class Linear, class Launch>
+    int rollout_policy_classic(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, bool bound32,
+                               const char* refusal, Linear&& linear, Launch&& launch) {
+        if (n == 0 || K == 0) return MGYM_OK;
+        if (refusal) { set_last_error(std::string(call.api) + refusal); return MGYM_ERR_BAD_ARG; }
+        if (!fused_rollout_args_ok(call.api, n, K, bound32, actions_out, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
+        if (roll_act_is_mlp2(call.source)) { if (const int st = mlp2_store(call, D, A)) return st; }
+        with_policy_source([&](auto S) {
+            constexpr int SRC = decltype(S)::value;
+            if constexpr (!TAKES(SRC)) return;
+            else if constexpr (roll_act_is_mlp2(SRC)) launch(S, decltype(linear(call.weights)){}, UniformDraw{call.seed, call.call}, mlp2_net<D, A>(call));
+            else if constexpr (SRC == ROLL_ACT_UNIFORM) launch(S, decltype(linear(call.weights)){}, UniformDraw{call.seed, uniform_calls++});
+            else if constexpr (SRC == ROLL_ACT_LINEAR) launch(S, linear(call.weights), UniformDraw{});
+            else {   // the hidden-layer sources
+                MlpPack<D, A> pack;
+                mlp_pack<D, A>(call.weights, call.hidden, pack);
+                if constexpr (roll_act_gauss(SRC)) launch(S, pack, GaussDraw{call.seed, call.call, call.sigma});
+                else if constexpr (roll_act_samples(SRC)) launch(S, pack, UniformDraw{call.seed, call.call});
+                else launch(S, pack, UniformDraw{});
+            }
+        }, call.source);
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+    // one thread per environment: export, import, zero
+    template <class Kernel, class... Args>
+    int launch_per_env(Kernel kernel, Args... args) {
+        if (n == 0) return MGYM_OK;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, args...);
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
+    // a classic family's reset kernel (Dev, m0, m1, all, masks_aligned, obs_out), one lane per group of 4 environments
+    template <class Kernel, class Dev>
+    int launch_reset(Kernel kernel, const Dev& dev, const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) {
+        if (n == 0) return MGYM_OK;
+        hipLaunchKernelGGL(kernel, dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, stream, dev, m0, m1, all ? 1 : 0, aligned(m0, 4) && aligned(m1, 4) ? 1 : 0, obs_out);
+        MGYM_HIP(hipGetLastError());
+        return MGYM_OK;
+    }
     virtual int observation(const float** obs, uint64_t* col_stride) = 0;
     virtual int get_state(void* blob) = 0;
     virtual int set_state(const void* blob) = 0;

@@ -442,102 +442,52 @@ struct MountainCarEnv final : ClassicEnv {
     }
 
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        const bool vec = vec_ok(act, obs_out, reward, done, trunc);
-        dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
-        const bool tl = dev.limit != 0u;
-        if (vec && n % 4 == 0 && n <= (1ull << 27)) {  // the structured 16-byte kernel
-            dim3 g;
-            const bool one = step4_grid(g);
-            if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)
-                with_bools([&](auto C, auto T, auto O) {
-                    hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, true, decltype(T)::value, decltype(O)::value, float*>), g, b, 0, stream, dev.pos, (uint32_t)n_pad,
-                                       (uint32_t)n, act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.p.goal_velocity,
-                                       final_obs);
-                }, continuous, tl, one);
-                MGYM_HIP(hipGetLastError());
-                return MGYM_OK;
-            }
-            with_bools([&](auto C, auto T, auto R, auto O) {
-                hipLaunchKernelGGL((mountaincar_step4_kernel<decltype(C)::value, decltype(R)::value, decltype(T)::value, decltype(O)::value>), g, b, 0, stream, dev.pos,
-                                   (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc,
-                                   dev.limit, dev.p.goal_velocity);
-            }, continuous, tl, dev.auto_reset != 0, one);
-            MGYM_HIP(hipGetLastError());
-            return MGYM_OK;
-        }
-        with_bools([&](auto C, auto T, auto V) {
-            constexpr int VEC = decltype(V)::value ? 4 : 1;
-            if (final_obs) hipLaunchKernelGGL((mountaincar_step_kernel<VEC, decltype(C)::value, decltype(T)::value, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
-            else hipLaunchKernelGGL((mountaincar_step_kernel<VEC, decltype(C)::value, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }, continuous, tl, vec);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
+        int st = MGYM_OK;
+        with_bools([&](auto C) {
+            constexpr bool CONT = decltype(C)::value;
+            st = launch_step(act, obs_out, reward, done, trunc,
+                [&](dim3 g, auto R, auto T, auto O, auto... fin) {
+                    hipLaunchKernelGGL((mountaincar_step4_kernel<CONT, decltype(R)::value, decltype(T)::value, decltype(O)::value, decltype(fin)...>), g, dim3(kBlock), 0, stream, dev.pos, (uint32_t)n_pad,
+                                       (uint32_t)n, act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.p.goal_velocity, fin...);
+                },
+                [&](dim3 g, auto V, auto T, auto... fin) {
+                    hipLaunchKernelGGL((mountaincar_step_kernel<decltype(V)::value ? 4 : 1, CONT, decltype(T)::value, decltype(fin)...>), g, dim3(kBlock), 0, stream, dev, act, obs_out, reward, done, trunc, fin...);
+                });
+        }, continuous);
+        return st;
     }
 
-    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear weights or the hidden-layer pack, `uni`: the uniform stream, or the Gaussian draw's sigma, seed and call word
-    template <int POLICY, bool CONT, bool TL>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
-                        const McPolicyArg<CONT, POLICY>& arg = McPolicyArg<CONT, POLICY>{}, McDrawArg<POLICY> uni = {}) {
-        if (final_obs) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, final_obs);
-        else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
+    // the one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear weights or the hidden-layer pack, `uni`: the uniform stream, or the
+    // Gaussian draw's sigma, seed and call word; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
+    template <bool CONT, int POLICY, class... Net>
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const McPolicyArg<CONT, POLICY>& arg,
+                        McDrawArg<POLICY> uni, Net... net) {
+        with_bools([&](auto T) {
+            constexpr bool TL = decltype(T)::value;
+            if (final_obs) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL, Net..., float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net..., final_obs);
+            else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL, Net...>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net...);
+        }, dev.limit != 0u);
     }
 
     void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        with_bools([&](auto C, auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(C)::value, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); },
-                   continuous, dev.limit != 0u);
+        with_bools([&](auto C) { launch_rollout<decltype(C)::value, ROLL_ACT_TABLE>(act, nullptr, K, obs_out, reward, done, trunc, McLinearPolicy{}, UniformDraw{}); }, continuous);
     }
 
-    int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (!fused_rollout_args_ok(call.api, n, K, false, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
-        if (roll_act_is_mlp2(call.source)) { if (const int st = mlp2_store(call, 2, continuous ? 1 : 3)) return st; }
-        with_bools([&](auto C, auto T) {
-            constexpr bool CONT = decltype(C)::value, TL = decltype(T)::value;
-            if (roll_act_is_mlp2(call.source)) {   // (the pack is on the stream already; the C ABI refuses the head the family does not have)
-                with_mlp2_source([&](auto S) {
-                    constexpr int SRC = decltype(S)::value, HEAD = roll_act_mlp2_head(SRC);
-                    const Mlp2Net<2, CONT ? 1 : 3> net = mlp2_net<2, CONT ? 1 : 3>(call);
-                    if constexpr (HEAD == MLP2_HEAD_GREEDY || (CONT ? HEAD == MLP2_HEAD_GAUSS : HEAD == MLP2_HEAD_SAMPLE)) {
-                        const uint32_t* none = nullptr;
-                        const UniformDraw uni{call.seed, call.call};
-                        if (final_obs) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, SRC, TL, Mlp2Net<2, CONT ? 1 : 3>, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni, net, final_obs);
-                        else hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, SRC, TL, Mlp2Net<2, CONT ? 1 : 3>>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, McLinearPolicy{}, ao, uni, net);
-                    }
-                }, call.source);
-                return;
-            }
-            switch (call.source) {
-            case ROLL_ACT_UNIFORM:
-                launch_rollout<ROLL_ACT_UNIFORM, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, McLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});
-                break;
-            case ROLL_ACT_LINEAR: {
+    // Discrete(3) takes the categorical draws and A = 3 scores, Box(-1, 1) the Gaussian draws and the one force (the C ABI refuses the other's entry points and heads)
+    template <bool CONT>
+    int rollout_policy_of(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
+        return rollout_policy_classic<2, CONT ? 1 : 3, CONT ? roll_act_box_takes : roll_act_discrete_takes>(call, K, actions_out, obs_out, reward, done, trunc, false, nullptr,
+            [](const float* w) {   // weights: `rows` rows of (w_position, w_velocity, bias)
                 McLinearPolicy lin{};
-                constexpr int rows = CONT ? 1 : 3;   // weights: `rows` rows of (w_position, w_velocity, bias)
-                for (int j = 0; j < rows; ++j) { lin.w[j][0] = call.weights[3 * j + 0]; lin.w[j][1] = call.weights[3 * j + 1]; lin.b[j] = call.weights[3 * j + 2]; }
-                launch_rollout<ROLL_ACT_LINEAR, CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, lin);
-                break;
-            }
-            default: {   // the hidden-layer sources
-                MlpPack<2, CONT ? 1 : 3> pack;
-                mlp_pack<2, CONT ? 1 : 3>(call.weights, call.hidden, pack);
-                with_mlp_act([&](auto H) {
-                    constexpr int ACT = decltype(H)::value;
-                    if (roll_act_gauss(call.source)) {   // (the C ABI rejects mgym_rollout_mlp_gauss on discrete MountainCar)
-                        if constexpr (CONT) launch_rollout<roll_act_mlp_gauss(ACT), CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, GaussDraw{call.seed, call.call, call.sigma});
-                    } else if (!roll_act_samples(call.source)) {
-                        launch_rollout<roll_act_mlp_plain(ACT), CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
-                    } else if constexpr (!CONT) {   // (the C ABI rejects mgym_rollout_mlp_sample on MountainCarContinuous)
-                        launch_rollout<roll_act_mlp_sample(ACT), CONT, TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, UniformDraw{call.seed, call.call});
-                    }
-                }, call.source);
-            }
-            }
-        }, continuous, dev.limit != 0u);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
+                constexpr int rows = CONT ? 1 : 3;
+                for (int j = 0; j < rows; ++j) { lin.w[j][0] = w[3 * j + 0]; lin.w[j][1] = w[3 * j + 1]; lin.b[j] = w[3 * j + 2]; }
+                return lin;
+            },
+            [&](auto S, const auto& arg, auto... draw_net) { launch_rollout<CONT, decltype(S)::value>(nullptr, static_cast<uint32_t*>(actions_out), K, obs_out, reward, done, trunc, arg, draw_net...); });
+    }
+    int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
+        return continuous ? rollout_policy_of<true>(call, K, actions_out, obs_out, reward, done, trunc) : rollout_policy_of<false>(call, K, actions_out, obs_out, reward, done, trunc);
     }
 
     int get_state(void* blob) override { return launch_per_env(mountaincar_export_kernel, dev, static_cast<uint32_t*>(blob)); }

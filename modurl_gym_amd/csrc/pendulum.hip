@@ -366,111 +366,44 @@ struct PendulumEnv final : ClassicEnv {
     int reset_deterministic(float* obs_out) override { return launch_per_env(pendulum_zero_kernel, dev, obs_out); }
 
     int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0) return MGYM_OK;
         const uint32_t* act = static_cast<const uint32_t*>(actions);
-        const bool vec = vec_ok(act, obs_out, reward, done, trunc);
-        const dim3 gv(grid_for((n + 3) / 4)), gs(grid_for(n)), b(kBlock);
-        const bool tl = dev.limit != 0u;
-        if (vec && n % 4 == 0 && n <= (1ull << 27)) {  // the structured 16-byte kernel
-            dim3 g;
-            const bool one = step4_grid(g);
-            if (final_live()) {
-                with_bools([&](auto O) {
-                    hipLaunchKernelGGL((pendulum_step4_kernel<true, true, decltype(O)::value, float*>), g, b, 0, stream, dev.cs, (uint32_t)n_pad, (uint32_t)n, act, dev.elapsed, dev.seed,
-                                       dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.c_g, final_obs);
-                }, one);
-                MGYM_HIP(hipGetLastError());
-                return MGYM_OK;
-            }
-            with_bools([&](auto R, auto T, auto O) {
-                hipLaunchKernelGGL((pendulum_step4_kernel<decltype(R)::value, decltype(T)::value, decltype(O)::value>), g, b, 0, stream, dev.cs, (uint32_t)n_pad, (uint32_t)n, act,
-                                   dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.c_g);
-            }, dev.auto_reset != 0, tl, one);
-            MGYM_HIP(hipGetLastError());
-            return MGYM_OK;
-        }
-        if (final_live()) {
-            with_bools([&](auto V) {
-                hipLaunchKernelGGL((pendulum_step_kernel<decltype(V)::value ? 4 : 1, true, float*>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc, final_obs);
-            }, vec);
-            MGYM_HIP(hipGetLastError());
-            return MGYM_OK;
-        }
-        with_bools([&](auto T, auto V) {
-            hipLaunchKernelGGL((pendulum_step_kernel<decltype(V)::value ? 4 : 1, decltype(T)::value>), decltype(V)::value ? gv : gs, b, 0, stream, dev, act, obs_out, reward, done, trunc);
-        }, tl, vec);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
+        // (the final-observation forms exist with a time limit only: final_live())
+        return launch_step(act, obs_out, reward, done, trunc,
+            [&](dim3 g, auto R, auto T, auto O, auto... fin) {
+                if constexpr (decltype(T)::value || sizeof...(fin) == 0)
+                    hipLaunchKernelGGL((pendulum_step4_kernel<decltype(R)::value, decltype(T)::value, decltype(O)::value, decltype(fin)...>), g, dim3(kBlock), 0, stream, dev.cs, (uint32_t)n_pad,
+                                       (uint32_t)n, act, dev.elapsed, dev.seed, dev.env_id_base, dev.err, dev.done_count, obs_out, reward, done, trunc, dev.limit, dev.c_g, fin...);
+            },
+            [&](dim3 g, auto V, auto T, auto... fin) {
+                if constexpr (decltype(T)::value || sizeof...(fin) == 0)
+                    hipLaunchKernelGGL((pendulum_step_kernel<decltype(V)::value ? 4 : 1, decltype(T)::value, decltype(fin)...>), g, dim3(kBlock), 0, stream, dev, act, obs_out, reward, done, trunc, fin...);
+            });
     }
 
-    // one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the Gaussian draw's sigma, seed and call word
-    template <int POLICY, bool TL>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc,
-                        const PdPolicyArg<POLICY>& arg = PdPolicyArg<POLICY>{}, PdDrawArg<POLICY> uni = {}) {
-        if constexpr (TL) {
-            if (final_live()) {
-                hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, true, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, final_obs);
-                return;
-            }
-        }
-        hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni);
+    // the one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the
+    // Gaussian draw's sigma, seed and call word; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
+    template <int POLICY, class... Net>
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const PdPolicyArg<POLICY>& arg,
+                        PdDrawArg<POLICY> uni, Net... net) {
+        with_bools([&](auto T, auto F) {
+            constexpr bool TL = decltype(T)::value;
+            if constexpr (!decltype(F)::value) hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL, Net...>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net...);
+            else if constexpr (TL) hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, true, Net..., float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net..., final_obs);
+        }, dev.limit != 0u, final_live());
     }
 
-    // the same for a two-hidden-layer source: its Mlp2Net at the head of the trailing pack
-    template <int POLICY, bool TL>
-    void launch_rollout_mlp2(uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const Mlp2Net<3, 1>& net, UniformDraw uni) {
-        const uint32_t* none = nullptr;
-        if constexpr (TL) {
-            if (final_live()) {
-                hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, true, Mlp2Net<3, 1>, float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, PdLinearPolicy{}, act_out, uni, net, final_obs);
-                return;
-            }
-        }
-        hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL, Mlp2Net<3, 1>>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, none, K, obs_out, reward, done, trunc, PdLinearPolicy{}, act_out, uni, net);
-    }
-
-    // the channel of mgym_set_final_obs_out has something to deliver: without a time limit no Pendulum episode ever ends (and only auto-reset handles hold a pointer)
-    bool final_live() const { return final_obs != nullptr && dev.limit != 0u; }
+    // without a time limit no Pendulum episode ever ends
+    bool final_live() const override { return final_obs != nullptr && dev.limit != 0u; }
 
     void rollout_table(const uint32_t* act, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        with_bools([&](auto T) { launch_rollout<ROLL_ACT_TABLE, decltype(T)::value>(act, nullptr, K, obs_out, reward, done, trunc); }, dev.limit != 0u);
+        launch_rollout<ROLL_ACT_TABLE>(act, nullptr, K, obs_out, reward, done, trunc, PdLinearPolicy{}, UniformDraw{});
     }
 
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
-        if (n == 0 || K == 0) return MGYM_OK;
-        uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (roll_act_samples(call.source)) { set_last_error(std::string(call.api) + ": Pendulum has no discrete actions to draw from"); return MGYM_ERR_BAD_ARG; }   // (the C ABI refuses it first)
-        if (!fused_rollout_args_ok(call.api, n, K, false, ao, obs_out, reward, done, trunc)) return MGYM_ERR_BAD_ARG;
-        if (roll_act_is_mlp2(call.source)) { if (const int st = mlp2_store(call, 3, 1)) return st; }
-        with_bools([&](auto T) {
-            constexpr bool TL = decltype(T)::value;
-            if (roll_act_is_mlp2(call.source)) {   // (the pack is on the stream already)
-                with_mlp2_source([&](auto S) {
-                    constexpr int SRC = decltype(S)::value;
-                    if constexpr (roll_act_mlp2_head(SRC) != MLP2_HEAD_SAMPLE) launch_rollout_mlp2<SRC, TL>(ao, K, obs_out, reward, done, trunc, mlp2_net<3, 1>(call), UniformDraw{call.seed, call.call});
-                }, call.source);
-                return;
-            }
-            switch (call.source) {
-            case ROLL_ACT_UNIFORM:
-                launch_rollout<ROLL_ACT_UNIFORM, TL>(nullptr, ao, K, obs_out, reward, done, trunc, PdLinearPolicy{}, UniformDraw{call.seed, uniform_calls++});
-                break;
-            case ROLL_ACT_LINEAR:
-                launch_rollout<ROLL_ACT_LINEAR, TL>(nullptr, ao, K, obs_out, reward, done, trunc, PdLinearPolicy{{call.weights[0], call.weights[1], call.weights[2]}, call.weights[3]});
-                break;
-            default: {   // the hidden-layer sources
-                MlpPack<3, 1> pack;
-                mlp_pack<3, 1>(call.weights, call.hidden, pack);
-                with_mlp_act([&](auto H) {
-                    constexpr int ACT = decltype(H)::value;
-                    if (roll_act_gauss(call.source)) launch_rollout<roll_act_mlp_gauss(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack, GaussDraw{call.seed, call.call, call.sigma});
-                    else launch_rollout<roll_act_mlp_plain(ACT), TL>(nullptr, ao, K, obs_out, reward, done, trunc, pack);
-                }, call.source);
-            }
-            }
-        }, dev.limit != 0u);
-        MGYM_HIP(hipGetLastError());
-        return MGYM_OK;
+        const char* refusal = roll_act_samples(call.source) ? ": Pendulum has no discrete actions to draw from" : nullptr;   // (the C ABI refuses it first)
+        return rollout_policy_classic<3, 1, roll_act_box_takes>(call, K, actions_out, obs_out, reward, done, trunc, false, refusal,
+            [](const float* w) { return PdLinearPolicy{{w[0], w[1], w[2]}, w[3]}; },
+            [&](auto S, const auto& arg, auto... draw_net) { launch_rollout<decltype(S)::value>(nullptr, static_cast<uint32_t*>(actions_out), K, obs_out, reward, done, trunc, arg, draw_net...); });
     }
 
     int get_state(void* blob) override { return launch_per_env(pendulum_export_kernel, dev, static_cast<uint32_t*>(blob)); }

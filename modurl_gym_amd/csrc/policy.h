@@ -44,31 +44,20 @@ constexpr int roll_act_mlp_act(int source) {
 constexpr int roll_act_mlp_plain(int act) { return act == MLP_ACT_TANH_FAST ? ROLL_ACT_MLP_TANH_FAST : act == MLP_ACT_TANH ? ROLL_ACT_MLP_TANH : ROLL_ACT_MLP_RELU; }
 constexpr int roll_act_mlp_sample(int act) { return act == MLP_ACT_TANH_FAST ? ROLL_ACT_MLP_TANH_FAST_SAMPLE : act == MLP_ACT_TANH ? ROLL_ACT_MLP_TANH_SAMPLE : ROLL_ACT_MLP_RELU_SAMPLE; }
 constexpr int roll_act_mlp_gauss(int act) { return act == MLP_ACT_TANH_FAST ? ROLL_ACT_MLP_TANH_FAST_GAUSS : act == MLP_ACT_TANH ? ROLL_ACT_MLP_TANH_GAUSS : ROLL_ACT_MLP_RELU_GAUSS; }
-// from a run-time source to its activation as a template argument, as with_bools (common.h) does for bools: f(std::integral_constant<int, MLP_ACT_*>{})
-template <class F>
-void with_mlp_act(F&& f, int source) {
-    switch (roll_act_mlp_act(source)) {
-    case MLP_ACT_TANH_FAST: f(std::integral_constant<int, MLP_ACT_TANH_FAST>{}); break;
-    case MLP_ACT_TANH: f(std::integral_constant<int, MLP_ACT_TANH>{}); break;
-    default: f(std::integral_constant<int, MLP_ACT_RELU>{}); break;
-    }
-}
 // the two-hidden-layer sources: their activation (MLP_ACT_RELU or MLP_ACT_TANH_FAST), their head (MLP2_HEAD_*; -1 for any other source), and back
 constexpr bool roll_act_is_mlp2(int source) { return source >= ROLL_ACT_MLP2_RELU && source <= ROLL_ACT_MLP2_TANH_FAST_GAUSS; }
 constexpr int roll_act_mlp2_act(int source) { return ((source - ROLL_ACT_MLP2_RELU) & 1) ? MLP_ACT_TANH_FAST : MLP_ACT_RELU; }
 constexpr int roll_act_mlp2_head(int source) { return roll_act_is_mlp2(source) ? (source - ROLL_ACT_MLP2_RELU) / 2 : -1; }
 constexpr int roll_act_mlp2(int act, int head) { return ROLL_ACT_MLP2_RELU + 2 * head + (act == MLP_ACT_TANH_FAST ? 1 : 0); }
-// from a run-time two-hidden-layer source to the source as a template argument: f(std::integral_constant<int, ROLL_ACT_MLP2_*>{})
-template <class F>
-void with_mlp2_source(F&& f, int source) {
-    switch (source) {
-    case ROLL_ACT_MLP2_RELU: f(std::integral_constant<int, ROLL_ACT_MLP2_RELU>{}); break;
-    case ROLL_ACT_MLP2_TANH_FAST: f(std::integral_constant<int, ROLL_ACT_MLP2_TANH_FAST>{}); break;
-    case ROLL_ACT_MLP2_RELU_SAMPLE: f(std::integral_constant<int, ROLL_ACT_MLP2_RELU_SAMPLE>{}); break;
-    case ROLL_ACT_MLP2_TANH_FAST_SAMPLE: f(std::integral_constant<int, ROLL_ACT_MLP2_TANH_FAST_SAMPLE>{}); break;
-    case ROLL_ACT_MLP2_RELU_GAUSS: f(std::integral_constant<int, ROLL_ACT_MLP2_RELU_GAUSS>{}); break;
-    default: f(std::integral_constant<int, ROLL_ACT_MLP2_TANH_FAST_GAUSS>{}); break;
-    }
+// the policy sources a family with discrete actions has kernels for (all but the Gaussian draws), and one with a continuous action (all but the categorical)
+constexpr bool roll_act_discrete_takes(int source) { return !roll_act_gauss(source) && roll_act_mlp2_head(source) != MLP2_HEAD_GAUSS; }
+constexpr bool roll_act_box_takes(int source) { return !roll_act_samples(source) && roll_act_mlp2_head(source) != MLP2_HEAD_SAMPLE; }
+// from the run-time source of a PolicyCall to the source as a template argument, as with_bools (common.h) does for bools: f(std::integral_constant<int, ROLL_ACT_*>{})
+// for the one of ROLL_ACT_LINEAR .. ROLL_ACT_MLP2_TANH_FAST_GAUSS that `source` is (the table is no policy call)
+template <int S = ROLL_ACT_LINEAR, class F>
+void with_policy_source(F&& f, int source) {
+    if (source == S) f(std::integral_constant<int, S>{});
+    else if constexpr (S < ROLL_ACT_MLP2_TANH_FAST_GAUSS) with_policy_source<S + 1>(f, source);
 }
 // the sources that decide from the observation
 constexpr bool roll_act_observes(int source) { return source == ROLL_ACT_LINEAR || roll_act_is_mlp(source); }

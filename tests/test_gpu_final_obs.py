@@ -182,17 +182,21 @@ def copy_state(src, twin, limit):
         twin.set_elapsed_steps(src.elapsed_steps())
 
 
-def twin_replay(kind, n, limit, actions):
+def twin_replay(kind, n, limit, actions, mis_rew=0, with_obs=True):
     """K single steps of an auto-reset handle with the channel unset, its state copied into the twin before each: -> (the stepping handle's outputs,
-    the twin's obs [K, D, n], done and truncated [K, n])"""
+    the twin's obs [K, D, n], done and truncated [K, n]).  The twin steps on buffers of the case's shape (mis_rew, with_obs: Outs), so the launch form
+    under test runs without auto-reset as well; without obs_out its observation is the engine's view."""
     stepper, twin = make(kind, n, limit), make(kind, n, limit, auto_reset=False)
     prep(stepper, limit)
     twin.reset()
+    to = Outs(twin, 1, mis_rew, with_obs)
     outs, tobs, tdone, ttrunc = [], [], [], []
     for a in actions:
         copy_state(stepper, twin, limit)
         outs.append([x.copy() for x in stepper.step(a)])
-        o, _, d, t = twin.step(a)
+        do_call(twin, "step", 1, to, mg.DeviceArray.from_numpy(a))
+        h = to.host()
+        o, d, t = h["obs"][0] if with_obs else twin.observation(), h["done"][0], h["trunc"][0]
         tobs.append(o.copy()), tdone.append(d.astype(bool)), ttrunc.append(t.astype(bool))
         assert same(outs[-1][2], d) and same(outs[-1][3], t), "the twin's flags are the stepping handle's"
     stepper.close(), twin.close()
@@ -204,6 +208,9 @@ def check_coverage(kind, limit, d, t):
     K, n = d.shape
     fin = d | t
     has_done, has_trunc = kind != mg.PENDULUM, kind == mg.CARTPOLE or limit != 0
+    if not (has_done or has_trunc):   # Pendulum without a limit: nothing ever finishes
+        assert not fin.any()
+        return
     if has_done and has_trunc:
         assert (d & ~t).sum() >= 8 and (~d & t).sum() >= 8, "done-only and truncated-only endings"
     assert fin.sum() >= 8
@@ -237,7 +244,7 @@ def run_case(kind, limit, src, K, n=N, mis_fin=0, mis_rew=0, with_obs=True):
     for key, got in res["set"].items():   # (a)
         assert same(got, res["unset"][key]), f"{what}: {key} differs from the same call with the channel unset"
     used = acts if is_table else res["set"]["act"].view(acts.dtype)
-    outs, tobs, tdone, ttrunc = twin_replay(kind, n, limit, used)
+    outs, tobs, tdone, ttrunc = twin_replay(kind, n, limit, used, mis_rew, with_obs)
     for t, (so, sr, sd, st) in enumerate(outs):   # the call is K steps of the stepping handle, so the twin saw the states the call went through
         got = res["set"]
         assert same(got["rew"][t], sr) and same(got["done"][t], sd) and same(got["trunc"][t], st) and (not with_obs or same(got["obs"][t], so)), f"{what}: step {t}"
@@ -268,10 +275,11 @@ STEP_SHAPES = {"tiles": dict(), "odd": dict(n=1030), "odd_no_obs": dict(n=1030, 
 
 
 @pytest.mark.parametrize("shape", list(STEP_SHAPES))
-@pytest.mark.parametrize("kind,limit", KIND_CASES)
+@pytest.mark.parametrize("kind,limit", KIND_CASES + [pytest.param(mg.PENDULUM, 0, id="pendulum")])
 def test_step_launch_forms(kind, limit, shape, monkeypatch):
     """4 per lane single-pass (tiles), one env per lane (odd, misaligned_reward), 4 per lane with a ragged last group (odd_no_obs: MountainCar and
-    Pendulum), 4 per lane grid-stride (MGYM_CLASSIC_MAX_BLOCKS=1, read when a handle is created: three passes of one block)"""
+    Pendulum), 4 per lane grid-stride (MGYM_CLASSIC_MAX_BLOCKS=1, read when a handle is created: three passes of one block).  Each with auto-reset and the
+    channel unset, with the channel set, and (the twin) without auto-reset.  Pendulum without a limit: the forms that never finish and never write."""
     if shape == "grid_stride":
         monkeypatch.setenv("MGYM_CLASSIC_MAX_BLOCKS", "1")
     else:

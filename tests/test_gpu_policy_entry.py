@@ -1,5 +1,5 @@
-"""The one policy-rollout entry of every family (Env::rollout_policy behind mgym_rollout_uniform / _linear / _mlp): what the three
-entry points share must not leak between them.
+"""The one policy-rollout entry of every family (Env::rollout_policy behind mgym_rollout_uniform / _linear / _mlp / _mlp_sample / _mlp_gauss / _mlp2): what
+the entry points share must not leak between them.
   1. The handle's count of uniform calls (a Philox counter word of the policy stream) moves only with uniform calls that launch.
   2. Every rejection names the entry point that was called."""
 import numpy as np
@@ -12,13 +12,13 @@ from words import same
 pytestmark = pytest.mark.gpu
 
 L = mg.envs.L
-CLASSIC = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_cont": mg.MOUNTAINCAR_CONT}
+CLASSIC = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_cont": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM, "acrobot": mg.ACROBOT}
 N, K = 8, 4
 SEEDS = (11, 12)
 
 
 def linear_policy(env):
-    rows = {mg.MOUNTAINCAR: 3, mg.LUNARLANDER: 4}.get(env.kind, 1)
+    rows = {mg.MOUNTAINCAR: 3, mg.ACROBOT: 3, mg.LUNARLANDER: 4}.get(env.kind, 1)
     return np.random.default_rng(3).uniform(-1, 1, rows * (env.obs_dim + 1)).astype(np.float32)
 
 
@@ -92,9 +92,19 @@ def test_every_rejection_names_its_entry_point(fam):
     def entry_points(env, o):
         out = (o["act"], o["obs"], o["rew"].ptr + 4 if env.n == N else o["rew"], o["done"], o["trunc"])
         policy, H = env.pack_mlp(*mlp_weights(env))
+        D, A = env.mlp_dims()
+        r = np.random.default_rng(5)
+        policy2, H1, H2 = env.pack_mlp2(*(r.uniform(-1, 1, s) for s in ((3, D), (3,), (5, 3), (5,), (A, 5), (A,))))
+        if env.action_is_float:                                  # the family's drawing entry point and head
+            draw = ("mgym_rollout_mlp_gauss", lambda: env.rollout_mlp_gauss_device(policy, H, "relu", 0.5, SEEDS[0], 0, K, *out))
+        else:
+            draw = ("mgym_rollout_mlp_sample", lambda: env.rollout_mlp_sample_device(policy, H, "relu", SEEDS[0], 0, K, *out))
         return (("mgym_rollout_uniform", lambda: env.rollout_uniform_device(SEEDS[0], K, *out)),
                 ("mgym_rollout_linear", lambda: env.rollout_linear_device(linear_policy(env), K, *out)),
-                ("mgym_rollout_mlp", lambda: env.rollout_mlp_device(policy, H, "relu", K, *out)))
+                ("mgym_rollout_mlp", lambda: env.rollout_mlp_device(policy, H, "relu", K, *out)),
+                draw,
+                ("mgym_rollout_mlp2", lambda: env.rollout_mlp2_device(policy2, H1, H2, "relu", "greedy", 0.0, SEEDS[0], 0, K, *out)),
+                ("mgym_rollout_mlp2", lambda: env.rollout_mlp2_device(policy2, H1, H2, "relu", "gauss" if env.action_is_float else "sample", 0.5, SEEDS[0], 0, K, *out)))
 
     for n in (6, N):                                             # n_envs no multiple of 4; a reward pointer off its 16-byte alignment
         env = mg.VecEnv(CLASSIC[fam], n, seed=7)
