@@ -253,7 +253,7 @@ int mgym_destroy(mgym_env* env) {
 // mgym_set_final_obs_out: a call that steps K times needs K slabs — refused before any launch, the state untouched
 #define FINAL_CAP_OR_FAIL(api, K)                                                                                                     \
     if (e->final_obs && (K) > e->final_cap)                                                                                            \
-        return bad_arg((std::string(api ": K = ") + std::to_string(K) + " exceeds steps_cap = " + std::to_string(e->final_cap) +      \
+        return bad_arg((std::string(api) + ": K = " + std::to_string(K) + " exceeds steps_cap = " + std::to_string(e->final_cap) +    \
                         " of mgym_set_final_obs_out").c_str());
 
 #define ENV_OR_FAIL(env)                                        \
@@ -314,36 +314,63 @@ int mgym_rollout(mgym_env* env, const void* actions, int32_t K, float* obs_out, 
     return e->rollout(actions, K, obs_out, reward_out, done_out, trunc_out);
 }
 
+// The families by kind: the name a refusal uses and the key mgym_get_info prints (kKindUnassigned has neither).
+static const struct { const char* name; const char* key; } kFamilies[] = {{"CartPole", "cartpole"}, {"MountainCar", "mountain_car"}, {"MountainCarContinuous", "mountain_car_continuous"},
+                                                                          {"LunarLander", "lunar_lander"}, {"Pendulum", "pendulum"}, {"", ""}, {"Acrobot", "acrobot"}};
+static bool box_actions(const Env* e) { return e->cfg.kind == MGYM_MOUNTAINCAR_CONT || e->cfg.kind == MGYM_PENDULUM; }
+
+// The argument checks of the six policy entry points, written once.  An entry point states what it takes beyond K and the outputs (TAKES_*; DRAWS: its actions come
+// from the policy stream, keyed per 4 consecutive global env ids — the uniform policy, the one that draws without weights, words that its own way) and, where it does
+// not offer the handle's family, its refusal; the order below is the one order they all report in — a refusal comes first, or behind the head it depends on.
+enum { TAKES_POLICY = 1, TAKES_HIDDEN = 2, TAKES_HIDDEN2 = 4, TAKES_HEAD = 8, TAKES_SIGMA = 16, DRAWS = 32 };
+struct PolicyArgs { int32_t K; const float* policy = nullptr; int32_t hidden = 0, hidden2 = 0, activation = 0, head = 0; float sigma = 0.0f; };
+static_assert(MGYM_ACT_RELU == MLP_ACT_RELU && MGYM_ACT_TANH == MLP_ACT_TANH && MGYM_ACT_TANH_FAST == MLP_ACT_TANH_FAST, "mgym.h and mlp_policy.h number the activations alike");
+static_assert(MGYM_HEAD_GREEDY == MLP2_HEAD_GREEDY && MGYM_HEAD_SAMPLE == MLP2_HEAD_SAMPLE && MGYM_HEAD_GAUSS == MLP2_HEAD_GAUSS, "mgym.h and mlp2_policy.h number the heads alike");
+
+static int policy_args_ok(const Env* e, const char* api, int takes, const std::string& refusal, const PolicyArgs& a) {
+    auto bad = [api](const std::string& what) { return bad_arg((std::string(api) + ": " + what).c_str()); };
+    const bool two = takes & TAKES_HIDDEN2;   // two hidden layers: "hidden1" and "hidden2", and no exact tanh
+    if (a.K < 0) return bad("K < 0");
+    FINAL_CAP_OR_FAIL(api, a.K);
+    if (!refusal.empty() && !(takes & TAKES_HEAD)) return bad(refusal);
+    if ((takes & TAKES_POLICY) && !a.policy) return bad("policy is NULL");
+    if (takes & TAKES_HIDDEN) {
+        if (a.hidden < 1 || a.hidden > 64) return bad(two ? "hidden1 must be between 1 and 64" : "hidden must be between 1 and 64");
+        if (two && (a.hidden2 < 1 || a.hidden2 > 64)) return bad("hidden2 must be between 1 and 64");
+        if (two && a.activation == MGYM_ACT_TANH)
+            return bad("activation MGYM_ACT_TANH is not offered with two hidden layers (the exact tanh would be nearly all of the launch): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
+        if (a.activation != MGYM_ACT_RELU && a.activation != MGYM_ACT_TANH && a.activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
+            return bad(two ? "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST" : "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    }
+    if (takes & TAKES_HEAD) {
+        if (a.head != MGYM_HEAD_GREEDY && a.head != MGYM_HEAD_SAMPLE && a.head != MGYM_HEAD_GAUSS) return bad("head must be MGYM_HEAD_GREEDY, MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
+        if (!refusal.empty()) return bad(refusal);
+    }
+    if ((takes & TAKES_SIGMA) && (!(a.sigma >= 0.0f) || a.sigma > 3.402823466e+38f)) return bad("sigma must be finite and >= 0");   // (a NaN fails the first test)
+    if ((takes & DRAWS) && e->cfg.env_id_base % 4 != 0)
+        return bad(std::string("env_id_base must be a multiple of 4") + ((takes & TAKES_HEAD) ? " for a drawing head" : "") +
+                   ((takes & TAKES_POLICY) ? " (one Philox block serves 4 consecutive global env ids)" : " (policy bits are keyed per 4 consecutive global env ids)"));
+    return MGYM_OK;
+}
+
 int mgym_rollout_uniform(mgym_env* env, uint64_t policy_seed, int32_t K, void* actions_out, float* obs_out, float* reward_out,
                          uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
-    if (K < 0) return bad_arg("mgym_rollout_uniform: K < 0");
-    FINAL_CAP_OR_FAIL("mgym_rollout_uniform", K);
-    if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_uniform: env_id_base must be a multiple of 4 (policy bits are keyed per 4 consecutive global env ids)");
+    if (const int st = policy_args_ok(e, "mgym_rollout_uniform", DRAWS, "", PolicyArgs{K})) return st;
     return e->rollout_policy(PolicyCall{ROLL_ACT_UNIFORM, "mgym_rollout_uniform", nullptr, 0, policy_seed}, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
 int mgym_rollout_linear(mgym_env* env, const float* policy, int32_t K, void* actions_out, float* obs_out, float* reward_out,
                         uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
-    if (K < 0) return bad_arg("mgym_rollout_linear: K < 0");
-    FINAL_CAP_OR_FAIL("mgym_rollout_linear", K);
-    if (!policy) return bad_arg("mgym_rollout_linear: policy is NULL");
+    if (const int st = policy_args_ok(e, "mgym_rollout_linear", TAKES_POLICY, "", PolicyArgs{K, policy})) return st;
     return e->rollout_policy(PolicyCall{ROLL_ACT_LINEAR, "mgym_rollout_linear", policy, 0, 0}, K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
-
-// the hidden activations of the three hidden-layer entry points (2 is not one)
-static_assert(MGYM_ACT_RELU == MLP_ACT_RELU && MGYM_ACT_TANH == MLP_ACT_TANH && MGYM_ACT_TANH_FAST == MLP_ACT_TANH_FAST, "mgym.h and mlp_policy.h number the activations alike");
-static bool act_known(int32_t activation) { return activation == MGYM_ACT_RELU || activation == MGYM_ACT_TANH || activation == MGYM_ACT_TANH_FAST; }
 
 int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, int32_t K, void* actions_out, float* obs_out,
                      float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
-    if (K < 0) return bad_arg("mgym_rollout_mlp: K < 0");
-    FINAL_CAP_OR_FAIL("mgym_rollout_mlp", K);
-    if (!policy) return bad_arg("mgym_rollout_mlp: policy is NULL");
-    if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp: hidden must be between 1 and 64");
-    if (!act_known(activation)) return bad_arg("mgym_rollout_mlp: activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    if (const int st = policy_args_ok(e, "mgym_rollout_mlp", TAKES_POLICY | TAKES_HIDDEN, "", PolicyArgs{K, policy, hidden, 0, activation})) return st;
     return e->rollout_policy(PolicyCall{roll_act_mlp_plain(activation), "mgym_rollout_mlp", policy, hidden, 0}, K, actions_out, obs_out, reward_out, done_out,
                              trunc_out);
 }
@@ -351,14 +378,8 @@ int mgym_rollout_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t
 int mgym_rollout_mlp_sample(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, uint64_t policy_seed, uint32_t policy_call, int32_t K,
                             void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
-    if (K < 0) return bad_arg("mgym_rollout_mlp_sample: K < 0");
-    FINAL_CAP_OR_FAIL("mgym_rollout_mlp_sample", K);
-    if (e->cfg.kind == MGYM_MOUNTAINCAR_CONT) return bad_arg("mgym_rollout_mlp_sample: MountainCarContinuous has no discrete actions to draw from (a Gaussian head is not implemented)");
-    if (e->cfg.kind == MGYM_PENDULUM) return bad_arg("mgym_rollout_mlp_sample: Pendulum has no discrete actions to draw from (a Gaussian head is not implemented)");
-    if (!policy) return bad_arg("mgym_rollout_mlp_sample: policy is NULL");
-    if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp_sample: hidden must be between 1 and 64");
-    if (!act_known(activation)) return bad_arg("mgym_rollout_mlp_sample: activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
-    if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_sample: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
+    const std::string refusal = box_actions(e) ? std::string(kFamilies[e->cfg.kind].name) + " has no discrete actions to draw from (a Gaussian head is not implemented)" : "";
+    if (const int st = policy_args_ok(e, "mgym_rollout_mlp_sample", TAKES_POLICY | TAKES_HIDDEN | DRAWS, refusal, PolicyArgs{K, policy, hidden, 0, activation})) return st;
     return e->rollout_policy(PolicyCall{roll_act_mlp_sample(activation), "mgym_rollout_mlp_sample", policy, hidden, policy_seed, policy_call},
                              K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
@@ -366,43 +387,21 @@ int mgym_rollout_mlp_sample(mgym_env* env, const float* policy, int32_t hidden, 
 int mgym_rollout_mlp_gauss(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, float sigma, uint64_t policy_seed, uint32_t policy_call, int32_t K,
                            void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
     ENV_OR_FAIL(env);
-    if (K < 0) return bad_arg("mgym_rollout_mlp_gauss: K < 0");
-    FINAL_CAP_OR_FAIL("mgym_rollout_mlp_gauss", K);
-    if (e->cfg.kind != MGYM_MOUNTAINCAR_CONT && e->cfg.kind != MGYM_PENDULUM) {
-        static const char* const names[] = {"CartPole", "MountainCar", "", "LunarLander", "", "", "Acrobot"};
-        return bad_arg((std::string("mgym_rollout_mlp_gauss: ") + names[e->cfg.kind] + " has discrete actions: use mgym_rollout_mlp_sample").c_str());
-    }
-    if (!policy) return bad_arg("mgym_rollout_mlp_gauss: policy is NULL");
-    if (hidden < 1 || hidden > 64) return bad_arg("mgym_rollout_mlp_gauss: hidden must be between 1 and 64");
-    if (!act_known(activation)) return bad_arg("mgym_rollout_mlp_gauss: activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
-    if (!(sigma >= 0.0f) || sigma > 3.402823466e+38f) return bad_arg("mgym_rollout_mlp_gauss: sigma must be finite and >= 0");   // (a NaN fails the first test)
-    if (e->cfg.env_id_base % 4 != 0) return bad_arg("mgym_rollout_mlp_gauss: env_id_base must be a multiple of 4 (one Philox block serves 4 consecutive global env ids)");
+    const std::string refusal = box_actions(e) ? "" : std::string(kFamilies[e->cfg.kind].name) + " has discrete actions: use mgym_rollout_mlp_sample";
+    if (const int st = policy_args_ok(e, "mgym_rollout_mlp_gauss", TAKES_POLICY | TAKES_HIDDEN | TAKES_SIGMA | DRAWS, refusal, PolicyArgs{K, policy, hidden, 0, activation, 0, sigma}))
+        return st;
     return e->rollout_policy(PolicyCall{roll_act_mlp_gauss(activation), "mgym_rollout_mlp_gauss", policy, hidden, policy_seed, policy_call, sigma},
                              K, actions_out, obs_out, reward_out, done_out, trunc_out);
 }
 
 int mgym_rollout_mlp2(mgym_env* env, const float* policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, uint64_t policy_seed,
                       uint32_t policy_call, int32_t K, void* actions_out, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* trunc_out) {
-    static_assert(MGYM_HEAD_GREEDY == MLP2_HEAD_GREEDY && MGYM_HEAD_SAMPLE == MLP2_HEAD_SAMPLE && MGYM_HEAD_GAUSS == MLP2_HEAD_GAUSS, "mgym.h and mlp2_policy.h number the heads alike");
     ENV_OR_FAIL(env);
-    if (K < 0) return bad_arg("mgym_rollout_mlp2: K < 0");
-    FINAL_CAP_OR_FAIL("mgym_rollout_mlp2", K);
-    if (!policy) return bad_arg("mgym_rollout_mlp2: policy is NULL");
-    if (hidden1 < 1 || hidden1 > 64) return bad_arg("mgym_rollout_mlp2: hidden1 must be between 1 and 64");
-    if (hidden2 < 1 || hidden2 > 64) return bad_arg("mgym_rollout_mlp2: hidden2 must be between 1 and 64");
-    if (activation == MGYM_ACT_TANH)
-        return bad_arg("mgym_rollout_mlp2: activation MGYM_ACT_TANH is not offered with two hidden layers (the exact tanh would be nearly all of the launch): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
-    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH_FAST) return bad_arg("mgym_rollout_mlp2: activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST");
-    if (head != MGYM_HEAD_GREEDY && head != MGYM_HEAD_SAMPLE && head != MGYM_HEAD_GAUSS) return bad_arg("mgym_rollout_mlp2: head must be MGYM_HEAD_GREEDY, MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
-    const bool continuous = e->cfg.kind == MGYM_MOUNTAINCAR_CONT || e->cfg.kind == MGYM_PENDULUM;
-    static const char* const names[] = {"CartPole", "MountainCar", "MountainCarContinuous", "LunarLander", "Pendulum", "", "Acrobot"};
-    if (head == MGYM_HEAD_SAMPLE && continuous)
-        return bad_arg((std::string("mgym_rollout_mlp2: head MGYM_HEAD_SAMPLE: ") + names[e->cfg.kind] + " has no discrete actions to draw from (use MGYM_HEAD_GAUSS)").c_str());
-    if (head == MGYM_HEAD_GAUSS && !continuous)
-        return bad_arg((std::string("mgym_rollout_mlp2: head MGYM_HEAD_GAUSS: ") + names[e->cfg.kind] + " has discrete actions (use MGYM_HEAD_SAMPLE)").c_str());
-    if (head == MGYM_HEAD_GAUSS && (!(sigma >= 0.0f) || sigma > 3.402823466e+38f)) return bad_arg("mgym_rollout_mlp2: sigma must be finite and >= 0");   // (a NaN fails the first test)
-    if (head != MGYM_HEAD_GREEDY && e->cfg.env_id_base % 4 != 0)
-        return bad_arg("mgym_rollout_mlp2: env_id_base must be a multiple of 4 for a drawing head (one Philox block serves 4 consecutive global env ids)");
+    std::string refusal;
+    if (head == MGYM_HEAD_SAMPLE && box_actions(e)) refusal = std::string("head MGYM_HEAD_SAMPLE: ") + kFamilies[e->cfg.kind].name + " has no discrete actions to draw from (use MGYM_HEAD_GAUSS)";
+    if (head == MGYM_HEAD_GAUSS && !box_actions(e)) refusal = std::string("head MGYM_HEAD_GAUSS: ") + kFamilies[e->cfg.kind].name + " has discrete actions (use MGYM_HEAD_SAMPLE)";
+    const int takes = TAKES_POLICY | TAKES_HIDDEN | TAKES_HIDDEN2 | TAKES_HEAD | (head == MGYM_HEAD_GAUSS ? TAKES_SIGMA : 0) | (head != MGYM_HEAD_GREEDY ? DRAWS : 0);
+    if (const int st = policy_args_ok(e, "mgym_rollout_mlp2", takes, refusal, PolicyArgs{K, policy, hidden1, hidden2, activation, head, sigma})) return st;
     PolicyCall call{roll_act_mlp2(activation, head), "mgym_rollout_mlp2", policy, hidden1, policy_seed, policy_call, sigma};
     call.hidden2 = hidden2;
     return e->rollout_policy(call, K, actions_out, obs_out, reward_out, done_out, trunc_out);
@@ -557,8 +556,7 @@ const char* mgym_last_error(void) { return g_last_error.c_str(); }
 int mgym_get_info(mgym_env* env, char* buf, size_t cap) {
     ENV_OR_FAIL(env);
     if (!buf || cap == 0) return bad_arg("mgym_get_info: buf is NULL or cap is 0");
-    static const char* const kinds[] = {"cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander", "pendulum", "", "acrobot"};
-    std::string out = std::string("kind=") + kinds[e->kind] + "\nn_envs=" + std::to_string(e->n) + "\ndevice=" + std::to_string(e->cfg.device) +
+    std::string out = std::string("kind=") + kFamilies[e->kind].key +"\nn_envs=" + std::to_string(e->n) + "\ndevice=" + std::to_string(e->cfg.device) +
                       "\nauto_reset=" + ((e->cfg.flags & MGYM_FLAG_AUTO_RESET) ? "1" : "0") + "\nmax_episode_steps=" + std::to_string(e->cfg.max_episode_steps) +
                       "\nGPU_MAX_HW_QUEUES=" + e->hwq_env + "\n";
     int st = e->info(out);

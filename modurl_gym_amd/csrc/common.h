@@ -77,15 +77,18 @@ struct Env {
     virtual int init() = 0;
     virtual int reset(const uint8_t* m0, const uint8_t* m1, bool all, float* obs_out) = 0;
     virtual int step(const void* actions, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) = 0;
+    // step k of a K-step call: step() under the step's own action column, into slab k of each [K][..] output that is not null
+    int step_k(int k, const void* actions_k, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
+        return step(actions_k, obs_out ? obs_out + (size_t)k * obs_dim * n : nullptr, reward ? reward + (size_t)k * n : nullptr,
+                    done ? done + (size_t)k * n : nullptr, trunc ? trunc + (size_t)k * n : nullptr);
+    }
     // K fused steps; default: K launches of step() with strided per-step buffers
     virtual int rollout(const void* actions, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) {
         float* const fin0 = final_obs;   // step k of the call writes its finished envs' observations to slab k (mgym_set_final_obs_out)
         int st = MGYM_OK;
         for (int k = 0; k < K && st == MGYM_OK; ++k) {
-            const char* a = static_cast<const char*>(actions) + (size_t)k * n * 4;
             if (fin0) final_obs = fin0 + (size_t)k * obs_dim * n;
-            st = step(a, obs_out ? obs_out + (size_t)k * obs_dim * n : nullptr, reward ? reward + (size_t)k * n : nullptr,
-                      done ? done + (size_t)k * n : nullptr, trunc ? trunc + (size_t)k * n : nullptr);
+            st = step_k(k, static_cast<const char*>(actions) + (size_t)k * n * 4, obs_out, reward, done, trunc);
         }
         final_obs = fin0;
         return st;

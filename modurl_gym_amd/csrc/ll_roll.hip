@@ -29,10 +29,11 @@ int ll_rollout_policy_blocks_per_cu(int* per_cu, int* mlp_per_cu) {
 // every instantiation's by-value arguments fit the 4 KiB kernel-argument segment the launch can rely on (the hidden-layer pack is NOT among them)
 static_assert(sizeof(LLDev) + sizeof(LLIo) + sizeof(RollQ) + sizeof(RollPolicy) <= 4096, "ll_rollout_kernel: by-value kernel arguments above 4096 bytes");
 void ll_rollout_policy_launch(hipStream_t s, unsigned grid, const LLDev& d, const LLIo& io, const RollQ& q, const RollPolicy& pol, int policy) {
-    if (policy == ROLL_ACT_LINEAR) hipLaunchKernelGGL((ll_rollout_kernel<32, ROLL_ACT_LINEAR, RollPolicy>), dim3(grid), dim3(64), 0, s, d, io, q, pol);
-    else if (policy == ROLL_ACT_UNIFORM) hipLaunchKernelGGL((ll_rollout_kernel<32, ROLL_ACT_UNIFORM, RollPolicy>), dim3(grid), dim3(64), 0, s, d, io, q, pol);
-    else if (policy == ROLL_ACT_MLP_RELU) hipLaunchKernelGGL((ll_rollout_kernel<32, ROLL_ACT_MLP_RELU, RollPolicy>), dim3(grid), dim3(64), 0, s, d, io, q, pol);
-    else hipLaunchKernelGGL((ll_rollout_kernel<32, ROLL_ACT_MLP_TANH, RollPolicy>), dim3(grid), dim3(64), 0, s, d, io, q, pol);
+    with_policy_source([&](auto S) {   // the four sources the persistent launch carries: no other is instantiated, and none reaches this call
+        constexpr int SRC = decltype(S)::value;
+        if constexpr (SRC == ROLL_ACT_LINEAR || SRC == ROLL_ACT_UNIFORM || SRC == ROLL_ACT_MLP_RELU || SRC == ROLL_ACT_MLP_TANH)
+            hipLaunchKernelGGL((ll_rollout_kernel<32, SRC, RollPolicy>), dim3(grid), dim3(64), 0, s, d, io, q, pol);
+    }, policy);
 }
 // the handle's weight pack, stored on the stream ahead of the launch that reads it: the caller's array is read during the call only (it travels in this
 // kernel's arguments), and consecutive calls on one stream each find their own weights

@@ -1278,36 +1278,34 @@ struct LunarLanderEnv final : Env {
                                       h[RS_N_HELPER_STEPS] ? (double)h[RS_N_HELPER_LANE_STEPS] / h[RS_N_HELPER_STEPS] : 0.0, (double)h[RS_N_FREE_STEPS]);
         return MGYM_OK;
     }
-    // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp / mgym_rollout_mlp_sample, the one place that unpacks the call and chooses the form: the persistent launch with the
-    // action source `policy` (ll_roll.h) when the handle has one, K >= rollout_min_k, the stream is not being captured and — hidden-layer sources — the activation runs
-    // there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else K x (policy kernel, step()).  The sampling sources always run the second form, whatever MGYM_LL_ROLLOUT_MLP says,
-    // and so do the MGYM_ACT_TANH_FAST sources: the persistent kernel has no instantiation for them.
+    // The K-step form of a policy call, K x (policy kernel, step()): launch_policy_kernel(t, a) puts the kernel that writes step t's action column a — actions_out[t],
+    // or the engine's [n] next-action words — on the stream.
+    template <class Launch>
+    int policy_steps(int K, uint32_t* ao, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, Launch launch_policy_kernel) {
+        for (int t = 0; t < K; ++t) {
+            uint32_t* a = ao ? ao + (size_t)t * n : next_act;
+            launch_policy_kernel((uint32_t)t, a);
+            MGYM_HIP(hipGetLastError());
+            if (const int st = step_k(t, a, obs_out, reward, done, trunc)) return st;
+        }
+        return MGYM_OK;
+    }
+    // mgym_rollout_linear / mgym_rollout_uniform / mgym_rollout_mlp / mgym_rollout_mlp_sample / mgym_rollout_mlp2, the one place that unpacks the call and chooses the form: the
+    // persistent launch with the action source `policy` (ll_roll.h) when the handle has one, K >= rollout_min_k, the stream is not being captured and — hidden-layer sources — the
+    // activation runs there (kRollMlpPersistent, MGYM_LL_ROLLOUT_MLP); else the K-step form, its policy kernel chosen once from the source (with_policy_source, policy.h, as the
+    // classic families choose their launch).  The sampling sources always run the second form, whatever MGYM_LL_ROLLOUT_MLP says, and so do the MGYM_ACT_TANH_FAST and the
+    // two-hidden-layer sources: the persistent kernel has no instantiation for them.
     int rollout_policy(const PolicyCall& call, int K, void* actions_out, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc) override {
         if (n == 0 || K == 0) return MGYM_OK;
         const int policy = call.source;
-        const bool mlp = roll_act_is_mlp(policy);
+        const bool mlp = roll_act_is_mlp(policy), mlp2 = roll_act_is_mlp2(policy);
         uint32_t* ao = static_cast<uint32_t*>(actions_out);
-        if (roll_act_is_mlp2(policy)) {   // mgym_rollout_mlp2: always K x (policy kernel, step()), the pack stored on the stream first
-            if (roll_act_mlp2_head(policy) == MLP2_HEAD_GAUSS) { set_last_error(std::string(call.api) + ": LunarLander has discrete actions"); return MGYM_ERR_BAD_ARG; }   // (the C ABI refuses it first)
-            if (const int st = mlp2_store(call, 8, 4)) return st;
-            const Mlp2Net<8, 4> net = mlp2_net<8, 4>(call);
-            const unsigned g = (unsigned)((n + 255) / 256);
-            for (int t = 0; t < K; ++t) {
-                uint32_t* a = ao ? ao + (size_t)t * n : next_act;
-                with_bools([&](auto F, auto S) {
-                    hipLaunchKernelGGL((ll_policy_mlp2_kernel<decltype(F)::value ? MLP_ACT_TANH_FAST : MLP_ACT_RELU, decltype(S)::value>), dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad,
-                                       net, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
-                }, roll_act_mlp2_act(policy) == MLP_ACT_TANH_FAST, roll_act_mlp2_head(policy) == MLP2_HEAD_SAMPLE);
-                MGYM_HIP(hipGetLastError());
-                int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
-                              trunc ? trunc + (size_t)t * n : nullptr);
-                if (st != MGYM_OK) return st;
-            }
-            return MGYM_OK;
-        }
+        if (!roll_act_discrete_takes(policy)) { set_last_error(std::string(call.api) + ": LunarLander has discrete actions"); return MGYM_ERR_BAD_ARG; }   // (the C ABI refuses it first)
         RollPolicy pol{};
         LLMlpPack pack;   // (the hidden-layer sources only: their weights as the kernels read them)
-        if (policy == ROLL_ACT_UNIFORM) {
+        if (mlp2) {   // mgym_rollout_mlp2: always K x (policy kernel, step()), the pack stored on the stream first
+            if (const int st = mlp2_store(call, 8, 4)) return st;
+        } else if (policy == ROLL_ACT_UNIFORM) {
             pol.seed = call.seed;
             pol.call = uniform_calls++;
         } else if (policy == ROLL_ACT_LINEAR) {
@@ -1321,25 +1319,23 @@ struct LunarLanderEnv final : Env {
         pol.next = next_act;
         const bool sample = roll_act_samples(policy);
         const bool fast = mlp && roll_act_mlp_act(policy) == MLP_ACT_TANH_FAST;
-        const bool persistent = !sample && !fast && opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
+        const bool persistent = !mlp2 && !sample && !fast && opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
         if (!persistent) {
-            const unsigned g = (unsigned)((n + 255) / 256);
-            for (int t = 0; t < K; ++t) {
-                uint32_t* a = ao ? ao + (size_t)t * n : next_act;
-                if (policy == ROLL_ACT_LINEAR) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_LINEAR>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
-                else if (policy == ROLL_ACT_UNIFORM) hipLaunchKernelGGL(ll_policy_kernel<ROLL_ACT_UNIFORM>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, dev.env_id_base, pol, (uint32_t)t, a);
-                else if (policy == ROLL_ACT_MLP_TANH_FAST_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_TANH_FAST>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
-                else if (policy == ROLL_ACT_MLP_TANH_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
-                else if (policy == ROLL_ACT_MLP_RELU_SAMPLE) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, (uint32_t)t, a);
-                else if (policy == ROLL_ACT_MLP_TANH_FAST) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH_FAST>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
-                else if (policy == ROLL_ACT_MLP_TANH) hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_TANH>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);   // (the pack as a kernel argument: a captured graph carries it)
-                else hipLaunchKernelGGL(ll_policy_mlp_kernel<MLP_ACT_RELU>, dim3(g), dim3(256), 0, stream, (const float*)dev.obs, n, n_pad, pack, a);
-                MGYM_HIP(hipGetLastError());
-                int st = step(a, obs_out ? obs_out + (size_t)t * 8 * n : nullptr, reward ? reward + (size_t)t * n : nullptr, done ? done + (size_t)t * n : nullptr,
-                              trunc ? trunc + (size_t)t * n : nullptr);
-                if (st != MGYM_OK) return st;
-            }
-            return MGYM_OK;
+            int st = MGYM_OK;
+            const dim3 g((unsigned)((n + 255) / 256));
+            const float* const obs = dev.obs;
+            const Mlp2Net<8, 4> net = mlp2_net<8, 4>(call);
+            with_policy_source([&](auto S) {   // (no kernel is instantiated for a source the family does not take)
+                constexpr int SRC = decltype(S)::value;
+                if constexpr (roll_act_discrete_takes(SRC)) st = policy_steps(K, ao, obs_out, reward, done, trunc, [&](uint32_t t, uint32_t* a) {
+                    if constexpr (roll_act_is_mlp2(SRC))
+                        hipLaunchKernelGGL((ll_policy_mlp2_kernel<roll_act_mlp2_act(SRC), roll_act_mlp2_head(SRC) == MLP2_HEAD_SAMPLE>), g, dim3(256), 0, stream, obs, n, n_pad, net, dev.env_id_base, call.seed, call.call, t, a);
+                    else if constexpr (roll_act_samples(SRC)) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<roll_act_mlp_act(SRC)>, g, dim3(256), 0, stream, obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, t, a);
+                    else if constexpr (roll_act_is_mlp(SRC)) hipLaunchKernelGGL(ll_policy_mlp_kernel<roll_act_mlp_act(SRC)>, g, dim3(256), 0, stream, obs, n, n_pad, pack, a);   // (the pack as a kernel argument: a captured graph carries it)
+                    else hipLaunchKernelGGL(ll_policy_kernel<SRC>, g, dim3(256), 0, stream, obs, n, n_pad, dev.env_id_base, pol, t, a);
+                });
+            }, policy);
+            return st;
         }
         if (mlp) {   // the pack goes to the handle's buffer by a kernel on the stream: the caller's array is not read after the call, and the next call's weights wait for this call's launches
             ll_rollout_mlp_pack_store(stream, pack, roll_mlp_pack);

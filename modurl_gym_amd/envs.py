@@ -118,6 +118,38 @@ def _ptr(x):
     return x.data_ptr()
 
 
+# the names the policy entry points take for an MGYM_ACT_* / MGYM_HEAD_* value (the value itself passes through)
+_ACTIVATIONS = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH, "tanh_fast": L.ACT_TANH_FAST}
+_HEADS = {"greedy": L.HEAD_GREEDY, "sample": L.HEAD_SAMPLE, "gauss": L.HEAD_GAUSS}
+
+
+def _named(names, value, wording):
+    """names[value], or the integer value itself; anything else raises PolicyShapeError with `wording`"""
+    v = names.get(value, value)
+    if not isinstance(v, (int, np.integer)):
+        raise PolicyShapeError(L.ERR_BAD_ARG, f"{wording}, got {value!r}")
+    return int(v)
+
+
+def _policy_floats(policy, want, what):
+    """policy as the contiguous float32 words an entry point reads: `want` of them, or PolicyShapeError "policy must hold .. floats for `what`" (want None: not
+    checked, the engine rejects the call for its hidden width first)"""
+    pol = np.ascontiguousarray(np.asarray(policy, np.float32).ravel())
+    if want is not None and pol.size != want:
+        raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {want} floats for {what}, got {pol.size}")
+    return pol
+
+
+def _fptr(pol):
+    """the const float* of a float32 array (None: NULL, which the engine rejects)"""
+    return None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _draw(seed, call):
+    """the policy seed and call word of the drawing entry points as the ABI takes them: 64 and 32 bits"""
+    return int(seed) & (2**64 - 1), int(call) & 0xFFFFFFFF
+
+
 class VecEnv:
     """n_envs environments of one family on one GPU (one mgym_env handle, one stream)."""
 
@@ -197,10 +229,13 @@ class VecEnv:
         _check(self._lib.mgym_rollout(self._h, _ptr(actions), int(K), _ptr(obs_out), _ptr(reward_out), _ptr(done_out),
                                       _ptr(trunc_out)))
 
+    def _policy_device(self, fn, lead, outs):
+        """one policy entry point of the C ABI: fn(handle, its own leading arguments `lead`, already converted, K among them; the five output pointers)"""
+        _check(fn(self._h, *lead, *(_ptr(x) for x in outs)))
+
     def rollout_uniform_device(self, policy_seed, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device uniform random policy (mgym_rollout_uniform; every family — include/mgym.h documents the draws)."""
-        _check(self._lib.mgym_rollout_uniform(self._h, int(policy_seed), int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out),
-                                              _ptr(done_out), _ptr(trunc_out)))
+        self._policy_device(self._lib.mgym_rollout_uniform, (int(policy_seed), int(K)), (actions_out, obs_out, reward_out, done_out, trunc_out))
 
     def rollout_linear_device(self, policy, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device linear policy (mgym_rollout_linear): policy = obs_dim weights + bias (CartPole: action 1 if the score is
@@ -208,13 +243,8 @@ class VecEnv:
         the index of the largest score, the first of equal ones).  Host floats.  A policy of the wrong length raises PolicyShapeError (an MgymError with
         status ERR_BAD_ARG and a ValueError)."""
         rows = {L.MOUNTAINCAR: 3, L.ACROBOT: 3, L.LUNARLANDER: 4}.get(self.kind, 1)   # a row of (weights, bias) per action for the argmax families
-        n_pol = rows * (self.obs_dim + 1)
-        pol_in = np.asarray(policy, np.float32).ravel()
-        if pol_in.size != n_pol:
-            raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {n_pol} floats for this family, got {pol_in.size}")
-        pol = (C.c_float * n_pol)(*[float(v) for v in pol_in])
-        _check(self._lib.mgym_rollout_linear(self._h, pol, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out),
-                                             _ptr(trunc_out)))
+        pol = _policy_floats(policy, rows * (self.obs_dim + 1), "this family")
+        self._policy_device(self._lib.mgym_rollout_linear, (_fptr(pol), int(K)), (actions_out, obs_out, reward_out, done_out, trunc_out))
 
     def _rollout_host(self, K, call, action_dtype=np.uint32):
         """The host-array form of every K-step call: allocate the [K, ..] outputs, run call(actions, obs, reward, done, trunc) on them, sync
@@ -250,42 +280,33 @@ class VecEnv:
 
     def _mlp_args(self, policy, hidden, activation):
         """(contiguous float32 policy or None, activation value) of the hidden-layer entry points, the policy's length checked against H and the family"""
-        act = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH, "tanh_fast": L.ACT_TANH_FAST}.get(activation, activation)
-        if not isinstance(act, (int, np.integer)):
-            raise PolicyShapeError(L.ERR_BAD_ARG, f'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value, got {activation!r}')
-        pol = None
-        if policy is not None:
-            D, A = self.mlp_dims()
-            pol_in = np.asarray(policy, np.float32).ravel()
-            if 1 <= int(hidden) <= 64 and pol_in.size != int(hidden) * (D + 1) + A * (int(hidden) + 1):
-                raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {int(hidden) * (D + 1) + A * (int(hidden) + 1)} floats for hidden = {hidden}, got {pol_in.size}")
-            pol = np.ascontiguousarray(pol_in)
-        return pol, int(act)
+        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
+        (D, A), h = self.mlp_dims(), int(hidden)
+        want = h * (D + 1) + A * (h + 1) if 1 <= h <= 64 else None
+        return None if policy is None else _policy_floats(policy, want, f"hidden = {hidden}"), act
 
     def rollout_mlp_device(self, policy, hidden, activation, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): `policy` = the packed host floats of pack_mlp (or None, which the
         engine rejects), `hidden` = H, `activation` = "relu" / "tanh" / "tanh_fast" or the MGYM_ACT_* value ("tanh" is glibc's tanhf to the bit and most of the
         launch's time; "tanh_fast" is the cheap tanh include/mgym.h defines word for word, within 2.5 f32 spacings of tanh).  A policy of the wrong length for H raises PolicyShapeError."""
         pol, act = self._mlp_args(policy, hidden, activation)
-        _check(self._lib.mgym_rollout_mlp(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, int(K), _ptr(actions_out),
-                                          _ptr(obs_out), _ptr(reward_out), _ptr(done_out), _ptr(trunc_out)))
+        self._policy_device(self._lib.mgym_rollout_mlp, (_fptr(pol), int(hidden), act, int(K)), (actions_out, obs_out, reward_out, done_out, trunc_out))
 
     def rollout_mlp_sample_device(self, policy, hidden, activation, seed, call, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """rollout_mlp_device with the action drawn from the softmax of the scores (mgym_rollout_mlp_sample; the discrete families): the draw is a pure
         function of (seed, call, global env id, step) and the scores — include/mgym.h states it to the word.  The handle keeps no count: pass a new `call`
         (a 32-bit word) for each call that is to draw afresh."""
         pol, act = self._mlp_args(policy, hidden, activation)
-        _check(self._lib.mgym_rollout_mlp_sample(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, int(seed) & (2**64 - 1),
-                                                 int(call) & 0xFFFFFFFF, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out), _ptr(done_out), _ptr(trunc_out)))
+        self._policy_device(self._lib.mgym_rollout_mlp_sample, (_fptr(pol), int(hidden), act, *_draw(seed, call), int(K)),
+                            (actions_out, obs_out, reward_out, done_out, trunc_out))
 
     def rollout_mlp_gauss_device(self, policy, hidden, activation, sigma, seed, call, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """rollout_mlp_device for MountainCarContinuous and Pendulum with the action drawn from a Gaussian around the score (mgym_rollout_mlp_gauss):
         a = mu + sigma * z, `sigma` finite and >= 0, z a pure function of (seed, call, global env id, step) — include/mgym.h states it to the word.
         actions_out receives a before the step's clamp.  The handle keeps no count: pass a new `call` (a 32-bit word) for each call that is to draw afresh."""
         pol, act = self._mlp_args(policy, hidden, activation)
-        _check(self._lib.mgym_rollout_mlp_gauss(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden), act, float(sigma),
-                                                int(seed) & (2**64 - 1), int(call) & 0xFFFFFFFF, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out),
-                                                _ptr(done_out), _ptr(trunc_out)))
+        self._policy_device(self._lib.mgym_rollout_mlp_gauss, (_fptr(pol), int(hidden), act, float(sigma), *_draw(seed, call), int(K)),
+                            (actions_out, obs_out, reward_out, done_out, trunc_out))
 
     def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
         """host-array form: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc); actions float32 for MountainCarContinuous"""
@@ -320,23 +341,13 @@ class VecEnv:
         engine rejects), `activation` = "relu" / "tanh_fast" or the MGYM_ACT_* value (the exact tanh is refused), `head` = "greedy" (argmax / the score), "sample"
         (the draw of rollout_mlp_sample; discrete families) or "gauss" (mu + sigma * z of rollout_mlp_gauss; MountainCarContinuous, Pendulum) or the MGYM_HEAD_*
         value.  sigma, seed and call are ignored by the heads that do not use them.  A policy of the wrong length for (H1, H2) raises PolicyShapeError."""
-        act = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH, "tanh_fast": L.ACT_TANH_FAST}.get(activation, activation)
-        hd = {"greedy": L.HEAD_GREEDY, "sample": L.HEAD_SAMPLE, "gauss": L.HEAD_GAUSS}.get(head, head)
-        if not isinstance(act, (int, np.integer)):
-            raise PolicyShapeError(L.ERR_BAD_ARG, f'activation must be "relu", "tanh_fast" or an MGYM_ACT_* value, got {activation!r}')
-        if not isinstance(hd, (int, np.integer)):
-            raise PolicyShapeError(L.ERR_BAD_ARG, f'head must be "greedy", "sample", "gauss" or an MGYM_HEAD_* value, got {head!r}')
-        pol = None
-        if policy is not None:
-            D, A = self.mlp_dims()
-            h1, h2 = int(hidden1), int(hidden2)
-            pol = np.ascontiguousarray(np.asarray(policy, np.float32).ravel())
-            want = h1 * (D + 1) + h2 * (h1 + 1) + A * (h2 + 1)
-            if 1 <= h1 <= 64 and 1 <= h2 <= 64 and pol.size != want:
-                raise PolicyShapeError(L.ERR_BAD_ARG, f"policy must hold {want} floats for hidden1 = {h1}, hidden2 = {h2}, got {pol.size}")
-        _check(self._lib.mgym_rollout_mlp2(self._h, None if pol is None else pol.ctypes.data_as(C.POINTER(C.c_float)), int(hidden1), int(hidden2), int(act), int(hd),
-                                           float(sigma), int(seed) & (2**64 - 1), int(call) & 0xFFFFFFFF, int(K), _ptr(actions_out), _ptr(obs_out), _ptr(reward_out),
-                                           _ptr(done_out), _ptr(trunc_out)))
+        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh_fast" or an MGYM_ACT_* value')
+        hd = _named(_HEADS, head, 'head must be "greedy", "sample", "gauss" or an MGYM_HEAD_* value')
+        (D, A), h1, h2 = self.mlp_dims(), int(hidden1), int(hidden2)
+        want = h1 * (D + 1) + h2 * (h1 + 1) + A * (h2 + 1) if 1 <= h1 <= 64 and 1 <= h2 <= 64 else None
+        pol = None if policy is None else _policy_floats(policy, want, f"hidden1 = {h1}, hidden2 = {h2}")
+        self._policy_device(self._lib.mgym_rollout_mlp2, (_fptr(pol), h1, h2, act, hd, float(sigma), *_draw(seed, call), int(K)),
+                            (actions_out, obs_out, reward_out, done_out, trunc_out))
 
     def rollout_mlp2(self, w1, b1, w2, b2, w3, b3, K, activation="relu", head="greedy", sigma=0.0, seed=0, call=0):
         """host-array form of rollout_mlp2_device: -> (actions [K, n], obs [K, obs_dim, n], reward [K, n], done, trunc); actions float32 for the continuous families"""

@@ -133,96 +133,73 @@ class TorchVecEnv:
     def rollout(self, actions):
         """K fused steps for a caller-supplied action tensor [K, n] (mgym_rollout): returns
         (obs [K, obs_dim, n], reward [K, n], done [K, n], truncated [K, n]) as fresh tensors."""
-        torch = self._torch
         self._bind_stream()
         K = int(actions.shape[0])
         a = self._actions(actions, (K,))
-        obs = torch.empty((K, self.obs_dim, self.n), dtype=torch.float32, device=self.device)
-        rew = torch.empty((K, self.n), dtype=torch.float32, device=self.device)
-        done = torch.empty((K, self.n), dtype=torch.uint8, device=self.device)
-        trunc = torch.empty((K, self.n), dtype=torch.uint8, device=self.device)
+        obs, rew, done, trunc = self._policy_outputs(K, actions=False)
         self.env.rollout_device(a, K, obs, rew, done, trunc)
-        return obs, rew, done.view(torch.bool), trunc.view(torch.bool)
+        return obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
 
-    def _policy_outputs(self, K):
+    def _policy_outputs(self, K, actions=True):
+        """fresh [K, ..] tensors for a K-step call to fill: (actions if asked for,) obs, reward, done, truncated — the flags as uint8"""
         torch = self._torch
-        act = torch.empty((K, self.n), dtype=torch.float32 if self.action_is_float else torch.int32, device=self.device)
-        obs = torch.empty((K, self.obs_dim, self.n), dtype=torch.float32, device=self.device)
-        rew = torch.empty((K, self.n), dtype=torch.float32, device=self.device)
-        done = torch.empty((K, self.n), dtype=torch.uint8, device=self.device)
-        trunc = torch.empty((K, self.n), dtype=torch.uint8, device=self.device)
-        return act, obs, rew, done, trunc
+
+        def new(dtype, *mid):
+            return torch.empty((K, *mid, self.n), dtype=dtype, device=self.device)
+
+        out = new(torch.float32, self.obs_dim), new(torch.float32), new(torch.uint8), new(torch.uint8)
+        return (new(torch.float32 if self.action_is_float else torch.int32),) + out if actions else out
+
+    def _rollout_policy(self, weights, K, call):
+        """The tensor form of every policy call: on torch's current stream, the weights as host arrays (they are read on the host, during the call), fresh
+        [K, ..] outputs, call(host weights, K, outputs) — a VecEnv.*_device call — -> (actions, obs, reward, done, truncated), the flags as bool."""
+        torch = self._torch
+        self._bind_stream()
+        host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
+        K = int(K)
+        act, obs, rew, done, trunc = out = self._policy_outputs(K)
+        call(host, K, out)
+        return act, obs, rew, done.view(torch.bool), trunc.view(torch.bool)
 
     def rollout_linear(self, policy, K):
         """K fused steps under the on-device linear policy (mgym_rollout_linear; `policy`: host floats or a tensor, the layout
         VecEnv.rollout_linear_device documents): returns (actions [K, n], obs [K, obs_dim, n], reward [K, n], done [K, n], truncated [K, n])
         as fresh tensors, stream-ordered on torch's current stream (actions int32, float32 for MountainCarContinuous and Pendulum)."""
-        self._bind_stream()
-        if isinstance(policy, self._torch.Tensor):
-            policy = policy.detach().to("cpu", self._torch.float32).numpy()   # (the weights are read on the host, during the call)
-        K = int(K)
-        act, obs, rew, done, trunc = self._policy_outputs(K)
-        self.env.rollout_linear_device(policy, K, act, obs, rew, done, trunc)
-        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+        return self._rollout_policy((policy,), K, lambda host, K, out: self.env.rollout_linear_device(host[0], K, *out))
 
     def rollout_mlp(self, w1, b1, w2, b2, K, activation="relu"):
         """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): w1 [H, D], b1 [H], w2 [A, H], b2 [A] are tensors (or arrays) in
         nn.Linear layout — `rollout_mlp(net[0].weight, net[0].bias, net[2].weight, net[2].bias, K)` for nn.Sequential(Linear, ReLU / Tanh, Linear) — read on the
         host during the call; activation "relu", "tanh" or "tanh_fast" (the cheap tanh of include/mgym.h: what a collector wants).  Returns (actions, obs, reward, done, truncated) like rollout_linear."""
-        self._bind_stream()
-        host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2)]
-        policy, H = self.env.pack_mlp(*host)
-        K = int(K)
-        act, obs, rew, done, trunc = self._policy_outputs(K)
-        self.env.rollout_mlp_device(policy, H, activation, K, act, obs, rew, done, trunc)
-        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+        return self._rollout_policy((w1, b1, w2, b2), K, lambda host, K, out: self.env.rollout_mlp_device(*self.env.pack_mlp(*host), activation, K, *out))
 
     def rollout_mlp_sample(self, w1, b1, w2, b2, K, seed, call=0, activation="relu"):
         """rollout_mlp with the action drawn from the softmax of the scores (mgym_rollout_mlp_sample; the discrete families) — the collector of an on-policy
         trainer.  The draw is a pure function of (seed, call, global env id, step) and the scores: pass a new `call` for each call that is to draw afresh.
         Returns (actions, obs, reward, done, truncated) like rollout_mlp; log-probabilities are the learner's forward pass over obs and actions."""
-        self._bind_stream()
-        host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2)]
-        policy, H = self.env.pack_mlp(*host)
-        K = int(K)
-        act, obs, rew, done, trunc = self._policy_outputs(K)
-        self.env.rollout_mlp_sample_device(policy, H, activation, seed, call, K, act, obs, rew, done, trunc)
-        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+        return self._rollout_policy((w1, b1, w2, b2), K,
+                                    lambda host, K, out: self.env.rollout_mlp_sample_device(*self.env.pack_mlp(*host), activation, seed, call, K, *out))
 
     def rollout_mlp_gauss(self, w1, b1, w2, b2, K, sigma, seed, call=0, activation="relu"):
         """rollout_mlp for MountainCarContinuous and Pendulum with the action drawn from a Gaussian around the score, a = mu + sigma * z with a
         state-independent `sigma` >= 0 (mgym_rollout_mlp_gauss) — the collector of a continuous-control on-policy trainer.  z is a pure function of (seed,
         call, global env id, step): pass a new `call` for each call that is to draw afresh.  Returns (actions, obs, reward, done, truncated) like rollout_mlp;
         the actions are float32 and not clamped (the step clamps), so the learner's forward pass over obs and actions gives the log-probabilities."""
-        self._bind_stream()
-        host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2)]
-        policy, H = self.env.pack_mlp(*host)
-        K = int(K)
-        act, obs, rew, done, trunc = self._policy_outputs(K)
-        self.env.rollout_mlp_gauss_device(policy, H, activation, float(sigma), seed, call, K, act, obs, rew, done, trunc)
-        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+        return self._rollout_policy((w1, b1, w2, b2), K,
+                                    lambda host, K, out: self.env.rollout_mlp_gauss_device(*self.env.pack_mlp(*host), activation, float(sigma), seed, call, K, *out))
 
     def rollout_mlp2(self, w1, b1, w2, b2, w3, b3, K, activation="relu", head="greedy", sigma=0.0, seed=0, call=0):
         """K fused steps under the on-device two-hidden-layer policy (mgym_rollout_mlp2): the six tensors (or arrays) of nn.Sequential(Linear(D, H1), act,
         Linear(H1, H2), act, Linear(H2, A)) in nn.Linear layout, read on the host during the call; activation "relu" or "tanh_fast"; head "greedy", "sample" (the
         discrete families: the draw of rollout_mlp_sample) or "gauss" (MountainCarContinuous, Pendulum: mu + sigma * z of rollout_mlp_gauss).  Pass a new `call`
         for each call that is to draw afresh.  Returns (actions, obs, reward, done, truncated) like rollout_mlp."""
-        self._bind_stream()
-        host = [x.detach().to("cpu", self._torch.float32).numpy() if isinstance(x, self._torch.Tensor) else x for x in (w1, b1, w2, b2, w3, b3)]
-        policy, H1, H2 = self.env.pack_mlp2(*host)
-        K = int(K)
-        act, obs, rew, done, trunc = self._policy_outputs(K)
-        self.env.rollout_mlp2_device(policy, H1, H2, activation, head, float(sigma), seed, call, K, act, obs, rew, done, trunc)
-        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+        return self._rollout_policy((w1, b1, w2, b2, w3, b3), K,
+                                    lambda host, K, out: self.env.rollout_mlp2_device(*self.env.pack_mlp2(*host), activation, head, float(sigma), seed, call, K, *out))
 
     def rollout_uniform(self, seed, K):
         """K fused steps under the on-device uniform random policy (mgym_rollout_uniform, include/mgym.h): returns (actions, obs, reward,
         done, truncated) like rollout_linear."""
-        self._bind_stream()
-        K = int(K)
-        act, obs, rew, done, trunc = self._policy_outputs(K)
-        self.env.rollout_uniform_device(int(seed), K, act, obs, rew, done, trunc)
-        return act, obs, rew, done.view(self._torch.bool), trunc.view(self._torch.bool)
+        return self._rollout_policy((), K, lambda host, K, out: self.env.rollout_uniform_device(int(seed), K, *out))
 
     def bootstrap_obs(self, obs, done, truncated):
         """The observation a learner evaluates V on after each env-step of the last call: `obs` ([K, obs_dim, n], or [obs_dim, n] from step) with the final

@@ -1,7 +1,8 @@
 """The one policy-rollout entry of every family (Env::rollout_policy behind mgym_rollout_uniform / _linear / _mlp / _mlp_sample / _mlp_gauss / _mlp2): what
 the entry points share must not leak between them.
   1. The handle's count of uniform calls (a Philox counter word of the policy stream) moves only with uniform calls that launch.
-  2. Every rejection names the entry point that was called."""
+  2. Every rejection names the entry point that was called.
+  3. The C ABI's own rejections keep their order and their text."""
 import numpy as np
 import pytest
 
@@ -117,4 +118,82 @@ def test_every_rejection_names_its_entry_point(fam):
             assert ("below 2^30" in msg) == (fam == "cartpole"), msg
         env.sync()
         assert same(env.get_state(), before)                     # nothing ran
+        env.close()
+
+
+def test_abi_rejections_keep_their_order_and_text():
+    """The C ABI's own argument checks, called through the ctypes prototypes (the Python wrappers' checks out of the way) with two faults at once: which
+    one is reported, and its full text — the name of the entry point that was called, ": ", and the literal given here.  Nothing launches; every
+    handle's state stays what it was.  (The Pendulum handle with env_id_base = 2 is there for the checks that precede env_id_base in the Gaussian forms.)"""
+    import ctypes as C
+    lib = L.load()
+    P = (C.c_float * 8192)()                                     # a policy that is not NULL (nothing reads it)
+    NAN, RELU, TANH, SAMPLE, GAUSS = float("nan"), L.ACT_RELU, L.ACT_TANH, L.HEAD_SAMPLE, L.HEAD_GAUSS
+    PHILOX = "(one Philox block serves 4 consecutive global env ids)"
+    cp, pd = (mg.VecEnv(k, N, seed=7, auto_reset=True) for k in (mg.CARTPOLE, mg.PENDULUM))
+    cp2, pd2 = (mg.VecEnv(k, N, seed=7, auto_reset=True, env_id_base=2) for k in (mg.CARTPOLE, mg.PENDULUM))
+    envs = (cp, pd, cp2, pd2)
+    before = []
+    for env in envs:
+        env.reset()
+        before.append(env.get_state())
+
+    def refused(env, name, lead, text):
+        st = getattr(lib, "mgym_rollout_" + name)(env._h, *lead, None, None, None, None, None)
+        assert st == L.ERR_BAD_ARG, (name, lead, st)
+        assert lib.mgym_last_error().decode() == "mgym_rollout_" + name + ": " + text, (name, lead)
+
+    # the leading arguments of each entry point with every fault it can carry at once (NULL policy, widths, activation 2, head 3, sigma) and the given K
+    def every_fault(K):
+        return (("uniform", cp2, (1, K)), ("linear", cp, (None, K)), ("mlp", cp, (None, 0, 2, K)), ("mlp_sample", pd, (None, 0, 2, 1, 0, K)),
+                ("mlp_gauss", cp, (None, 0, 2, NAN, 1, 0, K)), ("mlp2", cp2, (None, 0, 65, 2, 3, -1.0, 1, 0, K)))
+
+    for name, env, lead in every_fault(-1):                      # K < 0 before a NULL policy, a family refusal and env_id_base
+        refused(env, name, lead, "K < 0")
+    bufs = [DeviceArray((1, env.obs_dim, N), np.float32) for env in envs]
+    for env, buf in zip(envs, bufs):
+        env.set_final_obs_out_device(buf, 1)
+    for name, env, lead in every_fault(2):                       # then the final-observation channel's steps_cap
+        refused(env, name, lead, "K = 2 exceeds steps_cap = 1 of mgym_set_final_obs_out")
+    for env in envs:
+        env.set_final_obs_out_device(None)
+
+    refused(cp, "mlp", (None, 0, 2, 1), "policy is NULL")
+    refused(cp, "mlp", (P, 0, 2, 1), "hidden must be between 1 and 64")
+    refused(cp, "mlp", (P, 3, 2, 1), "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST")
+    refused(cp, "linear", (None, 1), "policy is NULL")
+
+    refused(pd, "mlp_sample", (None, 0, 2, 1, 0, 1), "Pendulum has no discrete actions to draw from (a Gaussian head is not implemented)")
+    refused(cp2, "mlp_sample", (None, 0, 2, 1, 0, 1), "policy is NULL")
+    refused(cp2, "mlp_sample", (P, 0, 2, 1, 0, 1), "hidden must be between 1 and 64")
+    refused(cp2, "mlp_sample", (P, 3, 2, 1, 0, 1), "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST")
+    refused(cp2, "mlp_sample", (P, 3, RELU, 1, 0, 1), "env_id_base must be a multiple of 4 " + PHILOX)
+
+    refused(cp, "mlp_gauss", (None, 0, 2, NAN, 1, 0, 1), "CartPole has discrete actions: use mgym_rollout_mlp_sample")
+    refused(pd, "mlp_gauss", (None, 0, 2, NAN, 1, 0, 1), "policy is NULL")
+    refused(pd, "mlp_gauss", (P, 65, 2, NAN, 1, 0, 1), "hidden must be between 1 and 64")
+    refused(pd, "mlp_gauss", (P, 3, 2, NAN, 1, 0, 1), "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST")
+    refused(pd, "mlp_gauss", (P, 3, RELU, NAN, 1, 0, 1), "sigma must be finite and >= 0")
+    refused(pd2, "mlp_gauss", (P, 3, RELU, NAN, 1, 0, 1), "sigma must be finite and >= 0")
+    refused(pd2, "mlp_gauss", (P, 3, RELU, float("inf"), 1, 0, 1), "sigma must be finite and >= 0")
+    refused(pd2, "mlp_gauss", (P, 3, RELU, 0.5, 1, 0, 1), "env_id_base must be a multiple of 4 " + PHILOX)
+
+    refused(pd2, "mlp2", (None, 0, 65, TANH, 3, -1.0, 1, 0, 1), "policy is NULL")
+    refused(pd2, "mlp2", (P, 0, 65, TANH, 3, -1.0, 1, 0, 1), "hidden1 must be between 1 and 64")
+    refused(pd2, "mlp2", (P, 3, 65, TANH, 3, -1.0, 1, 0, 1), "hidden2 must be between 1 and 64")
+    refused(pd2, "mlp2", (P, 3, 5, TANH, 3, -1.0, 1, 0, 1), "activation MGYM_ACT_TANH is not offered with two hidden layers (the exact tanh would be nearly all of the "
+                                                            "launch): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU")
+    refused(pd2, "mlp2", (P, 3, 5, 2, 3, -1.0, 1, 0, 1), "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST")
+    refused(pd2, "mlp2", (P, 3, 5, RELU, 3, -1.0, 1, 0, 1), "head must be MGYM_HEAD_GREEDY, MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS")
+    refused(pd2, "mlp2", (P, 3, 5, RELU, SAMPLE, -1.0, 1, 0, 1), "head MGYM_HEAD_SAMPLE: Pendulum has no discrete actions to draw from (use MGYM_HEAD_GAUSS)")
+    refused(cp2, "mlp2", (P, 3, 5, RELU, GAUSS, -1.0, 1, 0, 1), "head MGYM_HEAD_GAUSS: CartPole has discrete actions (use MGYM_HEAD_SAMPLE)")
+    refused(pd2, "mlp2", (P, 3, 5, RELU, GAUSS, -1.0, 1, 0, 1), "sigma must be finite and >= 0")
+    refused(pd2, "mlp2", (P, 3, 5, RELU, GAUSS, 0.5, 1, 0, 1), "env_id_base must be a multiple of 4 for a drawing head " + PHILOX)
+    refused(cp2, "mlp2", (P, 3, 5, RELU, SAMPLE, -1.0, 1, 0, 1), "env_id_base must be a multiple of 4 for a drawing head " + PHILOX)
+
+    refused(cp2, "uniform", (1, 1), "env_id_base must be a multiple of 4 (policy bits are keyed per 4 consecutive global env ids)")
+
+    for env, b in zip(envs, before):
+        env.sync()
+        assert same(env.get_state(), b)                          # nothing ran
         env.close()

@@ -110,6 +110,48 @@ def test_rollout_tensor_equals_steps():
     fused.check(), plain.check()
 
 
+def test_policy_rollout_tensors_equal_the_host_forms():
+    """Every TorchVecEnv.rollout_* with tensor weights against the VecEnv.rollout_* of the same name with array weights, on handles created and reset alike:
+    the five outputs word for word, the actions' dtype, the flags as bool.  max_episode_steps = 3 < K where the family takes one (CartPole keeps the
+    reference's 500: mgym_create refuses 3), so on MountainCarContinuous every episode is truncated and reset inside the call."""
+    from words import same
+    n, K, H, H1, H2 = 8, 4, 3, 3, 5
+    rng = np.random.default_rng(21)
+
+    def weights(kind, *hidden):
+        """nn.Linear-layout arrays of a net D -> hidden.. -> A of the family"""
+        spec = mg.envs.get_spec(kind)
+        dims = (spec.obs_dim,) + hidden + (1 if spec.action_is_float else spec.n_actions,)
+        return [rng.uniform(-1, 1, s).astype(np.float32) for i in range(len(dims) - 1) for s in ((dims[i + 1], dims[i]), (dims[i + 1],))]
+
+    cases = []   # (kind, method, weight arrays, the arguments behind them)
+    for kind, draw, head in ((mg.CARTPOLE, "rollout_mlp_sample", "sample"), (mg.MOUNTAINCAR_CONT, "rollout_mlp_gauss", "gauss")):
+        sigma = (0.5,) if head == "gauss" else ()
+        cases.append((kind, draw, weights(kind, H), (K,) + sigma + (17, 2, "tanh_fast")))
+        cases.append((kind, "rollout_mlp2", weights(kind, H1, H2), (K, "relu", head, 0.5, 17, 2)))
+    cases.append((mg.CARTPOLE, "rollout_uniform", [], (23, K)))
+    cases.append((mg.CARTPOLE, "rollout_linear", [rng.uniform(-1, 1, 5).astype(np.float32)], (K,)))
+    cases.append((mg.CARTPOLE, "rollout_mlp", weights(mg.CARTPOLE, H), (K, "tanh")))
+    assert {c[1] for c in cases} == {"rollout_uniform", "rollout_linear", "rollout_mlp", "rollout_mlp_sample", "rollout_mlp_gauss", "rollout_mlp2"}
+
+    for kind, method, w, args in cases:
+        limit = 0 if kind == mg.CARTPOLE else 3
+        tenv = mg.TorchVecEnv(kind, n, seed=5, auto_reset=True, max_episode_steps=limit)
+        henv = mg.VecEnv(kind, n, seed=5, auto_reset=True, max_episode_steps=limit)
+        tenv.reset(), henv.reset()
+        got = getattr(tenv, method)(*(torch.from_numpy(x).to(tenv.device) for x in w), *args)
+        tenv.check()
+        exp = getattr(henv, method)(*w, *args)
+        what = f"{method} on {mg.envs.KIND_NAMES[kind]}"
+        assert got[0].dtype == (torch.float32 if kind == mg.MOUNTAINCAR_CONT else torch.int32), what
+        assert got[3].dtype == torch.bool and got[4].dtype == torch.bool, what
+        assert np.asarray(exp[4])[2].all() == (limit == 3), what   # the time limit ended every episode at the call's third step
+        for g, e, nm in zip(got, exp, ("actions", "obs", "reward", "done", "truncated")):
+            g = g.cpu().numpy()
+            assert same(g != 0, e != 0) if nm in ("done", "truncated") else same(g, e), f"{what}: {nm}"
+        tenv.close(), henv.close()
+
+
 def test_argument_checks():
     env = mg.TorchVecEnv(mg.CARTPOLE, 64, seed=1)
     env.reset()
