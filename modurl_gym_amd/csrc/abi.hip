@@ -325,7 +325,7 @@ static bool box_actions(const Env* e) { return e->cfg.kind == MGYM_MOUNTAINCAR_C
 enum { TAKES_POLICY = 1, TAKES_HIDDEN = 2, TAKES_HIDDEN2 = 4, TAKES_HEAD = 8, TAKES_SIGMA = 16, DRAWS = 32 };
 struct PolicyArgs { int32_t K; const float* policy = nullptr; int32_t hidden = 0, hidden2 = 0, activation = 0, head = 0; float sigma = 0.0f; };
 static_assert(MGYM_ACT_RELU == MLP_ACT_RELU && MGYM_ACT_TANH == MLP_ACT_TANH && MGYM_ACT_TANH_FAST == MLP_ACT_TANH_FAST, "mgym.h and mlp_policy.h number the activations alike");
-static_assert(MGYM_HEAD_GREEDY == MLP2_HEAD_GREEDY && MGYM_HEAD_SAMPLE == MLP2_HEAD_SAMPLE && MGYM_HEAD_GAUSS == MLP2_HEAD_GAUSS, "mgym.h and mlp2_policy.h number the heads alike");
+static_assert(MGYM_HEAD_GREEDY == MLP_HEAD_GREEDY && MGYM_HEAD_SAMPLE == MLP_HEAD_SAMPLE && MGYM_HEAD_GAUSS == MLP_HEAD_GAUSS, "mgym.h and mlp_policy.h number the heads alike");
 
 static int policy_args_ok(const Env* e, const char* api, int takes, const std::string& refusal, const PolicyArgs& a) {
     auto bad = [api](const std::string& what) { return bad_arg((std::string(api) + ": " + what).c_str()); };

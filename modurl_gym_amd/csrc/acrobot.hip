@@ -243,13 +243,12 @@ acrobot_step4_kernel(float* obs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 // per-env function and the same in-place auto-reset as the step kernels, hence bit-identical to K separate steps.
 // The policies decide from the six observation words held before the step (acrobot_step.h); actions_out holds u32 words.
 // (mgym_rollout_mlp2's sources take the address of the handle's pack and its widths at the head of the trailing pack: soa4.h)
-template <int POLICY> using AbPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<6, 3>, AbLinearPolicy>;
 template <int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 acrobot_rollout_kernel(AcrobotDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
-                       uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, AbPolicyArg<POLICY> pol = {}, uint32_t* __restrict__ act_out = nullptr,
+                       uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, PolicyArg<POLICY, 6, 3, AbLinearPolicy> pol = {}, uint32_t* __restrict__ act_out = nullptr,
                        UniformDraw uni = {}, Fin... fin) {
-    static_assert(!roll_act_gauss(POLICY), "Acrobot has discrete actions: no Gaussian draw");
+    static_assert(roll_act_discrete_takes(POLICY), "Acrobot has discrete actions: no Gaussian draw");
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool bad = false;
@@ -268,27 +267,15 @@ acrobot_rollout_kernel(AcrobotDev d, const uint32_t* __restrict__ act, int K, fl
                 if ((t & 1) == 0) bits = acrobot_uniform_block(uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = acrobot_uniform_action(bits.w[k], (uint32_t)t);
-            } else if constexpr (roll_act_is_mlp2(POLICY)) {
-                // mgym_rollout_mlp2: the argmax, or (SAMPLE) the draw of mgym_rollout_mlp_sample from the scores
-                static_assert(roll_act_mlp2_head(POLICY) != MLP2_HEAD_GAUSS, "Acrobot has discrete actions: no Gaussian draw");
+            } else if constexpr (roll_act_is_mlp(POLICY) || roll_act_is_mlp2(POLICY)) {
+                // hidden-layer policy of either depth on the six observation words: the argmax, or (SAMPLE) the draw from the scores — one Philox evaluation per
+                // lane per step, its four words for the lane's four envs (policy.h: net, activation and head)
                 float o[4][6];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acrobot_obs(e[k], o[k]);
-                Philox4 w{};
-                if constexpr (roll_act_mlp2_head(POLICY) == MLP2_HEAD_SAMPLE) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
-                mlp2_actions<6, 3, roll_act_mlp2_act(POLICY), roll_act_mlp2_head(POLICY), 4>(mlp2_net_of(fin...), o, w.w, 0.0f, a);
-            } else if constexpr (roll_act_is_mlp(POLICY)) {
-                float o[4][6];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acrobot_obs(e[k], o[k]);
-                constexpr int ACT = roll_act_mlp_act(POLICY);
-                if constexpr (roll_act_samples(POLICY)) {
-                    // mgym_rollout_mlp_sample: one Philox evaluation per lane per step, its four words for the lane's four envs
-                    const Philox4 w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
-                    mlp_actions<6, 3, ACT, 4>(pol, o, w.w, a);
-                } else {
-                    mlp_actions<6, 3, ACT, false, 4>(pol, o, a);
-                }
+                Philox4 w;
+                policy_draw<POLICY>(uni.seed, d.env_id_base + i0, uni.call, (uint32_t)t, w);
+                policy_actions4<POLICY, 6, 3>(pol, w.w, 0.0f, o, a, fin...);
             } else if constexpr (POLICY == ROLL_ACT_LINEAR) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -423,7 +410,7 @@ struct AcrobotEnv final : ClassicEnv {
     // the one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the
     // categorical draw's seed and call word; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
     template <int POLICY, class... Net>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const AbPolicyArg<POLICY>& arg, UniformDraw uni,
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const PolicyArg<POLICY, 6, 3, AbLinearPolicy>& arg, UniformDraw uni,
                         Net... net) {
         with_bools([&](auto T) {
             constexpr bool TL = decltype(T)::value;

@@ -293,11 +293,9 @@ cartpole_step_kernel(float* col0, uint32_t n_pad, uint32_t n, const uint32_t* __
 
 // policy of a fused rollout: actions from the caller's [K][n] table, or drawn / decided on the device (the action sources of policy.h)
 struct LinearPolicy { float w[4], b; };   // action = ((w0 x + w1 x_dot) + w2 theta) + w3 theta_dot + b > 0 (mgym_rollout_linear)
-// mgym_rollout_mlp: the weight pack of mlp_policy.h takes the place of the five linear words in the kernel's arguments (1 804 bytes by value; the other
-// policies' instantiations keep the arguments they had)
-typedef MlpPack<4, 2> CpMlpPack;
+// mgym_rollout_mlp: the weight pack of mlp_policy.h, MlpPack<4, 2>, takes the place of the five linear words in the kernel's arguments (PolicyArg, policy.h:
+// 1 804 bytes by value; the other policies' instantiations keep the arguments they had)
 // (mgym_rollout_mlp2's sources take the address of the handle's pack and its widths at the head of the trailing pack: soa4.h)
-template <int POLICY> using CpPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), CpMlpPack, LinearPolicy>;
 
 // Fused K-step rollout (mgym_rollout / mgym_rollout_uniform): one lane keeps its 4 environments in registers for
 // K steps; per step it reads one 16-B action word (or takes the next bit of its Philox policy stream) and writes
@@ -306,7 +304,7 @@ template <int POLICY> using CpPolicyArg = std::conditional_t<roll_act_is_mlp(POL
 // Fin: the call's [K][4][n] final observations — stored before the reset pass, which replaces the registers (the other outputs of a step leave after it)
 template <bool EULER, bool SB, bool RESET, int POLICY, class... Fin>
 __global__ void __launch_bounds__(kBlock)
-cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_t* __restrict__ act_out, uint64_t policy_seed, uint32_t policy_call, CpPolicyArg<POLICY> lin,
+cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_t* __restrict__ act_out, uint64_t policy_seed, uint32_t policy_call, PolicyArg<POLICY, 4, 2, LinearPolicy> lin,
                         int K, float* __restrict__ obs_out, float* __restrict__ rew, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, Fin... fin) {
     __shared__ WaveResetScratch<4> lds_[RESET ? kWaves : 1];
     constexpr uint64_t kPerBlock = (uint64_t)kBlock * 4;
@@ -344,37 +342,34 @@ cartpole_rollout_kernel(CartPoleDev d, const uint32_t* __restrict__ act, uint32_
             float r[4];
             if constexpr (POLICY == ROLL_ACT_TABLE) {
                 if (in) { const u32x4 va = __builtin_amdgcn_raw_buffer_load_b128(ra, off4, so, 2); a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w; }
-            } else if constexpr (roll_act_is_mlp2(POLICY)) {
-                // mgym_rollout_mlp2: the argmax, or (SAMPLE) the draw of mgym_rollout_mlp_sample from the scores
-                static_assert(roll_act_mlp2_head(POLICY) != MLP2_HEAD_GAUSS, "CartPole has discrete actions: no Gaussian draw");
+            } else if constexpr (roll_act_is_mlp(POLICY) || roll_act_is_mlp2(POLICY)) {
+                // hidden-layer policy of either depth on the observations the lane's four envs hold before the step (policy.h: net, activation and head; the
+                // heads that draw take one Philox evaluation per lane per step, its four words for the lane's four envs — policy_call: the caller's call word)
+                static_assert(roll_act_discrete_takes(POLICY), "CartPole has discrete actions: no Gaussian draw");
                 const float o[4][4] = {{s[0].x, s[0].xd, s[0].th, s[0].thd}, {s[1].x, s[1].xd, s[1].th, s[1].thd}, {s[2].x, s[2].xd, s[2].th, s[2].thd}, {s[3].x, s[3].xd, s[3].th, s[3].thd}};
-                Philox4 w{};
-                if constexpr (roll_act_mlp2_head(POLICY) == MLP2_HEAD_SAMPLE) w = env_draw(policy_seed, d.env_id_base + i0, policy_call, SLOT_POLICY_SAMPLE + (uint32_t)t);
-                mlp2_actions<4, 2, roll_act_mlp2_act(POLICY), roll_act_mlp2_head(POLICY), 4>(mlp2_net_of(fin...), o, w.w, 0.0f, a);
-                if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
-            } else if constexpr (roll_act_is_mlp(POLICY)) {
-                // hidden-layer policy on the observations the lane's four envs hold before the step (mlp_policy.h: fmaf chains from the bias, ascending index)
-                const float o[4][4] = {{s[0].x, s[0].xd, s[0].th, s[0].thd}, {s[1].x, s[1].xd, s[1].th, s[1].thd}, {s[2].x, s[2].xd, s[2].th, s[2].thd}, {s[3].x, s[3].xd, s[3].th, s[3].thd}};
-                constexpr int ACT = roll_act_mlp_act(POLICY);
-                if constexpr (roll_act_samples(POLICY)) {
-                    // mgym_rollout_mlp_sample: one Philox evaluation per lane per step, its four words for the lane's four envs (policy_call: the caller's call word)
-                    const Philox4 w = env_draw(policy_seed, d.env_id_base + i0, policy_call, SLOT_POLICY_SAMPLE + (uint32_t)t);
-                    mlp_actions<4, 2, ACT, 4>(lin, o, w.w, a);
+                if constexpr (roll_act_is_mlp2(POLICY)) {
+                    // (written out a second time for one dead initialiser: the two-layer kernels always zeroed their words first, the one-layer ones never did,
+                    // and either set allocates its registers otherwise with the other's declaration — DESIGN.md)
+                    Philox4 w{};
+                    policy_draw<POLICY>(policy_seed, d.env_id_base + i0, policy_call, (uint32_t)t, w);
+                    policy_actions4<POLICY, 4, 2>(lin, w.w, 0.0f, o, a, fin...);
                 } else {
-                    mlp_actions<4, 2, ACT, false, 4>(lin, o, a);
+                    Philox4 w;
+                    policy_draw<POLICY>(policy_seed, d.env_id_base + i0, policy_call, (uint32_t)t, w);
+                    policy_actions4<POLICY, 4, 2>(lin, w.w, 0.0f, o, a, fin...);
                 }
-                if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
             } else if constexpr (POLICY == ROLL_ACT_LINEAR) {
                 // linear policy on the observation the env holds before the step, in the documented order (the file is compiled with -ffp-contract=off)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = ((((lin.w[0] * s[k].x + lin.w[1] * s[k].xd) + lin.w[2] * s[k].th) + lin.w[3] * s[k].thd) + lin.b > 0.0f) ? 1u : 0u;
-                if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
             } else {
                 // uniform random policy: env i takes bit (t % 32) of word (i % 4) of Philox(policy_seed; lane's first
                 // global env id, policy_call, SLOT_POLICY + t / 32) — one Philox evaluation per lane per 32 steps
                 if ((t & 31) == 0) bits = env_draw(policy_seed, d.env_id_base + i0, policy_call, SLOT_POLICY + (uint32_t)(t >> 5));
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = (bits.w[k] >> (t & 31)) & 1u;
+            }
+            if constexpr (POLICY != ROLL_ACT_TABLE) {
                 if (in && act_out) __builtin_amdgcn_raw_buffer_store_b128(u32x4{a[0], a[1], a[2], a[3]}, ra, off4, so, 2);
             }
             cartpole_wave_advance<4, EULER, SB>(s, a, valid, r, dn, tr, bad);
@@ -565,7 +560,7 @@ struct CartPoleEnv final : Env {
     // the one launch of the fused rollout kernel with the action source POLICY; `lin`: the linear words or the hidden-layer pack, `uni`: the policy seed and call
     // word of a drawing source; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
     template <int POLICY, class... Net>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const CpPolicyArg<POLICY>& lin, UniformDraw uni,
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const PolicyArg<POLICY, 4, 2, LinearPolicy>& lin, UniformDraw uni,
                         Net... net) {
         const dim3 g(grid_for(n / 4)), b(kBlock);
         if (final_obs) {   // (an auto-reset handle: mgym_set_final_obs_out)

@@ -282,7 +282,7 @@ LLD uint32_t roll_decide(const RollPolicy& pol, const float* state) {
         uint32_t a[1];
 #pragma unroll
         for (int c = 0; c < 8; ++c) o[0][c] = state[c];
-        mlp_actions<8, 4, POLICY == ROLL_ACT_MLP_TANH ? MLP_ACT_TANH : MLP_ACT_RELU, false, 1>(pack, o, a);
+        mlp_actions<8, 4, roll_act_hidden_act(POLICY), MLP_HEAD_GREEDY, 1>(pack, o, {0u}, 0.0f, a);
         return a[0];
     }
 }

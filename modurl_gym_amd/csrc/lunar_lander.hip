@@ -706,7 +706,7 @@ __global__ void __launch_bounds__(256) ll_policy_mlp_kernel(const float* __restr
     uint32_t a[1];
 #pragma unroll
     for (int c = 0; c < 8; ++c) o[0][c] = obs[(uint64_t)c * n_pad + i];
-    mlp_actions<8, 4, ACT, false, 1>(pack, o, a);
+    mlp_actions<8, 4, ACT, MLP_HEAD_GREEDY, 1>(pack, o, {0u}, 0.0f, a);
     out[i] = a[0];
 }
 
@@ -722,11 +722,8 @@ __global__ void __launch_bounds__(256) ll_policy_mlp_sample_kernel(const float* 
     uint32_t a[1];
 #pragma unroll
     for (int c = 0; c < 8; ++c) o[0][c] = obs[(uint64_t)c * n_pad + i];
-    const uint64_t g = env_id_base + i;
-    const Philox4 w = env_draw(seed, g & ~3ull, call, SLOT_POLICY_SAMPLE + t);
-    const uint32_t k = (uint32_t)g & 3u;
-    const uint32_t word[1] = {k == 0u ? w.w[0] : k == 1u ? w.w[1] : k == 2u ? w.w[2] : w.w[3]};
-    mlp_actions<8, 4, ACT, 1>(pack, o, word, a);
+    const uint32_t word[1] = {env_draw_word(seed, env_id_base + i, call, SLOT_POLICY_SAMPLE + t)};
+    mlp_actions<8, 4, ACT, MLP_HEAD_SAMPLE, 1>(pack, o, word, 0.0f, a);
     out[i] = a[0];
 }
 
@@ -742,13 +739,8 @@ __global__ void __launch_bounds__(256) ll_policy_mlp2_kernel(const float* __rest
     uint32_t a[1], word[1] = {0u};
 #pragma unroll
     for (int c = 0; c < 8; ++c) o[0][c] = obs[(uint64_t)c * n_pad + i];
-    if constexpr (SAMPLE) {
-        const uint64_t g = env_id_base + i;
-        const Philox4 w = env_draw(seed, g & ~3ull, call, SLOT_POLICY_SAMPLE + t);
-        const uint32_t k = (uint32_t)g & 3u;
-        word[0] = k == 0u ? w.w[0] : k == 1u ? w.w[1] : k == 2u ? w.w[2] : w.w[3];
-    }
-    mlp2_actions<8, 4, ACT, SAMPLE ? MLP2_HEAD_SAMPLE : MLP2_HEAD_GREEDY, 1>(net, o, word, 0.0f, a);
+    if constexpr (SAMPLE) word[0] = env_draw_word(seed, env_id_base + i, call, SLOT_POLICY_SAMPLE + t);
+    mlp_actions<8, 4, ACT, SAMPLE ? MLP_HEAD_SAMPLE : MLP_HEAD_GREEDY, 1>(net, o, word, 0.0f, a);
     out[i] = a[0];
 }
 
@@ -1318,7 +1310,7 @@ struct LunarLanderEnv final : Env {
         }
         pol.next = next_act;
         const bool sample = roll_act_samples(policy);
-        const bool fast = mlp && roll_act_mlp_act(policy) == MLP_ACT_TANH_FAST;
+        const bool fast = mlp && roll_act_hidden_act(policy) == MLP_ACT_TANH_FAST;
         const bool persistent = !mlp2 && !sample && !fast && opt.roll_enabled && K >= opt.roll_min_k && !capturing() && (!mlp || opt.roll_mlp || kRollMlpPersistent[policy == ROLL_ACT_MLP_TANH]);
         if (!persistent) {
             int st = MGYM_OK;
@@ -1329,9 +1321,9 @@ struct LunarLanderEnv final : Env {
                 constexpr int SRC = decltype(S)::value;
                 if constexpr (roll_act_discrete_takes(SRC)) st = policy_steps(K, ao, obs_out, reward, done, trunc, [&](uint32_t t, uint32_t* a) {
                     if constexpr (roll_act_is_mlp2(SRC))
-                        hipLaunchKernelGGL((ll_policy_mlp2_kernel<roll_act_mlp2_act(SRC), roll_act_mlp2_head(SRC) == MLP2_HEAD_SAMPLE>), g, dim3(256), 0, stream, obs, n, n_pad, net, dev.env_id_base, call.seed, call.call, t, a);
-                    else if constexpr (roll_act_samples(SRC)) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<roll_act_mlp_act(SRC)>, g, dim3(256), 0, stream, obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, t, a);
-                    else if constexpr (roll_act_is_mlp(SRC)) hipLaunchKernelGGL(ll_policy_mlp_kernel<roll_act_mlp_act(SRC)>, g, dim3(256), 0, stream, obs, n, n_pad, pack, a);   // (the pack as a kernel argument: a captured graph carries it)
+                        hipLaunchKernelGGL((ll_policy_mlp2_kernel<roll_act_hidden_act(SRC), roll_act_head(SRC) == MLP_HEAD_SAMPLE>), g, dim3(256), 0, stream, obs, n, n_pad, net, dev.env_id_base, call.seed, call.call, t, a);
+                    else if constexpr (roll_act_samples(SRC)) hipLaunchKernelGGL(ll_policy_mlp_sample_kernel<roll_act_hidden_act(SRC)>, g, dim3(256), 0, stream, obs, n, n_pad, pack, dev.env_id_base, call.seed, call.call, t, a);
+                    else if constexpr (roll_act_is_mlp(SRC)) hipLaunchKernelGGL(ll_policy_mlp_kernel<roll_act_hidden_act(SRC)>, g, dim3(256), 0, stream, obs, n, n_pad, pack, a);   // (the pack as a kernel argument: a captured graph carries it)
                     else hipLaunchKernelGGL(ll_policy_kernel<SRC>, g, dim3(256), 0, stream, obs, n, n_pad, dev.env_id_base, pol, t, a);
                 });
             }, policy);

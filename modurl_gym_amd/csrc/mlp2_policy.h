@@ -6,7 +6,8 @@
 //   pre1_j = b1[j];  q = 0 .. D-1  ascending:  pre1_j = fmaf(W1[j][q], o[q], pre1_j);   h1_j = act(pre1_j)
 //   pre2_k = b2[k];  j = 0 .. H1-1 ascending:  pre2_k = fmaf(W2[k][j], h1_j, pre2_k);   h2_k = act(pre2_k)
 //   s_a    = b3[a];  k = 0 .. H2-1 ascending:  s_a    = fmaf(W3[a][k], h2_k, s_a)
-// act is mlp_policy.h's mlp_activate (ReLU or mg_tanhf_fast), and the heads are mlp_policy.h's too: mlp_argmax / the one score, mlp_sample, mlp_gauss_pair.
+// act is mlp_policy.h's mlp_activate (ReLU or mg_tanhf_fast).  This header gives the scores only, as an overload of mlp_scores on Mlp2Net: the action call and its
+// three heads are mlp_policy.h's mlp_actions, the same function for both depths.
 //
 // No chain is padded: fmaf(+0, +0, -0) is +0, so a chain run past its length over zero weights would turn a -0 pre-activation into +0, and mg_tanhf_fast
 // and the last chain carry that sign into the action word.  The chains over H1 terms run in whole chunks of 8 with a wave-uniform exit, then over the
@@ -17,8 +18,6 @@
 #include "mlp_policy.h"
 
 namespace mgym {
-
-enum { MLP2_HEAD_GREEDY = 0, MLP2_HEAD_SAMPLE = 1, MLP2_HEAD_GAUSS = 2 };   // = MGYM_HEAD_*
 
 // The weights as the kernels read them: a run of floats in device memory, the handle's own (Env::mlp2_dev), addressed in the constant address space — every
 // read is a wave-uniform scalar load.  At (64, 64) they are up to 20 768 bytes, five times what a kernel argument may hold.
@@ -93,7 +92,7 @@ MG_HD float mlp2_hidden1(Mlp2Ptr u, const float (&o)[D]) {
 // the A scores of N environments.  N = 4 (a lane of the classic kernels): two pairs, one after the other — a pair's h1 is 128 registers, four environments'
 // would be 256 beside the state — each FMA of the middle layer serving both members of the pair with one scalar weight; N = 1: LunarLander and the host.
 template <int D, int A, int ACT, int N>
-MG_HD void mlp2_scores(const Mlp2Net<D, A>& net, const float (&o)[N][D], float (&s)[N][A]) {
+MG_HD void mlp_scores(const Mlp2Net<D, A>& net, const float (&o)[N][D], float (&s)[N][A]) {
     constexpr int P = N >= 2 ? 2 : 1;
     static_assert(N % P == 0, "whole pairs");
     const int H1 = net.h1, H2 = net.h2;
@@ -156,31 +155,15 @@ MG_HD void mlp2_scores(const Mlp2Net<D, A>& net, const float (&o)[N][D], float (
     }
 }
 
-// the action words of N environments under HEAD, word for word what mlp_policy.h's three mlp_actions do with their scores:
-//   GREEDY  the argmax (A > 1) or the one score's bits (A = 1: the continuous families)
-//   SAMPLE  environment k draws with the word w[k] (A > 1)
-//   GAUSS   N = 4, A = 1: (w0, w1) serve the first pair, (w2, w3) the second; mu + sigma * z
+#if !defined(__HIPCC__)
+// Host builds only (g++): the earlier names of the scores, the heads and the action call, for tests/native/mlp2_check.cpp as it stands (mlp_policy.h says why).
+enum { MLP2_HEAD_GREEDY = MLP_HEAD_GREEDY, MLP2_HEAD_SAMPLE = MLP_HEAD_SAMPLE, MLP2_HEAD_GAUSS = MLP_HEAD_GAUSS };
+template <int D, int A, int ACT, int N>
+MG_HD void mlp2_scores(const Mlp2Net<D, A>& net, const float (&o)[N][D], float (&s)[N][A]) { mlp_scores<D, A, ACT, N>(net, o, s); }
 template <int D, int A, int ACT, int HEAD, int N>
 MG_HD void mlp2_actions(const Mlp2Net<D, A>& net, const float (&o)[N][D], const uint32_t (&w)[N], float sigma, uint32_t (&act)[N]) {
-    float s[N][A];
-    mlp2_scores<D, A, ACT, N>(net, o, s);
-    if constexpr (HEAD == MLP2_HEAD_GAUSS) {
-        static_assert(A == 1 && N == 4, "the Gaussian head: the continuous families, a lane of four");
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            float ze, zo;
-            mlp_gauss_pair(w[2 * h], w[2 * h + 1], &ze, &zo);
-            act[2 * h] = as_u32(s[2 * h][0] + sigma * ze);
-            act[2 * h + 1] = as_u32(s[2 * h + 1][0] + sigma * zo);
-        }
-    } else if constexpr (HEAD == MLP2_HEAD_SAMPLE) {
-        static_assert(A >= 2, "a draw needs two actions");
-#pragma unroll
-        for (int k = 0; k < N; ++k) act[k] = mlp_sample<A>(s[k], w[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) act[k] = A == 1 ? as_u32(s[k][0]) : mlp_argmax<A>(s[k]);
-    }
+    mlp_actions<D, A, ACT, HEAD, N>(net, o, w, sigma, act);
 }
+#endif
 
 }  // namespace mgym

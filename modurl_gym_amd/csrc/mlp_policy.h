@@ -1,7 +1,8 @@
 // mlp_policy.h — the one-hidden-layer policy of mgym_rollout_mlp, mgym_rollout_mlp_sample and mgym_rollout_mlp_gauss (include/mgym.h), shared by the rollout
 // kernels of CartPole, MountainCar and Pendulum (cartpole.hip, mountain_car.hip, pendulum.hip: the lane's four environments), LunarLander's policy kernel
 // (lunar_lander.hip: one environment per lane) and the host checks tests/native/mlp_policy_check.cpp, mlp_sample_check.cpp, mlp_gauss_check.cpp and mlp_tanh_fast_check.cpp, which compile this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
-// -ffp-contract=off: the only fused operations are the cp_fmaf of the two chains.
+// -ffp-contract=off: the only fused operations are the cp_fmaf of the two chains.  The header also holds the one action call of both depths, mlp_actions<D, A,
+// ACT, HEAD, N>(net, o, w, sigma, act): the scores of `net` (this header's MlpPack, or mlp2_policy.h's Mlp2Net) and then the head, MLP_HEAD_GREEDY / _SAMPLE / _GAUSS.
 //
 //   pre_j = b1[j];  q = 0 .. D-1 ascending:  pre_j = fmaf(W1[j][q], o[q], pre_j)
 //   h_j   = pre_j > 0 ? pre_j : +0  (ReLU: NaN and -0 give +0)   |   mg_tanhf(pre_j)   |   mg_tanhf_fast(pre_j)
@@ -10,12 +11,14 @@
 // computes with the bias as its C input, and what glibc's fmaf computes on the host.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 #include "mgym_math.h"
 
 namespace mgym {
 
 constexpr int kMlpMaxHidden = 64;
 enum { MLP_ACT_RELU = 0, MLP_ACT_TANH = 1, MLP_ACT_TANH_FAST = 3 };   // = MGYM_ACT_RELU / MGYM_ACT_TANH / MGYM_ACT_TANH_FAST (2 is not an activation)
+enum { MLP_HEAD_GREEDY = 0, MLP_HEAD_SAMPLE = 1, MLP_HEAD_GAUSS = 2 };     // = MGYM_HEAD_*: how the scores become the action word (mlp_actions, below)
 
 // The weights as the kernels read them, passed BY VALUE as a kernel argument (wave-uniform: scalar loads from the kernel-argument segment, and a
 // captured graph carries them).  Hidden unit j's words are contiguous — W1[j][0 .. D-1], b1[j], W2[0 .. A-1][j] — so one unit is one run of scalar
@@ -94,15 +97,6 @@ MG_HD uint32_t mlp_argmax(const float (&s)[A]) {
     return a;
 }
 
-// the action words of N environments: the argmax (discrete families), or the one score's bits (MountainCarContinuous: CONT, A = 1)
-template <int D, int A, int ACT, bool CONT, int N>
-MG_HD void mlp_actions(const MlpPack<D, A>& p, const float (&o)[N][D], uint32_t (&act)[N]) {
-    float s[N][A];
-    mlp_scores<D, A, ACT, N>(p, o, s);
-#pragma unroll
-    for (int k = 0; k < N; ++k) act[k] = CONT ? as_u32(s[k][0]) : mlp_argmax<A>(s[k]);
-}
-
 // ---- mgym_rollout_mlp_sample: the action drawn from the categorical distribution over the scores (include/mgym.h, "The draw") ----
 //   m = the running best of mlp_argmax;  e_a = mg_expm1f(s_a - m) + 1;  c_a = c_{a-1} + e_a;  thr = u * c_{A-1};  the first a with thr < c_a, else A - 1
 // f32, nothing fused.  The best action b (the index mlp_argmax returns) has s_b - m = m - m, which is +0 for a finite m and a NaN otherwise, and
@@ -151,15 +145,6 @@ MG_HD uint32_t mlp_sample(const float (&s)[A], uint32_t w) {
     return mlp_sample_pick<A>(c, w);
 }
 
-// the SAMPLE form of mlp_actions: environment k draws with the word w[k] (discrete families only)
-template <int D, int A, int ACT, int N>
-MG_HD void mlp_actions(const MlpPack<D, A>& p, const float (&o)[N][D], const uint32_t (&w)[N], uint32_t (&act)[N]) {
-    float s[N][A];
-    mlp_scores<D, A, ACT, N>(p, o, s);
-#pragma unroll
-    for (int k = 0; k < N; ++k) act[k] = mlp_sample<A>(s[k], w[k]);
-}
-
 // ---- mgym_rollout_mlp_gauss: the one score is the mean of a Gaussian, a = mu + sigma * z (include/mgym.h, "The draw of z") ----
 // One Box-Muller transform turns a pair of Philox words into two independent normals, r cos(phi) for the even member of an environment pair and r sin(phi)
 // for the odd one, with r = sqrt(-2 ln u1).  The logarithm is the project's own: no library's log is defined to the word, and this one is a handful of
@@ -205,19 +190,61 @@ MG_HD void mlp_gauss_pair(uint32_t wa, uint32_t wb, float* z_even, float* z_odd)
     *z_odd = r * s;
 }
 
-// the GAUSS form of mlp_actions, N = 4: the lane's four environments (global ids g .. g + 3, g a multiple of 4) take the four normals of one Philox block w —
-// (w0, w1) for the first pair, (w2, w3) for the second — and the action word is that of mu + sigma * z, an f32 multiply and an f32 add, before any clamp
-template <int D, int ACT>
-MG_HD void mlp_actions(const MlpPack<D, 1>& p, const float (&o)[4][D], const uint32_t (&w)[4], float sigma, uint32_t (&act)[4]) {
-    float mu[4][1];
-    mlp_scores<D, 1, ACT, 4>(p, o, mu);
+// ---- the action call, the one copy for both depths: the scores of N environments under `net`, then the head that turns them into action words ----
+// `net` is an MlpPack here, or mlp2_policy.h's Mlp2Net: mlp_scores is overloaded on it.  The heads (MLP_HEAD_*):
+//   GREEDY  the argmax (A > 1) or the one score's bits (A = 1: the continuous families); w and sigma are not read
+//   SAMPLE  environment k draws with the word w[k] (A > 1)
+//   GAUSS   N = 4, A = 1: the lane's four environments (global ids g .. g + 3, g a multiple of 4) take the four normals of one Philox block w — (w0, w1) for
+//           the first pair, (w2, w3) for the second — and the action word is that of mu + sigma * z, an f32 multiply and an f32 add, before any clamp
+// The head stands in the function that owns the scores, not in one of its own that takes them: handed on by reference the twelve scores of a lane come out of
+// the compiler's scalar replacement in another order, and every SAMPLE kernel of the classic families changes its register allocation.
+template <int D, int A> struct Mlp2Net;   // (mlp2_policy.h)
+template <int D, int A, int ACT, int HEAD, int N, class Net>
+MG_HD void mlp_actions(const Net& net, const float (&o)[N][D], const uint32_t (&w)[N], float sigma, uint32_t (&act)[N]) {
+    static_assert(std::is_same_v<Net, MlpPack<D, A>> || std::is_same_v<Net, Mlp2Net<D, A>>, "net: the MlpPack or the Mlp2Net of these D and A");
+    float s[N][A];
+    mlp_scores<D, A, ACT, N>(net, o, s);
+    if constexpr (HEAD == MLP_HEAD_GAUSS) {
+        static_assert(A == 1 && N == 4, "the Gaussian head: the continuous families, a lane of four");
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        float ze, zo;
-        mlp_gauss_pair(w[2 * h], w[2 * h + 1], &ze, &zo);
-        act[2 * h] = as_u32(mu[2 * h][0] + sigma * ze);
-        act[2 * h + 1] = as_u32(mu[2 * h + 1][0] + sigma * zo);
+        for (int h = 0; h < 2; ++h) {
+            float ze, zo;
+            mlp_gauss_pair(w[2 * h], w[2 * h + 1], &ze, &zo);
+            act[2 * h] = as_u32(s[2 * h][0] + sigma * ze);
+            act[2 * h + 1] = as_u32(s[2 * h + 1][0] + sigma * zo);
+        }
+    } else if constexpr (HEAD == MLP_HEAD_SAMPLE) {
+        static_assert(A >= 2, "a draw needs two actions");
+#pragma unroll
+        for (int k = 0; k < N; ++k) act[k] = mlp_sample<A>(s[k], w[k]);
+    } else {
+        static_assert(HEAD == MLP_HEAD_GREEDY, "one of the three heads");
+#pragma unroll
+        for (int k = 0; k < N; ++k) act[k] = A == 1 ? as_u32(s[k][0]) : mlp_argmax<A>(s[k]);
     }
 }
+
+#if !defined(__HIPCC__)
+// Host builds only (g++, tests/native): the three earlier spellings of that call, told apart by their argument lists.  The host checks call them, and those
+// files underlie some 320 host and GPU tests that have to pass unchanged, so the spellings stay for them and forward to the one call above.  A kernel's
+// translation unit does not see them: under hipcc mlp_actions is the one template.
+//   <D, A, ACT, CONT, N>(p, o, act)        GREEDY (CONT said what A == 1 says)
+//   <D, A, ACT, N>(p, o, w, act)            SAMPLE
+//   <D, ACT>(p, o, w, sigma, act)           GAUSS, N = 4
+template <int D, int A, int ACT, bool CONT, int N>
+MG_HD void mlp_actions(const MlpPack<D, A>& p, const float (&o)[N][D], uint32_t (&act)[N]) {
+    static_assert(CONT == (A == 1), "the one score is the action exactly when there is one");
+    const uint32_t w[N] = {};
+    mlp_actions<D, A, ACT, MLP_HEAD_GREEDY, N>(p, o, w, 0.0f, act);
+}
+template <int D, int A, int ACT, int N>
+MG_HD void mlp_actions(const MlpPack<D, A>& p, const float (&o)[N][D], const uint32_t (&w)[N], uint32_t (&act)[N]) {
+    mlp_actions<D, A, ACT, MLP_HEAD_SAMPLE, N>(p, o, w, 0.0f, act);
+}
+template <int D, int ACT>
+MG_HD void mlp_actions(const MlpPack<D, 1>& p, const float (&o)[4][D], const uint32_t (&w)[4], float sigma, uint32_t (&act)[4]) {
+    mlp_actions<D, 1, ACT, MLP_HEAD_GAUSS, 4>(p, o, w, sigma, act);
+}
+#endif
 
 }  // namespace mgym

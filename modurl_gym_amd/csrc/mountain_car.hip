@@ -264,15 +264,13 @@ struct McLinearPolicy { float w[3][2], b[3]; };
 // the force u 2^-23 - 1, uniform over the multiples of 2^-23 in [-1, 1).
 // mgym_rollout_mlp: the weight pack of mlp_policy.h (A = 3 scores, or the one force of MountainCarContinuous) takes the place of the linear words in the
 // kernel's arguments; the other policies' instantiations keep the arguments they had
-// (mgym_rollout_mlp2's sources take the address of the handle's pack, its widths and sigma at the head of the trailing pack: soa4.h)
-template <bool CONT, int POLICY> using McPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<2, CONT ? 1 : 3>, McLinearPolicy>;
-// mgym_rollout_mlp_gauss (MountainCarContinuous only): sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
-template <int POLICY> using McDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, UniformDraw>;
+// (PolicyArg, policy.h; mgym_rollout_mlp2's sources take the address of the handle's pack, its widths and sigma at the head of the trailing pack: soa4.h)
+// mgym_rollout_mlp_gauss (MountainCarContinuous only): sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream (DrawArg)
 template <bool CONT, int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
-                           uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, McPolicyArg<CONT, POLICY> lin = {}, uint32_t* __restrict__ act_out = nullptr,
-                           McDrawArg<POLICY> uni = {}, Fin... fin_out) {
+                           uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, PolicyArg<POLICY, 2, CONT ? 1 : 3, McLinearPolicy> lin = {}, uint32_t* __restrict__ act_out = nullptr,
+                           DrawArg<POLICY> uni = {}, Fin... fin_out) {
     constexpr bool LINEAR = POLICY == ROLL_ACT_LINEAR;
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -297,37 +295,13 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                     if constexpr (CONT) a[k] = __float_as_uint((float)(bits.w[k] >> 8) * 1.1920928955078125e-07f - 1.0f);
                     else a[k] = ((((t & 1) ? bits.w[k] >> 16 : bits.w[k] & 0xffffu)) * 3u) >> 16;
                 }
-                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
-            } else if constexpr (roll_act_is_mlp2(POLICY)) {
-                // mgym_rollout_mlp2: the argmax / the one score, or the draw of mgym_rollout_mlp_sample (Discrete(3)) / mgym_rollout_mlp_gauss (Box(-1, 1))
-                constexpr int HEAD = roll_act_mlp2_head(POLICY);
-                static_assert(HEAD == MLP2_HEAD_GREEDY || (CONT ? HEAD == MLP2_HEAD_GAUSS : HEAD == MLP2_HEAD_SAMPLE), "the heads a family has");
+            } else if constexpr (roll_act_is_mlp(POLICY) || roll_act_is_mlp2(POLICY)) {
+                // hidden-layer policy of either depth on (position, velocity) of the lane's four envs before the step (policy.h: net, activation, head and draw)
+                static_assert(CONT ? roll_act_box_takes(POLICY) : roll_act_discrete_takes(POLICY), "the heads a family has");
                 const float o[4][2] = {{ps[0], vs[0]}, {ps[1], vs[1]}, {ps[2], vs[2]}, {ps[3], vs[3]}};
-                const Mlp2Net<2, CONT ? 1 : 3>& net = mlp2_net_of(fin_out...);
-                Philox4 w{};
-                if constexpr (HEAD == MLP2_HEAD_SAMPLE) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
-                if constexpr (HEAD == MLP2_HEAD_GAUSS) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_GAUSS + (uint32_t)t);
-                mlp2_actions<2, CONT ? 1 : 3, roll_act_mlp2_act(POLICY), HEAD, 4>(net, o, w.w, net.sigma, a);
-                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
-            } else if constexpr (roll_act_is_mlp(POLICY)) {
-                // hidden-layer policy on (position, velocity) of the lane's four envs before the step (mlp_policy.h)
-                const float o[4][2] = {{ps[0], vs[0]}, {ps[1], vs[1]}, {ps[2], vs[2]}, {ps[3], vs[3]}};
-                constexpr int ACT = roll_act_mlp_act(POLICY);
-                if constexpr (roll_act_samples(POLICY)) {
-                    // mgym_rollout_mlp_sample (Discrete(3) only): one Philox evaluation per lane per step, its four words for the lane's four envs; `uni`
-                    // carries the policy seed and the caller's call word
-                    static_assert(!CONT, "MountainCarContinuous has no categorical draw");
-                    const Philox4 w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_SAMPLE + (uint32_t)t);
-                    mlp_actions<2, 3, ACT, 4>(lin, o, w.w, a);
-                } else if constexpr (roll_act_gauss(POLICY)) {
-                    // mgym_rollout_mlp_gauss (Box(-1, 1) only): one Philox evaluation per lane per step, its two word pairs for the lane's two env pairs
-                    static_assert(CONT, "MountainCar has discrete actions: no Gaussian draw");
-                    const Philox4 w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_GAUSS + (uint32_t)t);
-                    mlp_actions<2, ACT>(lin, o, w.w, uni.sigma, a);
-                } else {
-                    mlp_actions<2, CONT ? 1 : 3, ACT, CONT, 4>(lin, o, a);
-                }
-                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
+                Philox4 w;
+                policy_draw<POLICY>(uni.seed, d.env_id_base + i0, uni.call, (uint32_t)t, w);
+                policy_actions4<POLICY, 2, CONT ? 1 : 3>(lin, w.w, draw_sigma(uni), o, a, fin_out...);
             } else if constexpr (LINEAR) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -340,10 +314,12 @@ mountaincar_rollout_kernel(MountainCarDev d, const uint32_t* __restrict__ act, i
                         a[k] = s2 > sb ? 2u : best;
                     }
                 }
-                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
             } else {
                 u32x4 va = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(act + off));
                 a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w;
+            }
+            if constexpr (POLICY != ROLL_ACT_TABLE) {
+                if (act_out) __builtin_nontemporal_store(u32x4{a[0], a[1], a[2], a[3]}, reinterpret_cast<u32x4*>(act_out + off));
             }
             float r[4];
             uint32_t tr[4] = {0u, 0u, 0u, 0u};
@@ -461,8 +437,8 @@ struct MountainCarEnv final : ClassicEnv {
     // the one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear weights or the hidden-layer pack, `uni`: the uniform stream, or the
     // Gaussian draw's sigma, seed and call word; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
     template <bool CONT, int POLICY, class... Net>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const McPolicyArg<CONT, POLICY>& arg,
-                        McDrawArg<POLICY> uni, Net... net) {
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const PolicyArg<POLICY, 2, CONT ? 1 : 3, McLinearPolicy>& arg,
+                        DrawArg<POLICY> uni, Net... net) {
         with_bools([&](auto T) {
             constexpr bool TL = decltype(T)::value;
             if (final_obs) hipLaunchKernelGGL((mountaincar_rollout_kernel<CONT, POLICY, TL, Net..., float*>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net..., final_obs);

@@ -214,15 +214,13 @@ pendulum_step4_kernel(float* cs_col, uint32_t n_pad, uint32_t n, const uint32_t*
 // function and the same in-place auto-reset as the step kernels, hence bit-identical to K separate steps.  One sincos per environment-step.
 // The policies decide from (cos, sin, thdot) held before the step (pendulum_step.h); actions_out holds f32 words.
 // (mgym_rollout_mlp2's sources take the address of the handle's pack, its widths and sigma at the head of the trailing pack: soa4.h)
-template <int POLICY> using PdPolicyArg = std::conditional_t<roll_act_is_mlp(POLICY), MlpPack<3, 1>, PdLinearPolicy>;
-// mgym_rollout_mlp_gauss: sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream
-template <int POLICY> using PdDrawArg = std::conditional_t<roll_act_gauss(POLICY), GaussDraw, UniformDraw>;
+// mgym_rollout_mlp_gauss: sigma, the policy seed and the call word travel beside the pack, in the place of the uniform stream (PolicyArg, DrawArg: policy.h)
 template <int POLICY = ROLL_ACT_TABLE, bool TL = false, class... Fin>
 __global__ void __launch_bounds__(kBlock)
 pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, float* __restrict__ obs_out, float* __restrict__ rew,
-                        uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, PdPolicyArg<POLICY> pol = {}, uint32_t* __restrict__ act_out = nullptr,
-                        PdDrawArg<POLICY> uni = {}, Fin... fin) {
-    static_assert(!roll_act_samples(POLICY), "Pendulum has no categorical draw");
+                        uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, PolicyArg<POLICY, 3, 1, PdLinearPolicy> pol = {}, uint32_t* __restrict__ act_out = nullptr,
+                        DrawArg<POLICY> uni = {}, Fin... fin) {
+    static_assert(roll_act_box_takes(POLICY), "Pendulum has no categorical draw");
     const uint64_t groups = d.n / 4;  // n % 4 == 0 is required by the host wrapper
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool bad = false;
@@ -239,21 +237,17 @@ pendulum_rollout_kernel(PendulumDev d, const uint32_t* __restrict__ act, int K, 
             uint32_t a[4];
             if constexpr (POLICY == ROLL_ACT_UNIFORM) {
                 pendulum_uniform_actions(uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, a);
-            } else if constexpr (roll_act_is_mlp2(POLICY)) {
-                // mgym_rollout_mlp2: the score, or (GAUSS) the draw of mgym_rollout_mlp_gauss around it
-                static_assert(roll_act_mlp2_head(POLICY) != MLP2_HEAD_SAMPLE, "Pendulum has no categorical draw");
-                const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
-                const Mlp2Net<3, 1>& net = mlp2_net_of(fin...);
-                Philox4 w{};
-                if constexpr (roll_act_mlp2_head(POLICY) == MLP2_HEAD_GAUSS) w = env_draw(uni.seed, d.env_id_base + i0, uni.call, SLOT_POLICY_GAUSS + (uint32_t)t);
-                mlp2_actions<3, 1, roll_act_mlp2_act(POLICY), roll_act_mlp2_head(POLICY), 4>(net, o, w.w, net.sigma, a);
             } else if constexpr (roll_act_gauss(POLICY)) {
-                // mgym_rollout_mlp_gauss: one Philox evaluation per lane per step, its two word pairs for the lane's two env pairs
+                // mgym_rollout_mlp_gauss: written out beside the branch below, through the forwarding function it always had (no other form kept its code)
                 const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
-                pendulum_gauss_actions<roll_act_mlp_act(POLICY)>(pol, o, uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, uni.sigma, a);
-            } else if constexpr (roll_act_is_mlp(POLICY)) {
+                pendulum_gauss_actions<roll_act_hidden_act(POLICY)>(pol, o, uni.seed, uni.call, d.env_id_base + i0, (uint32_t)t, uni.sigma, a);
+            } else if constexpr (roll_act_is_mlp(POLICY) || roll_act_is_mlp2(POLICY)) {
+                // hidden-layer policy of either depth on (cos, sin, thdot): the one score is the torque, or (the two-layer GAUSS head) the mean of the draw around it —
+                // one Philox evaluation per lane per step, its two word pairs for the lane's two env pairs (policy.h: net, activation and head; the step clamps the torque)
                 const float o[4][3] = {{cs[0], sn[0], td[0]}, {cs[1], sn[1], td[1]}, {cs[2], sn[2], td[2]}, {cs[3], sn[3], td[3]}};
-                pendulum_mlp_actions<roll_act_mlp_act(POLICY), 4>(pol, o, a);
+                Philox4 w;
+                policy_draw<POLICY>(uni.seed, d.env_id_base + i0, uni.call, (uint32_t)t, w);
+                policy_actions4<POLICY, 3, 1>(pol, w.w, draw_sigma(uni), o, a, fin...);
             } else if constexpr (POLICY == ROLL_ACT_LINEAR) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) a[k] = pendulum_linear_action(pol, cs[k], sn[k], td[k]);
@@ -383,8 +377,8 @@ struct PendulumEnv final : ClassicEnv {
     // the one launch of the fused rollout kernel with the action source POLICY; `arg`: the linear words or the hidden-layer pack, `uni`: the uniform stream, or the
     // Gaussian draw's sigma, seed and call word; `net`: a two-hidden-layer source's Mlp2Net, the head of the kernel's trailing pack
     template <int POLICY, class... Net>
-    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const PdPolicyArg<POLICY>& arg,
-                        PdDrawArg<POLICY> uni, Net... net) {
+    void launch_rollout(const uint32_t* act, uint32_t* act_out, int K, float* obs_out, float* reward, uint8_t* done, uint8_t* trunc, const PolicyArg<POLICY, 3, 1, PdLinearPolicy>& arg,
+                        DrawArg<POLICY> uni, Net... net) {
         with_bools([&](auto T, auto F) {
             constexpr bool TL = decltype(T)::value;
             if constexpr (!decltype(F)::value) hipLaunchKernelGGL((pendulum_rollout_kernel<POLICY, TL, Net...>), dim3(grid_for(n / 4)), dim3(kBlock), 0, stream, dev, act, K, obs_out, reward, done, trunc, arg, act_out, uni, net...);

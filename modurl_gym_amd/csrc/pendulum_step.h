@@ -102,17 +102,22 @@ MG_HD uint32_t pendulum_linear_action(const PdLinearPolicy& p, float cs, float s
     return as_u32(((p.w[0] * cs + p.w[1] * sn) + p.w[2] * thdot) + p.b);
 }
 
-// mgym_rollout_mlp: D = 3, A = 1, s_0 is the torque (mlp_policy.h's CONT form)
+// mgym_rollout_mlp / _mlp2: D = 3, A = 1 in mlp_policy.h's mlp_actions — s_0 is the torque (policy.h's policy_actions4)
+#if !defined(__HIPCC__)
+// Host builds only (g++): the forwarding function the kernels once called, for tests/native/pendulum_check.cpp as it stands (mlp_policy.h says why)
 template <int ACT, int N>
 MG_HD void pendulum_mlp_actions(const MlpPack<3, 1>& p, const float (&o)[N][3], uint32_t (&a)[N]) { mlp_actions<3, 1, ACT, true, N>(p, o, a); }
+#endif
 
 // mgym_rollout_mlp_gauss: the torque is s_0 + sigma * z, the four envs with global ids g .. g + 3 (g a multiple of 4) taking the four normals of one Philox
-// block keyed by the policy seed, counter (g lo, g hi, call, SLOT_POLICY_GAUSS + t) (mlp_policy.h's GAUSS form; the step clamps the torque)
+// block keyed by the policy seed, counter (g lo, g hi, call, SLOT_POLICY_GAUSS + t) (mlp_policy.h's GAUSS head; the step clamps the torque).  A forwarding
+// function kept on purpose: with this draw and call written into the kernel, or made through policy.h's policy_draw / policy_actions4, the nine Gaussian
+// kernels of one hidden layer hoist their Philox key schedule in another order
 template <int ACT>
 __device__ __forceinline__ void pendulum_gauss_actions(const MlpPack<3, 1>& p, const float (&o)[4][3], uint64_t policy_seed, uint32_t call, uint64_t g, uint32_t t, float sigma,
                                                        uint32_t (&a)[4]) {
     const Philox4 b = env_draw(policy_seed, g, call, SLOT_POLICY_GAUSS + t);
-    mlp_actions<3, ACT>(p, o, b.w, sigma, a);
+    mlp_actions<3, 1, ACT, MLP_HEAD_GAUSS, 4>(p, o, b.w, sigma, a);
 }
 
 }  // namespace mgym

@@ -42,6 +42,14 @@ __device__ __forceinline__ Philox4 env_draw(uint64_t seed, uint64_t env_id, uint
                          (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
+// one environment per lane where a lane of four shares a block: environment g takes word g % 4 of the block of g & ~3.  Every lane evaluates the block of its
+// group of four ids itself.
+__device__ __forceinline__ uint32_t env_draw_word(uint64_t seed, uint64_t g, uint32_t call, uint32_t slot) {
+    const Philox4 w = env_draw(seed, g & ~3ull, call, slot);
+    const uint32_t k = (uint32_t)g & 3u;
+    return k == 0u ? w.w[0] : k == 1u ? w.w[1] : k == 2u ? w.w[2] : w.w[3];
+}
+
 // [0,1) with 53 random bits
 __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {
     uint64_t m = ((uint64_t)(hi >> 5) << 26) | (uint64_t)(lo >> 6);

@@ -85,13 +85,13 @@ __device__ __forceinline__ uint32_t reset_mask4(const uint8_t* m0, const uint8_t
 // mgym_set_final_obs_out.  The stepping kernels end their template parameters with `class... Fin` and their arguments with `Fin... fin`: the pack is
 // empty (the kernel as it always was: same arguments, same code) or one float* (the channel's instantiation, launched only while a pointer is set).
 // The rollout kernels of the two-hidden-layer sources (mgym_rollout_mlp2) take their Mlp2Net at the head of the same pack, before the channel's pointer:
-// what a newer source adds to the argument list travels there, so every instantiation from before it keeps its arguments, its code and its name.
+// what a newer source adds to the argument list travels there, so every instantiation from before it keeps its arguments, its code and its name
+// (policy.h's mlp2_net_of reads it).
 template <class... Fin> constexpr bool has_final = (std::is_same_v<Fin, float*> || ...);
 __device__ __forceinline__ float* final_ptr() { return nullptr; }
 __device__ __forceinline__ float* final_ptr(float* p) { return p; }
 template <int D, int A> __device__ __forceinline__ float* final_ptr(const Mlp2Net<D, A>&) { return nullptr; }
 template <int D, int A> __device__ __forceinline__ float* final_ptr(const Mlp2Net<D, A>&, float* p) { return p; }
-template <int D, int A, class... Rest> __device__ __forceinline__ const Mlp2Net<D, A>& mlp2_net_of(const Mlp2Net<D, A>& net, Rest...) { return net; }
 // the D observation words of one finished environment, column k at fin + k * n — sparse 4-byte stores by the owning lane,
 // made after the physics and before the fused reset replaces the registers.  `fin` points at the step's [D][n] slab, at the env's column.
 // Plain stores, not non-temporal ones like the dense outputs: measured at 1 Mi CartPole envs, the K = 16 uniform rollout with the channel set costs
