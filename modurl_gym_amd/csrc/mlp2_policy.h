@@ -1,5 +1,5 @@
 // mlp2_policy.h — the two-hidden-layer policy of mgym_rollout_mlp2 (include/mgym.h), shared by the rollout kernels of the classic families (the lane's four
-// environments, taken as two packed pairs), LunarLander's ll_policy_mlp2_kernel (one environment per lane) and the host check tests/native/mlp2_check.cpp,
+// environments, taken as two packed pairs), LunarLander's ll_policy_mlp2_kernel (one environment per lane) and the host check tests/native/policy_check.cpp,
 // which compiles this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with -ffp-contract=off: the only fused operations are the cp_fmaf of
 // the three chains.
 //
@@ -156,7 +156,8 @@ MG_HD void mlp_scores(const Mlp2Net<D, A>& net, const float (&o)[N][D], float (&
 }
 
 #if !defined(__HIPCC__)
-// Host builds only (g++): the earlier names of the scores, the heads and the action call, for tests/native/mlp2_check.cpp as it stands (mlp_policy.h says why).
+// Host builds only (g++): the earlier names of the scores, the heads and the action call, forwarding to mlp_scores and mlp_actions; no file of the tree uses them
+// (as mlp_policy.h's earlier spellings).
 enum { MLP2_HEAD_GREEDY = MLP_HEAD_GREEDY, MLP2_HEAD_SAMPLE = MLP_HEAD_SAMPLE, MLP2_HEAD_GAUSS = MLP_HEAD_GAUSS };
 template <int D, int A, int ACT, int N>
 MG_HD void mlp2_scores(const Mlp2Net<D, A>& net, const float (&o)[N][D], float (&s)[N][A]) { mlp_scores<D, A, ACT, N>(net, o, s); }

@@ -1,6 +1,6 @@
 // mlp_policy.h — the one-hidden-layer policy of mgym_rollout_mlp, mgym_rollout_mlp_sample and mgym_rollout_mlp_gauss (include/mgym.h), shared by the rollout
 // kernels of CartPole, MountainCar and Pendulum (cartpole.hip, mountain_car.hip, pendulum.hip: the lane's four environments), LunarLander's policy kernel
-// (lunar_lander.hip: one environment per lane) and the host checks tests/native/mlp_policy_check.cpp, mlp_sample_check.cpp, mlp_gauss_check.cpp and mlp_tanh_fast_check.cpp, which compile this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
+// (lunar_lander.hip: one environment per lane) and the host checks tests/native/policy_check.cpp, mlp_sample_check.cpp and mlp_gauss_check.cpp, which compile this header with g++ (mgym_math.h's MG_HD is empty there).  Compile with
 // -ffp-contract=off: the only fused operations are the cp_fmaf of the two chains.  The header also holds the one action call of both depths, mlp_actions<D, A,
 // ACT, HEAD, N>(net, o, w, sigma, act): the scores of `net` (this header's MlpPack, or mlp2_policy.h's Mlp2Net) and then the head, MLP_HEAD_GREEDY / _SAMPLE / _GAUSS.
 //
@@ -225,9 +225,9 @@ MG_HD void mlp_actions(const Net& net, const float (&o)[N][D], const uint32_t (&
 }
 
 #if !defined(__HIPCC__)
-// Host builds only (g++, tests/native): the three earlier spellings of that call, told apart by their argument lists.  The host checks call them, and those
-// files underlie some 320 host and GPU tests that have to pass unchanged, so the spellings stay for them and forward to the one call above.  A kernel's
-// translation unit does not see them: under hipcc mlp_actions is the one template.
+// Host builds only (g++): the three earlier spellings of that call, told apart by their argument lists, forwarding to the one call above.  No file of the tree
+// calls them — every host check under tests/native uses the five-argument call; they keep a check program written against the earlier spellings compiling
+// against this header.  A kernel's translation unit does not see them: under hipcc mlp_actions is the one template.
 //   <D, A, ACT, CONT, N>(p, o, act)        GREEDY (CONT said what A == 1 says)
 //   <D, A, ACT, N>(p, o, w, act)            SAMPLE
 //   <D, ACT>(p, o, w, sigma, act)           GAUSS, N = 4

@@ -104,7 +104,7 @@ MG_HD uint32_t pendulum_linear_action(const PdLinearPolicy& p, float cs, float s
 
 // mgym_rollout_mlp / _mlp2: D = 3, A = 1 in mlp_policy.h's mlp_actions — s_0 is the torque (policy.h's policy_actions4)
 #if !defined(__HIPCC__)
-// Host builds only (g++): the forwarding function the kernels once called, for tests/native/pendulum_check.cpp as it stands (mlp_policy.h says why)
+// Host builds only (g++): the forwarding function the kernels once called; no file of the tree calls it (as mlp_policy.h's earlier spellings)
 template <int ACT, int N>
 MG_HD void pendulum_mlp_actions(const MlpPack<3, 1>& p, const float (&o)[N][3], uint32_t (&a)[N]) { mlp_actions<3, 1, ACT, true, N>(p, o, a); }
 #endif

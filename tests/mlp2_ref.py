@@ -1,21 +1,16 @@
 """The two-hidden-layer policy of include/mgym.h (mgym_rollout_mlp2) restated on numpy float32 arrays: three fmaf chains in ascending index order from the
 bias, every link one glibc fmaf (tests/glibc_f32.py), the one hidden activation of both layers (tests/mlp_ref.py's), and the heads of the one-layer entry points
-(mlp_ref.argmax_words, mlp_sample_ref.draw, mlp_gauss_ref.gauss_actions).  Also the build of tests/native/mlp2_check.cpp (modurl_gym_amd/csrc/mlp2_policy.h
-compiled for the host) as a shared object.  Shared by test_mlp2_host.py and test_gpu_mlp2.py.  No test here."""
-import ctypes as C
-import functools
-
+(mlp_ref.argmax_words, mlp_sample_ref.draw, mlp_gauss_ref.gauss_actions).  Shared by test_mlp2_host.py and test_gpu_mlp2.py (the host-compiled header is
+tests/policy_header.py's).  No test here."""
 import numpy as np
 
 import glibc_f32 as G
 import mlp_gauss_ref as GA
 import mlp_ref as M
 import mlp_sample_ref as S
-import native_build
 from mlp_ref import FAMILIES, RELU, TANH_FAST   # noqa: F401  (re-exported)
 from words import words_of
 
-SRC = "mlp2_check.cpp"
 F = np.float32
 GREEDY, SAMPLE, GAUSS = range(3)   # MGYM_HEAD_*
 SHAPES = ((1, 1), (3, 5), (1, 64), (64, 1), (17, 33), (64, 64))
@@ -88,44 +83,6 @@ def head_actions(head, s, sigma=0.0, seed=0, call=0, g=None, t=0):
         return S.draw(s, S.words(seed, call, g, t))[0]
     assert A == 1
     return words_of(GA.gauss_actions(s[0], sigma, seed, call, g, t)).copy()
-
-
-@functools.lru_cache(maxsize=None)
-def check_lib():
-    lib = C.CDLL(native_build.shared(SRC))
-    lib.mlp2_eval.restype = C.c_int
-    lib.mlp2_eval.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mlp2_one_layer_scores.restype = C.c_int
-    lib.mlp2_one_layer_scores.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    return lib
-
-
-def header_actions(head, policy, D, A, H1, H2, obs, activation, sigma=0.0, seed=0, call=0, g0=0, t=0):
-    """the same from the host-compiled header for the ids g0 .. g0 + n - 1 (SAMPLE, GAUSS: g0 a multiple of 4; GAUSS: n too) -> (action words, scores [A, n])"""
-    obs = np.ascontiguousarray(obs, F)
-    pol = np.ascontiguousarray(policy, F)
-    n = obs.shape[1]
-    assert obs.shape[0] == D and pol.size == n_floats(D, A, H1, H2)
-    words = np.zeros(1, np.uint32)
-    if head == SAMPLE:
-        words = np.ascontiguousarray(S.words(seed, call, np.uint64(g0) + np.arange(n, dtype=np.uint64), t), np.uint32)
-    elif head == GAUSS:
-        words = GA.lane_words(seed, call, g0, n, t)
-    out, sc = np.zeros(n, np.uint32), np.zeros((n, A), F)
-    st = check_lib().mlp2_eval(D, A, activation, head, H1, H2, pol.ctypes.data, float(F(sigma)), n, obs.ctypes.data, words.ctypes.data, out.ctypes.data, sc.ctypes.data)
-    assert st == 0, f"mlp2_eval: status {st} (2: the one-per-lane and the four-per-lane forms of the header differ)"
-    return out, np.ascontiguousarray(sc.T)
-
-
-def header_one_layer_scores(policy, D, A, H, obs):
-    """mlp_policy.h's one-hidden-layer ReLU scores [A, n] from the host-compiled header"""
-    obs = np.ascontiguousarray(obs, F)
-    pol = np.ascontiguousarray(policy, F)
-    n = obs.shape[1]
-    assert pol.size == M.n_floats(D, A, H)
-    sc = np.zeros((n, A), F)
-    assert check_lib().mlp2_one_layer_scores(D, A, H, pol.ctypes.data, n, obs.ctypes.data, sc.ctypes.data) == 0
-    return np.ascontiguousarray(sc.T)
 
 
 def identity_middle(one_layer, H):

@@ -88,8 +88,6 @@ def gauss_actions(mu, sigma, seed, call, g, t):
 def check_lib():
     lib = C.CDLL(native_build.shared(SRC))
     lib.mlp_gauss_eval.restype, lib.mlp_gauss_eval.argtypes = None, [C.c_uint64] + [C.c_void_p] * 6
-    lib.mlp_gauss_actions.restype = C.c_int
-    lib.mlp_gauss_actions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -107,17 +105,6 @@ def lane_words(seed, call, g0, n, t):
     assert n % 4 == 0 and g0 % 4 == 0
     g4 = np.uint64(g0) + np.uint64(4) * np.arange(n // 4, dtype=np.uint64)
     return np.ascontiguousarray(np.stack(block_words(seed, call, g4, SLOT_POLICY_GAUSS + int(t))), np.uint32)
-
-
-def header_actions(policy, D, H, act, sigma, obs, seed, call, g0, t):
-    """the lane form of the host-compiled header on an observation [D, n] for the ids g0 .. g0 + n - 1 (g0 and n multiples of 4) -> action words as float32"""
-    obs = np.ascontiguousarray(obs, F)
-    n = obs.shape[1]
-    w = lane_words(seed, call, g0, n, t)
-    pol = np.ascontiguousarray(policy, F)
-    out = np.zeros(n, np.uint32)
-    assert check_lib().mlp_gauss_actions(D, act, H, pol.ctypes.data, float(F(sigma)), n, obs.ctypes.data, w.ctypes.data, out.ctypes.data) == 0
-    return out.view(F)
 
 
 # ---- the cases the host test and the probe test share: every k1, k2 a fixed integer hash of k1, and the hand cases ----

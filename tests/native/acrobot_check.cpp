@@ -93,10 +93,10 @@ static void run(AbRun& p) {
                 const uint32_t w1[1] = {w.w[i - i0]};
                 if (p.policy == POL_UNIFORM) a1[0] = acrobot_uniform_action(bits.w[i - i0], (uint32_t)t);
                 else if (p.policy == POL_LINEAR) a1[0] = acrobot_linear_action(lin, o[0]);
-                else if (samples && tanh_act) mlp_actions<6, 3, MLP_ACT_TANH, 1>(pack, o, w1, a1);
-                else if (samples) mlp_actions<6, 3, MLP_ACT_RELU, 1>(pack, o, w1, a1);
-                else if (mlp && tanh_act) mlp_actions<6, 3, MLP_ACT_TANH, false, 1>(pack, o, a1);
-                else if (mlp) mlp_actions<6, 3, MLP_ACT_RELU, false, 1>(pack, o, a1);
+                else if (samples && tanh_act) mlp_actions<6, 3, MLP_ACT_TANH, MLP_HEAD_SAMPLE, 1>(pack, o, w1, 0.0f, a1);
+                else if (samples) mlp_actions<6, 3, MLP_ACT_RELU, MLP_HEAD_SAMPLE, 1>(pack, o, w1, 0.0f, a1);
+                else if (mlp && tanh_act) mlp_actions<6, 3, MLP_ACT_TANH, MLP_HEAD_GREEDY, 1>(pack, o, w1, 0.0f, a1);
+                else if (mlp) mlp_actions<6, 3, MLP_ACT_RELU, MLP_HEAD_GREEDY, 1>(pack, o, w1, 0.0f, a1);
                 else a1[0] = p.actions_in[(uint64_t)t * n + i];
                 a[i] = a1[0];
             }

@@ -71,6 +71,7 @@ static void run(PdRun& p) {
     if (p.policy == POL_MLP_RELU || p.policy == POL_MLP_TANH) mlp_pack<3, 1>(p.weights, p.hidden, pack);
     if (p.policy == POL_LINEAR) lin = PdLinearPolicy{{p.weights[0], p.weights[1], p.weights[2]}, p.weights[3]};
     p.finished = 0; p.bad = 0;
+    const uint32_t no_word[1] = {0u};   // (the greedy head reads no word)
     for (int t = 0; t < p.steps; ++t) {
         // the action of every env from what it holds before the step (pendulum_rollout_kernel)
         if (p.policy == POL_UNIFORM) {
@@ -84,8 +85,8 @@ static void run(PdRun& p) {
                 const float o[1][3] = {{cs[i], sn[i], td[i]}};
                 uint32_t a1[1];
                 if (p.policy == POL_LINEAR) a1[0] = pendulum_linear_action(lin, cs[i], sn[i], td[i]);
-                else if (p.policy == POL_MLP_RELU) pendulum_mlp_actions<MLP_ACT_RELU, 1>(pack, o, a1);
-                else if (p.policy == POL_MLP_TANH) pendulum_mlp_actions<MLP_ACT_TANH, 1>(pack, o, a1);
+                else if (p.policy == POL_MLP_RELU) mlp_actions<3, 1, MLP_ACT_RELU, MLP_HEAD_GREEDY, 1>(pack, o, no_word, 0.0f, a1);
+                else if (p.policy == POL_MLP_TANH) mlp_actions<3, 1, MLP_ACT_TANH, MLP_HEAD_GREEDY, 1>(pack, o, no_word, 0.0f, a1);
                 else a1[0] = p.actions_in[(uint64_t)t * n + i];
                 a[i] = a1[0];
             }

@@ -6,7 +6,6 @@ test_gpu_tanh_fast_probe.py and test_gpu_mlp_tanh_fast.py.  No test here.
  * policy_actions — the action words of the three entry points from the scores of tests/mlp_ref.py with this activation: the argmax (or the score's bits), the categorical draw of
    tests/mlp_sample_ref.py, the Gaussian draw of tests/mlp_gauss_ref.py.
  * the build of tests/native/tanh_fast_check.cpp — csrc/mgym_math.h compiled for the host — as a shared object: header_tanh_fast, enumerate_all.
- * the build of tests/native/mlp_tanh_fast_check.cpp — csrc/mlp_policy.h with ACT = MLP_ACT_TANH_FAST compiled for the host: header_policy_actions.
 """
 import ctypes as C
 import functools
@@ -22,7 +21,6 @@ from mlp_ref import TANH_FAST, n_floats
 from words import words_of
 
 SRC = "tanh_fast_check.cpp"
-MLP_SRC = "mlp_tanh_fast_check.cpp"
 F = np.float32
 ARGMAX, SAMPLE, GAUSS = range(3)   # the three entry points: mgym_rollout_mlp, _mlp_sample, _mlp_gauss; a continuous family's drawn form is GAUSS, the others' SAMPLE
 CLAMP_END = 0x41200100   # just past the clamp: 10.0f is 0x41200000
@@ -111,27 +109,3 @@ def policy_actions(form, policy, D, A, H, obs, sigma=0.0, seed=0, call=0, g=None
         return S.draw(s, S.words(seed, call, g, t))[0], s
     assert A == 1
     return words_of(G.gauss_actions(s[0], sigma, seed, call, g, t)).copy(), s
-
-
-@functools.lru_cache(maxsize=None)
-def mlp_check_fn():
-    fn = C.CDLL(native_build.shared(MLP_SRC)).mlp_tanh_fast_eval
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return fn
-
-
-def header_policy_actions(form, policy, D, A, H, obs, sigma=0.0, seed=0, call=0, g0=0, t=0):
-    """the same from the host-compiled header for the ids g0 .. g0 + n - 1 (SAMPLE, GAUSS: g0 a multiple of 4; GAUSS: n too) -> (action words, scores [A, n])"""
-    obs = np.ascontiguousarray(obs, F)
-    pol = np.ascontiguousarray(policy, F)
-    n = obs.shape[1]
-    assert obs.shape[0] == D and pol.size == n_floats(D, A, H)
-    words = np.zeros(1, np.uint32)
-    if form == SAMPLE:
-        words = np.ascontiguousarray(S.words(seed, call, np.uint64(g0) + np.arange(n, dtype=np.uint64), t), np.uint32)
-    elif form == GAUSS:
-        words = G.lane_words(seed, call, g0, n, t)
-    out, sc = np.zeros(n, np.uint32), np.zeros((n, A), F)
-    assert mlp_check_fn()(D, A, form, H, pol.ctypes.data, float(F(sigma)), n, obs.ctypes.data, words.ctypes.data, out.ctypes.data, sc.ctypes.data) == 0
-    return out, np.ascontiguousarray(sc.T)

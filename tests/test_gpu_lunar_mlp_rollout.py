@@ -1,5 +1,5 @@
 """mgym_rollout_mlp for LunarLanderV3 through the persistent rollout launch (ll_roll.h, action sources MLP_RELU / MLP_TANH).  The reference for the
-actions is modurl_gym_amd/csrc/mlp_policy.h compiled for the host (mlp_policy_ref.header_actions) on the observation each environment holds before
+actions is modurl_gym_amd/csrc/mlp_policy.h compiled for the host (policy_header.header_actions) on the observation each environment holds before
 the step; the reference for everything else is a second handle stepped with mgym_step.  Whole words, no tolerance, wind on.  Which form ran is read
 from mgym_get_info's rollout_persistent_launches (the words are the same either way).  The handles of these tests set MGYM_LL_ROLLOUT_MLP=1, so both
 activations go through the launch whatever the default is; test_default_form_of_each_activation checks the default (PERSISTENT_BY_DEFAULT)."""
@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
-from mlp_policy_ref import FAMILIES, RELU, TANH, header_actions, header_eval
+from mlp_policy_ref import FAMILIES, RELU, TANH
+from policy_header import GREEDY, check_lib, header_actions
 from mlp_ref import normal_weights, packed
 from words import same
 
@@ -49,7 +50,8 @@ def launches(env):
 
 @pytest.fixture(scope="module")
 def header():
-    return header_eval()
+    check_lib()   # compiled once, before the first GPU call
+    return header_actions
 
 
 class Loop:
@@ -66,7 +68,7 @@ class Loop:
         pol = packed(w)
         acts, gobs, grew, gdone, gtrunc = got
         for t in range(acts.shape[0]):
-            a = header_actions(self.header, D, A, 0, act, H, pol, self.obs)
+            a = self.header(D, A, 1, act, GREEDY, (H,), pol, self.obs)[0]
             assert np.array_equal(acts[t], a), f"{what} step {t}: actions"
             o, r, d, tr = self.env.step(a)
             for g, e, nm in zip((gobs[t], grew[t], gdone[t], gtrunc[t]), (o, r, d, tr), ("obs", "reward", "done", "truncated")):

@@ -1,5 +1,5 @@
 """mgym_rollout_mlp2 (include/mgym.h): the two-hidden-layer policy inside the classic families' rollout kernels and LunarLander's policy kernel.  The reference
-for the actions is modurl_gym_amd/csrc/mlp2_policy.h itself, compiled for the host (tests/native/mlp2_check.cpp; tests/test_mlp2_host.py pins that build to the
+for the actions is modurl_gym_amd/csrc/mlp2_policy.h itself, compiled for the host (tests/native/policy_check.cpp; tests/test_mlp2_host.py pins that build to the
 documented arithmetic), applied to the observation each env holds before the step; the reference for everything else is a second handle stepped with those
 actions.  Every comparison is of whole words: no tolerance anywhere."""
 import numpy as np
@@ -8,6 +8,7 @@ import pytest
 import modurl_gym_amd as mg
 import mlp2_ref as R
 import mlp_ref as M
+import policy_header as P
 from words import bits, same
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +65,7 @@ def call(env, w, k, act, head, c=0):
 
 def header(fam, w, H1, H2, act, head, obs, c, t):
     D, A, _ = R.FAMILIES[fam]
-    return R.header_actions(head, R.packed(w), D, A, H1, H2, obs, act, SIGMA, POLICY_SEED, c, 0, t)[0]
+    return P.header_actions(D, A, 2, act, head, (H1, H2), R.packed(w), obs, SIGMA, POLICY_SEED, c, 0, t)[0]
 
 
 def forward64(w, obs, act):

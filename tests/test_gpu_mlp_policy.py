@@ -1,5 +1,5 @@
 """mgym_rollout_mlp (include/mgym.h): the one-hidden-layer policy inside the CartPole / MountainCar rollout kernels and LunarLander's K-step policy kernel.
-The reference for the actions is modurl_gym_amd/csrc/mlp_policy.h itself, compiled for the host (tests/native/mlp_policy_check.cpp as a shared object;
+The reference for the actions is modurl_gym_amd/csrc/mlp_policy.h itself, compiled for the host (tests/native/policy_check.cpp as a shared object;
 tests/test_mlp_policy_host.py pins that build to the documented arithmetic), applied to the observation each env holds before the step; the reference for
 everything else is a second handle stepped with those actions.  Every comparison is of whole words: no tolerance anywhere."""
 import itertools
@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
-from mlp_policy_ref import FAMILIES, RELU, TANH, header_actions, header_eval
+from mlp_policy_ref import FAMILIES, RELU, TANH
+from policy_header import GREEDY, check_lib, header_actions
 from mlp_ref import normal_weights, packed
 from words import bits, same
 
@@ -45,7 +46,8 @@ def make(fam, n, auto_reset, limit=0, seed=ENV_SEED):
 
 @pytest.fixture(scope="module")
 def header():
-    return header_eval()
+    check_lib()   # compiled once, before the first GPU call
+    return header_actions
 
 
 class Facts:
@@ -98,7 +100,7 @@ def run_case(header, fam, n, H, act, auto_reset, limit=0):
         assert same(env.observation(), obs)   # the first step of a call uses the handle's current observation
         acts, gobs, grew, gdone, gtrunc = env.rollout_mlp(*w, K, activation=ACT_NAME[act])
         for t in range(K):
-            a = header_actions(header, D, A, cont, act, H, pol, obs)
+            a = header(D, A, 1, act, GREEDY, (H,), pol, obs)[0]
             assert np.array_equal(bits(acts[t]), a), f"call {c} step {t}: actions"
             o, r, d, tr = loop.step(a.view(np.float32) if cont else a)
             for g, e, nm in zip((gobs[t], grew[t], gdone[t], gtrunc[t]), (o, r, d, tr), ("obs", "reward", "done", "truncated")):
@@ -179,7 +181,7 @@ def test_mlp_rollouts_interleave_with_the_other_entry_points(header, fam, n):
         w = weights(fam, H, act)
         acts = env.rollout_mlp(*w, k, activation=ACT_NAME[act])[0]
         for t in range(k):   # (the header on the loop's observations, so a wrong action is caught here and not only as a state difference)
-            a = header_actions(header, D, A, cont, act, H, packed(w), obs)
+            a = header(D, A, 1, act, GREEDY, (H,), packed(w), obs)[0]
             assert np.array_equal(acts[t], a), f"H={H} step {t}"
             obs = loop.step(a)[0]
         follow([])

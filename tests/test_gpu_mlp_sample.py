@@ -1,5 +1,5 @@
 """mgym_rollout_mlp_sample (include/mgym.h): softmax-sampled actions inside the CartPole / MountainCar rollout kernels and LunarLander's sampling policy
-kernel, by the scheme of test_gpu_mlp_policy.py.  The reference for the actions is the host-compiled header's scores (tests/native/mlp_policy_check.cpp,
+kernel, by the scheme of test_gpu_mlp_policy.py.  The reference for the actions is the host-compiled header's scores (tests/native/policy_check.cpp,
 pinned to the documented arithmetic by test_mlp_policy_host.py) on the observation each env holds before the step, then the Python restatement of the
 documented draw (tests/mlp_sample_ref.py); the reference for everything else is a second handle stepped with those actions.  Whole words, no tolerance."""
 import numpy as np
@@ -8,7 +8,8 @@ import pytest
 import modurl_gym_amd as mg
 import mlp_sample_ref as R
 from glibc_f32 import glibc_has_fdlibm_expm1f
-from mlp_policy_ref import FAMILIES, RELU, TANH, header_eval, n_floats
+from mlp_policy_ref import FAMILIES, RELU, TANH, n_floats
+from policy_header import GREEDY, check_lib, header_actions
 from mlp_ref import normal_weights, packed
 from words import same
 
@@ -41,18 +42,14 @@ def make(fam, n, auto_reset, limit=0, seed=ENV_SEED, base=0):
 
 @pytest.fixture(scope="module")
 def header():
-    return header_eval()
+    check_lib()   # compiled once, before the first GPU call
+    return header_actions
 
 
-def header_scores(fn, D, A, act, H, policy, obs):
-    """scores [A, n] of the host-compiled header for an SoA observation [D, n]"""
-    obs = np.ascontiguousarray(obs, np.float32)
-    pol = np.ascontiguousarray(policy, np.float32)
-    n = obs.shape[1]
-    acts, sc = np.zeros(n, np.uint32), np.zeros((n, A), np.float32)
-    assert pol.size == n_floats(D, A, H)
-    assert fn(D, A, 0, act, H, pol.ctypes.data, obs.ctypes.data, n, n, acts.ctypes.data, sc.ctypes.data) == 0
-    return np.ascontiguousarray(sc.T), acts
+def header_scores(header, D, A, act, H, policy, obs):
+    """scores [A, n] and argmax actions of the host-compiled header for an SoA observation [D, n]"""
+    acts, sc = header(D, A, 1, act, GREEDY, (H,), policy, obs)
+    return sc, acts
 
 
 def run_case(header, fam, n, H, act, auto_reset, limit=0, base=0, K=24, calls=(0, 1)):

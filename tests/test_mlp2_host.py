@@ -1,5 +1,5 @@
 """No-GPU check of the two-hidden-layer policy header: modurl_gym_amd/csrc/mlp2_policy.h (the lines the rollout kernels and LunarLander's policy kernel compile)
-built for the host by tests/native/mlp2_check.cpp with -ffp-contract=off, against the numpy restatement of include/mgym.h's mgym_rollout_mlp2 text in
+built for the host by tests/native/policy_check.cpp with -ffp-contract=off, against the numpy restatement of include/mgym.h's mgym_rollout_mlp2 text in
 tests/mlp2_ref.py (glibc fmaf) — every score and every action word, bit for bit, no tolerance.  The header is evaluated one environment at a time (LunarLander's
 form) and, by the check itself, four to a lane (the classic kernels' packed pairs); a difference between the two forms fails header_actions."""
 import numpy as np
@@ -7,6 +7,7 @@ import pytest
 
 import mlp2_ref as R
 import mlp_ref as M
+import policy_header as P
 from words import words_of
 
 F = np.float32
@@ -52,7 +53,7 @@ def test_header_scores_equal_the_restatement(fam):
             obs = observations(rng, fam)
             s, pre1, pre2 = R.scores(pol, D, A, H1, H2, obs, act, want_pre=True)
             assert pre1.shape == (H1, obs.shape[1]) and pre2.shape == (H2, obs.shape[1])
-            got_a, got_s = R.header_actions(R.GREEDY, pol, D, A, H1, H2, obs, act)
+            got_a, got_s = P.header_actions(D, A, 2, act, P.GREEDY, (H1, H2), pol, obs)
             assert same_words(got_s, s), f"{fam} ({H1}, {H2}) act {act}: header\n{words_of(got_s)}\nrestatement\n{words_of(s)}"
             exp_a = R.head_actions(R.GREEDY, s)
             assert same_words(got_a.view(F), exp_a.view(F)) if cont else np.array_equal(got_a, exp_a)
@@ -77,14 +78,14 @@ def test_heads_equal_the_one_layer_heads_on_the_scores(fam):
         # under mg_tanhf_fast a NaN observation component reaches every score (no weight is zero); ReLU turns a NaN pre-activation into +0
         nan = np.isnan(obs).any(axis=0) if act == R.TANH_FAST else np.zeros(n, bool)
         assert act != R.TANH_FAST or (nan[-NAN_COLUMNS:].all() and np.isnan(s[:, nan]).all())
-        got, _ = R.header_actions(R.GREEDY, pol, D, A, H1, H2, obs, act)
+        got, _ = P.header_actions(D, A, 2, act, P.GREEDY, (H1, H2), pol, obs)
         exp = R.head_actions(R.GREEDY, s)
         assert same_words(got.view(F), exp.view(F)) if cont else np.array_equal(got, exp)
         if not cont:
             assert (got[nan] == 0).all()                    # nothing compares greater than a NaN s_0
         else:
             assert np.isnan(got.view(F)[nan]).all()
-        got, _ = R.header_actions(head, pol, D, A, H1, H2, obs, act, sigma, seed, call, g0, t)
+        got, _ = P.header_actions(D, A, 2, act, head, (H1, H2), pol, obs, sigma, seed, call, g0, t)
         exp = R.head_actions(head, s, sigma, seed, call, g, t)
         if cont:
             assert same_words(got.view(F), exp.view(F)) and np.isnan(got.view(F)[nan]).all()   # NaN + sigma * z
@@ -104,8 +105,8 @@ def test_identity_middle_layer_gives_the_one_layer_scores(H):
         one = M.normal_weights(rng, D, A, H, in_scale(fam))
         obs = observations(rng, fam)[:, :-NAN_COLUMNS]   # finite h1
         two = R.packed(R.identity_middle(one, H))
-        _, got = R.header_actions(R.GREEDY, two, D, A, H, H, obs, R.RELU)
-        exp = R.header_one_layer_scores(M.packed(one), D, A, H, obs)
+        _, got = P.header_actions(D, A, 2, R.RELU, P.GREEDY, (H, H), two, obs)
+        _, exp = P.header_actions(D, A, 1, R.RELU, P.GREEDY, (H,), M.packed(one), obs)
         assert np.isfinite(exp).all()
         assert np.array_equal(words_of(got), words_of(exp)), (fam, H)
         assert np.array_equal(words_of(got), words_of(M.scores(M.packed(one), D, A, H, obs, M.RELU)))
@@ -119,17 +120,17 @@ def test_signed_zero_reaches_the_action_word(fam, act):
     pol = R.packed(R.signed_zero_policy(D, act))
     obs = observations(np.random.default_rng(5), fam)[:, :8]
     exp = R.head_actions(R.GREEDY, R.scores(pol, D, A, 3, 5, obs, act))
-    got, _ = R.header_actions(R.GREEDY, pol, D, A, 3, 5, obs, act)
+    got, _ = P.header_actions(D, A, 2, act, P.GREEDY, (3, 5), pol, obs)
     assert [f"{v:08x}" for v in exp] == ["80000000"] * 8
     assert [f"{v:08x}" for v in got] == ["80000000"] * 8
 
 
 def test_pack_layout_and_refusals():
     """the check refuses what no family has: a draw on a continuous family, a Gaussian on a discrete one, widths outside 1 .. 64, the exact tanh"""
-    lib = R.check_lib()
+    lib = P.check_lib()
     z = np.zeros(8192, F)
     out = np.zeros(8, np.uint32)
-    call = lambda D, A, act, head, H1, H2: lib.mlp2_eval(D, A, act, head, H1, H2, z.ctypes.data, 0.0, 4, z.ctypes.data, out.ctypes.data, out.ctypes.data, None)
+    call = lambda D, A, act, head, H1, H2: lib.policy_eval(D, A, 2, act, head, H1, H2, z.ctypes.data, 0.0, 4, 4, z.ctypes.data, out.ctypes.data, out.ctypes.data, None)
     assert call(4, 2, R.RELU, R.GREEDY, 64, 64) == 0
     assert call(4, 2, R.RELU, R.GAUSS, 3, 5) == 1 and call(3, 1, R.RELU, R.SAMPLE, 3, 5) == 1
     assert call(4, 2, R.RELU, R.GREEDY, 0, 5) == 1 and call(4, 2, R.RELU, R.GREEDY, 5, 65) == 1

@@ -1,5 +1,5 @@
 """No-GPU checks of the draw of mgym_rollout_mlp_gauss: mg_log_u25, mlp_gauss_pair and the GAUSS form of mlp_actions of modurl_gym_amd/csrc/mlp_policy.h
-(the lines the rollout kernels compile) built for the host by tests/native/mlp_gauss_check.cpp with -ffp-contract=off, against the numpy restatement of
+(the lines the rollout kernels compile) built for the host by tests/native/mlp_gauss_check.cpp and policy_check.cpp with -ffp-contract=off, against the numpy restatement of
 include/mgym.h's text in tests/mlp_gauss_ref.py — z_even, z_odd and q word for word over every k1; the restated logarithm against numpy's log / log1p; and
 the distribution of the specification itself under a constant policy."""
 import numpy as np
@@ -7,6 +7,7 @@ import pytest
 
 import mlp_gauss_ref as R
 import mlp_ref as M
+import policy_header as P
 from oracle import oracle as ora
 from philox_ref import SLOT_POLICY_GAUSS, philox4x32_10
 from words import same_words
@@ -87,7 +88,7 @@ def test_lane_form_equals_the_restatement(D, act):
         obs[0, :4] = [np.nan, np.inf, -0.0, 0.0]
         mu = M.scores(pol, D, 1, H, obs, act)[0]
         for sigma in (0.0, 0.3, 2.5):
-            got = R.header_actions(pol, D, H, act, sigma, obs, 0xC0FFEE1234, 9, g0, 3)
+            got = P.header_actions(D, 1, 1, act, P.GAUSS, (H,), pol, obs, sigma, 0xC0FFEE1234, 9, g0, 3)[0].view(F)
             exp = R.gauss_actions(mu, sigma, 0xC0FFEE1234, 9, g, 3)
             assert same_words(got, exp), (H, sigma)
             if sigma == 0.0:

@@ -1,5 +1,5 @@
 """No-GPU check of the MLP policy header: modurl_gym_amd/csrc/mlp_policy.h (the lines the CartPole / MountainCar rollout kernels and LunarLander's
-policy kernel compile) built for the host by tests/native/mlp_policy_check.cpp with -ffp-contract=off, against the Python restatement of
+policy kernel compile) built for the host by tests/native/policy_check.cpp with -ffp-contract=off, against the Python restatement of
 include/mgym.h's mgym_rollout_mlp text in tests/mlp_ref.py (glibc fmaf / tanhf) — the action word and every score, bit for bit."""
 import itertools
 import subprocess
@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 
 import mlp_ref as M
-from mlp_policy_ref import RELU, TANH, check_program, header_actions, header_eval, mlp_refs, n_floats, split
+from mlp_policy_ref import RELU, TANH, mlp_refs, n_floats, split
+from policy_header import GREEDY, check_program, header_actions
 
-FAMILIES = {fam: M.FAMILIES[fam] for fam in ("cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander")}   # the families of mlp_policy_check.cpp
+FAMILIES = {fam: M.FAMILIES[fam] for fam in ("cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander")}   # the four families of this file's cases (policy_check.cpp knows all six)
 HIDDEN = (1, 2, 7, 32, 64)
 KINDS = (("ordinary", 40), ("ties", 15), ("zeros", 15), ("huge", 15), ("inf", 15))
 
@@ -125,14 +126,13 @@ def test_relu_of_negative_zero_and_nan_is_positive_zero(check_exe):
 
 def test_shared_object_form_equals_the_program(check_exe):
     """the bulk form test_gpu_mlp_policy.py uses is the same header: same actions as the program on one batch per family"""
-    fn = header_eval()
     rng = np.random.default_rng(21)
     for D, A, cont in FAMILIES.values():
         H, n = 7, 33
         pol = rng.normal(0, 1, n_floats(D, A, H)).astype(np.float32)
         obs = rng.normal(0, 1, (D, n)).astype(np.float32)
         for act in (RELU, TANH):
-            bulk = header_actions(fn, D, A, cont, act, H, pol, obs)
+            bulk = header_actions(D, A, 1, act, GREEDY, (H,), pol, obs)[0]
             text = "\n".join(f"{D} {A} {cont} {act} {H} {hexs(pol)} {hexs(obs[:, i])}" for i in range(n)) + "\n"
             out = subprocess.run([check_exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
             assert [int(l.split()[0], 16) for l in out] == [int(v) for v in bulk]

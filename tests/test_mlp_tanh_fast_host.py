@@ -1,10 +1,11 @@
 """No-GPU check of the MLP policy header with MGYM_ACT_TANH_FAST: modurl_gym_amd/csrc/mlp_policy.h compiled for the host with ACT = MLP_ACT_TANH_FAST
-(tests/native/mlp_tanh_fast_check.cpp, g++ -ffp-contract=off) against the restated fmaf chains of include/mgym.h with tests/tanh_fast_ref.py as the hidden
+(tests/native/policy_check.cpp, g++ -ffp-contract=off) against the restated fmaf chains of include/mgym.h with tests/tanh_fast_ref.py as the hidden
 activation — every score and every action word, for the argmax, the categorical draw and the Gaussian draw where the family has them."""
 import numpy as np
 import pytest
 
 import mlp_ref as M
+import policy_header as P
 import tanh_fast_ref as T
 from words import same_words
 
@@ -38,7 +39,7 @@ def test_header_matches_the_restated_chains(fam, form, H):
         pol, obs = make_case(rng, D, A, H)
         seed, call, g0, t, sigma = 0x1234567887654321 + rep, 7 + rep, 4 * (rep + (1 << 31)), 3 + rep, 0.5 * rep
         g = np.uint64(g0) + np.arange(N, dtype=np.uint64)
-        got_a, got_s = T.header_policy_actions(form, pol, D, A, H, obs, sigma, seed, call, g0, t)
+        got_a, got_s = P.header_actions(D, A, 1, M.TANH_FAST, form, (H,), pol, obs, sigma, seed, call, g0, t)
         exp_a, exp_s = T.policy_actions(form, pol, D, A, H, obs, sigma, seed, call, g, t)
         assert same_words(got_s, exp_s), (fam, form, H, rep)
         if A == 1:   # action words are floats: NaNs compare as a class
@@ -55,7 +56,7 @@ def test_discrete_actions_all_occur_and_the_activation_is_not_relu_or_exact_tanh
     D, A, H = 3, 1, 64
     pol = rng.normal(0, 1.0, T.n_floats(D, A, H)).astype(F)
     obs = rng.normal(0, 1.0, (D, 256)).astype(F)
-    _, s = T.header_policy_actions(T.ARGMAX, pol, D, A, H, obs)
+    _, s = P.header_actions(D, A, 1, M.TANH_FAST, P.GREEDY, (H,), pol, obs)
     exact, relu = M.scores(pol, D, 1, H, obs, M.TANH)[0], M.scores(pol, D, 1, H, obs, M.RELU)[0]
     assert np.abs(s[0] - exact).max() < 1e-4 and not np.array_equal(s[0], exact)
     assert np.abs(s[0] - relu).max() > 1e-2
@@ -63,6 +64,6 @@ def test_discrete_actions_all_occur_and_the_activation_is_not_relu_or_exact_tanh
     for fam in ("cartpole", "mountain_car", "acrobot", "lunar_lander"):
         D, A, _ = M.FAMILIES[fam]
         pol = rng.normal(0, 1.5, T.n_floats(D, A, 7)).astype(F)
-        a, _ = T.header_policy_actions(T.ARGMAX, pol, D, A, 7, rng.normal(0, 2.0, (D, 256)).astype(F))
+        a, _ = P.header_actions(D, A, 1, M.TANH_FAST, P.GREEDY, (7,), pol, rng.normal(0, 2.0, (D, 256)).astype(F))
         seen.add((fam, len(set(a.tolist())) == A))
     assert all(ok for _, ok in seen), seen
