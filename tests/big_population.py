@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from families import FAMILIES
+
 P = 4096                 # the period of the action tables and the width of a window
 SENTINEL_BYTE = 0xFF     # outputs are prefilled with 0xFF bytes: the word 0xFFFFFFFF (a NaN no kernel here produces), the flag byte 0xFF (flags are 0 / 1)
 GIB = 1 << 30
@@ -203,7 +205,6 @@ def assert_windows_equal(big_outputs, make_small, wins, what=""):
 
 
 # ---- memory ---------------------------------------------------------------------------------------------------------------------------------
-ENGINE_COLUMNS = {"cartpole": 5, "mountaincar": 3, "mountaincar_cont": 3, "pendulum": 5, "acrobot": 9}   # f32 / u32 columns, n_pad words apart
 LL_BYTES_PER_ENV = 2 * (1152 + 32) + 4 + 16 * 4 + 1   # records and observation (and their reset shadows), next action, 16 work lists, class byte
 LL_BYTES_PER_HANDLE = 563 << 20   # whatever the population: the far-constraint slices of the contact kernels' bounded grids (measured: 0.52 GiB a handle)
 
@@ -211,9 +212,9 @@ LL_BYTES_PER_HANDLE = 563 << 20   # whatever the population: the far-constraint 
 def engine_bytes(family, n):
     """what mgym_create allocates per handle of n environments, to the leading term"""
     n_pad = (max(n, 1) + 1023) // 1024 * 1024
-    if family == "lunarlander":
+    if family == "lunar_lander":
         return LL_BYTES_PER_ENV * n_pad + LL_BYTES_PER_HANDLE
-    return ENGINE_COLUMNS[family] * 4 * n_pad + (0 if family == "cartpole" else 2 * n_pad)   # + the u16 elapsed column
+    return FAMILIES[family].engine_cols * 4 * n_pad + (0 if family == "cartpole" else 2 * n_pad)   # + the u16 elapsed column
 
 
 def need_bytes(handles=(), buffers=()):

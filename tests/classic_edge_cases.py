@@ -366,7 +366,7 @@ NON_FINITE = (INF, -INF, NAN)
 
 @functools.lru_cache(None)
 def non_finite_cases(kind):
-    """kind in ("pendulum", "acrobot", "mountain_car_cont") -> (blob, actions): +-inf and NaN in each f32 column in turn, over a small product of
+    """kind in ("pendulum", "acrobot", "mountain_car_continuous") -> (blob, actions): +-inf and NaN in each f32 column in turn, over a small product of
     ordinary values in the other columns and the family's actions"""
     if kind == "pendulum":
         base, acts, rest = [F([0, 1e-40, 3.0, -200.0]), F([0, -1.0, 8.0])], F([0, -2.5, 1e-40, np.inf]), (F(0), F(0), F(0))

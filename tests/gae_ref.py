@@ -170,38 +170,3 @@ def poisoned_final_value(rng, d, u, lo=-100.0, hi=100.0):
     sel = u & ~d
     fv[sel] = rng.uniform(lo, hi, int(sel.sum())).astype(F)
     return fv
-
-
-# ---- device buffers of the GPU tests ----------------------------------------------------------------------------------------------------
-class Guarded:
-    """`words` 32-bit words of device memory between two guards of four words each, everything filled with NAN_WORD; mis = 1: 4 bytes off a 16-byte boundary"""
-
-    def __init__(self, words, mis=0, host=None):
-        import modurl_gym_amd as mg
-        self.words, self.off = int(words), 4 + mis   # (the allocation is 256-byte aligned)
-        self.dev = mg.DeviceArray(self.words + 8 + mis, np.uint32)
-        self.ptr = self.dev.ptr + 4 * self.off
-        self.fill(host)
-
-    def fill(self, host=None):
-        """NAN_WORD everywhere, then `host` (float32 or uint32, any shape of `words` elements) in the payload"""
-        a = np.full(self.words + 8 + self.off - 4, NAN_WORD, np.uint32)
-        if host is not None:
-            h = np.ascontiguousarray(host)
-            assert h.size == self.words and h.dtype.itemsize == 4
-            a[self.off: self.off + self.words] = h.reshape(-1).view(np.uint32)
-        self.dev.copy_from(a)
-        self.initial = a
-
-    def data_ptr(self):
-        return self.ptr
-
-    def payload(self, shape, dtype=np.uint32):
-        return self.dev.numpy()[self.off: self.off + self.words].view(dtype).reshape(shape)
-
-    def guards_hold(self):
-        a = self.dev.numpy()
-        return bool((a[: self.off] == NAN_WORD).all() and (a[self.off + self.words:] == NAN_WORD).all())
-
-    def untouched(self):
-        return bool(np.array_equal(self.dev.numpy(), self.initial))

@@ -82,6 +82,6 @@ class VecAdapter:
         self.v.set_state(s)
 
     def step(self, action):
-        dt = np.float32 if self.kind == "mountain_car_cont" else np.uint32
+        dt = np.float32 if self.kind == "mountain_car_continuous" else np.uint32
         obs, rew, done, trunc = self.v.step(np.array([action], dt))
         return obs[:, 0].tolist(), float(rew[0]), bool(done[0]), bool(trunc[0])

@@ -4,13 +4,13 @@ layout and the families' dimensions.  The draws built on the scores stay with th
 tanh_fast_ref.tanh_fast.  No test here."""
 import numpy as np
 
+import families
 import glibc_f32 as G
 
 F = np.float32
 RELU, TANH, TANH_FAST = 0, 1, 3   # MGYM_ACT_RELU, MGYM_ACT_TANH, MGYM_ACT_TANH_FAST
-# (D, A, continuous): a continuous family has A = 1 and its score is the action
-FAMILIES = {"cartpole": (4, 2, 0), "mountain_car": (2, 3, 0), "mountain_car_continuous": (2, 1, 1), "pendulum": (3, 1, 1), "acrobot": (6, 3, 0),
-            "lunar_lander": (8, 4, 0)}
+# (D, A, continuous) of tests/families.py: a continuous family has A = 1 and its score is the action
+FAMILIES = {name: (f.D, f.A, int(f.box is not None)) for name, f in families.FAMILIES.items()}
 
 
 def n_floats(D, A, H):

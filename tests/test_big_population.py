@@ -113,8 +113,8 @@ def test_assert_windows_equal_accepts_the_clean_and_catches_each_planted_defect(
 def shapes():
     import test_gpu_addressing_bounds as T
     for fam, n in T.STEP_CASES:
-        yield fam, n, (n + 1023) // 1024 * 1024, bp.ENGINE_COLUMNS[fam], 0
-    yield "lunarlander", T.LL_N, T.LL_N, 1, T.LL_RECORD_BYTES
+        yield fam, n, (n + 1023) // 1024 * 1024, bp.FAMILIES[fam].engine_cols, 0
+    yield "lunar_lander", T.LL_N, T.LL_N, 1, T.LL_RECORD_BYTES
 
 
 def test_windows_hold_every_required_window():

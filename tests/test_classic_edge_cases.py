@@ -12,9 +12,9 @@ from oracle import oracle as ora
 
 F = np.float32
 BUILDERS = {"pendulum": (E.pendulum_cases, 3, F), "acrobot": (E.acrobot_cases, 5, np.uint32), "mountain_car": (lambda: E.mountain_car_cases(False), 3, np.uint32),
-            "mountain_car_cont": (lambda: E.mountain_car_cases(True), 3, F), "cartpole": (E.cartpole_cases, 7, np.uint32),
+            "mountain_car_continuous": (lambda: E.mountain_car_cases(True), 3, F), "cartpole": (E.cartpole_cases, 7, np.uint32),
             "pendulum-non_finite": (lambda: E.non_finite_cases("pendulum"), 3, F), "acrobot-non_finite": (lambda: E.non_finite_cases("acrobot"), 5, np.uint32),
-            "mountain_car_cont-non_finite": (lambda: E.non_finite_cases("mountain_car_cont"), 3, F)}
+            "mountain_car_continuous-non_finite": (lambda: E.non_finite_cases("mountain_car_continuous"), 3, F)}
 
 
 @pytest.mark.parametrize("name", list(BUILDERS))
@@ -51,7 +51,7 @@ def test_case_lists_hold_what_the_issue_names():
 def test_oracle_evaluates_its_families_cases():
     for kind, (blob, a), cfgs in ((ora.MOUNTAINCAR, E.mountain_car_cases(False), [dict(goal_velocity=g) for g in E.MC_GOAL_VELOCITIES]),
                                   (ora.MOUNTAINCAR_CONT, E.mountain_car_cases(True), [dict(goal_velocity=g) for g in E.MC_GOAL_VELOCITIES]),
-                                  (ora.MOUNTAINCAR_CONT, E.non_finite_cases("mountain_car_cont"), [{}]),
+                                  (ora.MOUNTAINCAR_CONT, E.non_finite_cases("mountain_car_continuous"), [{}]),
                                   (ora.CARTPOLE, E.cartpole_cases(), [dict(sutton_barto_reward=sb, is_euler=eu) for sb, eu in E.CP_CONFIGS])):
         for cfg in cfgs:
             obs, rew, done, trunc = E.oracle_step(kind, blob, a, **cfg)

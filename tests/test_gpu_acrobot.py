@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import acrobot_ref as R
+from device_buffers import CallBuffers, FinalBuf, twin_steps
 from glibc_f32 import glibc_has_fdlibm_expm1f
 from words import bits, same
 import modurl_gym_amd as mg
@@ -73,32 +74,6 @@ def reference(n, limit, auto):
     return _refs[key]
 
 
-class Buffers:
-    """device buffers of one call of K steps; the reward buffer optionally `offset` bytes off its 16-byte alignment"""
-
-    def __init__(self, n, K=1, offset=0, with_obs=True):
-        self.n, self.K, self.offset = n, K, offset
-        self.act, self.obs = mg.DeviceArray((K, n), np.uint32), (mg.DeviceArray((K, 6, n), F) if with_obs else None)
-        self.rew = mg.DeviceArray(K * n + 4, F)
-        self.done, self.trunc = mg.DeviceArray((K, n), np.uint8), mg.DeviceArray((K, n), np.uint8)
-
-    def outs(self):
-        return self.obs, self.rew.ptr + self.offset, self.done, self.trunc
-
-    def read(self):
-        K, n = self.K, self.n
-        rew = self.rew.numpy().view(np.uint8)[self.offset: self.offset + 4 * K * n].view(F).copy().reshape(K, n)
-        obs = self.obs.numpy().reshape(K, 6, n) if self.obs is not None else None   # (obs_out NULL: the caller reads the engine's columns)
-        return obs, rew, self.done.numpy().reshape(K, n), self.trunc.numpy().reshape(K, n)
-
-    def step(self, env, a):
-        self.act.copy_from(np.ascontiguousarray(a, np.uint32).reshape(1, self.n))
-        env.step_device(self.act, *self.outs())
-        env.sync()
-        o, r, d, t = self.read()
-        return (o[0] if o is not None else env.observation()), r[0], d[0], t[0]
-
-
 def test_spec_created_state_and_single_env():
     s = mg.get_spec(mg.ACROBOT)
     assert (s.obs_dim, s.n_actions, s.action_is_float, s.state_cols) == (6, 3, 0, 5)
@@ -134,7 +109,7 @@ def test_reset_observation_masked_reset_and_sharding():
 def test_step_forms_equal_the_reference(form, limit, auto, monkeypatch):
     env, n, offset, with_obs = form_env(form, limit, auto, monkeypatch)
     exp = reference(n, limit, auto)
-    buf = Buffers(n, 1, offset, with_obs)
+    buf = CallBuffers(n, 6, np.uint32, 1, offset, with_obs)
     acts = table_actions(n, STEPS + 2)
     assert same(env.reset(), exp["obs0"])
     for t in range(2):
@@ -160,9 +135,10 @@ def test_table_rollout_equals_the_reference(form, limit, auto, K, monkeypatch):
     env, n, offset, with_obs = form_env(form, limit, auto, monkeypatch)
     exp = reference(n, limit, auto)
     env.set_state(near_swing_up(n).view(F))
-    buf = Buffers(n, K, offset, with_obs)
-    buf.act.copy_from(table_actions(n, STEPS + 2)[2:2 + K])
-    env.rollout_device(buf.act, K, *buf.outs())
+    buf = CallBuffers(n, 6, np.uint32, K, offset, with_obs)
+    buf.put_actions(table_actions(n, STEPS + 2)[2:2 + K])
+    act, *outs = buf.pointers()
+    env.rollout_device(act, K, *outs)
     env.sync()
     got = buf.read()
     for t in range(K):
@@ -294,9 +270,9 @@ def test_action_3_is_a_sticky_error_and_leaves_the_environment(form, monkeypatch
     bad = np.zeros(n, bool)
     bad[[0, 513, n - 1]] = True
     a[bad] = (3, 0xFFFFFFFF, 1 << 31)
-    buf = Buffers(n, 1, 0, with_obs)
-    buf.act.copy_from(a.reshape(1, n))
-    env.step_device(buf.act, *buf.outs())
+    buf = CallBuffers(n, 6, np.uint32, with_obs=with_obs)
+    buf.put_actions(a)
+    env.step_device(*buf.pointers())
     with pytest.raises(mg.InvalidActionError):
         env.sync()
     after = env.get_state()
@@ -308,23 +284,12 @@ def test_action_3_is_a_sticky_error_and_leaves_the_environment(form, monkeypatch
 
 
 def twin_finals(n, limit, actions):
-    """K single steps of an auto-reset handle, its state and count copied into a twin without auto-reset before each: -> (the twin's obs [K, 6, n] — what
-    each step produced before any reset — and its done | truncated [K, n])"""
+    """device_buffers.twin_steps from the seeded states: -> (the twin's obs [K, 6, n] — what each step produced before any reset — and its
+    done | truncated [K, n])"""
     stepper, twin = make(n, limit, True), make(n, limit, False)
     stepper.set_state(near_swing_up(n).view(F))
-    tobs, tfin = [], []
-    for a in actions:
-        twin.set_state(stepper.get_state())
-        if limit:
-            twin.set_elapsed_steps(stepper.elapsed_steps())
-        _, _, sd, st = stepper.step(a)
-        o, _, d, t = twin.step(a)
-        assert same(sd, d) and same(st, t)
-        tobs.append(o.copy()), tfin.append((d | t).astype(bool))
-    return np.array(tobs), np.array(tfin)
-
-
-FILL = np.uint32(0x7FC12345)
+    _, tobs, tdone, ttrunc = twin_steps(stepper, twin, actions)
+    return tobs, tdone | ttrunc
 
 
 @pytest.mark.parametrize("limit", [LIMIT, 0])
@@ -339,18 +304,17 @@ def test_final_observations_equal_a_twin_without_auto_reset(src, limit, monkeypa
     K = 9
     env.set_state(near_swing_up(n).view(F))
     cap = 1 if src.startswith("step") else K
-    fill = np.full((cap, 6, n), FILL, np.uint32)
-    fin = mg.DeviceArray.from_numpy(fill)
-    env.set_final_obs_out_device(fin, cap)
+    fb = FinalBuf(cap, 6, n)
+    env.set_final_obs_out_device(fb.ptr, cap)
     w = mlp_weights(33)
     used = table_actions(n, K)
-    if src.startswith("step"):   # nine mgym_step calls, the one slab read and refilled after each
-        got, buf = [], Buffers(n, 1, 0, with_obs)
-        for a in used:
+    if src.startswith("step"):   # nine mgym_step calls, the one slab checked and refilled after each
+        tobs, tfin = twin_finals(n, limit, list(used))
+        buf = CallBuffers(n, 6, np.uint32, with_obs=with_obs)
+        for t, a in enumerate(used):
             buf.step(env, a)
-            got.append(fin.numpy().reshape(6, n).copy())
-            fin.copy_from(fill)
-        got = np.array(got)
+            fb.check(tobs[t: t + 1], tfin[t: t + 1], f"{src} step {t}")
+            fb.fill()
     else:
         if src.startswith("table"):
             env.rollout(used)
@@ -358,13 +322,10 @@ def test_final_observations_equal_a_twin_without_auto_reset(src, limit, monkeypa
             call = {"uniform": lambda: env.rollout_uniform(PSEED, K), "linear": lambda: env.rollout_linear(SWING, K), "mlp": lambda: env.rollout_mlp(*w, K),
                     "sample": lambda: env.rollout_mlp_sample(*w, K, seed=PSEED, call=3)}[src]
             used = call()[0]
-        got = fin.numpy().reshape(K, 6, n)
+        tobs, tfin = twin_finals(n, limit, list(used))
+        fb.check(tobs, tfin, src)
     env.set_final_obs_out_device(None)
-    tobs, tfin = twin_finals(n, limit, list(used))
-    mask = np.broadcast_to(tfin[:, None, :], got.shape)
     assert tfin[:2].sum() >= 8 and (limit == 0 or tfin[6:].sum() >= 8), "the case has endings of both kinds"
-    assert np.array_equal(got[mask], bits(tobs)[mask]), f"{src}: final words differ from the twin's"
-    assert np.all(got[~mask] == FILL), f"{src}: words outside the finished env-steps were written"
 
 
 def test_final_observations_cover_done_and_truncated_endings():
@@ -381,17 +342,17 @@ def test_captured_step_and_rollout_replay_like_eager_calls():
     for e in (env, eager):
         e.set_state(near_swing_up(n).view(F))
     a = table_actions(n, K)
-    buf = Buffers(n)
-    buf.act.copy_from(a[:1])
-    graph = env.graph_capture(lambda: env.step_device(buf.act, *buf.outs()))
+    buf = CallBuffers(n, 6, np.uint32)
+    buf.put_actions(a[:1])
+    graph = env.graph_capture(lambda: env.step_device(*buf.pointers()))
     for t in range(3):
         env.graph_launch(graph)
         env.sync()
         assert all(same(g[0], e) for g, e in zip(buf.read(), eager.step(a[0]))), f"step replay {t}"
     env.graph_destroy(graph)
-    rb = Buffers(n, K)
-    rb.act.copy_from(a)
-    graph = env.graph_capture(lambda: env.rollout_device(rb.act, K, *rb.outs()))
+    rb = CallBuffers(n, 6, np.uint32, K)
+    rb.put_actions(a)
+    graph = env.graph_capture(lambda: env.rollout_device(rb.pointers()[0], K, *rb.pointers()[1:]))
     for t in range(2):
         env.graph_launch(graph)
         env.sync()

@@ -16,6 +16,7 @@ import torch
 import big_population as bp
 import modurl_gym_amd as mg
 from big_population import GIB, P
+from families import FAMILIES
 
 pytestmark = pytest.mark.gpu
 
@@ -24,21 +25,17 @@ SEED = 20260
 DEV = "cuda"
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 
-# kind, the largest population of the 16-byte step form, actions, engine columns (f32 / u32, n_pad words apart), the floats of a linear policy
-FAMILIES = {
-    "cartpole": dict(kind=mg.CARTPOLE, bound=1 << 27, n_actions=2, box=None, limit=0, lin=5),
-    "mountaincar": dict(kind=mg.MOUNTAINCAR, bound=1 << 27, n_actions=3, box=None, limit=3, lin=9),
-    "mountaincar_cont": dict(kind=mg.MOUNTAINCAR_CONT, bound=1 << 27, n_actions=None, box=(-1.5, 1.5), limit=3, lin=3),
-    "pendulum": dict(kind=mg.PENDULUM, bound=1 << 27, n_actions=None, box=(-2.5, 2.5), limit=3, lin=4),
-    "acrobot": dict(kind=mg.ACROBOT, bound=1 << 26, n_actions=3, box=None, limit=3, lin=21),
-}
-OBS_DIM = {"cartpole": 4, "mountaincar": 2, "mountaincar_cont": 2, "pendulum": 3, "acrobot": 6, "lunarlander": 8}
-STEP_CASES = [("cartpole", 1 << 27)] + [(f, FAMILIES[f]["bound"] + d) for f in ("mountaincar", "mountaincar_cont", "pendulum", "acrobot") for d in (0, 4)]
+# this file's own per family: the largest population of the 16-byte step form, the range of a table's box actions (beyond the bounds: the step clamps)
+# and the time limit; what the family is comes from tests/families.py
+BOUND = {"cartpole": 1 << 27, "mountain_car": 1 << 27, "mountain_car_continuous": 1 << 27, "pendulum": 1 << 27, "acrobot": 1 << 26}
+TABLE_BOX = {"mountain_car_continuous": (-1.5, 1.5), "pendulum": (-2.5, 2.5)}
+LIMIT = {"cartpole": 0, "mountain_car": 3, "mountain_car_continuous": 3, "pendulum": 3, "acrobot": 3}
+STEP_CASES = [("cartpole", 1 << 27)] + [(f, BOUND[f] + d) for f in ("mountain_car", "mountain_car_continuous", "pendulum", "acrobot") for d in (0, 4)]
 WHOLE_STEPS, WINDOW_STEPS, CARTPOLE_WINDOW_STEPS = 6, 7, 12
 N_WINDOWS = 3 + bp.N_SEEDED + 1   # at most: first, last, middle, one column crossing, the seeded ones
 
 CP_BOUND_CASES = [(1 << 20, 1023), (1 << 27, 7), (1 << 20, 1024), (1 << 27, 8)]   # K n = 2^30 - n twice (fused), then 2^30 exactly (K plain steps)
-ROLL_CASES = [("mountaincar", 1 << 27, 9), ("mountaincar_cont", 1 << 27, 9), ("pendulum", 1 << 27, 9), ("acrobot", 1 << 26, 17)]
+ROLL_CASES = [("mountain_car", 1 << 27, 9), ("mountain_car_continuous", 1 << 27, 9), ("pendulum", 1 << 27, 9), ("acrobot", 1 << 26, 17)]
 FINAL_N, FINAL_K = 1 << 20, 300
 GAE_N, GAE_K = 1 << 22, 257
 EP_SPLIT = (200, 57)
@@ -50,14 +47,14 @@ LL_RECORD_BYTES = 1152
 def step_outputs(fam, n, lead=()):
     """(itemsize, dims..) of obs, reward, done, truncated"""
     k = tuple(lead)
-    return [(4,) + k + (OBS_DIM[fam], n), (4,) + k + (n,), (1,) + k + (n,), (1,) + k + (n,)]
+    return [(4,) + k + (FAMILIES[fam].D, n), (4,) + k + (n,), (1,) + k + (n,), (1,) + k + (n,)]
 
 
 def footprint(key):
     """handles and buffers alive at the peak of the test `key` -> bytes (big_population.need_bytes)"""
     what, fam, n, K = key
     small = [(fam, P)]
-    d = OBS_DIM[fam]
+    d = FAMILIES[fam].D
     if what == "whole":      # the action table, the outputs, elapsed; the reset's obs_out and the row-major observation; the handle, the 4096-env twins
         return bp.need_bytes([(fam, n)] + small * (1 + N_WINDOWS), [(4, K, n)] + step_outputs(fam, n) + [(4, n), (1, n), (4, d, n), (4, n, d)])
     if what == "windows":    # the action table, the outputs, elapsed, the flags' OR
@@ -84,15 +81,15 @@ def footprint(key):
 # declared peak device footprints in GiB (each test's docstring repeats its own); test_big_population.py recomputes them from the shapes
 FOOTPRINT = {
     ("whole", "cartpole", 1 << 27, WHOLE_STEPS): 14.9, ("windows", "cartpole", 1 << 27, CARTPOLE_WINDOW_STEPS): 13.9,
-    **{("whole", f, (1 << 27) + d, WHOLE_STEPS): 11.2 for f in ("mountaincar", "mountaincar_cont") for d in (0, 4)},
-    **{("windows", f, (1 << 27) + d, WINDOW_STEPS): 9.7 for f in ("mountaincar", "mountaincar_cont") for d in (0, 4)},
+    **{("whole", f, (1 << 27) + d, WHOLE_STEPS): 11.2 for f in ("mountain_car", "mountain_car_continuous") for d in (0, 4)},
+    **{("windows", f, (1 << 27) + d, WINDOW_STEPS): 9.7 for f in ("mountain_car", "mountain_car_continuous") for d in (0, 4)},
     **{("whole", "pendulum", (1 << 27) + d, WHOLE_STEPS): 13.7 for d in (0, 4)}, **{("windows", "pendulum", (1 << 27) + d, WINDOW_STEPS): 11.2 for d in (0, 4)},
     **{("whole", "acrobot", (1 << 26) + d, WHOLE_STEPS): 11.1 for d in (0, 4)}, **{("windows", "acrobot", (1 << 26) + d, WINDOW_STEPS): 8.4 for d in (0, 4)},
     ("cp_bound", "cartpole", 1 << 20, 1023): 30.8, ("cp_bound", "cartpole", 1 << 27, 7): 33.5,
     ("cp_bound", "cartpole", 1 << 20, 1024): 30.8, ("cp_bound", "cartpole", 1 << 27, 8): 36.8,
     ("cp_uniform", "cartpole", 1 << 20, 1023): 18.1, ("cp_final", "cartpole", FINAL_N, FINAL_K): 15.8,
-    ("roll", "mountaincar", 1 << 27, 9): 25.3, ("roll", "mountaincar_cont", 1 << 27, 9): 25.3, ("roll", "pendulum", 1 << 27, 9): 27.3, ("roll", "acrobot", 1 << 26, 17): 24.7,
-    ("gae", "cartpole", GAE_N, GAE_K): 24.2, ("ep", "cartpole", GAE_N, GAE_K): 16.2, ("ll", "lunarlander", LL_N, LL_STEPS): 18.4,
+    ("roll", "mountain_car", 1 << 27, 9): 25.3, ("roll", "mountain_car_continuous", 1 << 27, 9): 25.3, ("roll", "pendulum", 1 << 27, 9): 27.3, ("roll", "acrobot", 1 << 26, 17): 24.7,
+    ("gae", "cartpole", GAE_N, GAE_K): 24.2, ("ep", "cartpole", GAE_N, GAE_K): 16.2, ("ll", "lunar_lander", LL_N, LL_STEPS): 18.4,
 }
 
 
@@ -129,10 +126,9 @@ def call(env, fn, *args):
 
 
 def make(fam, n, **kw):
-    if fam == "lunarlander":
+    if fam == "lunar_lander":
         return mg.VecEnv(mg.LUNARLANDER, n, seed=SEED, enable_wind=True, **kw)
-    f = FAMILIES[fam]
-    return mg.VecEnv(f["kind"], n, seed=SEED, max_episode_steps=f["limit"], **kw)
+    return mg.VecEnv(FAMILIES[fam].kind, n, seed=SEED, max_episode_steps=LIMIT[fam], **kw)
 
 
 def reset_deterministic(env):
@@ -141,8 +137,7 @@ def reset_deterministic(env):
 
 
 def table(fam, K, n, seed):
-    f = FAMILIES[fam]
-    return bp.periodic_actions(K, n, P, n_actions=f["n_actions"], box=f["box"], seed=seed, device=DEV)
+    return bp.periodic_actions(K, n, P, n_actions=FAMILIES[fam].n_actions or None, box=TABLE_BOX.get(fam), seed=seed, device=DEV)
 
 
 class _Span:
@@ -153,7 +148,7 @@ class _Span:
 
 def engine_columns(env, fam):
     """zero-copy int32 [columns][n] over the engine's own columns (mgym_observation: the observation's come first, the rest lie behind them)"""
-    cols = 8 if fam == "lunarlander" else bp.ENGINE_COLUMNS[fam]
+    cols = FAMILIES[fam].engine_cols or FAMILIES[fam].D   # (LunarLander: its observation)
     ptr, stride = env.observation_device()
     return torch.as_tensor(_Span(ptr, (cols, env.n), (4 * stride, 4), env), device=torch.device(DEV, 0))
 
@@ -163,7 +158,7 @@ class Outputs:
 
     def __init__(self, fam, n, lead=(), obs=True, mis_rew=False):
         lead = tuple(lead)
-        self.obs = bp.sentinel(lead + (OBS_DIM[fam], n), F32, DEV) if obs else None
+        self.obs = bp.sentinel(lead + (FAMILIES[fam].D, n), F32, DEV) if obs else None
         count = int(np.prod(lead + (n,), dtype=np.int64))
         self._rew = bp.sentinel((count + 4,), F32, DEV)
         self.rew = self._rew[1: count + 1].view(lead + (n,)) if mis_rew else self._rew[:count].view(lead + (n,))
@@ -200,7 +195,6 @@ def finished(o):
 
 # ---- 2. the step kernels at both sides of their bound ----------------------------------------------------------------------------------------
 def whole_population(fam, n, mark, mis_rew=False, with_reset=True):
-    F = FAMILIES[fam]
     env, small = make(fam, n), make(fam, P)
     twins = []
     try:
@@ -228,11 +222,11 @@ def whole_population(fam, n, mark, mis_rew=False, with_reset=True):
             return
         # masked reset under a periodic mask: the draws are keyed by the global id, so the reference is the windows' handles, driven the same way
         mask = bp.periodic_bytes(1, n, 0.3, P, seed=2, device=DEV, lead=False)
-        robs, aos = bp.sentinel((OBS_DIM[fam], n), F32, DEV), bp.sentinel((n, OBS_DIM[fam]), F32, DEV)
+        robs, aos = bp.sentinel((FAMILIES[fam].D, n), F32, DEV), bp.sentinel((n, FAMILIES[fam].D), F32, DEV)
         mark()
         call(env, env.reset_device, mask, robs)
         call(env, lambda: mg.envs._check(env._lib.mgym_observation_aos(env._h, aos.data_ptr())))
-        wins = bp.windows(n, SEED, (n + 1023) // 1024 * 1024, bp.ENGINE_COLUMNS[fam])
+        wins = bp.windows(n, SEED, (n + 1023) // 1024 * 1024, FAMILIES[fam].engine_cols)
 
         def make_small(k, a, b):
             w = make(fam, b - a, env_id_base=a)
@@ -241,7 +235,7 @@ def whole_population(fam, n, mark, mis_rew=False, with_reset=True):
             wo = Outputs(fam, b - a)
             for t in range(WHOLE_STEPS):
                 call(w, w.step_device, acts[t, a:b].contiguous(), *wo.args())
-            wr, wa = bp.sentinel((OBS_DIM[fam], b - a), F32, DEV), bp.sentinel((b - a, OBS_DIM[fam]), F32, DEV)
+            wr, wa = bp.sentinel((FAMILIES[fam].D, b - a), F32, DEV), bp.sentinel((b - a, FAMILIES[fam].D), F32, DEV)
             call(w, w.reset_device, mask[a:b].contiguous(), wr)
             call(w, lambda: mg.envs._check(w._lib.mgym_observation_aos(w._h, wa.data_ptr())))
             return dict(reset_obs=wr, aos=wa.t(), columns=engine_columns(w, fam))
@@ -278,7 +272,7 @@ def test_windows_equal_small_handles_through_resets(fam, n, report):
     reserve(("windows", fam, n, steps))
     base = (1 << 32) - n // 2
     env = make(fam, n, auto_reset=True, env_id_base=base)
-    wins = bp.windows(n, SEED, (n + 1023) // 1024 * 1024, bp.ENGINE_COLUMNS[fam])
+    wins = bp.windows(n, SEED, (n + 1023) // 1024 * 1024, FAMILIES[fam].engine_cols)
     assert len(wins) <= N_WINDOWS
     twins = [make(fam, b - a, auto_reset=True, env_id_base=base + a) for a, b in wins]
     try:
@@ -476,7 +470,7 @@ def test_rollouts_with_buffers_beyond_4gib(fam, n, K, report):
 
         same_state("after mgym_rollout")
         assert A.episode_count() == finished(oa) >= 2 * n   # the limit of 3 ends every episode at least twice in 9 steps
-        pol = np.random.default_rng(12).normal(0, 1, FAMILIES[fam]["lin"]).astype(np.float32)
+        pol = np.random.default_rng(12).normal(0, 1, FAMILIES[fam].lin).astype(np.float32)
         oa.refill(), ob.refill(), bp.fill_sentinel(acts)
         call(A, A.rollout_linear_device, pol, K, acts, *oa.args())
         assert not bp.has_sentinel(acts)
@@ -577,18 +571,18 @@ def test_lunar_lander_records_beyond_4gib(report):
     auto-reset: 72 mgym_step calls under a periodic table; every 8 steps and at the end every output, the engine's observation and the elapsed counts
     equal, in every window, a 4096-environment handle at the same global ids.  Peak footprint: 18.4 GiB (twelve handles: half a GiB each whatever the population)."""
     n = LL_N
-    reserve(("ll", "lunarlander", n, LL_STEPS))
-    env = make("lunarlander", n, auto_reset=True)
+    reserve(("ll", "lunar_lander", n, LL_STEPS))
+    env = make("lunar_lander", n, auto_reset=True)
     wins = bp.windows(n, SEED, n, 1, record_bytes=LL_RECORD_BYTES)
     assert len(wins) <= N_WINDOWS + 1 and any(a * LL_RECORD_BYTES < 1 << 32 <= b * LL_RECORD_BYTES for a, b in wins)
-    twins = [make("lunarlander", b - a, auto_reset=True, env_id_base=a) for a, b in wins]
+    twins = [make("lunar_lander", b - a, auto_reset=True, env_id_base=a) for a, b in wins]
     try:
         assert env.info()["rollout"] == "k_steps"
         for e in [env] + twins:
             call(e, e.reset_device, None, None)
         acts = bp.periodic_actions(LL_STEPS, n, P, n_actions=4, seed=13, device=DEV)
-        out, el = Outputs("lunarlander", n), bp.sentinel((n,), I32, DEV)
-        wout = [(Outputs("lunarlander", b - a), bp.sentinel((b - a,), I32, DEV)) for a, b in wins]
+        out, el = Outputs("lunar_lander", n), bp.sentinel((n,), I32, DEV)
+        wout = [(Outputs("lunar_lander", b - a), bp.sentinel((b - a,), I32, DEV)) for a, b in wins]
         total = 0
         report()
         for t in range(LL_STEPS):
@@ -600,13 +594,13 @@ def test_lunar_lander_records_beyond_4gib(report):
                 call(twins[k], twins[k].step_device, acts[t, a:b].contiguous(), *wout[k][0].args())
             if (t + 1) % LL_EVERY and t + 1 != LL_STEPS:
                 continue
-            elapsed_of(env, "lunarlander", el)
+            elapsed_of(env, "lunar_lander", el)
 
             def make_small(k, a, b):
-                elapsed_of(twins[k], "lunarlander", wout[k][1])
-                return dict(wout[k][0].named(), columns=engine_columns(twins[k], "lunarlander"), elapsed=wout[k][1])
+                elapsed_of(twins[k], "lunar_lander", wout[k][1])
+                return dict(wout[k][0].named(), columns=engine_columns(twins[k], "lunar_lander"), elapsed=wout[k][1])
 
-            bp.assert_windows_equal(dict(out.named(), columns=engine_columns(env, "lunarlander"), elapsed=el), make_small, wins, f"LunarLander step {t}:")
+            bp.assert_windows_equal(dict(out.named(), columns=engine_columns(env, "lunar_lander"), elapsed=el), make_small, wins, f"LunarLander step {t}:")
         assert total > 0 and env.episode_count() == total   # contacts and crashes occurred
         report()
     finally:

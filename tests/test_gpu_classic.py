@@ -9,17 +9,16 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+from families import FAMILIES
 from harness import VecAdapter, replay
 from oracle import oracle as ora
 from sincos_mid_range import ANGLES as MID_RANGE_ANGLES
 
 pytestmark = pytest.mark.gpu
 
-PAIRS = {"cartpole": (mg.CARTPOLE, ora.CARTPOLE, 2), "mountain_car": (mg.MOUNTAINCAR, ora.MOUNTAINCAR, 3)}
-
 
 def both(name, n, seed=1, base=0, **kw):
-    k, ok, nact = PAIRS[name] if name in PAIRS else (mg.MOUNTAINCAR_CONT, ora.MOUNTAINCAR_CONT, 0)
+    k, ok, nact = FAMILIES[name].kind, FAMILIES[name].okind, FAMILIES[name].n_actions
     okw = dict(kw)
     okw.pop("auto_reset", None)
     return mg.VecEnv(k, n, seed=seed, env_id_base=base, **kw), ora.OracleVec(ok, n, seed=seed, env_id_base=base, **okw), nact
@@ -158,7 +157,7 @@ def test_mountain_car_full_size_1mi_envs():
 
 def test_mountain_car_continuous_vs_oracle():
     n = 1 << 20  # BASELINE configs[2], second half — NOT in the reference: parity unpinned
-    env, ref, _ = both("mountain_car_cont", n, seed=5)
+    env, ref, _ = both("mountain_car_continuous", n, seed=5)
     assert np.array_equal(env.reset(), ref.reset())
     rng = np.random.default_rng(3)
     for t in range(20):
@@ -441,7 +440,7 @@ def test_rollout_fallback_paths():
         assert np.array_equal(obs[t], eo) and np.array_equal(rew[t], er)
 
 
-@pytest.mark.parametrize("name,okind,kind", [("mountain_car", ora.MOUNTAINCAR, mg.MOUNTAINCAR), ("mountain_car_cont", ora.MOUNTAINCAR_CONT, mg.MOUNTAINCAR_CONT)])
+@pytest.mark.parametrize("name,okind,kind", [(name, FAMILIES[name].okind, FAMILIES[name].kind) for name in ("mountain_car", "mountain_car_continuous")])
 def test_mountain_car_fused_rollout_equals_k_steps(name, okind, kind):
     n, K = 4096, 40
     rng = np.random.default_rng(8)

@@ -12,20 +12,19 @@ import pytest
 
 import modurl_gym_amd as mg
 from classic_edge_cases import CP_THETA_THR
-from modurl_gym_amd.envs import DeviceArray
+from device_buffers import FILL, CallBuffers, FinalBuf, policy_call
+from families import BY_KIND, CLASSIC, FAMILIES
 from words import same
 
 pytestmark = pytest.mark.gpu
 
 N, K, LIMIT = 8, 5, 3
 SEED, PSEED, CALL, SIGMA = 31, 77, 3, 0.5
-FILL = 0x7FC0DEAD   # a NaN word no step produces
-KINDS = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_cont": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM, "acrobot": mg.ACROBOT}
-BOX = (mg.MOUNTAINCAR_CONT, mg.PENDULUM)
 MODES = ("plain", "auto_reset", "final")
 SOURCES = ("table", "uniform", "linear", "mlp_relu", "mlp_tanh_fast_draw", "mlp2_relu", "mlp2_tanh_fast_draw")
-CASES = [pytest.param(kind, mode, limit, src, id=f"{fam}-{mode}-limit{limit}-{src}")
-         for fam, kind in KINDS.items() for mode in MODES for limit in ((0,) if kind == mg.CARTPOLE else (0, LIMIT)) for src in SOURCES]
+CASE_ID = {"mountain_car_continuous": "mountain_car_cont"}   # the cases keep the ids they have had
+CASES = [pytest.param(FAMILIES[fam].kind, mode, limit, src, id=f"{CASE_ID.get(fam, fam)}-{mode}-limit{limit}-{src}")
+         for fam in CLASSIC for mode in MODES for limit in ((0, LIMIT) if FAMILIES[fam].limit_ok else (0,)) for src in SOURCES]
 
 
 def make(kind, mode, limit):
@@ -39,80 +38,60 @@ def make(kind, mode, limit):
     return env
 
 
-class Bufs:
-    """the [K, ..] device outputs of a case and its final-observation buffer, filled with FILL"""
+def buffers(env):
+    """the [K, ..] device buffers of a case and its final-observation buffer"""
+    return CallBuffers(N, env.obs_dim, np.uint32, K), FinalBuf(K, env.obs_dim, N)
 
-    def __init__(self, env):
-        self.D = env.obs_dim
-        self.act = DeviceArray((K, N), np.uint32)
-        self.obs, self.rew = DeviceArray((K, self.D, N), np.float32), DeviceArray((K, N), np.float32)
-        self.done, self.trunc = DeviceArray((K, N), np.uint8), DeviceArray((K, N), np.uint8)
-        self.fin = DeviceArray.from_numpy(np.full((K, self.D, N), FILL, np.uint32))
 
-    def outs(self, k=0):
-        """the pointers of step k's slabs: obs, reward, done, truncated"""
-        return self.obs.ptr + 4 * k * self.D * N, self.rew.ptr + 4 * k * N, self.done.ptr + k * N, self.trunc.ptr + k * N
-
-    def host(self, env):
-        res = dict(obs=self.obs.numpy(), rew=self.rew.numpy(), done=self.done.numpy(), trunc=self.trunc.numpy(), final=self.fin.numpy(),
-                   state=env.get_state(), count=np.array([env.episode_count()]))
-        if env.kind != mg.CARTPOLE:
-            res["elapsed"] = env.elapsed_steps()
-        return res
+def host(env, b, fb):
+    assert fb.guards_hold()
+    res = dict(b.host(), final=fb.payload(fb.shape), state=env.get_state(), count=np.array([env.episode_count()]))
+    if env.kind != mg.CARTPOLE:
+        res["elapsed"] = env.elapsed_steps()
+    return res
 
 
 def table_actions(kind):
     rng = np.random.default_rng(3)
-    if kind in BOX:
+    if BY_KIND[kind].box is not None:
         return rng.uniform(-2.5, 2.5, (K, N)).astype(np.float32).view(np.uint32)   # beyond the action bounds: the step clamps
     return rng.integers(0, 2 if kind == mg.CARTPOLE else 3, (K, N)).astype(np.uint32)
 
 
 def fused_call(env, src, b):
-    """the K-step call of the source, its actions into b.act (the table's are there already)"""
+    """the K-step call of the source, its actions into b's (the table's are there already)"""
     rng = np.random.default_rng(9)
     D, A = env.mlp_dims()
-    draw = "gauss" if env.kind in BOX else "sample"
-    if src == "table":
-        env.rollout_device(b.act, K, *b.outs())
-    elif src == "uniform":
-        env.rollout_uniform_device(PSEED, K, b.act, *b.outs())
-    elif src == "linear":
-        rows = 3 if env.kind in (mg.MOUNTAINCAR, mg.ACROBOT) else 1
-        env.rollout_linear_device(rng.normal(0, 1, rows * (D + 1)).astype(np.float32), K, b.act, *b.outs())
+    draw = "sample" if BY_KIND[env.kind].box is None else "gauss"
+    linear = mlp = None
+    if src == "linear":
+        linear = rng.normal(0, 1, BY_KIND[env.kind].lin).astype(np.float32)
     elif src.startswith("mlp2"):
-        pol, h1, h2 = env.pack_mlp2(*(rng.normal(0, 1, s) for s in ((3, D), (3,), (5, 3), (5,), (A, 5), (A,))))
-        activation, head = ("relu", "greedy") if src == "mlp2_relu" else ("tanh_fast", draw)
-        env.rollout_mlp2_device(pol, h1, h2, activation, head, SIGMA, PSEED, CALL, K, b.act, *b.outs())
-    else:
-        pol, h = env.pack_mlp(*(rng.normal(0, 1, s) for s in ((2, D), (2,), (A, 2), (A,))))
-        if src == "mlp_relu":
-            env.rollout_mlp_device(pol, h, "relu", K, b.act, *b.outs())
-        elif draw == "sample":
-            env.rollout_mlp_sample_device(pol, h, "tanh_fast", PSEED, CALL, K, b.act, *b.outs())
-        else:
-            env.rollout_mlp_gauss_device(pol, h, "tanh_fast", SIGMA, PSEED, CALL, K, b.act, *b.outs())
-    env.sync()
+        mlp = env.pack_mlp2(*(rng.normal(0, 1, s) for s in ((3, D), (3,), (5, 3), (5,), (A, 5), (A,))))
+    elif src.startswith("mlp"):
+        mlp = env.pack_mlp(*(rng.normal(0, 1, s) for s in ((2, D), (2,), (A, 2), (A,))))
+    name = {"mlp_tanh_fast_draw": f"{draw}_tanh_fast", "mlp2_relu": "mlp2_relu_greedy", "mlp2_tanh_fast_draw": f"mlp2_tanh_fast_{draw}"}.get(src, src)
+    policy_call(env, name, K, b, linear, mlp, PSEED, CALL, SIGMA)
 
 
 @pytest.mark.parametrize("kind,mode,limit,src", CASES)
 def test_fused_call_is_k_steps(kind, mode, limit, src):
     env, ref = make(kind, mode, limit), make(kind, mode, limit)
-    b, rb = Bufs(env), Bufs(ref)
+    (b, fb), (rb, rfb) = buffers(env), buffers(ref)
     if src == "table":
-        b.act.copy_from(table_actions(kind))
+        b.put_actions(table_actions(kind))
     if mode == "final":
-        env.set_final_obs_out_device(b.fin, K)
+        env.set_final_obs_out_device(fb.ptr, K)
     fused_call(env, src, b)
-    got = b.host(env)
+    got = host(env, b, fb)
 
-    rb.act.copy_from(b.act.numpy())
+    rb.put_actions(b.actions())
     for k in range(K):
         if mode == "final":
-            ref.set_final_obs_out_device(rb.fin.ptr + 4 * k * rb.D * N, 1)
-        ref.step_device(rb.act.ptr + 4 * k * N, *rb.outs(k))
+            ref.set_final_obs_out_device(rfb.ptr + 4 * k * ref.obs_dim * N, 1)
+        ref.step_device(*rb.pointers(k))
     ref.sync()
-    exp = rb.host(ref)
+    exp = host(ref, rb, rfb)
     env.close(), ref.close()
 
     for key in exp:

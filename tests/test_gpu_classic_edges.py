@@ -16,21 +16,27 @@ import acrobot_ref as AR
 import classic_edge_cases as E
 import modurl_gym_amd as mg
 import pendulum_ref as PR
+from device_buffers import CallBuffers, FinalBuf
+from families import FAMILIES
 from mlp_ref import argmax_words
 from oracle import oracle as ora
+from time_limit_ref import TimeLimitRef
 from words import same_words
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SEED = 0xED6E5
-FILL = 0x7FC0DEAD   # a NaN word no step produces
 
 
 # ---- families ---------------------------------------------------------------------------------------------------------------------------
 class Family:
-    def __init__(self, name, kind, cases, f32_cols, cfg=None, okind=None, subset=None, limit_ok=True):
-        self.name, self.kind, self._cases, self.f32_cols, self.cfg, self.okind, self.subset, self.limit_ok = name, kind, cases, f32_cols, cfg or {}, okind, subset, limit_ok
+    """a family of tests/families.py with what is this file's: the edge cases, the configuration and a subset of the cases"""
+
+    def __init__(self, name, cases, cfg=None, subset=None):
+        self.name, self._cases, self.cfg, self.subset = name, cases, cfg or {}, subset
+        self.table = FAMILIES[name.split("-")[0]]
+        self.kind, self.okind, self.f32_cols, self.limit_ok = self.table.kind, self.table.okind, self.table.f32_cols, self.table.limit_ok
 
     def cases(self):
         blob, a = self._cases()
@@ -40,20 +46,18 @@ class Family:
         return blob, a
 
 
-FAMILIES = [Family(f"cartpole-sb{int(sb)}-euler{int(eu)}", mg.CARTPOLE, E.cartpole_cases, 4, dict(sutton_barto_reward=sb, is_euler=eu), ora.CARTPOLE, limit_ok=False)
-            for sb, eu in E.CP_CONFIGS]
-FAMILIES += [Family(f"mountain_car-gv{gv}", mg.MOUNTAINCAR, lambda: E.mountain_car_cases(False), 2, dict(goal_velocity=gv), ora.MOUNTAINCAR) for gv in E.MC_GOAL_VELOCITIES]
-FAMILIES += [Family(f"mountain_car_cont-gv{gv}", mg.MOUNTAINCAR_CONT, lambda: E.mountain_car_cases(True), 2, dict(goal_velocity=gv), ora.MOUNTAINCAR_CONT)
-             for gv in E.MC_GOAL_VELOCITIES]
-FAMILIES += [Family("pendulum-g10", mg.PENDULUM, E.pendulum_cases, 2, dict(gravity=10.0))]
-FAMILIES += [Family(f"pendulum-g{g}", mg.PENDULUM, E.pendulum_cases, 2, dict(gravity=g), subset=E.pendulum_gravity_subset) for g in (0.0, -3.5)]
-FAMILIES += [Family("acrobot", mg.ACROBOT, E.acrobot_cases, 4)]
-NON_FINITE = [Family("pendulum-non_finite", mg.PENDULUM, lambda: E.non_finite_cases("pendulum"), 2, dict(gravity=10.0)),
-              Family("acrobot-non_finite", mg.ACROBOT, lambda: E.non_finite_cases("acrobot"), 4),
-              Family("mountain_car_cont-non_finite", mg.MOUNTAINCAR_CONT, lambda: E.non_finite_cases("mountain_car_cont"), 2, dict(goal_velocity=0.0), ora.MOUNTAINCAR_CONT)]
-BY_NAME = {f.name: f for f in FAMILIES + NON_FINITE}
-NAMES = [f.name for f in FAMILIES]
-ONE_PER_KIND = ["cartpole-sb0-euler1", "mountain_car-gv0.0", "mountain_car_cont-gv0.03", "pendulum-g10", "acrobot"]
+EDGES = [Family(f"cartpole-sb{int(sb)}-euler{int(eu)}", E.cartpole_cases, dict(sutton_barto_reward=sb, is_euler=eu)) for sb, eu in E.CP_CONFIGS]
+EDGES += [Family(f"mountain_car-gv{gv}", lambda: E.mountain_car_cases(False), dict(goal_velocity=gv)) for gv in E.MC_GOAL_VELOCITIES]
+EDGES += [Family(f"mountain_car_continuous-gv{gv}", lambda: E.mountain_car_cases(True), dict(goal_velocity=gv)) for gv in E.MC_GOAL_VELOCITIES]
+EDGES += [Family("pendulum-g10", E.pendulum_cases, dict(gravity=10.0))]
+EDGES += [Family(f"pendulum-g{g}", E.pendulum_cases, dict(gravity=g), subset=E.pendulum_gravity_subset) for g in (0.0, -3.5)]
+EDGES += [Family("acrobot", E.acrobot_cases)]
+NON_FINITE = [Family("pendulum-non_finite", lambda: E.non_finite_cases("pendulum"), dict(gravity=10.0)),
+              Family("acrobot-non_finite", lambda: E.non_finite_cases("acrobot")),
+              Family("mountain_car_continuous-non_finite", lambda: E.non_finite_cases("mountain_car_continuous"), dict(goal_velocity=0.0))]
+BY_NAME = {f.name: f for f in EDGES + NON_FINITE}
+NAMES = [f.name for f in EDGES]
+ONE_PER_KIND = ["cartpole-sb0-euler1", "mountain_car-gv0.0", "mountain_car_continuous-gv0.03", "pendulum-g10", "acrobot"]
 
 
 class PdRef(PR.PendulumRef):
@@ -71,28 +75,6 @@ class PdRef(PR.PendulumRef):
         return out
 
 
-class OracleRef:
-    """the CPU oracle with gymnasium's TimeLimit rule and the fused reset round it (tests/time_limit_ref.py, for CartPole too, whose own step truncates
-    at 500): elapsed += 1, truncated |= elapsed >= limit, and with auto-reset the finished environments are reset through the oracle"""
-
-    def __init__(self, ref, limit, auto):
-        self.ref, self.limit, self.auto = ref, int(limit), auto
-        self.elapsed, self.finished = np.zeros(ref.n, np.uint32), 0
-
-    def step(self, a):
-        obs, rew, done, trunc = self.ref.step(a)
-        self.elapsed += 1
-        if self.limit:
-            trunc = trunc | (self.elapsed >= self.limit).astype(np.uint8)
-        fin = (done | trunc).astype(bool)
-        self.final_obs = obs.copy()
-        self.finished += int(fin.sum())
-        if self.auto and fin.any():
-            obs = np.where(fin[None, :], self.ref.reset(fin.astype(np.uint8)), obs)
-            self.elapsed[fin] = 0
-        return obs, rew, done, trunc
-
-
 class Ref:
     """the family's reference behind one surface: import, observation, step -> (obs, reward, done, truncated) and the pre-reset observation"""
 
@@ -100,7 +82,8 @@ class Ref:
         n = blob.shape[1]
         self.fam, self.n = fam, n
         if fam.okind is not None:
-            self.r = OracleRef(ora.OracleVec(fam.okind, n, seed=SEED, **fam.cfg), limit, auto)
+            # (tests/time_limit_ref.py, for CartPole too, whose own step truncates at 500: its flag is OR-ed in)
+            self.r = TimeLimitRef(ora.OracleVec(fam.okind, n, seed=SEED, **fam.cfg), limit, auto, own_truncation=not fam.limit_ok)
             self.r.ref.set_state(np.ascontiguousarray(blob).view(F))
             self._obs0 = np.ascontiguousarray(blob[:fam.f32_cols]).view(F).copy()
         elif fam.kind == mg.PENDULUM:
@@ -201,26 +184,6 @@ def imported(fam, blob, limit, auto):
     return env
 
 
-class Buffers:
-    """device buffers of one call of K steps; the reward buffer optionally `offset` bytes off its 16-byte alignment"""
-
-    def __init__(self, env, K=1, offset=0, with_obs=True):
-        n, D = env.n, env.obs_dim
-        self.n, self.K, self.D, self.offset = n, K, D, offset
-        self.act, self.obs = mg.DeviceArray((K, n), env.action_dtype), (mg.DeviceArray((K, D, n), F) if with_obs else None)
-        self.rew = mg.DeviceArray(K * n + 4, F)
-        self.done, self.trunc = mg.DeviceArray((K, n), np.uint8), mg.DeviceArray((K, n), np.uint8)
-
-    def outs(self):
-        return self.obs, self.rew.ptr + self.offset, self.done, self.trunc
-
-    def read(self):
-        K, n = self.K, self.n
-        rew = self.rew.numpy().view(np.uint8)[self.offset: self.offset + 4 * K * n].view(F).copy().reshape(K, n)
-        obs = self.obs.numpy().reshape(K, self.D, n) if self.obs is not None else None
-        return obs, rew, self.done.numpy().reshape(K, n), self.trunc.numpy().reshape(K, n)
-
-
 def check_end(fam, env, exp, limit, what):
     assert same_state(fam, env.get_state(), exp["state"]), f"{what}: state blob"
     assert same_words(env.observation(), exp["steps"][-1][0]), f"{what}: engine observation"
@@ -251,9 +214,9 @@ def test_one_step_through_each_launch_form(name, form, monkeypatch):
         what = f"{name} {form} {order}"
         assert same_words(env.observation(), exp["obs0"]), f"{what}: observation after the import"
         assert same_state(fam, env.get_state(), blob), f"{what}: get_state after the import"
-        buf = Buffers(env, 1, offset, not ragged)
-        buf.act.copy_from(a.reshape(1, -1))
-        env.step_device(buf.act, *buf.outs())
+        buf = CallBuffers(env.n, env.obs_dim, env.action_dtype, 1, offset, not ragged)
+        buf.put_actions(a)
+        env.step_device(*buf.pointers())
         env.sync()
         o, r, d, t = buf.read()
         assert_step((o[0] if o is not None else env.observation(), r[0], d[0], t[0]), exp["steps"][0], what)
@@ -282,7 +245,7 @@ def test_rollout_of_three_steps(name):
 def constant_policies(fam):
     """-> [(id, host policy floats, reference policy: observation -> actions)]: all-zero weights and a bias that selects a constant action (a zero weight
     times a non-finite observation word is a NaN score: the reference evaluates the text's sum)"""
-    D = {mg.CARTPOLE: 4, mg.MOUNTAINCAR: 2, mg.MOUNTAINCAR_CONT: 2, mg.PENDULUM: 3, mg.ACROBOT: 6}[fam.kind]
+    D = fam.table.D
     out = []
 
     def zero_sum(obs):
@@ -302,7 +265,7 @@ def constant_policies(fam):
             ref = (lambda obs, pol=pol: argmax_words(np.stack([zero_sum(obs) + pol[j, D] for j in range(3)])))
             out.append((f"a{act}", pol.ravel(), ref))
     else:
-        top = 1.0 if fam.kind == mg.MOUNTAINCAR_CONT else 2.0
+        top = fam.table.box[1]
         for b in (F(-top), np.nextafter(F(top), F(3)), F(1e30)):
             out.append((f"b{float(b):g}", np.array([0] * D + [b], F), lambda obs, b=b: (zero_sum(obs) + b).astype(F)))
     return out
@@ -325,28 +288,8 @@ def test_linear_policy_rollout_with_a_constant_action(name):
 
 
 # ---- endings: auto-reset and the final-observation channel ---------------------------------------------------------------------------------------
-class FinalBuf:
-    """the caller's [K][obs_dim][n] buffer between guard words, filled with FILL"""
-
-    def __init__(self, env, K):
-        self.shape = (K, env.obs_dim, env.n)
-        self.words = int(np.prod(self.shape))
-        self.dev = mg.DeviceArray(self.words + 8, np.uint32)
-        self.dev.copy_from(np.full(self.words + 8, FILL, np.uint32))
-        self.ptr = self.dev.ptr + 16
-
-    def check(self, finals, fin, what):
-        got = self.dev.numpy()
-        body = got[4: 4 + self.words].reshape(self.shape)
-        assert np.all(got[:4] == FILL) and np.all(got[4 + self.words:] == FILL), f"{what}: a guard word was written"
-        for t in range(self.shape[0]):
-            m = fin[t]
-            assert same_words(body[t][:, m].view(F), finals[t][:, m]), f"{what} step {t}: final observations differ"
-            assert np.all(body[t][:, ~m] == FILL), f"{what} step {t}: words of unfinished env-steps were written"
-
-
 @pytest.mark.parametrize("call", ["step", "rollout3"])
-@pytest.mark.parametrize("name", ONE_PER_KIND + ["cartpole-sb1-euler0", "mountain_car_cont-gv0.0"])
+@pytest.mark.parametrize("name", ONE_PER_KIND + ["cartpole-sb1-euler0", "mountain_car_continuous-gv0.0"])
 def test_endings_with_auto_reset_and_final_observations(name, call):
     """max_episode_steps = 1 (CartPole: the imported counters at 499 and 500 and the threshold cases): the final observation of every finished env-step
     is the observation the step produced before the fused reset — edge, denormal and NaN words alike — obs_out holds the reset observation, and no
@@ -358,7 +301,7 @@ def test_endings_with_auto_reset_and_final_observations(name, call):
     fin = [(s[2] | s[3]).astype(bool) for s in exp["steps"]]
     assert fin[0].sum() >= blob.shape[1] // 4 and (fam.limit_ok or not fin[0].all())
     env = imported(fam, blob, 1, True)
-    fb = FinalBuf(env, K)
+    fb = FinalBuf(K, env.obs_dim, env.n)
     env.set_final_obs_out_device(fb.ptr, K)
     if call == "step":
         got = [x[None] for x in env.step(a)]
@@ -366,14 +309,14 @@ def test_endings_with_auto_reset_and_final_observations(name, call):
         got = env.rollout(action_table(a, K))
     for t in range(K):
         assert_step([x[t] for x in got], exp["steps"][t], f"{name} {call} step {t}")
-    fb.check(exp["finals"], fin, f"{name} {call}")
+    fb.check(exp["finals"], fin, f"{name} {call}", same_words)
     check_end(fam, env, exp, 1, f"{name} {call}")
     env.set_final_obs_out_device(None)
     env.close()
 
 
 # ---- a NaN torque or force on a step that truncates and auto-resets ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["pendulum-g10", "mountain_car_cont-gv0.0"])
+@pytest.mark.parametrize("name", ["pendulum-g10", "mountain_car_continuous-gv0.0"])
 def test_nan_action_on_a_truncating_step(name):
     """The refused step leaves the state and gives reward 0 and done 0, but the elapsed count advances: with max_episode_steps = 1 the environment is
     truncated and reset, and its final observation is the untouched imported one.  The other environments of its lane equal the reference, and the
@@ -394,16 +337,16 @@ def test_nan_action_on_a_truncating_step(name):
     finals[:, bad], er[bad], ed[bad] = obs0[:, bad], 0, 0
     assert np.all(et == 1)
     env = imported(fam, blob, 1, True)
-    fb = FinalBuf(env, 1)
+    fb = FinalBuf(1, env.obs_dim, env.n)
     env.set_final_obs_out_device(fb.ptr, 1)
-    buf = Buffers(env)
-    buf.act.copy_from(a.reshape(1, -1))
-    env.step_device(buf.act, *buf.outs())
+    buf = CallBuffers(env.n, env.obs_dim, env.action_dtype)
+    buf.put_actions(a)
+    env.step_device(*buf.pointers())
     with pytest.raises(mg.InvalidActionError):
         env.sync()
     o, r, d, t = buf.read()
     assert_step((o[0], r[0], d[0], t[0]), (eo, er, ed, et), f"{name} NaN action")
-    fb.check([finals], [np.ones(n, bool)], f"{name} NaN action")
+    fb.check([finals], [np.ones(n, bool)], f"{name} NaN action", same_words)
     assert not env.elapsed_steps().any() and env.episode_count() == n   # every environment was truncated and reset, the refused ones too
     assert same_state(fam, env.get_state(), ref.state())
     env.sync()   # the status was cleared
@@ -451,4 +394,4 @@ def test_non_finite_states_acrobot():
 def test_non_finite_states_mountain_car_cont():
     """+-inf and NaN in position and in velocity.  The MountainCarContinuous step has no fmodf and no data-dependent loop at all: the device assembly
     holds only the grid-stride and K loops, on scalar integer compares."""
-    non_finite_run("mountain_car_cont-non_finite")
+    non_finite_run("mountain_car_continuous-non_finite")

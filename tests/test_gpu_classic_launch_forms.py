@@ -8,6 +8,7 @@ import pytest
 
 import modurl_gym_amd as mg
 from oracle import oracle as ora
+from families import BY_KIND
 from time_limit_ref import TimeLimitRef
 from words import same
 
@@ -15,7 +16,6 @@ pytestmark = pytest.mark.gpu
 
 STEPS = 64
 NAMES = ("obs_out", "reward", "done", "truncated")
-OKIND = {mg.CARTPOLE: ora.CARTPOLE, mg.MOUNTAINCAR: ora.MOUNTAINCAR, mg.MOUNTAINCAR_CONT: ora.MOUNTAINCAR_CONT}
 
 
 def actions(kind, rng, n):
@@ -101,7 +101,7 @@ def test_mountaincar_vs_oracle(kind, limit, n):
     """limit = 5 forces truncations and resets every few steps and takes the instantiation that reads the elapsed column."""
     seed = 300 + n + limit
     env = mg.VecEnv(kind, n, seed=seed, auto_reset=True, max_episode_steps=limit)
-    ref = TimeLimitRef(ora.OracleVec(OKIND[kind], n, seed=seed), limit, True)
+    ref = TimeLimitRef(ora.OracleVec(BY_KIND[kind].okind, n, seed=seed), limit, True)
     rng = np.random.default_rng(seed)
     assert same(env.reset(), ref.reset())
     for t in range(STEPS):

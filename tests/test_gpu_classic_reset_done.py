@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+from families import CLASSIC, KIND
 
 pytestmark = pytest.mark.gpu
 
 N = 1027
-KINDS = {"mountain_car": mg.MOUNTAINCAR, "mountain_car_cont": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM, "acrobot": mg.ACROBOT}
+NAMES = [name for name in CLASSIC if name != "cartpole"]
 
 
 def masks(seed):
@@ -27,9 +28,9 @@ def masks(seed):
 
 
 @pytest.mark.parametrize("unaligned", [False, True], ids=["aligned", "unaligned"])
-@pytest.mark.parametrize("name", list(KINDS))
+@pytest.mark.parametrize("name", NAMES)
 def test_reset_done_two_masks_equal_one_mask_reset(name, unaligned):
-    a, b = (mg.VecEnv(KINDS[name], N, seed=41) for _ in range(2))
+    a, b = (mg.VecEnv(KIND[name], N, seed=41) for _ in range(2))
     done, trunc = masks(7)
     mask = ((done | trunc) != 0).astype(np.uint8)
     el = np.random.default_rng(8).integers(1, 70000, N).astype(np.uint32)

@@ -8,6 +8,7 @@ import functools
 import numpy as np
 import pytest
 
+import device_buffers
 import gae_ref as R
 import modurl_gym_amd as mg
 from modurl_gym_amd import _lib
@@ -19,6 +20,7 @@ F = np.float32
 N = 2052
 B = R.batch()
 KS = sorted({1, 2, 17, B - 1, B, B + 1})
+Guarded = functools.partial(device_buffers.Guarded, fill=R.NAN_WORD)   # the word the inputs are built round
 
 
 @functools.lru_cache(maxsize=None)
@@ -41,16 +43,16 @@ def expected(K, n, with_d=True, with_u=True):
     return R.episode_returns(c["r"], c["d"] if with_d else None, c["u"] if with_u else None, c["acc"], c["len"])
 
 
-class Bufs:
+class Slabs:
     def __init__(self, K, n, mis_rew=0, with_d=True, with_u=True, with_ret=True, with_len=True):
         c = case(K, n)
         self.K, self.n = K, n
-        self.r = R.Guarded(K * n, mis_rew, c["r"])
+        self.r = Guarded(K * n, mis_rew, c["r"])
         self.d = mg.DeviceArray.from_numpy(c["d"]) if with_d else None
         self.u = mg.DeviceArray.from_numpy(c["u"]) if with_u else None
-        self.acc, self.len = R.Guarded(n, 0, c["acc"]), R.Guarded(n, 0, c["len"])
-        self.ret_out = R.Guarded(K * n) if with_ret else None
-        self.len_out = R.Guarded(K * n) if with_len else None
+        self.acc, self.len = Guarded(n, 0, c["acc"]), Guarded(n, 0, c["len"])
+        self.ret_out = Guarded(K * n) if with_ret else None
+        self.len_out = Guarded(K * n) if with_len else None
 
     def args(self):
         return (self.K, self.r, self.d, self.u, self.acc, self.len, self.ret_out, self.len_out)
@@ -82,7 +84,7 @@ def env():
 
 
 def run(env, K, n=N, **kw):
-    b = Bufs(K, n, **kw)
+    b = Slabs(K, n, **kw)
     env.episode_returns_device(*b.args())
     env.sync()
     b.check(expected(K, n, kw.get("with_d", True), kw.get("with_u", True)), f"K={K} n={n} {kw}")
@@ -118,8 +120,8 @@ def test_two_calls_leave_the_words_of_one(env, K1, K2):
     K = K1 + K2
     c = case(K, N)
     one = expected(K, N)
-    acc, length = R.Guarded(N, 0, c["acc"]), R.Guarded(N, 0, c["len"])
-    ret_out, len_out = R.Guarded(K * N), R.Guarded(K * N)
+    acc, length = Guarded(N, 0, c["acc"]), Guarded(N, 0, c["len"])
+    ret_out, len_out = Guarded(K * N), Guarded(K * N)
     r, d, u = mg.DeviceArray.from_numpy(c["r"]), mg.DeviceArray.from_numpy(c["d"]), mg.DeviceArray.from_numpy(c["u"])
     env.episode_returns_device(K1, r, d, u, acc, length, ret_out, len_out)
     env.episode_returns_device(K2, r.ptr + 4 * K1 * N, d.ptr + K1 * N, u.ptr + K1 * N, acc, length, ret_out.ptr + 4 * K1 * N, len_out.ptr + 4 * K1 * N)
@@ -130,7 +132,7 @@ def test_two_calls_leave_the_words_of_one(env, K1, K2):
 
 def test_graph_replay_equals_the_eager_call(env):
     K = B + 1
-    b = Bufs(K, N)
+    b = Slabs(K, N)
     g = env.graph_capture(lambda: env.episode_returns_device(*b.args()))
     try:
         env.sync()
@@ -146,7 +148,7 @@ def test_lunar_lander_handle_never_reset():
     e = mg.VecEnv(mg.LUNARLANDER, 8)
     r, d = np.arange(24, dtype=F).reshape(3, 8), np.zeros((3, 8), np.uint8)
     d[1, :4], d[2, 2:6] = 1, 1
-    acc, length, ret_out, len_out = R.Guarded(8, 0, np.zeros(8, F)), R.Guarded(8, 0, np.zeros(8, np.uint32)), R.Guarded(24), R.Guarded(24)
+    acc, length, ret_out, len_out = Guarded(8, 0, np.zeros(8, F)), Guarded(8, 0, np.zeros(8, np.uint32)), Guarded(24), Guarded(24)
     e.episode_returns_device(3, mg.DeviceArray.from_numpy(r), mg.DeviceArray.from_numpy(d), None, acc, length, ret_out, len_out)
     e.sync()
     exp = R.episode_returns(r, d, None, np.zeros(8, F), np.zeros(8, np.uint32))
@@ -165,7 +167,7 @@ def bad_arg(fn, *needles):
 
 def test_errors(env):
     K = 2
-    b = Bufs(K, N)
+    b = Slabs(K, N)
     a = list(b.args())
     IK, IR, ID, IU, IACC, ILEN, IRO, ILO = range(8)
 

@@ -19,19 +19,20 @@ import pytest
 
 import modurl_gym_amd as mg
 from modurl_gym_amd import _lib
+from device_buffers import FILL, CallBuffers, FinalBuf, copy_state, policy_call, twin_steps
+from families import BY_KIND, FAMILIES as FAM
 from words import bits, same
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0x7FC0DEAD   # a NaN word no step produces
 SEED, PSEED, H, N = 2024, 77, 8, 2052
 LIMIT = 7
 MC_KINDS = (mg.MOUNTAINCAR, mg.MOUNTAINCAR_CONT)
 DISCRETE_SRC = ["table", "uniform", "linear", "mlp_relu", "mlp_tanh", "sample_relu", "sample_tanh"]
 BOX_SRC = ["table", "uniform", "linear", "mlp_relu", "mlp_tanh", "gauss_relu", "gauss_tanh"]
-FAMILIES = [(mg.CARTPOLE, 0, DISCRETE_SRC), (mg.MOUNTAINCAR, LIMIT, DISCRETE_SRC), (mg.MOUNTAINCAR, 0, DISCRETE_SRC),
-            (mg.MOUNTAINCAR_CONT, LIMIT, BOX_SRC), (mg.MOUNTAINCAR_CONT, 0, BOX_SRC), (mg.PENDULUM, LIMIT, BOX_SRC)]
-FAMILY_IDS = ["cartpole", "mountaincar-tl", "mountaincar", "mountaincar_cont-tl", "mountaincar_cont", "pendulum-tl"]
+CASES = [("cartpole", 0), ("mountain_car", LIMIT), ("mountain_car", 0), ("mountain_car_continuous", LIMIT), ("mountain_car_continuous", 0), ("pendulum", LIMIT)]
+FAMILIES = [(FAM[f].kind, lim, DISCRETE_SRC if FAM[f].box is None else BOX_SRC) for f, lim in CASES]
+FAMILY_IDS = ["cartpole", "mountaincar-tl", "mountaincar", "mountaincar_cont-tl", "mountaincar_cont", "pendulum-tl"]   # the cases' ids, kept as they were
 SOURCE_CASES = [pytest.param(k, lim, s, id=f"{fid}-{s}") for (k, lim, srcs), fid in zip(FAMILIES, FAMILY_IDS) for s in srcs]
 KIND_CASES = [pytest.param(k, lim, id=fid) for (k, lim, _), fid in zip(FAMILIES, FAMILY_IDS)]
 
@@ -96,111 +97,31 @@ def table_actions(kind, K, n):
 def policies(env):
     rng = np.random.default_rng(9)
     D, A = env.mlp_dims()
-    rows = 3 if env.kind == mg.MOUNTAINCAR else 1
     mlp, _ = env.pack_mlp(rng.normal(0, 1, (H, D)), rng.normal(0, 1, H), rng.normal(0, 1, (A, H)), rng.normal(0, 1, A))
-    return dict(linear=rng.normal(0, 1, rows * (D + 1)).astype(np.float32), mlp=mlp)
+    return dict(linear=rng.normal(0, 1, BY_KIND[env.kind].lin).astype(np.float32), mlp=mlp)
 
 
-class Outs:
-    """device outputs of one K-step call; mis_rew = 1 puts the reward buffer 4 bytes off a 16-byte boundary (the one-env-per-lane kernels)"""
-
-    def __init__(self, env, K, mis_rew=0, with_obs=True):
-        n, D = env.n, env.obs_dim
-        self.K, self.n, self.D, self.mis = K, n, D, mis_rew
-        self.act = mg.DeviceArray(K * n, np.uint32)
-        self.obs = mg.DeviceArray(K * D * n, np.float32) if with_obs else None
-        self.rew = mg.DeviceArray(K * n + 4, np.float32)
-        self.done, self.trunc = mg.DeviceArray(K * n, np.uint8), mg.DeviceArray(K * n, np.uint8)
-        self.act.copy_from(np.zeros(K * n, np.uint32))
-
-    def pointers(self):
-        return (self.obs.ptr if self.obs else None, self.rew.ptr + 4 * self.mis, self.done.ptr, self.trunc.ptr)
-
-    def host(self):
-        K, n, D = self.K, self.n, self.D
-        out = dict(act=self.act.numpy().reshape(K, n), rew=self.rew.numpy()[self.mis: self.mis + K * n].reshape(K, n),
-                   done=self.done.numpy().reshape(K, n), trunc=self.trunc.numpy().reshape(K, n))
-        if self.obs:
-            out["obs"] = self.obs.numpy().reshape(K, D, n)
-        return out
+def buffers(env, K, mis_rew=0, with_obs=True):
+    """device buffers of one K-step call; mis_rew = 1 puts the reward buffer 4 bytes off a 16-byte boundary (the one-env-per-lane kernels)"""
+    return CallBuffers(env.n, env.obs_dim, env.action_dtype, K, 4 * mis_rew, with_obs)
 
 
-class FinalBuf:
-    """the caller's [cap][obs_dim][n] buffer between two guard words, filled with FILL; mis = 1: 4 bytes off a 16-byte boundary"""
-
-    def __init__(self, env, cap, mis=0):
-        self.cap, self.D, self.n, self.mis = cap, env.obs_dim, env.n, mis
-        self.words = cap * self.D * self.n
-        self.dev = mg.DeviceArray(self.words + 8, np.uint32)
-        self.off = 4 + mis   # (the allocation is 256-byte aligned)
-        self.ptr = self.dev.ptr + 4 * self.off
-        self.fill()
-
-    def fill(self):
-        self.dev.copy_from(np.full(self.words + 8, FILL, np.uint32))
-
-    def expected(self, twin_obs, twin_fin):
-        exp = np.full(self.words + 8, FILL, np.uint32)
-        view = exp[self.off: self.off + self.words].reshape(self.cap, self.D, self.n)
-        for t in range(len(twin_obs)):
-            view[t][:, twin_fin[t]] = bits(twin_obs[t])[:, twin_fin[t]]
-        return exp
-
-    def check(self, twin_obs, twin_fin, what):
-        got, exp = self.dev.numpy(), self.expected(twin_obs, twin_fin)
-        written = exp != FILL
-        assert np.array_equal(got[written], exp[written]), f"{what}: {int((got[written] != exp[written]).sum())} of {int(written.sum())} final words differ from the twin's"
-        assert np.array_equal(got[~written], exp[~written]), f"{what}: {int((got[~written] != FILL).sum())} words outside the finished env-steps were written"
-
-
-def do_call(env, src, K, o, acts):
-    obs, rew, done, trunc = o.pointers()
-    if src == "step":
-        assert K == 1
-        env.step_device(acts, obs, rew, done, trunc)
-    elif src == "table":
-        env.rollout_device(acts, K, obs, rew, done, trunc)
-    elif src == "uniform":
-        env.rollout_uniform_device(PSEED, K, o.act, obs, rew, done, trunc)
-    elif src == "linear":
-        env.rollout_linear_device(policies(env)["linear"], K, o.act, obs, rew, done, trunc)
-    else:
-        form, activation = src.split("_")
-        pol = policies(env)["mlp"]
-        if form == "mlp":
-            env.rollout_mlp_device(pol, H, activation, K, o.act, obs, rew, done, trunc)
-        elif form == "sample":
-            env.rollout_mlp_sample_device(pol, H, activation, PSEED, 3, K, o.act, obs, rew, done, trunc)
-        else:
-            env.rollout_mlp_gauss_device(pol, H, activation, 0.5, PSEED, 3, K, o.act, obs, rew, done, trunc)
-    env.sync()
-
-
-def copy_state(src, twin, limit):
-    twin.set_state(src.get_state())
-    if limit and src.kind != mg.CARTPOLE:
-        twin.set_elapsed_steps(src.elapsed_steps())
+def do_call(env, src, K, o):
+    """the call of the source on o, whose actions a step or a table reads"""
+    p = policies(env)
+    policy_call(env, src, K, o, p["linear"], (p["mlp"], H), PSEED, 3, 0.5)
 
 
 def twin_replay(kind, n, limit, actions, mis_rew=0, with_obs=True):
-    """K single steps of an auto-reset handle with the channel unset, its state copied into the twin before each: -> (the stepping handle's outputs,
-    the twin's obs [K, D, n], done and truncated [K, n]).  The twin steps on buffers of the case's shape (mis_rew, with_obs: Outs), so the launch form
-    under test runs without auto-reset as well; without obs_out its observation is the engine's view."""
+    """K single steps of an auto-reset handle with the channel unset, its state copied into the twin before each (device_buffers.twin_steps): -> (the
+    stepping handle's outputs, the twin's obs [K, D, n], done and truncated [K, n]).  The twin steps on buffers of the case's shape (mis_rew, with_obs),
+    so the launch form under test runs without auto-reset as well; without obs_out its observation is the engine's view."""
     stepper, twin = make(kind, n, limit), make(kind, n, limit, auto_reset=False)
     prep(stepper, limit)
     twin.reset()
-    to = Outs(twin, 1, mis_rew, with_obs)
-    outs, tobs, tdone, ttrunc = [], [], [], []
-    for a in actions:
-        copy_state(stepper, twin, limit)
-        outs.append([x.copy() for x in stepper.step(a)])
-        do_call(twin, "step", 1, to, mg.DeviceArray.from_numpy(a))
-        h = to.host()
-        o, d, t = h["obs"][0] if with_obs else twin.observation(), h["done"][0], h["trunc"][0]
-        tobs.append(o.copy()), tdone.append(d.astype(bool)), ttrunc.append(t.astype(bool))
-        assert same(outs[-1][2], d) and same(outs[-1][3], t), "the twin's flags are the stepping handle's"
+    res = twin_steps(stepper, twin, actions, buffers(twin, 1, mis_rew, with_obs).step)
     stepper.close(), twin.close()
-    return outs, np.array(tobs), np.array(tdone), np.array(ttrunc)
+    return res
 
 
 def check_coverage(kind, limit, d, t):
@@ -231,19 +152,20 @@ def run_case(kind, limit, src, K, n=N, mis_fin=0, mis_rew=0, with_obs=True):
     for mode in ("unset", "set"):
         env = make(kind, n, limit)
         prep(env, limit)
-        o = Outs(env, K, mis_rew, with_obs)
-        dact = mg.DeviceArray.from_numpy(acts) if is_table else None
+        o = buffers(env, K, mis_rew, with_obs)
+        if is_table:
+            o.put_actions(acts)
         if mode == "set":
-            fb = FinalBuf(env, cap, mis_fin)
+            fb = FinalBuf(cap, env.obs_dim, env.n, mis_fin)
             env.set_final_obs_out_device(fb.ptr, cap)
-        do_call(env, src, K, o, dact)
+        do_call(env, src, K, o)
         res[mode] = dict(o.host(), state=env.get_state(), view=env.observation(), count=np.array([env.episode_count()]))
         if limit and kind != mg.CARTPOLE:
             res[mode]["elapsed"] = env.elapsed_steps()
         env.close()
     for key, got in res["set"].items():   # (a)
         assert same(got, res["unset"][key]), f"{what}: {key} differs from the same call with the channel unset"
-    used = acts if is_table else res["set"]["act"].view(acts.dtype)
+    used = acts if is_table else res["set"]["act"]
     outs, tobs, tdone, ttrunc = twin_replay(kind, n, limit, used, mis_rew, with_obs)
     for t, (so, sr, sd, st) in enumerate(outs):   # the call is K steps of the stepping handle, so the twin saw the states the call went through
         got = res["set"]
@@ -300,20 +222,20 @@ def test_table_rollout_shapes(kind, limit, shape, K):
 def test_null_turns_the_channel_off(kind, limit, K):
     env = make(kind, N, limit)
     prep(env, limit)
-    fb = FinalBuf(env, K)
+    fb = FinalBuf(K, env.obs_dim, env.n)
     env.set_final_obs_out_device(fb.ptr, K)
-    o = Outs(env, K)
-    do_call(env, "uniform", K, o, None)
+    o = buffers(env, K)
+    do_call(env, "uniform", K, o)
     before = fb.dev.numpy()
     assert (before != FILL).any()
     env.set_final_obs_out_device(None)
-    do_call(env, "uniform", K, o, None)
+    do_call(env, "uniform", K, o)
     h = o.host()
     assert (h["done"] | h["trunc"]).sum() >= 8, "the further call has endings of its own"
     assert np.array_equal(fb.dev.numpy(), before)
     env.set_final_obs_out_device(fb.ptr, K)   # ... and on again: replaced, not latched off
     fb.fill()
-    do_call(env, "uniform", K, o, None)
+    do_call(env, "uniform", K, o)
     assert (fb.dev.numpy() != FILL).any()
     env.close()
 
@@ -324,12 +246,12 @@ def test_pendulum_without_a_limit_never_writes():
     for with_channel in (False, True):
         env = make(mg.PENDULUM, N, 0)
         env.reset()
-        fb = FinalBuf(env, 5)
+        fb = FinalBuf(5, env.obs_dim, env.n)
         if with_channel:
             env.set_final_obs_out_device(fb.ptr, 5)
-        o = Outs(env, 5)
-        do_call(env, "uniform", 5, o, None)
-        do_call(env, "step", 1, o, o.act)
+        o = buffers(env, 5)
+        do_call(env, "uniform", 5, o)
+        do_call(env, "step", 1, o)
         res.append(dict(o.host(), state=env.get_state()))
         assert (fb.dev.numpy() == FILL).all()
         env.close()
@@ -369,20 +291,20 @@ def test_more_steps_than_the_cap(kind, limit):
     n, cap, K = 1028, 4, 5
     env = make(kind, n, limit)
     prep(env, limit)
-    fb = FinalBuf(env, cap)
+    fb = FinalBuf(cap, env.obs_dim, env.n)
     env.set_final_obs_out_device(fb.ptr, cap)
-    o = Outs(env, K)
-    dact = mg.DeviceArray.from_numpy(table_actions(kind, K, n))
+    o = buffers(env, K)
+    o.put_actions(table_actions(kind, K, n))
     state, view, count = env.get_state(), env.observation(), env.episode_count()
     sources = {"table": "mgym_rollout:", "uniform": "mgym_rollout_uniform:", "linear": "mgym_rollout_linear:", "mlp_relu": "mgym_rollout_mlp:"}
     sources["sample_tanh" if kind in (mg.CARTPOLE, mg.MOUNTAINCAR) else "gauss_tanh"] = "mgym_rollout_mlp_sample:" if kind in (mg.CARTPOLE, mg.MOUNTAINCAR) else "mgym_rollout_mlp_gauss:"
     for src, name in sources.items():
-        bad_arg(lambda: do_call(env, src, K, o, dact), name, "steps_cap")
+        bad_arg(lambda: do_call(env, src, K, o), name, "steps_cap")
         env.sync()
         assert same(env.observation(), view) and same(env.get_state(), state) and env.episode_count() == count, src
         assert (fb.dev.numpy() == FILL).all(), src
-    do_call(env, "table", cap, o, dact)
-    do_call(env, "step", 1, o, dact)
+    do_call(env, "table", cap, o)
+    do_call(env, "step", 1, o)
     env.close()
 
 
@@ -393,13 +315,14 @@ def test_graph_replay_of_a_step(kind, limit):
     prep(env, limit)
     twin.reset()
     acts = table_actions(kind, 1, N)
-    dact, o, fb = mg.DeviceArray.from_numpy(acts), Outs(env, 1), FinalBuf(env, 1)
+    o, fb = buffers(env, 1), FinalBuf(1, env.obs_dim, env.n)
+    o.put_actions(acts)
     env.set_final_obs_out_device(fb.ptr, 1)
-    g = env.graph_capture(lambda: env.step_device(dact, *o.pointers()))
+    g = env.graph_capture(lambda: env.step_device(*o.pointers()))
     env.set_final_obs_out_device(None)   # later settings leave the captured launch what it was (and the graph valid)
     try:
         for rep in range(2):
-            copy_state(env, twin, limit)
+            copy_state(env, twin)
             fb.fill()
             env.graph_launch(g)
             env.sync()

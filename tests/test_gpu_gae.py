@@ -12,6 +12,7 @@ import functools
 import numpy as np
 import pytest
 
+import device_buffers
 import gae_ref as R
 import modurl_gym_amd as mg
 from modurl_gym_amd import _lib
@@ -23,6 +24,7 @@ F = np.float32
 N = 2052
 B = R.batch()
 KS = sorted({1, 2, 17, B - 1, B, B + 1})
+Guarded = functools.partial(device_buffers.Guarded, fill=R.NAN_WORD)   # the word the inputs are built round
 GAMMA, LAM = 0.99, 0.95
 
 
@@ -57,16 +59,16 @@ def expected(K, n, with_d=True, with_u=True, with_fv=True):
     return R.gae(c["r"], c["d"] if with_d else None, c["u"] if with_u else None, c["v"], c["lv"], final_value(K, n, with_d, with_u) if with_fv else None, GAMMA, LAM)
 
 
-class Bufs:
+class Slabs:
     def __init__(self, K, n, mis_rew=0, with_d=True, with_u=True, with_fv=True, with_adv=True, with_ret=True):
         c = case(K, n)
         self.K, self.n = K, n
-        self.r, self.v, self.lv = R.Guarded(K * n, mis_rew, c["r"]), R.Guarded(K * n, 0, c["v"]), R.Guarded(n, 0, c["lv"])
+        self.r, self.v, self.lv = Guarded(K * n, mis_rew, c["r"]), Guarded(K * n, 0, c["v"]), Guarded(n, 0, c["lv"])
         self.d = mg.DeviceArray.from_numpy(c["d"]) if with_d else None
         self.u = mg.DeviceArray.from_numpy(c["u"]) if with_u else None
-        self.fv = R.Guarded(K * n, 0, final_value(K, n, with_d, with_u)) if with_fv else None
-        self.adv = R.Guarded(K * n) if with_adv else None
-        self.ret = R.Guarded(K * n) if with_ret else None
+        self.fv = Guarded(K * n, 0, final_value(K, n, with_d, with_u)) if with_fv else None
+        self.adv = Guarded(K * n) if with_adv else None
+        self.ret = Guarded(K * n) if with_ret else None
 
     def args(self):
         return (self.K, self.r, self.d, self.u, self.v, self.lv, self.fv, GAMMA, LAM, self.adv, self.ret)
@@ -95,7 +97,7 @@ def env():
 
 
 def run(env, K, n=N, **kw):
-    b = Bufs(K, n, **kw)
+    b = Slabs(K, n, **kw)
     env.gae_device(*b.args())
     env.sync()
     exp = expected(K, n, kw.get("with_d", True), kw.get("with_u", True), kw.get("with_fv", True))
@@ -133,7 +135,7 @@ def test_a_nan_beyond_an_episode_end_stays_there(env):
     """value, reward and last_value NaN in the odd environments: the even ones give the words of the clean run"""
     K = 17
     c = case(K, N)
-    b = Bufs(K, N)
+    b = Slabs(K, N)
     r, v, lv = c["r"].copy(), c["v"].copy(), c["lv"].copy()
     r[:, 1::2], v[:, 1::2], lv[1::2] = np.nan, np.nan, np.nan
     b.r.fill(r), b.v.fill(v), b.lv.fill(lv)
@@ -147,7 +149,7 @@ def test_a_nan_beyond_an_episode_end_stays_there(env):
 
 def test_graph_replay_equals_the_eager_call(env):
     K = B + 1
-    b = Bufs(K, N)
+    b = Slabs(K, N)
     g = env.graph_capture(lambda: env.gae_device(*b.args()))
     try:
         env.sync()
@@ -178,7 +180,7 @@ def test_lunar_lander_handle_never_reset():
     c = dict(r=np.arange(24, dtype=F).reshape(3, 8), v=np.ones((3, 8), F), lv=np.full(8, 2, F), d=np.zeros((3, 8), np.uint8), u=np.zeros((3, 8), np.uint8))
     c["d"][1, :4], c["u"][2, 2:6] = 1, 1
     dev = {k: mg.DeviceArray.from_numpy(a) for k, a in c.items()}
-    adv, ret = R.Guarded(24), R.Guarded(24)
+    adv, ret = Guarded(24), Guarded(24)
     e.gae_device(3, dev["r"], dev["d"], dev["u"], dev["v"], dev["lv"], None, GAMMA, LAM, adv, ret)
     e.sync()   # (no sticky status: no state of the handle was stepped)
     exp = R.gae(c["r"], c["d"], c["u"], c["v"], c["lv"], None, GAMMA, LAM)
@@ -192,9 +194,9 @@ def test_lunar_lander_handle_never_reset():
 def test_no_environments():
     e = mg.VecEnv(mg.CARTPOLE, 0)
     x = mg.DeviceArray(4, F)
-    e.gae_device(3, x, None, None, x.ptr, x.ptr, None, GAMMA, LAM, R.Guarded(4), None)   # MGYM_OK without a launch
+    e.gae_device(3, x, None, None, x.ptr, x.ptr, None, GAMMA, LAM, Guarded(4), None)   # MGYM_OK without a launch
     with pytest.raises(mg.MgymError):
-        e.gae_device(0, x, None, None, x, x, None, GAMMA, LAM, R.Guarded(4), None)          # ... after the argument checks
+        e.gae_device(0, x, None, None, x, x, None, GAMMA, LAM, Guarded(4), None)          # ... after the argument checks
     e.close()
 
 
@@ -206,7 +208,7 @@ def bad_arg(fn, *needles):
 
 def test_errors(env):
     K = 2
-    b = Bufs(K, N)
+    b = Slabs(K, N)
     a = list(b.args())
     IK, IR, ID, IU, IV, ILV, IFV, IG, IL, IADV, IRET = range(11)
 

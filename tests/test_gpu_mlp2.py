@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+from device_buffers import FinalBuf, twin_steps
+from families import KIND
 import mlp2_ref as R
 import mlp_ref as M
 import policy_header as P
@@ -14,8 +16,6 @@ from words import bits, same
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-KINDS = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_continuous": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM, "acrobot": mg.ACROBOT,
-         "lunar_lander": mg.LUNARLANDER}
 ACT_NAME = {R.RELU: "relu", R.TANH_FAST: "tanh_fast"}
 HEAD_NAME = {R.GREEDY: "greedy", R.SAMPLE: "sample", R.GAUSS: "gauss"}
 # what a unit of each observation component is worth to the first layer, sized to the reset observations (CartPole's are within 0.05 of 0, MountainCar's position
@@ -56,7 +56,7 @@ def weights(fam, H1, H2, act, seed=None):
 
 def make(fam, n, auto_reset=True, limit=0, seed=ENV_SEED, **kw):
     extra = {"enable_wind": True} if fam == "lunar_lander" else {}
-    return mg.VecEnv(KINDS[fam], n, seed=seed, auto_reset=auto_reset, max_episode_steps=limit, **extra, **kw)
+    return mg.VecEnv(KIND[fam], n, seed=seed, auto_reset=auto_reset, max_episode_steps=limit, **extra, **kw)
 
 
 def call(env, w, k, act, head, c=0):
@@ -232,30 +232,18 @@ def test_final_observations_under_rollout_mlp2(fam, head):
     env, ref, twin = make(fam, n, True, LIMIT), make(fam, n, True, LIMIT), make(fam, n, False, LIMIT)
     assert same(env.reset(), ref.reset())
     twin.reset()
-    FILL = 0x7FC0BEEF
-    fin = mg.DeviceArray(k * D * n, np.uint32)
-    fin.copy_from(np.full(k * D * n, FILL, np.uint32))
+    fin = FinalBuf(k, D, n)
     env.set_final_obs_out_device(fin, k)
     with pytest.raises(mg.MgymError) as ei:
         call(env, w, k + 1, R.RELU, head)
     assert ei.value.status == mg.envs.L.ERR_BAD_ARG and "mgym_rollout_mlp2" in str(ei.value) and "steps_cap" in str(ei.value)
     acts, gobs, grew, gdone, gtrunc = call(env, w, k, R.RELU, head, 1)
-    got = fin.numpy().reshape(k, D, n)
-    finished = 0
-    for t in range(k):
-        twin.set_state(ref.get_state())
-        twin.set_elapsed_steps(ref.elapsed_steps())
-        a = acts[t]
-        o, r, d, tr = ref.step(a)
-        to, _, td, tt = twin.step(a)
-        for g, e, nm in zip((gobs[t], grew[t], gdone[t], gtrunc[t]), (o, r, d, tr), ("obs", "reward", "done", "truncated")):
+    outs, tobs, tdone, ttrunc = twin_steps(ref, twin, acts)
+    for t, exp in enumerate(outs):
+        for g, e, nm in zip((gobs[t], grew[t], gdone[t], gtrunc[t]), exp, ("obs", "reward", "done", "truncated")):
             assert same(g, e), f"step {t}: {nm}"
-        f = (td | tt).astype(bool)
-        assert np.array_equal(f, (d | tr).astype(bool))
-        assert np.array_equal(got[t][:, f], bits(to)[:, f]), f"step {t}: final observations"
-        assert np.all(got[t][:, ~f] == FILL), f"step {t}: words outside the finished env-steps were written"
-        finished += int(f.sum())
-    assert finished >= n
+    fin.check(tobs, tdone | ttrunc, f"{fam} mlp2")
+    assert (tdone | ttrunc).sum() >= n
     env.set_final_obs_out_device(None)
     env.close(); ref.close(); twin.close()
 
@@ -323,7 +311,7 @@ def test_errors_are_reported_before_any_launch():
 def test_torch_rollout_mlp2_equals_vecenv():
     torch = pytest.importorskip("torch")
     fam, n = "acrobot", 1028
-    te = mg.TorchVecEnv(KINDS[fam], n, seed=31, auto_reset=True, max_episode_steps=LIMIT)
+    te = mg.TorchVecEnv(KIND[fam], n, seed=31, auto_reset=True, max_episode_steps=LIMIT)
     ve = make(fam, n, True, LIMIT, seed=31)
     te.reset()
     ve.reset()

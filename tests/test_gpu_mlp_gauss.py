@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+from families import CLASSIC, FAMILIES, KIND
 import mlp_gauss_ref as R
 import mlp_ref as M
 from mlp_ref import RELU, TANH, packed
@@ -15,8 +16,8 @@ from words import bits, same
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-KINDS = {"mountain_car_continuous": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM}
-DIMS = {fam: M.FAMILIES[fam][0] for fam in KINDS}
+BOX_FAMILIES = [fam for fam in CLASSIC if FAMILIES[fam].box]
+DIMS = {fam: FAMILIES[fam].D for fam in BOX_FAMILIES}
 IN_SCALE = {"mountain_car_continuous": (2.0, 40.0), "pendulum": (1.0, 1.0, 0.3)}
 ACT_NAME = {RELU: "relu", TANH: "tanh"}
 N, K, HALF = 2056, 7, 1028            # 514 lanes: two full blocks of the rollout kernel and a two-lane tail
@@ -31,7 +32,7 @@ def weights(fam, H, act):
 
 
 def make(fam, n=N, base=BASE, limit=LIMIT, auto_reset=True):
-    return mg.VecEnv(KINDS[fam], n, seed=ENV_SEED, auto_reset=auto_reset, max_episode_steps=limit, env_id_base=base)
+    return mg.VecEnv(KIND[fam], n, seed=ENV_SEED, auto_reset=auto_reset, max_episode_steps=limit, env_id_base=base)
 
 
 @pytest.mark.parametrize("H", [1, 5, 64])
@@ -101,8 +102,8 @@ def test_rollout_equals_the_restated_draw_and_a_stepping_loop(fam, act, H):
 def test_torch_rollout_mlp_gauss_equals_vecenv():
     torch = pytest.importorskip("torch")
     fam = "pendulum"
-    te = mg.TorchVecEnv(KINDS[fam], N, seed=31, auto_reset=True, env_id_base=BASE, max_episode_steps=LIMIT)
-    ve = mg.VecEnv(KINDS[fam], N, seed=31, auto_reset=True, env_id_base=BASE, max_episode_steps=LIMIT)
+    te = mg.TorchVecEnv(KIND[fam], N, seed=31, auto_reset=True, env_id_base=BASE, max_episode_steps=LIMIT)
+    ve = mg.VecEnv(KIND[fam], N, seed=31, auto_reset=True, env_id_base=BASE, max_episode_steps=LIMIT)
     te.reset()
     ve.reset()
     w = weights(fam, 5, TANH)
@@ -130,7 +131,7 @@ def test_bad_arguments_are_reported_before_any_launch():
         assert same(env.get_state(), before)
         env.close()
 
-    for fam in KINDS:
+    for fam in BOX_FAMILIES:
         pol = packed(weights(fam, 5, RELU))
         env = make(fam, 8, 0)
         env.reset()

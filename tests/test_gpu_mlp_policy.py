@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+from families import KIND
 from mlp_policy_ref import FAMILIES, RELU, TANH
 from policy_header import GREEDY, check_lib, header_actions
 from mlp_ref import normal_weights, packed
@@ -15,7 +16,6 @@ from words import bits, same
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_continuous": mg.MOUNTAINCAR_CONT, "lunar_lander": mg.LUNARLANDER}
 ACT_NAME = {RELU: "relu", TANH: "tanh"}
 # what a unit of each observation component is worth to the first layer: MountainCar's velocity lives in +-0.07, CartPole's angle in +-0.2
 IN_SCALE = {"cartpole": (2.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "mountain_car_continuous": (2.0, 40.0), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
@@ -41,7 +41,7 @@ def weights(fam, H, act, seed=None):
 
 def make(fam, n, auto_reset, limit=0, seed=ENV_SEED):
     extra = {"enable_wind": True} if fam == "lunar_lander" else {}
-    return mg.VecEnv(KINDS[fam], n, seed=seed, auto_reset=auto_reset, max_episode_steps=limit, **extra)
+    return mg.VecEnv(KIND[fam], n, seed=seed, auto_reset=auto_reset, max_episode_steps=limit, **extra)
 
 
 @pytest.fixture(scope="module")
@@ -235,7 +235,7 @@ def test_captured_mlp_rollout_equals_the_eager_call_and_freezes_the_weights(fam,
 def test_torch_rollout_mlp_equals_vecenv(fam, n):
     torch = pytest.importorskip("torch")
     extra = {"enable_wind": True} if fam == "lunar_lander" else {}
-    te = mg.TorchVecEnv(KINDS[fam], n, seed=31, auto_reset=True, **extra)
+    te = mg.TorchVecEnv(KIND[fam], n, seed=31, auto_reset=True, **extra)
     ve = make(fam, n, True, seed=31)
     te.reset()
     ve.reset()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+from families import KIND
 import mlp_sample_ref as R
 from glibc_f32 import glibc_has_fdlibm_expm1f
 from mlp_policy_ref import FAMILIES, RELU, TANH, n_floats
@@ -15,7 +16,6 @@ from words import same
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not glibc_has_fdlibm_expm1f(), reason="this glibc's expm1f is not the fdlibm one that mg_expm1f restates")]
 
-KINDS = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_continuous": mg.MOUNTAINCAR_CONT, "lunar_lander": mg.LUNARLANDER}
 ACT_NAME = {RELU: "relu", TANH: "tanh"}
 IN_SCALE = {"cartpole": (2.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
 # weight seeds, chosen on the CPU (the oracle stepped under the host-compiled header's scores and the restated draw) so that in every case below that uses
@@ -37,7 +37,7 @@ def weights(fam, H, act):
 
 def make(fam, n, auto_reset, limit=0, seed=ENV_SEED, base=0):
     extra = {"enable_wind": True} if fam == "lunar_lander" else {}
-    return mg.VecEnv(KINDS[fam], n, seed=seed, auto_reset=auto_reset, max_episode_steps=limit, env_id_base=base, **extra)
+    return mg.VecEnv(KIND[fam], n, seed=seed, auto_reset=auto_reset, max_episode_steps=limit, env_id_base=base, **extra)
 
 
 @pytest.fixture(scope="module")
@@ -161,7 +161,7 @@ def test_call_word_sharding_and_the_uniform_count(fam):
 def test_torch_rollout_mlp_sample_equals_vecenv():
     torch = pytest.importorskip("torch")
     fam, n = "cartpole", 1028
-    te = mg.TorchVecEnv(KINDS[fam], n, seed=31, auto_reset=True)
+    te = mg.TorchVecEnv(KIND[fam], n, seed=31, auto_reset=True)
     ve = make(fam, n, True, seed=31)
     te.reset()
     ve.reset()

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
+from device_buffers import FinalBuf
+from families import CLASSIC, KIND
 import mlp_ref as M
 import tanh_fast_ref as T
 from glibc_f32 import tanhf
@@ -21,25 +23,22 @@ F = np.float32
 K, LIMIT = 5, 3
 ENV_SEED, POLICY_SEED, CALL, SIGMA = 17, 0xFA57C0DE77, 9, 0.4
 BASE = (1 << 32) - 8   # the global ids straddle 2^32 (a multiple of 4)
-KINDS = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_continuous": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM,
-         "acrobot": mg.ACROBOT, "lunar_lander": mg.LUNARLANDER}
 IN_SCALE = {"cartpole": (1.0, 1.0, 8.0, 1.0), "mountain_car": (2.0, 40.0), "mountain_car_continuous": (2.0, 40.0), "pendulum": (1.0, 1.0, 0.3),
             "acrobot": (1.0, 1.0, 1.0, 1.0, 0.3, 0.2), "lunar_lander": (2.0, 2.0, 2.0, 2.0, 3.0, 2.0, 2.0, 2.0)}
 FORM_NAME = {T.ARGMAX: "mlp", T.SAMPLE: "mlp_sample", T.GAUSS: "mlp_gauss"}
-CLASSIC = [f for f in KINDS if f != "lunar_lander"]
 ROLLOUT_CASES = [(fam, form, H, n) for fam in CLASSIC for form in ((T.ARGMAX, T.GAUSS) if M.FAMILIES[fam][1] == 1 else (T.ARGMAX, T.SAMPLE))
                  for H, n in ((1, 260), (5, 260), (64, 260), (5, 4))]
 
 
 def weights(fam, H, form):
     D, A, _ = M.FAMILIES[fam]
-    rng = np.random.default_rng(7000 + 100 * list(KINDS).index(fam) + 10 * form + H)
+    rng = np.random.default_rng(7000 + 100 * list(KIND).index(fam) + 10 * form + H)
     return M.normal_weights(rng, D, A, H, IN_SCALE[fam], w2_scale=2.0)
 
 
 def make(fam, n, auto_reset=True, base=BASE, **kw):
     limit = 0 if fam in ("cartpole", "lunar_lander") else LIMIT
-    return mg.VecEnv(KINDS[fam], n, seed=ENV_SEED, auto_reset=auto_reset, max_episode_steps=limit, env_id_base=base, **kw)
+    return mg.VecEnv(KIND[fam], n, seed=ENV_SEED, auto_reset=auto_reset, max_episode_steps=limit, env_id_base=base, **kw)
 
 
 def prepare(env, fam):
@@ -107,9 +106,6 @@ def test_rollout_equals_the_restatement_and_a_stepping_loop(fam, form, H, n):
     env.close(), stepper.close()
 
 
-FILL = 0x7FC0DEAD   # a NaN word no step produces
-
-
 @pytest.mark.parametrize("fam", CLASSIC)
 def test_final_observation_channel(fam):
     """one case per family with mgym_set_final_obs_out set: everything else as with the channel unset, the finals those of a handle without auto-reset"""
@@ -119,17 +115,13 @@ def test_final_observation_channel(fam):
     env, stepper, twin = make(fam, n), make(fam, n), make(fam, n, auto_reset=False)
     prepare(env, fam), prepare(stepper, fam), twin.reset()
     obs = env.observation()
-    fb = mg.DeviceArray((K + 1) * D * n, np.uint32)
-    fb.copy_from(np.full((K + 1) * D * n, FILL, np.uint32))
+    fb = FinalBuf(K + 1, D, n)
     env.set_final_obs_out_device(fb.ptr, K + 1)
     got = call(env, form, w)
     finals = check_against_restatement_and_steps(fam, form, H, got, obs, stepper, twin)
     fin = got[3].astype(bool) | got[4].astype(bool)
-    exp = np.full((K + 1, D, n), FILL, np.uint32)
-    for t in range(K):
-        exp[t][:, fin[t]] = bits(finals[t])[:, fin[t]]
     assert fin.sum() >= 8
-    assert np.array_equal(fb.numpy().reshape(K + 1, D, n), exp)
+    fb.check(finals, fin, fam)
     env.set_final_obs_out_device(None)
     env.close(), stepper.close(), twin.close()
 
@@ -247,7 +239,7 @@ def test_discrete_action_turns_on_the_last_bit_of_the_activation(fam, form):
 def test_torch_vecenv_accepts_tanh_fast_and_equals_vecenv():
     torch = pytest.importorskip("torch")
     fam, H, n = "pendulum", 5, 260
-    te = mg.TorchVecEnv(KINDS[fam], n, seed=ENV_SEED, auto_reset=True, env_id_base=BASE, max_episode_steps=LIMIT)
+    te = mg.TorchVecEnv(KIND[fam], n, seed=ENV_SEED, auto_reset=True, env_id_base=BASE, max_episode_steps=LIMIT)
     ve = make(fam, n)
     te.reset(), ve.reset()
     w = weights(fam, H, T.GAUSS)
@@ -311,7 +303,7 @@ def test_entry_points_a_family_lacks_refuse_activation_3_with_their_existing_mes
         assert same(env.get_state(), before)
         env.close()
     for fam, name in (("cartpole", "CartPole"), ("mountain_car", "MountainCar"), ("acrobot", "Acrobot"), ("lunar_lander", "LunarLander")):
-        env = mg.VecEnv(KINDS[fam], 8, seed=ENV_SEED)
+        env = mg.VecEnv(KIND[fam], 8, seed=ENV_SEED)
         env.reset()
         before = env.get_state()
         bad(env.rollout_mlp_gauss_device, f"mgym_rollout_mlp_gauss: {name} has discrete actions: use mgym_rollout_mlp_sample", packed(weights(fam, 5, T.ARGMAX)), 5, 3, SIGMA, 1, 0, 4)

@@ -6,6 +6,7 @@ import pytest
 
 import modurl_gym_amd as mg
 import pendulum_ref as R
+from device_buffers import CallBuffers
 from words import bits, same
 from modurl_gym_amd import _lib as L
 
@@ -38,25 +39,6 @@ def reference(n, auto_reset):
         for v in (obs0, *[x for s in steps for x in s]):
             v.setflags(write=False)
     return _refs[key]
-
-
-class Buffers:
-    """device buffers of one mgym_step call; the reward buffer optionally `offset` bytes off its 16-byte alignment"""
-
-    def __init__(self, n, offset=0, with_obs=True):
-        self.n, self.offset = n, offset
-        self.act, self.obs = mg.DeviceArray(n, F), (mg.DeviceArray((3, n), F) if with_obs else None)
-        self.rew = mg.DeviceArray(n + 4, F)
-        self.done, self.trunc = mg.DeviceArray(n, np.uint8), mg.DeviceArray(n, np.uint8)
-
-    def step(self, env, a):
-        self.act.copy_from(a)
-        env.step_device(self.act, self.obs, self.rew.ptr + self.offset, self.done, self.trunc)
-        env.sync()
-        return self.read(env)
-
-    def read(self, env):
-        return (self.obs.numpy() if self.obs is not None else env.observation()), self.rew.numpy().view(np.uint8)[self.offset: self.offset + 4 * self.n].view(F).copy(), self.done.numpy(), self.trunc.numpy()
 
 
 def test_spec_and_defaults():
@@ -102,7 +84,7 @@ def test_step_forms_equal_the_reference(form, auto_reset, monkeypatch):
         monkeypatch.setenv("MGYM_CLASSIC_MAX_BLOCKS", max_blocks)   # read when the handle is created
     exp = reference(n, auto_reset)
     env = mg.VecEnv(mg.PENDULUM, n, seed=SEED, auto_reset=auto_reset, max_episode_steps=LIMIT)
-    buf = Buffers(n, offset, with_obs)
+    buf = CallBuffers(n, 3, F, 1, offset, with_obs)
     assert same(env.reset(), exp["obs0"])
     for t, a in enumerate(step_actions(n)):
         got = buf.step(env, a)
@@ -206,15 +188,15 @@ def test_errors():
     before, obs = env.get_state().copy(), env.observation()
     a = np.zeros(n, F)
     a[[0, 1029, 2051]] = np.nan
-    buf = Buffers(n)
-    buf.act.copy_from(a)
-    env.step_device(buf.act, buf.obs, buf.rew, buf.done, buf.trunc)
+    buf = CallBuffers(n, 3, F)
+    buf.put_actions(a)
+    env.step_device(*buf.pointers())
     with pytest.raises(mg.InvalidActionError):
         env.sync()
     after = env.get_state()
     bad = np.isnan(a)
     assert same(after[:, bad], before[:, bad]) and same(env.observation()[:, bad], obs[:, bad]) and not same(after[:, ~bad], before[:, ~bad])
-    o, r, d, t = buf.read(env)
+    o, r, d, t = (x[0] for x in buf.read())
     assert same(o[:, bad], obs[:, bad]) and not r[bad].any() and not d.any() and not t.any()
     env.sync()   # the status was cleared
     # +-inf is inside the Box once clamped: the words of +-2
@@ -240,13 +222,13 @@ def test_captured_step_replays_like_eager_steps():
     env, eager = mg.VecEnv(mg.PENDULUM, n, **kw), mg.VecEnv(mg.PENDULUM, n, **kw)
     env.reset(); eager.reset()
     a = np.random.default_rng(3).uniform(-2.5, 2.5, n).astype(F)
-    buf = Buffers(n)
-    buf.act.copy_from(a)
-    graph = env.graph_capture(lambda: env.step_device(buf.act, buf.obs, buf.rew, buf.done, buf.trunc))   # one stream, one kernel node
+    buf = CallBuffers(n, 3, F)
+    buf.put_actions(a)
+    graph = env.graph_capture(lambda: env.step_device(*buf.pointers()))   # one stream, one kernel node
     for t in range(3):
         env.graph_launch(graph)
         env.sync()
-        assert all(same(g, e) for g, e in zip(buf.read(env), eager.step(a))), f"replay {t}"
+        assert all(same(g, e) for g, e in zip((x[0] for x in buf.read()), eager.step(a))), f"replay {t}"
     env.graph_destroy(graph)
     assert same(env.get_state(), eager.get_state()) and env.episode_count() == eager.episode_count() == n
 

@@ -7,32 +7,26 @@ import numpy as np
 import pytest
 
 import modurl_gym_amd as mg
-from modurl_gym_amd.envs import DeviceArray
+from device_buffers import CallBuffers
+from families import BY_KIND, CLASSIC as CLASSIC_NAMES, KIND
 from words import same
 
 pytestmark = pytest.mark.gpu
 
 L = mg.envs.L
-CLASSIC = {"cartpole": mg.CARTPOLE, "mountain_car": mg.MOUNTAINCAR, "mountain_car_cont": mg.MOUNTAINCAR_CONT, "pendulum": mg.PENDULUM, "acrobot": mg.ACROBOT}
+CLASSIC = {name: KIND[name] for name in CLASSIC_NAMES}
 N, K = 8, 4
 SEEDS = (11, 12)
 
 
 def linear_policy(env):
-    rows = {mg.MOUNTAINCAR: 3, mg.ACROBOT: 3, mg.LUNARLANDER: 4}.get(env.kind, 1)
-    return np.random.default_rng(3).uniform(-1, 1, rows * (env.obs_dim + 1)).astype(np.float32)
+    return np.random.default_rng(3).uniform(-1, 1, BY_KIND[env.kind].lin).astype(np.float32)
 
 
 def mlp_weights(env, H=2):
     D, A = env.mlp_dims()
     r = np.random.default_rng(4)
     return tuple(r.uniform(-1, 1, s).astype(np.float32) for s in ((H, D), (H,), (A, H), (A,)))
-
-
-def outputs(env, n=N):
-    """[K, n] device outputs of a *_device call, the reward with a spare word so that a pointer 4 bytes in still has K * n floats behind it"""
-    return dict(act=DeviceArray((K, n), np.uint32), obs=DeviceArray((K, env.obs_dim, n), np.float32), rew=DeviceArray(K * n + 4, np.float32),
-                done=DeviceArray((K, n), np.uint8), trunc=DeviceArray((K, n), np.uint8))
 
 
 def rejected(call):
@@ -58,8 +52,8 @@ def check_counter(kind, misaligned):
     env.reset()
     env.rollout_uniform_device(SEEDS[0], 0)                      # K = 0: nothing launches
     if misaligned:
-        o = outputs(env)
-        rejected(lambda: env.rollout_uniform_device(SEEDS[0], K, o["act"], o["obs"], o["rew"].ptr + 4, o["done"], o["trunc"]))
+        o = CallBuffers(N, env.obs_dim, np.uint32, K, mis=4)     # the reward pointer 4 bytes off its alignment
+        rejected(lambda: env.rollout_uniform_device(SEEDS[0], K, *o.pointers()))
     other_sources(env)
     got = uniform_twice(env)
     env.close()
@@ -91,7 +85,7 @@ def test_uniform_call_counter_moves_only_with_calls_that_launch(fam):
 @pytest.mark.parametrize("fam", list(CLASSIC))
 def test_every_rejection_names_its_entry_point(fam):
     def entry_points(env, o):
-        out = (o["act"], o["obs"], o["rew"].ptr + 4 if env.n == N else o["rew"], o["done"], o["trunc"])
+        out = o.pointers()
         policy, H = env.pack_mlp(*mlp_weights(env))
         D, A = env.mlp_dims()
         r = np.random.default_rng(5)
@@ -111,7 +105,7 @@ def test_every_rejection_names_its_entry_point(fam):
         env = mg.VecEnv(CLASSIC[fam], n, seed=7)
         env.reset()
         before = env.get_state()
-        for api, call in entry_points(env, outputs(env, n)):
+        for api, call in entry_points(env, CallBuffers(n, env.obs_dim, np.uint32, K, mis=4 if n == N else 0)):
             msg = rejected(call)
             assert msg.startswith(api + ":"), (api, msg)
             assert "multiple of 4" in msg, msg
@@ -150,7 +144,7 @@ def test_abi_rejections_keep_their_order_and_text():
 
     for name, env, lead in every_fault(-1):                      # K < 0 before a NULL policy, a family refusal and env_id_base
         refused(env, name, lead, "K < 0")
-    bufs = [DeviceArray((1, env.obs_dim, N), np.float32) for env in envs]
+    bufs = [mg.DeviceArray((1, env.obs_dim, N), np.float32) for env in envs]
     for env, buf in zip(envs, bufs):
         env.set_final_obs_out_device(buf, 1)
     for name, env, lead in every_fault(2):                       # then the final-observation channel's steps_cap

@@ -11,6 +11,8 @@ import pytest
 import modurl_gym_amd as mg
 import native_build
 from oracle import oracle as ora
+from device_buffers import CallBuffers
+from families import BY_KIND
 from time_limit_ref import TimeLimitRef
 from words import same
 
@@ -23,7 +25,7 @@ NAMES = ("obs", "reward", "done", "truncated")
 POL_D = np.array([0, -1, 0, 0, 0, -1e30, 0, 1, 0], np.float32)
 POL_C = np.array([0, 1e3, 0], np.float32)
 MC_SEED, MC_STEPS, MC_K, RESET_EVERY = 5, 400, 16, 32
-OKIND = {mg.MOUNTAINCAR: ora.MOUNTAINCAR, mg.MOUNTAINCAR_CONT: ora.MOUNTAINCAR_CONT}
+ALL_OFF = (4, 4, 4, 1, 3)   # every caller buffer off its 16-byte alignment: the scalar kernels
 
 
 def mc_policy(kind, obs):
@@ -66,7 +68,7 @@ def mc_expected(kind, n, limit, auto_reset):
     finished (done | truncated) after every RESET_EVERY-th step, so environments run on past their limit in between."""
     key = (kind, n, limit, auto_reset)
     if key not in _mc_expected:
-        w = TimeLimitRef(ora.OracleVec(OKIND[kind], n, seed=MC_SEED), limit, auto_reset)
+        w = TimeLimitRef(ora.OracleVec(BY_KIND[kind].okind, n, seed=MC_SEED), limit, auto_reset)
         obs, steps, elapsed = w.reset(), [], []
         for t in range(MC_STEPS):
             a = mc_policy(kind, obs)
@@ -90,31 +92,6 @@ def mc_classes_ok(kind, limit, kinds):
     if limit == 200:
         return kinds["done_only"] > 0
     return kinds["done_only"] > 0 and kinds["trunc_only"] > 0 and kinds["both"] > 0
-
-
-class Bufs:
-    """caller buffers of one step, 16-byte aligned or deliberately misaligned (the scalar kernels)"""
-
-    def __init__(self, n, obs_dim, adt, unaligned, K=1):
-        self.n, self.obs_dim, self.adt, self.K = n, obs_dim, adt, K
-        off = (4, 4, 4, 1, 3) if unaligned else (0, 0, 0, 0, 0)
-        self.sizes = (4 * K * n, 4 * K * obs_dim * n, 4 * K * n, K * n, K * n)
-        self.arr = [mg.DeviceArray(s + 16, np.uint8) for s in self.sizes]
-        self.ptr = [a.ptr + o for a, o in zip(self.arr, off)]
-        assert all((p % 16 != 0) == bool(unaligned) for p in self.ptr)
-
-    def put_actions(self, a):
-        a = np.ascontiguousarray(a, self.adt)
-        mg.envs._check(mg.envs.L.load().mgym_memcpy_h2d(0, self.ptr[0], a.ctypes.data, a.nbytes))
-
-    def get(self):
-        out = []
-        for p, s, dt, sh in zip(self.ptr[1:], self.sizes[1:], (np.float32, np.float32, np.uint8, np.uint8),
-                                ((self.K, self.obs_dim, self.n), (self.K, self.n), (self.K, self.n), (self.K, self.n))):
-            h = np.empty(sh, dt)
-            mg.envs._check(mg.envs.L.load().mgym_memcpy_d2h(0, h.ctypes.data, p, s))
-            out.append(h[0] if self.K == 1 else h)
-        return out
 
 
 def mc_env(kind, n, limit, auto_reset, **kw):
@@ -144,17 +121,17 @@ def test_mountain_car_steps_and_graph_replays_equal_oracle_plus_wrapper(kind, n,
     for form in ("step", "graph"):
         env = mc_env(kind, n, limit, auto_reset)
         env.reset()
-        b = Bufs(n, 2, adt, unaligned=(n % 4 != 0))
-        graph = env.graph_capture(lambda: env.step_device(*b.ptr)) if form == "graph" else None
+        b = CallBuffers(n, 2, adt, mis=ALL_OFF if n % 4 else (0,) * 5)
+        graph = env.graph_capture(lambda: env.step_device(*b.pointers())) if form == "graph" else None
         for t, (a, eo, er, ed, et) in enumerate(steps):
             b.put_actions(a)
             if graph is not None:
                 env.graph_launch(graph)
             else:
-                env.step_device(*b.ptr)
+                env.step_device(*b.pointers())
             env.sync()
-            for g, e, nm in zip(b.get(), (eo, er, ed, et), NAMES):
-                assert same(g, e), f"{form} step {t}: {nm}"
+            for g, e, nm in zip(b.read(), (eo, er, ed, et), NAMES):
+                assert same(g[0], e), f"{form} step {t}: {nm}"
             caller_reset(env, t, auto_reset, ed, et)
             if t in (6, 99, 250):
                 assert np.array_equal(env.elapsed_steps(), elapsed[t]), f"{form} step {t}: elapsed"
@@ -178,14 +155,14 @@ def test_mountain_car_rollouts_equal_oracle_plus_wrapper(kind, n, limit, auto_re
             continue
         env = mc_env(kind, n, limit, auto_reset)
         env.reset()
-        b = Bufs(n, 2, adt, unaligned=(n % 4 != 0), K=K)
+        b = CallBuffers(n, 2, adt, K, mis=ALL_OFF if n % 4 else (0,) * 5)
         for c in range(MC_STEPS // K):
             exp = steps[c * K:(c + 1) * K]
             if form == "table":
                 b.put_actions(np.stack([s[0] for s in exp]))
-                env.rollout_device(b.ptr[0], K, *b.ptr[1:])
+                env.rollout_device(b.pointers()[0], K, *b.pointers()[1:])
                 env.sync()
-                got = b.get()
+                got = b.read()
             else:
                 acts, *got = env.rollout_linear(POL_C if kind == mg.MOUNTAINCAR_CONT else POL_D, K)
                 assert same(acts.view(adt), np.stack([s[0] for s in exp])), f"{form} call {c}: actions"
@@ -210,7 +187,7 @@ def test_mountain_car_uniform_rollout_equals_oracle_driven_by_the_same_draws(kin
     n, K, base, seed = 4096, 64, 8192, 0x1234ABCD5678
     cont = kind == mg.MOUNTAINCAR_CONT
     env = mg.VecEnv(kind, n, seed=19, env_id_base=base, auto_reset=auto_reset, max_episode_steps=limit)
-    w = TimeLimitRef(ora.OracleVec(OKIND[kind], n, seed=19, env_id_base=base), limit, auto_reset)
+    w = TimeLimitRef(ora.OracleVec(BY_KIND[kind].okind, n, seed=19, env_id_base=base), limit, auto_reset)
     env.reset(), w.reset()
     for call in range(2):
         acts, obs, rew, done, trunc = env.rollout_uniform(seed, K)
@@ -488,7 +465,7 @@ def test_mountain_car_checkpoint_carries_the_elapsed_count(kind):
     The blob stays 3 columns and mgym_set_state alone starts the count at 0; mgym_set_elapsed_steps clamps to 65535."""
     n, limit = 4096, mc_limit(kind, 100, 4096)
     a_env, b_env = mc_env(kind, n, limit, True), mc_env(kind, n, limit, True)
-    w = TimeLimitRef(ora.OracleVec(OKIND[kind], n, seed=MC_SEED), limit, True)
+    w = TimeLimitRef(ora.OracleVec(BY_KIND[kind].okind, n, seed=MC_SEED), limit, True)
     obs = a_env.reset()
     assert same(obs, w.reset())
     for t in range(150):

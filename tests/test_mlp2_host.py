@@ -13,7 +13,7 @@ from words import words_of
 F = np.float32
 ACTS = (R.RELU, R.TANH_FAST)
 # the observation box each family's observations are drawn over (an unbounded component: a few units of it)
-BOX = {"cartpole": ((-4.8, 4.8), (-5, 5), (-0.42, 0.42), (-5, 5)), "mountain_car": ((-1.2, 0.6), (-0.07, 0.07)),
+OBS_BOX = {"cartpole": ((-4.8, 4.8), (-5, 5), (-0.42, 0.42), (-5, 5)), "mountain_car": ((-1.2, 0.6), (-0.07, 0.07)),
        "mountain_car_continuous": ((-1.2, 0.6), (-0.07, 0.07)), "pendulum": ((-1, 1), (-1, 1), (-8, 8)),
        "acrobot": ((-1, 1), (-1, 1), (-1, 1), (-1, 1), (-12.57, 12.57), (-28.27, 28.27)),
        "lunar_lander": ((-2.5, 2.5), (-2.5, 2.5), (-10, 10), (-10, 10), (-6.28, 6.28), (-10, 10), (0, 1), (0, 1))}
@@ -22,7 +22,7 @@ NAN_COLUMNS = 4   # the last columns of observations(): a NaN in one component
 
 def observations(rng, fam, n=24):
     """[D, n] over the family's box; then columns with +0, -0 and a denormal in one component each, and NAN_COLUMNS columns with a NaN in one component"""
-    lo, hi = np.array(BOX[fam], np.float64).T
+    lo, hi = np.array(OBS_BOX[fam], np.float64).T
     D = len(lo)
     o = rng.uniform(lo[:, None], hi[:, None], (D, n)).astype(F)
     for col, v in zip(range(n - NAN_COLUMNS - 6, n - NAN_COLUMNS), (0.0, -0.0, 1e-40, -1e-40, 0.0, -0.0)):
@@ -33,7 +33,7 @@ def observations(rng, fam, n=24):
 
 
 def in_scale(fam):
-    return [2.0 / (hi - lo) for lo, hi in BOX[fam]]
+    return [2.0 / (hi - lo) for lo, hi in OBS_BOX[fam]]
 
 
 def same_words(got, exp):

@@ -13,7 +13,7 @@ from policy_header import GREEDY, check_program, header_actions
 
 FAMILIES = {fam: M.FAMILIES[fam] for fam in ("cartpole", "mountain_car", "mountain_car_continuous", "lunar_lander")}   # the four families of this file's cases (policy_check.cpp knows all six)
 HIDDEN = (1, 2, 7, 32, 64)
-KINDS = (("ordinary", 40), ("ties", 15), ("zeros", 15), ("huge", 15), ("inf", 15))
+CASE_KINDS = (("ordinary", 40), ("ties", 15), ("zeros", 15), ("huge", 15), ("inf", 15))
 
 
 @pytest.fixture(scope="module")
@@ -63,7 +63,7 @@ def cases():
     for fam, (D, A, cont) in FAMILIES.items():
         for act in (RELU, TANH):
             for H in HIDDEN:
-                for kind, count in KINDS:
+                for kind, count in CASE_KINDS:
                     for _ in range(count):
                         pol, o = make_case(rng, kind, D, A, H)
                         out.append((kind, D, A, cont, act, H, pol, o))

@@ -1,12 +1,16 @@
 """The support layer the other tests stand on: philox_ref's Philox against the published vectors, the two meanings of word equality in words.py,
-glibc_f32.fmaf's single rounding and broadcasting, and native_build's one compilation per process.  No GPU."""
+glibc_f32.fmaf's single rounding and broadcasting, native_build's one compilation per process, the family table of families.py against the library's spec,
+and the buffers of device_buffers.py on host memory: each stray write they exist to catch is caught.  No GPU."""
 import os
 
 import numpy as np
+import pytest
 
+import device_buffers as B
 import glibc_f32
 import native_build
 import philox_ref
+from families import FAMILIES
 from words import same, same_words
 
 F = np.float32
@@ -83,3 +87,108 @@ def test_each_artefact_is_compiled_once_per_process():
     with open(other, "rb") as f:
         assert other == stale and f.read(4) == b"\x7fELF"
     assert os.stat(first).st_mtime_ns == mtime
+
+
+# ---- families.py and device_buffers.py: the table is the library's, and each checker catches what it is there to catch ------------------------
+def test_family_table_agrees_with_the_library_spec():
+    import modurl_gym_amd as mg
+    for name, f in FAMILIES.items():
+        s = mg.get_spec(f.kind)
+        assert (s.obs_dim, s.n_actions, s.action_is_float, s.state_cols) == (f.D, f.n_actions, int(f.box is not None), f.state_cols), name
+        assert (s.action_low, s.action_high) == (f.box or (0.0, 0.0)), name
+        assert f.A == (1 if f.box else f.n_actions) and (f.f32_cols is None or f.f32_cols < f.state_cols), name
+
+
+class HostArray:
+    """host memory behind mg.DeviceArray's ptr, copy_from and numpy; the pointer is `skew` bytes past a 256-byte boundary (a device allocation: 0)"""
+    skew = 0
+
+    def __init__(self, shape, dtype):
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        self.raw = np.zeros(n + 512, np.uint8)
+        start = -self.raw.ctypes.data % 256 + self.skew
+        self.a = self.raw[start: start + n].view(dtype).reshape(shape)
+        self.ptr = self.raw.ctypes.data + start
+
+    def copy_from(self, host):
+        self.a[...] = np.ascontiguousarray(host, self.a.dtype).reshape(self.a.shape)
+
+    def numpy(self):
+        return self.a.copy()
+
+
+@pytest.mark.parametrize("mis", [0, 1])
+def test_guarded_sees_a_write_to_either_guard_and_to_the_payload(mis):
+    words = 10
+    for fill in (B.FILL, 0x7FC0BEEF):
+        for at, held, same_bytes in ((None, True, True), (2 + mis, False, False), (4 + mis + words + 3, False, False), (4 + mis + 5, True, False)):
+            g = B.Guarded(words, mis, fill=fill, alloc=HostArray)
+            assert g.ptr % 16 == 4 * mis and (g.payload(words) == fill).all()
+            if at is not None:
+                g.dev.a[at] ^= 1
+            assert g.guards_hold() == held and g.untouched() == same_bytes, (fill, at)
+    g = B.Guarded(words, mis, np.arange(words, dtype=F), alloc=HostArray)
+    assert same(g.payload(words, F), np.arange(words, dtype=F)) and g.guards_hold() and g.untouched()
+
+
+@pytest.mark.parametrize("mis", [0, 1])
+def test_final_buf_check_fails_on_each_kind_of_stray_write(mis):
+    cap, D, n = 2, 3, 8
+    rng = np.random.default_rng(5)
+    finals = rng.normal(0, 1, (cap, D, n)).astype(F)
+    finished = rng.random((cap, n)) < 0.4
+    finished[0, 0], finished[1, 7], finished[0, 1] = True, True, False
+
+    def written():
+        fb = B.FinalBuf(cap, D, n, mis, alloc=HostArray)
+        body = fb.dev.a[fb.off: fb.off + fb.words].reshape(cap, D, n)
+        for t in range(cap):
+            body[t][:, finished[t]] = finals[t][:, finished[t]].view(np.uint32)
+        return fb, body
+
+    fb, body = written()
+    fb.check(finals, finished, "exact")
+    body[0, 2, 1] = 0x3F800000            # an unfinished env-step
+    with pytest.raises(AssertionError, match="1 words outside the finished env-steps were written"):
+        fb.check(finals, finished, "stray")
+    fb, body = written()
+    body[1, 0, 7] ^= 1                    # a finished word, one bit off
+    for eq in (same, same_words):
+        with pytest.raises(AssertionError, match="1 of .* final words differ"):
+            fb.check(finals, finished, "bit", eq)
+    for at in (3 + mis, fb.off + fb.words):
+        fb, _ = written()
+        fb.dev.a[at] = 0
+        with pytest.raises(AssertionError, match="a guard word was written"):
+            fb.check(finals, finished, "guard")
+    fb, body = written()                  # NaNs are equal as a class only where the caller says so
+    body[0, 0, 0], finals.view(np.uint32)[0, 0, 0] = 0x7FC00001, 0x7FC00002
+    fb.check(finals, finished, "nan class", same_words)
+    with pytest.raises(AssertionError, match="final words differ"):
+        fb.check(finals, finished, "nan bits")
+
+
+def test_call_buffers_hand_out_the_alignment_asked_for_and_read_what_lies_there():
+    for K, n, D, mis in ((1, 5, 3, 0), (3, 5, 3, 0), (1, 5, 3, (4, 4, 4, 1, 3)), (3, 5, 3, (4, 4, 4, 1, 3)), (3, 8, 2, 4)):
+        b = B.CallBuffers(n, D, F, K, mis, alloc=HostArray)
+        off = (0, 0, mis, 0, 0) if isinstance(mis, int) else mis
+        assert [p % 16 for p in b.pointers()] == list(off)
+        rng = np.random.default_rng(K + n)
+        placed = []
+        for a, o, shape, dt in zip(b.arr, off, b.shapes, b.dtypes):   # words put where the pointers point, by hand
+            v = rng.integers(0, 256, int(np.prod(shape)) * dt.itemsize).astype(np.uint8)
+            a.raw[:] = 0xEE
+            a.a[o: o + v.size] = v
+            placed.append(v.view(dt).reshape(shape))
+        assert same(b.actions(), placed[0]) and all(same(g, e) for g, e in zip(b.read(), placed[1:]))
+        acts = rng.normal(0, 1, (K, n)).astype(F)
+        b.put_actions(acts)
+        assert same(b.actions(), acts) and same(b.arr[0].a[off[0]: off[0] + acts.nbytes].view(F), acts.ravel())
+        if K == 3:   # the slabs of step 2 start two steps' worth of bytes in
+            assert [q - p for p, q in zip(b.pointers(), b.pointers(2))] == [8 * n, 8 * D * n, 8 * n, 2 * n, 2 * n]
+    b = B.CallBuffers(5, 3, np.uint32, 2, 4, with_obs=False, alloc=HostArray)
+    assert b.pointers()[1] is None and b.pointers(1)[1] is None and b.read()[0] is None and b.read()[1].shape == (2, 5)
+    skewed = type("Skewed", (HostArray,), dict(skew=12))
+    for mis in ((0, 0, 0, 4, 0), 0):   # 12 + 4: the done pointer comes out aligned after all; 12: nothing is aligned
+        with pytest.raises(AssertionError, match="alignment"):
+            B.CallBuffers(8, 2, F, mis=mis, alloc=skewed)

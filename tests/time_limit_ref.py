@@ -6,8 +6,9 @@ import numpy as np
 
 
 class TimeLimitRef:
-    def __init__(self, ref, limit, auto_reset, nthreads=1):
-        self.ref, self.limit, self.auto_reset, self.nthreads = ref, int(limit), bool(auto_reset), nthreads
+    def __init__(self, ref, limit, auto_reset, nthreads=1, own_truncation=False):
+        """own_truncation: the oracle truncates by itself (CartPole at 500 steps) and its flag is OR-ed in; otherwise it is asserted absent"""
+        self.ref, self.limit, self.auto_reset, self.nthreads, self.own_truncation = ref, int(limit), bool(auto_reset), nthreads, own_truncation
         self.elapsed = np.zeros(ref.n, np.int64)
         self.finished = 0                     # steps with either flag (what mgym_episode_count counts)
         self.kinds = {"done_only": 0, "trunc_only": 0, "both": 0}
@@ -21,10 +22,10 @@ class TimeLimitRef:
         return obs
 
     def step(self, actions):
-        obs, rew, done, trunc = self.ref.step(actions, nthreads=self.nthreads)
-        assert not trunc.any()                # the oracle itself (the reference's rule) never truncates these families
+        obs, rew, done, own = self.ref.step(actions, nthreads=self.nthreads)
+        assert self.own_truncation or not own.any()   # the oracle itself (the reference's rule) never truncates the other families
         self.elapsed += 1
-        trunc = ((self.elapsed >= self.limit) & (self.limit != 0)).astype(np.uint8)
+        trunc = ((self.elapsed >= self.limit) & (self.limit != 0)).astype(np.uint8) | own
         d, t = done.astype(bool), trunc.astype(bool)
         self.kinds["done_only"] += int((d & ~t).sum())
         self.kinds["trunc_only"] += int((~d & t).sum())
