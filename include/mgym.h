@@ -251,7 +251,7 @@ int mgym_default_config(int kind, mgym_config *cfg);
  *   LunarLander: any n_envs; mgym_rollout's persistent launch needs n_envs <= 16 777 215 and its records (1152 bytes per environment, n_envs rounded up to
  *     a multiple of 1024) below 4 GiB, that is at most 3 727 360 environments; beyond that it runs as K steps (mgym_get_info: rollout=k_steps).  (By default the engine
  *     chooses K steps long before that bound: see mgym_rollout.)
- * Every [K][n_envs] buffer of the rollout entry points, of mgym_set_final_obs_out, mgym_gae and mgym_episode_returns may exceed 4 GiB: rows are addressed
+ * Every [K][n_envs] buffer of the rollout entry points, of mgym_set_final_obs_out, mgym_gae, mgym_value_mlp and mgym_episode_returns may exceed 4 GiB: rows are addressed
  * in 64 bits.  The one exception is CartPole's fused rollout kernel (mgym_rollout below). */
 int mgym_create(const mgym_config *cfg, mgym_env **out);
 int mgym_destroy(mgym_env *env);
@@ -576,6 +576,48 @@ int mgym_set_final_obs_out(mgym_env *env, float *final_obs_out, int32_t steps_ca
  * the caller's error and undefined).  n_envs == 0 returns MGYM_OK without a launch. */
 int mgym_gae(mgym_env *env, int32_t K, const float *reward, const uint8_t *done, const uint8_t *trunc, const float *value, const float *last_value,
              const float *final_value, float gamma, float lambda, float *adv_out, float *ret_out);
+
+/* A critic's values over the buffers of a K-step rollout: exactly the three inputs of mgym_gae that nothing else in the engine produces.  A pure function
+ * of its arguments like mgym_gae: the handle supplies the device, the stream, n_envs and D = obs_dim of its kind (2, 3, 4, 6 or 8); every kind is accepted, no
+ * state of the handle is read or written (a LunarLander handle that was never reset is accepted), nothing is allocated or synchronised, the call is capturable.
+ * critic is a HOST pointer, read during the call, in nn.Linear order; 1 <= H1 = hidden1 <= 64:
+ *   hidden2 == 0   one hidden layer:   W1[H1][D], b1[H1], W2[1][H1], b2[1]                                   the words of mgym_rollout_mlp with A = 1
+ *   hidden2 >= 1   two hidden layers:  W1[H1][D], b1[H1], W2[H2][H1], b2[H2], W3[1][H2], b3[1], H2 <= 64     the words of mgym_rollout_mlp2 with A = 1
+ * V(o) is that text's one score s_0 for the observation o: every link one correctly rounded f32 fmaf, in ascending order from the bias, nothing else fused,
+ * no chain padded (the words of mlp_scores<D, 1, ACT, N> of modurl_gym_amd/csrc/mlp_policy.h and mlp2_policy.h; this entry point adds no arithmetic definition).
+ * activation: MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST with one hidden layer; with two MGYM_ACT_TANH is refused, as in mgym_rollout_mlp2.
+ * All other pointers are DEVICE pointers.
+ *   obs_first         [D][n_envs]     dense: the observation held before step 0 of the rollout
+ *   obs               [K][D][n_envs]  the rollout's obs_out
+ *   final_obs         [K][D][n_envs]  the buffer of mgym_set_final_obs_out, or NULL
+ *   done, trunc       [K][n_envs]     the rollout's flags; they select the final values and are ignored when final_obs is NULL; done may be NULL = all 0
+ *   value_out         [K][n_envs]     value_out[0][i] = V(obs_first[:, i]);  value_out[t][i] = V(obs[t-1][:, i]) for t = 1 .. K-1
+ *   last_value_out    [n_envs]        last_value_out[i] = V(obs[K-1][:, i])
+ *   final_value_out   [K][n_envs]     final_value_out[t][i] = V(final_obs[t][:, i]), written ONLY where trunc[t][i] != 0 && (done == NULL || done[t][i] == 0)
+ * (modurl_gym_amd/csrc/value.h is this mapping as the kernels and a g++ build compile it.)
+ *  - value_out and last_value_out are mgym_gae's value and last_value: under MGYM_FLAG_AUTO_RESET obs holds the reset observation where an episode ended,
+ *    which is the observation the policy acts on next, so it is the right input.
+ *  - The set where final_value_out is written is the set mgym_gae selects.  No other word of final_value_out is written, and no word of final_obs outside
+ *    that set is read into any result: a NaN there reaches nothing (the kernels load final_obs only where it is selected).
+ *  - final_obs, final_value_out and trunc are either all non-NULL or the first two are NULL (LunarLander callers pass them NULL: it has no final-observation
+ *    channel yet).
+ * The one-layer critic travels by value as a kernel argument.  The two-layer critic goes through a device pack the handle owns from mgym_create — a second
+ * one, not the actor's of mgym_rollout_mlp2 — which the call fills on the stream ahead of its launches as mgym_rollout_mlp2 does: consecutive calls on one
+ * stream each find their own weights, a captured graph that holds a mgym_rollout_mlp2 and a mgym_value_mlp replays each with its own, and under capture the
+ * weights are frozen.
+ * The dense values: four environments per lane and 16-byte accesses when n_envs is a multiple of 4 and below 2^30 and the float pointers are 16-byte aligned,
+ * otherwise one environment per lane; the [K][D][n_envs] buffers may exceed 4 GiB.  The final values: a second launch whose cost follows the number of
+ * selected env-steps (the flag rows are walked, the selected (t, i) compacted per wave, and only those evaluated); no atomics, no run-dependent order.
+ * The words are the same in every form.
+ * MGYM_ERR_BAD_ARG before any launch, the message starting "mgym_value_mlp:" and naming the argument: K < 1; a NULL critic, obs_first, obs, value_out or
+ * last_value_out; hidden1 outside 1 .. 64; hidden2 outside 0 .. 64; an unknown activation (2 is unknown), or MGYM_ACT_TANH with hidden2 >= 1; one of final_obs
+ * and final_value_out without the other, or either of them without trunc; a float pointer that is not 4-byte aligned; an output pointer equal to an input
+ * pointer or to another output (overlap beyond pointer equality is the caller's error and undefined).  n_envs == 0 returns MGYM_OK after the checks
+ * without a launch. */
+int mgym_value_mlp(mgym_env *env, const float *critic, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t K,
+                   const float *obs_first, const float *obs, const float *final_obs,
+                   const uint8_t *done, const uint8_t *trunc,
+                   float *value_out, float *last_value_out, float *final_value_out);
 
 /* The return and length of every episode that ends inside a K-step rollout: one launch, a forward scan per environment whose carry the CALLER owns, so
  * that episodes span calls.  A pure function of its arguments like mgym_gae (every kind, no handle state, capturable); all pointers are DEVICE pointers.

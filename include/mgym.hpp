@@ -108,6 +108,13 @@ class VecGym {
              float gamma, float lambda, float* adv_out, float* ret_out) {
         check(mgym_gae(env_, K, reward, done, trunc, value, last_value, final_value, gamma, lambda, adv_out, ret_out));
     }
+    // A critic's values over a rollout's buffers, in the shapes gae() takes (mgym_value_mlp): critic is a HOST pointer in nn.Linear order, one hidden layer
+    // (hidden2 == 0) or two; the rest are device pointers.  final_obs / final_value_out / trunc all set or the first two nullptr; done may be nullptr.
+    // final_value_out is written only where trunc && !done, and final_obs is read only there
+    void value_mlp(const float* critic, int hidden1, int hidden2, int activation, int K, const float* obs_first, const float* obs, const float* final_obs,
+                   const uint8_t* done, const uint8_t* trunc, float* value_out, float* last_value_out, float* final_value_out) {
+        check(mgym_value_mlp(env_, critic, hidden1, hidden2, activation, K, obs_first, obs, final_obs, done, trunc, value_out, last_value_out, final_value_out));
+    }
     // The return and length of the episodes that end inside a rollout (mgym_episode_returns): ep_return / ep_length [n_envs] are the caller's carry of the
     // running episodes (read and written); return_out / length_out [K][n_envs] (or nullptr) are written only where done | trunc
     void episode_returns(int K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length, float* return_out,

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "gae.h"
 #include "time_limit.h"
+#include "value.h"
 
 namespace mgym {
 
@@ -60,16 +61,18 @@ __global__ void __launch_bounds__(256) mlp2_pack_kernel(Mlp2Slice slice, float* 
     for (int i = threadIdx.x; i < count; i += blockDim.x) dst[i] = slice.w[i];
 }
 
-int mgym::Env::mlp2_store(const PolicyCall& call, int D, int A) {
+int mgym::Env::mlp2_store(const PolicyCall& call, int D, int A) { return mlp2_store_to(mlp2_dev, call.weights, D, A, call.hidden, call.hidden2); }
+
+int mgym::Env::mlp2_store_to(float* dst, const float* weights, int D, int A, int H1, int H2) {
     static_assert(kMlp2PackMax == 5192, "the pack of mlp2_policy.h at its largest");
     float pack[kMlp2PackMax];
-    mlp2_pack(call.weights, D, A, call.hidden, call.hidden2, pack);
-    const int total = mlp2_pack_floats(D, call.hidden, call.hidden2);
+    mlp2_pack(weights, D, A, H1, H2, pack);
+    const int total = mlp2_pack_floats(D, H1, H2);
     for (int at = 0; at < total; at += kMlp2Slice) {
         Mlp2Slice slice{};   // (value-initialised: the words past `count` travel in the launch and in a captured graph node too)
         const int count = total - at < kMlp2Slice ? total - at : kMlp2Slice;
         memcpy(slice.w, pack + at, (size_t)count * sizeof(float));
-        hipLaunchKernelGGL(mlp2_pack_kernel, dim3(1), dim3(256), 0, stream, slice, mlp2_dev + at, count);
+        hipLaunchKernelGGL(mlp2_pack_kernel, dim3(1), dim3(256), 0, stream, slice, dst + at, count);
         MGYM_HIP(hipGetLastError());
     }
     return MGYM_OK;
@@ -214,6 +217,7 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
         if (hipHostMalloc((void**)&impl->h_done, kDoneShards * sizeof(unsigned long long), 0) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipHostMalloc failed"); break; }
         if (hipMemsetAsync(impl->d_done, 0, kDoneShards * sizeof(unsigned long long), impl->stream) != hipSuccess) { st = MGYM_ERR_HIP; break; }
         if (hipMalloc((void**)&impl->mlp2_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
+        if (hipMalloc((void**)&impl->value_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipEventCreate(&impl->ev0) != hipSuccess || hipEventCreate(&impl->ev1) != hipSuccess) { st = MGYM_ERR_HIP; break; }
         st = impl->init();
         if (st != MGYM_OK) break;
@@ -242,6 +246,7 @@ int mgym_destroy(mgym_env* env) {
         if (e->d_done) (void)hipFree(e->d_done);
         if (e->h_done) (void)hipHostFree(e->h_done);
         if (e->mlp2_dev) (void)hipFree(e->mlp2_dev);
+        if (e->value_dev) (void)hipFree(e->value_dev);
         hipStream_t s = e->own_stream ? e->stream : nullptr;
         delete e;
         if (s) (void)hipStreamDestroy(s);
@@ -443,6 +448,45 @@ int mgym_gae(mgym_env* env, int32_t K, const float* reward, const uint8_t* done,
             if (f.out && f.p && f.p == g.p) return bad_arg((std::string("mgym_gae: ") + f.name + " is the same pointer as " + g.name).c_str());
     if (e->n == 0) return MGYM_OK;
     return gae_launch(e->stream, GaeCall{e->n, K, reward, done, trunc, value, last_value, final_value, gamma, gamma * lambda, adv_out, ret_out});
+}
+
+int mgym_value_mlp(mgym_env* env, const float* critic, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t K, const float* obs_first, const float* obs,
+                   const float* final_obs, const uint8_t* done, const uint8_t* trunc, float* value_out, float* last_value_out, float* final_value_out) {
+    ENV_OR_FAIL(env);
+    auto bad = [](const std::string& what) { return bad_arg(("mgym_value_mlp: " + what).c_str()); };
+    if (K < 1) return bad("K must be at least 1");
+    if (!critic) return bad("critic is NULL");
+    if (!obs_first) return bad("obs_first is NULL");
+    if (!obs) return bad("obs is NULL");
+    if (!value_out) return bad("value_out is NULL");
+    if (!last_value_out) return bad("last_value_out is NULL");
+    if (hidden1 < 1 || hidden1 > 64) return bad("hidden1 must be between 1 and 64");
+    if (hidden2 < 0 || hidden2 > 64) return bad("hidden2 must be between 0 (one hidden layer) and 64");
+    if (hidden2 >= 1 && activation == MGYM_ACT_TANH)
+        return bad("activation MGYM_ACT_TANH is not offered with two hidden layers (as in mgym_rollout_mlp2): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
+    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH && activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
+        return bad(hidden2 >= 1 ? "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST" : "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    if (final_obs && !final_value_out) return bad("final_value_out is NULL while final_obs is not");
+    if (final_value_out && !final_obs) return bad("final_obs is NULL while final_value_out is not");
+    if (final_obs && !trunc) return bad("trunc is NULL while final_obs and final_value_out are not");
+    if (!final_obs) done = trunc = nullptr;   // ignored without the final arguments
+    const struct { const char* name; const float* p; bool out; } fp[] = {{"obs_first", obs_first, false}, {"obs", obs, false}, {"final_obs", final_obs, false},
+                                                                         {"value_out", value_out, true}, {"last_value_out", last_value_out, true},
+                                                                         {"final_value_out", final_value_out, true}};
+    for (const auto& f : fp)
+        if (!aligned(f.p, 4)) return bad(std::string(f.name) + " must be 4-byte aligned");
+    const struct { const char* name; const void* p; } in[] = {{"obs_first", obs_first}, {"obs", obs}, {"final_obs", final_obs}, {"done", done}, {"trunc", trunc}};
+    for (const auto& f : fp) {
+        if (!f.out || !f.p) continue;
+        for (const auto& g : in)
+            if (f.p == g.p) return bad(std::string(f.name) + " is the same pointer as " + g.name);
+        for (const auto& g : fp)
+            if (g.out && g.p == f.p && g.name != f.name) return bad(std::string(f.name) + " is the same pointer as " + g.name);
+    }
+    if (e->n == 0) return MGYM_OK;
+    if (hidden2 >= 1) { if (const int st = e->mlp2_store_to(e->value_dev, critic, e->obs_dim, 1, hidden1, hidden2)) return st; }
+    return value_launch(e->stream, ValueCall{e->n, K, obs_first, obs, final_obs, done, trunc, value_out, last_value_out, final_value_out}, e->obs_dim, critic, hidden1,
+                        hidden2, activation, e->value_dev);
 }
 
 int mgym_episode_returns(mgym_env* env, int32_t K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length,

@@ -103,6 +103,10 @@ struct Env {
     // array is read during the call only, a captured graph carries the weights, and consecutive calls on one stream each find their own.
     float* mlp2_dev = nullptr;
     int mlp2_store(const PolicyCall& call, int D, int A);
+    // mgym_value_mlp: a second pack of the same size for a two-hidden-layer critic, so that an actor's and a critic's weights never share a buffer (a captured
+    // graph that holds a mgym_rollout_mlp2 and a mgym_value_mlp replays each with its own); mlp2_store_to is the store of both
+    float* value_dev = nullptr;
+    int mlp2_store_to(float* dst, const float* weights, int D, int A, int H1, int H2);
     template <int D, int A>
     Mlp2Net<D, A> mlp2_net(const PolicyCall& call) const { return Mlp2Net<D, A>{mlp2_dev, call.hidden, call.hidden2, call.sigma}; }
     uint32_t uniform_calls = 0;  // mgym_rollout_uniform calls that launched so far (Philox counter word of the policy stream)

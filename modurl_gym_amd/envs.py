@@ -389,6 +389,48 @@ class VecEnv:
         self.sync()
         return tuple(x.numpy().reshape(-1)[: K * n].reshape(K, n) for x in (adv, ret))
 
+    def pack_critic(self, weights):
+        """nn.Linear-layout critic weights, (w1 [H1, D], b1 [H1], w2 [1, H1], b2 [1]) or (w1, b1, w2 [H2, H1], b2 [H2], w3 [1, H2], b3 [1]) -> (critic, H1, H2):
+        the float32 words mgym_value_mlp reads, H2 = 0 for one hidden layer.  Shapes are checked against the family (PolicyShapeError); the widths by the engine."""
+        D = self.obs_dim
+        ws = [np.asarray(x, np.float32) for x in weights]
+        if len(ws) not in (4, 6):
+            raise PolicyShapeError(L.ERR_BAD_ARG, f"a critic is (w1, b1, w2, b2) or (w1, b1, w2, b2, w3, b3); got {len(ws)} arrays")
+        H1 = ws[0].shape[0] if ws[0].ndim == 2 else -1
+        H2 = (ws[2].shape[0] if ws[2].ndim == 2 else -1) if len(ws) == 6 else 0
+        want = [(H1, D), (H1,), (1, H1), (1,)] if len(ws) == 4 else [(H1, D), (H1,), (H2, H1), (H2,), (1, H2), (1,)]
+        if [w.shape for w in ws] != want:
+            raise PolicyShapeError(L.ERR_BAD_ARG, f"{KIND_NAMES[self.kind]} takes a critic of shapes {want} (H1, H2 free); got {[w.shape for w in ws]}")
+        return np.concatenate([w.ravel() for w in ws]).astype(np.float32), H1, H2
+
+    def value_mlp_device(self, critic, hidden1, hidden2, activation, K, obs_first, obs, final_obs=None, done=None, trunc=None, value_out=None, last_value_out=None,
+                         final_value_out=None):
+        """mgym_value_mlp on device buffers (pointers, DeviceArrays or tensors): `critic` = the packed host floats of pack_critic (or None, which the engine
+        rejects), hidden2 = 0 for one hidden layer; obs_first [D, n], obs [K, D, n], final_obs [K, D, n] or None, done / trunc uint8 [K, n] or None; value_out
+        [K, n], last_value_out [n], final_value_out [K, n] or None — written only where trunc && !done, final_obs read only there.  The three outputs are
+        gae_device's value, last_value and final_value.  On the env's stream, nothing synchronised.  A critic of the wrong length raises PolicyShapeError."""
+        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
+        D, h1, h2 = self.obs_dim, int(hidden1), int(hidden2)
+        want = None
+        if 1 <= h1 <= 64 and 0 <= h2 <= 64:
+            want = h1 * (D + 1) + (h2 * (h1 + 1) + h2 + 1 if h2 else h1 + 1)
+        pol = None if critic is None else _policy_floats(critic, want, f"hidden1 = {h1}, hidden2 = {h2}")
+        _check(self._lib.mgym_value_mlp(self._h, _fptr(pol), h1, h2, act, int(K), _ptr(obs_first), _ptr(obs), _ptr(final_obs), _ptr(done), _ptr(trunc),
+                                        _ptr(value_out), _ptr(last_value_out), _ptr(final_value_out)))
+
+    def value_mlp(self, weights, obs_first, obs, final_obs=None, done=None, trunc=None, activation="relu"):
+        """host-array form of value_mlp_device: weights as pack_critic takes them, obs_first [D, n], obs [K, D, n], final_obs [K, D, n] or None with done /
+        trunc [K, n] -> (value [K, n], last_value [n], final_value [K, n] or None); final_value is 0 where the call does not write it"""
+        critic, H1, H2 = self.pack_critic(weights)
+        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
+        of, ob, fo = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n)), self._dev(final_obs, np.float32, (K, D, n))
+        d, u = (self._dev(None if x is None else np.asarray(x) != 0, np.uint8, (K, n)) for x in (done, trunc))
+        val, last = DeviceArray((K, max(n, 1)), np.float32, self.device), DeviceArray((max(n, 1),), np.float32, self.device)
+        fv = None if fo is None else self._dev(np.zeros((K, n), np.float32), np.float32, (K, n))
+        self.value_mlp_device(critic, H1, H2, activation, K, of, ob, fo, d, u, val, last, fv)
+        self.sync()
+        return (val.numpy().reshape(-1)[: K * n].reshape(K, n), last.numpy().reshape(-1)[:n], None if fv is None else fv.numpy().reshape(-1)[: K * n].reshape(K, n))
+
     def episode_returns(self, reward, done, trunc, ep_return=None, ep_length=None):
         """host-array form of episode_returns_device: the carry in (None: zeros) -> (return_out [K, n] float32, length_out [K, n] uint32, both 0 where no
         episode ended, and the carry out: ep_return [n], ep_length [n])"""

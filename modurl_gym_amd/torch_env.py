@@ -238,6 +238,28 @@ class TorchVecEnv:
         self.env.gae_device(K, r, d, u, v, lv, fv, gamma, lam, adv, ret)
         return adv, ret
 
+    def value_mlp(self, weights, obs_first, obs, done=None, truncated=None, activation="relu"):
+        """A critic's values over a rollout's buffers in one call (mgym_value_mlp, include/mgym.h), in place of three passes of a torch MLP.  weights: (w1, b1,
+        w2, b2) or (w1, b1, w2, b2, w3, b3), tensors (or arrays) in nn.Linear layout with one output, as in rollout_mlp / rollout_mlp2, read on the host during
+        the call; obs_first [obs_dim, n]: the observation held before the rollout's step 0 (clone it: reset() and step() reuse their tensor); obs [K, obs_dim, n]:
+        the rollout's obs.  Returns (value [K, n], last_value [n], final_value): value[t] is V of the observation the policy acted on at step t, last_value is
+        V(obs[-1]), and final_value [K, n] is V(final_obs[t]) where truncated & ~done and 0 elsewhere — or None unless the env was built with
+        final_obs_steps >= K and `truncated` is given.  The three are shaped for gae().  Fresh tensors on torch's current stream."""
+        torch = self._torch
+        self._bind_stream()
+        f32, u8 = torch.float32, torch.uint8
+        host = [x.detach().to("cpu", f32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
+        critic, h1, h2 = self.env.pack_critic(host)
+        K = int(obs.shape[0])
+        of, ob = self._kn(obs_first, f32, "obs_first", (self.obs_dim,)), self._kn(obs, f32, "obs", (K, self.obs_dim))
+        value, last = torch.empty((K, self.n), dtype=f32, device=self.device), torch.empty(self.n, dtype=f32, device=self.device)
+        fo = d = u = fv = None
+        if self.final_obs is not None and self.final_obs.shape[0] >= K and truncated is not None:
+            fo, fv = self.final_obs, torch.zeros((K, self.n), dtype=f32, device=self.device)
+            d, u = self._kn(done, u8, "done", (K,)), self._kn(truncated, u8, "truncated", (K,))
+        self.env.value_mlp_device(critic, h1, h2, activation, K, of, ob, fo, d, u, value, last, fv)
+        return value, last, fv
+
     def episode_returns(self, reward, done, truncated):
         """The return and length of every episode that ended inside the rollout (mgym_episode_returns): (return_out float32 [K, n], length_out int32 [K, n]),
         fresh tensors that are 0 except where done | truncated — `length_out > 0` is that mask.  The running episodes' carry lives in this object, created

@@ -227,6 +227,22 @@ unsafe extern "C" {
         adv_out: *mut f32,
         ret_out: *mut f32,
     ) -> c_int;
+    pub fn mgym_value_mlp(
+        env: *mut mgym_env,
+        critic: *const f32,
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        k: i32,
+        obs_first: *const f32,
+        obs: *const f32,
+        final_obs: *const f32,
+        done: *const u8,
+        trunc: *const u8,
+        value_out: *mut f32,
+        last_value_out: *mut f32,
+        final_value_out: *mut f32,
+    ) -> c_int;
     pub fn mgym_episode_returns(
         env: *mut mgym_env,
         k: i32,

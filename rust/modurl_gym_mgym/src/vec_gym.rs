@@ -373,6 +373,30 @@ impl VecGym {
     ) -> Result<(), MgymError> {
         check(unsafe { mgym_gae(self.env, k, reward, done, truncated, value, last_value, final_value, gamma, lambda, adv_out, ret_out) })
     }
+    /// A critic's values over a rollout's buffers in the shapes `gae` takes (`mgym_value_mlp`, `include/mgym.h`).  `critic`: host floats in `nn.Linear` order, one
+    /// hidden layer (`hidden2 == 0`) or two; the other pointers are device pointers.  `final_obs` / `final_value_out` / `truncated` are all set or the first two
+    /// null; `done` may be null.  `final_value_out` is written only where `truncated && !done`, and `final_obs` is read only there.
+    #[allow(clippy::too_many_arguments)]
+    pub fn value_mlp(
+        &mut self,
+        critic: &[f32],
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        k: i32,
+        obs_first: *const f32,
+        obs: *const f32,
+        final_obs: *const f32,
+        done: *const u8,
+        truncated: *const u8,
+        value_out: *mut f32,
+        last_value_out: *mut f32,
+        final_value_out: *mut f32,
+    ) -> Result<(), MgymError> {
+        check(unsafe {
+            mgym_value_mlp(self.env, critic.as_ptr(), hidden1, hidden2, activation, k, obs_first, obs, final_obs, done, truncated, value_out, last_value_out, final_value_out)
+        })
+    }
     /// The return and length of the episodes that end inside a rollout (`mgym_episode_returns`): `ep_return` / `ep_length` are the caller's carry of the
     /// running episodes (read and written); `return_out` / `length_out` (`[K][n]`, may be null) are written only where `done | truncated`.
     #[allow(clippy::too_many_arguments)]
