@@ -420,7 +420,7 @@ int mgym_rollout_mlp(mgym_env *env, const float *policy, int32_t hidden, int32_t
  *  - A temperature is the caller dividing W2 and b2 by it beforehand.
  *  - Non-finite scores give a defined but meaningless action; a NaN makes every comparison false, hence A-1.  This is specified only so that every form
  *    of the code agrees (NaNs compare as a class: the weight of the best action is computed as (m - m) + 1.0f, the same word as the text's for a finite m).
- * The learner recomputes log-probabilities (and any value head) in its own forward pass over obs_out and actions_out; none are returned.
+ * No log-probabilities are returned from inside the rollout; mgym_logprob_mlp computes them, in this arithmetic, in a pass of its own over obs_out and actions_out.
  *
  * CartPole (A = 2), MountainCar (A = 3): inside the fused rollout kernels, one Philox evaluation per lane per step serving the lane's four environments;
  * the conditions of mgym_rollout_mlp (n_envs a multiple of 4, 16-byte aligned buffers, CartPole K * n_envs below 2^30) plus env_id_base a multiple of 4.
@@ -442,7 +442,7 @@ int mgym_rollout_mlp_sample(mgym_env *env, const float *policy, int32_t hidden, 
  *
  * The action.  mu is the one score s_0.  a = mu + sigma * z: one f32 multiply, then one f32 add, nothing fused.  actions_out receives a BEFORE any clamp;
  * the step clamps as it does for any action.  The learner needs the unclamped word for its log-probability and recovers z as (a - mu) / sigma in its own
- * forward pass over obs_out and actions_out; as with mgym_rollout_mlp_sample no log-probabilities are returned.  sigma == 0 gives a = mu, the words of
+ * forward pass over obs_out and actions_out; as with mgym_rollout_mlp_sample no log-probabilities are returned (mgym_logprob_mlp).  sigma == 0 gives a = mu, the words of
  * mgym_rollout_mlp (a -0 mu becomes +0: equal as a value).  A NaN mu gives a NaN action and the step's sticky MGYM_ERR_INVALID_ACTION.
  *
  * The draw of z.  A pure function of (policy_seed, policy_call, g, t), g = env_id_base + i the global environment id and t the step index within this call:
@@ -618,6 +618,59 @@ int mgym_value_mlp(mgym_env *env, const float *critic, int32_t hidden1, int32_t 
                    const float *obs_first, const float *obs, const float *final_obs,
                    const uint8_t *done, const uint8_t *trunc,
                    float *value_out, float *last_value_out, float *final_value_out);
+
+/* The actor's log-probabilities over the buffers of a K-step rollout: log pi(a | o) of every env-step, under the distribution the rollout entry points draw
+ * from — PPO's "old" log-probability, in the arithmetic of the behaviour policy itself (a torch forward pass of the same weights differs from it by rounding
+ * and by the tanh).  A pure function of its arguments like mgym_gae and mgym_value_mlp: the handle supplies the device, the stream, n_envs and the family's
+ * (D, A) — CartPole (4, 2), MountainCar (2, 3), MountainCarContinuous (2, 1), Pendulum (3, 1), Acrobot (6, 3), LunarLander (8, 4); every kind is accepted, no
+ * state of the handle is read or written (a LunarLander handle that was never reset is accepted), nothing is allocated or synchronised, the call is capturable.
+ * policy is a HOST pointer, read during the call; 1 <= H1 = hidden1 <= 64:
+ *   hidden2 == 0   the layout and the scores of mgym_rollout_mlp:   W1[H1][D], b1[H1], W2[A][H1], b2[A]
+ *   hidden2 >= 1   the layout and the scores of mgym_rollout_mlp2:  W1[H1][D], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A], H2 <= 64
+ * activation: MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST with one hidden layer; with two MGYM_ACT_TANH is refused, as in mgym_rollout_mlp2.
+ * All other pointers are DEVICE pointers.
+ *   obs_first   [D][n_envs]      the observation held before step 0 of the rollout
+ *   obs         [K][D][n_envs]   the rollout's obs_out
+ *   actions     [K][n_envs]      the rollout's actions_out: uint32 words for the discrete families, f32 words for the continuous ones (the word BEFORE the step's clamp)
+ *   logp_out    [K][n_envs]      logp_out[t][i] = log pi(actions[t][i] | o),  o = t == 0 ? obs_first[:, i] : obs[t-1][:, i]
+ * o is the observation the policy acted on (the row mgym_value_mlp's value_out[t] reads); under MGYM_FLAG_AUTO_RESET, where an episode ended, it is the reset
+ * observation.  The scores s_a of o are those of the rollout entry points, unchanged.  All arithmetic below is f32 unless marked f64; nothing is fused beyond
+ * the chains' fmaf, nothing reassociated.
+ *
+ * mg_log_pos(x), an f64 function of a positive normal f32 x — the series of mg_log_u25 above, every operation individually rounded:
+ *   (double)x = m * 2^e with m in [1, 2) (read from the bits);  if (m > 0x1.6a09e667f3bcdp+0) { m = m * 0.5; e = e + 1; }
+ *   s  = (m - 1.0) / (m + 1.0);   s2 = s * s
+ *   p  = 2/15;  then for c in (2/13, 2/11, 2/9, 2/7, 2/5, 2/3, 2):  p = p * s2 + c;      p = p * s
+ *   L  = (double)e * 0x1.62e42fefa39efp-1 + p
+ *
+ * head = MGYM_HEAD_SAMPLE (the discrete families), the distribution of mgym_rollout_mlp_sample:
+ *   m, e_a, c_{A-1}   exactly as in "The draw" there
+ *   lse  = (float)mg_log_pos(c_{A-1})
+ *   d    = s_act - m                       ((m - m) for the best action, as the draw has it)
+ *   logp = d - lse
+ *   the quiet NaN 0x7fc00000 instead if !(c_{A-1} >= 1.0f && c_{A-1} <= (float)A) — which covers non-finite scores — or if the action word is >= A.  No
+ *   error is raised for such a word: this is a function of buffers, not a step.
+ * head = MGYM_HEAD_GAUSS (MountainCarContinuous, Pendulum), the distribution of mgym_rollout_mlp_gauss:
+ *   mu = s_0;   z = (a - mu) / sigma       the IEEE f32 divide;      q = z * z;      logp = k - 0.5f * q
+ *   k  = (float)(-(mg_log_pos(sigma) + 0.91893853320467274))         f64, once on the host
+ *   sigma must be a finite, normal, positive f32: sigma == 0 has no density, unlike in the rollout call.  sigma is ignored under MGYM_HEAD_SAMPLE.
+ * MGYM_HEAD_GREEDY is refused: a deterministic policy has no density.  (modurl_gym_amd/csrc/logprob.h is this text as the kernels and a g++ build compile it.)
+ *  - Entropy is not returned: the learner's entropy bonus needs a gradient, which its own forward pass has.  Under the Gaussian head the entropy is the
+ *    constant log sigma + 1.4189385.
+ *  - Nothing is returned from inside the rollout kernels: this is a separate pass over their outputs, and they are unchanged.
+ * The one-layer actor travels by value as a kernel argument.  The two-layer actor goes through a third device pack the handle owns from mgym_create — neither
+ * the actor's of mgym_rollout_mlp2 nor the critic's of mgym_value_mlp — which the call fills on the stream ahead of its launch: consecutive calls on one stream
+ * each find their own weights, a captured graph that holds a mgym_rollout_mlp2, a mgym_value_mlp and a mgym_logprob_mlp replays each with its own, and under
+ * capture the weights and sigma are frozen.
+ * One launch: four environments per lane and 16-byte accesses when n_envs is a multiple of 4 and below 2^30 and obs_first, obs, actions and logp_out are
+ * 16-byte aligned, otherwise one environment per lane; the words are the same.
+ * MGYM_ERR_BAD_ARG before any launch, the message starting "mgym_logprob_mlp:" and naming the argument: K < 1; a NULL policy, obs_first, obs, actions or
+ * logp_out; hidden1 outside 1 .. 64; hidden2 outside 0 .. 64; an unknown activation (2 is unknown), or MGYM_ACT_TANH with hidden2 >= 1; MGYM_HEAD_GREEDY, an
+ * unknown head, MGYM_HEAD_SAMPLE on a continuous family or MGYM_HEAD_GAUSS on a discrete one; under MGYM_HEAD_GAUSS a sigma that is zero, denormal, negative,
+ * NaN or infinite; a device pointer that is not 4-byte aligned; logp_out equal to an input pointer (overlap beyond pointer equality is the caller's error and
+ * undefined).  n_envs == 0 returns MGYM_OK after the checks without a launch. */
+int mgym_logprob_mlp(mgym_env *env, const float *policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, int32_t K,
+                     const float *obs_first, const float *obs, const void *actions, float *logp_out);
 
 /* The return and length of every episode that ends inside a K-step rollout: one launch, a forward scan per environment whose carry the CALLER owns, so
  * that episodes span calls.  A pure function of its arguments like mgym_gae (every kind, no handle state, capturable); all pointers are DEVICE pointers.

@@ -115,6 +115,13 @@ class VecGym {
                    const uint8_t* done, const uint8_t* trunc, float* value_out, float* last_value_out, float* final_value_out) {
         check(mgym_value_mlp(env_, critic, hidden1, hidden2, activation, K, obs_first, obs, final_obs, done, trunc, value_out, last_value_out, final_value_out));
     }
+    // The actor's log-probabilities of a rollout's actions (mgym_logprob_mlp): policy is a HOST pointer in nn.Linear order, one hidden layer (hidden2 == 0) or
+    // two; head MGYM_HEAD_SAMPLE (discrete families) or MGYM_HEAD_GAUSS (continuous; sigma positive and normal); the rest are device pointers, actions the
+    // rollout's actions_out words, logp_out [K][n_envs]
+    void logprob_mlp(const float* policy, int hidden1, int hidden2, int activation, int head, float sigma, int K, const float* obs_first, const float* obs,
+                     const void* actions, float* logp_out) {
+        check(mgym_logprob_mlp(env_, policy, hidden1, hidden2, activation, head, sigma, K, obs_first, obs, actions, logp_out));
+    }
     // The return and length of the episodes that end inside a rollout (mgym_episode_returns): ep_return / ep_length [n_envs] are the caller's carry of the
     // running episodes (read and written); return_out / length_out [K][n_envs] (or nullptr) are written only where done | trunc
     void episode_returns(int K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length, float* return_out,

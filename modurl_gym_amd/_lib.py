@@ -66,6 +66,7 @@ PROTOTYPES = {
     "mgym_set_final_obs_out": (C.c_int, [_vp, _vp, C.c_int32]),
     "mgym_gae": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp]),
     "mgym_value_mlp": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mgym_logprob_mlp": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp]),
     "mgym_episode_returns": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mgym_set_dispersion_override": (C.c_int, [_vp, _vp]),
     "mgym_get_spec": (C.c_int, [C.c_int, C.POINTER(Spec)]),

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "gae.h"
+#include "logprob.h"
 #include "time_limit.h"
 #include "value.h"
 
@@ -218,6 +219,7 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
         if (hipMemsetAsync(impl->d_done, 0, kDoneShards * sizeof(unsigned long long), impl->stream) != hipSuccess) { st = MGYM_ERR_HIP; break; }
         if (hipMalloc((void**)&impl->mlp2_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipMalloc((void**)&impl->value_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
+        if (hipMalloc((void**)&impl->logp_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipEventCreate(&impl->ev0) != hipSuccess || hipEventCreate(&impl->ev1) != hipSuccess) { st = MGYM_ERR_HIP; break; }
         st = impl->init();
         if (st != MGYM_OK) break;
@@ -247,6 +249,7 @@ int mgym_destroy(mgym_env* env) {
         if (e->h_done) (void)hipHostFree(e->h_done);
         if (e->mlp2_dev) (void)hipFree(e->mlp2_dev);
         if (e->value_dev) (void)hipFree(e->value_dev);
+        if (e->logp_dev) (void)hipFree(e->logp_dev);
         hipStream_t s = e->own_stream ? e->stream : nullptr;
         delete e;
         if (s) (void)hipStreamDestroy(s);
@@ -487,6 +490,42 @@ int mgym_value_mlp(mgym_env* env, const float* critic, int32_t hidden1, int32_t 
     if (hidden2 >= 1) { if (const int st = e->mlp2_store_to(e->value_dev, critic, e->obs_dim, 1, hidden1, hidden2)) return st; }
     return value_launch(e->stream, ValueCall{e->n, K, obs_first, obs, final_obs, done, trunc, value_out, last_value_out, final_value_out}, e->obs_dim, critic, hidden1,
                         hidden2, activation, e->value_dev);
+}
+
+int mgym_logprob_mlp(mgym_env* env, const float* policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, int32_t K,
+                     const float* obs_first, const float* obs, const void* actions, float* logp_out) {
+    ENV_OR_FAIL(env);
+    auto bad = [](const std::string& what) { return bad_arg(("mgym_logprob_mlp: " + what).c_str()); };
+    if (K < 1) return bad("K must be at least 1");
+    if (!policy) return bad("policy is NULL");
+    if (!obs_first) return bad("obs_first is NULL");
+    if (!obs) return bad("obs is NULL");
+    if (!actions) return bad("actions is NULL");
+    if (!logp_out) return bad("logp_out is NULL");
+    if (hidden1 < 1 || hidden1 > 64) return bad("hidden1 must be between 1 and 64");
+    if (hidden2 < 0 || hidden2 > 64) return bad("hidden2 must be between 0 (one hidden layer) and 64");
+    if (hidden2 >= 1 && activation == MGYM_ACT_TANH)
+        return bad("activation MGYM_ACT_TANH is not offered with two hidden layers (as in mgym_rollout_mlp2): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
+    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH && activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
+        return bad(hidden2 >= 1 ? "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST" : "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    if (head == MGYM_HEAD_GREEDY) return bad("head MGYM_HEAD_GREEDY: a deterministic policy has no density (use MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS)");
+    if (head != MGYM_HEAD_SAMPLE && head != MGYM_HEAD_GAUSS) return bad("head must be MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
+    if (head == MGYM_HEAD_SAMPLE && box_actions(e)) return bad(std::string("head MGYM_HEAD_SAMPLE: ") + kFamilies[e->cfg.kind].name + " has no discrete actions (use MGYM_HEAD_GAUSS)");
+    if (head == MGYM_HEAD_GAUSS && !box_actions(e)) return bad(std::string("head MGYM_HEAD_GAUSS: ") + kFamilies[e->cfg.kind].name + " has discrete actions (use MGYM_HEAD_SAMPLE)");
+    if (head == MGYM_HEAD_GAUSS && !logp_sigma_ok(sigma)) return bad("sigma must be a finite, normal, positive float (sigma == 0 has no density)");   // (a NaN fails the first test)
+    const struct { const char* name; const void* p; } dp[] = {{"obs_first", obs_first}, {"obs", obs}, {"actions", actions}, {"logp_out", logp_out}};
+    for (const auto& f : dp)
+        if (!aligned(f.p, 4)) return bad(std::string(f.name) + " must be 4-byte aligned");
+    for (int i = 0; i < 3; ++i)
+        if (dp[i].p == logp_out) return bad(std::string("logp_out is the same pointer as ") + dp[i].name);
+    if (e->n == 0) return MGYM_OK;
+    mgym_spec spec;
+    mgym_get_spec(e->cfg.kind, &spec);
+    const int A = spec.n_actions ? spec.n_actions : 1;   // a continuous family has one score, the mean
+    if (hidden2 >= 1) { if (const int st = e->mlp2_store_to(e->logp_dev, policy, e->obs_dim, A, hidden1, hidden2)) return st; }
+    const float k = head == MGYM_HEAD_GAUSS ? logp_gauss_k(sigma) : 0.0f;   // f64 on the host, the header's own lines
+    return logprob_launch(e->stream, LogpCall{e->n, K, sigma, k, obs_first, obs, static_cast<const uint32_t*>(actions), logp_out}, e->obs_dim, A, policy, hidden1,
+                          hidden2, activation, e->logp_dev);
 }
 
 int mgym_episode_returns(mgym_env* env, int32_t K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length,

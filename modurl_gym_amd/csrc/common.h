@@ -106,6 +106,9 @@ struct Env {
     // mgym_value_mlp: a second pack of the same size for a two-hidden-layer critic, so that an actor's and a critic's weights never share a buffer (a captured
     // graph that holds a mgym_rollout_mlp2 and a mgym_value_mlp replays each with its own); mlp2_store_to is the store of both
     float* value_dev = nullptr;
+    // mgym_logprob_mlp: a third pack, for the same reason — the call re-evaluates an actor, usually the one a mgym_rollout_mlp2 on the same stream or in the same
+    // graph drew with, but it may be another (the learner's current weights against the behaviour policy's), and neither call may find the other's words
+    float* logp_dev = nullptr;
     int mlp2_store_to(float* dst, const float* weights, int D, int A, int H1, int H2);
     template <int D, int A>
     Mlp2Net<D, A> mlp2_net(const PolicyCall& call) const { return Mlp2Net<D, A>{mlp2_dev, call.hidden, call.hidden2, call.sigma}; }

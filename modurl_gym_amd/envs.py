@@ -431,6 +431,37 @@ class VecEnv:
         self.sync()
         return (val.numpy().reshape(-1)[: K * n].reshape(K, n), last.numpy().reshape(-1)[:n], None if fv is None else fv.numpy().reshape(-1)[: K * n].reshape(K, n))
 
+    def logprob_mlp_device(self, policy, hidden1, hidden2, activation, head, sigma, K, obs_first, obs, actions, logp_out):
+        """mgym_logprob_mlp on device buffers (pointers, DeviceArrays or tensors): `policy` = the packed host floats of pack_mlp (hidden2 = 0) or pack_mlp2 (or
+        None, which the engine rejects); head "sample" (the discrete families) or "gauss" (MountainCarContinuous, Pendulum; sigma a positive normal float, ignored
+        by "sample"); obs_first [D, n], obs [K, D, n] and actions [K, n] (uint32 or float32 words) are a rollout's buffers, logp_out [K, n] receives the
+        log-probability of each action under the distribution the rollout drew from.  On the env's stream, nothing synchronised.  A policy of the wrong length
+        raises PolicyShapeError."""
+        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
+        hd = _named(_HEADS, head, 'head must be "sample", "gauss" or an MGYM_HEAD_* value')
+        (D, A), h1, h2 = self.mlp_dims(), int(hidden1), int(hidden2)
+        want = None
+        if 1 <= h1 <= 64 and 0 <= h2 <= 64:
+            want = h1 * (D + 1) + (h2 * (h1 + 1) + A * (h2 + 1) if h2 else A * (h1 + 1))
+        pol = None if policy is None else _policy_floats(policy, want, f"hidden1 = {h1}, hidden2 = {h2}")
+        _check(self._lib.mgym_logprob_mlp(self._h, _fptr(pol), h1, h2, act, hd, float(sigma), int(K), _ptr(obs_first), _ptr(obs), _ptr(actions), _ptr(logp_out)))
+
+    def logprob_mlp(self, weights, obs_first, obs, actions, activation="relu", head=None, sigma=0.0):
+        """host-array form of logprob_mlp_device: weights (w1, b1, w2, b2) or (w1, b1, w2, b2, w3, b3) as pack_mlp / pack_mlp2 take them, obs_first [D, n],
+        obs [K, D, n], actions [K, n] (this family's action dtype) -> logp [K, n] float32.  head: None takes the family's ("gauss" for a continuous one)."""
+        if len(weights) not in (4, 6):
+            raise PolicyShapeError(L.ERR_BAD_ARG, f"a policy is (w1, b1, w2, b2) or (w1, b1, w2, b2, w3, b3); got {len(weights)} arrays")
+        policy, H1, H2 = (*self.pack_mlp(*weights), 0) if len(weights) == 4 else self.pack_mlp2(*weights)
+        if head is None:
+            head = "gauss" if self.action_dtype == np.float32 else "sample"
+        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
+        of, ob = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n))
+        ac = self._dev(actions, self.action_dtype, (K, n))
+        out = DeviceArray((K, max(n, 1)), np.float32, self.device)
+        self.logprob_mlp_device(policy, H1, H2, activation, head, sigma, K, of, ob, ac, out)
+        self.sync()
+        return out.numpy().reshape(-1)[: K * n].reshape(K, n)
+
     def episode_returns(self, reward, done, trunc, ep_return=None, ep_length=None):
         """host-array form of episode_returns_device: the carry in (None: zeros) -> (return_out [K, n] float32, length_out [K, n] uint32, both 0 where no
         episode ended, and the carry out: ep_return [n], ep_length [n])"""

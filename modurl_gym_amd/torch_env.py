@@ -176,7 +176,7 @@ class TorchVecEnv:
     def rollout_mlp_sample(self, w1, b1, w2, b2, K, seed, call=0, activation="relu"):
         """rollout_mlp with the action drawn from the softmax of the scores (mgym_rollout_mlp_sample; the discrete families) — the collector of an on-policy
         trainer.  The draw is a pure function of (seed, call, global env id, step) and the scores: pass a new `call` for each call that is to draw afresh.
-        Returns (actions, obs, reward, done, truncated) like rollout_mlp; log-probabilities are the learner's forward pass over obs and actions."""
+        Returns (actions, obs, reward, done, truncated) like rollout_mlp; logprob_mlp gives the log-probabilities of these actions over obs and actions."""
         return self._rollout_policy((w1, b1, w2, b2), K,
                                     lambda host, K, out: self.env.rollout_mlp_sample_device(*self.env.pack_mlp(*host), activation, seed, call, K, *out))
 
@@ -184,7 +184,7 @@ class TorchVecEnv:
         """rollout_mlp for MountainCarContinuous and Pendulum with the action drawn from a Gaussian around the score, a = mu + sigma * z with a
         state-independent `sigma` >= 0 (mgym_rollout_mlp_gauss) — the collector of a continuous-control on-policy trainer.  z is a pure function of (seed,
         call, global env id, step): pass a new `call` for each call that is to draw afresh.  Returns (actions, obs, reward, done, truncated) like rollout_mlp;
-        the actions are float32 and not clamped (the step clamps), so the learner's forward pass over obs and actions gives the log-probabilities."""
+        the actions are float32 and not clamped (the step clamps): logprob_mlp over obs and these actions gives their log-probabilities."""
         return self._rollout_policy((w1, b1, w2, b2), K,
                                     lambda host, K, out: self.env.rollout_mlp_gauss_device(*self.env.pack_mlp(*host), activation, float(sigma), seed, call, K, *out))
 
@@ -259,6 +259,28 @@ class TorchVecEnv:
             d, u = self._kn(done, u8, "done", (K,)), self._kn(truncated, u8, "truncated", (K,))
         self.env.value_mlp_device(critic, h1, h2, activation, K, of, ob, fo, d, u, value, last, fv)
         return value, last, fv
+
+    def logprob_mlp(self, weights, obs_first, obs, actions, activation="relu", head=None, sigma=0.0):
+        """log pi(a | o) of every env-step of a rollout in one call (mgym_logprob_mlp, include/mgym.h): PPO's old log-probabilities under the distribution the
+        rollout drew from, in its own arithmetic, in place of a torch forward pass of the actor.  weights: (w1, b1, w2, b2) or (w1, b1, w2, b2, w3, b3), the
+        tensors (or arrays) given to rollout_mlp_sample / rollout_mlp_gauss / rollout_mlp2, read on the host during the call; obs_first [obs_dim, n]: the
+        observation held before the rollout's step 0 (clone it: reset() and step() reuse their tensor); obs [K, obs_dim, n] and actions [K, n]: the rollout's
+        (int32 for the discrete families, float32 and unclamped for the continuous ones).  head "sample" or "gauss" (None: the family's); sigma: the Gaussian
+        head's, the one the rollout drew with.  Returns a fresh [K, n] float32 tensor on torch's current stream; no entropy (the learner's own pass has it)."""
+        torch = self._torch
+        self._bind_stream()
+        host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
+        if len(host) not in (4, 6):
+            raise ValueError(f"a policy is (w1, b1, w2, b2) or (w1, b1, w2, b2, w3, b3); got {len(host)} arrays")
+        policy, h1, h2 = (*self.env.pack_mlp(*host), 0) if len(host) == 4 else self.env.pack_mlp2(*host)
+        if head is None:
+            head = "gauss" if self.action_is_float else "sample"
+        K = int(obs.shape[0])
+        of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))
+        ac = self._kn(actions, torch.float32 if self.action_is_float else torch.int32, "actions", (K,))
+        logp = torch.empty((K, self.n), dtype=torch.float32, device=self.device)
+        self.env.logprob_mlp_device(policy, h1, h2, activation, head, float(sigma), K, of, ob, ac, logp)
+        return logp
 
     def episode_returns(self, reward, done, truncated):
         """The return and length of every episode that ended inside the rollout (mgym_episode_returns): (return_out float32 [K, n], length_out int32 [K, n]),

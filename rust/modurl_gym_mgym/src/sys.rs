@@ -243,6 +243,20 @@ unsafe extern "C" {
         last_value_out: *mut f32,
         final_value_out: *mut f32,
     ) -> c_int;
+    pub fn mgym_logprob_mlp(
+        env: *mut mgym_env,
+        policy: *const f32,
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        head: i32,
+        sigma: f32,
+        k: i32,
+        obs_first: *const f32,
+        obs: *const f32,
+        actions: *const c_void,
+        logp_out: *mut f32,
+    ) -> c_int;
     pub fn mgym_episode_returns(
         env: *mut mgym_env,
         k: i32,

@@ -397,6 +397,26 @@ impl VecGym {
             mgym_value_mlp(self.env, critic.as_ptr(), hidden1, hidden2, activation, k, obs_first, obs, final_obs, done, truncated, value_out, last_value_out, final_value_out)
         })
     }
+    /// The actor's log-probabilities of a rollout's actions (`mgym_logprob_mlp`, `include/mgym.h`).  `policy`: host floats in `nn.Linear` order, one hidden layer
+    /// (`hidden2 == 0`) or two; `head`: `MGYM_HEAD_SAMPLE` (1, the discrete families) or `MGYM_HEAD_GAUSS` (2, the continuous ones; `sigma` positive and normal);
+    /// the other pointers are device pointers: `actions` the rollout's `actions_out` words, `logp_out` `[K][n]`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn logprob_mlp(
+        &mut self,
+        policy: &[f32],
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        head: i32,
+        sigma: f32,
+        k: i32,
+        obs_first: *const f32,
+        obs: *const f32,
+        actions: *const c_void,
+        logp_out: *mut f32,
+    ) -> Result<(), MgymError> {
+        check(unsafe { mgym_logprob_mlp(self.env, policy.as_ptr(), hidden1, hidden2, activation, head, sigma, k, obs_first, obs, actions, logp_out) })
+    }
     /// The return and length of the episodes that end inside a rollout (`mgym_episode_returns`): `ep_return` / `ep_length` are the caller's carry of the
     /// running episodes (read and written); `return_out` / `length_out` (`[K][n]`, may be null) are written only where `done | truncated`.
     #[allow(clippy::too_many_arguments)]
