@@ -672,6 +672,74 @@ int mgym_value_mlp(mgym_env *env, const float *critic, int32_t hidden1, int32_t 
 int mgym_logprob_mlp(mgym_env *env, const float *policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, int32_t K,
                      const float *obs_first, const float *obs, const void *actions, float *logp_out);
 
+/* PPO's loss and the actor's gradient, and a critic's squared-error loss and gradient, over the buffers of a K-step rollout: the update a learner handed to a
+ * torch forward pass (a [K n][H] activation written), a surrogate and autograd's backward pass (the activation read back).  One hidden layer, 1 <= H = hidden
+ * <= 64; the six (D, A) of mgym_logprob_mlp; MGYM_HEAD_SAMPLE on the discrete families and MGYM_HEAD_GAUSS on the continuous ones; MGYM_ACT_RELU, MGYM_ACT_TANH
+ * and MGYM_ACT_TANH_FAST.  Out of scope: two hidden layers (dW2[H2][H1] needs a tiled product over the batch dimension, a separate piece of work); the
+ * optimizer step; advantage normalisation; flat-index minibatches; a clipped value loss; any state of the handle.
+ *
+ * Purity.  As mgym_logprob_mlp: the handle supplies the device, the stream, n_envs and (D, A); every kind is accepted and no state of the handle is read or
+ * written.  policy / critic is a HOST pointer in nn.Linear order, W1[H][D], b1[H], W2[A][H], b2[A] (A = 1 for the critic), read during the call and passed to the
+ * kernels by value.  Every other pointer is a DEVICE pointer.  Nothing is allocated and nothing synchronised — the caller owns the workspace — so the calls are
+ * capturable (the weights, sigma, clip and ent_coef are frozen under capture).
+ *   obs_first [D][n_envs], obs [K][D][n_envs], actions [K][n_envs]     the rollout's buffers, as for mgym_logprob_mlp
+ *   logp_old  [K][n_envs]     the output of mgym_logprob_mlp;     adv, ret  [K][n_envs]     the outputs of mgym_gae.  Every row keeps the stride n_envs.
+ * Minibatch.  The call covers every step t in 0 .. K-1 of the environments env_first <= i < env_first + env_count: environments are independent, so contiguous
+ * slices partition a batch, and the full range is one batch.  B = K * env_count.  No word of any input outside the range reaches any result — a NaN there is
+ * harmless — and the kernels do not load those words.
+ *   grad_out  mlp_policy_floats(D, A, H) + 1 = H (D + 1) + A (H + 1) + 1 floats: dW1[H][D], db1[H], dW2[A][H], db2[A] in nn.Linear order (an optimizer can view
+ *             them as the parameters' .grad), then one word: dL / d log sigma under the Gaussian head, +0 under the sample head and for the critic
+ *   stats_out 8 floats.  Actor: [0] the policy loss -mean(min(r adv, clamp(r) adv)) (without the entropy bonus), [1] the mean entropy, [2] the approximate KL
+ *             mean(r - 1 - d), [3] the clipped fraction, [4] the mean ratio, [5] (float)B, [6] and [7] +0.  Critic: [0] the loss, [5] (float)B, the rest +0.
+ *
+ * Per env-step, f32 words; the chains keep the fmaf rule of mgym_rollout_mlp, nothing else is fused, nothing reassociated, every selection is a selection:
+ *   s_a        exactly the scores of mgym_rollout_mlp on o = t == 0 ? obs_first[:, i] : obs[t-1][:, i]
+ *   logp_new   exactly the word of mgym_logprob_mlp (logp_head of csrc/logprob.h) — with unchanged weights d is +0 and the ratio exactly 1
+ *   d = logp_new - logp_old;     r = mg_expm1f(d) + 1.0f
+ *   L = -mean(min(r adv, clamp(r, lo, hi) adv)) - ent_coef mean(entropy),     lo = 1.0f - clip and hi = 1.0f + clip computed on the host
+ *   clipped = (adv > 0 && r > hi) || (adv < 0 && r < lo);     g = clipped ? +0 : (-adv) * r          a selection, not a mask multiply: at r == hi or r == lo the
+ *             gradient passes, as torch's clamp and min pass it
+ *   the statistics' terms:  rc = r < lo ? lo : (r > hi ? hi : r);  u = r * adv;  uc = rc * adv;  loss = -(uc < u ? uc : u);  kl = (r - 1.0f) - d
+ * MGYM_HEAD_SAMPLE:  m, e_a, c_{A-1} exactly as in "The draw" of mgym_rollout_mlp_sample;  lse = (float)mg_log_pos(c_{A-1});  p_a = e_a / c_{A-1};
+ *   lp_a = (s_a - m) - lse;     t = p_0 * lp_0, then a = 1 .. A-1: t = t + p_a * lp_a;     Hent = -t                      (the env-step's entropy)
+ *   ds_a = g * ((a == act ? 1.0f : 0.0f) - p_a) + (ent_coef * p_a) * (lp_a + Hent)
+ * MGYM_HEAD_GAUSS:  z = (a - mu) / sigma;     ds_0 = (g * z) / sigma;     the log-sigma word receives g * (z * z - 1.0f) per env-step and -ent_coef * B once, so
+ *   after the division by B it is the mean of g (z z - 1) minus ent_coef.  The entropy is the constant (float)(mg_log_pos(sigma) + 1.4189385332046727).
+ * Critic:  L = 1/2 mean((V - ret)^2);     e = V - ret;     ds_0 = e;     the loss term 0.5f * (e * e).
+ * Backward pass, all heads, hidden unit j:  pre_j and h_j as mgym_rollout_mlp computes them;
+ *   dh = W2[0][j] * ds_0, then a = 1 .. A-1: dh = dh + W2[a][j] * ds_a;     dpre = dh * act',  act' = (pre_j > 0 ? 1.0f : 0.0f) under ReLU, 1.0f - h_j * h_j of the
+ *   h_j word under both tanh forms (tanh_fast is differentiated as the tanh it approximates)
+ *   dW2[a][j] += ds_a * h_j;     db2[a] += ds_a;     dW1[j][q] += dpre * o_q;     db1[j] += dpre
+ * Every sum is divided by B once, at the end.  (modurl_gym_amd/csrc/grad.h is this text as the kernels and a g++ build compile it.)
+ *  - An env-step whose logp_new is the NaN word (an action word that is no action, scores without a finite softmax) makes the gradient NaN: the caller's error,
+ *    not special-cased.
+ * The sums over the B env-steps are the one part that is not word-defined: their order belongs to the kernels.  (a) No float atomics, no tickets, no
+ * run-dependent order: two calls with the same arguments (workspace_bytes included) on the same device return identical words.  (b) The values are bounded
+ * against float64 (tests/grad_ref.py: GRAD_BOUND times the word's mean absolute per-env-step term).  A lane adds its own env-steps' terms, a wave adds across its
+ * lanes, each wave owns an f64 slab in LDS, each block stores one f64 slab of P + 8 sums to the workspace, and a second small launch adds the slabs in index
+ * order in f64, scales by 1 / B, rounds to f32 and writes grad_out and stats_out.
+ * Workspace.  mgym_grad_workspace_bytes(kind, hidden) gives min_bytes, one slab, and best_bytes, 1024 slabs (four blocks on each of the chip's 256 compute
+ * units); the same sizes serve both calls.  A call uses min(1024, workspace_bytes / min_bytes) slabs, and its blocks stride over the tiles when there are more
+ * tiles than slabs; no word at or beyond workspace_bytes is written.  Four environments per lane with 16-byte rows when n_envs, env_first and env_count are
+ * multiples of 4, n_envs < 2^30 and obs_first, obs, actions, logp_old / ret and adv are 16-byte aligned; otherwise one environment per lane.
+ * MGYM_ERR_BAD_ARG before any launch, the message starting with the entry point's name and naming the argument: K < 1; a NULL policy / critic, obs_first, obs,
+ * actions, logp_old / ret, adv, workspace, grad_out or stats_out; hidden outside 1 .. 64; an unknown activation (2 is unknown); the head and sigma rules of
+ * mgym_logprob_mlp; env_count == 0, or env_first + env_count > n_envs; clip NaN, negative or >= 1; ent_coef NaN or infinite; workspace_bytes below min_bytes;
+ * workspace not 16-byte aligned; another device pointer not 4-byte aligned; grad_out, stats_out or workspace equal to an input or to each other.  n_envs == 0
+ * returns MGYM_OK after the other checks without a launch (there is no range to refuse).  mgym_grad_workspace_bytes refuses an unknown kind, hidden outside
+ * 1 .. 64 and a NULL output. */
+int mgym_grad_workspace_bytes(int kind, int32_t hidden, size_t *min_bytes, size_t *best_bytes);
+
+int mgym_ppo_grad_mlp(mgym_env *env, const float *policy, int32_t hidden, int32_t activation, int32_t head, float sigma,
+                      int32_t K, uint64_t env_first, uint64_t env_count,
+                      const float *obs_first, const float *obs, const void *actions, const float *logp_old, const float *adv,
+                      float clip, float ent_coef, void *workspace, size_t workspace_bytes, float *grad_out, float *stats_out);
+
+int mgym_value_grad_mlp(mgym_env *env, const float *critic, int32_t hidden, int32_t activation,
+                        int32_t K, uint64_t env_first, uint64_t env_count,
+                        const float *obs_first, const float *obs, const float *ret,
+                        void *workspace, size_t workspace_bytes, float *grad_out, float *stats_out);
+
 /* The return and length of every episode that ends inside a K-step rollout: one launch, a forward scan per environment whose carry the CALLER owns, so
  * that episodes span calls.  A pure function of its arguments like mgym_gae (every kind, no handle state, capturable); all pointers are DEVICE pointers.
  *   reward, done, trunc      [K][n_envs]; done / trunc may be NULL = all 0

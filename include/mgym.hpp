@@ -122,6 +122,23 @@ class VecGym {
                      const void* actions, float* logp_out) {
         check(mgym_logprob_mlp(env_, policy, hidden1, hidden2, activation, head, sigma, K, obs_first, obs, actions, logp_out));
     }
+    // PPO's loss and the actor's gradient, and a critic's squared-error loss and gradient, over a rollout's buffers (mgym_ppo_grad_mlp, mgym_value_grad_mlp):
+    // one hidden layer; policy / critic are HOST pointers in nn.Linear order, the rest device pointers; the range is the environments env_first ..
+    // env_first + env_count - 1 over all K steps; workspace: 16-byte aligned, at least min_bytes of grad_workspace_bytes; grad_out receives the parameters'
+    // gradient in nn.Linear order and one more word (d / d log sigma, or +0), stats_out 8 floats
+    static void grad_workspace_bytes(int kind, int hidden, size_t* min_bytes, size_t* best_bytes) {
+        if (mgym_grad_workspace_bytes(kind, hidden, min_bytes, best_bytes) != MGYM_OK) throw std::runtime_error(mgym_last_error());
+    }
+    void ppo_grad_mlp(const float* policy, int hidden, int activation, int head, float sigma, int K, uint64_t env_first, uint64_t env_count, const float* obs_first,
+                      const float* obs, const void* actions, const float* logp_old, const float* adv, float clip, float ent_coef, void* workspace,
+                      size_t workspace_bytes, float* grad_out, float* stats_out) {
+        check(mgym_ppo_grad_mlp(env_, policy, hidden, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip, ent_coef,
+                                workspace, workspace_bytes, grad_out, stats_out));
+    }
+    void value_grad_mlp(const float* critic, int hidden, int activation, int K, uint64_t env_first, uint64_t env_count, const float* obs_first, const float* obs,
+                        const float* ret, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
+        check(mgym_value_grad_mlp(env_, critic, hidden, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out));
+    }
     // The return and length of the episodes that end inside a rollout (mgym_episode_returns): ep_return / ep_length [n_envs] are the caller's carry of the
     // running episodes (read and written); return_out / length_out [K][n_envs] (or nullptr) are written only where done | trunc
     void episode_returns(int K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length, float* return_out,

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "gae.h"
+#include "grad.h"
 #include "logprob.h"
 #include "time_limit.h"
 #include "value.h"
@@ -526,6 +527,114 @@ int mgym_logprob_mlp(mgym_env* env, const float* policy, int32_t hidden1, int32_
     const float k = head == MGYM_HEAD_GAUSS ? logp_gauss_k(sigma) : 0.0f;   // f64 on the host, the header's own lines
     return logprob_launch(e->stream, LogpCall{e->n, K, sigma, k, obs_first, obs, static_cast<const uint32_t*>(actions), logp_out}, e->obs_dim, A, policy, hidden1,
                           hidden2, activation, e->logp_dev);
+}
+
+// ---- mgym_ppo_grad_mlp / mgym_value_grad_mlp: one argument check for both (ppo: the actor's call) ----
+struct GradArgs {
+    const char* name;
+    bool ppo;
+    const float* weights;
+    int32_t hidden, activation, head;
+    float sigma;
+    int32_t K;
+    uint64_t env_first, env_count;
+    const float *obs_first, *obs;
+    const void* actions;
+    const float *x0, *x1;   // logp_old, adv | ret, nothing
+    float clip, ent_coef;
+    void* workspace;
+    size_t workspace_bytes;
+    float *grad_out, *stats_out;
+};
+
+static int family_dims(int kind, int* D, int* A) {
+    mgym_spec spec;
+    if (const int st = mgym_get_spec(kind, &spec)) return st;
+    *D = spec.obs_dim;
+    *A = spec.n_actions ? spec.n_actions : 1;   // a continuous family has one score, the mean
+    return MGYM_OK;
+}
+
+static int grad_call(Env* e, const GradArgs& a) {
+    auto bad = [&](const std::string& what) { return bad_arg((std::string(a.name) + ": " + what).c_str()); };
+    const char *n0 = a.ppo ? "logp_old" : "ret", *wname = a.ppo ? "policy" : "critic";
+    if (a.K < 1) return bad("K must be at least 1");
+    if (!a.weights) return bad(std::string(wname) + " is NULL");
+    if (!a.obs_first) return bad("obs_first is NULL");
+    if (!a.obs) return bad("obs is NULL");
+    if (a.ppo && !a.actions) return bad("actions is NULL");
+    if (!a.x0) return bad(std::string(n0) + " is NULL");
+    if (a.ppo && !a.x1) return bad("adv is NULL");
+    if (!a.workspace) return bad("workspace is NULL");
+    if (!a.grad_out) return bad("grad_out is NULL");
+    if (!a.stats_out) return bad("stats_out is NULL");
+    if (a.hidden < 1 || a.hidden > 64) return bad("hidden must be between 1 and 64");
+    if (a.activation != MGYM_ACT_RELU && a.activation != MGYM_ACT_TANH && a.activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
+        return bad("activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    if (a.ppo) {
+        if (a.head == MGYM_HEAD_GREEDY) return bad("head MGYM_HEAD_GREEDY: a deterministic policy has no density (use MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS)");
+        if (a.head != MGYM_HEAD_SAMPLE && a.head != MGYM_HEAD_GAUSS) return bad("head must be MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
+        if (a.head == MGYM_HEAD_SAMPLE && box_actions(e)) return bad(std::string("head MGYM_HEAD_SAMPLE: ") + kFamilies[e->cfg.kind].name + " has no discrete actions (use MGYM_HEAD_GAUSS)");
+        if (a.head == MGYM_HEAD_GAUSS && !box_actions(e)) return bad(std::string("head MGYM_HEAD_GAUSS: ") + kFamilies[e->cfg.kind].name + " has discrete actions (use MGYM_HEAD_SAMPLE)");
+        if (a.head == MGYM_HEAD_GAUSS && !logp_sigma_ok(a.sigma)) return bad("sigma must be a finite, normal, positive float (sigma == 0 has no density)");
+    }
+    if (e->n != 0 && a.env_count == 0) return bad("env_count must be at least 1");   // (a handle without environments has no range to give: MGYM_OK below)
+    if (e->n != 0 && (a.env_first > e->n || a.env_count > e->n - a.env_first)) return bad("env_first + env_count exceeds n_envs");
+    if (a.ppo && !grad_clip_ok(a.clip)) return bad("clip must be at least 0 and below 1");
+    if (a.ppo && !grad_ent_coef_ok(a.ent_coef)) return bad("ent_coef must be finite");
+    int D = 0, A = 1;
+    if (const int st = family_dims(e->cfg.kind, &D, &A)) return st;
+    const uint64_t slab_bytes = grad_slab_bytes(D, A, a.hidden);
+    if (a.workspace_bytes < slab_bytes) return bad("workspace_bytes is below min_bytes of mgym_grad_workspace_bytes (" + std::to_string(slab_bytes) + ")");
+    if (!aligned(a.workspace, 16)) return bad("workspace must be 16-byte aligned");
+    const struct { const char* name; const void* p; } in[] = {{"obs_first", a.obs_first}, {"obs", a.obs}, {"actions", a.actions}, {n0, a.x0}, {"adv", a.x1}};
+    const struct { const char* name; const void* p; } out[] = {{"workspace", a.workspace}, {"grad_out", a.grad_out}, {"stats_out", a.stats_out}};
+    for (const auto& f : in)
+        if (f.p && !aligned(f.p, 4)) return bad(std::string(f.name) + " must be 4-byte aligned");
+    for (int i = 1; i < 3; ++i)
+        if (!aligned(out[i].p, 4)) return bad(std::string(out[i].name) + " must be 4-byte aligned");
+    for (int i = 0; i < 3; ++i) {
+        for (const auto& f : in)
+            if (f.p && f.p == out[i].p) return bad(std::string(out[i].name) + " is the same pointer as " + f.name);
+        for (int k = 0; k < i; ++k)
+            if (out[k].p == out[i].p) return bad(std::string(out[i].name) + " is the same pointer as " + out[k].name);
+    }
+    if (e->n == 0) return MGYM_OK;
+    const uint64_t fit = a.workspace_bytes / slab_bytes;
+    GradCall c{};
+    c.n = e->n; c.env_first = a.env_first; c.env_count = a.env_count; c.K = a.K;
+    c.slabs = (int32_t)(fit < (uint64_t)kGradSlabCap ? fit : (uint64_t)kGradSlabCap);
+    c.lo = 1.0f - a.clip; c.hi = 1.0f + a.clip; c.ent_coef = a.ppo ? a.ent_coef : 0.0f;
+    const bool gauss = a.ppo && a.head == MGYM_HEAD_GAUSS;
+    c.sigma = a.sigma; c.k = gauss ? logp_gauss_k(a.sigma) : 0.0f; c.ent = gauss ? grad_gauss_entropy(a.sigma) : 0.0f;   // f64 on the host, the headers' own lines
+    c.obs_first = a.obs_first; c.obs = a.obs; c.actions = static_cast<const uint32_t*>(a.actions); c.x0 = a.x0; c.x1 = a.x1;
+    c.workspace = static_cast<double*>(a.workspace); c.grad_out = a.grad_out; c.stats_out = a.stats_out;
+    return grad_launch(e->stream, c, D, A, !a.ppo ? GRAD_HEAD_VALUE : (gauss ? GRAD_HEAD_GAUSS : GRAD_HEAD_CATEGORICAL), a.weights, a.hidden, a.activation);
+}
+
+int mgym_grad_workspace_bytes(int kind, int32_t hidden, size_t* min_bytes, size_t* best_bytes) {
+    int D = 0, A = 1;
+    if (family_dims(kind, &D, &A) != MGYM_OK) return bad_arg("mgym_grad_workspace_bytes: unknown kind");
+    if (hidden < 1 || hidden > 64) return bad_arg("mgym_grad_workspace_bytes: hidden must be between 1 and 64");
+    if (!min_bytes || !best_bytes) return bad_arg(!min_bytes ? "mgym_grad_workspace_bytes: min_bytes is NULL" : "mgym_grad_workspace_bytes: best_bytes is NULL");
+    *min_bytes = (size_t)grad_slab_bytes(D, A, hidden);
+    *best_bytes = (size_t)grad_slab_bytes(D, A, hidden) * (size_t)kGradSlabCap;
+    return MGYM_OK;
+}
+
+int mgym_ppo_grad_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, int32_t head, float sigma, int32_t K, uint64_t env_first,
+                      uint64_t env_count, const float* obs_first, const float* obs, const void* actions, const float* logp_old, const float* adv, float clip,
+                      float ent_coef, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
+    ENV_OR_FAIL(env);
+    return grad_call(e, GradArgs{"mgym_ppo_grad_mlp", true, policy, hidden, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv,
+                                 clip, ent_coef, workspace, workspace_bytes, grad_out, stats_out});
+}
+
+int mgym_value_grad_mlp(mgym_env* env, const float* critic, int32_t hidden, int32_t activation, int32_t K, uint64_t env_first, uint64_t env_count,
+                        const float* obs_first, const float* obs, const float* ret, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
+    ENV_OR_FAIL(env);
+    return grad_call(e, GradArgs{"mgym_value_grad_mlp", false, critic, hidden, activation, 0, 0.0f, K, env_first, env_count, obs_first, obs, nullptr, ret, nullptr,
+                                 0.0f, 0.0f, workspace, workspace_bytes, grad_out, stats_out});
 }
 
 int mgym_episode_returns(mgym_env* env, int32_t K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length,

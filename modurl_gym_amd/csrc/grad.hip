@@ -1,0 +1,252 @@
+// grad.hip — mgym_ppo_grad_mlp and mgym_value_grad_mlp (include/mgym.h): a loss and its gradient over a rollout's buffers, the words of grad.h.
+//
+// Two launches.  The first covers the K x env_count env-steps in tiles of 256 lanes x N environments x S steps (N = 4 with 16-byte rows when n_envs, env_first
+// and env_count are multiples of 4, n_envs < 2^30 and every row pointer is 16-byte aligned, else N = 1 with 64-bit addresses; S: kGradFillTiles below).  A lane
+// loads its N x S observations, action words and targets, runs mlp_scores once over all of them (weights as scalar operands) and the head per env-step, and
+// keeps o and ds in registers.  The second pass walks the hidden units: unit j's pre_j / h_j are recomputed for every env-step of the lane (D fused
+// multiply-adds each: cheaper than 64 stored h words per environment), its D + 1 + A terms added by fmaf into the lane's accumulators, which the wave then
+// adds across its lanes (four DPP steps inside each row of 16, then the four rows) and lane v adds value v into the wave's own f64 slab in LDS.  At the end
+// of its tiles (a block strides over them when there are more tiles than slabs) the block adds its four waves' slabs in wave order and stores one f64 slab to
+// the workspace.  The second launch adds the slabs in index order in f64, scales by 1 / B, rounds to f32 and writes grad_out and stats_out.  No atomics, no
+// tickets: the order of every sum is a function of the arguments alone.  A word outside the environments' range or beyond step K - 1 is never loaded.
+#include "common.h"
+#include "grad.h"
+
+namespace mgym {
+
+constexpr int kGradWaves = kBlock / 64;
+static_assert(kGradWaves == 4, "the block's last sum names its four waves' slabs");
+
+// Steps of its environments a lane takes before each wave reduction: the registers hold N x S x (D + A) words of o and ds, and the heads of all N x S
+// env-steps are in flight together.  Four environments per lane: 2 steps when that gives at least kGradFillTiles tiles, else 1 — measured (DESIGN.md 5i:
+// three builds in one session): at 1 Mi environments, K = 16 (8 192 tiles) 1 step is 4 - 28 % slower than 2, the wave sums shared by twice the terms; at
+// 4 096 environments (32 tiles on 256 compute units) 1 step is up to 36 % faster (one row of 24 equal), twice the blocks at half the serial work each.  Between those two sizes the
+// threshold is a choice, the chip's compute units, not a measurement.  4 steps were not timed: the (4, 2) kernels then take 219 - 251 VGPRs and the (2, 3),
+// (6, 3) and (8, 4) ones a private segment (profiles/grad_kernel_resources.txt).  One environment per lane: 4 steps, not measured against others.
+// (make EXTRA=-DGRAD_STEPS4=1 or 2 builds one count for every size: the builds of that measurement.)
+constexpr uint64_t kGradFillTiles = 256;
+constexpr int kGradSteps1 = 4;
+
+#if defined(GRAD_WAVE_SHFL)
+// (make EXTRA=-DGRAD_WAVE_SHFL: the same sum through six ds_bpermute butterflies.  Measured against the DPP form below in one session, DESIGN.md 5i: between
+// equal within 1 % and 26 % slower on the actor's rows, 1 - 4 % faster on the critic's tanh_fast rows only; not kept)
+__device__ __forceinline__ float grad_wave_sum(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+#else
+template <int CTRL>
+__device__ __forceinline__ float grad_dpp(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
+}
+// the sum of x over the wave's 64 lanes, the same word in every lane; all 64 lanes are active at every call.  quad_perm [1,0,3,2] and [2,3,0,1] leave every
+// lane of a quad with the quad's sum, row_half_mirror every lane of 8 with the sum of its two quads, row_mirror every lane of a row of 16 with the row's
+// sum (each step adds two values that both sides hold, so both get the same word); the four rows' sums are then read as scalars and added in row order
+__device__ __forceinline__ float grad_wave_sum(float x) {
+    x += grad_dpp<0xB1>(x);
+    x += grad_dpp<0x4E>(x);
+    x += grad_dpp<0x141>(x);
+    x += grad_dpp<0x140>(x);
+    const int xi = __float_as_int(x);
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(xi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(xi, 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(xi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(xi, 48));
+    return ((r0 + r1) + r2) + r3;
+}
+#endif
+
+template <class V, class T>
+__device__ __forceinline__ const V& grad_word_at(const T* row, uint32_t off) {
+    return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(row) + off);
+}
+
+// N words of row `row` ([n] each) at environments i .. i + N - 1; the four-per-lane form by one 16-byte load at a 32-bit byte offset
+template <int N, class T>
+__device__ __forceinline__ void grad_load(const T* row, uint64_t i, T (&out)[N]) {
+    if constexpr (N == 4) {
+        typedef typename std::conditional<std::is_same<T, float>::value, float4, uint4>::type V4;
+        const V4 v = grad_word_at<V4>(row, (uint32_t)i * 4u);
+        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+    } else {
+        out[0] = row[i];
+    }
+}
+
+template <int D, int A, int ACT, class Head, int N, int S>
+__global__ void __launch_bounds__(kBlock) grad_kernel(const MlpPack<D, A> net, const Head head, const GradCall c) {
+    constexpr int V = D + 1 + A, E = N * S, T = A + 1 + kGradStats, WMAX = D * kMlpMaxHidden + kMlpMaxHidden + A * (kMlpMaxHidden + 1) + kGradTail;
+    static_assert(V <= 64 && T <= 64, "one lane per reduced value");
+    __shared__ double slab[kGradWaves][WMAX];
+    const int H = net.hidden, P = mlp_policy_floats(D, A, H), W = P + kGradTail;
+    for (int i = (int)threadIdx.x; i < kGradWaves * WMAX; i += kBlock) (&slab[0][0])[i] = 0.0;
+    __syncthreads();
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    // where lane v's value of unit j stands: dW1[j][v], db1[j], dW2[v - D - 1][j]
+    const int unit_base = lane < D ? lane : (lane == D ? H * D : H * D + H + (lane - D - 1) * H), unit_stride = lane < D ? D : 1;
+    double* mine_slab = slab[wave];
+    const uint64_t lanes = (c.env_count + N - 1) / N, tiles_x = (lanes + kBlock - 1) / kBlock;
+    const uint64_t tiles = tiles_x * (uint64_t)((c.K + S - 1) / S);
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // block-uniform
+        const int32_t t0 = (int32_t)(tile / tiles_x) * S;
+        const int steps = c.K - t0 < S ? c.K - t0 : S;
+        const uint64_t q = (tile % tiles_x) * kBlock + threadIdx.x;
+        const bool in = q < lanes;
+        const uint64_t i0 = c.env_first + q * N;   // (in: i0 + N <= env_first + env_count <= n)
+        float o[E][D], ds[E][A], tail[T];
+#pragma unroll
+        for (int v = 0; v < T; ++v) tail[v] = 0.0f;
+        {
+            uint32_t w[E];
+            float x0[E], x1[E];
+#pragma unroll
+            for (int st = 0; st < S; ++st) {
+                const bool live = in && st < steps;
+                float ob[D][N], a0[N], a1[N];
+                uint32_t aw[N];
+#pragma unroll
+                for (int k = 0; k < N; ++k) { a0[k] = 0.0f; a1[k] = 0.0f; aw[k] = 0u; }
+#pragma unroll
+                for (int d = 0; d < D; ++d)
+#pragma unroll
+                    for (int k = 0; k < N; ++k) ob[d][k] = 0.0f;
+                if (live) {
+                    const int32_t t = t0 + st;
+                    const float* row = value_row_in(t, c.n, D, c.obs_first, c.obs);
+#pragma unroll
+                    for (int d = 0; d < D; ++d) grad_load<N>(row + (uint64_t)d * c.n, i0, ob[d]);
+                    grad_load<N>(c.x0 + (uint64_t)t * c.n, i0, a0);
+                    if constexpr (Head::kPpo) {
+                        grad_load<N>(c.actions + (uint64_t)t * c.n, i0, aw);
+                        grad_load<N>(c.x1 + (uint64_t)t * c.n, i0, a1);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+#pragma unroll
+                    for (int d = 0; d < D; ++d) o[st * N + k][d] = ob[d][k];
+                    w[st * N + k] = aw[k]; x0[st * N + k] = a0[k]; x1[st * N + k] = a1[k];
+                }
+            }
+            float s[E][A];
+            mlp_scores<D, A, ACT, E>(net, o, s);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const bool live = in && e / N < steps;
+                GradStep<A> g;
+                head.step(s[e], w[e], x0[e], x1[e], g);
+#pragma unroll
+                for (int a = 0; a < A; ++a) {
+                    ds[e][a] = live ? g.ds[a] : 0.0f;
+                    tail[a] += ds[e][a];
+                }
+                tail[A] += live ? g.dls : 0.0f;
+#pragma unroll
+                for (int k = 0; k < kGradStats; ++k) tail[A + 1 + k] += live ? g.stat[k] : 0.0f;
+            }
+        }
+        for (int j = 0; j < H; ++j) {
+            const float* u = net.unit[j];
+            float acc[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) acc[v] = 0.0f;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                if (e / N < steps) {   // block-uniform
+                    float h, dpre;
+                    grad_unit<D, A, ACT>(u, o[e], ds[e], &h, &dpre);
+#pragma unroll
+                    for (int d = 0; d < D; ++d) acc[d] = cp_fmaf(dpre, o[e][d], acc[d]);
+                    acc[D] += dpre;
+#pragma unroll
+                    for (int a = 0; a < A; ++a) acc[D + 1 + a] = cp_fmaf(ds[e][a], h, acc[D + 1 + a]);
+                }
+            }
+            float mine = 0.0f;
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const float r = grad_wave_sum(acc[v]);
+                mine = lane == v ? r : mine;
+            }
+            if (lane < V) mine_slab[unit_base + j * unit_stride] += (double)mine;
+        }
+        float mine = 0.0f;
+#pragma unroll
+        for (int v = 0; v < T; ++v) {
+            const float r = grad_wave_sum(tail[v]);
+            mine = lane == v ? r : mine;
+        }
+        if (lane < T) mine_slab[P - A + lane] += (double)mine;   // db2[0 .. A-1], the log-sigma sum, the five statistics' sums
+    }
+    __syncthreads();
+    double* out = c.workspace + (uint64_t)blockIdx.x * (uint64_t)W;
+    for (int i = (int)threadIdx.x; i < W; i += kBlock) out[i] = ((slab[0][i] + slab[1][i]) + slab[2][i]) + slab[3][i];
+}
+
+// the slabs added in index order, scaled and rounded: grad_out[0 .. P], stats_out[0 .. 7]
+__global__ void __launch_bounds__(kBlock) grad_finish_kernel(const double* ws, int slabs, int P, double B, float ent_coef, int gauss, float* grad_out, float* stats_out) {
+    const int out = (int)(blockIdx.x * kBlock + threadIdx.x), W = P + kGradTail;
+    if (out > P + kGradTail) return;
+    double sum = 0.0;
+    if (out <= P + kGradStats)
+        for (int s = 0; s < slabs; ++s) sum += ws[(uint64_t)s * (uint64_t)W + (uint64_t)out];
+    const float r = grad_result(sum, P, out, B, ent_coef, gauss != 0);
+    if (out <= P) grad_out[out] = r;
+    else stats_out[out - (P + 1)] = r;
+}
+
+constexpr uint64_t kGradFourMaxEnvs = 1ull << 30;   // the four-per-lane kernel addresses a row by a 32-bit byte offset
+
+template <int D, int A, int ACT, class Head>
+static void launch_form(hipStream_t stream, const GradCall& c, const MlpPack<D, A>& net, const Head& head) {
+    bool four = c.n % 4 == 0 && c.n < kGradFourMaxEnvs && c.env_first % 4 == 0 && c.env_count % 4 == 0 && aligned(c.obs_first, 16) && aligned(c.obs, 16) && aligned(c.x0, 16);
+    if (Head::kPpo) four = four && aligned(c.actions, 16) && aligned(c.x1, 16);
+    const uint64_t lanes = (c.env_count + (four ? 4 : 1) - 1) / (four ? 4 : 1), tiles_x = (lanes + kBlock - 1) / kBlock;
+    const auto tiles_at = [&](int S) { return tiles_x * (uint64_t)((c.K + S - 1) / S); };
+#if defined(GRAD_STEPS4)
+    const bool two = GRAD_STEPS4 == 2;
+#else
+    const bool two = tiles_at(2) >= kGradFillTiles;
+#endif
+    const uint64_t tiles = tiles_at(four ? (two ? 2 : 1) : kGradSteps1);
+    const unsigned blocks = (unsigned)(tiles < (uint64_t)c.slabs ? tiles : (uint64_t)c.slabs);
+    if (four && two) hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 4, 2>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
+    else if (four) hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 4, 1>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
+    else hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 1, kGradSteps1>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
+    const int P = mlp_policy_floats(D, A, net.hidden);
+    hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((P + kGradTail + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, c.workspace, (int)blocks, P,
+                       (double)c.K * (double)c.env_count, c.ent_coef, std::is_same<Head, PpoGaussian>::value ? 1 : 0, c.grad_out, c.stats_out);
+}
+
+template <int D, int A, class Head>
+static void launch_act(hipStream_t stream, const GradCall& c, const Head& head, const float* weights, int32_t hidden, int32_t act) {
+    static_assert(sizeof(MlpPack<8, 4>) + sizeof(PpoGaussian) + sizeof(GradCall) + 16 <= 4096, "grad kernels: by-value kernel arguments above 4096 bytes");
+    MlpPack<D, A> pack;
+    mlp_pack<D, A>(weights, hidden, pack);
+    if (act == MLP_ACT_RELU) launch_form<D, A, MLP_ACT_RELU>(stream, c, pack, head);
+    else if (act == MLP_ACT_TANH) launch_form<D, A, MLP_ACT_TANH>(stream, c, pack, head);
+    else launch_form<D, A, MLP_ACT_TANH_FAST>(stream, c, pack, head);
+}
+
+template <int D, int A>
+static void launch_family(hipStream_t stream, const GradCall& c, int head, const float* weights, int32_t hidden, int32_t act) {
+    const PpoTerms terms{c.lo, c.hi, c.ent_coef};
+    if (head == GRAD_HEAD_VALUE) launch_act<D, 1>(stream, c, ValueMse{}, weights, hidden, act);
+    else if constexpr (A == 1) launch_act<D, 1>(stream, c, PpoGaussian{terms, c.sigma, c.k, c.ent}, weights, hidden, act);
+    else launch_act<D, A>(stream, c, PpoCategorical<A>{terms}, weights, hidden, act);
+}
+
+int grad_launch(hipStream_t stream, const GradCall& c, int D, int A, int head, const float* weights, int32_t hidden, int32_t activation) {
+    switch (D * 10 + A) {
+    case 42: launch_family<4, 2>(stream, c, head, weights, hidden, activation); break;   // CartPole
+    case 23: launch_family<2, 3>(stream, c, head, weights, hidden, activation); break;   // MountainCar
+    case 21: launch_family<2, 1>(stream, c, head, weights, hidden, activation); break;   // MountainCarContinuous
+    case 31: launch_family<3, 1>(stream, c, head, weights, hidden, activation); break;   // Pendulum
+    case 63: launch_family<6, 3>(stream, c, head, weights, hidden, activation); break;   // Acrobot
+    case 84: launch_family<8, 4>(stream, c, head, weights, hidden, activation); break;   // LunarLander
+    default: set_last_error("mgym gradient call: no kernels for this family"); return MGYM_ERR_BAD_ARG;
+    }
+    MGYM_HIP(hipGetLastError());
+    return MGYM_OK;
+}
+
+}  // namespace mgym

@@ -247,4 +247,8 @@ MG_HD void mlp_actions(const MlpPack<D, 1>& p, const float (&o)[4][D], const uin
 }
 #endif
 
+// (grad.h restates two pieces of this header line for line, so that these stay as they are: mlp_hidden's chain in grad_unit, which also needs pre_j, and
+// mlp_sample_cum's weights in PpoCategorical::step, which needs the e_a themselves.  A change to either belongs in both places; tests/test_grad_host.py
+// compares the copies' words with the restatement of these.)
+
 }  // namespace mgym

@@ -462,6 +462,70 @@ class VecEnv:
         self.sync()
         return out.numpy().reshape(-1)[: K * n].reshape(K, n)
 
+    def grad_workspace_bytes(self, hidden):
+        """(min_bytes, best_bytes) of the workspace of ppo_grad_mlp_device / value_grad_mlp_device at this hidden width (mgym_grad_workspace_bytes): one slab of
+        partial sums, and the most a launch uses"""
+        lo, hi = C.c_size_t(), C.c_size_t()
+        _check(self._lib.mgym_grad_workspace_bytes(self.kind, int(hidden), C.byref(lo), C.byref(hi)))
+        return int(lo.value), int(hi.value)
+
+    def ppo_grad_mlp_device(self, policy, hidden, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip, ent_coef,
+                            workspace, workspace_bytes, grad_out, stats_out):
+        """mgym_ppo_grad_mlp on device buffers (pointers, DeviceArrays or tensors): PPO's clipped loss and the actor's gradient over the env-steps of environments
+        env_first .. env_first + env_count - 1 of a K-step rollout.  `policy` = the packed host floats of pack_mlp; obs_first, obs, actions as logprob_mlp_device
+        takes them, logp_old [K, n] its output, adv [K, n] gae_device's; workspace: 16-byte aligned, workspace_bytes of it (grad_workspace_bytes); grad_out
+        receives H (D + 1) + A (H + 1) + 1 floats (dW1, db1, dW2, db2 in nn.Linear order, d / d log sigma), stats_out 8.  On the env's stream, nothing
+        synchronised, nothing allocated."""
+        pol, act = self._mlp_args(policy, hidden, activation)
+        hd = _named(_HEADS, head, 'head must be "sample", "gauss" or an MGYM_HEAD_* value')
+        _check(self._lib.mgym_ppo_grad_mlp(self._h, _fptr(pol), int(hidden), act, hd, float(sigma), int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs),
+                                           _ptr(actions), _ptr(logp_old), _ptr(adv), float(clip), float(ent_coef), _ptr(workspace), int(workspace_bytes),
+                                           _ptr(grad_out), _ptr(stats_out)))
+
+    def value_grad_mlp_device(self, critic, hidden, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out):
+        """mgym_value_grad_mlp on device buffers: the loss 1/2 mean((V - ret)^2) of a one-hidden-layer critic (pack_critic's floats) and its gradient over the same
+        range; grad_out receives H (D + 1) + (H + 1) + 1 floats (the last +0), stats_out 8."""
+        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
+        h = int(hidden)
+        cr = None if critic is None else _policy_floats(critic, h * (self.obs_dim + 1) + h + 1 if 1 <= h <= 64 else None, f"hidden = {hidden}")
+        _check(self._lib.mgym_value_grad_mlp(self._h, _fptr(cr), h, act, int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs), _ptr(ret),
+                                             _ptr(workspace), int(workspace_bytes), _ptr(grad_out), _ptr(stats_out)))
+
+    def _grad_host(self, A, H, call, env_slice, workspace_bytes):
+        """the workspace and the outputs of a host-array gradient call -> (grad [P + 1], stats [8])"""
+        first, count = (0, self.n) if env_slice is None else env_slice
+        lo, hi = self.grad_workspace_bytes(H)
+        nbytes = hi if workspace_bytes is None else int(workspace_bytes)
+        ws = DeviceArray(max(nbytes, lo) // 8, np.float64, self.device)
+        P = H * (self.obs_dim + 1) + A * (H + 1)
+        grad, stats = DeviceArray(P + 1, np.float32, self.device), DeviceArray(8, np.float32, self.device)
+        call(first, count, ws, nbytes, grad, stats)
+        self.sync()
+        return grad.numpy().copy(), stats.numpy().copy()
+
+    def ppo_grad_mlp(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None,
+                     workspace_bytes=None):
+        """host-array form of ppo_grad_mlp_device: weights (w1, b1, w2, b2), obs_first [D, n], obs [K, D, n], actions, logp_old and adv [K, n] -> (grad [P + 1]
+        float32, stats [8] float32).  head: None takes the family's; env_slice: (first, count), None the full range; workspace_bytes: None takes best_bytes."""
+        policy, H = self.pack_mlp(*weights)
+        if head is None:
+            head = "gauss" if self.action_dtype == np.float32 else "sample"
+        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
+        of, ob = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n))
+        ac, lp, ad = self._dev(actions, self.action_dtype, (K, n)), self._dev(logp_old, np.float32, (K, n)), self._dev(adv, np.float32, (K, n))
+        return self._grad_host(self.mlp_dims()[1], H, lambda first, count, ws, nbytes, grad, stats: self.ppo_grad_mlp_device(
+            policy, H, activation, head, sigma, K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats), env_slice, workspace_bytes)
+
+    def value_grad_mlp(self, weights, obs_first, obs, ret, activation="relu", env_slice=None, workspace_bytes=None):
+        """host-array form of value_grad_mlp_device: a one-hidden-layer critic (w1, b1, w2 [1, H], b2 [1]) -> (grad [P + 1] float32, stats [8] float32)"""
+        critic, H, H2 = self.pack_critic(weights)
+        if H2:
+            raise PolicyShapeError(L.ERR_BAD_ARG, "value_grad_mlp takes a critic with one hidden layer")
+        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
+        of, ob, rt = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n)), self._dev(ret, np.float32, (K, n))
+        return self._grad_host(1, H, lambda first, count, ws, nbytes, grad, stats: self.value_grad_mlp_device(
+            critic, H, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats), env_slice, workspace_bytes)
+
     def episode_returns(self, reward, done, trunc, ep_return=None, ep_length=None):
         """host-array form of episode_returns_device: the carry in (None: zeros) -> (return_out [K, n] float32, length_out [K, n] uint32, both 0 where no
         episode ended, and the carry out: ep_return [n], ep_length [n])"""

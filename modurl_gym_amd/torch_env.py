@@ -66,6 +66,7 @@ class TorchVecEnv:
             self.final_obs = torch.zeros((int(final_obs_steps), self.obs_dim, self.n), dtype=f32, device=self.device)
             self.env.set_final_obs_out_device(self.final_obs, int(final_obs_steps))
         self._ep_return = self._ep_length = None   # the carry of episode_returns(), created by its first call
+        self._grad_ws = {}   # the workspaces of ppo_grad_mlp / value_grad_mlp, one per (hidden, stream), created by the first call that needs one
 
     # ---- plumbing -----------------------------------------------------------------------
     def _bind_stream(self):
@@ -281,6 +282,63 @@ class TorchVecEnv:
         logp = torch.empty((K, self.n), dtype=torch.float32, device=self.device)
         self.env.logprob_mlp_device(policy, h1, h2, activation, head, float(sigma), K, of, ob, ac, logp)
         return logp
+
+    def _grad_buffers(self, hidden, P):
+        """the cached workspace of this hidden width on torch's current stream — best_bytes of mgym_grad_workspace_bytes, 16-byte aligned; one per stream, so
+        that calls issued on two streams never share the slabs — and fresh outputs"""
+        torch = self._torch
+        key = (int(hidden), self._stream)   # (_bind_stream has made the engine's stream torch's current one)
+        if key not in self._grad_ws:
+            self._grad_ws[key] = torch.empty(self.env.grad_workspace_bytes(hidden)[1] // 8, dtype=torch.float64, device=self.device)
+        ws = self._grad_ws[key]
+        return ws, ws.numel() * 8, torch.empty(P + 1, dtype=torch.float32, device=self.device), torch.empty(8, dtype=torch.float32, device=self.device)
+
+    def _grad_views(self, grad, D, A, H, log_sigma):
+        o1, o2, o3 = H * D, H * D + H, H * D + H + A * H
+        views = (grad[:o1].view(H, D), grad[o1:o2], grad[o2:o3].view(A, H), grad[o3: o3 + A])
+        return views + ((grad[o3 + A:],) if log_sigma else ())
+
+    def ppo_grad_mlp(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None):
+        """PPO's clipped loss and the actor's gradient in one call (mgym_ppo_grad_mlp, include/mgym.h) in place of a torch forward pass, the surrogate and
+        autograd's backward pass.  weights: (w1, b1, w2, b2) of a one-hidden-layer actor, read on the host during the call; obs_first, obs, actions as
+        logprob_mlp takes them; logp_old [K, n]: logprob_mlp's output under the behaviour policy; adv [K, n]: gae's (normalise it yourself if you do);
+        env_slice = (first, count): the minibatch, the environments first .. first + count - 1 over all K steps (None: all of them).  Returns (grads, stats):
+        grads = (dw1, db1, dw2, db2) as views of one tensor, shaped like the weights — and d / d log sigma [1] under the Gaussian head; stats [8] float32:
+        policy loss, mean entropy, approximate KL, clipped fraction, mean ratio, the batch size, 0, 0.  Fresh tensors on torch's current stream; the workspace is
+        cached per (hidden, stream) of this object, which lives on one device."""
+        torch = self._torch
+        self._bind_stream()
+        host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
+        policy, H = self.env.pack_mlp(*host)
+        if head is None:
+            head = "gauss" if self.action_is_float else "sample"
+        K = int(obs.shape[0])
+        D, A = self.env.mlp_dims()
+        of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))
+        ac = self._kn(actions, torch.float32 if self.action_is_float else torch.int32, "actions", (K,))
+        lp, ad = self._kn(logp_old, torch.float32, "logp_old", (K,)), self._kn(adv, torch.float32, "adv", (K,))
+        first, count = (0, self.n) if env_slice is None else env_slice
+        ws, nbytes, grad, stats = self._grad_buffers(H, H * (D + 1) + A * (H + 1))
+        self.env.ppo_grad_mlp_device(policy, H, activation, head, float(sigma), K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats)
+        return self._grad_views(grad, D, A, H, head in ("gauss", E.L.HEAD_GAUSS)), stats
+
+    def value_grad_mlp(self, critic, obs_first, obs, ret, activation="relu", env_slice=None):
+        """The loss 1/2 mean((V - ret)^2) of a one-hidden-layer critic (w1, b1, w2 [1, H], b2 [1]) and its gradient in one call (mgym_value_grad_mlp): ret
+        [K, n] is gae's.  Returns (grads, stats): grads = (dw1, db1, dw2, db2) views shaped like the weights, stats [8] float32: the loss at [0], the batch size
+        at [5].  env_slice as in ppo_grad_mlp."""
+        torch = self._torch
+        self._bind_stream()
+        host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in critic]
+        packed, H, H2 = self.env.pack_critic(host)
+        if H2:
+            raise ValueError("value_grad_mlp takes a critic with one hidden layer")
+        K, D = int(obs.shape[0]), self.obs_dim
+        of, ob = self._kn(obs_first, torch.float32, "obs_first", (D,)), self._kn(obs, torch.float32, "obs", (K, D))
+        rt = self._kn(ret, torch.float32, "ret", (K,))
+        first, count = (0, self.n) if env_slice is None else env_slice
+        ws, nbytes, grad, stats = self._grad_buffers(H, H * (D + 1) + H + 1)
+        self.env.value_grad_mlp_device(packed, H, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats)
+        return self._grad_views(grad, D, 1, H, False), stats
 
     def episode_returns(self, reward, done, truncated):
         """The return and length of every episode that ended inside the rollout (mgym_episode_returns): (return_out float32 [K, n], length_out int32 [K, n]),

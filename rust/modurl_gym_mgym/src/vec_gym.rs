@@ -417,6 +417,65 @@ impl VecGym {
     ) -> Result<(), MgymError> {
         check(unsafe { mgym_logprob_mlp(self.env, policy.as_ptr(), hidden1, hidden2, activation, head, sigma, k, obs_first, obs, actions, logp_out) })
     }
+    /// `(min_bytes, best_bytes)` of the workspace of the gradient calls at this hidden width (`mgym_grad_workspace_bytes`).
+    pub fn grad_workspace_bytes(kind: i32, hidden: i32) -> Result<(usize, usize), MgymError> {
+        let (mut lo, mut hi) = (0usize, 0usize);
+        check(unsafe { mgym_grad_workspace_bytes(kind, hidden, &mut lo, &mut hi) })?;
+        Ok((lo, hi))
+    }
+    /// PPO's clipped loss and the actor's gradient over a rollout's buffers (`mgym_ppo_grad_mlp`, `include/mgym.h`).  `policy`: host floats in `nn.Linear`
+    /// order, one hidden layer; the range is the environments `env_first .. env_first + env_count` over all `k` steps; the other pointers are device
+    /// pointers: `workspace` 16-byte aligned, `grad_out` the parameters' gradient and one more word, `stats_out` 8 floats.
+    #[allow(clippy::too_many_arguments)]
+    pub fn ppo_grad_mlp(
+        &mut self,
+        policy: &[f32],
+        hidden: i32,
+        activation: i32,
+        head: i32,
+        sigma: f32,
+        k: i32,
+        env_first: u64,
+        env_count: u64,
+        obs_first: *const f32,
+        obs: *const f32,
+        actions: *const c_void,
+        logp_old: *const f32,
+        adv: *const f32,
+        clip: f32,
+        ent_coef: f32,
+        workspace: *mut c_void,
+        workspace_bytes: usize,
+        grad_out: *mut f32,
+        stats_out: *mut f32,
+    ) -> Result<(), MgymError> {
+        check(unsafe {
+            mgym_ppo_grad_mlp(self.env, policy.as_ptr(), hidden, activation, head, sigma, k, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip, ent_coef,
+                              workspace, workspace_bytes, grad_out, stats_out)
+        })
+    }
+    /// A one-hidden-layer critic's loss `1/2 mean((V - ret)^2)` and its gradient over the same range (`mgym_value_grad_mlp`).
+    #[allow(clippy::too_many_arguments)]
+    pub fn value_grad_mlp(
+        &mut self,
+        critic: &[f32],
+        hidden: i32,
+        activation: i32,
+        k: i32,
+        env_first: u64,
+        env_count: u64,
+        obs_first: *const f32,
+        obs: *const f32,
+        ret: *const f32,
+        workspace: *mut c_void,
+        workspace_bytes: usize,
+        grad_out: *mut f32,
+        stats_out: *mut f32,
+    ) -> Result<(), MgymError> {
+        check(unsafe {
+            mgym_value_grad_mlp(self.env, critic.as_ptr(), hidden, activation, k, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out)
+        })
+    }
     /// The return and length of the episodes that end inside a rollout (`mgym_episode_returns`): `ep_return` / `ep_length` are the caller's carry of the
     /// running episodes (read and written); `return_out` / `length_out` (`[K][n]`, may be null) are written only where `done | truncated`.
     #[allow(clippy::too_many_arguments)]
