@@ -336,20 +336,74 @@ struct PolicyArgs { int32_t K; const float* policy = nullptr; int32_t hidden = 0
 static_assert(MGYM_ACT_RELU == MLP_ACT_RELU && MGYM_ACT_TANH == MLP_ACT_TANH && MGYM_ACT_TANH_FAST == MLP_ACT_TANH_FAST, "mgym.h and mlp_policy.h number the activations alike");
 static_assert(MGYM_HEAD_GREEDY == MLP_HEAD_GREEDY && MGYM_HEAD_SAMPLE == MLP_HEAD_SAMPLE && MGYM_HEAD_GAUSS == MLP_HEAD_GAUSS, "mgym.h and mlp_policy.h number the heads alike");
 
+// ---- checks the policy entry points and the learner calls (mgym_value_mlp, mgym_logprob_mlp, the gradient calls) share ----
+// a call's refusal: "<api>: <what>" as the last error, MGYM_ERR_BAD_ARG
+struct Bad {
+    const char* api;
+    int operator()(const std::string& what) const { return bad_arg((std::string(api) + ": " + what).c_str()); }
+};
+
+// The widths, then the activation.  NET_HIDDEN: one layer, worded "hidden".  NET_ROLLOUT2: two layers, hidden2 from 1.  NET_LEARNER: "hidden1" and "hidden2",
+// hidden2 == 0 meaning one layer.  Two layers offer no exact tanh; the rollout and the learner calls word that refusal differently.
+enum NetNames { NET_HIDDEN, NET_ROLLOUT2, NET_LEARNER };
+static int net_shape_ok(const Bad& bad, int32_t h1, int32_t h2, int32_t activation, NetNames names) {
+    if (h1 < 1 || h1 > 64) return bad(names == NET_HIDDEN ? "hidden must be between 1 and 64" : "hidden1 must be between 1 and 64");
+    if (names == NET_ROLLOUT2 && (h2 < 1 || h2 > 64)) return bad("hidden2 must be between 1 and 64");
+    if (names == NET_LEARNER && (h2 < 0 || h2 > 64)) return bad("hidden2 must be between 0 (one hidden layer) and 64");
+    const bool two = names != NET_HIDDEN && h2 >= 1;
+    if (two && activation == MGYM_ACT_TANH)
+        return bad(std::string("activation MGYM_ACT_TANH is not offered with two hidden layers (") +
+                   (names == NET_ROLLOUT2 ? "the exact tanh would be nearly all of the launch" : "as in mgym_rollout_mlp2") + "): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
+    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH && activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
+        return bad(two ? "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST" : "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    return MGYM_OK;
+}
+
+// the head of a call that needs a density: a drawing head, the one the family's actions have, and for the Gaussian a sigma with a density
+static int density_head_ok(const Bad& bad, const Env* e, int32_t head, float sigma) {
+    if (head == MGYM_HEAD_GREEDY) return bad("head MGYM_HEAD_GREEDY: a deterministic policy has no density (use MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS)");
+    if (head != MGYM_HEAD_SAMPLE && head != MGYM_HEAD_GAUSS) return bad("head must be MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
+    if (head == MGYM_HEAD_SAMPLE && box_actions(e)) return bad(std::string("head MGYM_HEAD_SAMPLE: ") + kFamilies[e->cfg.kind].name + " has no discrete actions (use MGYM_HEAD_GAUSS)");
+    if (head == MGYM_HEAD_GAUSS && !box_actions(e)) return bad(std::string("head MGYM_HEAD_GAUSS: ") + kFamilies[e->cfg.kind].name + " has discrete actions (use MGYM_HEAD_SAMPLE)");
+    if (head == MGYM_HEAD_GAUSS && !logp_sigma_ok(sigma)) return bad("sigma must be a finite, normal, positive float (sigma == 0 has no density)");   // (a NaN fails the first test)
+    return MGYM_OK;
+}
+
+// A call's device pointers.  Alignments first, in table order (alignment 0: not checked here; a null optional pointer is skipped); then every output against
+// every input in table order and against the outputs before it — or, `any_output`, against every other output (mgym_value_mlp's wording).
+struct Pointer { const char* name; const void* p; bool out; size_t alignment; };
+static int pointers_ok(const Bad& bad, std::initializer_list<Pointer> table, bool any_output = false) {
+    for (const Pointer& f : table)
+        if (f.p && f.alignment && !aligned(f.p, f.alignment)) return bad(std::string(f.name) + " must be " + std::to_string(f.alignment) + "-byte aligned");
+    for (const Pointer& f : table) {
+        if (!f.out || !f.p) continue;
+        for (const Pointer& g : table)
+            if (!g.out && g.p == f.p) return bad(std::string(f.name) + " is the same pointer as " + g.name);
+        for (const Pointer& g : table) {
+            if (&g == &f && !any_output) break;
+            if (g.out && &g != &f && g.p == f.p) return bad(std::string(f.name) + " is the same pointer as " + g.name);
+        }
+    }
+    return MGYM_OK;
+}
+
+// a family's observation width and scores
+static int family_dims(int kind, int* D, int* A) {
+    mgym_spec spec;
+    if (const int st = mgym_get_spec(kind, &spec)) return st;
+    *D = spec.obs_dim;
+    *A = spec.n_actions ? spec.n_actions : 1;   // a continuous family has one score, the mean
+    return MGYM_OK;
+}
+
 static int policy_args_ok(const Env* e, const char* api, int takes, const std::string& refusal, const PolicyArgs& a) {
-    auto bad = [api](const std::string& what) { return bad_arg((std::string(api) + ": " + what).c_str()); };
-    const bool two = takes & TAKES_HIDDEN2;   // two hidden layers: "hidden1" and "hidden2", and no exact tanh
+    const Bad bad{api};
     if (a.K < 0) return bad("K < 0");
     FINAL_CAP_OR_FAIL(api, a.K);
     if (!refusal.empty() && !(takes & TAKES_HEAD)) return bad(refusal);
     if ((takes & TAKES_POLICY) && !a.policy) return bad("policy is NULL");
     if (takes & TAKES_HIDDEN) {
-        if (a.hidden < 1 || a.hidden > 64) return bad(two ? "hidden1 must be between 1 and 64" : "hidden must be between 1 and 64");
-        if (two && (a.hidden2 < 1 || a.hidden2 > 64)) return bad("hidden2 must be between 1 and 64");
-        if (two && a.activation == MGYM_ACT_TANH)
-            return bad("activation MGYM_ACT_TANH is not offered with two hidden layers (the exact tanh would be nearly all of the launch): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
-        if (a.activation != MGYM_ACT_RELU && a.activation != MGYM_ACT_TANH && a.activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
-            return bad(two ? "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST" : "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+        if (const int st = net_shape_ok(bad, a.hidden, a.hidden2, a.activation, (takes & TAKES_HIDDEN2) ? NET_ROLLOUT2 : NET_HIDDEN)) return st;
     }
     if (takes & TAKES_HEAD) {
         if (a.head != MGYM_HEAD_GREEDY && a.head != MGYM_HEAD_SAMPLE && a.head != MGYM_HEAD_GAUSS) return bad("head must be MGYM_HEAD_GREEDY, MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
@@ -457,36 +511,21 @@ int mgym_gae(mgym_env* env, int32_t K, const float* reward, const uint8_t* done,
 int mgym_value_mlp(mgym_env* env, const float* critic, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t K, const float* obs_first, const float* obs,
                    const float* final_obs, const uint8_t* done, const uint8_t* trunc, float* value_out, float* last_value_out, float* final_value_out) {
     ENV_OR_FAIL(env);
-    auto bad = [](const std::string& what) { return bad_arg(("mgym_value_mlp: " + what).c_str()); };
+    const Bad bad{"mgym_value_mlp"};
     if (K < 1) return bad("K must be at least 1");
     if (!critic) return bad("critic is NULL");
     if (!obs_first) return bad("obs_first is NULL");
     if (!obs) return bad("obs is NULL");
     if (!value_out) return bad("value_out is NULL");
     if (!last_value_out) return bad("last_value_out is NULL");
-    if (hidden1 < 1 || hidden1 > 64) return bad("hidden1 must be between 1 and 64");
-    if (hidden2 < 0 || hidden2 > 64) return bad("hidden2 must be between 0 (one hidden layer) and 64");
-    if (hidden2 >= 1 && activation == MGYM_ACT_TANH)
-        return bad("activation MGYM_ACT_TANH is not offered with two hidden layers (as in mgym_rollout_mlp2): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
-    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH && activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
-        return bad(hidden2 >= 1 ? "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST" : "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
+    if (const int st = net_shape_ok(bad, hidden1, hidden2, activation, NET_LEARNER)) return st;
     if (final_obs && !final_value_out) return bad("final_value_out is NULL while final_obs is not");
     if (final_value_out && !final_obs) return bad("final_obs is NULL while final_value_out is not");
     if (final_obs && !trunc) return bad("trunc is NULL while final_obs and final_value_out are not");
     if (!final_obs) done = trunc = nullptr;   // ignored without the final arguments
-    const struct { const char* name; const float* p; bool out; } fp[] = {{"obs_first", obs_first, false}, {"obs", obs, false}, {"final_obs", final_obs, false},
-                                                                         {"value_out", value_out, true}, {"last_value_out", last_value_out, true},
-                                                                         {"final_value_out", final_value_out, true}};
-    for (const auto& f : fp)
-        if (!aligned(f.p, 4)) return bad(std::string(f.name) + " must be 4-byte aligned");
-    const struct { const char* name; const void* p; } in[] = {{"obs_first", obs_first}, {"obs", obs}, {"final_obs", final_obs}, {"done", done}, {"trunc", trunc}};
-    for (const auto& f : fp) {
-        if (!f.out || !f.p) continue;
-        for (const auto& g : in)
-            if (f.p == g.p) return bad(std::string(f.name) + " is the same pointer as " + g.name);
-        for (const auto& g : fp)
-            if (g.out && g.p == f.p && g.name != f.name) return bad(std::string(f.name) + " is the same pointer as " + g.name);
-    }
+    if (const int st = pointers_ok(bad, {{"obs_first", obs_first, false, 4}, {"obs", obs, false, 4}, {"final_obs", final_obs, false, 4}, {"done", done, false, 0},
+                                         {"trunc", trunc, false, 0}, {"value_out", value_out, true, 4}, {"last_value_out", last_value_out, true, 4},
+                                         {"final_value_out", final_value_out, true, 4}}, true)) return st;
     if (e->n == 0) return MGYM_OK;
     if (hidden2 >= 1) { if (const int st = e->mlp2_store_to(e->value_dev, critic, e->obs_dim, 1, hidden1, hidden2)) return st; }
     return value_launch(e->stream, ValueCall{e->n, K, obs_first, obs, final_obs, done, trunc, value_out, last_value_out, final_value_out}, e->obs_dim, critic, hidden1,
@@ -496,36 +535,22 @@ int mgym_value_mlp(mgym_env* env, const float* critic, int32_t hidden1, int32_t 
 int mgym_logprob_mlp(mgym_env* env, const float* policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, int32_t K,
                      const float* obs_first, const float* obs, const void* actions, float* logp_out) {
     ENV_OR_FAIL(env);
-    auto bad = [](const std::string& what) { return bad_arg(("mgym_logprob_mlp: " + what).c_str()); };
+    const Bad bad{"mgym_logprob_mlp"};
     if (K < 1) return bad("K must be at least 1");
     if (!policy) return bad("policy is NULL");
     if (!obs_first) return bad("obs_first is NULL");
     if (!obs) return bad("obs is NULL");
     if (!actions) return bad("actions is NULL");
     if (!logp_out) return bad("logp_out is NULL");
-    if (hidden1 < 1 || hidden1 > 64) return bad("hidden1 must be between 1 and 64");
-    if (hidden2 < 0 || hidden2 > 64) return bad("hidden2 must be between 0 (one hidden layer) and 64");
-    if (hidden2 >= 1 && activation == MGYM_ACT_TANH)
-        return bad("activation MGYM_ACT_TANH is not offered with two hidden layers (as in mgym_rollout_mlp2): use MGYM_ACT_TANH_FAST or MGYM_ACT_RELU");
-    if (activation != MGYM_ACT_RELU && activation != MGYM_ACT_TANH && activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
-        return bad(hidden2 >= 1 ? "activation must be MGYM_ACT_RELU or MGYM_ACT_TANH_FAST" : "activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
-    if (head == MGYM_HEAD_GREEDY) return bad("head MGYM_HEAD_GREEDY: a deterministic policy has no density (use MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS)");
-    if (head != MGYM_HEAD_SAMPLE && head != MGYM_HEAD_GAUSS) return bad("head must be MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
-    if (head == MGYM_HEAD_SAMPLE && box_actions(e)) return bad(std::string("head MGYM_HEAD_SAMPLE: ") + kFamilies[e->cfg.kind].name + " has no discrete actions (use MGYM_HEAD_GAUSS)");
-    if (head == MGYM_HEAD_GAUSS && !box_actions(e)) return bad(std::string("head MGYM_HEAD_GAUSS: ") + kFamilies[e->cfg.kind].name + " has discrete actions (use MGYM_HEAD_SAMPLE)");
-    if (head == MGYM_HEAD_GAUSS && !logp_sigma_ok(sigma)) return bad("sigma must be a finite, normal, positive float (sigma == 0 has no density)");   // (a NaN fails the first test)
-    const struct { const char* name; const void* p; } dp[] = {{"obs_first", obs_first}, {"obs", obs}, {"actions", actions}, {"logp_out", logp_out}};
-    for (const auto& f : dp)
-        if (!aligned(f.p, 4)) return bad(std::string(f.name) + " must be 4-byte aligned");
-    for (int i = 0; i < 3; ++i)
-        if (dp[i].p == logp_out) return bad(std::string("logp_out is the same pointer as ") + dp[i].name);
+    if (const int st = net_shape_ok(bad, hidden1, hidden2, activation, NET_LEARNER)) return st;
+    if (const int st = density_head_ok(bad, e, head, sigma)) return st;
+    if (const int st = pointers_ok(bad, {{"obs_first", obs_first, false, 4}, {"obs", obs, false, 4}, {"actions", actions, false, 4}, {"logp_out", logp_out, true, 4}})) return st;
     if (e->n == 0) return MGYM_OK;
-    mgym_spec spec;
-    mgym_get_spec(e->cfg.kind, &spec);
-    const int A = spec.n_actions ? spec.n_actions : 1;   // a continuous family has one score, the mean
-    if (hidden2 >= 1) { if (const int st = e->mlp2_store_to(e->logp_dev, policy, e->obs_dim, A, hidden1, hidden2)) return st; }
+    int D = 0, A = 1;
+    if (const int st = family_dims(e->cfg.kind, &D, &A)) return st;
+    if (hidden2 >= 1) { if (const int st = e->mlp2_store_to(e->logp_dev, policy, D, A, hidden1, hidden2)) return st; }
     const float k = head == MGYM_HEAD_GAUSS ? logp_gauss_k(sigma) : 0.0f;   // f64 on the host, the header's own lines
-    return logprob_launch(e->stream, LogpCall{e->n, K, sigma, k, obs_first, obs, static_cast<const uint32_t*>(actions), logp_out}, e->obs_dim, A, policy, hidden1,
+    return logprob_launch(e->stream, LogpCall{e->n, K, sigma, k, obs_first, obs, static_cast<const uint32_t*>(actions), logp_out}, D, A, policy, hidden1,
                           hidden2, activation, e->logp_dev);
 }
 
@@ -547,16 +572,8 @@ struct GradArgs {
     float *grad_out, *stats_out;
 };
 
-static int family_dims(int kind, int* D, int* A) {
-    mgym_spec spec;
-    if (const int st = mgym_get_spec(kind, &spec)) return st;
-    *D = spec.obs_dim;
-    *A = spec.n_actions ? spec.n_actions : 1;   // a continuous family has one score, the mean
-    return MGYM_OK;
-}
-
 static int grad_call(Env* e, const GradArgs& a) {
-    auto bad = [&](const std::string& what) { return bad_arg((std::string(a.name) + ": " + what).c_str()); };
+    const Bad bad{a.name};
     const char *n0 = a.ppo ? "logp_old" : "ret", *wname = a.ppo ? "policy" : "critic";
     if (a.K < 1) return bad("K must be at least 1");
     if (!a.weights) return bad(std::string(wname) + " is NULL");
@@ -568,16 +585,8 @@ static int grad_call(Env* e, const GradArgs& a) {
     if (!a.workspace) return bad("workspace is NULL");
     if (!a.grad_out) return bad("grad_out is NULL");
     if (!a.stats_out) return bad("stats_out is NULL");
-    if (a.hidden < 1 || a.hidden > 64) return bad("hidden must be between 1 and 64");
-    if (a.activation != MGYM_ACT_RELU && a.activation != MGYM_ACT_TANH && a.activation != MGYM_ACT_TANH_FAST)   // (2 is not one)
-        return bad("activation must be MGYM_ACT_RELU, MGYM_ACT_TANH or MGYM_ACT_TANH_FAST");
-    if (a.ppo) {
-        if (a.head == MGYM_HEAD_GREEDY) return bad("head MGYM_HEAD_GREEDY: a deterministic policy has no density (use MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS)");
-        if (a.head != MGYM_HEAD_SAMPLE && a.head != MGYM_HEAD_GAUSS) return bad("head must be MGYM_HEAD_SAMPLE or MGYM_HEAD_GAUSS");
-        if (a.head == MGYM_HEAD_SAMPLE && box_actions(e)) return bad(std::string("head MGYM_HEAD_SAMPLE: ") + kFamilies[e->cfg.kind].name + " has no discrete actions (use MGYM_HEAD_GAUSS)");
-        if (a.head == MGYM_HEAD_GAUSS && !box_actions(e)) return bad(std::string("head MGYM_HEAD_GAUSS: ") + kFamilies[e->cfg.kind].name + " has discrete actions (use MGYM_HEAD_SAMPLE)");
-        if (a.head == MGYM_HEAD_GAUSS && !logp_sigma_ok(a.sigma)) return bad("sigma must be a finite, normal, positive float (sigma == 0 has no density)");
-    }
+    if (const int st = net_shape_ok(bad, a.hidden, 0, a.activation, NET_HIDDEN)) return st;
+    if (a.ppo) { if (const int st = density_head_ok(bad, e, a.head, a.sigma)) return st; }
     if (e->n != 0 && a.env_count == 0) return bad("env_count must be at least 1");   // (a handle without environments has no range to give: MGYM_OK below)
     if (e->n != 0 && (a.env_first > e->n || a.env_count > e->n - a.env_first)) return bad("env_first + env_count exceeds n_envs");
     if (a.ppo && !grad_clip_ok(a.clip)) return bad("clip must be at least 0 and below 1");
@@ -587,18 +596,9 @@ static int grad_call(Env* e, const GradArgs& a) {
     const uint64_t slab_bytes = grad_slab_bytes(D, A, a.hidden);
     if (a.workspace_bytes < slab_bytes) return bad("workspace_bytes is below min_bytes of mgym_grad_workspace_bytes (" + std::to_string(slab_bytes) + ")");
     if (!aligned(a.workspace, 16)) return bad("workspace must be 16-byte aligned");
-    const struct { const char* name; const void* p; } in[] = {{"obs_first", a.obs_first}, {"obs", a.obs}, {"actions", a.actions}, {n0, a.x0}, {"adv", a.x1}};
-    const struct { const char* name; const void* p; } out[] = {{"workspace", a.workspace}, {"grad_out", a.grad_out}, {"stats_out", a.stats_out}};
-    for (const auto& f : in)
-        if (f.p && !aligned(f.p, 4)) return bad(std::string(f.name) + " must be 4-byte aligned");
-    for (int i = 1; i < 3; ++i)
-        if (!aligned(out[i].p, 4)) return bad(std::string(out[i].name) + " must be 4-byte aligned");
-    for (int i = 0; i < 3; ++i) {
-        for (const auto& f : in)
-            if (f.p && f.p == out[i].p) return bad(std::string(out[i].name) + " is the same pointer as " + f.name);
-        for (int k = 0; k < i; ++k)
-            if (out[k].p == out[i].p) return bad(std::string(out[i].name) + " is the same pointer as " + out[k].name);
-    }
+    if (const int st = pointers_ok(bad, {{"obs_first", a.obs_first, false, 4}, {"obs", a.obs, false, 4}, {"actions", a.actions, false, 4}, {n0, a.x0, false, 4},
+                                         {"adv", a.x1, false, 4}, {"workspace", a.workspace, true, 0}, {"grad_out", a.grad_out, true, 4}, {"stats_out", a.stats_out, true, 4}}))
+        return st;
     if (e->n == 0) return MGYM_OK;
     const uint64_t fit = a.workspace_bytes / slab_bytes;
     GradCall c{};

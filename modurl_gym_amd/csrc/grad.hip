@@ -9,8 +9,7 @@
 // of its tiles (a block strides over them when there are more tiles than slabs) the block adds its four waves' slabs in wave order and stores one f64 slab to
 // the workspace.  The second launch adds the slabs in index order in f64, scales by 1 / B, rounds to f32 and writes grad_out and stats_out.  No atomics, no
 // tickets: the order of every sum is a function of the arguments alone.  A word outside the environments' range or beyond step K - 1 is never loaded.
-#include "common.h"
-#include "grad.h"
+#include "learner.h"
 
 namespace mgym {
 
@@ -55,17 +54,12 @@ __device__ __forceinline__ float grad_wave_sum(float x) {
 }
 #endif
 
-template <class V, class T>
-__device__ __forceinline__ const V& grad_word_at(const T* row, uint32_t off) {
-    return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(row) + off);
-}
-
 // N words of row `row` ([n] each) at environments i .. i + N - 1; the four-per-lane form by one 16-byte load at a 32-bit byte offset
 template <int N, class T>
 __device__ __forceinline__ void grad_load(const T* row, uint64_t i, T (&out)[N]) {
     if constexpr (N == 4) {
         typedef typename std::conditional<std::is_same<T, float>::value, float4, uint4>::type V4;
-        const V4 v = grad_word_at<V4>(row, (uint32_t)i * 4u);
+        const V4 v = word_at<const V4>(row, (uint32_t)i * 4u);
         out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
     } else {
         out[0] = row[i];
@@ -194,11 +188,9 @@ __global__ void __launch_bounds__(kBlock) grad_finish_kernel(const double* ws, i
     else stats_out[out - (P + 1)] = r;
 }
 
-constexpr uint64_t kGradFourMaxEnvs = 1ull << 30;   // the four-per-lane kernel addresses a row by a 32-bit byte offset
-
 template <int D, int A, int ACT, class Head>
 static void launch_form(hipStream_t stream, const GradCall& c, const MlpPack<D, A>& net, const Head& head) {
-    bool four = c.n % 4 == 0 && c.n < kGradFourMaxEnvs && c.env_first % 4 == 0 && c.env_count % 4 == 0 && aligned(c.obs_first, 16) && aligned(c.obs, 16) && aligned(c.x0, 16);
+    bool four = four_per_lane(c.n, c.obs_first, c.obs, c.x0) && c.env_first % 4 == 0 && c.env_count % 4 == 0;
     if (Head::kPpo) four = four && aligned(c.actions, 16) && aligned(c.x1, 16);
     const uint64_t lanes = (c.env_count + (four ? 4 : 1) - 1) / (four ? 4 : 1), tiles_x = (lanes + kBlock - 1) / kBlock;
     const auto tiles_at = [&](int S) { return tiles_x * (uint64_t)((c.K + S - 1) / S); };
@@ -219,34 +211,18 @@ static void launch_form(hipStream_t stream, const GradCall& c, const MlpPack<D, 
 
 template <int D, int A, class Head>
 static void launch_act(hipStream_t stream, const GradCall& c, const Head& head, const float* weights, int32_t hidden, int32_t act) {
-    static_assert(sizeof(MlpPack<8, 4>) + sizeof(PpoGaussian) + sizeof(GradCall) + 16 <= 4096, "grad kernels: by-value kernel arguments above 4096 bytes");
     MlpPack<D, A> pack;
     mlp_pack<D, A>(weights, hidden, pack);
-    if (act == MLP_ACT_RELU) launch_form<D, A, MLP_ACT_RELU>(stream, c, pack, head);
-    else if (act == MLP_ACT_TANH) launch_form<D, A, MLP_ACT_TANH>(stream, c, pack, head);
-    else launch_form<D, A, MLP_ACT_TANH_FAST>(stream, c, pack, head);
-}
-
-template <int D, int A>
-static void launch_family(hipStream_t stream, const GradCall& c, int head, const float* weights, int32_t hidden, int32_t act) {
-    const PpoTerms terms{c.lo, c.hi, c.ent_coef};
-    if (head == GRAD_HEAD_VALUE) launch_act<D, 1>(stream, c, ValueMse{}, weights, hidden, act);
-    else if constexpr (A == 1) launch_act<D, 1>(stream, c, PpoGaussian{terms, c.sigma, c.k, c.ent}, weights, hidden, act);
-    else launch_act<D, A>(stream, c, PpoCategorical<A>{terms}, weights, hidden, act);
+    with_activation(act, std::false_type{}, [&](auto ACT) { launch_form<D, A, ACT.value>(stream, c, pack, head); });
 }
 
 int grad_launch(hipStream_t stream, const GradCall& c, int D, int A, int head, const float* weights, int32_t hidden, int32_t activation) {
-    switch (D * 10 + A) {
-    case 42: launch_family<4, 2>(stream, c, head, weights, hidden, activation); break;   // CartPole
-    case 23: launch_family<2, 3>(stream, c, head, weights, hidden, activation); break;   // MountainCar
-    case 21: launch_family<2, 1>(stream, c, head, weights, hidden, activation); break;   // MountainCarContinuous
-    case 31: launch_family<3, 1>(stream, c, head, weights, hidden, activation); break;   // Pendulum
-    case 63: launch_family<6, 3>(stream, c, head, weights, hidden, activation); break;   // Acrobot
-    case 84: launch_family<8, 4>(stream, c, head, weights, hidden, activation); break;   // LunarLander
-    default: set_last_error("mgym gradient call: no kernels for this family"); return MGYM_ERR_BAD_ARG;
-    }
-    MGYM_HIP(hipGetLastError());
-    return MGYM_OK;
+    return with_family(D, A, "mgym gradient call: no kernels for this family", [&](auto d, auto a) {
+        const PpoTerms terms{c.lo, c.hi, c.ent_coef};
+        if (head == GRAD_HEAD_VALUE) launch_act<d.value, 1>(stream, c, ValueMse{}, weights, hidden, activation);
+        else if constexpr (a.value == 1) launch_act<d.value, 1>(stream, c, PpoGaussian{terms, c.sigma, c.k, c.ent}, weights, hidden, activation);
+        else launch_act<d.value, a.value>(stream, c, PpoCategorical<a.value>{terms}, weights, hidden, activation);
+    });
 }
 
 }  // namespace mgym

@@ -107,6 +107,12 @@ struct LogpCall {
     const float *obs_first, *obs;
     const uint32_t* actions;
     float* logp_out;
+    // what learner.h's dense kernel asks of a call: steps 0 .. K - 1, the step's action row, the family's head
+    static constexpr bool kActions = true;
+    __device__ __forceinline__ int32_t rows() const { return K; }
+    __device__ __forceinline__ float* out_row(int32_t r) const { return logp_out + (uint64_t)r * n; }
+    __device__ __forceinline__ const uint32_t* action_row(int32_t r) const { return actions + (uint64_t)r * n; }
+    template <int A> __device__ __forceinline__ float word(const float (&s)[A], uint32_t w) const { return logp_head<A>(s, w, sigma, k); }
 };
 int logprob_launch(hipStream_t stream, const LogpCall& call, int D, int A, const float* policy, int32_t hidden1, int32_t hidden2, int32_t activation, const float* pack_dev);
 #endif

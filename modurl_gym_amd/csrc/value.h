@@ -59,6 +59,11 @@ struct ValueCall {
     const float *obs_first, *obs, *final_obs;
     const uint8_t *done, *trunc;
     float *value_out, *last_value_out, *final_value_out;
+    // what learner.h's dense kernel asks of a call: rows 0 .. K, no action row, the one score
+    static constexpr bool kActions = false;
+    __device__ __forceinline__ int32_t rows() const { return K + 1; }
+    __device__ __forceinline__ float* out_row(int32_t r) const { return value_row_out(r, K, n, value_out, last_value_out); }
+    template <int A> __device__ __forceinline__ float word(const float (&s)[A], uint32_t) const { return s[0]; }
 };
 int value_launch(hipStream_t stream, const ValueCall& call, int D, const float* critic, int32_t hidden1, int32_t hidden2, int32_t activation, const float* pack_dev);
 #endif

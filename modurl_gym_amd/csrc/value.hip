@@ -1,7 +1,7 @@
 // value.hip — mgym_value_mlp (include/mgym.h): a critic's values over a rollout's observation rows, the words of value.h.
 //
 // Dense pass, one launch: the (K + 1) x n independent evaluations of value_out and last_value_out.  Four-per-lane form (n % 4 == 0 and below 2^30, float
-// pointers 16-byte aligned): a lane owns four consecutive environments of one row, loads the row's D components as D 16-byte words, runs
+// pointers 16-byte aligned), the dense kernel of learner.h with ValueCall: a lane owns four consecutive environments of one row, loads the row's D components as D 16-byte words, runs
 // mlp_scores<D, 1, ACT, 4> — the weights are scalar operands of its packed chains — and stores one 16-byte word.  A row's address is a wave-uniform 64-bit
 // base plus the lane's 32-bit byte offset, as in gae.hip; blockIdx.y is the row, so a wave walks one row per weight fetch (rows beyond the grid's 65535 by a
 // stride loop).  Otherwise one environment per lane with 64-bit addresses, the same words.
@@ -12,34 +12,9 @@
 // Phase 2 evaluates the list 64 entries at a time, one environment per lane: D sparse 4-byte loads of final_obs, mlp_scores<D, 1, ACT, 1>, one 4-byte store.
 // No global queue and no atomics: every output word is a pure function of its own inputs, so the list's order reaches no result.  A word of final_obs
 // outside the selection is never loaded.
-#include "common.h"
-#include "value.h"
+#include "learner.h"
 
 namespace mgym {
-
-template <class V, class T>
-__device__ __forceinline__ V& word_at(T* row, uint32_t off) {
-    typedef typename std::conditional<std::is_const<T>::value, const char, char>::type Byte;
-    return *reinterpret_cast<V*>(reinterpret_cast<Byte*>(row) + off);
-}
-
-template <int D, int ACT, class Net>
-__global__ void __launch_bounds__(kBlock) value4_kernel(const Net net, const ValueCall a) {
-    const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;   // (n < 2^30: lanes and byte offsets fit 32 bits)
-    if (lane >= (uint32_t)(a.n / 4)) return;
-    const uint32_t off16 = lane * 16u;
-    for (int32_t r = (int32_t)blockIdx.y; r <= a.K; r += (int32_t)gridDim.y) {   // wave-uniform
-        const float* in = value_row_in(r, a.n, D, a.obs_first, a.obs);
-        float4 c[D];
-#pragma unroll
-        for (int q = 0; q < D; ++q) c[q] = word_at<const float4>(in + (uint64_t)q * a.n, off16);
-        float o[4][D], s[4][1];
-#pragma unroll
-        for (int q = 0; q < D; ++q) { o[0][q] = c[q].x; o[1][q] = c[q].y; o[2][q] = c[q].z; o[3][q] = c[q].w; }
-        mlp_scores<D, 1, ACT, 4>(net, o, s);
-        word_at<float4>(value_row_out(r, a.K, a.n, a.value_out, a.last_value_out), off16) = make_float4(s[0][0], s[1][0], s[2][0], s[3][0]);
-    }
-}
 
 template <int D, int ACT, class Net>
 __global__ void __launch_bounds__(kBlock) value1_kernel(const Net net, const ValueCall a) {
@@ -115,50 +90,22 @@ __global__ void __launch_bounds__(64) value_final_kernel(const Net net, const Va
     }
 }
 
-constexpr uint64_t kFourMaxEnvs = 1ull << 30;   // the four-per-lane kernel addresses a row by a 32-bit byte offset
-constexpr unsigned kMaxGridY = 65535u;
-
 template <int D, int ACT, class Net>
 static void launch_all(hipStream_t stream, const ValueCall& c, const Net& net) {
-    const bool four = c.n % 4 == 0 && c.n < kFourMaxEnvs && aligned(c.obs_first, 16) && aligned(c.obs, 16) && aligned(c.value_out, 16) && aligned(c.last_value_out, 16);
-    const unsigned rows = (unsigned)c.K + 1u < kMaxGridY ? (unsigned)c.K + 1u : kMaxGridY;
-    if (four) hipLaunchKernelGGL((value4_kernel<D, ACT, Net>), dim3((unsigned)((c.n / 4 + kBlock - 1) / kBlock), rows), dim3(kBlock), 0, stream, net, c);
-    else hipLaunchKernelGGL((value1_kernel<D, ACT, Net>), dim3((unsigned)((c.n + kBlock - 1) / kBlock), rows), dim3(kBlock), 0, stream, net, c);
+    launch_dense<D, 1, ACT>(stream, c, net, four_per_lane(c.n, c.obs_first, c.obs, c.value_out, c.last_value_out), (unsigned)c.K + 1u, value1_kernel<D, ACT, Net>);
     if (c.final_obs) {
         const int words = c.n % 4 == 0 && aligned(c.done, 4) && aligned(c.trunc, 4) ? 1 : 0;   // (a null done is aligned)
-        const unsigned chunks = (unsigned)((c.K + kValueChunk - 1) / kValueChunk);
-        hipLaunchKernelGGL((value_final_kernel<D, ACT, Net>), dim3((unsigned)((c.n + kValueWaveEnvs - 1) / kValueWaveEnvs), chunks < kMaxGridY ? chunks : kMaxGridY),
+        hipLaunchKernelGGL((value_final_kernel<D, ACT, Net>), dim3((unsigned)((c.n + kValueWaveEnvs - 1) / kValueWaveEnvs), grid_rows((unsigned)((c.K + kValueChunk - 1) / kValueChunk))),
                            dim3(64), 0, stream, net, c, words);
     }
 }
 
-template <int D>
-static void launch_dim(hipStream_t stream, const ValueCall& c, const float* critic, int32_t h1, int32_t h2, int32_t act, const float* pack_dev) {
-    if (h2 == 0) {
-        static_assert(sizeof(MlpPack<8, 1>) == 2568 && sizeof(MlpPack<8, 1>) + sizeof(ValueCall) + 16 <= 4096, "value kernels: by-value kernel arguments above 4096 bytes");
-        MlpPack<D, 1> pack;
-        mlp_pack<D, 1>(critic, h1, pack);
-        if (act == MLP_ACT_RELU) launch_all<D, MLP_ACT_RELU>(stream, c, pack);
-        else if (act == MLP_ACT_TANH) launch_all<D, MLP_ACT_TANH>(stream, c, pack);
-        else launch_all<D, MLP_ACT_TANH_FAST>(stream, c, pack);
-    } else {
-        const Mlp2Net<D, 1> net{pack_dev, h1, h2, 0.0f};
-        if (act == MLP_ACT_RELU) launch_all<D, MLP_ACT_RELU>(stream, c, net);
-        else launch_all<D, MLP_ACT_TANH_FAST>(stream, c, net);
-    }
-}
-
 int value_launch(hipStream_t stream, const ValueCall& c, int D, const float* critic, int32_t hidden1, int32_t hidden2, int32_t activation, const float* pack_dev) {
-    switch (D) {
-    case 2: launch_dim<2>(stream, c, critic, hidden1, hidden2, activation, pack_dev); break;
-    case 3: launch_dim<3>(stream, c, critic, hidden1, hidden2, activation, pack_dev); break;
-    case 4: launch_dim<4>(stream, c, critic, hidden1, hidden2, activation, pack_dev); break;
-    case 6: launch_dim<6>(stream, c, critic, hidden1, hidden2, activation, pack_dev); break;
-    case 8: launch_dim<8>(stream, c, critic, hidden1, hidden2, activation, pack_dev); break;
-    default: set_last_error("mgym_value_mlp: no kernels for this observation width"); return MGYM_ERR_BAD_ARG;
-    }
-    MGYM_HIP(hipGetLastError());
-    return MGYM_OK;
+    return with_family(D, 0, "mgym_value_mlp: no kernels for this observation width", [&](auto d, auto) {
+        with_net<d.value, 1>(critic, hidden1, hidden2, pack_dev, 0.0f, [&](const auto& net, auto two) {
+            with_activation(activation, two, [&](auto act) { launch_all<d.value, act.value>(stream, c, net); });
+        });
+    });
 }
 
 }  // namespace mgym

@@ -123,12 +123,24 @@ _ACTIVATIONS = {"relu": L.ACT_RELU, "tanh": L.ACT_TANH, "tanh_fast": L.ACT_TANH_
 _HEADS = {"greedy": L.HEAD_GREEDY, "sample": L.HEAD_SAMPLE, "gauss": L.HEAD_GAUSS}
 
 
+_ACT_WORDING = 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value'
+_DENSITY_HEAD_WORDING = 'head must be "sample", "gauss" or an MGYM_HEAD_* value'   # (the calls that need a density take no "greedy")
+
+
 def _named(names, value, wording):
     """names[value], or the integer value itself; anything else raises PolicyShapeError with `wording`"""
     v = names.get(value, value)
     if not isinstance(v, (int, np.integer)):
         raise PolicyShapeError(L.ERR_BAD_ARG, f"{wording}, got {value!r}")
     return int(v)
+
+
+def _mlp_floats(D, A, h1, h2=0):
+    """the packed float32 words of a net D -> h1 (-> h2) -> A, h2 = 0 for one hidden layer; None when a width is out of range (the engine rejects the call for
+    it first)"""
+    if not (1 <= h1 <= 64 and 0 <= h2 <= 64):
+        return None
+    return h1 * (D + 1) + (h2 * (h1 + 1) + A * (h2 + 1) if h2 else A * (h1 + 1))
 
 
 def _policy_floats(policy, want, what):
@@ -280,10 +292,12 @@ class VecEnv:
 
     def _mlp_args(self, policy, hidden, activation):
         """(contiguous float32 policy or None, activation value) of the hidden-layer entry points, the policy's length checked against H and the family"""
-        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
-        (D, A), h = self.mlp_dims(), int(hidden)
-        want = h * (D + 1) + A * (h + 1) if 1 <= h <= 64 else None
-        return None if policy is None else _policy_floats(policy, want, f"hidden = {hidden}"), act
+        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
+        return None if policy is None else _policy_floats(policy, _mlp_floats(*self.mlp_dims(), int(hidden)), f"hidden = {hidden}"), act
+
+    def _family_head(self):
+        """the head a family's actions have: the name a call takes where `head` is None"""
+        return "gauss" if self.action_dtype == np.float32 else "sample"
 
     def rollout_mlp_device(self, policy, hidden, activation, K, actions_out=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None):
         """K fused steps under the on-device one-hidden-layer policy (mgym_rollout_mlp): `policy` = the packed host floats of pack_mlp (or None, which the
@@ -409,12 +423,9 @@ class VecEnv:
         rejects), hidden2 = 0 for one hidden layer; obs_first [D, n], obs [K, D, n], final_obs [K, D, n] or None, done / trunc uint8 [K, n] or None; value_out
         [K, n], last_value_out [n], final_value_out [K, n] or None — written only where trunc && !done, final_obs read only there.  The three outputs are
         gae_device's value, last_value and final_value.  On the env's stream, nothing synchronised.  A critic of the wrong length raises PolicyShapeError."""
-        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
-        D, h1, h2 = self.obs_dim, int(hidden1), int(hidden2)
-        want = None
-        if 1 <= h1 <= 64 and 0 <= h2 <= 64:
-            want = h1 * (D + 1) + (h2 * (h1 + 1) + h2 + 1 if h2 else h1 + 1)
-        pol = None if critic is None else _policy_floats(critic, want, f"hidden1 = {h1}, hidden2 = {h2}")
+        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
+        h1, h2 = int(hidden1), int(hidden2)
+        pol = None if critic is None else _policy_floats(critic, _mlp_floats(self.obs_dim, 1, h1, h2), f"hidden1 = {h1}, hidden2 = {h2}")
         _check(self._lib.mgym_value_mlp(self._h, _fptr(pol), h1, h2, act, int(K), _ptr(obs_first), _ptr(obs), _ptr(final_obs), _ptr(done), _ptr(trunc),
                                         _ptr(value_out), _ptr(last_value_out), _ptr(final_value_out)))
 
@@ -437,13 +448,10 @@ class VecEnv:
         by "sample"); obs_first [D, n], obs [K, D, n] and actions [K, n] (uint32 or float32 words) are a rollout's buffers, logp_out [K, n] receives the
         log-probability of each action under the distribution the rollout drew from.  On the env's stream, nothing synchronised.  A policy of the wrong length
         raises PolicyShapeError."""
-        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
-        hd = _named(_HEADS, head, 'head must be "sample", "gauss" or an MGYM_HEAD_* value')
-        (D, A), h1, h2 = self.mlp_dims(), int(hidden1), int(hidden2)
-        want = None
-        if 1 <= h1 <= 64 and 0 <= h2 <= 64:
-            want = h1 * (D + 1) + (h2 * (h1 + 1) + A * (h2 + 1) if h2 else A * (h1 + 1))
-        pol = None if policy is None else _policy_floats(policy, want, f"hidden1 = {h1}, hidden2 = {h2}")
+        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
+        hd = _named(_HEADS, head, _DENSITY_HEAD_WORDING)
+        h1, h2 = int(hidden1), int(hidden2)
+        pol = None if policy is None else _policy_floats(policy, _mlp_floats(*self.mlp_dims(), h1, h2), f"hidden1 = {h1}, hidden2 = {h2}")
         _check(self._lib.mgym_logprob_mlp(self._h, _fptr(pol), h1, h2, act, hd, float(sigma), int(K), _ptr(obs_first), _ptr(obs), _ptr(actions), _ptr(logp_out)))
 
     def logprob_mlp(self, weights, obs_first, obs, actions, activation="relu", head=None, sigma=0.0):
@@ -453,7 +461,7 @@ class VecEnv:
             raise PolicyShapeError(L.ERR_BAD_ARG, f"a policy is (w1, b1, w2, b2) or (w1, b1, w2, b2, w3, b3); got {len(weights)} arrays")
         policy, H1, H2 = (*self.pack_mlp(*weights), 0) if len(weights) == 4 else self.pack_mlp2(*weights)
         if head is None:
-            head = "gauss" if self.action_dtype == np.float32 else "sample"
+            head = self._family_head()
         K, D, n = np.shape(obs)[0], self.obs_dim, self.n
         of, ob = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n))
         ac = self._dev(actions, self.action_dtype, (K, n))
@@ -477,7 +485,7 @@ class VecEnv:
         receives H (D + 1) + A (H + 1) + 1 floats (dW1, db1, dW2, db2 in nn.Linear order, d / d log sigma), stats_out 8.  On the env's stream, nothing
         synchronised, nothing allocated."""
         pol, act = self._mlp_args(policy, hidden, activation)
-        hd = _named(_HEADS, head, 'head must be "sample", "gauss" or an MGYM_HEAD_* value')
+        hd = _named(_HEADS, head, _DENSITY_HEAD_WORDING)
         _check(self._lib.mgym_ppo_grad_mlp(self._h, _fptr(pol), int(hidden), act, hd, float(sigma), int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs),
                                            _ptr(actions), _ptr(logp_old), _ptr(adv), float(clip), float(ent_coef), _ptr(workspace), int(workspace_bytes),
                                            _ptr(grad_out), _ptr(stats_out)))
@@ -485,9 +493,9 @@ class VecEnv:
     def value_grad_mlp_device(self, critic, hidden, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out):
         """mgym_value_grad_mlp on device buffers: the loss 1/2 mean((V - ret)^2) of a one-hidden-layer critic (pack_critic's floats) and its gradient over the same
         range; grad_out receives H (D + 1) + (H + 1) + 1 floats (the last +0), stats_out 8."""
-        act = _named(_ACTIVATIONS, activation, 'activation must be "relu", "tanh", "tanh_fast" or an MGYM_ACT_* value')
+        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
         h = int(hidden)
-        cr = None if critic is None else _policy_floats(critic, h * (self.obs_dim + 1) + h + 1 if 1 <= h <= 64 else None, f"hidden = {hidden}")
+        cr = None if critic is None else _policy_floats(critic, _mlp_floats(self.obs_dim, 1, h), f"hidden = {hidden}")
         _check(self._lib.mgym_value_grad_mlp(self._h, _fptr(cr), h, act, int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs), _ptr(ret),
                                              _ptr(workspace), int(workspace_bytes), _ptr(grad_out), _ptr(stats_out)))
 
@@ -509,7 +517,7 @@ class VecEnv:
         float32, stats [8] float32).  head: None takes the family's; env_slice: (first, count), None the full range; workspace_bytes: None takes best_bytes."""
         policy, H = self.pack_mlp(*weights)
         if head is None:
-            head = "gauss" if self.action_dtype == np.float32 else "sample"
+            head = self._family_head()
         K, D, n = np.shape(obs)[0], self.obs_dim, self.n
         of, ob = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n))
         ac, lp, ad = self._dev(actions, self.action_dtype, (K, n)), self._dev(logp_old, np.float32, (K, n)), self._dev(adv, np.float32, (K, n))

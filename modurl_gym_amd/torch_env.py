@@ -275,7 +275,7 @@ class TorchVecEnv:
             raise ValueError(f"a policy is (w1, b1, w2, b2) or (w1, b1, w2, b2, w3, b3); got {len(host)} arrays")
         policy, h1, h2 = (*self.env.pack_mlp(*host), 0) if len(host) == 4 else self.env.pack_mlp2(*host)
         if head is None:
-            head = "gauss" if self.action_is_float else "sample"
+            head = self.env._family_head()
         K = int(obs.shape[0])
         of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))
         ac = self._kn(actions, torch.float32 if self.action_is_float else torch.int32, "actions", (K,))
@@ -311,7 +311,7 @@ class TorchVecEnv:
         host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
         policy, H = self.env.pack_mlp(*host)
         if head is None:
-            head = "gauss" if self.action_is_float else "sample"
+            head = self.env._family_head()
         K = int(obs.shape[0])
         D, A = self.env.mlp_dims()
         of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))

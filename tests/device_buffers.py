@@ -1,9 +1,11 @@
-"""The device memory a GPU test hands to the engine, once: a slab between guard words that shows what a kernel did not write (Guarded), the caller's
+"""The device memory a GPU test hands to the engine, once: a slab between guard words that shows what a kernel did not write (Guarded), the refusal of a call's bad argument (bad_arg), the caller's
 final-observation buffer on it (FinalBuf), the five buffers of a call (CallBuffers), the call of a named action source (policy_call) and the twin loop
 that shows what a step produced before the fused reset (twin_steps).  tests/test_support.py checks the checkers on host memory.  No test here."""
 import numpy as np
+import pytest
 
 import modurl_gym_amd as mg
+from modurl_gym_amd import _lib
 from words import bits, same
 
 F = np.float32
@@ -41,6 +43,13 @@ class Guarded:
 
     def untouched(self):
         return bool(np.array_equal(self.dev.numpy(), self.initial))
+
+
+def bad_arg(fn, name, *needles):
+    """fn() is refused as a bad argument, in one message of entry point `name` that holds every needle"""
+    with pytest.raises(mg.MgymError) as ei:
+        fn()
+    assert ei.value.status == _lib.ERR_BAD_ARG and str(ei.value).count(name + ":") == 1 and all(s in str(ei.value) for s in needles), str(ei.value)
 
 
 class FinalBuf(Guarded):

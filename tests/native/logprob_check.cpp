@@ -4,7 +4,7 @@
 //     depth 1 (policy: W1[H1][D], b1, W2[A][H1], b2; H2 is ignored) or 2 (W1[H1][D], b1, W2[H2][H1], b2, W3[A][H2], b3; no MLP_ACT_TANH): logprob_env over
 //     every environment; A == 1 is the Gaussian head with k = logp_gauss_k(sigma), else the categorical head and sigma is not read.
 //     -> 0; 1 for a combination the entry point refuses; 2 where, with n a multiple of 4, the rows taken four to a lane (mlp_scores<D, A, ACT, 4> and the
-//        head, the form of logp4_kernel) differ from logprob_env's
+//        head, the form of learner.h's dense4_kernel) differ from logprob_env's
 //   logprob_k(sigma) -> logp_gauss_k;  logprob_sigma_ok(sigma) -> logp_sigma_ok
 //   log_pos_eval(n, x, out): out[i] = mg_log_pos(x[i])
 //   log_pos_sweep(first, last, &max_abs, &max_rel, &differ): over every f32 bit pattern first .. last (positive normal floats), against libm's float64 log of

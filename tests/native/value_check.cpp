@@ -4,7 +4,7 @@
 //     depth 1 (critic: W1[H1][D], b1, W2[1][H1], b2; H2 is ignored) or 2 (W1[H1][D], b1, W2[H2][H1], b2, W3[1][H2], b3; no MLP_ACT_TANH): value_env over every
 //     environment.  final_obs / trunc / final_value_out all NULL or all set; done may be NULL.
 //     -> 0; 1 for a combination the entry point refuses; 2 where, with n a multiple of 4, the dense rows taken four to a lane (mlp_scores<D, 1, ACT, 4>, the
-//        form of value4_kernel) differ from value_env's
+//        form of learner.h's dense4_kernel) differ from value_env's
 //   value_chunk() -> kValueChunk;  value_wave_envs() -> kValueWaveEnvs
 #include <stdint.h>
 #include <string.h>

@@ -28,6 +28,7 @@ N = 2052
 KS = (1, 2, 17)
 HS = (1, 17, 64)
 Guarded = functools.partial(device_buffers.Guarded, fill=R.POISON)
+bad_arg = device_buffers.bad_arg
 
 
 @functools.lru_cache(maxsize=None)
@@ -300,12 +301,6 @@ def test_torch():
         env.close()
 
 
-def bad_arg(fn, name, *needles):
-    with pytest.raises(mg.MgymError) as ei:
-        fn()
-    assert ei.value.status == _lib.ERR_BAD_ARG and str(ei.value).count(name + ":") == 1 and all(s in str(ei.value) for s in needles), str(ei.value)
-
-
 def test_errors():
     """every refusal names its entry point and its argument, launches nothing and leaves the handle usable"""
     c, v = G.case("cartpole", 2, N, 17, G.RELU), G.case("cartpole", 2, N, 17, G.RELU, G.VALUE)
@@ -334,7 +329,11 @@ def test_errors():
             ({IOLD: b.x0.ptr + 3}, "logp_old", "4-byte aligned"), ({IADV: b.x1.ptr + 1}, "adv", "4-byte aligned"), ({IG: b.grad.ptr + 2}, "grad_out", "4-byte aligned"),
             ({IS: b.stats.ptr + 1}, "stats_out", "4-byte aligned"), ({IG: b.obs.ptr}, "grad_out", "obs"), ({IS: b.x1.ptr}, "stats_out", "adv"),
             ({IS: b.x0.ptr}, "stats_out", "logp_old"), ({IWS: b.obs_first.ptr}, "workspace", "obs_first"), ({IG: b.actions.ptr}, "grad_out", "actions"),
-            ({IS: b.grad.ptr}, "stats_out", "grad_out"), ({IG: b.ws.ptr}, "grad_out", "workspace"), ({IS: b.ws.ptr}, "stats_out", "workspace")]
+            ({IS: b.grad.ptr}, "stats_out", "grad_out"), ({IG: b.ws.ptr}, "grad_out", "workspace"), ({IS: b.ws.ptr}, "stats_out", "workspace"),
+            # two faults: the earlier group's is the one reported — K, the NULLs, width and activation, head and sigma, the call's own checks, alignment, aliasing
+            ({IK: 0, IPOL: None}, "K must be"), ({IG: None, IH: 0}, "grad_out is NULL"), ({IH: 0, IHEAD: 3}, "hidden must be"),
+            ({IHEAD: 3, IOBS: b.obs.ptr + 1}, "head must be"), ({IHEAD: 3, ICOUNT: 0}, "head must be"), ({IWB: lo - 1, IOBS: b.obs.ptr + 1}, "workspace_bytes is below"),
+            ({IOBS: b.obs.ptr + 1, IG: b.actions.ptr}, "obs must be 4-byte aligned")]
     state = e.get_state()
     for repl, *needles in rows:
         bad_arg(ppo(repl), "mgym_ppo_grad_mlp", *needles)
@@ -364,7 +363,9 @@ def test_errors():
     for repl, *needles in (({3: 0}, "K"), ({0: None}, "critic"), ({6: None}, "obs_first"), ({7: None}, "obs"), ({8: None}, "ret"), ({9: None}, "workspace"),
                            ({11: None}, "grad_out"), ({12: None}, "stats_out"), ({1: 65}, "hidden"), ({2: 2}, "activation"), ({5: 0}, "env_count"), ({4: 5}, "n_envs"),
                            ({10: 8}, "workspace_bytes"), ({9: q.ws.ptr + 4}, "workspace", "16-byte"), ({8: q.x0.ptr + 2}, "ret", "4-byte aligned"),
-                           ({11: q.x0.ptr}, "grad_out", "ret"), ({12: q.grad.ptr}, "stats_out", "grad_out"), ({9: q.obs.ptr}, "workspace", "obs")):
+                           ({11: q.x0.ptr}, "grad_out", "ret"), ({12: q.grad.ptr}, "stats_out", "grad_out"), ({9: q.obs.ptr}, "workspace", "obs"),
+                           ({3: 0, 0: None}, "K must be"), ({11: None, 1: 0}, "grad_out is NULL"), ({1: 0, 5: 0}, "hidden must be"),   # two faults, as above
+                           ({10: 8, 7: q.obs.ptr + 1}, "workspace_bytes is below"), ({7: q.obs.ptr + 1, 11: q.x0.ptr}, "obs must be 4-byte aligned")):
         bad_arg(val(repl), "mgym_value_grad_mlp", *needles)
     e.sync()
     assert q.grad.untouched() and q.ws.untouched()

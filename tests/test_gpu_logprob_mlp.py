@@ -26,6 +26,7 @@ N = 2052
 KS = (1, 2, 17)
 SIGMA = 0.5
 Guarded = functools.partial(device_buffers.Guarded, fill=R.POISON)
+bad_arg = lambda fn, *needles: device_buffers.bad_arg(fn, "mgym_logprob_mlp", *needles)
 
 
 class Slabs:
@@ -239,12 +240,6 @@ def test_no_environments():
     e.close()
 
 
-def bad_arg(fn, *needles):
-    with pytest.raises(mg.MgymError) as ei:
-        fn()
-    assert ei.value.status == _lib.ERR_BAD_ARG and all(s in str(ei.value) for s in ("mgym_logprob_mlp:",) + needles), str(ei.value)
-
-
 def _raw_call(env, good, repl):
     IPOL, IH1, IK, IOF = 0, 1, 6, 7
     args = list(good)
@@ -270,7 +265,10 @@ def test_errors(env, pend):
             ({IHEAD: _lib.HEAD_GAUSS, ISIG: 0.5}, "head", "MGYM_HEAD_GAUSS", "CartPole"),
             ({IOF: b.obs_first.ptr + 2}, "obs_first", "4-byte aligned"), ({IOBS: b.obs.ptr + 1}, "obs", "4-byte aligned"),
             ({IA: b.actions.ptr + 2}, "actions", "4-byte aligned"), ({IOUT: b.logp.ptr + 3}, "logp_out", "4-byte aligned"),
-            ({IOUT: b.obs_first.ptr}, "logp_out", "obs_first"), ({IOUT: b.obs.ptr}, "logp_out", "obs"), ({IOUT: b.actions.ptr}, "logp_out", "actions")]
+            ({IOUT: b.obs_first.ptr}, "logp_out", "obs_first"), ({IOUT: b.obs.ptr}, "logp_out", "obs"), ({IOUT: b.actions.ptr}, "logp_out", "actions"),
+            # two faults: the earlier group's is the one reported — K, the NULLs, widths and activation, head and sigma, alignment, aliasing
+            ({IK: 0, IPOL: None}, "K must be"), ({IOUT: None, IH1: 0}, "logp_out is NULL"), ({IH1: 0, IHEAD: 3}, "hidden1 must be"),
+            ({IHEAD: 3, IOBS: b.obs.ptr + 1}, "head must be"), ({IOBS: b.obs.ptr + 1, IOUT: b.actions.ptr}, "obs must be 4-byte aligned")]
     state = env.get_state()
     for repl, *needles in rows:
         bad_arg(_raw_call(env, good, repl), *needles)

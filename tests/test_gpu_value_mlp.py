@@ -28,6 +28,7 @@ F = np.float32
 N = 2052
 KS = (1, 2, 17)
 Guarded = functools.partial(device_buffers.Guarded, fill=R.POISON)
+bad_arg = lambda fn, *needles: device_buffers.bad_arg(fn, "mgym_value_mlp", *needles)
 
 
 @functools.lru_cache(maxsize=None)
@@ -39,8 +40,8 @@ def expected(family, K, n, widths, act, with_final=True, with_d=True):
 
 
 class Slabs:
-    def __init__(self, family, K, n, mis_obs=0, with_final=True, with_d=True):
-        c = R.case(family, K, n)
+    def __init__(self, family, K, n, mis_obs=0, with_final=True, with_d=True, case=None):
+        c = case or R.case(family, K, n)
         self.c, self.K, self.n, self.with_final, self.with_d = c, K, n, with_final, with_d
         D = c["D"]
         self.obs_first, self.obs = Guarded(D * n, 0, c["obs_first"]), Guarded(K * D * n, mis_obs, c["obs"])
@@ -122,6 +123,22 @@ def test_one_per_lane(K):
     run(e, "mountain_car", K, 1030, (17,), R.RELU)
     run(e, "mountain_car", K, 1030, (3, 5), R.RELU, with_d=False)
     e.close()
+
+
+def test_more_rows_than_the_grid_holds():
+    """K = 65 540 at n = 4 on MountainCar with H = 3, without the final triple: rows 65 535 .. 65 540 of the K + 1 come from the stride loop; then one per lane
+    (n = 5) with the same K"""
+    K, widths = 65540, (3,)
+    crit = R.critic("mountain_car", widths)[0]
+    for n in (4, 5):
+        rng = np.random.default_rng(n)
+        c = dict(D=2, obs_first=R.observations(rng, "mountain_car", (), n), obs=R.observations(rng, "mountain_car", (K,), n))
+        e = mg.VecEnv(mg.MOUNTAINCAR, n)
+        b = Slabs("mountain_car", K, n, with_final=False, with_d=False, case=c)
+        b.call(e, crit, widths, R.RELU)
+        e.sync()
+        b.check(R.value_mlp(crit, 2, widths, R.RELU, c["obs_first"], c["obs"]), f"K={K} n={n}")
+        e.close()
 
 
 @pytest.mark.parametrize("K", [2, 17])
@@ -246,12 +263,6 @@ def test_no_environments():
     e.close()
 
 
-def bad_arg(fn, *needles):
-    with pytest.raises(mg.MgymError) as ei:
-        fn()
-    assert ei.value.status == _lib.ERR_BAD_ARG and all(s in str(ei.value) for s in ("mgym_value_mlp:",) + needles), str(ei.value)
-
-
 def test_errors(env):
     K, widths = 2, (17,)
     b = Slabs("cartpole", K, N)
@@ -280,7 +291,10 @@ def test_errors(env):
             ({ILV: b.last.ptr + 3}, "last_value_out", "4-byte aligned"), ({IFV: b.final.ptr + 2}, "final_value_out", "4-byte aligned"),
             ({IV: b.obs_first.ptr}, "value_out", "obs_first"), ({ILV: b.obs.ptr}, "last_value_out", "obs"), ({IFV: b.final_obs.ptr}, "final_value_out", "final_obs"),
             ({IV: b.d.ptr}, "value_out", "done"), ({IFV: b.u.ptr}, "final_value_out", "trunc"),
-            ({IV: b.last.ptr}, "value_out", "last_value_out"), ({IFV: b.value.ptr}, "final_value_out", "value_out")]
+            ({IV: b.last.ptr}, "value_out is the same pointer as last_value_out"), ({IFV: b.value.ptr}, "final_value_out", "value_out"),
+            # two faults: the earlier group's is the one reported — K, the NULLs, widths and activation, the final triple, alignment, aliasing
+            ({IK: 0, ICRIT: None}, "K must be"), ({IV: None, IH1: 0}, "value_out is NULL"), ({IH1: 0, IFV: None}, "hidden1 must be"),
+            ({IFV: None, IOBS: b.obs.ptr + 1}, "final_value_out is NULL"), ({IOBS: b.obs.ptr + 1, IV: b.last.ptr}, "obs must be 4-byte aligned")]
     state = env.get_state()
     for repl, *needles in rows:
         bad_arg(call(repl), *needles)

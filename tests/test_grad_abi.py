@@ -10,28 +10,13 @@ import re
 import pytest
 
 import modurl_gym_amd as mg
+from abi_surface import check_exported_and_tables_match_the_header, header_params, read
 from modurl_gym_amd import _lib, torch_env
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("mgym_grad_workspace_bytes", "mgym_ppo_grad_mlp", "mgym_value_grad_mlp")
-C_TYPES = {"mgym_env *": C.c_void_p, "const float *": C.c_void_p, "const void *": C.c_void_p, "float *": C.c_void_p, "void *": C.c_void_p, "int32_t ": C.c_int32,
-           "float ": C.c_float, "uint64_t ": C.c_uint64, "size_t ": C.c_size_t, "int ": C.c_int, "size_t *": C.POINTER(C.c_size_t)}
-RUST_TYPES = {"mgym_env *": "*mut mgym_env", "const float *": "*const f32", "const void *": "*const c_void", "float *": "*mut f32", "void *": "*mut c_void",
-              "int32_t ": "i32", "float ": "f32", "uint64_t ": "u64", "size_t ": "usize", "int ": "c_int", "size_t *": "*mut usize"}
 PPO = ["env", "policy", "hidden", "activation", "head", "sigma", "K", "env_first", "env_count", "obs_first", "obs", "actions", "logp_old", "adv", "clip", "ent_coef",
        "workspace", "workspace_bytes", "grad_out", "stats_out"]
 VALUE = ["env", "critic", "hidden", "activation", "K", "env_first", "env_count", "obs_first", "obs", "ret", "workspace", "workspace_bytes", "grad_out", "stats_out"]
-
-
-def read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
-
-
-def header_params(name):
-    """[(C type as written, name)] of the declaration in include/mgym.h"""
-    text = re.sub(r"/\*.*?\*/", "", read("include", "mgym.h"), flags=re.S)
-    args = re.search(r"\bint %s\((.*?)\);" % name, text, re.S).group(1)
-    return [re.fullmatch(r"(.*?[ *])([A-Za-z0-9_]+)", " ".join(a.split())).groups() for a in args.split(",")]
 
 
 def test_the_declarations_are_the_issue_s():
@@ -46,19 +31,7 @@ def test_the_declarations_are_the_issue_s():
 
 @pytest.mark.parametrize("name", NAMES)
 def test_the_call_is_exported_and_the_tables_match_the_header(name):
-    assert hasattr(C.CDLL(_lib.LIB_PATH), name), f"libmgym.so does not export {name}"
-    res, args = _lib.PROTOTYPES[name]
-    want = [C_TYPES[t] for t, _ in header_params(name)]
-    if name != NAMES[0]:
-        want[1] = C.POINTER(C.c_float)   # the one host pointer: the weights' words
-    assert res is C.c_int and args == want
-    sys_rs = read("rust", "modurl_gym_mgym", "src", "sys.rs")
-    decl = re.search(r"pub fn %s\((.*?)\) -> c_int;" % name, sys_rs, re.S).group(1)
-    rust = [tuple(x.strip() for x in a.split(":")) for a in decl.split(",") if a.strip()]
-    assert [t for _, t in rust] == [RUST_TYPES[t] for t, _ in header_params(name)]
-    assert [n for n, _ in rust] == [n.lower() for _, n in header_params(name)]
-    assert _lib.load().mgym_abi_version() == 4   # added entry points: the version stays
-    assert re.search(r"#define MGYM_ABI_VERSION 4\b", read("include", "mgym.h"))
+    check_exported_and_tables_match_the_header(name, None if name == NAMES[0] else 1)   # (the one host pointer: the weights' words)
 
 
 def test_null_handle_is_a_bad_argument():

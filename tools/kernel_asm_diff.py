@@ -8,7 +8,13 @@ Every kernel of OLD is looked up in NEW by its mangled name; an empty trailing t
 "DpT<k>_" closing the parameter types) is not part of the name for this purpose, and the kernel's own name is masked in its text.  Compared are (1) the function body from its label to its end label, with the
 comments and the function-order-dependent numbers of local labels (.LBB<fn>_<bb>, .Lfunc_end<fn>) taken out, (2) the .amdhsa_kernel block, (3) the kernel's
 .args entry of the code-object metadata.  Prints one line per file and per changed or missing kernel; exit status 1 if any OLD kernel changed.
+
+    tools/kernel_asm_diff.py --by-text OLD/build NEW/build
+
+pairs by content instead, for a change that renames kernels: every OLD kernel's masked (text, descriptor, arguments) triple must occur among NEW's, counted
+with multiplicity; an OLD kernel without one is CHANGED.
 """
+import collections
 import os
 import re
 import sys
@@ -58,14 +64,22 @@ def kernels(path):
 
 
 def main():
-    old, new = sys.argv[1], sys.argv[2]
+    by_text = "--by-text" in sys.argv[1:]
+    old, new = [a for a in sys.argv[1:] if a != "--by-text"]
     pairs = [(old, new)] if os.path.isfile(old) else [(os.path.join(old, f), os.path.join(new, f)) for f in sorted(os.listdir(old)) if f.endswith(".s")]
     compared = changed = 0
     for a, b in pairs:
         ka, kb = kernels(a), kernels(b)
         c = 0
+        left = collections.Counter(kb.values())
         for name, parts in ka.items():
             compared += 1
+            if by_text:
+                if left[parts] == 0:
+                    print(f"CHANGED  {name}: no kernel of the new build has its text, descriptor and arguments")
+                    c += 1
+                left[parts] -= 1
+                continue
             if name not in kb:
                 print(f"MISSING  {name}")
                 c += 1
@@ -75,7 +89,7 @@ def main():
                 print(f"CHANGED  {name}: {', '.join(what)}")
                 c += 1
         changed += c
-        print(f"{os.path.basename(a)}: {len(ka)} kernels of the old build compared, {c} changed; the new build has {len(kb) - len(set(ka) & set(kb))} more")
+        print(f"{os.path.basename(a)}: {len(ka)} kernels of the old build compared, {c} changed; the new build has {len(kb) - (len(ka) - c if by_text else len(set(ka) & set(kb)))} more")
     print(f"total: {compared} compared, {changed} changed")
     sys.exit(1 if changed else 0)
 
