@@ -675,8 +675,9 @@ int mgym_logprob_mlp(mgym_env *env, const float *policy, int32_t hidden1, int32_
 /* PPO's loss and the actor's gradient, and a critic's squared-error loss and gradient, over the buffers of a K-step rollout: the update a learner handed to a
  * torch forward pass (a [K n][H] activation written), a surrogate and autograd's backward pass (the activation read back).  One hidden layer, 1 <= H = hidden
  * <= 64; the six (D, A) of mgym_logprob_mlp; MGYM_HEAD_SAMPLE on the discrete families and MGYM_HEAD_GAUSS on the continuous ones; MGYM_ACT_RELU, MGYM_ACT_TANH
- * and MGYM_ACT_TANH_FAST.  Out of scope: two hidden layers (dW2[H2][H1] needs a tiled product over the batch dimension, a separate piece of work); the
- * optimizer step; advantage normalisation; flat-index minibatches; a clipped value loss; any state of the handle.
+ * and MGYM_ACT_TANH_FAST.  Two hidden layers are the calls after these, mgym_ppo_grad_mlp2 and mgym_value_grad_mlp2 (dW2[H2][H1] is a tiled product over
+ * the batch dimension, kernels of their own).  Out of scope: the optimizer step; advantage normalisation; flat-index minibatches; a clipped value loss; any
+ * state of the handle.
  *
  * Purity.  As mgym_logprob_mlp: the handle supplies the device, the stream, n_envs and (D, A); every kind is accepted and no state of the handle is read or
  * written.  policy / critic is a HOST pointer in nn.Linear order, W1[H][D], b1[H], W2[A][H], b2[A] (A = 1 for the critic), read during the call and passed to the
@@ -739,6 +740,50 @@ int mgym_value_grad_mlp(mgym_env *env, const float *critic, int32_t hidden, int3
                         int32_t K, uint64_t env_first, uint64_t env_count,
                         const float *obs_first, const float *obs, const float *ret,
                         void *workspace, size_t workspace_bytes, float *grad_out, float *stats_out);
+
+/* The same two calls for the net of mgym_rollout_mlp2, Linear(D, H1) - act - Linear(H1, H2) - act - Linear(H2, A): the update of the network a collector runs
+ * with mgym_rollout_mlp2 and a learner evaluates with mgym_value_mlp / mgym_logprob_mlp at hidden2 >= 1.  Everything not named here is as in mgym_ppo_grad_mlp /
+ * mgym_value_grad_mlp: purity and capturability; obs_first, obs, actions, logp_old, adv, ret; the env_first / env_count slice, no word outside it loaded;
+ * clip, ent_coef and the stats_out layout; no float atomics, no tickets, a call repeats to the word; four environments per lane under the same conditions, else
+ * one; the refusals, each message starting with the entry point's name.  The optimizer step, advantage normalisation, flat-index minibatches, a clipped value
+ * loss and any state of the handle stay out of scope.
+ *   policy / critic   a HOST pointer in the layout of mgym_rollout_mlp2: W1[H1][D], b1[H1], W2[H2][H1], b2[H2], W3[A][H2], b3[A] (A = 1 for the critic), read
+ *             during the call; the kernels read the weights from device packs the handle owns from mgym_create (a fourth and a fifth: the actor's and the
+ *             critic's under these calls), filled on the stream ahead of the launch — so a captured graph that holds a rollout, a value, a log-probability and
+ *             both gradient calls replays each with its own weights
+ *   1 <= hidden1, hidden2 <= 64; hidden2 == 0 is refused (the one-layer calls above).  MGYM_ACT_RELU or MGYM_ACT_TANH_FAST; MGYM_ACT_TANH is refused as in
+ *             every two-layer entry point
+ *   grad_out  P2 + 1 floats, P2 = mlp2_policy_floats(D, A, H1, H2) = H1 (D + 1) + H2 (H1 + 1) + A (H2 + 1): dW1, db1, dW2, db2, dW3, db3 in nn.Linear order,
+ *             then the log-sigma word (+0 under the sample head and for the critic).  stats_out 8 floats.
+ * Per env-step, f32 words, nothing fused beyond the named fmaf, nothing reassociated, every selection a selection:
+ *   pre1_j, h1_j, pre2_k, h2_k, s_a     exactly mgym_rollout_mlp2's text (the chains of csrc/mlp2_policy.h, unpadded)
+ *   logp_new, d, r, g, ds_a, the log-sigma term, the statistics' terms, the critic's e and ds_0     exactly mgym_ppo_grad_mlp's text applied to these s_a;
+ *             logp_new is the word mgym_logprob_mlp returns at hidden2 >= 1, so with unchanged weights the ratio is exactly 1
+ *   dh2_k   = W3[0][k] * ds_0;  a = 1 .. A-1: dh2_k = dh2_k + W3[a][k] * ds_a
+ *   dpre2_k = dh2_k * act'(k)           act' = pre2_k > 0 ? 1.0f : 0.0f (ReLU), 1.0f - h2_k * h2_k (tanh_fast)
+ *   dh1_j   = +0.0f;  k = 0 .. H2-1 ascending: dh1_j = fmaf(W2[k][j], dpre2_k, dh1_j)
+ *   dpre1_j = dh1_j * act'(j)           the same rule on pre1_j / h1_j
+ *   terms:  dW3[a][k] += ds_a * h2_k;  db3[a] += ds_a;  dW2[k][j] += dpre2_k * h1_j;  db2[k] += dpre2_k;  dW1[j][q] += dpre1_j * o_q;  db1[j] += dpre1_j
+ * (modurl_gym_amd/csrc/grad2.h is this text as the kernels and a g++ build compile it.)  The SUMS over the B env-steps are not word-defined, and neither are the
+ * products inside them: the kernels form them on the f32 matrix pipe (exact f32 products, an f32 accumulator over at most 128 env-steps of a wave) and add
+ * everything beyond in f64; every sum is divided by B once at the end, in f64.  The values are bounded against float64 (tests/grad2_ref.py: GRAD2_BOUND times
+ * the word's mean absolute per-env-step term).
+ * Workspace.  A slab is P2 + 8 f64 words.  mgym_grad_workspace_bytes2(kind, hidden1, hidden2) gives min_bytes, one slab, and best_bytes, 256 slabs: a block of
+ * these kernels holds most of a compute unit's LDS, so one block is resident on each of the chip's 256 compute units and more slabs would only lengthen the last
+ * sum.  The query uses the family's own A, so one size serves both calls; a workspace sized by mgym_grad_workspace_bytes for the same hidden1 is too small and
+ * refused.  A call uses min(256, workspace_bytes / min_bytes) slabs; its blocks stride over the tiles when there are more tiles than slabs; no word at or beyond
+ * workspace_bytes is written.  mgym_grad_workspace_bytes2 refuses an unknown kind, hidden1 or hidden2 outside 1 .. 64 and a NULL output. */
+int mgym_grad_workspace_bytes2(int kind, int32_t hidden1, int32_t hidden2, size_t *min_bytes, size_t *best_bytes);
+
+int mgym_ppo_grad_mlp2(mgym_env *env, const float *policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma,
+                       int32_t K, uint64_t env_first, uint64_t env_count,
+                       const float *obs_first, const float *obs, const void *actions, const float *logp_old, const float *adv,
+                       float clip, float ent_coef, void *workspace, size_t workspace_bytes, float *grad_out, float *stats_out);
+
+int mgym_value_grad_mlp2(mgym_env *env, const float *critic, int32_t hidden1, int32_t hidden2, int32_t activation,
+                         int32_t K, uint64_t env_first, uint64_t env_count,
+                         const float *obs_first, const float *obs, const float *ret,
+                         void *workspace, size_t workspace_bytes, float *grad_out, float *stats_out);
 
 /* The return and length of every episode that ends inside a K-step rollout: one launch, a forward scan per environment whose carry the CALLER owns, so
  * that episodes span calls.  A pure function of its arguments like mgym_gae (every kind, no handle state, capturable); all pointers are DEVICE pointers.

@@ -139,6 +139,22 @@ class VecGym {
                         const float* ret, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
         check(mgym_value_grad_mlp(env_, critic, hidden, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out));
     }
+    // The same for the two-hidden-layer net of rollout_mlp2 (mgym_grad_workspace_bytes2, mgym_ppo_grad_mlp2, mgym_value_grad_mlp2): policy / critic in the layout
+    // of mgym_rollout_mlp2; grad_out receives dW1, db1, dW2, db2, dW3, db3 and one more word
+    static void grad_workspace_bytes2(int kind, int hidden1, int hidden2, size_t* min_bytes, size_t* best_bytes) {
+        if (mgym_grad_workspace_bytes2(kind, hidden1, hidden2, min_bytes, best_bytes) != MGYM_OK) throw std::runtime_error(mgym_last_error());
+    }
+    void ppo_grad_mlp2(const float* policy, int hidden1, int hidden2, int activation, int head, float sigma, int K, uint64_t env_first, uint64_t env_count,
+                       const float* obs_first, const float* obs, const void* actions, const float* logp_old, const float* adv, float clip, float ent_coef,
+                       void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
+        check(mgym_ppo_grad_mlp2(env_, policy, hidden1, hidden2, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip,
+                                 ent_coef, workspace, workspace_bytes, grad_out, stats_out));
+    }
+    void value_grad_mlp2(const float* critic, int hidden1, int hidden2, int activation, int K, uint64_t env_first, uint64_t env_count, const float* obs_first,
+                         const float* obs, const float* ret, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
+        check(mgym_value_grad_mlp2(env_, critic, hidden1, hidden2, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out,
+                                   stats_out));
+    }
     // The return and length of the episodes that end inside a rollout (mgym_episode_returns): ep_return / ep_length [n_envs] are the caller's carry of the
     // running episodes (read and written); return_out / length_out [K][n_envs] (or nullptr) are written only where done | trunc
     void episode_returns(int K, const float* reward, const uint8_t* done, const uint8_t* trunc, float* ep_return, uint32_t* ep_length, float* return_out,

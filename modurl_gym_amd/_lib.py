@@ -71,6 +71,11 @@ PROTOTYPES = {
     "mgym_ppo_grad_mlp": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp,
                                     C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp]),
     "mgym_value_grad_mlp": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "mgym_grad_workspace_bytes2": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "mgym_ppo_grad_mlp2": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
+                                     _vp, _vp, C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp]),
+    "mgym_value_grad_mlp2": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t,
+                                       _vp, _vp]),
     "mgym_episode_returns": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mgym_set_dispersion_override": (C.c_int, [_vp, _vp]),
     "mgym_get_spec": (C.c_int, [C.c_int, C.POINTER(Spec)]),

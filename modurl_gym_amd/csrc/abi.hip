@@ -9,6 +9,7 @@
 #include "common.h"
 #include "gae.h"
 #include "grad.h"
+#include "grad2.h"
 #include "logprob.h"
 #include "time_limit.h"
 #include "value.h"
@@ -221,6 +222,8 @@ int mgym_create(const mgym_config* cfg, mgym_env** out) {
         if (hipMalloc((void**)&impl->mlp2_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipMalloc((void**)&impl->value_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipMalloc((void**)&impl->logp_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
+        if (hipMalloc((void**)&impl->ppo_grad_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
+        if (hipMalloc((void**)&impl->value_grad_dev, kMlp2PackMax * sizeof(float)) != hipSuccess) { st = MGYM_ERR_HIP; set_last_error("hipMalloc failed"); break; }
         if (hipEventCreate(&impl->ev0) != hipSuccess || hipEventCreate(&impl->ev1) != hipSuccess) { st = MGYM_ERR_HIP; break; }
         st = impl->init();
         if (st != MGYM_OK) break;
@@ -251,6 +254,8 @@ int mgym_destroy(mgym_env* env) {
         if (e->mlp2_dev) (void)hipFree(e->mlp2_dev);
         if (e->value_dev) (void)hipFree(e->value_dev);
         if (e->logp_dev) (void)hipFree(e->logp_dev);
+        if (e->ppo_grad_dev) (void)hipFree(e->ppo_grad_dev);
+        if (e->value_grad_dev) (void)hipFree(e->value_grad_dev);
         hipStream_t s = e->own_stream ? e->stream : nullptr;
         delete e;
         if (s) (void)hipStreamDestroy(s);
@@ -344,12 +349,14 @@ struct Bad {
 };
 
 // The widths, then the activation.  NET_HIDDEN: one layer, worded "hidden".  NET_ROLLOUT2: two layers, hidden2 from 1.  NET_LEARNER: "hidden1" and "hidden2",
-// hidden2 == 0 meaning one layer.  Two layers offer no exact tanh; the rollout and the learner calls word that refusal differently.
-enum NetNames { NET_HIDDEN, NET_ROLLOUT2, NET_LEARNER };
+// hidden2 == 0 meaning one layer.  NET_GRAD2: the two-layer gradient calls, hidden2 from 1, the refusal naming the one-layer calls.  Two layers offer no
+// exact tanh; the rollout and the learner calls word that refusal differently.
+enum NetNames { NET_HIDDEN, NET_ROLLOUT2, NET_LEARNER, NET_GRAD2 };
 static int net_shape_ok(const Bad& bad, int32_t h1, int32_t h2, int32_t activation, NetNames names) {
     if (h1 < 1 || h1 > 64) return bad(names == NET_HIDDEN ? "hidden must be between 1 and 64" : "hidden1 must be between 1 and 64");
     if (names == NET_ROLLOUT2 && (h2 < 1 || h2 > 64)) return bad("hidden2 must be between 1 and 64");
     if (names == NET_LEARNER && (h2 < 0 || h2 > 64)) return bad("hidden2 must be between 0 (one hidden layer) and 64");
+    if (names == NET_GRAD2 && (h2 < 1 || h2 > 64)) return bad("hidden2 must be between 1 and 64 (one hidden layer: mgym_ppo_grad_mlp / mgym_value_grad_mlp)");
     const bool two = names != NET_HIDDEN && h2 >= 1;
     if (two && activation == MGYM_ACT_TANH)
         return bad(std::string("activation MGYM_ACT_TANH is not offered with two hidden layers (") +
@@ -554,12 +561,12 @@ int mgym_logprob_mlp(mgym_env* env, const float* policy, int32_t hidden1, int32_
                           hidden2, activation, e->logp_dev);
 }
 
-// ---- mgym_ppo_grad_mlp / mgym_value_grad_mlp: one argument check for both (ppo: the actor's call) ----
+// ---- mgym_ppo_grad_mlp / mgym_value_grad_mlp and their two-layer forms: one argument check for the four (ppo: the actor's call; two: hidden2 is taken) ----
 struct GradArgs {
     const char* name;
-    bool ppo;
+    bool ppo, two;
     const float* weights;
-    int32_t hidden, activation, head;
+    int32_t hidden, hidden2, activation, head;
     float sigma;
     int32_t K;
     uint64_t env_first, env_count;
@@ -585,7 +592,7 @@ static int grad_call(Env* e, const GradArgs& a) {
     if (!a.workspace) return bad("workspace is NULL");
     if (!a.grad_out) return bad("grad_out is NULL");
     if (!a.stats_out) return bad("stats_out is NULL");
-    if (const int st = net_shape_ok(bad, a.hidden, 0, a.activation, NET_HIDDEN)) return st;
+    if (const int st = net_shape_ok(bad, a.hidden, a.hidden2, a.activation, a.two ? NET_GRAD2 : NET_HIDDEN)) return st;
     if (a.ppo) { if (const int st = density_head_ok(bad, e, a.head, a.sigma)) return st; }
     if (e->n != 0 && a.env_count == 0) return bad("env_count must be at least 1");   // (a handle without environments has no range to give: MGYM_OK below)
     if (e->n != 0 && (a.env_first > e->n || a.env_count > e->n - a.env_first)) return bad("env_first + env_count exceeds n_envs");
@@ -593,8 +600,9 @@ static int grad_call(Env* e, const GradArgs& a) {
     if (a.ppo && !grad_ent_coef_ok(a.ent_coef)) return bad("ent_coef must be finite");
     int D = 0, A = 1;
     if (const int st = family_dims(e->cfg.kind, &D, &A)) return st;
-    const uint64_t slab_bytes = grad_slab_bytes(D, A, a.hidden);
-    if (a.workspace_bytes < slab_bytes) return bad("workspace_bytes is below min_bytes of mgym_grad_workspace_bytes (" + std::to_string(slab_bytes) + ")");
+    const uint64_t slab_bytes = a.two ? grad2_slab_bytes(D, A, a.hidden, a.hidden2) : grad_slab_bytes(D, A, a.hidden);
+    if (a.workspace_bytes < slab_bytes)
+        return bad(std::string("workspace_bytes is below min_bytes of ") + (a.two ? "mgym_grad_workspace_bytes2" : "mgym_grad_workspace_bytes") + " (" + std::to_string(slab_bytes) + ")");
     if (!aligned(a.workspace, 16)) return bad("workspace must be 16-byte aligned");
     if (const int st = pointers_ok(bad, {{"obs_first", a.obs_first, false, 4}, {"obs", a.obs, false, 4}, {"actions", a.actions, false, 4}, {n0, a.x0, false, 4},
                                          {"adv", a.x1, false, 4}, {"workspace", a.workspace, true, 0}, {"grad_out", a.grad_out, true, 4}, {"stats_out", a.stats_out, true, 4}}))
@@ -603,13 +611,45 @@ static int grad_call(Env* e, const GradArgs& a) {
     const uint64_t fit = a.workspace_bytes / slab_bytes;
     GradCall c{};
     c.n = e->n; c.env_first = a.env_first; c.env_count = a.env_count; c.K = a.K;
-    c.slabs = (int32_t)(fit < (uint64_t)kGradSlabCap ? fit : (uint64_t)kGradSlabCap);
+    const uint64_t cap = (uint64_t)(a.two ? kGrad2SlabCap : kGradSlabCap);
+    c.slabs = (int32_t)(fit < cap ? fit : cap);
     c.lo = 1.0f - a.clip; c.hi = 1.0f + a.clip; c.ent_coef = a.ppo ? a.ent_coef : 0.0f;
     const bool gauss = a.ppo && a.head == MGYM_HEAD_GAUSS;
     c.sigma = a.sigma; c.k = gauss ? logp_gauss_k(a.sigma) : 0.0f; c.ent = gauss ? grad_gauss_entropy(a.sigma) : 0.0f;   // f64 on the host, the headers' own lines
     c.obs_first = a.obs_first; c.obs = a.obs; c.actions = static_cast<const uint32_t*>(a.actions); c.x0 = a.x0; c.x1 = a.x1;
     c.workspace = static_cast<double*>(a.workspace); c.grad_out = a.grad_out; c.stats_out = a.stats_out;
-    return grad_launch(e->stream, c, D, A, !a.ppo ? GRAD_HEAD_VALUE : (gauss ? GRAD_HEAD_GAUSS : GRAD_HEAD_CATEGORICAL), a.weights, a.hidden, a.activation);
+    const int head = !a.ppo ? GRAD_HEAD_VALUE : (gauss ? GRAD_HEAD_GAUSS : GRAD_HEAD_CATEGORICAL);
+    if (!a.two) return grad_launch(e->stream, c, D, A, head, a.weights, a.hidden, a.activation);
+    float* pack_dev = a.ppo ? e->ppo_grad_dev : e->value_grad_dev;
+    if (const int st = e->mlp2_store_to(pack_dev, a.weights, D, a.ppo ? A : 1, a.hidden, a.hidden2)) return st;
+    return grad2_launch(e->stream, c, D, A, head, pack_dev, a.hidden, a.hidden2, a.activation);
+}
+
+int mgym_grad_workspace_bytes2(int kind, int32_t hidden1, int32_t hidden2, size_t* min_bytes, size_t* best_bytes) {
+    int D = 0, A = 1;
+    if (family_dims(kind, &D, &A) != MGYM_OK) return bad_arg("mgym_grad_workspace_bytes2: unknown kind");
+    if (hidden1 < 1 || hidden1 > 64) return bad_arg("mgym_grad_workspace_bytes2: hidden1 must be between 1 and 64");
+    if (hidden2 < 1 || hidden2 > 64) return bad_arg("mgym_grad_workspace_bytes2: hidden2 must be between 1 and 64");
+    if (!min_bytes || !best_bytes) return bad_arg(!min_bytes ? "mgym_grad_workspace_bytes2: min_bytes is NULL" : "mgym_grad_workspace_bytes2: best_bytes is NULL");
+    *min_bytes = (size_t)grad2_slab_bytes(D, A, hidden1, hidden2);
+    *best_bytes = (size_t)grad2_slab_bytes(D, A, hidden1, hidden2) * (size_t)kGrad2SlabCap;
+    return MGYM_OK;
+}
+
+int mgym_ppo_grad_mlp2(mgym_env* env, const float* policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, int32_t K,
+                       uint64_t env_first, uint64_t env_count, const float* obs_first, const float* obs, const void* actions, const float* logp_old,
+                       const float* adv, float clip, float ent_coef, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
+    ENV_OR_FAIL(env);
+    return grad_call(e, GradArgs{"mgym_ppo_grad_mlp2", true, true, policy, hidden1, hidden2, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions,
+                                 logp_old, adv, clip, ent_coef, workspace, workspace_bytes, grad_out, stats_out});
+}
+
+int mgym_value_grad_mlp2(mgym_env* env, const float* critic, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t K, uint64_t env_first,
+                         uint64_t env_count, const float* obs_first, const float* obs, const float* ret, void* workspace, size_t workspace_bytes, float* grad_out,
+                         float* stats_out) {
+    ENV_OR_FAIL(env);
+    return grad_call(e, GradArgs{"mgym_value_grad_mlp2", false, true, critic, hidden1, hidden2, activation, 0, 0.0f, K, env_first, env_count, obs_first, obs, nullptr,
+                                 ret, nullptr, 0.0f, 0.0f, workspace, workspace_bytes, grad_out, stats_out});
 }
 
 int mgym_grad_workspace_bytes(int kind, int32_t hidden, size_t* min_bytes, size_t* best_bytes) {
@@ -626,14 +666,14 @@ int mgym_ppo_grad_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_
                       uint64_t env_count, const float* obs_first, const float* obs, const void* actions, const float* logp_old, const float* adv, float clip,
                       float ent_coef, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
     ENV_OR_FAIL(env);
-    return grad_call(e, GradArgs{"mgym_ppo_grad_mlp", true, policy, hidden, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv,
+    return grad_call(e, GradArgs{"mgym_ppo_grad_mlp", true, false, policy, hidden, 0, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv,
                                  clip, ent_coef, workspace, workspace_bytes, grad_out, stats_out});
 }
 
 int mgym_value_grad_mlp(mgym_env* env, const float* critic, int32_t hidden, int32_t activation, int32_t K, uint64_t env_first, uint64_t env_count,
                         const float* obs_first, const float* obs, const float* ret, void* workspace, size_t workspace_bytes, float* grad_out, float* stats_out) {
     ENV_OR_FAIL(env);
-    return grad_call(e, GradArgs{"mgym_value_grad_mlp", false, critic, hidden, activation, 0, 0.0f, K, env_first, env_count, obs_first, obs, nullptr, ret, nullptr,
+    return grad_call(e, GradArgs{"mgym_value_grad_mlp", false, false, critic, hidden, 0, activation, 0, 0.0f, K, env_first, env_count, obs_first, obs, nullptr, ret, nullptr,
                                  0.0f, 0.0f, workspace, workspace_bytes, grad_out, stats_out});
 }
 

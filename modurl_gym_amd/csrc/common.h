@@ -109,6 +109,9 @@ struct Env {
     // mgym_logprob_mlp: a third pack, for the same reason — the call re-evaluates an actor, usually the one a mgym_rollout_mlp2 on the same stream or in the same
     // graph drew with, but it may be another (the learner's current weights against the behaviour policy's), and neither call may find the other's words
     float* logp_dev = nullptr;
+    // mgym_ppo_grad_mlp2 / mgym_value_grad_mlp2: a fourth and a fifth pack, the actor's and the critic's under their gradient calls, for the same reason
+    float* ppo_grad_dev = nullptr;
+    float* value_grad_dev = nullptr;
     int mlp2_store_to(float* dst, const float* weights, int D, int A, int H1, int H2);
     template <int D, int A>
     Mlp2Net<D, A> mlp2_net(const PolicyCall& call) const { return Mlp2Net<D, A>{mlp2_dev, call.hidden, call.hidden2, call.sigma}; }

@@ -15,8 +15,8 @@
 // f32 throughout, nothing reassociated, every selection a selection.  The SUMS over env-steps are not word-defined: the kernels add a lane's terms with fmaf
 // in f32, a wave's in f32, and everything beyond in f64; the host check adds in f64.
 //
-// Out of scope, here and in include/mgym.h: two hidden layers (dW2[H2][H1] needs a tiled product over the batch), the optimizer step, advantage normalisation,
-// flat-index minibatches, a clipped value loss, any state of the handle.
+// Two hidden layers are grad2.h and grad2.hip (dW2[H2][H1] is a tiled product over the batch).  Out of scope, here and in include/mgym.h: the optimizer step,
+// advantage normalisation, flat-index minibatches, a clipped value loss, any state of the handle.
 #pragma once
 #include <stdint.h>
 #include "logprob.h"

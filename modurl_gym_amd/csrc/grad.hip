@@ -10,6 +10,7 @@
 // the workspace.  The second launch adds the slabs in index order in f64, scales by 1 / B, rounds to f32 and writes grad_out and stats_out.  No atomics, no
 // tickets: the order of every sum is a function of the arguments alone.  A word outside the environments' range or beyond step K - 1 is never loaded.
 #include "learner.h"
+#include "grad2.h"
 
 namespace mgym {
 
@@ -26,45 +27,7 @@ static_assert(kGradWaves == 4, "the block's last sum names its four waves' slabs
 constexpr uint64_t kGradFillTiles = 256;
 constexpr int kGradSteps1 = 4;
 
-#if defined(GRAD_WAVE_SHFL)
-// (make EXTRA=-DGRAD_WAVE_SHFL: the same sum through six ds_bpermute butterflies.  Measured against the DPP form below in one session, DESIGN.md 5i: between
-// equal within 1 % and 26 % slower on the actor's rows, 1 - 4 % faster on the critic's tanh_fast rows only; not kept)
-__device__ __forceinline__ float grad_wave_sum(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-#else
-template <int CTRL>
-__device__ __forceinline__ float grad_dpp(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-// the sum of x over the wave's 64 lanes, the same word in every lane; all 64 lanes are active at every call.  quad_perm [1,0,3,2] and [2,3,0,1] leave every
-// lane of a quad with the quad's sum, row_half_mirror every lane of 8 with the sum of its two quads, row_mirror every lane of a row of 16 with the row's
-// sum (each step adds two values that both sides hold, so both get the same word); the four rows' sums are then read as scalars and added in row order
-__device__ __forceinline__ float grad_wave_sum(float x) {
-    x += grad_dpp<0xB1>(x);
-    x += grad_dpp<0x4E>(x);
-    x += grad_dpp<0x141>(x);
-    x += grad_dpp<0x140>(x);
-    const int xi = __float_as_int(x);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(xi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(xi, 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(xi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(xi, 48));
-    return ((r0 + r1) + r2) + r3;
-}
-#endif
-
-// N words of row `row` ([n] each) at environments i .. i + N - 1; the four-per-lane form by one 16-byte load at a 32-bit byte offset
-template <int N, class T>
-__device__ __forceinline__ void grad_load(const T* row, uint64_t i, T (&out)[N]) {
-    if constexpr (N == 4) {
-        typedef typename std::conditional<std::is_same<T, float>::value, float4, uint4>::type V4;
-        const V4 v = word_at<const V4>(row, (uint32_t)i * 4u);
-        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-    } else {
-        out[0] = row[i];
-    }
-}
+// (the wave sum, grad_wave_sum, is learner.h's: the two-layer kernels of grad2.hip take their tails through it too)
 
 template <int D, int A, int ACT, class Head, int N, int S>
 __global__ void __launch_bounds__(kBlock) grad_kernel(const MlpPack<D, A> net, const Head head, const GradCall c) {
@@ -188,6 +151,11 @@ __global__ void __launch_bounds__(kBlock) grad_finish_kernel(const double* ws, i
     else stats_out[out - (P + 1)] = r;
 }
 
+void grad_finish_launch(hipStream_t stream, const GradCall& c, int slabs, int P, bool gauss) {
+    hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((P + kGradTail + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, c.workspace, slabs, P,
+                       (double)c.K * (double)c.env_count, c.ent_coef, gauss ? 1 : 0, c.grad_out, c.stats_out);
+}
+
 template <int D, int A, int ACT, class Head>
 static void launch_form(hipStream_t stream, const GradCall& c, const MlpPack<D, A>& net, const Head& head) {
     bool four = four_per_lane(c.n, c.obs_first, c.obs, c.x0) && c.env_first % 4 == 0 && c.env_count % 4 == 0;
@@ -204,9 +172,7 @@ static void launch_form(hipStream_t stream, const GradCall& c, const MlpPack<D, 
     if (four && two) hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 4, 2>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
     else if (four) hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 4, 1>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
     else hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 1, kGradSteps1>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
-    const int P = mlp_policy_floats(D, A, net.hidden);
-    hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((P + kGradTail + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, c.workspace, (int)blocks, P,
-                       (double)c.K * (double)c.env_count, c.ent_coef, std::is_same<Head, PpoGaussian>::value ? 1 : 0, c.grad_out, c.stats_out);
+    grad_finish_launch(stream, c, (int)blocks, mlp_policy_floats(D, A, net.hidden), std::is_same<Head, PpoGaussian>::value);
 }
 
 template <int D, int A, class Head>

@@ -70,6 +70,47 @@ __device__ __forceinline__ V& word_at(T* row, uint32_t off) {
     return *reinterpret_cast<V*>(reinterpret_cast<Byte*>(row) + off);
 }
 
+// ---- the gradient kernels' wave sum (grad.hip, grad2.hip) ----
+#if defined(GRAD_WAVE_SHFL)
+// (make EXTRA=-DGRAD_WAVE_SHFL: the same sum through six ds_bpermute butterflies.  Measured against the DPP form below in one session, DESIGN.md 5i: between
+// equal within 1 % and 26 % slower on the actor's rows, 1 - 4 % faster on the critic's tanh_fast rows only; not kept)
+__device__ __forceinline__ float grad_wave_sum(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+#else
+template <int CTRL>
+__device__ __forceinline__ float grad_dpp(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
+}
+// the sum of x over the wave's 64 lanes, the same word in every lane; all 64 lanes are active at every call.  quad_perm [1,0,3,2] and [2,3,0,1] leave every
+// lane of a quad with the quad's sum, row_half_mirror every lane of 8 with the sum of its two quads, row_mirror every lane of a row of 16 with the row's
+// sum (each step adds two values that both sides hold, so both get the same word); the four rows' sums are then read as scalars and added in row order
+__device__ __forceinline__ float grad_wave_sum(float x) {
+    x += grad_dpp<0xB1>(x);
+    x += grad_dpp<0x4E>(x);
+    x += grad_dpp<0x141>(x);
+    x += grad_dpp<0x140>(x);
+    const int xi = __float_as_int(x);
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(xi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(xi, 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(xi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(xi, 48));
+    return ((r0 + r1) + r2) + r3;
+}
+#endif
+
+// N words of row `row` ([n] each) at environments i .. i + N - 1 (the gradient kernels); the four-per-lane form by one 16-byte load at a 32-bit byte offset
+template <int N, class T>
+__device__ __forceinline__ void grad_load(const T* row, uint64_t i, T (&out)[N]) {
+    if constexpr (N == 4) {
+        typedef typename std::conditional<std::is_same<T, float>::value, float4, uint4>::type V4;
+        const V4 v = word_at<const V4>(row, (uint32_t)i * 4u);
+        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+    } else {
+        out[0] = row[i];
+    }
+}
+
 // The four-per-lane dense pass of mgym_value_mlp and mgym_logprob_mlp (n % 4 == 0 and below 2^30, the rows 16-byte aligned): a lane owns four consecutive
 // environments of one row, loads the row's D components as D 16-byte words — and, where the call has actions, the four action words as one more, all issued
 // before the chains — runs mlp_scores<D, A, ACT, 4> with the weights as scalar operands, and stores one 16-byte word.  A row's address is a wave-uniform 64-bit

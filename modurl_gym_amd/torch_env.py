@@ -340,6 +340,61 @@ class TorchVecEnv:
         self.env.value_grad_mlp_device(packed, H, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats)
         return self._grad_views(grad, D, 1, H, False), stats
 
+    def _grad2_buffers(self, H1, H2, P):
+        """_grad_buffers for the two-layer calls: best_bytes of mgym_grad_workspace_bytes2, cached per ((H1, H2), stream)"""
+        torch = self._torch
+        key = ((int(H1), int(H2)), self._stream)
+        if key not in self._grad_ws:
+            self._grad_ws[key] = torch.empty(self.env.grad_workspace_bytes2(H1, H2)[1] // 8, dtype=torch.float64, device=self.device)
+        ws = self._grad_ws[key]
+        return ws, ws.numel() * 8, torch.empty(P + 1, dtype=torch.float32, device=self.device), torch.empty(8, dtype=torch.float32, device=self.device)
+
+    def _grad2_views(self, grad, D, A, H1, H2, log_sigma):
+        o1 = H1 * D
+        o2 = o1 + H1
+        o3 = o2 + H2 * H1
+        o4 = o3 + H2
+        o5 = o4 + A * H2
+        views = (grad[:o1].view(H1, D), grad[o1:o2], grad[o2:o3].view(H2, H1), grad[o3:o4], grad[o4:o5].view(A, H2), grad[o5: o5 + A])
+        return views + ((grad[o5 + A:],) if log_sigma else ())
+
+    def ppo_grad_mlp2(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None):
+        """ppo_grad_mlp for the two-hidden-layer actor (mgym_ppo_grad_mlp2): weights (w1, b1, w2, b2, w3, b3); activation "relu" or "tanh_fast".  Returns
+        (grads, stats): grads = (dw1, db1, dw2, db2, dw3, db3) as views of one tensor, shaped like the weights — and d / d log sigma [1] under the Gaussian
+        head; stats as ppo_grad_mlp's.  The workspace is cached per ((H1, H2), stream)."""
+        torch = self._torch
+        self._bind_stream()
+        host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
+        policy, H1, H2 = self.env.pack_mlp2(*host)
+        if head is None:
+            head = self.env._family_head()
+        K = int(obs.shape[0])
+        D, A = self.env.mlp_dims()
+        of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))
+        ac = self._kn(actions, torch.float32 if self.action_is_float else torch.int32, "actions", (K,))
+        lp, ad = self._kn(logp_old, torch.float32, "logp_old", (K,)), self._kn(adv, torch.float32, "adv", (K,))
+        first, count = (0, self.n) if env_slice is None else env_slice
+        ws, nbytes, grad, stats = self._grad2_buffers(H1, H2, H1 * (D + 1) + H2 * (H1 + 1) + A * (H2 + 1))
+        self.env.ppo_grad_mlp2_device(policy, H1, H2, activation, head, float(sigma), K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats)
+        return self._grad2_views(grad, D, A, H1, H2, head in ("gauss", E.L.HEAD_GAUSS)), stats
+
+    def value_grad_mlp2(self, critic, obs_first, obs, ret, activation="relu", env_slice=None):
+        """value_grad_mlp for a two-hidden-layer critic (w1, b1, w2, b2, w3 [1, H2], b3 [1]) (mgym_value_grad_mlp2).  Returns (grads, stats): grads = (dw1, db1,
+        dw2, db2, dw3, db3) views shaped like the weights, stats [8] float32."""
+        torch = self._torch
+        self._bind_stream()
+        host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in critic]
+        packed, H1, H2 = self.env.pack_critic(host)
+        if not H2:
+            raise ValueError("value_grad_mlp2 takes a critic with two hidden layers")
+        K, D = int(obs.shape[0]), self.obs_dim
+        of, ob = self._kn(obs_first, torch.float32, "obs_first", (D,)), self._kn(obs, torch.float32, "obs", (K, D))
+        rt = self._kn(ret, torch.float32, "ret", (K,))
+        first, count = (0, self.n) if env_slice is None else env_slice
+        ws, nbytes, grad, stats = self._grad2_buffers(H1, H2, H1 * (D + 1) + H2 * (H1 + 1) + H2 + 1)
+        self.env.value_grad_mlp2_device(packed, H1, H2, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats)
+        return self._grad2_views(grad, D, 1, H1, H2, False), stats
+
     def episode_returns(self, reward, done, truncated):
         """The return and length of every episode that ended inside the rollout (mgym_episode_returns): (return_out float32 [K, n], length_out int32 [K, n]),
         fresh tensors that are 0 except where done | truncated — `length_out > 0` is that mask.  The running episodes' carry lives in this object, created

@@ -296,6 +296,47 @@ unsafe extern "C" {
         grad_out: *mut f32,
         stats_out: *mut f32,
     ) -> c_int;
+    pub fn mgym_grad_workspace_bytes2(kind: c_int, hidden1: i32, hidden2: i32, min_bytes: *mut usize, best_bytes: *mut usize) -> c_int;
+    pub fn mgym_ppo_grad_mlp2(
+        env: *mut mgym_env,
+        policy: *const f32,
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        head: i32,
+        sigma: f32,
+        k: i32,
+        env_first: u64,
+        env_count: u64,
+        obs_first: *const f32,
+        obs: *const f32,
+        actions: *const c_void,
+        logp_old: *const f32,
+        adv: *const f32,
+        clip: f32,
+        ent_coef: f32,
+        workspace: *mut c_void,
+        workspace_bytes: usize,
+        grad_out: *mut f32,
+        stats_out: *mut f32,
+    ) -> c_int;
+    pub fn mgym_value_grad_mlp2(
+        env: *mut mgym_env,
+        critic: *const f32,
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        k: i32,
+        env_first: u64,
+        env_count: u64,
+        obs_first: *const f32,
+        obs: *const f32,
+        ret: *const f32,
+        workspace: *mut c_void,
+        workspace_bytes: usize,
+        grad_out: *mut f32,
+        stats_out: *mut f32,
+    ) -> c_int;
     pub fn mgym_episode_returns(
         env: *mut mgym_env,
         k: i32,

@@ -476,6 +476,67 @@ impl VecGym {
             mgym_value_grad_mlp(self.env, critic.as_ptr(), hidden, activation, k, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out)
         })
     }
+    /// `(min_bytes, best_bytes)` of the workspace of the two-layer gradient calls at these widths (`mgym_grad_workspace_bytes2`).
+    pub fn grad_workspace_bytes2(kind: i32, hidden1: i32, hidden2: i32) -> Result<(usize, usize), MgymError> {
+        let (mut lo, mut hi) = (0usize, 0usize);
+        check(unsafe { mgym_grad_workspace_bytes2(kind, hidden1, hidden2, &mut lo, &mut hi) })?;
+        Ok((lo, hi))
+    }
+    /// `ppo_grad_mlp` for the two-hidden-layer actor of `rollout_mlp2` (`mgym_ppo_grad_mlp2`): `policy` in that call's layout; `grad_out` receives
+    /// `dW1, db1, dW2, db2, dW3, db3` and one more word.
+    #[allow(clippy::too_many_arguments)]
+    pub fn ppo_grad_mlp2(
+        &mut self,
+        policy: &[f32],
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        head: i32,
+        sigma: f32,
+        k: i32,
+        env_first: u64,
+        env_count: u64,
+        obs_first: *const f32,
+        obs: *const f32,
+        actions: *const c_void,
+        logp_old: *const f32,
+        adv: *const f32,
+        clip: f32,
+        ent_coef: f32,
+        workspace: *mut c_void,
+        workspace_bytes: usize,
+        grad_out: *mut f32,
+        stats_out: *mut f32,
+    ) -> Result<(), MgymError> {
+        check(unsafe {
+            mgym_ppo_grad_mlp2(self.env, policy.as_ptr(), hidden1, hidden2, activation, head, sigma, k, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip,
+                               ent_coef, workspace, workspace_bytes, grad_out, stats_out)
+        })
+    }
+    /// `value_grad_mlp` for a two-hidden-layer critic (`mgym_value_grad_mlp2`).
+    #[allow(clippy::too_many_arguments)]
+    pub fn value_grad_mlp2(
+        &mut self,
+        critic: &[f32],
+        hidden1: i32,
+        hidden2: i32,
+        activation: i32,
+        k: i32,
+        env_first: u64,
+        env_count: u64,
+        obs_first: *const f32,
+        obs: *const f32,
+        ret: *const f32,
+        workspace: *mut c_void,
+        workspace_bytes: usize,
+        grad_out: *mut f32,
+        stats_out: *mut f32,
+    ) -> Result<(), MgymError> {
+        check(unsafe {
+            mgym_value_grad_mlp2(self.env, critic.as_ptr(), hidden1, hidden2, activation, k, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes,
+                                 grad_out, stats_out)
+        })
+    }
     /// The return and length of the episodes that end inside a rollout (`mgym_episode_returns`): `ep_return` / `ep_length` are the caller's carry of the
     /// running episodes (read and written); `return_out` / `length_out` (`[K][n]`, may be null) are written only where `done | truncated`.
     #[allow(clippy::too_many_arguments)]

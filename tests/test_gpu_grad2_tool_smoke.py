@@ -1,0 +1,29 @@
+"""tools/grad_time.py --hidden2 8 end to end at its small size: one repeat, a 20 ms window, 4 096 environments only (--sizes 4096).  The record names the
+two-layer run (hidden2, the nets "32x8" and "64x8"), holds every row of that population with a positive median, and the ratios of every row.  No figure is
+compared: the tool runs a product path that tests/test_gpu_grad2_mlp.py checks against float64, and this is about the option running and writing its record."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIMIT_S = 240
+
+
+def test_grad_time_hidden2_runs_and_writes_its_record(tmp_path):
+    out = tmp_path / "record.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "grad_time.py"), "--hidden2", "8", "--repeats", "1", "--window", "0.02", "--sizes", "4096",
+                        "--out", str(out)], capture_output=True, text=True, timeout=LIMIT_S)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    doc = json.loads(out.read_text())
+    assert doc["hidden2"] == 8 and doc["nets"] == ["32x8", "64x8"] and doc["n_envs"] == [4096] and doc["repeats"] == 1
+    rows = {f"{f}/n4096/{net}/{act}" for f in ("cartpole", "pendulum") for net in ("32x8", "64x8") for act in ("relu", "tanh_fast")}
+    assert set(doc["summary"]) == {f"{row}/{c}" for row in rows for c in ("ppo", "ppo4", "value", "logp", "torch")}
+    for row in doc["summary"].values():
+        assert row["median"] > 0 and len(row["repeats"]) == 1
+    assert set(doc["ratios"]) == rows
+    assert all({"torch_over_ppo", "faster_beyond_spread", "ppo4_over_ppo", "ppo_over_logp"} <= set(v) for v in doc["ratios"].values())

@@ -17,6 +17,9 @@ Columns, ns per env-step (K x n of them), all in one process:
               the entropy bonus, backward(), the gradients flattened into one tensor
 The record's ratios: torch / ppo with faster_beyond_spread (the slowest fused repeat beats the fastest torch repeat); ppo4 / ppo; ppo / logp; and the
 algorithmic bytes of a ppo env-step, D + 3 words, over its time as a share of 8 TB/s.
+--hidden2 H2 (default 0: everything above, unchanged) times the two-layer calls instead — mgym_ppo_grad_mlp2, mgym_value_grad_mlp2 and mgym_logprob_mlp at
+hidden2 = H2 — against the torch update of the same two-layer net, H2 = -1 meaning the first width again ((32, 32) and (64, 64)); the rows are then named
+"32x32" and the record says hidden2.
 Not measured here: hardware counters, other sizes or K, LunarLander, the one-per-lane kernels, a full training loop."""
 import argparse
 import os
@@ -37,7 +40,7 @@ SIGMA, CLIP, ENT_COEF = 0.5, 0.2, 0.01
 PEAK_BYTES_PER_S = 8e12
 
 
-def worker(sizes, window, rotate, columns, lib):
+def worker(sizes, window, rotate, columns, lib, hidden2=0):
     sys.path.insert(0, ROOT)
     if lib:
         from modurl_gym_amd import _lib
@@ -50,11 +53,17 @@ def worker(sizes, window, rotate, columns, lib):
     def window_of(body):
         return timing.window_of(timing.torch_timed(body), window, 3, 3)
 
+    def second(H):
+        return H if hidden2 < 0 else hidden2
+
     def weights(family, H, outputs):
         lo, hi = FAMILIES[family]
         rng = np.random.default_rng(100 + H)
-        return [(rng.normal(0, 1, (H, len(lo))) / np.array(hi)).astype(np.float32), rng.normal(0, 0.5, H).astype(np.float32),
-                (rng.normal(0, 1, (outputs, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.5, outputs).astype(np.float32)]
+        w = [(rng.normal(0, 1, (H, len(lo))) / np.array(hi)).astype(np.float32), rng.normal(0, 0.5, H).astype(np.float32)]
+        if hidden2:
+            w += [(rng.normal(0, 1.5, (second(H), H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.5, second(H)).astype(np.float32)]
+            H = second(H)
+        return w + [(rng.normal(0, 1, (outputs, H)) / np.sqrt(H)).astype(np.float32), rng.normal(0, 0.5, outputs).astype(np.float32)]
 
     def inputs(family, n, env, policy, H, act):
         lo, hi = (torch.tensor(x, device="cuda")[:, None] for x in FAMILIES[family])
@@ -64,7 +73,7 @@ def worker(sizes, window, rotate, columns, lib):
         x["acts"] = torch.randint(0, 2, (K, n), device="cuda", generator=g, dtype=torch.int32) if family == "cartpole" else torch.randn(K, n, device="cuda", generator=g)
         x["old"] = torch.empty((K, n), device="cuda")
         if policy is not None:
-            env.env.logprob_mlp_device(policy, H, 0, act, HEAD[family], SIGMA, K, x["first"], x["obs"], x["acts"], x["old"])
+            env.env.logprob_mlp_device(policy, H, second(H) if hidden2 else 0, act, HEAD[family], SIGMA, K, x["first"], x["obs"], x["acts"], x["old"])
             x["old"] += 0.1 * torch.randn(K, n, device="cuda", generator=g)
         x["adv"], x["ret"] = torch.randn(K, n, device="cuda", generator=g), torch.randn(K, n, device="cuda", generator=g)
         return x
@@ -74,19 +83,27 @@ def worker(sizes, window, rotate, columns, lib):
         w = weights(family, H, outputs)
         env = mg.TorchVecEnv(kinds[family], n)
         env._bind_stream()
-        policy = (env.env.pack_critic(w)[0] if column == "value" else env.env.pack_mlp(*w)[0])
+        policy = env.env.pack_critic(w)[0] if column == "value" else (env.env.pack_mlp2(*w)[0] if hidden2 else env.env.pack_mlp(*w)[0])
+        H2 = second(H) if hidden2 else 0
         x = inputs(family, n, env, None if column == "value" else policy, H, act)
-        nbytes = env.env.grad_workspace_bytes(H)[1]
+        nbytes = env.env.grad_workspace_bytes2(H, H2)[1] if H2 else env.env.grad_workspace_bytes(H)[1]
         ws = torch.empty(nbytes // 8, dtype=torch.float64, device="cuda")
         grad, stats, logp = torch.empty(len(policy) + 1, device="cuda"), torch.empty(8, device="cuda"), torch.empty((K, n), device="cuda")
         e = env.env
 
         def ppo(first, count):
+            if H2:
+                return e.ppo_grad_mlp2_device(policy, H, H2, act, HEAD[family], SIGMA, K, first, count, x["first"], x["obs"], x["acts"], x["old"], x["adv"], CLIP, ENT_COEF,
+                                              ws, nbytes, grad, stats)
             e.ppo_grad_mlp_device(policy, H, act, HEAD[family], SIGMA, K, first, count, x["first"], x["obs"], x["acts"], x["old"], x["adv"], CLIP, ENT_COEF, ws, nbytes,
                                   grad, stats)
-        body = {"ppo": lambda: ppo(0, n), "ppo4": lambda: [ppo(k * (n // 4), n // 4) for k in range(4)],
-                "value": lambda: e.value_grad_mlp_device(policy, H, act, K, 0, n, x["first"], x["obs"], x["ret"], ws, nbytes, grad, stats),
-                "logp": lambda: e.logprob_mlp_device(policy, H, 0, act, HEAD[family], SIGMA, K, x["first"], x["obs"], x["acts"], logp)}[column]
+
+        def value():
+            if H2:
+                return e.value_grad_mlp2_device(policy, H, H2, act, K, 0, n, x["first"], x["obs"], x["ret"], ws, nbytes, grad, stats)
+            e.value_grad_mlp_device(policy, H, act, K, 0, n, x["first"], x["obs"], x["ret"], ws, nbytes, grad, stats)
+        body = {"ppo": lambda: ppo(0, n), "ppo4": lambda: [ppo(k * (n // 4), n // 4) for k in range(4)], "value": value,
+                "logp": lambda: e.logprob_mlp_device(policy, H, H2, act, HEAD[family], SIGMA, K, x["first"], x["obs"], x["acts"], logp)}[column]
         res = window_of(body)
         env.check()
         assert bool(torch.isfinite(grad).all()) or column == "logp"
@@ -97,7 +114,7 @@ def worker(sizes, window, rotate, columns, lib):
         env = mg.TorchVecEnv(kinds[family], n)
         env._bind_stream()
         w = weights(family, H, OUTPUTS[family])
-        x = inputs(family, n, env, env.env.pack_mlp(*w)[0], H, act)
+        x = inputs(family, n, env, (env.env.pack_mlp2(*w) if hidden2 else env.env.pack_mlp(*w))[0], H, act)
         env.close()
         params = [torch.from_numpy(a).cuda().requires_grad_(True) for a in w] + [torch.tensor([float(np.log(SIGMA))], device="cuda", requires_grad=True)]
         fn = torch.relu if act == "relu" else torch.tanh
@@ -106,10 +123,12 @@ def worker(sizes, window, rotate, columns, lib):
         acts, old, adv = x["acts"].reshape(-1), x["old"].reshape(-1), x["adv"].reshape(-1)
 
         def body():
-            w1, b1, w2, b2, ls = params
             for p in params:
                 p.grad = None
-            s = torch.addmm(b2, fn(torch.addmm(b1, rows, w1.T)), w2.T)
+            s, ls = rows, params[-1]
+            for k in range(0, len(params) - 3, 2):
+                s = fn(torch.addmm(params[k + 1], s, params[k].T))
+            s = torch.addmm(params[-2], s, params[-3].T)
             if index is not None:
                 lsm = torch.log_softmax(s, 1)
                 logp, ent = lsm.gather(1, index)[:, 0], -(lsm.exp() * lsm).sum(1).mean()
@@ -133,8 +152,12 @@ def worker(sizes, window, rotate, columns, lib):
     out = []
     for n, family, H, act, column, run in timing.rotated(cases, rotate):
         ms, count = run()
-        out.append(dict(n_envs=n, family=family, net=str(H), activation=act, case=column, calls=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n)))
+        out.append(dict(n_envs=n, family=family, net=net_name(H, hidden2), activation=act, case=column, calls=count, window_ms=ms, ns_per_env_step=ms * 1e6 / (count * K * n)))
     timing.emit(out)
+
+
+def net_name(H, hidden2):
+    return str(H) if not hidden2 else f"{H}x{H if hidden2 < 0 else hidden2}"
 
 
 def record(runs, args, sizes):
@@ -150,7 +173,7 @@ def record(runs, args, sizes):
         ratios[row] = dict(torch_over_ppo=t["median"] / v["median"], faster_beyond_spread=v["max"] < t["min"], ppo4_over_ppo=four["median"] / v["median"],
                            ppo_over_logp=v["median"] / logp["median"], share_of_8_tb_s=4 * words / (v["median"] * 1e-9) / PEAK_BYTES_PER_S)
     head = dict(unit="ns per env-step (K x n per call)", window_s=args.window, repeats=args.repeats, n_envs=list(sizes), K=K, families=list(FAMILIES), heads=HEAD,
-                sigma=SIGMA, clip=CLIP, ent_coef=ENT_COEF, nets=[str(h) for h in WIDTHS], activations=list(ACTIVATIONS),
+                sigma=SIGMA, clip=CLIP, ent_coef=ENT_COEF, nets=[net_name(h, args.hidden2) for h in WIDTHS], activations=list(ACTIVATIONS),
                 cases="ppo: mgym_ppo_grad_mlp over the full range; ppo4: the same batch as 4 calls on 4 slices of the environments; value: mgym_value_grad_mlp, a critic "
                       "of the same width; logp: mgym_logprob_mlp of the same actor; torch: addmm / activation, log_softmax + gather or the Gaussian log-density, the "
                       "clipped surrogate with the entropy bonus, backward(), the gradients flattened; all of a repeat in one process, device events around a window of "
@@ -160,6 +183,9 @@ def record(runs, args, sizes):
                 not_measured="hardware counters, other sizes or K, LunarLander, the one-per-lane kernels, a full training loop", ratios=ratios)
     if args.lib or tuple(args.columns) != COLUMNS:   # an A/B run names its build and its columns; the full run's record keeps its keys
         head.update(lib=os.path.basename(args.lib) if args.lib else "the package's", columns=list(args.columns))
+    if args.hidden2:   # the two-layer run names itself; the one-layer record keeps its keys
+        head.update(hidden2=args.hidden2, two_layers="ppo, ppo4 and value are mgym_ppo_grad_mlp2 / mgym_value_grad_mlp2, logp is mgym_logprob_mlp at hidden2, torch is "
+                                                    "the update of the same two-layer net")
     return head, table
 
 
@@ -171,15 +197,16 @@ def main():
     ap.add_argument("--out", required=True, help="record file (the committed record of the full run: profiles/grad_time.json)")
     ap.add_argument("--columns", default=",".join(COLUMNS), help="the columns to time, comma separated (the ratios need all of them)")
     ap.add_argument("--lib", default="", help="time this build of libmgym.so instead of the package's (an A/B of two builds on one machine)")
+    ap.add_argument("--hidden2", type=int, default=0, help="0: one hidden layer; H2: the two-layer calls at (H, H2); -1: at (H, H)")
     ap.add_argument("--worker", metavar="ROTATE", type=int)
     args = ap.parse_args()
     sizes = tuple(int(s) for s in args.sizes.split(","))
     args.columns = tuple(args.columns.split(","))
     assert set(args.columns) <= set(COLUMNS), args.columns
     if args.worker is not None:
-        return worker(sizes, args.window, args.worker, args.columns, args.lib)
+        return worker(sizes, args.window, args.worker, args.columns, args.lib, args.hidden2)
     runs = timing.run_children(lambda _, rep: [os.path.abspath(__file__), "--worker", str(7 * rep), "--window", str(args.window), "--sizes", args.sizes, "--out", args.out,
-                                                "--columns", ",".join(args.columns), "--lib", args.lib],
+                                                "--columns", ",".join(args.columns), "--lib", args.lib, "--hidden2", str(args.hidden2)],
                                [None], args.repeats, 900)
     head, table = record(runs, args, sizes)
     timing.write_record(args.out, head, table)
