@@ -766,7 +766,7 @@ int mgym_value_grad_mlp(mgym_env *env, const float *critic, int32_t hidden, int3
  *   terms:  dW3[a][k] += ds_a * h2_k;  db3[a] += ds_a;  dW2[k][j] += dpre2_k * h1_j;  db2[k] += dpre2_k;  dW1[j][q] += dpre1_j * o_q;  db1[j] += dpre1_j
  * (modurl_gym_amd/csrc/grad2.h is this text as the kernels and a g++ build compile it.)  The SUMS over the B env-steps are not word-defined, and neither are the
  * products inside them: the kernels form them on the f32 matrix pipe (exact f32 products, an f32 accumulator over at most 128 env-steps of a wave) and add
- * everything beyond in f64; every sum is divided by B once at the end, in f64.  The values are bounded against float64 (tests/grad2_ref.py: GRAD2_BOUND times
+ * everything beyond in f64; every sum is divided by B once at the end, in f64.  The values are bounded against float64 (tests/grad_ref.py: GRAD2_BOUND times
  * the word's mean absolute per-env-step term).
  * Workspace.  A slab is P2 + 8 f64 words.  mgym_grad_workspace_bytes2(kind, hidden1, hidden2) gives min_bytes, one slab, and best_bytes, 256 slabs: a block of
  * these kernels holds most of a compute unit's LDS, so one block is resident on each of the chip's 256 compute units and more slabs would only lengthen the last

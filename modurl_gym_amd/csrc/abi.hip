@@ -625,15 +625,21 @@ static int grad_call(Env* e, const GradArgs& a) {
     return grad2_launch(e->stream, c, D, A, head, pack_dev, a.hidden, a.hidden2, a.activation);
 }
 
-int mgym_grad_workspace_bytes2(int kind, int32_t hidden1, int32_t hidden2, size_t* min_bytes, size_t* best_bytes) {
+// the workspace query `name` of a gradient call with `depth` hidden layers of the widths hidden[0 .. depth - 1]; cap: the most slabs a launch uses
+static int grad_workspace_bytes(const char* name, int kind, int depth, const int32_t (&hidden)[2], int cap, size_t* min_bytes, size_t* best_bytes) {
+    const auto bad = [&](const std::string& what) { return bad_arg((std::string(name) + ": " + what).c_str()); };
     int D = 0, A = 1;
-    if (family_dims(kind, &D, &A) != MGYM_OK) return bad_arg("mgym_grad_workspace_bytes2: unknown kind");
-    if (hidden1 < 1 || hidden1 > 64) return bad_arg("mgym_grad_workspace_bytes2: hidden1 must be between 1 and 64");
-    if (hidden2 < 1 || hidden2 > 64) return bad_arg("mgym_grad_workspace_bytes2: hidden2 must be between 1 and 64");
-    if (!min_bytes || !best_bytes) return bad_arg(!min_bytes ? "mgym_grad_workspace_bytes2: min_bytes is NULL" : "mgym_grad_workspace_bytes2: best_bytes is NULL");
-    *min_bytes = (size_t)grad2_slab_bytes(D, A, hidden1, hidden2);
-    *best_bytes = (size_t)grad2_slab_bytes(D, A, hidden1, hidden2) * (size_t)kGrad2SlabCap;
+    if (family_dims(kind, &D, &A) != MGYM_OK) return bad("unknown kind");
+    for (int l = 0; l < depth; ++l)
+        if (hidden[l] < 1 || hidden[l] > 64) return bad((depth == 1 ? std::string("hidden") : "hidden" + std::to_string(l + 1)) + " must be between 1 and 64");
+    if (!min_bytes || !best_bytes) return bad(!min_bytes ? "min_bytes is NULL" : "best_bytes is NULL");
+    *min_bytes = (size_t)(depth == 1 ? grad_slab_bytes(D, A, hidden[0]) : grad2_slab_bytes(D, A, hidden[0], hidden[1]));
+    *best_bytes = *min_bytes * (size_t)cap;
     return MGYM_OK;
+}
+
+int mgym_grad_workspace_bytes2(int kind, int32_t hidden1, int32_t hidden2, size_t* min_bytes, size_t* best_bytes) {
+    return grad_workspace_bytes("mgym_grad_workspace_bytes2", kind, 2, {hidden1, hidden2}, kGrad2SlabCap, min_bytes, best_bytes);
 }
 
 int mgym_ppo_grad_mlp2(mgym_env* env, const float* policy, int32_t hidden1, int32_t hidden2, int32_t activation, int32_t head, float sigma, int32_t K,
@@ -653,13 +659,7 @@ int mgym_value_grad_mlp2(mgym_env* env, const float* critic, int32_t hidden1, in
 }
 
 int mgym_grad_workspace_bytes(int kind, int32_t hidden, size_t* min_bytes, size_t* best_bytes) {
-    int D = 0, A = 1;
-    if (family_dims(kind, &D, &A) != MGYM_OK) return bad_arg("mgym_grad_workspace_bytes: unknown kind");
-    if (hidden < 1 || hidden > 64) return bad_arg("mgym_grad_workspace_bytes: hidden must be between 1 and 64");
-    if (!min_bytes || !best_bytes) return bad_arg(!min_bytes ? "mgym_grad_workspace_bytes: min_bytes is NULL" : "mgym_grad_workspace_bytes: best_bytes is NULL");
-    *min_bytes = (size_t)grad_slab_bytes(D, A, hidden);
-    *best_bytes = (size_t)grad_slab_bytes(D, A, hidden) * (size_t)kGradSlabCap;
-    return MGYM_OK;
+    return grad_workspace_bytes("mgym_grad_workspace_bytes", kind, 1, {hidden, 0}, kGradSlabCap, min_bytes, best_bytes);
 }
 
 int mgym_ppo_grad_mlp(mgym_env* env, const float* policy, int32_t hidden, int32_t activation, int32_t head, float sigma, int32_t K, uint64_t env_first,

@@ -142,6 +142,10 @@ struct ValueMse {
 MG_HD bool grad_clip_ok(float clip) { return clip >= 0.0f && clip < 1.0f; }                                       // (a NaN fails the first test)
 MG_HD bool grad_ent_coef_ok(float x) { return x >= -3.402823466e+38f && x <= 3.402823466e+38f; }
 
+// act' of a unit from its pre-activation and its activation: the one rule of the backward words at both depths
+template <int ACT>
+MG_HD float grad_dact(float pre, float h) { return ACT == MLP_ACT_RELU ? (pre > 0.0f ? 1.0f : 0.0f) : 1.0f - h * h; }
+
 // hidden unit j of one env-step, u = W1[j][0 .. D-1], b1[j], W2[0 .. A-1][j]: h_j (recomputed: the chain and the activation of mlp_hidden) and dpre_j
 template <int D, int A, int ACT>
 MG_HD void grad_unit(const float* u, const float (&o)[D], const float (&ds)[A], float* h_out, float* dpre_out) {
@@ -152,9 +156,8 @@ MG_HD void grad_unit(const float* u, const float (&o)[D], const float (&ds)[A], 
     float dh = u[D + 1] * ds[0];
 #pragma unroll
     for (int a = 1; a < A; ++a) dh = dh + u[D + 1 + a] * ds[a];
-    const float dact = ACT == MLP_ACT_RELU ? (pre > 0.0f ? 1.0f : 0.0f) : 1.0f - h * h;
     *h_out = h;
-    *dpre_out = dh * dact;
+    *dpre_out = dh * grad_dact<ACT>(pre, h);
 }
 
 // where the sums of a slab stand, the caller's nn.Linear order: dW1[H][D], db1[H], dW2[A][H], db2[A], then the tail
@@ -216,6 +219,8 @@ struct GradCall {
 };
 enum { GRAD_HEAD_CATEGORICAL = 0, GRAD_HEAD_GAUSS = 1, GRAD_HEAD_VALUE = 2 };
 int grad_launch(hipStream_t stream, const GradCall& call, int D, int A, int head, const float* weights, int32_t hidden, int32_t activation);
+// grad.hip: the last sum of a gradient call of either depth, grad_finish_kernel over `slabs` slabs of P + kGradTail words
+void grad_finish_launch(hipStream_t stream, const GradCall& call, int slabs, int P, bool gauss);
 #endif
 
 }  // namespace mgym

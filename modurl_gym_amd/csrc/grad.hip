@@ -10,7 +10,6 @@
 // the workspace.  The second launch adds the slabs in index order in f64, scales by 1 / B, rounds to f32 and writes grad_out and stats_out.  No atomics, no
 // tickets: the order of every sum is a function of the arguments alone.  A word outside the environments' range or beyond step K - 1 is never loaded.
 #include "learner.h"
-#include "grad2.h"
 
 namespace mgym {
 
@@ -158,17 +157,14 @@ void grad_finish_launch(hipStream_t stream, const GradCall& c, int slabs, int P,
 
 template <int D, int A, int ACT, class Head>
 static void launch_form(hipStream_t stream, const GradCall& c, const MlpPack<D, A>& net, const Head& head) {
-    bool four = four_per_lane(c.n, c.obs_first, c.obs, c.x0) && c.env_first % 4 == 0 && c.env_count % 4 == 0;
-    if (Head::kPpo) four = four && aligned(c.actions, 16) && aligned(c.x1, 16);
-    const uint64_t lanes = (c.env_count + (four ? 4 : 1) - 1) / (four ? 4 : 1), tiles_x = (lanes + kBlock - 1) / kBlock;
-    const auto tiles_at = [&](int S) { return tiles_x * (uint64_t)((c.K + S - 1) / S); };
+    const bool four = grad_four_per_lane(c, Head::kPpo);
+    const int N = four ? 4 : 1;
 #if defined(GRAD_STEPS4)
     const bool two = GRAD_STEPS4 == 2;
 #else
-    const bool two = tiles_at(2) >= kGradFillTiles;
+    const bool two = grad_tiles(c, N, 2) >= kGradFillTiles;
 #endif
-    const uint64_t tiles = tiles_at(four ? (two ? 2 : 1) : kGradSteps1);
-    const unsigned blocks = (unsigned)(tiles < (uint64_t)c.slabs ? tiles : (uint64_t)c.slabs);
+    const unsigned blocks = grad_blocks(c, N, four ? (two ? 2 : 1) : kGradSteps1);
     if (four && two) hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 4, 2>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
     else if (four) hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 4, 1>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
     else hipLaunchKernelGGL((grad_kernel<D, A, ACT, Head, 1, kGradSteps1>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);

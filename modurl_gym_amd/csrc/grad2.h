@@ -1,12 +1,12 @@
 // grad2.h — the words of mgym_ppo_grad_mlp2 and mgym_value_grad_mlp2 (include/mgym.h): the gradient calls of grad.h for the two-hidden-layer net of
 // mgym_rollout_mlp2.  The heads (ds, the log-sigma term, the statistics' terms) are grad.h's, unchanged, applied to the scores of mlp2_policy.h; this header
 // adds the backward words of the two hidden layers and the host form of the whole call.  Shared by the kernels of grad2.hip and the host check
-// tests/native/grad2_check.cpp, which compiles it with g++.  Compile with -ffp-contract=off: the only fused operations are the cp_fmaf of the chains.
+// tests/native/grad_check.cpp, which compiles it with g++.  Compile with -ffp-contract=off: the only fused operations are the cp_fmaf of the chains.
 //
 //   pre1_j, h1_j, pre2_k, h2_k, s_a     mlp2_policy.h's three chains, unpadded
 //   ds_a, the log-sigma term, the statistics' terms     grad.h's heads on these s_a
 //   dh2_k   = W3[0][k] * ds_0;  a = 1 .. A-1: dh2_k = dh2_k + W3[a][k] * ds_a
-//   dpre2_k = dh2_k * act'(k)           act' = pre2_k > 0 ? 1.0f : 0.0f (ReLU), 1.0f - h2_k * h2_k (tanh_fast)
+//   dpre2_k = dh2_k * act'(k)           act' = pre2_k > 0 ? 1.0f : 0.0f (ReLU), 1.0f - h2_k * h2_k (tanh_fast): grad.h's grad_dact
 //   dh1_j   = +0.0f;  k = 0 .. H2-1 ascending: dh1_j = fmaf(W2[k][j], dpre2_k, dh1_j)
 //   dpre1_j = dh1_j * act'(j)           the same rule on pre1_j / h1_j (under ReLU h1_j > 0 exactly when pre1_j > 0: mlp_activate)
 //   terms   dW3[a][k] += ds_a * h2_k;  db3[a] += ds_a;  dW2[k][j] += dpre2_k * h1_j;  db2[k] += dpre2_k;  dW1[j][q] += dpre1_j * o_q;  db1[j] += dpre1_j
@@ -32,12 +32,6 @@ MG_HD int grad2_at_w2(int D, int H1, int k, int j) { return H1 * (D + 1) + k * H
 MG_HD int grad2_at_b2(int D, int H1, int H2, int k) { return H1 * (D + 1) + H2 * H1 + k; }
 MG_HD int grad2_at_w3(int D, int H1, int H2, int a, int k) { return H1 * (D + 1) + H2 * (H1 + 1) + a * H2 + k; }
 MG_HD int grad2_at_b3(int D, int A, int H1, int H2, int a) { return H1 * (D + 1) + H2 * (H1 + 1) + A * H2 + a; }
-
-// act' of a unit from its pre-activation and its activation
-template <int ACT>
-MG_HD float grad2_dact(float pre, float h) {
-    return ACT == MLP_ACT_RELU ? (pre > 0.0f ? 1.0f : 0.0f) : 1.0f - h * h;
-}
 
 // dh2_k of one env-step; u = unit k's run of the pack: b2[k], W3[0 .. A-1][k]
 template <int A>
@@ -81,10 +75,10 @@ static inline void grad2_step(const float* pack, int H1, int H2, const Head& hea
     for (int j = 0; j < H1; ++j) w.dh1[j] = 0.0f;
     for (int k = 0; k < H2; ++k) {
         const float* u = pack + l2 + k * stride;
-        w.dpre2[k] = grad2_dh2<A>(u, w.g.ds) * grad2_dact<ACT>(w.pre2[k], w.h2[k]);
+        w.dpre2[k] = grad2_dh2<A>(u, w.g.ds) * grad_dact<ACT>(w.pre2[k], w.h2[k]);
         for (int j = 0; j < H1; ++j) w.dh1[j] = cp_fmaf(u[kMlp2Head + j], w.dpre2[k], w.dh1[j]);
     }
-    for (int j = 0; j < H1; ++j) w.dpre1[j] = w.dh1[j] * grad2_dact<ACT>(w.pre1[j], w.h1[j]);
+    for (int j = 0; j < H1; ++j) w.dpre1[j] = w.dh1[j] * grad_dact<ACT>(w.pre1[j], w.h1[j]);
 }
 
 // every env-step of environments first .. first + count - 1 added into sums[P2 + kGradTail] in f64, steps ascending inside environments ascending: the host
@@ -120,8 +114,6 @@ static inline void grad2_envs(const float* pack, int H1, int H2, const Head& hea
 #if defined(__HIPCC__)
 // grad2.hip: the two launches of a two-layer gradient call on `stream`, arguments already checked (abi.hip); the weights stand in `pack_dev` by then
 int grad2_launch(hipStream_t stream, const GradCall& call, int D, int A, int head, const float* pack_dev, int32_t hidden1, int32_t hidden2, int32_t activation);
-// grad.hip: the last sum of a gradient call, grad_finish_kernel over `slabs` slabs of P + kGradTail words
-void grad_finish_launch(hipStream_t stream, const GradCall& call, int slabs, int P, bool gauss);
 #endif
 
 }  // namespace mgym

@@ -196,7 +196,7 @@ __global__ void __launch_bounds__(kBlock) grad2_kernel(const Mlp2Net<D, A> net, 
                         const Mlp2Ptr u = p + l2 + (16 * cc + kk) * stride;
                         const float pre = pre2_of(u);
                         const float h2 = mlp_activate<ACT>(pre);
-                        const float dpre2 = grad2_dh2<A>(u, ds) * grad2_dact<ACT>(pre, h2);
+                        const float dpre2 = grad2_dh2<A>(u, ds) * grad_dact<ACT>(pre, h2);
                         c1[kk * kG2Stride + lane] = dpre2;
                         c2[kk * kG2Stride + lane] = h2;
 #pragma unroll
@@ -231,13 +231,13 @@ __global__ void __launch_bounds__(kBlock) grad2_kernel(const Mlp2Net<D, A> net, 
 #pragma unroll
                     for (int jj = 0; jj < 16; ++jj) {
                         const int j = 16 * cc + jj;
-                        if (j < full) c1[jj * kG2Stride + lane] = dh1[j] * grad2_dact<ACT>(h1[j], h1[j]);   // (ReLU: h1_j > 0 exactly when pre1_j > 0)
+                        if (j < full) c1[jj * kG2Stride + lane] = dh1[j] * grad_dact<ACT>(h1[j], h1[j]);   // (ReLU: h1_j > 0 exactly when pre1_j > 0)
                     }
                     if (cc == (full >> 4)) {
 #pragma unroll
                         for (int jj = 0; jj < 7; ++jj) {
                             if (jj >= rem) break;
-                            c1[((full & 15) + jj) * kG2Stride + lane] = dht[jj] * grad2_dact<ACT>(ht[jj], ht[jj]);
+                            c1[((full & 15) + jj) * kG2Stride + lane] = dht[jj] * grad_dact<ACT>(ht[jj], ht[jj]);
                         }
                     }
                     g2_wave_sync();
@@ -288,11 +288,9 @@ __global__ void __launch_bounds__(kBlock) grad2_kernel(const Mlp2Net<D, A> net, 
 
 template <int D, int A, int ACT, class Head>
 static void launch_form(hipStream_t stream, const GradCall& c, const Mlp2Net<D, A>& net, const Head& head) {
-    bool four = four_per_lane(c.n, c.obs_first, c.obs, c.x0) && c.env_first % 4 == 0 && c.env_count % 4 == 0;
-    if (Head::kPpo) four = four && aligned(c.actions, 16) && aligned(c.x1, 16);
-    const int N = four ? 4 : 1, S = kG2Steps / N;
-    const uint64_t lanes = (c.env_count + N - 1) / N, tiles = ((lanes + kBlock - 1) / kBlock) * (uint64_t)((c.K + S - 1) / S);
-    const unsigned blocks = (unsigned)(tiles < (uint64_t)c.slabs ? tiles : (uint64_t)c.slabs);
+    const bool four = grad_four_per_lane(c, Head::kPpo);
+    const int N = four ? 4 : 1;
+    const unsigned blocks = grad_blocks(c, N, kG2Steps / N);
     if (four) hipLaunchKernelGGL((grad2_kernel<D, A, ACT, Head, 4>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
     else hipLaunchKernelGGL((grad2_kernel<D, A, ACT, Head, 1>), dim3(blocks), dim3(kBlock), 0, stream, net, head, c);
     grad_finish_launch(stream, c, (int)blocks, mlp2_policy_floats(D, A, net.h1, net.h2), std::is_same<Head, PpoGaussian>::value);

@@ -15,6 +15,20 @@ inline unsigned grid_rows(unsigned rows) { return rows < kMaxGridY ? rows : kMax
 template <class... P>
 inline bool four_per_lane(uint64_t n, const P*... rows) { return n % 4 == 0 && n < kFourMaxEnvs && (aligned(rows, 16) && ...); }
 
+// The launch shape of a gradient call of either depth (grad.hip, grad2.hip).  Four environments per lane: every row the kernel loads 16 bytes at a time aligned
+// and the range a whole number of fours; the tiles of 256 lanes x N environments x S steps over K x env_count env-steps; one block per tile up to the slabs
+inline bool grad_four_per_lane(const GradCall& c, bool ppo) {
+    return four_per_lane(c.n, c.obs_first, c.obs, c.x0) && c.env_first % 4 == 0 && c.env_count % 4 == 0 && (!ppo || (aligned(c.actions, 16) && aligned(c.x1, 16)));
+}
+inline uint64_t grad_tiles(const GradCall& c, int N, int S) {
+    const uint64_t lanes = (c.env_count + N - 1) / N;
+    return ((lanes + kBlock - 1) / kBlock) * (uint64_t)((c.K + S - 1) / S);
+}
+inline unsigned grad_blocks(const GradCall& c, int N, int S) {
+    const uint64_t tiles = grad_tiles(c, N, S);
+    return (unsigned)(tiles < (uint64_t)c.slabs ? tiles : (uint64_t)c.slabs);
+}
+
 // The by-value kernel arguments of every learner kernel, against the largest net and the largest call struct (the actor's gradient call with its head).
 static_assert(sizeof(MlpPack<8, 1>) == 2568 && sizeof(MlpPack<8, 4>) == 3348 && sizeof(ValueCall) <= sizeof(GradCall) && sizeof(LogpCall) <= sizeof(GradCall) &&
                   sizeof(MlpPack<8, 4>) + sizeof(PpoGaussian) + sizeof(GradCall) + 16 <= 4096,

@@ -473,9 +473,52 @@ class VecEnv:
     def grad_workspace_bytes(self, hidden):
         """(min_bytes, best_bytes) of the workspace of ppo_grad_mlp_device / value_grad_mlp_device at this hidden width (mgym_grad_workspace_bytes): one slab of
         partial sums, and the most a launch uses"""
+        return self._grad_workspace(hidden)
+
+    def grad_workspace_bytes2(self, hidden1, hidden2):
+        """(min_bytes, best_bytes) of the workspace of ppo_grad_mlp2_device / value_grad_mlp2_device at these widths (mgym_grad_workspace_bytes2): one slab of
+        partial sums, and the most a launch uses"""
+        return self._grad_workspace(hidden1, hidden2)
+
+    def _grad_workspace(self, *widths):
+        """the workspace query of the gradient calls with as many hidden layers as there are widths"""
+        query = self._lib.mgym_grad_workspace_bytes if len(widths) == 1 else self._lib.mgym_grad_workspace_bytes2
         lo, hi = C.c_size_t(), C.c_size_t()
-        _check(self._lib.mgym_grad_workspace_bytes(self.kind, int(hidden), C.byref(lo), C.byref(hi)))
+        _check(query(self.kind, *(int(w) for w in widths), C.byref(lo), C.byref(hi)))
         return int(lo.value), int(hi.value)
+
+    def _mlp2_grad_floats(self, weights, A, h1, h2):
+        """the contiguous float32 words of a two-layer gradient call (None: NULL); the length is checked where the widths are ones the engine takes"""
+        want = _mlp_floats(self.obs_dim, A, h1, h2) if h2 >= 1 else None
+        return None if weights is None else _policy_floats(weights, want, f"hidden1 = {h1}, hidden2 = {h2}")
+
+    def _ppo_grad_device(self, policy, widths, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip, ent_coef, workspace,
+                         workspace_bytes, grad_out, stats_out):
+        """the actor's gradient call of either depth, widths = (hidden,) or (hidden1, hidden2): each depth's entry point, and its checks in its order"""
+        if len(widths) == 1:
+            pol, act = self._mlp_args(policy, widths[0], activation)
+            hd = _named(_HEADS, head, _DENSITY_HEAD_WORDING)
+            call, widths = self._lib.mgym_ppo_grad_mlp, (int(widths[0]),)
+        else:
+            act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
+            hd = _named(_HEADS, head, _DENSITY_HEAD_WORDING)
+            call, widths = self._lib.mgym_ppo_grad_mlp2, (int(widths[0]), int(widths[1]))
+            pol = self._mlp2_grad_floats(policy, self.mlp_dims()[1], *widths)
+        _check(call(self._h, _fptr(pol), *widths, act, hd, float(sigma), int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs), _ptr(actions),
+                    _ptr(logp_old), _ptr(adv), float(clip), float(ent_coef), _ptr(workspace), int(workspace_bytes), _ptr(grad_out), _ptr(stats_out)))
+
+    def _value_grad_device(self, critic, widths, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out):
+        """the critic's gradient call of either depth, as _ppo_grad_device"""
+        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
+        if len(widths) == 1:
+            h = int(widths[0])
+            cr = None if critic is None else _policy_floats(critic, _mlp_floats(self.obs_dim, 1, h), f"hidden = {widths[0]}")
+            call, widths = self._lib.mgym_value_grad_mlp, (h,)
+        else:
+            call, widths = self._lib.mgym_value_grad_mlp2, (int(widths[0]), int(widths[1]))
+            cr = self._mlp2_grad_floats(critic, 1, *widths)
+        _check(call(self._h, _fptr(cr), *widths, act, int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs), _ptr(ret), _ptr(workspace),
+                    int(workspace_bytes), _ptr(grad_out), _ptr(stats_out)))
 
     def ppo_grad_mlp_device(self, policy, hidden, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip, ent_coef,
                             workspace, workspace_bytes, grad_out, stats_out):
@@ -484,113 +527,83 @@ class VecEnv:
         takes them, logp_old [K, n] its output, adv [K, n] gae_device's; workspace: 16-byte aligned, workspace_bytes of it (grad_workspace_bytes); grad_out
         receives H (D + 1) + A (H + 1) + 1 floats (dW1, db1, dW2, db2 in nn.Linear order, d / d log sigma), stats_out 8.  On the env's stream, nothing
         synchronised, nothing allocated."""
-        pol, act = self._mlp_args(policy, hidden, activation)
-        hd = _named(_HEADS, head, _DENSITY_HEAD_WORDING)
-        _check(self._lib.mgym_ppo_grad_mlp(self._h, _fptr(pol), int(hidden), act, hd, float(sigma), int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs),
-                                           _ptr(actions), _ptr(logp_old), _ptr(adv), float(clip), float(ent_coef), _ptr(workspace), int(workspace_bytes),
-                                           _ptr(grad_out), _ptr(stats_out)))
+        self._ppo_grad_device(policy, (hidden,), activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip, ent_coef, workspace,
+                              workspace_bytes, grad_out, stats_out)
 
     def value_grad_mlp_device(self, critic, hidden, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out):
         """mgym_value_grad_mlp on device buffers: the loss 1/2 mean((V - ret)^2) of a one-hidden-layer critic (pack_critic's floats) and its gradient over the same
         range; grad_out receives H (D + 1) + (H + 1) + 1 floats (the last +0), stats_out 8."""
-        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
-        h = int(hidden)
-        cr = None if critic is None else _policy_floats(critic, _mlp_floats(self.obs_dim, 1, h), f"hidden = {hidden}")
-        _check(self._lib.mgym_value_grad_mlp(self._h, _fptr(cr), h, act, int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs), _ptr(ret),
-                                             _ptr(workspace), int(workspace_bytes), _ptr(grad_out), _ptr(stats_out)))
-
-    def _grad_host(self, A, H, call, env_slice, workspace_bytes, H2=0):
-        """the workspace and the outputs of a host-array gradient call -> (grad [P + 1], stats [8])"""
-        first, count = (0, self.n) if env_slice is None else env_slice
-        lo, hi = self.grad_workspace_bytes2(H, H2) if H2 else self.grad_workspace_bytes(H)
-        nbytes = hi if workspace_bytes is None else int(workspace_bytes)
-        ws = DeviceArray(max(nbytes, lo) // 8, np.float64, self.device)
-        P = _mlp_floats(self.obs_dim, A, H, H2)
-        grad, stats = DeviceArray(P + 1, np.float32, self.device), DeviceArray(8, np.float32, self.device)
-        call(first, count, ws, nbytes, grad, stats)
-        self.sync()
-        return grad.numpy().copy(), stats.numpy().copy()
-
-    def ppo_grad_mlp(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None,
-                     workspace_bytes=None):
-        """host-array form of ppo_grad_mlp_device: weights (w1, b1, w2, b2), obs_first [D, n], obs [K, D, n], actions, logp_old and adv [K, n] -> (grad [P + 1]
-        float32, stats [8] float32).  head: None takes the family's; env_slice: (first, count), None the full range; workspace_bytes: None takes best_bytes."""
-        policy, H = self.pack_mlp(*weights)
-        if head is None:
-            head = self._family_head()
-        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
-        of, ob = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n))
-        ac, lp, ad = self._dev(actions, self.action_dtype, (K, n)), self._dev(logp_old, np.float32, (K, n)), self._dev(adv, np.float32, (K, n))
-        return self._grad_host(self.mlp_dims()[1], H, lambda first, count, ws, nbytes, grad, stats: self.ppo_grad_mlp_device(
-            policy, H, activation, head, sigma, K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats), env_slice, workspace_bytes)
-
-    def value_grad_mlp(self, weights, obs_first, obs, ret, activation="relu", env_slice=None, workspace_bytes=None):
-        """host-array form of value_grad_mlp_device: a one-hidden-layer critic (w1, b1, w2 [1, H], b2 [1]) -> (grad [P + 1] float32, stats [8] float32)"""
-        critic, H, H2 = self.pack_critic(weights)
-        if H2:
-            raise PolicyShapeError(L.ERR_BAD_ARG, "value_grad_mlp takes a critic with one hidden layer")
-        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
-        of, ob, rt = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n)), self._dev(ret, np.float32, (K, n))
-        return self._grad_host(1, H, lambda first, count, ws, nbytes, grad, stats: self.value_grad_mlp_device(
-            critic, H, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats), env_slice, workspace_bytes)
-
-    def grad_workspace_bytes2(self, hidden1, hidden2):
-        """(min_bytes, best_bytes) of the workspace of ppo_grad_mlp2_device / value_grad_mlp2_device at these widths (mgym_grad_workspace_bytes2): one slab of
-        partial sums, and the most a launch uses"""
-        lo, hi = C.c_size_t(), C.c_size_t()
-        _check(self._lib.mgym_grad_workspace_bytes2(self.kind, int(hidden1), int(hidden2), C.byref(lo), C.byref(hi)))
-        return int(lo.value), int(hi.value)
-
-    def _mlp2_grad_floats(self, weights, A, h1, h2):
-        """the contiguous float32 words of a two-layer gradient call (None: NULL); the length is checked where the widths are ones the engine takes"""
-        want = _mlp_floats(self.obs_dim, A, h1, h2) if h2 >= 1 else None
-        return None if weights is None else _policy_floats(weights, want, f"hidden1 = {h1}, hidden2 = {h2}")
+        self._value_grad_device(critic, (hidden,), activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out)
 
     def ppo_grad_mlp2_device(self, policy, hidden1, hidden2, activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip,
                              ent_coef, workspace, workspace_bytes, grad_out, stats_out):
         """mgym_ppo_grad_mlp2 on device buffers: ppo_grad_mlp_device for the two-hidden-layer actor of pack_mlp2.  workspace_bytes of grad_workspace_bytes2;
         grad_out receives H1 (D + 1) + H2 (H1 + 1) + A (H2 + 1) + 1 floats (dW1, db1, dW2, db2, dW3, db3 in nn.Linear order, d / d log sigma), stats_out 8.
         On the env's stream, nothing synchronised, nothing allocated."""
-        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
-        hd = _named(_HEADS, head, _DENSITY_HEAD_WORDING)
-        h1, h2 = int(hidden1), int(hidden2)
-        pol = self._mlp2_grad_floats(policy, self.mlp_dims()[1], h1, h2)
-        _check(self._lib.mgym_ppo_grad_mlp2(self._h, _fptr(pol), h1, h2, act, hd, float(sigma), int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs),
-                                            _ptr(actions), _ptr(logp_old), _ptr(adv), float(clip), float(ent_coef), _ptr(workspace), int(workspace_bytes),
-                                            _ptr(grad_out), _ptr(stats_out)))
+        self._ppo_grad_device(policy, (hidden1, hidden2), activation, head, sigma, K, env_first, env_count, obs_first, obs, actions, logp_old, adv, clip, ent_coef,
+                              workspace, workspace_bytes, grad_out, stats_out)
 
     def value_grad_mlp2_device(self, critic, hidden1, hidden2, activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out,
                                stats_out):
         """mgym_value_grad_mlp2 on device buffers: value_grad_mlp_device for a two-hidden-layer critic (pack_critic's floats); grad_out receives
         H1 (D + 1) + H2 (H1 + 1) + (H2 + 1) + 1 floats (the last +0), stats_out 8."""
-        act = _named(_ACTIVATIONS, activation, _ACT_WORDING)
-        h1, h2 = int(hidden1), int(hidden2)
-        cr = self._mlp2_grad_floats(critic, 1, h1, h2)
-        _check(self._lib.mgym_value_grad_mlp2(self._h, _fptr(cr), h1, h2, act, int(K), int(env_first), int(env_count), _ptr(obs_first), _ptr(obs), _ptr(ret),
-                                              _ptr(workspace), int(workspace_bytes), _ptr(grad_out), _ptr(stats_out)))
+        self._value_grad_device(critic, (hidden1, hidden2), activation, K, env_first, env_count, obs_first, obs, ret, workspace, workspace_bytes, grad_out, stats_out)
 
-    def ppo_grad_mlp2(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None,
-                      workspace_bytes=None):
-        """host-array form of ppo_grad_mlp2_device: weights (w1, b1, w2, b2, w3, b3), the other arguments as ppo_grad_mlp -> (grad [P2 + 1] float32,
-        stats [8] float32)"""
-        policy, H1, H2 = self.pack_mlp2(*weights)
+    def _grad_host(self, A, widths, env_slice, workspace_bytes, call):
+        """the workspace and the outputs of a host-array gradient call -> (grad [P + 1], stats [8])"""
+        first, count = (0, self.n) if env_slice is None else env_slice
+        lo, hi = self._grad_workspace(*widths)
+        nbytes = hi if workspace_bytes is None else int(workspace_bytes)
+        ws = DeviceArray(max(nbytes, lo) // 8, np.float64, self.device)
+        grad, stats = DeviceArray(_mlp_floats(self.obs_dim, A, *widths) + 1, np.float32, self.device), DeviceArray(8, np.float32, self.device)
+        call(first, count, ws, nbytes, grad, stats)
+        self.sync()
+        return grad.numpy().copy(), stats.numpy().copy()
+
+    def _ppo_grad_host(self, policy, widths, obs_first, obs, actions, logp_old, adv, activation, head, sigma, clip, ent_coef, env_slice, workspace_bytes):
+        """the host-array form of _ppo_grad_device on packed weights: the inputs staged on the device"""
         if head is None:
             head = self._family_head()
         K, D, n = np.shape(obs)[0], self.obs_dim, self.n
         of, ob = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n))
         ac, lp, ad = self._dev(actions, self.action_dtype, (K, n)), self._dev(logp_old, np.float32, (K, n)), self._dev(adv, np.float32, (K, n))
-        return self._grad_host(self.mlp_dims()[1], H1, lambda first, count, ws, nbytes, grad, stats: self.ppo_grad_mlp2_device(
-            policy, H1, H2, activation, head, sigma, K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats), env_slice, workspace_bytes, H2)
+        return self._grad_host(self.mlp_dims()[1], widths, env_slice, workspace_bytes, lambda first, count, *out: self._ppo_grad_device(
+            policy, widths, activation, head, sigma, K, first, count, of, ob, ac, lp, ad, clip, ent_coef, *out))
+
+    def _value_grad_host(self, critic, widths, obs_first, obs, ret, activation, env_slice, workspace_bytes):
+        """the host-array form of _value_grad_device on packed weights"""
+        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
+        of, ob, rt = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n)), self._dev(ret, np.float32, (K, n))
+        return self._grad_host(1, widths, env_slice, workspace_bytes, lambda first, count, *out: self._value_grad_device(
+            critic, widths, activation, K, first, count, of, ob, rt, *out))
+
+    def ppo_grad_mlp(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None,
+                     workspace_bytes=None):
+        """host-array form of ppo_grad_mlp_device: weights (w1, b1, w2, b2), obs_first [D, n], obs [K, D, n], actions, logp_old and adv [K, n] -> (grad [P + 1]
+        float32, stats [8] float32).  head: None takes the family's; env_slice: (first, count), None the full range; workspace_bytes: None takes best_bytes."""
+        policy, *widths = self.pack_mlp(*weights)
+        return self._ppo_grad_host(policy, widths, obs_first, obs, actions, logp_old, adv, activation, head, sigma, clip, ent_coef, env_slice, workspace_bytes)
+
+    def ppo_grad_mlp2(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None,
+                      workspace_bytes=None):
+        """host-array form of ppo_grad_mlp2_device: weights (w1, b1, w2, b2, w3, b3), the other arguments as ppo_grad_mlp -> (grad [P2 + 1] float32,
+        stats [8] float32)"""
+        policy, *widths = self.pack_mlp2(*weights)
+        return self._ppo_grad_host(policy, widths, obs_first, obs, actions, logp_old, adv, activation, head, sigma, clip, ent_coef, env_slice, workspace_bytes)
+
+    def value_grad_mlp(self, weights, obs_first, obs, ret, activation="relu", env_slice=None, workspace_bytes=None):
+        """host-array form of value_grad_mlp_device: a one-hidden-layer critic (w1, b1, w2 [1, H], b2 [1]) -> (grad [P + 1] float32, stats [8] float32)"""
+        critic, H, H2 = self.pack_critic(weights)
+        if H2:
+            raise PolicyShapeError(L.ERR_BAD_ARG, "value_grad_mlp takes a critic with one hidden layer")
+        return self._value_grad_host(critic, (H,), obs_first, obs, ret, activation, env_slice, workspace_bytes)
 
     def value_grad_mlp2(self, weights, obs_first, obs, ret, activation="relu", env_slice=None, workspace_bytes=None):
         """host-array form of value_grad_mlp2_device: a two-hidden-layer critic (w1, b1, w2, b2, w3 [1, H2], b3 [1]) -> (grad [P2 + 1] float32, stats [8] float32)"""
         critic, H1, H2 = self.pack_critic(weights)
         if not H2:
             raise PolicyShapeError(L.ERR_BAD_ARG, "value_grad_mlp2 takes a critic with two hidden layers")
-        K, D, n = np.shape(obs)[0], self.obs_dim, self.n
-        of, ob, rt = self._dev(obs_first, np.float32, (D, n)), self._dev(obs, np.float32, (K, D, n)), self._dev(ret, np.float32, (K, n))
-        return self._grad_host(1, H1, lambda first, count, ws, nbytes, grad, stats: self.value_grad_mlp2_device(
-            critic, H1, H2, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats), env_slice, workspace_bytes, H2)
+        return self._value_grad_host(critic, (H1, H2), obs_first, obs, ret, activation, env_slice, workspace_bytes)
 
     def episode_returns(self, reward, done, trunc, ep_return=None, ep_length=None):
         """host-array form of episode_returns_device: the carry in (None: zeros) -> (return_out [K, n] float32, length_out [K, n] uint32, both 0 where no

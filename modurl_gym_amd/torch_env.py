@@ -66,7 +66,7 @@ class TorchVecEnv:
             self.final_obs = torch.zeros((int(final_obs_steps), self.obs_dim, self.n), dtype=f32, device=self.device)
             self.env.set_final_obs_out_device(self.final_obs, int(final_obs_steps))
         self._ep_return = self._ep_length = None   # the carry of episode_returns(), created by its first call
-        self._grad_ws = {}   # the workspaces of ppo_grad_mlp / value_grad_mlp, one per (hidden, stream), created by the first call that needs one
+        self._grad_ws = {}   # the workspaces of the gradient calls, one per (hidden widths, stream), created by the first call that needs one
 
     # ---- plumbing -----------------------------------------------------------------------
     def _bind_stream(self):
@@ -283,20 +283,49 @@ class TorchVecEnv:
         self.env.logprob_mlp_device(policy, h1, h2, activation, head, float(sigma), K, of, ob, ac, logp)
         return logp
 
-    def _grad_buffers(self, hidden, P):
-        """the cached workspace of this hidden width on torch's current stream — best_bytes of mgym_grad_workspace_bytes, 16-byte aligned; one per stream, so
-        that calls issued on two streams never share the slabs — and fresh outputs"""
+    def _grad_buffers(self, widths, P):
+        """the cached workspace of these hidden widths, (H,) or (H1, H2), on torch's current stream — best_bytes of mgym_grad_workspace_bytes /
+        mgym_grad_workspace_bytes2, 16-byte aligned; one per stream, so that calls issued on two streams never share the slabs — and fresh outputs"""
         torch = self._torch
-        key = (int(hidden), self._stream)   # (_bind_stream has made the engine's stream torch's current one)
+        key = (widths, self._stream)   # (_bind_stream has made the engine's stream torch's current one)
         if key not in self._grad_ws:
-            self._grad_ws[key] = torch.empty(self.env.grad_workspace_bytes(hidden)[1] // 8, dtype=torch.float64, device=self.device)
+            self._grad_ws[key] = torch.empty(self.env._grad_workspace(*widths)[1] // 8, dtype=torch.float64, device=self.device)
         ws = self._grad_ws[key]
         return ws, ws.numel() * 8, torch.empty(P + 1, dtype=torch.float32, device=self.device), torch.empty(8, dtype=torch.float32, device=self.device)
 
-    def _grad_views(self, grad, D, A, H, log_sigma):
-        o1, o2, o3 = H * D, H * D + H, H * D + H + A * H
-        views = (grad[:o1].view(H, D), grad[o1:o2], grad[o2:o3].view(A, H), grad[o3: o3 + A])
-        return views + ((grad[o3 + A:],) if log_sigma else ())
+    def _grad_views(self, grad, D, A, widths, log_sigma):
+        """(dw, db) of every layer in nn.Linear order as views of grad — and the log-sigma word"""
+        views, at = [], 0
+        for rows, cols in zip((*widths, A), (D, *widths)):
+            views += [grad[at: at + rows * cols].view(rows, cols), grad[at + rows * cols: at + rows * cols + rows]]
+            at += rows * (cols + 1)
+        return tuple(views) + ((grad[at:],) if log_sigma else ())
+
+    def _ppo_grad(self, policy, widths, obs_first, obs, actions, logp_old, adv, activation, head, sigma, clip, ent_coef, env_slice):
+        """ppo_grad_mlp / ppo_grad_mlp2 on packed weights"""
+        torch = self._torch
+        if head is None:
+            head = self.env._family_head()
+        K = int(obs.shape[0])
+        D, A = self.env.mlp_dims()
+        of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))
+        ac = self._kn(actions, torch.float32 if self.action_is_float else torch.int32, "actions", (K,))
+        lp, ad = self._kn(logp_old, torch.float32, "logp_old", (K,)), self._kn(adv, torch.float32, "adv", (K,))
+        first, count = (0, self.n) if env_slice is None else env_slice
+        ws, nbytes, grad, stats = self._grad_buffers(widths, E._mlp_floats(D, A, *widths))
+        self.env._ppo_grad_device(policy, widths, activation, head, float(sigma), K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats)
+        return self._grad_views(grad, D, A, widths, head in ("gauss", E.L.HEAD_GAUSS)), stats
+
+    def _value_grad(self, packed, widths, obs_first, obs, ret, activation, env_slice):
+        """value_grad_mlp / value_grad_mlp2 on packed weights"""
+        torch = self._torch
+        K, D = int(obs.shape[0]), self.obs_dim
+        of, ob = self._kn(obs_first, torch.float32, "obs_first", (D,)), self._kn(obs, torch.float32, "obs", (K, D))
+        rt = self._kn(ret, torch.float32, "ret", (K,))
+        first, count = (0, self.n) if env_slice is None else env_slice
+        ws, nbytes, grad, stats = self._grad_buffers(widths, E._mlp_floats(D, 1, *widths))
+        self.env._value_grad_device(packed, widths, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats)
+        return self._grad_views(grad, D, 1, widths, False), stats
 
     def ppo_grad_mlp(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None):
         """PPO's clipped loss and the actor's gradient in one call (mgym_ppo_grad_mlp, include/mgym.h) in place of a torch forward pass, the surrogate and
@@ -309,18 +338,8 @@ class TorchVecEnv:
         torch = self._torch
         self._bind_stream()
         host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
-        policy, H = self.env.pack_mlp(*host)
-        if head is None:
-            head = self.env._family_head()
-        K = int(obs.shape[0])
-        D, A = self.env.mlp_dims()
-        of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))
-        ac = self._kn(actions, torch.float32 if self.action_is_float else torch.int32, "actions", (K,))
-        lp, ad = self._kn(logp_old, torch.float32, "logp_old", (K,)), self._kn(adv, torch.float32, "adv", (K,))
-        first, count = (0, self.n) if env_slice is None else env_slice
-        ws, nbytes, grad, stats = self._grad_buffers(H, H * (D + 1) + A * (H + 1))
-        self.env.ppo_grad_mlp_device(policy, H, activation, head, float(sigma), K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats)
-        return self._grad_views(grad, D, A, H, head in ("gauss", E.L.HEAD_GAUSS)), stats
+        policy, *widths = self.env.pack_mlp(*host)
+        return self._ppo_grad(policy, tuple(widths), obs_first, obs, actions, logp_old, adv, activation, head, sigma, clip, ent_coef, env_slice)
 
     def value_grad_mlp(self, critic, obs_first, obs, ret, activation="relu", env_slice=None):
         """The loss 1/2 mean((V - ret)^2) of a one-hidden-layer critic (w1, b1, w2 [1, H], b2 [1]) and its gradient in one call (mgym_value_grad_mlp): ret
@@ -332,31 +351,7 @@ class TorchVecEnv:
         packed, H, H2 = self.env.pack_critic(host)
         if H2:
             raise ValueError("value_grad_mlp takes a critic with one hidden layer")
-        K, D = int(obs.shape[0]), self.obs_dim
-        of, ob = self._kn(obs_first, torch.float32, "obs_first", (D,)), self._kn(obs, torch.float32, "obs", (K, D))
-        rt = self._kn(ret, torch.float32, "ret", (K,))
-        first, count = (0, self.n) if env_slice is None else env_slice
-        ws, nbytes, grad, stats = self._grad_buffers(H, H * (D + 1) + H + 1)
-        self.env.value_grad_mlp_device(packed, H, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats)
-        return self._grad_views(grad, D, 1, H, False), stats
-
-    def _grad2_buffers(self, H1, H2, P):
-        """_grad_buffers for the two-layer calls: best_bytes of mgym_grad_workspace_bytes2, cached per ((H1, H2), stream)"""
-        torch = self._torch
-        key = ((int(H1), int(H2)), self._stream)
-        if key not in self._grad_ws:
-            self._grad_ws[key] = torch.empty(self.env.grad_workspace_bytes2(H1, H2)[1] // 8, dtype=torch.float64, device=self.device)
-        ws = self._grad_ws[key]
-        return ws, ws.numel() * 8, torch.empty(P + 1, dtype=torch.float32, device=self.device), torch.empty(8, dtype=torch.float32, device=self.device)
-
-    def _grad2_views(self, grad, D, A, H1, H2, log_sigma):
-        o1 = H1 * D
-        o2 = o1 + H1
-        o3 = o2 + H2 * H1
-        o4 = o3 + H2
-        o5 = o4 + A * H2
-        views = (grad[:o1].view(H1, D), grad[o1:o2], grad[o2:o3].view(H2, H1), grad[o3:o4], grad[o4:o5].view(A, H2), grad[o5: o5 + A])
-        return views + ((grad[o5 + A:],) if log_sigma else ())
+        return self._value_grad(packed, (H,), obs_first, obs, ret, activation, env_slice)
 
     def ppo_grad_mlp2(self, weights, obs_first, obs, actions, logp_old, adv, activation="relu", head=None, sigma=0.0, clip=0.2, ent_coef=0.0, env_slice=None):
         """ppo_grad_mlp for the two-hidden-layer actor (mgym_ppo_grad_mlp2): weights (w1, b1, w2, b2, w3, b3); activation "relu" or "tanh_fast".  Returns
@@ -365,18 +360,8 @@ class TorchVecEnv:
         torch = self._torch
         self._bind_stream()
         host = [x.detach().to("cpu", torch.float32).numpy() if isinstance(x, torch.Tensor) else x for x in weights]
-        policy, H1, H2 = self.env.pack_mlp2(*host)
-        if head is None:
-            head = self.env._family_head()
-        K = int(obs.shape[0])
-        D, A = self.env.mlp_dims()
-        of, ob = self._kn(obs_first, torch.float32, "obs_first", (self.obs_dim,)), self._kn(obs, torch.float32, "obs", (K, self.obs_dim))
-        ac = self._kn(actions, torch.float32 if self.action_is_float else torch.int32, "actions", (K,))
-        lp, ad = self._kn(logp_old, torch.float32, "logp_old", (K,)), self._kn(adv, torch.float32, "adv", (K,))
-        first, count = (0, self.n) if env_slice is None else env_slice
-        ws, nbytes, grad, stats = self._grad2_buffers(H1, H2, H1 * (D + 1) + H2 * (H1 + 1) + A * (H2 + 1))
-        self.env.ppo_grad_mlp2_device(policy, H1, H2, activation, head, float(sigma), K, first, count, of, ob, ac, lp, ad, clip, ent_coef, ws, nbytes, grad, stats)
-        return self._grad2_views(grad, D, A, H1, H2, head in ("gauss", E.L.HEAD_GAUSS)), stats
+        policy, *widths = self.env.pack_mlp2(*host)
+        return self._ppo_grad(policy, tuple(widths), obs_first, obs, actions, logp_old, adv, activation, head, sigma, clip, ent_coef, env_slice)
 
     def value_grad_mlp2(self, critic, obs_first, obs, ret, activation="relu", env_slice=None):
         """value_grad_mlp for a two-hidden-layer critic (w1, b1, w2, b2, w3 [1, H2], b3 [1]) (mgym_value_grad_mlp2).  Returns (grads, stats): grads = (dw1, db1,
@@ -387,13 +372,7 @@ class TorchVecEnv:
         packed, H1, H2 = self.env.pack_critic(host)
         if not H2:
             raise ValueError("value_grad_mlp2 takes a critic with two hidden layers")
-        K, D = int(obs.shape[0]), self.obs_dim
-        of, ob = self._kn(obs_first, torch.float32, "obs_first", (D,)), self._kn(obs, torch.float32, "obs", (K, D))
-        rt = self._kn(ret, torch.float32, "ret", (K,))
-        first, count = (0, self.n) if env_slice is None else env_slice
-        ws, nbytes, grad, stats = self._grad2_buffers(H1, H2, H1 * (D + 1) + H2 * (H1 + 1) + H2 + 1)
-        self.env.value_grad_mlp2_device(packed, H1, H2, activation, K, first, count, of, ob, rt, ws, nbytes, grad, stats)
-        return self._grad2_views(grad, D, 1, H1, H2, False), stats
+        return self._value_grad(packed, (H1, H2), obs_first, obs, ret, activation, env_slice)
 
     def episode_returns(self, reward, done, truncated):
         """The return and length of every episode that ended inside the rollout (mgym_episode_returns): (return_out float32 [K, n], length_out int32 [K, n]),
